@@ -13,6 +13,11 @@ Contract: `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched by
 data-path collective); `--sharded`: ONE stream into ONE map spatially sharded across the ranks, the exchanges of a frame
 enqueued by libifx.so itself on the communicator it is handed.  Barrier + synchronize on both sides
 of the timed region, max over ranks, rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the --steps frames and prints the line (frames/s and ms_per_step).  `--full` adds everything
+else this file measures: the per-stage split, the roofline of the kernels, the extra legs (host entry points, closeLoops = true,
+fast cadence, the sharded map, configuration 5) and the CPU-oracle baseline with its parity check.  `--dump-outputs DIR` writes
+what the timed path handed its caller after its last step as DIR/<name>.npy (dump_outputs below).
 """
 from __future__ import annotations
 
@@ -89,6 +94,70 @@ STAGE_OF = {"track": ("icp_residual", "rgb_step_solve", "gn_level", "model_l0", 
             "instance": ("count_colour", "count_colour_px", "project_bbox")}
 
 
+class _StreamNoise:
+    """Stands in for the stream's RandomState inside synth.render: hands out the frame's depth noise, drawn in advance in frame order."""
+
+    def __init__(self, z):
+        self.z = z
+
+    def standard_normal(self, shape):
+        assert tuple(shape) == self.z.shape
+        return self.z
+
+
+def _render_frame(job):
+    from instancefusion_amd import synth
+
+    scene, pose, w, h, K, z = job
+    return synth.render(scene, pose, w, h, K["fx"], K["fy"], K["cx"], K["cy"], _StreamNoise(z))
+
+
+def make_stream(n_frames, w, h, seed, K, workers):
+    """synth.make_stream(n_frames, w, h, noise=True, loop_len=n_frames, seed=seed, **K), bit for bit, with the frames ray-cast by `workers` fresh
+    processes: the noise of every frame is drawn here from the one seeded sequence in frame order, as synth.make_stream draws it (tests/test_bench_model_cpu.py)."""
+    from instancefusion_amd import synth
+
+    if workers <= 1:
+        return synth.make_stream(n_frames, w, h, noise=True, loop_len=n_frames, seed=seed, **K)
+    import concurrent.futures
+    import multiprocessing
+
+    scene = synth.Scene(seed)
+    poses = synth.trajectory(n_frames)
+    rng = np.random.RandomState(seed + 1)
+    jobs = [(scene, poses[i], w, h, K, rng.standard_normal((h, w))) for i in range(n_frames)]
+    with concurrent.futures.ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        frames = list(ex.map(_render_frame, jobs))
+    inv0 = np.linalg.inv(poses[0])
+    return dict(rgb=np.stack([f[0] for f in frames]), depth=np.stack([f[1] for f in frames]), obj=np.stack([f[2] for f in frames]),
+                poses=np.stack([inv0 @ p for p in poses]), poses_world=poses, scene=scene)
+
+
+DUMP_SEED = 20240611
+DUMP_SURFELS = 1 << 18      # surfels of the fixed sample of the map that --dump-outputs writes
+DUMP_VOTE_SURFELS = 1 << 16  # ... and the first of them whose 48 vote words are written too
+
+
+def dump_outputs(out_dir, ef, inst, pose):
+    """What the timed path handed its caller after its last step, as out_dir/<name>.npy (float32, integer-valued arrays float64; ~30 MB at 640x480):
+    the camera pose of the last frame, the surfel-id image it rendered, the live surfel count and the instance table, and a fixed, seeded sample of the
+    map in map order (position + confidence, normal + radius, colour, times, instance label; the votes of the first DUMP_VOTE_SURFELS of the sample)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = ef.count
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(n, min(n, DUMP_SURFELS), replace=False))
+    out = dict(pose=np.asarray(pose, np.float32).reshape(4, 4), ids_after=ef.image("ids_after").astype(np.float64),
+               surfel_count=np.array([n], np.float64), instance_table=inst.getInstanceTable().astype(np.float64))
+    m = ef.download(("pc", "nr", "col", "tm"))
+    for k_ in ("pc", "nr", "col", "tm"):
+        out["map_" + k_] = m[k_][idx]
+    del m
+    out["map_label"] = inst.labels()[idx].astype(np.float64)
+    out["map_votes"] = ef.download(("votes",))["votes"][idx[:DUMP_VOTE_SURFELS]]
+    for k_, a_ in out.items():
+        np.save(os.path.join(out_dir, k_ + ".npy"), a_)
+    return sum(a_.nbytes for a_ in out.values())
+
+
 def main():
     global GN_PERSIST
     ap = argparse.ArgumentParser()
@@ -125,6 +194,9 @@ def main():
     ap.add_argument("--config5-surfels", type=int, default=0, help="N > 1: surfels of the ONE shared map of the configuration-5 leg (0: --surfels x N, at most 50 M -- BASELINE configuration 5 at N = 8 within 20 %%)")
     ap.add_argument("--sharded-timeout", type=int, default=300, help="N > 1: seconds after which the line is printed without the sharded-map leg should that leg stall (0: wait for ever)")
     ap.add_argument("--extras-frames", type=int, default=60, help="frames of each extra leg at N = 1 (host entry point, closeLoops = true); 0 skips them")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline figure: the per-stage split, the kernel roofline, the extra legs, "
+                    "the sharded-map leg and the CPU baseline (the options above that shape them apply with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -166,7 +238,10 @@ def main():
     t_gen = time.time()
     one_map = args.sharded or args.sharded_projection
     srank = 0 if one_map else rank          # sharded: every rank is fed the same stream and map
-    st = synth.make_stream(L, W, H, noise=True, loop_len=L, seed=synth.SEED + srank, **K)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as ol
+
+    st = make_stream(L, W, H, synth.SEED + srank, K, workers=min(16, L, ol.usable_cores() // world))
     masks = [synth.canned_masks(st["obj"][i], st["scene"]) for i in range(L)]
     tick0 = 1000
     m = synth.make_map(args.surfels, st["scene"], st["poses_world"][0], tick0, seed=synth.SEED + 7 + srank, order=args.map_order)
@@ -204,7 +279,7 @@ def main():
         ef.upload(m)
         ef.set_pose(st["poses"][0], tick0)
         ef.combined_predict(st["poses"][0], tick0, tick0)
-    want_sharded_leg = (not one_map) and (world > 1 or args.extras_frames > 0) and not args.close_loops and not args.no_sharded_leg
+    want_sharded_leg = args.full and (not one_map) and (world > 1 or args.extras_frames > 0) and not args.close_loops and not args.no_sharded_leg
     if not want_sharded_leg:
         del m
 
@@ -336,18 +411,22 @@ def main():
     sp_ahead = ef.superpixel_ahead_stats(reset=True) if osh is None else None   # superpixels run ahead of the calls on the side stream (their device time is not in inst_ms)
     traj = ef.trajectory()                                  # poses up to the end of the timed region
     traj_all = traj
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ef, inst, traj[-1])
     dt = ifd.max_over_ranks(dt, dist, device=f"cuda:{dev}")
-    # ms/frame split of the other stages: measured on the frames that follow, with the per-stage event records switched on
-    # (eight marker packets per frame: they would cost ~4 % of the frame rate inside the timed region)
-    n_split = 40
-    ef.set_option("stage_timing", 1)
-    for _ in range(n_split):
-        step(k); k += 1
-    ef.sync()
-    stage = ef.stage_ms(reset=True)
-    ef.set_option("stage_timing", 0)
-    stage = {k_: v_ / n_split * args.steps for k_, v_ in stage.items()}     # scaled so that the common division below applies
-    stage["instance"] = inst_ms
+    stage = None
+    if args.full:
+        # ms/frame split of the other stages: measured on the frames that follow, with the per-stage event records switched on
+        # (eight marker packets per frame: they would cost ~4 % of the frame rate inside the timed region)
+        n_split = 40
+        ef.set_option("stage_timing", 1)
+        for _ in range(n_split):
+            step(k); k += 1
+        ef.sync()
+        stage = ef.stage_ms(reset=True)
+        ef.set_option("stage_timing", 0)
+        stage = {k_: v_ / n_split * args.steps for k_, v_ in stage.items()}     # scaled so that the common division below applies
+        stage["instance"] = inst_ms
     n_live, n_slots = ef.count, ef.slots
     # trajectory error vs the synthetic ground truth over the timed frames (diagnostic)
     gt = np.stack([st["poses"][(k_timed + j) % L] for j in range(args.steps)])
@@ -356,7 +435,7 @@ def main():
 
     # ---- roofline of the dominant kernel: per-launch HIP-event timing on the handle's stream
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ef.set_option("kernel_timing", 1)
         ef.kernel_ms("__reset__")
         seg["calls"] = 0
@@ -476,7 +555,7 @@ def main():
 
     # ---- extra legs (N = 1 only, bounded): the same workload through the reference-shaped host entry point, and with closeLoops = true
     extras = {}
-    if rank == 0 and world == 1 and sh is None and args.extras_frames > 0 and not args.close_loops:
+    if args.full and rank == 0 and world == 1 and sh is None and args.extras_frames > 0 and not args.close_loops:
         ne = args.extras_frames
         step(k, hint=False); k += 1                           # drains the one-frame look-ahead: the next leg hands over host buffers
         ef.sync()
@@ -554,7 +633,7 @@ def main():
     # ---- the FAST cadence (IF/Core/InstanceFusion.cpp:194-233): on a young map -- less than 80 % of the sampled id image covered by stable surfels, hardly any votes --
     # whetherDoSegmentation fires every 3rd frame instead of every 46th.  The 5M-surfel map of `value` is old by construction, so this leg starts a map from nothing
     # and runs the same stream's first frames: frames/s and the instance stage per frame in that regime.
-    if rank == 0 and world == 1 and sh is None and args.extras_frames > 0 and not args.close_loops and not args.no_instance:
+    if args.full and rank == 0 and world == 1 and sh is None and args.extras_frames > 0 and not args.close_loops and not args.no_instance:
         ef.sync()
         ef3 = ifx.ElasticFusion(w=W, h=H, max_surfels=3_000_000, device=dev, **K)
         inst3 = ifx.InstanceFusion(ef3)
@@ -634,7 +713,7 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{args.surfels}-surfel map, {W}x{H} synthetic RGBD stream, 3-level ICP+RGB + surfel fuse + canned-mask instance votes{'' if args.no_superpixels else ' with superpixel refinement'}{' + local loop-closure detection' if args.close_loops else ''}",
                        "surfels_live": n_live, "surfel_slots": n_slots, "map_order": args.map_order, "parallelism": (f"spatially sharded map x{world}" if args.sharded else (f"sharded projection x{world}" if args.sharded_projection else f"replicas x{world}")), "loop_frames": L},
-            "ms_per_frame_gpu": {k_: round(v / args.steps, 4) for k_, v in stage.items()},
+            **({"ms_per_frame_gpu": {k_: round(v / args.steps, 4) for k_, v in stage.items()}} if stage else {}),
             "instance": {"calls_in_window": calls_in_window, "ms_per_call": round(inst_ms / calls_in_window, 4) if calls_in_window else None,
                          "cadence_frames": 3 if seg["fast"] else 46, "ms_per_frame_at_cadence": round(inst_ms / calls_in_window / (3 if seg["fast"] else 46), 4) if calls_in_window else None,
                          "window_policy": "whetherDoSegmentation every frame; the cadence's phase is placed so that a window shorter than the cadence holds one call",
@@ -907,10 +986,7 @@ def main():
 
     # ---- CPU baseline: the oracle (CPU restatement) on a bounded sample of the same workload, one core and all cores
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N = 1 only (the other ranks of a multi-GPU run would wait for it)
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import oracle_lib as ol
-
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N = 1 only (the other ranks of a multi-GPU run would wait for it)
         n_cpu = min(args.surfels, 5_000_000)
         ncores = ol.usable_cores()                           # affinity capped by the cgroup quota (the GPU box shows 256 CPUs and grants 16)
         cpu_map = synth.make_map(n_cpu, st["scene"], st["poses_world"][0], tick0, seed=synth.SEED + 7)

@@ -1,7 +1,9 @@
-"""bench.py's byte model (roofline.achieved = algorithmic bytes / measured time): the per-level bookkeeping of the tracker's launches, on the CPU."""
+"""bench.py on the CPU: its byte model (roofline.achieved = algorithmic bytes / measured time), the per-level bookkeeping of the tracker's launches, and its stream generator."""
 import importlib
 import os
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -41,3 +43,16 @@ def test_list_kernels_have_byte_entries():
         assert bench.algorithmic_bytes(k, 5_000_000, P, vl=vl) > 0, k
     assert bench.algorithmic_bytes("raster_view", 5_000_000, P, vl=vl) == (vl[0] + vl[1]) * 44.0
     assert bench.algorithmic_bytes("no_such_kernel", 5_000_000, P, vl=vl) == 0.0
+
+
+def test_parallel_stream_equals_synth_stream():
+    """bench.py ray-casts its stream in worker processes; the frames, poses and depth noise must be synth.make_stream's, bit for bit."""
+    bench = importlib.import_module("bench")
+    from instancefusion_amd import synth
+
+    W, H, n = 96, 72, 5
+    K = dict(fx=528.0 * W / 640, fy=528.0 * W / 640, cx=W / 2.0, cy=H / 2.0)
+    got = bench.make_stream(n, W, H, synth.SEED + 3, K, workers=3)
+    want = synth.make_stream(n, W, H, noise=True, loop_len=n, seed=synth.SEED + 3, **K)
+    for k in ("rgb", "depth", "obj", "poses", "poses_world"):
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), k

@@ -16,9 +16,9 @@ shift $((OPTIND - 1))
 sets=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do sets+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 case $window in
-  driver) wargs="--steps 20 --warmup 5 --no-cpu-baseline --extras-frames 0";;
-  long)   wargs="--steps 200 --warmup 30 --no-cpu-baseline --extras-frames 0";;
-  full)   wargs="--no-cpu-baseline";;
+  driver) wargs="--full --steps 20 --warmup 5 --no-cpu-baseline --extras-frames 0";;
+  long)   wargs="--full --steps 200 --warmup 30 --no-cpu-baseline --extras-frames 0";;
+  full)   wargs="--full --no-cpu-baseline";;
   *) echo "unknown window $window"; exit 2;;
 esac
 if [ -n "$build" ]; then

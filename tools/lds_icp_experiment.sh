@@ -1,6 +1,6 @@
 python -m pytest tests -m gpu -x -q -k "lds_staged" 2>&1 | grep -E "passed|failed|assert" | tail -3
 for o in "" "--opt icp_lds=1"; do
-  python bench.py --gpus 1 --steps 150 --warmup 30 --no-cpu-baseline --extras-frames 0 $o 2>/dev/null | python -c "
+  python bench.py --full --gpus 1 --steps 150 --warmup 30 --no-cpu-baseline --extras-frames 0 $o 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernels']
 print('$o', d['value'], d['ms_per_frame_gpu']['track'], 'icp_residual (all levels, HIP events)', k['icp_residual']['avg_ms'])"
