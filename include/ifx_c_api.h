@@ -373,6 +373,12 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           iteration's first launch; "gn_prologue_blocks" n -- the prologue form only for launches of at most n blocks (default 2048)
  *   "fold_result" 0       -- the frame result by a launch of its own instead of the last block of the prediction's resolve
  *   "lazy_ids" 0          -- render the whole id image every frame (default: the lattice whetherDoSegmentation samples; the rest on demand)
+ *   "id_rule" 0|1         -- the id renders of an unsharded map (the frame's ids_after, dense or lattice, and its on-demand completion; the BEFORE / INSTANCECOMPARE
+ *                           renders of "reference_passes"; both modes of ifx_render_ids): 0 (default) a ray through each pixel centre against the disc, f32
+ *                           depth keys; 1 the reference's rule -- surfel_ids.geom's screen-space quad, texcoord interpolated affinely, dot > 1 discarded,
+ *                           24-bit depth with GL_LESS (ties: the lower slot) -- the reference's id images up to GL's sub-pixel latitude (DESIGN.md section 9-3
+ *                           has its cost).  Refused (IFX_E_STATE) on a sharded handle and while a frame is in flight or announced ahead; a change re-renders
+ *                           the current id image at once.  Not the INACTIVE splat of the loop-closure detection, which is a splat render.
  *   "fold_finish" 0, "seg_device" 0, "seg_aside" 0, "ff_union" 0, "ff_rounds" n -- the earlier forms of the end-of-frame sums and of the segmentation call's
  *                           schedule (host-driven / on the main stream / relaxation-only flood fill / length of the fixed relaxation schedule); identical results
  *   "clean_raster" 0, "hot_records" 0, "vlist_one" 1 -- round 5's map-pass forms off / on: the clean pass and the prediction's raster as ONE walk of the view list; the

@@ -219,10 +219,16 @@ _TRK_SPECS = {
 CORRES_DTYPE = np.dtype([("zx", np.int16), ("zy", np.int16), ("diff", np.float32)])
 
 
-class ElasticFusion:
-    """Mirror of ``ElasticFusion`` / ``ElasticFusionInterface`` for the hot path."""
+# option "id_rule" (include/ifx_c_api.h): which rule draws the surfel-id images
+ID_RULE_RAY_DISC = 0     # default: a ray through each pixel centre against the disc, f32 depth keys
+ID_RULE_REFERENCE = 1    # the reference's surfel_ids.geom / .frag: screen-space quads, 24-bit depth
 
-    def __init__(self, **cfg):
+
+class ElasticFusion:
+    """Mirror of ``ElasticFusion`` / ``ElasticFusionInterface`` for the hot path.  ``id_rule``: ID_RULE_REFERENCE draws the id images with the reference's
+    screen-space quad rule (option "id_rule"); None leaves the library's default."""
+
+    def __init__(self, id_rule=None, **cfg):
         self.cfgd = default_config(**cfg)
         self.cfg = IfxConfig(**self.cfgd)
         self.L = lib()
@@ -232,6 +238,8 @@ class ElasticFusion:
         if r != 0:
             raise IfxError(f"ifx_create failed ({r}): {self.L.ifx_global_error().decode()}")
         self.handle = hp
+        if id_rule is not None:
+            self.set_option("id_rule", id_rule)
 
     # -- life cycle
     def close(self):

@@ -357,6 +357,18 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
         if (value && ifx_own_lattice(h) + 1 > 16 * 1024) { h->err = "own_lazy_ids: the image's id lattice is larger than the pack kernel's one workgroup holds (16 383 entries)"; return IFX_E_INVALID; }
         h->opt_own_lazy_ids = value;   // (takes effect with the next frame; a sparse image that is still around is completed on demand as before)
     }
+    else if (s == "id_rule") {   // the id renders of an unsharded map: 0 ray-disc test, f32 keys (default); 1 the reference's screen-space quads, 24-bit depth
+        if (value != 0 && value != 1) { h->err = "id_rule must be 0 (ray-disc) or 1 (the reference's screen-space quads)"; return IFX_E_INVALID; }
+        if (h->own || h->shard_n > 1) { h->err = "id_rule: the id renders of a sharded map keep the ray-disc rule"; return IFX_E_STATE; }
+        if (h->hint_rgb || h->slot[h->tick & 1].for_tick == h->tick || h->ids_pending || h->clean_raster_pending) { h->err = "id_rule cannot change while a frame is in flight or announced ahead"; return IFX_E_STATE; }
+        if (value != h->opt_id_rule) {   // an id image drawn under the other rule is stale: re-rendered whole at once (ifx_should_segment's fallback reads ids_after as it is)
+            h->opt_id_rule = value;
+            h->ids_full_valid = 0; h->ids_sparse_frame = 1; h->ids_view_ok = 0;
+            h->seg_counts_valid = 0;
+            const int r = ifx_ids_ensure(h);
+            if (r) return r;
+        }
+    }
     else if (s == "vlist_one") h->opt_vlist_one = value;
     else if (s == "overdue_rule") h->opt_overdue_rule = value;
     else if (s == "cam_swap") h->opt_cam_swap = value;

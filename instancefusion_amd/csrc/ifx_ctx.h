@@ -354,6 +354,7 @@ struct ifx {
     int ids_view_ok = 0;                // the cached view list still describes store and pose of the frame that drew the sparse id image (ifx_ids_ensure may walk it)
     int view_scan_tick = -1;            // frame whose view-list scan is already on the queue (the loop-closure renders come before the map passes)
     int opt_lc_view = 1;                // loop-closure detection: its two renders from the view lists (one k_raster_view in dual mode) instead of a scan of the store + k_raster_list
+    int opt_id_rule = 0;                // id renders of the unsharded map: 0 the ray-disc test with f32 depth keys, 1 the reference's screen-space quads with 24-bit depth (ifx_map.hip k_raster_quad)
     int opt_lazy_ids = 1;               // the frame renders the id image on the lattice whetherDoSegmentation samples; the whole image on demand (ifx_ids_ensure)
     int ids_full_valid = 1, ids_sparse_frame = 0;
     int ids_full_hint = 0;              // the cadence says the NEXT frame ends with a segmentation call (ifx_should_segment): that frame draws the whole id image itself

@@ -538,6 +538,121 @@ __global__ __launch_bounds__(MAP_THREADS) void k_raster(const DevState* __restri
     }
 }
 
+// ------------------------------------------------------------------ option id_rule = 1: the reference's own id rule (a14)
+// surfel_ids.geom emits each surfel as a triangle strip of four separately projected corners with w = 1, so texcoord is interpolated affinely in SCREEN space;
+// surfel_ids.frag discards where dot(texcoord, texcoord) > 1; the image has a GL_DEPTH_COMPONENT24 buffer and GL_LESS.  Restated here as GL rasterises it:
+// corners snapped to 1/256 px, exact fixed-point edge functions with a top-left rule (y up: an edge owns its zero line when it runs downwards, or
+// horizontally to the left -- the strip's shared diagonal draws once), f32 barycentrics, GL's depth clip, key (depth24 << 32) | id: ties go to the lower
+// slot, the surfel drawn first.  Every f32 operation is the one tests/quad_ids_numpy.py performs (-ffp-contract=off): the GPU tests ask for equal images.
+#define QUAD_SUB 256
+#define QUAD_GUARD 65536.0f   // a quad with a corner farther out (window coordinates) is not drawn: a corner behind the camera
+struct Quad { long long x[4], y[4]; float z[4]; int x0, x1, y0, y1; };
+
+// project_point of surfel_ids.geom (through NDC, as GL's viewport transform takes it back) and the 1/256 px snap; false: not finite or outside the guard band
+__device__ __forceinline__ bool quad_corner(const float* T, float px, float py, float pz, const Cam& c, long long& X, long long& Y, float& zn)
+{
+    const v3 q = xf_point(T, v3m(px, py, pz));
+    const float hw = (float)c.w * 0.5f, hh = (float)c.h * 0.5f;
+    const float xl = (((c.fx * q.x) / q.z + c.cx) - hw) / hw, yl = (((c.fy * q.y) / q.z + c.cy) - hh) / hh;
+    const float xw = xl * hw + hw, yw = yl * hh + hh;
+    zn = q.z / c.maxDepth;
+    if (!(fabsf(xw) <= QUAD_GUARD) || !(fabsf(yw) <= QUAD_GUARD) || !(fabsf(zn) < INFINITY)) return false;
+    X = (long long)rintf(xw * (float)QUAD_SUB);
+    Y = (long long)rintf(yw * (float)QUAD_SUB);
+    return true;
+}
+
+// the per-surfel part: the corners of surfel_ids.geom:49-82 (world frame, raw normal) and the pixel box of the snapped quad; false = nothing to draw.
+// The culls of surfel_ids.vert (confidence) and of the votes (instance_surfel_ids.vert) are the caller's.
+__device__ __forceinline__ bool quad_setup(const float* T, float4 p4, float4 n4, const Cam& c, Quad& Q)
+{
+    if (!(xf_point(T, v3m(p4.x, p4.y, p4.z)).z / c.maxDepth > 0.01f)) return false;
+    float ax = n4.y - n4.z, ay = -n4.x, az = n4.x;
+    const float rn = 1.0f / sqrtf((ax * ax + ay * ay) + az * az);
+    ax = ((ax * rn) * n4.w) * 1.41421356f; ay = ((ay * rn) * n4.w) * 1.41421356f; az = ((az * rn) * n4.w) * 1.41421356f;
+    const float bx = n4.y * az - n4.z * ay, by = n4.z * ax - n4.x * az, bz = n4.x * ay - n4.y * ax;
+    bool ok = quad_corner(T, p4.x + ax, p4.y + ay, p4.z + az, c, Q.x[0], Q.y[0], Q.z[0]);
+    ok = quad_corner(T, p4.x + bx, p4.y + by, p4.z + bz, c, Q.x[1], Q.y[1], Q.z[1]) && ok;
+    ok = quad_corner(T, p4.x - bx, p4.y - by, p4.z - bz, c, Q.x[2], Q.y[2], Q.z[2]) && ok;
+    ok = quad_corner(T, p4.x - ax, p4.y - ay, p4.z - az, c, Q.x[3], Q.y[3], Q.z[3]) && ok;
+    if (!ok) return false;
+    long long mnx = Q.x[0], mxx = Q.x[0], mny = Q.y[0], mxy = Q.y[0];
+#pragma unroll
+    for (int k = 1; k < 4; k++) { mnx = min(mnx, Q.x[k]); mxx = max(mxx, Q.x[k]); mny = min(mny, Q.y[k]); mxy = max(mxy, Q.y[k]); }
+    // pixels whose centre (p * 256 + 128) lies in the box (>> 8: floor division of a signed value)
+    Q.x0 = (int)max(-((-(mnx - QUAD_SUB / 2)) >> 8), 0LL); Q.x1 = (int)min((mxx - QUAD_SUB / 2) >> 8, (long long)(c.w - 1));
+    Q.y0 = (int)max(-((-(mny - QUAD_SUB / 2)) >> 8), 0LL); Q.y1 = (int)min((mxy - QUAD_SUB / 2) >> 8, (long long)(c.h - 1));
+    return Q.x0 <= Q.x1 && Q.y0 <= Q.y1;
+}
+
+__device__ __forceinline__ long long quad_edge(long long ax, long long ay, long long bx, long long by, long long px, long long py) { return (bx - ax) * (py - ay) - (by - ay) * (px - ax); }
+__device__ __forceinline__ bool quad_in(long long e, long long ax, long long ay, long long bx, long long by) { return e > 0 || (e == 0 && (by - ay < 0 || (by == ay && bx - ax < 0))); }
+
+// one triangle of the strip at the pixel centre (sx, sy): depth24 << 32, or IFX_KEY_EMPTY
+__device__ __forceinline__ unsigned long long quad_tri(const Quad& Q, int ia, int ib, int ic, float ua, float va, float ub, float vb, float uc, float vc, long long sx, long long sy)
+{
+    const long long ax = Q.x[ia], ay = Q.y[ia];
+    long long bx = Q.x[ib], by = Q.y[ib], cx = Q.x[ic], cy = Q.y[ic];
+    float zb = Q.z[ib], zc = Q.z[ic];
+    long long A = quad_edge(ax, ay, bx, by, cx, cy);
+    if (A == 0) return IFX_KEY_EMPTY;
+    if (A < 0) {   // clockwise: b <-> c
+        long long t = bx; bx = cx; cx = t; t = by; by = cy; cy = t;
+        float f = zb; zb = zc; zc = f; f = ub; ub = uc; uc = f; f = vb; vb = vc; vc = f;
+        A = -A;
+    }
+    const long long w0 = quad_edge(bx, by, cx, cy, sx, sy), w1 = quad_edge(cx, cy, ax, ay, sx, sy), w2 = quad_edge(ax, ay, bx, by, sx, sy);
+    if (!quad_in(w0, bx, by, cx, cy) || !quad_in(w1, cx, cy, ax, ay) || !quad_in(w2, ax, ay, bx, by)) return IFX_KEY_EMPTY;
+    const float fA = (float)A, la = (float)w0 / fA, lb = (float)w1 / fA, lc = (float)w2 / fA;
+    const float u = (la * ua + lb * ub) + lc * uc, v = (la * va + lb * vb) + lc * vc;
+    const float z = (la * Q.z[ia] + lb * zb) + lc * zc;
+    if (u * u + v * v > 1.0f || !(z >= -1.0f && z <= 1.0f)) return IFX_KEY_EMPTY;
+    return (unsigned long long)(unsigned int)rintf((z * 0.5f + 0.5f) * 16777215.0f) << 32;
+}
+// the per-pixel part: the strip's triangles (v0 v1 v2) and (v2 v1 v3), texcoords (-1,-1) (1,-1) (-1,1) (1,1); the better of the two (both cover a pixel only when the quad folds over)
+__device__ __forceinline__ unsigned long long quad_key(const Quad& Q, int px, int py)
+{
+    const long long sx = (long long)px * QUAD_SUB + QUAD_SUB / 2, sy = (long long)py * QUAD_SUB + QUAD_SUB / 2;
+    const unsigned long long k1 = quad_tri(Q, 0, 1, 2, -1.f, -1.f, 1.f, -1.f, -1.f, 1.f, sx, sy), k2 = quad_tri(Q, 2, 1, 3, -1.f, 1.f, 1.f, -1.f, 1.f, 1.f, sx, sy);
+    return k1 < k2 ? k1 : k2;
+}
+
+// Every id render of an unsharded map under id_rule = 1: all slots, one thread per surfel (MODE 1 GENERAL, MODE 2 INSTANCECOMPARE as k_raster).  ids_step > 1:
+// only the pixels of that lattice (the frame's sparse id render, ifx_map_predict; the rest on demand, ifx_ids_ensure).
+template <int MODE>
+__global__ __launch_bounds__(MAP_THREADS) void k_raster_quad(const DevState* __restrict__ st, const float* __restrict__ pose_inv_ex, const float4* __restrict__ pc,
+                                                             const float4* __restrict__ nr, const float4* __restrict__ votes, Cam c, unsigned long long* __restrict__ keys, int ids_step)
+{
+    const int fl = FIRST_LIVE(c);
+    const float* Ti = pose_inv_ex ? pose_inv_ex : st->pose_inv;
+    float T[12];
+#pragma unroll
+    for (int k = 0; k < 12; k++) T[k] = Ti[k];
+    const int n = st->count;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += blockDim.x * gridDim.x) {
+        const float4 p4 = pc[i];
+        if (!(p4.w > c.conf)) continue;
+        if (MODE == 2) {
+            float4 a = VOTE4(votes, i, 0);
+            bool alleq = true;
+            for (int k = 1; k < 12 && alleq; k++) {
+                float4 b = VOTE4(votes, i, k);
+                alleq = (b.x == a.x) && (b.y == a.y) && (b.z == a.z) && (b.w == a.w);
+            }
+            if (alleq) continue;
+        }
+        Quad Q;
+        if (!quad_setup(T, p4, nr[i], c, Q)) continue;
+        const unsigned long long kid = key_id(c, (unsigned int)i, fl);
+        const int x0 = ((Q.x0 + ids_step - 1) / ids_step) * ids_step, y0 = ((Q.y0 + ids_step - 1) / ids_step) * ids_step;
+        for (int py = y0; py <= Q.y1; py += ids_step)
+            for (int px = x0; px <= Q.x1; px += ids_step) {
+                const unsigned long long k = quad_key(Q, px, py);
+                if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | kid);
+            }
+    }
+}
+
 __device__ inline float key_depth(unsigned long long key)
 {
     unsigned int b = (unsigned int)(key >> 32);
@@ -2051,14 +2166,17 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
 static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, unsigned int want, int32_t* ids_out, bool frame_sums = false, int part = 0, int old_target = 0,
                         bool fold_finish = false, int resolve_ids_step = 1, bool raw_ids = false)
 {
+    unsigned int want_r = want;   // what the cull / raster launches draw
     Cam c = make_cam(h);
     if (part == 0) { c.srank = 0; c.sn = 1; }   // a whole pass (stage API, re-render after a compaction) is never sliced
-    if (part != 2) {
+    const bool quad = h->opt_id_rule && !h->own && (want & LIST_IDS);   // option id_rule: the id half is k_raster_quad's, launched behind the splat half
+    if (quad) want_r &= ~LIST_IDS;
+    if (part != 2 && want_r) {
         const int tw = cdiv(h->w, TILE), th = cdiv(h->h, TILE);
         const bool want_tiles = h->opt_raster_tiles < 0 ? (h->P >= 1000000) : (h->opt_raster_tiles != 0);
         if (want_tiles && !h->tile_recs && hipMalloc(&h->tile_recs, (size_t)h->list_seg_cap * LIST_SEGS * 32) != hipSuccess) h->tile_recs = nullptr;   // 32 B per list entry, on first use
         const bool tiled = want_tiles && tw * th <= TILE_MAX && tw <= 255 && th <= 255 && h->tile_pairs && h->tile_recs;
-        LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, d_pose_inv, (const float4*)h->pc, (const float2*)h->tm, c, time, maxTime, want,
+        LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, d_pose_inv, (const float4*)h->pc, (const float2*)h->tm, c, time, maxTime, want_r,
                h->list_a, tiled ? h->tile_n : (unsigned int*)nullptr, tw * th);
         if (tiled) {
             TileArgs ta;
@@ -2076,6 +2194,9 @@ static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, 
                    h->key_ids, h->key_both, 0, (const int*)nullptr);
     }
     if (part == 1) return;
+    if (quad)
+        LAUNCH(h, "raster_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster_quad<1>, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
+               (const float4*)h->votes, c, h->key_ids, resolve_ids_step);
     if ((want & LIST_SPLAT) && old_target) {   // loop-closure renders: 1 = INACTIVE prediction into the old* images (IndexMap::oldFrameBuffer, EF/IndexMap.cpp:480-483),
         const bool old = old_target == 1;       // 2 = the predict() of EF/ElasticFusion.cpp:453 into the act* images; no fill-in, no dense flag
         LAUNCH(h, old ? "splat_resolve_old" : "splat_resolve_act", dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_splat_resolve, h->d_state, d_pose_inv, h->key_splat,
@@ -2121,6 +2242,18 @@ static void splat_pass(ifx* h, const float* d_pose_inv, int time, int maxTime) {
 
 static void ids_pass(ifx* h, const float* d_pose_inv, int mode, int32_t* out)
 {
+    if (h->opt_id_rule && !h->own) {   // option id_rule: the reference's quads, both modes
+        Cam c = make_cam(h);
+        c.srank = 0; c.sn = 1;
+        if (mode == 1)
+            LAUNCH(h, "ids_raster_quad_inst", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster_quad<2>, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
+                   (const float4*)h->votes, c, h->key_ids, 1);
+        else
+            LAUNCH(h, "ids_raster_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster_quad<1>, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
+                   (const float4*)h->votes, c, h->key_ids, 1);
+        LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, out);
+        return;
+    }
     if (mode != 1) { raster_pass(h, d_pose_inv, 0, 0, LIST_IDS, out); return; }
     Cam c = make_cam(h);   // INSTANCECOMPARE also reads the 192 B of votes: one-kernel version
     LAUNCH(h, "ids_raster_inst", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster<2>, h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
@@ -2159,7 +2292,7 @@ int ifx_ids_ensure(ifx* h)
         if (r == 1) { if ((r = ifx_comm_exchange(h, 200))) return r; if ((r = ifx_owner_ids_resume_impl(h))) return r; }
         return IFX_OK;
     }
-    if (h->ids_view_ok && !h->own) {   // nothing touched the store, the pose or the cached view list since the frame drew its lattice from it: the rest of the image from the same list
+    if (h->ids_view_ok && !h->own && !h->opt_id_rule) {   // nothing touched the store, the pose or the cached view list since the frame drew its lattice from it: the rest of the image from the same list
         Cam c = make_cam(h);
         c.srank = 0; c.sn = 1;
         LAUNCH(h, "raster_view_ids", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<false, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
@@ -2993,6 +3126,7 @@ int ifx_map_predict(ifx* h)
 {
     static const bool no_ids = getenv("IFX_EXPERIMENT_NO_IDS") != nullptr;   // measurement only: what the per-frame id render costs (the id image is then stale)
     const unsigned int want = LIST_SPLAT | ((h->ids_pending && !no_ids) ? LIST_IDS : 0u);
+    const unsigned int want_walk = (h->opt_id_rule && !h->own) ? (want & ~LIST_IDS) : want;   // option id_rule: the walk draws the splat half, raster_pass adds k_raster_quad's ids
     // the tiled rasteriser only on request: at 1280x960 / 20 M surfels the view-list rasteriser takes 455 us where cull + bin + tile raster take 744 (profiles/archive/r02_o_1280_20m.txt)
     const bool tiles = h->opt_raster_tiles > 0;
     if (h->view_frame && !(h->opt_compact_every_frame || h->last_compact_tick == h->tick) && !tiles) {   // the frame built / checked the view list and nothing renumbered the store since
@@ -3012,7 +3146,7 @@ int ifx_map_predict(ifx* h)
             ca.pc_rw = (float4*)h->pc; ca.tm_rw = (float2*)h->tm; ca.tap = (const float4*)h->index_tap; ca.nf_blocks = nb_new; ca.assoc = h->assoc_target; ca.mpc = (const float4*)h->meas_pc;
             ca.mnr = (const float4*)h->meas_nr; ca.flags = h->scan_flags; ca.block_counts = h->scan_block; ca.hot = (Hot*)h->frame_hot;
             LAUNCH(h, "clean_raster_view", dim3(nb_new + (h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS)), dim3(MAP_THREADS), (k_raster_view<false, true>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
-                   (const float2*)h->tm, c, h->tick, h->tick, want, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, ca, (const DevState*)h->d_state);
+                   (const float2*)h->tm, c, h->tick, h->tick, want_walk, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, ca, (const DevState*)h->d_state);
             LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, h->tick, h->tick, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
                    (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
                    h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, h->list_v, h->labels, h->seq, (Hot*)h->frame_hot);
@@ -3020,10 +3154,10 @@ int ifx_map_predict(ifx* h)
         } else {
         if (h->opt_raster_lds)
             LAUNCH(h, "raster_view", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<true, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, c, h->tick, h->tick,
-                   want, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
+                   want_walk, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
         else
             LAUNCH(h, "raster_view", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<false, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, c, h->tick, h->tick,
-                   want, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
+                   want_walk, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
         raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, h->opt_fold_finish != 0, ids_step);   // resolve + the end-of-pass sums in the same launch
         }
     } else {

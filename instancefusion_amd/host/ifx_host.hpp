@@ -353,6 +353,8 @@ public:
     void setPyramid(const bool& val) { option("pyramid", val ? 1 : 0); cfg_.pyramid = val; }
     void setFastOdom(const bool& val) { option("fast_odom", val ? 1 : 0); cfg_.fast_odom = val; }
     void setSo3(const bool& val) { option("so3", val ? 1 : 0); cfg_.so3 = val; }
+    // option "id_rule" (ifx_c_api.h): true = the id images by the reference's surfel_ids.geom / .frag rule (screen-space quads, 24-bit depth); unsharded maps only
+    void setReferenceIdRule(const bool& val) { option("id_rule", val ? 1 : 0); }
 
     // ---- hooks of the deformation an accepted local loop-closure candidate triggers (EF/ElasticFusion.cpp:566-613).  The graph optimisation
     // (Deformation::constrain -> DeformationGraph::optimiseGraphSparse, Eigen + cholmod) is host code of the reference and stays with the caller:

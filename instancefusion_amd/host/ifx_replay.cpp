@@ -21,7 +21,7 @@ struct Args {
     std::string log, masks, out = "./ResultModel", labels, gt_dir, eval_file;
     int width = 640, height = 480, max_frames = 0, max_surfels = 6 * 1000 * 1000, device = 0;
     float fx = 528.f, fy = 528.f, cx = 320.f, cy = 240.f;
-    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true;
+    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false;
     int decode_threads = 4;
     float confidence = 10.f;
     Sharding shard;   // --shard-ranks G --shard-rank r --shard-id FILE: this process is rank r of G over one spatially sharded map (one process per GPU)
@@ -31,7 +31,7 @@ int usage(const char* argv0)
 {
     std::fprintf(stderr,
                  "usage: %s LOG.klg|data.txt [--width W --height H --fx F --fy F --cx C --cy C] [--masks DIR] [--out PREFIX]\n"
-                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C]\n"
+                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids]\n"
                  "       [--gt-dir DIR (DIR/<frame, 6 digits>.png, 8-bit instance ground truth)] [--eval FILE (precision / recall rows, needs --gt-dir)]\n"
                  "       [--shard-ranks G --shard-rank r --shard-id FILE [--shard-nonce N] (one process per GPU over one spatially sharded map; every rank replays the same log; -1: a world of one)]\n",
                  argv0);
@@ -69,6 +69,7 @@ int main(int argc, char** argv)
         else if (s == "--detect-only") a.deform = false;   // loop closures are found and counted, the map is never deformed
         else if (s == "--confidence") a.confidence = (float)std::atof(val("--confidence"));
         else if (s == "--flip-colors") a.flip = true;
+        else if (s == "--reference-ids") a.reference_ids = true;   // id images by the reference's screen-space quad rule (option "id_rule" = 1; not on a sharded map)
         else if (s == "--no-lookahead") a.lookahead = false;   // frames are handed over one at a time, as the reference's loop does
         else if (s == "--shard-ranks") a.shard.ranks = std::atoi(val("--shard-ranks"));   // -1: a world of one on the sharded path
         else if (s == "--shard-rank") a.shard.rank = std::atoi(val("--shard-rank"));
@@ -110,6 +111,7 @@ int main(int argc, char** argv)
         // one stream into a sharded map: the frames exchange the id keys of the lattice whetherDoSegmentation samples, a segmentation call completes the image (ifx_c_api.h: "own_lazy_ids")
         if (a.shard.on()) ifx_set_option(map->handle(), "own_lazy_ids", 1);
         if (!a.deform) map->elasticFusion().setDeformOnLoopClosure(false);
+        if (a.reference_ids) map->elasticFusion().setReferenceIdRule(true);
 
         int frame_Fusion = 0, lastTimeFlann = -1;
         std::vector<int> instanceTableLoopClosure((size_t)instancefusion->getInstanceNum() * 5);
