@@ -473,6 +473,20 @@ int ifx_should_segment(ifx_t* h, int frame);
 int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth,
                              const uint8_t* masks, const int32_t* class_ids, int n, int frame,
                              int flags);
+/* The same call on a detector's raw output already in device memory of the handle's GPU (a PyTorch detector on the same device: no download, no host sort).
+ * d_masks: n x H x W elements, contiguous, in ANY order ([N,1,H,W] is the same layout).  mask_format IFX_MASK_U8: a pixel is inside iff its byte is non-zero
+ * (bool / uint8 masks, the host entry's 0/255); IFX_MASK_F32: inside iff its value is > threshold (mask probabilities as paste_mask_in_image thresholds them;
+ * NaN is outside); threshold is ignored for U8.  d_class_ids: n int32 (device), each follows its mask.  The call applies the bridge's two steps on the device
+ * (build/mask_ori.py:87-124): binarise to 0/255, then a STABLE sort by inside-pixel count, descending (ties keep their input order).  flags: as above; the frame
+ * is always the resident one (rgb = depth = NULL above; the superpixel look-ahead serves it the same way).  stream: the HIP stream the producer wrote on
+ * (NULL = the null stream): the call orders itself behind it with an event wait and does not synchronise the host on it.  Like the host entry, the call returns
+ * after its work has finished: the buffers may then be reused or freed.
+ * Result: bit for bit that of ifx_process_segmentation(h, NULL, NULL, bridge(masks), bridge(class_ids), n, frame, flags).
+ * Refusals (nothing enqueued, the handle stays usable): IFX_E_INVALID for n < 0, n > 256, an unknown format or NULL pointers with n > 0; IFX_E_STATE on a
+ * sharded handle (n_ranks > 1 or -1, ifx_set_shard), whose masks go through ifx_owner_process_segmentation. */
+enum { IFX_MASK_U8 = 0, IFX_MASK_F32 = 1 };
+int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
+                                    void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

@@ -155,6 +155,7 @@ _SIGS = {
     "ifx_tracker_buffer_download": (C.c_int, [_P, C.c_char_p, C.c_int, _P, C.c_int64]),
     "ifx_should_segment": (C.c_int, [_P, C.c_int]),
     "ifx_process_segmentation": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "ifx_process_segmentation_device": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
     "ifx_render_project_map": (C.c_int, [_P, _P, _P]),
     "ifx_set_instance_gt": (C.c_int, [_P, _P]),
@@ -218,6 +219,10 @@ _TRK_SPECS = {
 }
 CORRES_DTYPE = np.dtype([("zx", np.int16), ("zy", np.int16), ("diff", np.float32)])
 
+
+# mask formats of ifx_process_segmentation_device (include/ifx_c_api.h)
+MASK_U8 = 0     # inside iff the byte is non-zero (torch bool / uint8, the host entry's 0/255)
+MASK_F32 = 1    # inside iff the value is > threshold (mask probabilities; NaN is outside)
 
 # option "id_rule" (include/ifx_c_api.h): which rule draws the surfel-id images
 ID_RULE_RAY_DISC = 0     # default: a ray through each pixel centre against the disc, f32 depth keys
@@ -624,6 +629,49 @@ class InstanceFusion:
         flags = (1 if isflann else 0) | (2 if superpixels else 0)
         self.ef._chk(self.L.ifx_process_segmentation(self.ef.handle, _ptr(rgb), _ptr(depth), _ptr(masks), _ptr(cls), int(masks.shape[0]), int(frame), flags),
                      "ifx_process_segmentation")
+
+    def process_segmentation_device(self, masks, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
+        """ProcessSegmentation on a detector's raw output already on the handle's GPU (ifx_process_segmentation_device): no download, no host sort.
+        masks: torch tensor [N,H,W] or [N,1,H,W] on the handle's device, in any order; bool / uint8 (inside iff non-zero) or float32 (inside iff > threshold).
+        class_ids: N integers (tensor or sequence), each following its mask.  The library applies the bridge's binarisation and stable area sort itself.
+        stream: the torch stream the masks were written on (default: the current stream); the call waits for it on the device.  Always the resident frame."""
+        import torch
+
+        dev = torch.device("cuda", int(self.ef.cfgd["device"]))
+        if not isinstance(masks, torch.Tensor):
+            raise TypeError("masks must be a torch tensor on the handle's device")
+        if masks.dtype in (torch.bool, torch.uint8):
+            fmt = MASK_U8
+        elif masks.dtype == torch.float32:
+            fmt = MASK_F32
+        else:
+            raise TypeError(f"masks: dtype {masks.dtype} is not supported (bool, uint8 or float32)")
+        if masks.device != dev:
+            raise ValueError(f"masks are on {masks.device}, the handle on {dev}")
+        hw = (self.ef.h, self.ef.w)
+        if not ((masks.dim() == 3 and tuple(masks.shape[1:]) == hw) or (masks.dim() == 4 and masks.shape[1] == 1 and tuple(masks.shape[2:]) == hw)):
+            raise ValueError(f"masks: shape {tuple(masks.shape)}, expected [N,{hw[0]},{hw[1]}] or [N,1,{hw[0]},{hw[1]}]")
+        n = int(masks.shape[0])
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(stream):          # whatever has to be made on the way is made on the producer's stream
+            m = masks.contiguous()
+            if isinstance(class_ids, torch.Tensor):
+                if class_ids.dtype.is_floating_point or class_ids.dtype.is_complex or class_ids.dtype == torch.bool:
+                    raise TypeError(f"class_ids: dtype {class_ids.dtype} is not an integer type")
+                cls = class_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            else:
+                a = np.asarray(class_ids)
+                if a.size and not np.issubdtype(a.dtype, np.integer):
+                    raise TypeError(f"class_ids: {a.dtype} is not an integer type")
+                cls = torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)   # (no host synchronisation on the stream)
+        if int(cls.numel()) != n:
+            raise ValueError(f"class_ids: {int(cls.numel())} entries for {n} masks")
+        flags = (1 if isflann else 0) | (2 if superpixels else 0)
+        self.ef._chk(self.L.ifx_process_segmentation_device(self.ef.handle, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None), n,
+                                                            int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
+                     "ifx_process_segmentation_device")
+        # (the call returned after its work finished: m and cls may go; they were used on the handle's streams only behind `stream`)
 
     def labels(self):
         n = self.ef.getMapSurfelCount()

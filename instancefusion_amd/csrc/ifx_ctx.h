@@ -500,6 +500,7 @@ struct ifx {
     int* d_clean_list = nullptr;
     void* d_segctl = nullptr; void* h_segctl = nullptr;          // SegCtl of the device-side segmentation call + its pinned mirror (+ 256 verdict bytes)
     uint8_t* h_masks_stage = nullptr; size_t h_masks_cap = 0;    // pinned staging of the caller's masks
+    int* d_mask_rank = nullptr;        // masks already on the device (ifx_process_segmentation_device): [256] inside-pixel counts (zero between calls), [256] order, [256] class ids in that order
     int opt_seg_device = 1;            // segmentation call without the host in the middle (0: the host-driven schedule of round 2)
     int opt_ff_rounds = 0;             // relaxation launches of the flood fill's fixed schedule (0: 24)
     int last_seg_frame = -1;

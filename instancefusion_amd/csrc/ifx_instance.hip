@@ -51,6 +51,131 @@ __global__ void k_mask_clean_overlap_from(const uint8_t* __restrict__ ori, uint8
     }
 }
 
+// ---- masks already on the device (ifx_process_segmentation_device): the bridge's two steps (build/mask_ori.py:87-124 -- binarise to 0/255, stable sort by area,
+// descending) in place of the host's staging copy and upload.  A mask is n x P elements of T: uint8_t (inside iff non-zero) or float (inside iff > thr; NaN is
+// outside).  Loads are 16 B wide where the pointer and P allow (V elements), element-wide otherwise: the caller's tensor is only element-aligned.
+__device__ __forceinline__ bool mask_inside(uint8_t v, float) { return v != 0; }
+__device__ __forceinline__ bool mask_inside(float v, float thr) { return v > thr; }
+// the inside bits of the V elements of a 16-B word, bit j = element j
+__device__ __forceinline__ uint32_t mask_bits(uint4 q, float, const uint8_t*)
+{
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    uint32_t b = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) b |= (((w[k >> 2] >> (8 * (k & 3))) & 0xffu) != 0u ? 1u : 0u) << k;
+    return b;
+}
+__device__ __forceinline__ uint32_t mask_bits(uint4 q, float thr, const float*)
+{
+    return (__uint_as_float(q.x) > thr ? 1u : 0u) | (__uint_as_float(q.y) > thr ? 2u : 0u) | (__uint_as_float(q.z) > thr ? 4u : 0u) | (__uint_as_float(q.w) > thr ? 8u : 0u);
+}
+#define MI_THREADS 256
+#define MI_ITER 4      // k_mask_area: 16-B words per thread, a block covers MI_THREADS * MI_ITER of them of one mask
+// Inside pixels per mask: grid (chunks, n).  Integer counts: any order of the sums is exact.  Per wave, then across the block's waves in LDS, then one atomic per
+// block.  The counters are zero on entry (k_mask_order leaves them so).
+template <typename T>
+__global__ void __launch_bounds__(MI_THREADS) k_mask_area(const T* __restrict__ src, int P, float thr, int* __restrict__ area)
+{
+    constexpr int V = 16 / sizeof(T);
+    const int m = blockIdx.y, tid = threadIdx.x;
+    const T* row = src + (size_t)m * P;
+    const int head = min(P, (int)((V - ((uintptr_t)row / sizeof(T)) % V) % V));   // elements before the first 16-B boundary
+    const int nv = (P - head) / V, tail0 = head + nv * V;
+    const uint4* vrow = (const uint4*)(row + head);
+    int c = 0;
+    const int v0 = blockIdx.x * (MI_THREADS * MI_ITER) + tid;
+    uint4 q[MI_ITER];
+#pragma unroll
+    for (int it = 0; it < MI_ITER; it++) { const int v = v0 + it * MI_THREADS; q[it] = v < nv ? vrow[v] : make_uint4(0, 0, 0, 0); }
+#pragma unroll
+    for (int it = 0; it < MI_ITER; it++) if (v0 + it * MI_THREADS < nv) c += __popc(mask_bits(q[it], thr, (const T*)nullptr));
+    if (blockIdx.x == 0) {   // the unaligned head and the tail (fewer than V elements each)
+        if (tid < head) c += mask_inside(row[tid], thr) ? 1 : 0;
+        if (tid < P - tail0) c += mask_inside(row[tail0 + tid], thr) ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    __shared__ int s_c[MI_THREADS / 64];
+    if ((tid & 63) == 0) s_c[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int w = 0; w < MI_THREADS / 64; w++) sum += s_c[w];
+        if (sum) atomicAdd(&area[m], sum);
+    }
+}
+// The bridge's order in one workgroup: rank_i = #{j : a_j > a_i} + #{j < i : a_j == a_i} (Python's sorted(..., reverse=True) is stable: ties keep their input
+// order).  order[rank] = input index; the class ids follow their masks.  The counters are cleared for the next call.
+__global__ void __launch_bounds__(256) k_mask_order(int* __restrict__ area, const int32_t* __restrict__ cls_in, int nm, int* __restrict__ order, int* __restrict__ cls_out)
+{
+    __shared__ int s_a[256];
+    const int i = threadIdx.x;
+    if (i < nm) { s_a[i] = area[i]; area[i] = 0; }
+    __syncthreads();
+    if (i >= nm) return;
+    const int a = s_a[i];
+    int r = 0;
+    for (int j = 0; j < nm; j++) { const int b = s_a[j]; r += (b > a || (b == a && j < i)) ? 1 : 0; }
+    order[r] = i;
+    cls_out[r] = cls_in[i];
+}
+// One pass per pixel, the masks in sorted order from the last to the first (k_mask_clean_overlap_from): the binarised masks in sorted order (0/255: the
+// reference's "BAK ORI MASK"), the working copy after the overlap clean, and the per-mask verdict bytes of the call cleared.  A thread takes V consecutive
+// pixels: 16-B loads (4 masks in flight) and V-byte stores when every mask starts on a 16-B boundary (vec), element loads otherwise.
+template <typename T>
+__global__ void __launch_bounds__(MI_THREADS) k_mask_gather(const T* __restrict__ src, int P, float thr, const int* __restrict__ order, int nm, int vec,
+                                                            uint8_t* __restrict__ ori, uint8_t* __restrict__ masks, uint8_t* __restrict__ unavail)
+{
+    constexpr int V = 16 / sizeof(T);
+    __shared__ int s_ord[256];
+    const int g = blockIdx.x * MI_THREADS + threadIdx.x;
+    for (int t = threadIdx.x; t < nm; t += MI_THREADS) s_ord[t] = order[t];
+    if (unavail && g < nm) unavail[g] = 0;
+    __syncthreads();
+    const int p0 = g * V;
+    if (p0 >= P) return;
+    const int np = min(V, P - p0);
+    auto put = [&](int s, uint32_t in, uint32_t kept) {
+        uint8_t* o = ori + (size_t)s * P + p0;
+        uint8_t* w = masks + (size_t)s * P + p0;
+        if (vec) {
+            uint32_t wo[V / 4], ww[V / 4];
+#pragma unroll
+            for (int k = 0; k < V / 4; k++) { wo[k] = 0; ww[k] = 0; }
+#pragma unroll
+            for (int j = 0; j < V; j++) { wo[j >> 2] |= ((in >> j) & 1u) * (0xffu << (8 * (j & 3))); ww[j >> 2] |= ((kept >> j) & 1u) * (0xffu << (8 * (j & 3))); }
+            if constexpr (V == 16) { *(uint4*)o = make_uint4(wo[0], wo[1], wo[2], wo[3]); *(uint4*)w = make_uint4(ww[0], ww[1], ww[2], ww[3]); }
+            else { *(uint32_t*)o = wo[0]; *(uint32_t*)w = ww[0]; }
+        } else {
+            for (int j = 0; j < np; j++) { o[j] = ((in >> j) & 1u) ? 255 : 0; w[j] = ((kept >> j) & 1u) ? 255 : 0; }
+        }
+    };
+    uint32_t flag = 0;   // bit j: pixel p0 + j lies in a mask later in the sorted order
+    int s = nm - 1;
+    if (vec) {
+        for (; s >= 3; s -= 4) {
+            uint4 q[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) q[k] = *(const uint4*)(src + (size_t)s_ord[s - k] * P + p0);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const uint32_t in = mask_bits(q[k], thr, (const T*)nullptr);
+                put(s - k, in, in & ~flag);
+                flag |= in;
+            }
+        }
+    }
+    for (; s >= 0; s--) {
+        const T* row = src + (size_t)s_ord[s] * P + p0;
+        uint32_t in;
+        if (vec) in = mask_bits(*(const uint4*)row, thr, (const T*)nullptr);
+        else { in = 0; for (int j = 0; j < np; j++) in |= (mask_inside(row[j], thr) ? 1u : 0u) << j; }
+        put(s, in, in & ~flag);
+        flag |= in;
+    }
+}
+
 // checkProjectDepthAndInstanceKernel, IF/Core/InstanceFusionCuda.cu:736-760
 __global__ void k_check_project(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ votes, int cap, int w, int h, int downsample,
                                 int* __restrict__ counts)
@@ -412,7 +537,7 @@ int ifx_alloc_instance(ifx* h)
 void ifx_free_instance(ifx* h)
 {
     hipFree(h->d_inst_color); hipFree(h->d_masks); hipFree(h->d_masks_ori); hipFree(h->d_unavail); hipFree(h->d_ff_label); hipFree(h->d_pdm); hipFree(h->d_bbox); hipFree(h->d_inst_stats); hipFree(h->d_clean_list);
-    hipFree(h->d_segctl);
+    hipFree(h->d_segctl); hipFree(h->d_mask_rank);
     if (h->h_segctl) hipHostFree(h->h_segctl);
     if (h->h_masks_stage) hipHostFree(h->h_masks_stage);
 }
@@ -1082,12 +1207,34 @@ static int oseg_resume(ifx* h)
     return IFX_E_STATE;
 }
 
-static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags);
-static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags);
+// the masks of ifx_process_segmentation_device: the caller's n x P elements in device memory, their format, the class ids (device), and an event recorded on the
+// producer's stream at entry (the ingestion waits for it; nothing before the ingestion does)
+struct DevMasks { const void* d; int fmt; float thr; const int32_t* d_cls; hipEvent_t ready; };
+static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
+static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
+static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
 extern "C" int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
 {
     if (!h || nm < 0 || (nm > 0 && (!masks_in || !class_ids))) return IFX_E_INVALID;
     if (nm > 256) { h->err = "too many masks"; return IFX_E_INVALID; }
+    return process_segmentation(h, rgb, depth, masks_in, class_ids, nullptr, nm, frame, flags);
+}
+extern "C" int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || n > 256) { h->err = "ifx_process_segmentation_device: n must be 0 .. 256"; return IFX_E_INVALID; }
+    if (mask_format != IFX_MASK_U8 && mask_format != IFX_MASK_F32) { h->err = "ifx_process_segmentation_device: unknown mask format"; return IFX_E_INVALID; }
+    if (n > 0 && (!d_masks || !d_class_ids)) { h->err = "ifx_process_segmentation_device: null masks or class ids"; return IFX_E_INVALID; }
+    if (h->own || h->shard_n > 1) { h->err = "ifx_process_segmentation_device: a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
+    DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_device: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
+    const int r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags);
+    h->event_pool.push_back(dm.ready);
+    return r;
+}
+static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags)
+{
     // The next frame's tracker is already queued on the main stream (enqueue_frame, "tracked ahead") and touches nothing this call does: the call's ~60 short
     // launches then go to the handle's third stream (the loop-closure tracker's: four streams is what the runtime's hardware queues hold) and run beside the tracker's 170 instead of behind them.  The call ends with the host waiting for its stream,
     // so whatever the caller enqueues next is ordered behind it as before.
@@ -1097,8 +1244,8 @@ extern "C" int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint
         if (h->ev_result) HIPCHK(h, hipStreamWaitEvent(h->stream_c, h->ev_result, 0));   // behind the frame the call belongs to
         h->cur = h->stream_c;
     }
-    const int r = h->opt_seg_device ? process_segmentation_device(h, rgb, depth, masks_in, class_ids, nm, frame, flags)
-                                    : process_segmentation_host(h, rgb, depth, masks_in, class_ids, nm, frame, flags);
+    const int r = h->opt_seg_device ? process_segmentation_device(h, rgb, depth, masks_in, class_ids, dm, nm, frame, flags)
+                                    : process_segmentation_host(h, rgb, depth, masks_in, class_ids, dm, nm, frame, flags);
     if (aside) { hipStreamSynchronize(h->stream_c); h->cur = h->stream; }
     // a call that failed part-way may have updated votes without the label scan that follows them: the incremental scan of the next call assumes
     // that votes outside its own id image are unchanged since the last scan, so the next call scans everything
@@ -1170,7 +1317,34 @@ static int seg_label_scan(ifx* h, const int* gate = nullptr, bool default_done =
     return 1;
 }
 
-static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
+// The ingestion of the device entry's masks, behind the producer's event: inside-pixel counts, the bridge's order (class ids in that order to cls_out, device [nm]),
+// then d_masks_ori / d_masks in sorted order and the verdict bytes cleared (unavail, or none) -- three launches for the host entry's upload + overlap clean.
+template <typename T>
+static int seg_ingest_launch(ifx* h, const T* src, float thr, const int32_t* d_cls, int nm, int* cls_out, uint8_t* unavail)
+{
+    constexpr int V = 16 / sizeof(T);
+    const int P = h->P;
+    int* area = h->d_mask_rank;
+    int* order = area + 256;
+    LAUNCH(h, "mask_area", dim3(std::max(1, cdiv(P / V, MI_THREADS * MI_ITER)), nm), dim3(MI_THREADS), k_mask_area<T>, src, P, thr, area);
+    LAUNCH(h, "mask_order", dim3(1), dim3(256), k_mask_order, area, d_cls, nm, order, cls_out);
+    const int vec = ((uintptr_t)src % 16 == 0 && P % V == 0) ? 1 : 0;   // every mask then starts on a 16-B boundary, and so does every V-pixel group of the outputs
+    LAUNCH(h, "mask_gather", dim3(cdiv(cdiv(P, V), MI_THREADS)), dim3(MI_THREADS), k_mask_gather<T>, src, P, thr, (const int*)order, nm, vec, h->d_masks_ori, h->d_masks, unavail);
+    return IFX_OK;
+}
+static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail)
+{
+    if (!h->d_mask_rank) {
+        HIPCHK(h, hipMalloc(&h->d_mask_rank, 3 * 256 * sizeof(int)));
+        HIPCHK(h, hipMemsetAsync(h->d_mask_rank, 0, 256 * sizeof(int), h->cur));   // the counters; k_mask_order leaves them zero for the next call
+    }
+    HIPCHK(h, hipStreamWaitEvent(h->cur, dm->ready, 0));   // behind what the producer enqueued before the call (no host synchronisation)
+    if (!cls_out) cls_out = h->d_mask_rank + 512;
+    return dm->fmt == IFX_MASK_F32 ? seg_ingest_launch(h, (const float*)dm->d, dm->thr, dm->d_cls, nm, cls_out, unavail)
+                                   : seg_ingest_launch(h, (const uint8_t*)dm->d, dm->thr, dm->d_cls, nm, cls_out, unavail);
+}
+
+static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags)
 {
     ifx_ids_ensure(h);   // the call reads the id image under every mask pixel
     // Only the kNN smoothing looks at surfels the id image does not show: a slot outside the cached view list that has outlived the age rule
@@ -1188,11 +1362,19 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
     std::vector<uint8_t> unavailable(nm, 0);
     int r = ifx_ensure_masks(h, mbytes);
     if (r) return r;
-    // the masks stay on the device from here on: d_masks_ori = "BAK ORI MASK" (:705-706), d_masks = working copy
-    HIPCHK(h, hipMemcpyAsync(h->d_masks_ori, masks_in, mbytes, hipMemcpyHostToDevice, h->cur));
-    HIPCHK(h, hipMemcpyAsync(h->d_masks, h->d_masks_ori, mbytes, hipMemcpyDeviceToDevice, h->cur));
-    // step 0_1
-    LAUNCH(h, "mask_clean_overlap", dim3(cdiv(P, 256)), dim3(256), k_mask_clean_overlap, h->d_masks, nm, P);
+    std::vector<int32_t> cls_sorted;
+    if (dm) {   // the caller's device masks: sorted, binarised and cleaned on the device; the class ids in that order come back before compare_map (run_bboxes synchronises)
+        if ((r = seg_ingest_device(h, dm, nm, nullptr, nullptr))) return r;
+        cls_sorted.resize(nm);
+        HIPCHK(h, hipMemcpyAsync(cls_sorted.data(), h->d_mask_rank + 512, (size_t)nm * 4, hipMemcpyDeviceToHost, h->cur));
+        class_ids = cls_sorted.data();
+    } else {
+        // the masks stay on the device from here on: d_masks_ori = "BAK ORI MASK" (:705-706), d_masks = working copy
+        HIPCHK(h, hipMemcpyAsync(h->d_masks_ori, masks_in, mbytes, hipMemcpyHostToDevice, h->cur));
+        HIPCHK(h, hipMemcpyAsync(h->d_masks, h->d_masks_ori, mbytes, hipMemcpyDeviceToDevice, h->cur));
+        // step 0_1
+        LAUNCH(h, "mask_clean_overlap", dim3(cdiv(P, 256)), dim3(256), k_mask_clean_overlap, h->d_masks, nm, P);
+    }
     // steps -1_1 .. -1_3 (superpixel refinement)
     if (flags & 2) {
         r = ifx_superpixel_refine(h, rgb, depth, nm, frame);
@@ -1393,7 +1575,7 @@ static int seg_ensure_ctl(ifx* h, size_t mask_bytes)
     return IFX_OK;
 }
 
-static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
+static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags)
 {
     static const bool trace = getenv("IFX_SEG_TRACE") != nullptr;   // diagnostic: where the host is inside a call (us since entry, to stderr)
     const auto t_in = std::chrono::steady_clock::now();
@@ -1413,7 +1595,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     const size_t mbytes = (size_t)nm * P;
     int r = ifx_ensure_masks(h, mbytes);
     if (r) return r;
-    if ((r = seg_ensure_ctl(h, mbytes))) return r;
+    if ((r = seg_ensure_ctl(h, dm ? 0 : mbytes))) return r;   // (device masks: no staging)
     SegCtl* hc = (SegCtl*)h->h_segctl;
     hipEvent_t ea = ifx_event_get(h);
     hipEventRecord(ea, h->cur);
@@ -1428,19 +1610,25 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     const bool default_early = h->opt_labels_incremental && !h->labels_stale_all;
     if (default_early) LAUNCH(h, "colour_default", dim3(2048), dim3(256), k_colour_default, h->d_state, (const float2*)h->tm, (float2*)h->col, h->labels, (const int*)nullptr);
     if (flags & 2) { if ((r = ifx_superpixel_filter_prepare(h, nm))) return r; }
-    memcpy(h->h_masks_stage, masks_in, mbytes);
+    if (!dm) memcpy(h->h_masks_stage, masks_in, mbytes);
     hc->ff_incomplete = 0; hc->evict_at = -1; hc->nm = nm; hc->pad = 0;
     for (int i = 0; i < NI; i++) hc->inst_class[i] = h->inst_class[i];
-    for (int m = 0; m < 256; m++) { hc->cls[m] = m < nm ? class_ids[m] : -1; hc->best[m] = -1; hc->target[m] = -1; }
-    t_stage = us();
-    HIPCHK(h, hipMemcpyAsync(h->d_masks_ori, h->h_masks_stage, mbytes, hipMemcpyHostToDevice, h->cur));   // pinned: a true asynchronous copy
-    HIPCHK(h, hipMemcpyAsync(h->d_segctl, hc, sizeof(SegCtl), hipMemcpyHostToDevice, h->cur));
-    LAUNCH(h, "mask_clean_overlap", dim3(cdiv(P, 256)), dim3(256), k_mask_clean_overlap_from, (const uint8_t*)h->d_masks_ori, h->d_masks, nm, P, h->d_unavail);
+    for (int m = 0; m < 256; m++) { hc->cls[m] = m < nm && !dm ? class_ids[m] : -1; hc->best[m] = -1; hc->target[m] = -1; }   // (device masks: k_mask_order writes the class ids)
+    SegCtl* dc = (SegCtl*)h->d_segctl;
+    if (dm) {   // the caller's device masks: sorted, binarised and cleaned on the device, the class ids in sorted order into the control block
+        HIPCHK(h, hipMemcpyAsync(h->d_segctl, hc, sizeof(SegCtl), hipMemcpyHostToDevice, h->cur));
+        if ((r = seg_ingest_device(h, dm, nm, dc->cls, h->d_unavail))) return r;
+        t_stage = us();
+    } else {
+        t_stage = us();
+        HIPCHK(h, hipMemcpyAsync(h->d_masks_ori, h->h_masks_stage, mbytes, hipMemcpyHostToDevice, h->cur));   // pinned: a true asynchronous copy
+        HIPCHK(h, hipMemcpyAsync(h->d_segctl, hc, sizeof(SegCtl), hipMemcpyHostToDevice, h->cur));
+        LAUNCH(h, "mask_clean_overlap", dim3(cdiv(P, 256)), dim3(256), k_mask_clean_overlap_from, (const uint8_t*)h->d_masks_ori, h->d_masks, nm, P, h->d_unavail);
+    }
     if (flags & 2) {
         r = ifx_superpixel_filter(h, nm, true);
         if (r) return r;
     }
-    SegCtl* dc = (SegCtl*)h->d_segctl;
     LAUNCH(h, "project_bbox_mask", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<2>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
            h->d_bbox, ifx_idmap(h));
     LAUNCH(h, "seg_compare", dim3(1), dim3(256), k_seg_compare, dc, (const int*)h->d_bbox, h->d_unavail);
@@ -1480,7 +1668,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         std::vector<uint8_t> unavailable(h_un, h_un + nm);
         std::vector<int> cmp((size_t)nm * NI, 0), bbox;
         for (int m = 0; m < nm; m++) if (hc->best[m] > 0) cmp[hc->best[m] + m * NI] = 1;
-        r = seg_host_mask_loop(h, nm, class_ids, hc->evict_at, cmp, unavailable, bbox);
+        r = seg_host_mask_loop(h, nm, dm ? hc->cls : class_ids, hc->evict_at, cmp, unavailable, bbox);   // (device masks: the class ids in sorted order, as read back)
         if (r) return r;
         seg_label_scan(h);
     }

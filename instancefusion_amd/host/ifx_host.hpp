@@ -922,6 +922,22 @@ public:
         handle_ = map->handle();
         segmentations_++;
     }
+    // The same call on a detector's raw output already in device memory of the map's GPU (ifx_process_segmentation_device): d_masks n x H x W in any order,
+    // format IFX_MASK_U8 (inside iff non-zero) or IFX_MASK_F32 (inside iff > threshold), d_class_ids n int32 on the device, stream the HIP stream the detector
+    // wrote on (as a void*: this header includes no HIP header).  The library binarises and sorts by area as the bridge does; the frame is the resident one.
+    void ProcessSegmentationDevice(const std::unique_ptr<ElasticFusionInterface>& map, const void* d_masks, int format, float threshold, const int32_t* d_class_ids, int n,
+                                   int frame_num, bool isflann, void* stream)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDevice: the map has no handle (") + ifx_global_error() + ")");
+        if (map->elasticFusion().sharding().on())
+            throw std::runtime_error("InstanceFusion::ProcessSegmentationDevice: a sharded map takes its masks from the host (ProcessSegmentation)");
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        const int r = ifx_process_segmentation_device(h, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_device: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+    }
 
     // IF/Core/InstanceTable.cpp:336-445: precision / recall against the ground-truth ids the surfels carry (processFrame's instanceGT); appends to `path` the
     // rows the reference appends to ./temp/Precision_Recall_RAW.txt.  inUse: instance slots in use (+ evicted ones) as the reference's summary row reports them.
