@@ -379,15 +379,14 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           24-bit depth with GL_LESS (ties: the lower slot) -- the reference's id images up to GL's sub-pixel latitude (DESIGN.md section 9-3
  *                           has its cost).  Refused (IFX_E_STATE) on a sharded handle and while a frame is in flight or announced ahead; a change re-renders
  *                           the current id image at once.  Not the INACTIVE splat of the loop-closure detection, which is a splat render.
- *   "fold_finish" 0, "seg_device" 0, "seg_aside" 0, "ff_union" 0, "ff_rounds" n -- the earlier forms of the end-of-frame sums and of the segmentation call's
- *                           schedule (host-driven / on the main stream / relaxation-only flood fill / length of the fixed relaxation schedule); identical results
- *   "clean_raster" 0, "hot_records" 0, "vlist_one" 1 -- round 5's map-pass forms off / on: the clean pass and the prediction's raster as ONE walk of the view list; the
- *                           gathered 64-byte copy of the hot fields; list offsets + concatenation in one launch (measured equal: off).  Identical results
- *   "host_entry_async" 1  -- ifx_process_frame returns when the frame's POSE is known (see there); "vote_per_mask" 0 -- the instance votes of a call in ONE launch over all
- *                           masks instead of one per mask in mask order (experiments only: the order is part of the reference's result while a packed counter's low half is negative)
- *   "overdue_rule" 0, "own_first_live" 0 -- test switches: a view-list rebuild without the age rule its newcomers have outlived / the sharded map's "surfel 0" fixed at
- *                           creation number 0 (round 4's behaviour of both: results then differ from the reference's in the cases tests/test_gpu_sweep.py and
- *                           test_owner_sharded_map_emulated hold) */
+ *   "seg_device" 0, "seg_aside" 0, "ff_rounds" n -- the earlier forms of the segmentation call's schedule (host-driven / on the main stream) and the length
+ *                           of the flood fill's fixed relaxation schedule (default 4); identical results
+ *   "clean_raster" 0, "hot_records" 0 -- round 5's map-pass forms off: the clean pass and the prediction's raster as ONE walk of the view list; the
+ *                           gathered 64-byte copy of the hot fields.  Identical results
+ *   "host_entry_async" 1  -- ifx_process_frame returns when the frame's POSE is known (see there)
+ *   "own_first_live" 0    -- test switch: the sharded map's "surfel 0" fixed at creation number 0 (round 4's behaviour: results then differ from the
+ *                           reference's in the cases test_owner_sharded_map_emulated holds)
+ * An unknown name is refused (IFX_E_INVALID); ifx_create reports each entry of IFX_OPTS that is refused on stderr and goes on. */
 int ifx_set_option(ifx_t* h, const char* name, int value);
 
 /* R32I surfel-id image after fusion (getSurfelIdsAfterFusionGpu, ElasticFusionInterface.h:90-102):

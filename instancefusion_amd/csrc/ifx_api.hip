@@ -121,7 +121,6 @@ extern "C" int ifx_create(const ifx_config* cfg, ifx_t** out)
         hipError_t r1 = prio ? hipStreamCreateWithPriority(&h->stream, hipStreamDefault, hi) : hipStreamCreate(&h->stream);
         hipError_t r2 = prio ? hipStreamCreateWithPriority(&h->stream_b, hipStreamDefault, lo) : hipStreamCreate(&h->stream_b);
         if (r1 != hipSuccess || r2 != hipSuccess) { g_err = "hipStreamCreate failed"; delete h; return IFX_E_HIP; }
-        hipEventCreateWithFlags(&h->ev_gate, hipEventDisableTiming);
         // ONE more stream for everything that runs beside the main stream now and then (the model-to-model tracker of the loop-closure detection, a segmentation call):
         // the runtime multiplexes streams onto four hardware queues, the process's default stream has one, and a fifth stream shares a queue with another -- whose
         // barrier packets then hold it up (a stream of its own for the segmentation call cost closeLoops = true two thirds of its frame rate: 1031 -> 348 frames/s)
@@ -230,7 +229,8 @@ extern "C" int ifx_create(const ifx_config* cfg, ifx_t** out)
             if (p1 == std::string::npos) p1 = all.size();
             const std::string kv = all.substr(p0, p1 - p0);
             const size_t eq = kv.find('=');
-            if (eq != std::string::npos) ifx_set_option(h, kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1));
+            if (eq != std::string::npos && ifx_set_option(h, kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1)) != IFX_OK)
+                fprintf(stderr, "libifx: IFX_OPTS entry \"%s\" refused: %s\n", kv.c_str(), ifx_last_error(h));   // (an A/B line naming a removed switch must not measure the default twice in silence)
             p0 = p1 + 1;
         }
     }
@@ -276,7 +276,6 @@ extern "C" void ifx_destroy(ifx_t* h)
     ifx_slic_free(h);
     ifx_knn_free_all(h);
     for (int q = 0; q < 2; q++) { if (h->slot[q].ready) hipEventDestroy(h->slot[q].ready); if (h->slot[q].released) hipEventDestroy(h->slot[q].released); }
-    if (h->ev_gate) hipEventDestroy(h->ev_gate);
     if (h->stream_c) hipStreamDestroy(h->stream_c);
     if (h->stream_b) hipStreamDestroy(h->stream_b);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -339,8 +338,6 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
     else if (s == "clean_raster") h->opt_clean_raster = value;
     else if (s == "hot_records") { h->opt_hot = value; h->hot_valid = 0; }
     else if (s == "hot_verify") h->opt_hot_verify = value;
-    else if (s == "side_late") h->opt_side_late = value;
-    else if (s == "vote_per_mask") h->opt_vote_per_mask = value;
     else if (s == "own_first_live") h->opt_own_first_live = value;
     else if (s == "own_track_rows") {
         if (!h->own) { h->err = "own_track_rows: the handle was not created for a sharded map"; return IFX_E_STATE; }
@@ -369,8 +366,6 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
             if (r) return r;
         }
     }
-    else if (s == "vlist_one") h->opt_vlist_one = value;
-    else if (s == "overdue_rule") h->opt_overdue_rule = value;
     else if (s == "cam_swap") h->opt_cam_swap = value;
     else if (s == "cam_side") h->opt_cam_side = value;
     else if (s == "host_entry_async") h->opt_host_entry_async = value;
@@ -381,40 +376,14 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
     else if (s == "clean_blocks") h->opt_clean_blocks = std::max(0, std::min(65536, value));
     else if (s == "index_blocks") h->opt_index_blocks = std::max(0, std::min(8192, value));
     else if (s == "res_blocks") h->opt_res_blocks = std::max(0, std::min(4096, value));
-    else if (s == "icp_lds") {
-#ifdef IFX_EXPERIMENTS
-        h->opt_icp_lds = value;
-#else
-        if (value) { h->err = "icp_lds: a measured alternative that lost (DESIGN.md section 6); this library was built without -DIFX_EXPERIMENTS"; return IFX_E_STATE; }
-#endif
-    }
     else if (s == "rgb_blocks") h->opt_rgb_blocks = std::max(0, std::min(1024, value));
     else if (s == "raster_tiles") h->opt_raster_tiles = value;
     else if (s == "view_list") { h->opt_vlist = value; ifx_vlist_reap(h); hs_invalidate_view(h); }
     else if (s == "seg_aside") h->opt_seg_aside = value;
     else if (s == "pace") h->opt_pace = value;
-    else if (s == "lc_view") h->opt_lc_view = value;
-    else if (s == "side_gate") h->opt_side_gate = value;
-    else if (s == "ff_union") h->opt_ff_union = value;
-    else if (s == "fold_finish") h->opt_fold_finish = value;
     else if (s == "lazy_ids") { ifx_ids_ensure(h); h->opt_lazy_ids = value; }
     else if (s == "seg_device") h->opt_seg_device = value;
     else if (s == "ff_rounds") h->opt_ff_rounds = value;
-    else if (s == "labels_incremental") { h->opt_labels_incremental = value; h->labels_stale_all = 1; }
-    else if (s == "icp_px") {
-#ifdef IFX_EXPERIMENTS
-        h->opt_icp_px = value;
-#else
-        if (value) { h->err = "icp_px: a measured alternative that lost (DESIGN.md section 6); this library was built without -DIFX_EXPERIMENTS"; return IFX_E_STATE; }
-#endif
-    }
-    else if (s == "model_fused") {
-#ifdef IFX_EXPERIMENTS
-        h->opt_model_fused = value;
-#else
-        if (value) { h->err = "model_fused: a measured alternative that lost (DESIGN.md section 6); this library was built without -DIFX_EXPERIMENTS"; return IFX_E_STATE; }
-#endif
-    }
     else if (s == "gn_persist_blocks") { if (value < 1) return IFX_E_INVALID; ifx_drop_tracked(h); h->opt_gn_persist_blocks = value; }
     else if (s == "gn_persist") {   // a bit per pyramid level: that level's Gauss-Newton iterations in one persistent launch (k_gn_level); default 4 = the coarsest level only
         if (value < 0 || value > 7) { h->err = "gn_persist is a mask of pyramid levels (0..7)"; return IFX_E_INVALID; }
@@ -635,12 +604,8 @@ static int enqueue_frame(ifx* h, const uint8_t* rgb, const uint16_t* depth, int 
             if (tracked) {
                 ifx_tracker_commit(h);
                 if (weight_mult != 1.0f) ifx_tracker_set_weight(h, weight_mult);
-                if (h->opt_side_gate == 1 && h->ev_gate) { hipEventRecord(h->ev_gate, h->stream); hipStreamWaitEvent(h->stream_b, h->ev_gate, 0); }   // (experiment) not under the tracker's tail
-                // (option side_late: the announced frame's side enqueued behind this frame's map passes instead -- measured slower, see ifx_ctx.h)
-                if (h->opt_side_gate != 2 && !h->opt_side_late) {
-                    int r = ifx_enqueue_hinted_frame_side(h);   // no tracker enqueue to hide it in: it runs under this frame's map passes
-                    if (r) return r;
-                }
+                int r = ifx_enqueue_hinted_frame_side(h);   // no tracker enqueue to hide it in: it runs under this frame's map passes
+                if (r) return r;
             } else if (!in_pose16 || bootstrap) {
                 ifx_tracker_model_side(h);                       // model pyramid: independent of the frame side
                 HIPCHK(h, hipStreamWaitEvent(h->stream, f.ready, 0));
@@ -692,7 +657,6 @@ static int enqueue_frame(ifx* h, const uint8_t* rgb, const uint16_t* depth, int 
     hipEventRecord(f.released, h->stream);   // one marker: the side stream waits for it before it reuses the slot,
     h->ev_result = f.released;               // the host before it reads the frame result
     {
-        if (h->opt_side_gate == 2 && h->hint_rgb && h->opt_two_streams) hipStreamWaitEvent(h->stream_b, f.released, 0);   // (experiment) under the next tracker only
         int r = ifx_enqueue_hinted_frame_side(h);   // not consumed by the tracker (first frame, external pose)
         if (r) return r;
     }

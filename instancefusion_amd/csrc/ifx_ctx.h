@@ -26,7 +26,6 @@ struct DevState {
     int n_dead;           // tombstones
     int n_new;            // new surfels appended by the last clean
     int overflow;         // set when an append hit the capacity
-    unsigned int list_n[4];   // (unused: the work-list lengths live in ifx::d_list_ctr, one counter per list segment)
     unsigned int r_max_bits;  // float bits of an upper bound of every surfel radius ever stored (conservative frustum margin)
     // tracker state (RGBDOdometry::getIncrementalTransformation, EF/Utils/RGBDOdometry.cpp:267-603)
     float Rprev[9], tprev[3], Rprev_inv[9];
@@ -48,9 +47,9 @@ struct DevState {
     int seg_counts[2];
     int seg_acc[2];              // whetherDoSegmentation sums of the frame being finished (k_raster_finish -> k_frame_result)
     int fold_total;              // != 0: this frame's k_splat_resolve accumulated fold_acc itself (= the number of dense-test samples); k_frame_result folds and clears
-    int fold_acc[16][4];         // partial sums by blockIdx.x & 15: vote mass, empty lattice pixels, lit dense-test samples, -
+    alignas(64) int fold_acc[16][4];   // partial sums by blockIdx.x & 15: vote mass, empty lattice pixels, lit dense-test samples, - (targets of atomics from every block of
+                                       // k_splat_resolve: four rows to a line, and result_ticket not on a line with them -- 0.8 us of that launch, profiles/r08_prune_switches.txt)
     int first_live;              // lowest live slot: the reference's "surfel 0" (drawn as id 0 = "no surfel" in every id-carrying image; ifx_map.hip key_id)
-    unsigned int append_ticket;  // last-block ticket of k_vlist_flatten (k_append_scan, whose it was, publishes without one since round 5)
     int app_count0; unsigned int app_seq0, app_vln0;   // count / next_seq / vl_n[0] when the frame's new-surfel flags were taken (k_new_flags_count): k_append_scan's starting point
     unsigned int result_ticket;  // last-block ticket of k_splat_resolve when it also writes the frame result (FrameOut)
     unsigned int next_seq;       // creation number of the next new surfel (spatially sharded map: identical on every rank)
@@ -230,9 +229,8 @@ __device__ __forceinline__ void vlist_decide_core(DevState* st, const float* A, 
     for (int k = 0; k < 16; k++) st->vl_pose[k] = B[k];
     st->vl_n[0] = 0; st->vl_n[1] = 0;
 }
-__device__ inline void vlist_decide(DevState* st, unsigned int* __restrict__ lctr)
+__device__ inline void vlist_decide(DevState* st)
 {
-    (void)lctr;
     vlist_decide_core(st, st->vl_pose, st->pose, st->vl_valid, st->vl_age);
 }
 
@@ -329,14 +327,8 @@ struct ifx {
     int opt_slic_ahead = 1;             // when the cadence says the announced next frame ends with a segmentation call: its superpixels + merge (frame-only work) go to the side stream now
     int opt_track_ahead = 1;            // with a hinted next frame: enqueue its tracker right behind the current frame, before the host decides about segmentation
     int tracked_ahead = 0;              // tick whose tracker is already on the queue (result parked in DevState::spec_*)
-    int opt_side_gate = 0; hipEvent_t ev_gate = nullptr;   // (experiment) where the announced frame's image-only work may start: 0 at once, 1 behind the commit, 2 behind the frame
-    int opt_overdue_rule = 1;           // a list rebuild first applies the age rule that slots no list held have outlived (k_cull_frame); 0: round 4's scan, which let such a slot into the new list alive (test switch)
-    int opt_vlist_one = 0;              // the view list's segment offsets and its concatenation in ONE launch (k_vlist_flatten: the last block publishes) instead of two; measured equal (1504 against 1503 frames/s in the driver-shaped window, tools/ab_driver.sh: a launch that only finds out that it has nothing to do costs the chain next to nothing when the next launch is already queued): off
     int opt_own_first_live = 1;         // sharded map: the reference's "surfel 0" is the lowest live creation number of any rank (ifx_map.hip FIRST_LIVE); 0: round 4's rule -- creation number 0 for ever (test switch)
-    int opt_vote_per_mask = 1;          // instance votes: one launch per mask, in mask order, as the reference (IF/Core/InstanceFusion.cpp:986-1000) -- the order is part of the result while a packed counter's low half is negative (ifx_instance.hip k_vote_update_all); 0: round 4's one launch over all masks (experiments only)
-    int opt_side_late = 0;              // a frame whose tracker ran ahead enqueues the announced next frame's side behind its own map passes instead of in front of them (measured: 1490 against 1510 frames/s -- the frame side then runs beside the next tracker instead of beside this frame's map passes; off)
     int opt_pace = 1;                   // ifx_enqueue_frame_device waits for the previous frame's result before it enqueues (bounded run-ahead)
-    int opt_ff_union = 1;               // flood fill of the masks: two-way edges merged by union-find before the directed relaxation (k_ff_merge)
     int opt_seg_aside = 1;              // a segmentation call that finds the next frame's tracker already queued on the main stream runs beside it on stream_c (the call is
                                         // synchronous for the host, so nothing has to join afterwards); ifx_instance / ifx_slic / ifx_knn enqueue on h->cur throughout
     hipEvent_t ev_result = nullptr;     // the `released` event of the slot of the last frame (recorded after k_frame_result)
@@ -350,10 +342,8 @@ struct ifx {
     std::string err;
     int tick = 1;
     int ids_pending = 0;
-    int opt_fold_finish = 1;            // view-list frames: the end-of-pass sums (dense test, whetherDoSegmentation) ride in k_splat_resolve instead of a launch of their own
     int ids_view_ok = 0;                // the cached view list still describes store and pose of the frame that drew the sparse id image (ifx_ids_ensure may walk it)
     int view_scan_tick = -1;            // frame whose view-list scan is already on the queue (the loop-closure renders come before the map passes)
-    int opt_lc_view = 1;                // loop-closure detection: its two renders from the view lists (one k_raster_view in dual mode) instead of a scan of the store + k_raster_list
     int opt_id_rule = 0;                // id renders of the unsharded map: 0 the ray-disc test with f32 depth keys, 1 the reference's screen-space quads with 24-bit depth (ifx_map.hip k_raster_quad)
     int opt_lazy_ids = 1;               // the frame renders the id image on the lattice whetherDoSegmentation samples; the whole image on demand (ifx_ids_ensure)
     int ids_full_valid = 1, ids_sparse_frame = 0;
@@ -364,14 +354,11 @@ struct ifx {
     int opt_compact_divisor = 8;        // housekeeping: compact when tombstones exceed count / divisor (or capacity gets tight)
     int opt_kernel_timing = 0;
     int opt_reference_passes = 0;   // also run the id renders nobody consumes (EF/ElasticFusion.cpp:679-680)
-    int opt_icp_px = 0;              // ICP and residual reductions on the same pixels of one thread, all loads in two batches (k_icp_residual_px; bits: 1 level 0, 2 levels 1-2, 4 one pixel per thread); measured slower: off
-    int opt_model_fused = 0;         // model pyramid of the frame tracker in one launch (k_model_pyr3) when the image size allows; measured equal to the three launches (28 vs 27 us): off
     int opt_gn_persist_blocks = 128;  // ... and only while its grid has at most this many blocks: the meetings cost grows with the blocks (75 at 160 x 120: faster; 300: slower)
     int opt_gn_persist = 0;          // bit i: all Gauss-Newton iterations of pyramid level i in one persistent launch (k_gn_level) when its grid fits the GPU.  Round 3's default was 4 (the coarsest level,
                                      // +1.4 %); with the solve in the next launch's prologue the two-launch form is within 0.7 % of it (profiles/r04_b_ab_gn_prologue*.txt), and a spinning grid barrier does
                                      // not belong on the default frame path for that: off.  As an option it is safe: a meeting that does not happen costs time, never the pose (k_gn_level_solo)
     int gn_max_blocks[4] = {0, 0, 0, 0};   // co-resident blocks of k_gn_level<1 | 2 | 3 | 4>
-    int opt_icp_lds = 0;             // level-0 ICP reduction on 64 x 16 tiles with the model maps staged in LDS (measured slower: DESIGN.md section 6)
     int opt_rgb_blocks = 0;          // cap on the blocks of the photometric step (0: 192)
     int opt_gn_prologue = 1;         // two-launch Gauss-Newton iterations: the 6x6 solve of iteration j runs in the prologue of EVERY block of iteration j + 1's first launch (no last-block
                                      // hand-off inside the photometric step's launch); 0: round 3's form, the last block of the photometric step solves and stores the pose
@@ -383,7 +370,6 @@ struct ifx {
     void* d_kexp = nullptr;            // ifx_owner_knn_export: [cap] float4 (x, y, z, creation number) + [cap] int32 labels
     int gn_begin_folded = 0;         // the start of the next frame-tracker run was done by the model side's last launch
     int labels_stale_all = 1;        // the next segmentation call re-scans the labels of ALL surfels (after create / upload / table eviction); otherwise only what the call can have changed
-    int opt_labels_incremental = 1;
     int opt_raster_lds = 0;          // view raster: per-wave depth test in LDS before the global atomics (k_raster_view<true>)
     int opt_view_blocks = 0, opt_clean_blocks = 0, opt_index_blocks = 0;   // grids of the view-list kernels (0: LIST_BLOCKS)
     int icp_resident_blocks = 1024;   // blocks of k_icp_residual the GPU holds at once (occupancy query at tracker allocation: 4 per CU x 256 CUs on MI355X)

@@ -964,12 +964,11 @@ static int mask_geometric_filter_device(ifx* h, const uint16_t* d_depth, uint8_t
         LAUNCH(h, "ff_prep", dim3(cdiv(std::max(nm * cdiv(h->w, FF_T) * cdiv(h->h, FF_T), nm * 32), 256)), dim3(256), k_ff_prep, a, (const uint8_t*)d_unavail, d_skip,
                nm * cdiv(h->w, FF_T) * cdiv(h->h, FF_T));
         LAUNCH(h, "ff_init", per_px, dim3(256), k_ff_init, a);
-        if (h->opt_ff_union) {   // the two-way edges by union-find: three launches for what took the relaxation a launch per tile border crossed
-            const int pairs = ((h->w - 1) / FF_T) * h->h + ((h->h - 1) / FF_T) * h->w;
-            LAUNCH(h, "ff_local", tiles, dim3(256), k_ff_tile_uf, a);
-            if (pairs > 0) LAUNCH(h, "ff_merge", dim3(cdiv(pairs, 256), nm), dim3(256), k_ff_merge, a);
-            LAUNCH(h, "ff_flatten", per_px, dim3(256), k_ff_flatten, a);
-        }
+        // the two-way edges by union-find: three launches for what took the relaxation a launch per tile border crossed
+        const int pairs = ((h->w - 1) / FF_T) * h->h + ((h->h - 1) / FF_T) * h->w;
+        LAUNCH(h, "ff_local", tiles, dim3(256), k_ff_tile_uf, a);
+        if (pairs > 0) LAUNCH(h, "ff_merge", dim3(cdiv(pairs, 256), nm), dim3(256), k_ff_merge, a);
+        LAUNCH(h, "ff_flatten", per_px, dim3(256), k_ff_flatten, a);
     }
     if (fixed_rounds > 0 && !resume) {
         if (fixed_rounds > FF_SLOTS) fixed_rounds = FF_SLOTS;
@@ -1306,7 +1305,7 @@ static int seg_host_mask_loop(ifx* h, int nm, const int32_t* class_ids, int m_st
 static int seg_label_scan(ifx* h, const int* gate = nullptr, bool default_done = false)
 {
     const int P = h->P;
-    if (h->opt_labels_incremental && !h->labels_stale_all) {
+    if (!h->labels_stale_all) {
         if (!default_done) LAUNCH(h, "colour_default", dim3(2048), dim3(256), k_colour_default, h->d_state, (const float2*)h->tm, (float2*)h->col, h->labels, gate);
         LAUNCH(h, "count_colour_px", dim3(cdiv(P, 256)), dim3(256), k_count_colour_px, h->d_state, h->ids_after, P, (const float4*)h->votes, h->cap, (const float2*)h->tm, (float2*)h->col,
                h->d_inst_color, h->labels, ifx_idmap(h), gate);
@@ -1496,68 +1495,36 @@ __global__ void k_seg_register(SegCtl* __restrict__ s, uint8_t* __restrict__ una
     for (int t = threadIdx.x; t < NI; t += blockDim.x) s->inst_class[t] = s_cls[t];
     for (int t = threadIdx.x; t < nm; t += blockDim.x) s->target[t] = s_tgt[t];
 }
-// updateSurfelMapInstance (IF/Core/InstanceFusionCuda.cu:1100-1150) for every mask with the instance the device chose for it; masks without one (or behind the
-// point where the host takes over) are passed over.  All masks in one launch: the update is a saturating add of a positive increment, so the masks' updates of a surfel commute (any order ends at
-// min(65535, count + sum of increments)) and a pixel can serve every mask it lies in at once
-// ONE launch per mask, in mask order (m_only >= 0), as the reference runs updateSurfelMapInstanceKernel once per mask (IF/Core/InstanceFusion.cpp:986-1000): the packed counters are lossy
+// updateSurfelMapInstance (IF/Core/InstanceFusionCuda.cu:1100-1150) for mask m with the instance the device chose for it; a mask without one (or behind the
+// point where the host takes over) is passed over.
+// ONE launch per mask, in mask order, as the reference runs updateSurfelMapInstanceKernel once per mask (IF/Core/InstanceFusion.cpp:986-1000): the packed counters are lossy
 // while a word's low half is negative (a surfel of the FIRST frame starts with -1 in every word, init_unstable.vert): each read-modify-write of the high half then loses 1 to
 // the borrow of the low one, until a vote for the low half's instance makes it non-negative.  How many votes a surfel keeps therefore depends on WHICH MASK comes first --
-// within a mask every update goes to the same half with the same weight and commutes, across masks it does not.  All masks in one launch (round 4: 18 us against ~3 us per
-// mask here) let the arrival order of the atomics decide: 3 of 373 297 surfels differed from the oracle on a young 640x480 map (tests/test_gpu_sweep.py, round 5).
-__global__ void k_vote_update_all(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const uint8_t* __restrict__ masks, int P, int cap, const SegCtl* __restrict__ s, int nm,
-                                  float* __restrict__ votes, IdMap im, int m_only)
+// within a mask every update goes to the same half with the same weight and commutes, across masks it does not.
+__global__ void k_vote_update_mask(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const uint8_t* __restrict__ masks, int P, int cap, const SegCtl* __restrict__ s, int nm,
+                                   float* __restrict__ votes, IdMap im, int m)
 {
     if (s->ff_incomplete) return;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
     const int last = s->evict_at >= 0 ? min(nm, s->evict_at) : nm;
-    if (m_only >= 0) {
-        if (m_only >= last || !(masks[(size_t)m_only * P + k] > 0)) return;
-        const int instanceID = s->target[m_only];
-        if (instanceID < 0) return;
-        const int id = idmap_slot(im, st->count, ids[k]);
-        if (id < 0) return;
-        const int fi = instanceID / 2, p = instanceID % 2, inc = m_only + 1;
-        unsigned int* addr = (unsigned int*)&VOTEF(votes, id, fi);
-        unsigned int old = *addr, assumed;
-        do {
-            assumed = old;
-            int a, b;
-            vote_decode(__uint_as_float(assumed), a, b);
-            if (p == 0) a += inc; else b += inc;
-            if (a >= 65535) a = 65535;
-            if (b >= 65535) b = 65535;
-            old = atomicCAS(addr, assumed, __float_as_uint(vote_encode(a, b)));
-        } while (old != assumed);
-        return;
-    }
-    unsigned int in = 0;   // (nm <= 256: eight words would cover it; the masks of a call are few -- handled 32 at a time)
-    int id = -2;
-    for (int m0 = 0; m0 < last; m0 += 32) {
-        in = 0;
-        const int mc = min(32, last - m0);
-        for (int j = 0; j < mc; j++) in |= (masks[(size_t)(m0 + j) * P + k] > 0 ? 1u : 0u) << j;
-        while (in) {
-            const int j = __ffs(in) - 1;
-            in &= in - 1;
-            const int m = m0 + j, instanceID = s->target[m];
-            if (instanceID < 0) continue;
-            if (id == -2) id = idmap_slot(im, st->count, ids[k]);
-            if (id < 0) return;
-            const int fi = instanceID / 2, p = instanceID % 2, inc = m + 1;
-            unsigned int* addr = (unsigned int*)&VOTEF(votes, id, fi);
-            unsigned int old = *addr, assumed;
-            do {
-                assumed = old;
-                int a, b;
-                vote_decode(__uint_as_float(assumed), a, b);
-                if (p == 0) a += inc; else b += inc;
-                if (a >= 65535) a = 65535;
-                if (b >= 65535) b = 65535;
-                old = atomicCAS(addr, assumed, __float_as_uint(vote_encode(a, b)));
-            } while (old != assumed);
-        }
-    }
+    if (m >= last || !(masks[(size_t)m * P + k] > 0)) return;
+    const int instanceID = s->target[m];
+    if (instanceID < 0) return;
+    const int id = idmap_slot(im, st->count, ids[k]);
+    if (id < 0) return;
+    const int fi = instanceID / 2, p = instanceID % 2, inc = m + 1;
+    unsigned int* addr = (unsigned int*)&VOTEF(votes, id, fi);
+    unsigned int old = *addr, assumed;
+    do {
+        assumed = old;
+        int a, b;
+        vote_decode(__uint_as_float(assumed), a, b);
+        if (p == 0) a += inc; else b += inc;
+        if (a >= 65535) a = 65535;
+        if (b >= 65535) b = 65535;
+        old = atomicCAS(addr, assumed, __float_as_uint(vote_encode(a, b)));
+    } while (old != assumed);
 }
 
 static int seg_ensure_ctl(ifx* h, size_t mask_bytes)
@@ -1607,7 +1574,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
     LAUNCH(h, "project_bbox_inst", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<1>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr, nm,
            h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)h->pc, h->d_pdm);
-    const bool default_early = h->opt_labels_incremental && !h->labels_stale_all;
+    const bool default_early = !h->labels_stale_all;
     if (default_early) LAUNCH(h, "colour_default", dim3(2048), dim3(256), k_colour_default, h->d_state, (const float2*)h->tm, (float2*)h->col, h->labels, (const int*)nullptr);
     if (flags & 2) { if ((r = ifx_superpixel_filter_prepare(h, nm))) return r; }
     if (!dm) memcpy(h->h_masks_stage, masks_in, mbytes);
@@ -1632,14 +1599,14 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     LAUNCH(h, "project_bbox_mask", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<2>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
            h->d_bbox, ifx_idmap(h));
     LAUNCH(h, "seg_compare", dim3(1), dim3(256), k_seg_compare, dc, (const int*)h->d_bbox, h->d_unavail);
-    const int rounds = h->opt_ff_rounds > 0 ? h->opt_ff_rounds : (h->opt_ff_union ? 4 : 24);   // (after the union-find start the first relaxation normally finds the fixpoint: the rest are spares for one-way edges)
+    const int rounds = h->opt_ff_rounds > 0 ? h->opt_ff_rounds : 4;   // (after the union-find start the first relaxation normally finds the fixpoint: the rest are spares for one-way edges)
     r = mask_geometric_filter_device(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm, h->d_unavail, rounds, false, true);
     if (r) return r;
     const FFArgs fa = ff_args(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm);
     const int* gate = fa.changed + (std::min(rounds, FF_SLOTS) - 1);
     LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, gate, (const int*)fa.meta, fa.skip);
-    for (int m_ = h->opt_vote_per_mask ? 0 : -1; m_ < (h->opt_vote_per_mask ? nm : 0); m_++)   // (mask order is part of the result: see k_vote_update_all)
-            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_all, h->d_state, h->ids_after, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
+    for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
+            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, h->ids_after, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
     // the scan kernels look at the control block themselves: when the call has to be finished by the host (fill incomplete / table full) they return at once and
     // the ONE scan of the call runs behind the host-driven tail, after every mask and the eviction -- colours are assigned once, so an early scan would be visible
     const int full_scan = seg_label_scan(h, (const int*)dc, default_early);
@@ -1655,8 +1622,8 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         r = mask_geometric_filter_device(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm, h->d_unavail, 0, true);
         if (r) return r;
         LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, (const int*)nullptr, (const int*)nullptr, (const uint8_t*)nullptr);
-        for (int m_ = h->opt_vote_per_mask ? 0 : -1; m_ < (h->opt_vote_per_mask ? nm : 0); m_++)   // (mask order is part of the result: see k_vote_update_all)
-            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_all, h->d_state, h->ids_after, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
+        for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
+            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, h->ids_after, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
         const int full2 = seg_label_scan(h, (const int*)dc);   // (gated again: the table may turn out full at some mask)
         HIPCHK(h, hipMemcpyAsync(hc, dc, sizeof(SegCtl), hipMemcpyDeviceToHost, h->cur));
         HIPCHK(h, hipMemcpyAsync(h_un, h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));

@@ -1532,7 +1532,7 @@ __global__ void k_vlist_decide(DevState* st, unsigned int* lctr, int force)
 {
     if (threadIdx.x != 0) return;
     if (force) st->vl_valid = 0;
-    vlist_decide(st, lctr);
+    vlist_decide(st);
 }
 
 // can the disc of a surfel at camera-frame position q (scan pose) touch the image from a pose within the margins?
@@ -1618,7 +1618,7 @@ __global__ __launch_bounds__(MAP_THREADS) void k_cull_frame(DevState* st, const 
                 // The rule of the frame BEING ENQUEUED is not applied here: the reference removes such a surfel at the END of that frame, and until then it can still be the
                 // map's first live surfel ("surfel 0", whose id reads 0).  A slot this list leaves out stays as it is -- invisible -- until the next scan finds it overdue;
                 // k_append_scan's first_live steps over it from the frame on in which the rule removes it (tests/test_gpu_sweep.py::test_surfel_0_outside_the_view_lists).
-                const bool overdue = wv > DEAD_TIME && time_prev >= 0 && age_rule_gone(wv, p4.w, time_prev, c);
+                const bool overdue = age_rule_gone(wv, p4.w, time_prev, c) && wv > DEAD_TIME;   // (the rule first: its leading test is uniform)
                 if (overdue) {
                     float4 q4 = p4;
                     q4.w = -1.0f;
@@ -1631,18 +1631,6 @@ __global__ __launch_bounds__(MAP_THREADS) void k_cull_frame(DevState* st, const 
                     if (in && wv > 0.f && (float)time - wv > (float)c.timeDelta) {   // outside the time window for good
                         in = false;
                         in_i = !(p4.w < c.conf);   // (>=: the INACTIVE splat of the loop-closure detection draws a surfel exactly AT the threshold, the id render tests > per entry)
-                    } else if (!in && time_prev < 0) {   // (option overdue_rule 0, round 4's scan: the age rule of THIS frame's clean pass, applied now, to the slots the list leaves out)
-                        int test = 1;
-                        if (wv == -1 || (((float)time - wv) > 20 && p4.w < c.conf)) test = 0;
-                        if (wv > 0 && (float)time - wv > (float)c.timeDelta) test = 1;
-                        if (!test) {
-                            float4 q4 = p4;
-                            q4.w = -1.0f;
-                            pc_rw[i] = q4;
-                            tm[i] = make_float2(t.x, DEAD_TIME);
-                            if (hot) { hot[i].pc = q4; hot[i].tm = make_float2(t.x, DEAD_TIME); }
-                            dead++;
-                        }
                     }
                 }
             }
@@ -1705,54 +1693,6 @@ __global__ __launch_bounds__(MAP_THREADS) void k_vlist_concat(const DevState* __
     const unsigned int* __restrict__ raw = (which ? raw_i : raw_a) + (size_t)seg * c.seg_cap;
     unsigned int* __restrict__ flat = (which ? flat_i : flat_a) + off;
     for (unsigned int t = (blockIdx.x / LIST_SEGS) * blockDim.x + threadIdx.x; t < n; t += blockDim.x * (gridDim.x / LIST_SEGS)) flat[t] = raw[t];
-}
-// The two launches above in one (option vlist_one; measured equal, off): every block adds up the eight segment counters of its list itself (the scan's atomics were performed at the
-// memory side: plain loads behind the kernel boundary see them), copies its share, and the block that finishes LAST re-arms the counters, publishes the lengths and moves
-// first_live on -- one launch less on the frame's chain.
-__global__ __launch_bounds__(MAP_THREADS) void k_vlist_flatten(DevState* st, Cam c, const float2* __restrict__ tm, const unsigned int* __restrict__ raw_a, const unsigned int* __restrict__ raw_i,
-                                                               unsigned int* __restrict__ flat_a, unsigned int* __restrict__ flat_i)
-{
-    if (!st->vl_scan) return;
-    const int which = blockIdx.y, seg = blockIdx.x % LIST_SEGS;
-    unsigned int n = 0, off = 0;
-#pragma unroll
-    for (int s_ = 0; s_ < LIST_SEGS; s_++) {
-        const unsigned int v = *list_ctr(c, 1 + which, s_);
-        off += s_ < seg ? v : 0u;
-        n = s_ == seg ? v : n;
-    }
-    const unsigned int* __restrict__ raw = (which ? raw_i : raw_a) + (size_t)seg * c.seg_cap;
-    unsigned int* __restrict__ flat = (which ? flat_i : flat_a) + off;
-    for (unsigned int t = (blockIdx.x / LIST_SEGS) * blockDim.x + threadIdx.x; t < n; t += blockDim.x * (gridDim.x / LIST_SEGS)) flat[t] = raw[t];
-    // the last block: everybody has read the counters (their values bound the loops above) before the ticket
-    __shared__ int s_last;
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned int t = __hip_atomic_fetch_add(&st->append_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (t == gridDim.x * gridDim.y - 1u);
-    }
-    __syncthreads();
-    if (!s_last || threadIdx.x != 0) return;
-    __hip_atomic_store(&st->append_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int w_ = 0; w_ < 2; w_++) {
-        unsigned int run = 0;
-        for (int s_ = 0; s_ < LIST_SEGS; s_++) {
-            unsigned int* ctr = list_ctr(c, 1 + w_, s_);
-            const unsigned int v = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the clean pass / the next scan
-            st->vl_seg_n[w_ * LIST_SEGS + s_] = v;
-            st->vl_seg_off[w_ * LIST_SEGS + s_] = run;
-            run += v;
-        }
-        st->vl_n[w_] = run;
-    }
-    {   // the scan applied the age rule to slots outside the list: the lowest live slot may have moved on
-        int f = st->first_live;
-        const int nn = st->count;
-        while (f < nn && !(tm[f].y > DEAD_TIME)) f++;
-        st->first_live = f;
-    }
 }
 
 // index-map projection (index_map.vert:40-66) of the view-list entries: the work of k_index_project on the slots that can be seen at all
@@ -2162,6 +2102,21 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
     }
 }
 
+// One walk of the cached view lists at the frame's pose and time (k_raster_view).  clean: the frame's clean pass and its new-surfel flags ride in the walk
+// (k_raster_view<., true>, with CleanArgs::nf_blocks blocks of k_new_flags_count's work in front of the walk's own); lds: the per-wave depth test in LDS.
+static void launch_raster_view(ifx* h, const char* name, const Cam& c, unsigned int want, int ids_step, bool lds, const CleanArgs* clean)
+{
+    const CleanArgs ca = clean ? *clean : CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const dim3 grid(ca.nf_blocks + (h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS));
+    auto go = [&](auto kernel) {
+        LAUNCH(h, name, grid, dim3(MAP_THREADS), kernel, h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, c, h->tick, h->tick, want, h->list_v, h->list_vi,
+               h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, ca, (const DevState*)h->d_state);
+    };
+    if (clean) go(k_raster_view<false, true>);
+    else if (lds) go(k_raster_view<true, false>);
+    else go(k_raster_view<false, false>);
+}
+
 // splat prediction (want & LIST_SPLAT) and / or id render (want & LIST_IDS) in one cull + one dense raster pass
 static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, unsigned int want, int32_t* ids_out, bool frame_sums = false, int part = 0, int old_target = 0,
                         bool fold_finish = false, int resolve_ids_step = 1, bool raw_ids = false)
@@ -2218,18 +2173,12 @@ static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, 
             ff.total = nullptr;
             h->result_folded = 1;
         }
-        if (raw_ids) {   // option clean_raster: the walk drew slot numbers
-            c.raw_slots = 2;
-            LAUNCH(h, "splat_resolve", dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_splat_resolve, h->d_state, d_pose_inv, h->key_splat, (const float4*)h->pc,
-                   (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)h->pred_vertex, (float4*)h->pred_normal,
-                   (uchar4*)h->pred_image, (uchar4*)h->pred_inst, h->pred_time, (float4*)h->fill_vertex, (float4*)h->fill_normal, (uchar4*)h->fill_image, h->key_ids,
-                   h->key_both, (want & LIST_IDS) ? ids_out : (int32_t*)nullptr, (int*)nullptr, ff, (float*)nullptr, resolve_ids_step, (const int32_t*)nullptr, fo, (const Hot*)h->frame_hot);
-            if (ff.acc) return;
-        } else
+        if (raw_ids) c.raw_slots = 2;   // option clean_raster: the walk drew slot numbers, and the resolve reads the frame's gathered records
         LAUNCH(h, "splat_resolve", dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_splat_resolve, h->d_state, d_pose_inv, h->key_splat, (const float4*)h->pc,
                (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)h->pred_vertex, (float4*)h->pred_normal,
                (uchar4*)h->pred_image, (uchar4*)h->pred_inst, h->pred_time, (float4*)h->fill_vertex, (float4*)h->fill_normal, (uchar4*)h->fill_image, h->key_ids,
-               h->key_both, (want & LIST_IDS) ? ids_out : (int32_t*)nullptr, (int*)nullptr, ff, (float*)nullptr, resolve_ids_step, (const int32_t*)nullptr, fo);
+               h->key_both, (want & LIST_IDS) ? ids_out : (int32_t*)nullptr, (int*)nullptr, ff, (float*)nullptr, resolve_ids_step, (const int32_t*)nullptr, fo,
+               raw_ids ? (const Hot*)h->frame_hot : (const Hot*)nullptr);
         if (ff.acc) return;   // (the view-list pass leaves list 0 alone: nothing to re-arm)
     } else if (want & LIST_IDS) LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, ids_out);
     // dense flag, list re-arm and (frame path: the id image is ids_after) the whetherDoSegmentation sums
@@ -2295,8 +2244,7 @@ int ifx_ids_ensure(ifx* h)
     if (h->ids_view_ok && !h->own && !h->opt_id_rule) {   // nothing touched the store, the pose or the cached view list since the frame drew its lattice from it: the rest of the image from the same list
         Cam c = make_cam(h);
         c.srank = 0; c.sn = 1;
-        LAUNCH(h, "raster_view_ids", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<false, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
-               (const float2*)h->tm, c, h->tick, h->tick, LIST_IDS, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, 1, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
+        launch_raster_view(h, "raster_view_ids", c, LIST_IDS, 1, false, nullptr);
         LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, h->ids_after);
     } else
         ids_pass(h, nullptr, 0, h->ids_after);   // (all slots, per-pass cull: unstable surfels -- the only ones the view list's age rule concerns -- are never drawn here)
@@ -2933,6 +2881,21 @@ __global__ void k_adopt_est_pose(DevState* st)
     st->vl_valid = 0;   // another pose, and a deformation follows (positions move): the frame takes the per-pass culls, the list is rebuilt next frame
 }
 
+// The new surfels of a frame: k_new_flags_count marks the measurement pixels that become surfels and counts them per block, k_append_scan appends them to the store -- and
+// to the view list `list` while one is valid (null: none); hot: the frame's gathered records, kept coherent (option hot_records).
+static void launch_new_flags_count(ifx* h, const float* d_pose_inv, const Cam& c, int time)
+{
+    LAUNCH(h, "new_flags_count", dim3(cdiv(h->P, NEW_PER_BLOCK)), dim3(256), k_new_flags_count, h->d_state, d_pose_inv, c, time, h->assoc_target, (const float4*)h->meas_pc,
+           (const float4*)h->meas_nr, (const float4*)h->index_tap, h->scan_flags, h->scan_block);
+}
+static void launch_append_scan(ifx* h, const Cam& c, int time, unsigned int* list, Hot* hot = nullptr)
+{
+    const int nb_new = cdiv(h->P, NEW_PER_BLOCK);
+    LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, time, time, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
+           (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
+           h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, list, h->labels, h->seq, hot);
+}
+
 // the first clean pass that sees the store as an upload / a jump of the clock left it: from here on the age rule counts (age_rule_gone)
 static inline void age_epoch_begin(ifx* h, int time) { if (h->age_epoch == INT_MAX) h->age_epoch = time; }
 static void clean_pass(ifx* h, const float* d_pose_inv, int time, int part = 0)
@@ -2961,12 +2924,8 @@ static void clean_pass(ifx* h, const float* d_pose_inv, int time, int part = 0)
                     (const float4*)h->old_vertex, (float4*)h->pc, (float4*)h->nr, (float2*)h->tm);
         h->graph_nodes = 0;   // rawGraph lives for one frame (EF/ElasticFusion.cpp:482)
     }
-    const int nb_new = cdiv(h->P, NEW_PER_BLOCK);
-    LAUNCH(h, "new_flags_count", dim3(nb_new), dim3(256), k_new_flags_count, h->d_state, d_pose_inv, c, time, h->assoc_target, (const float4*)h->meas_pc, (const float4*)h->meas_nr,
-           (const float4*)h->index_tap, h->scan_flags, h->scan_block);
-    LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, time, time, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
-           (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
-           h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, h->own ? (unsigned int*)nullptr : h->list_v, h->labels, h->seq);
+    launch_new_flags_count(h, d_pose_inv, c, time);
+    launch_append_scan(h, c, time, h->own ? (unsigned int*)nullptr : h->list_v);
     // the new surfels were never associated: clear the arbitration words nobody reset (losing pixels)
 }
 
@@ -2984,11 +2943,7 @@ static void view_scan(ifx* h, int time)
     // raw output in the clean pass's lists 1, 2 (free at this point of a frame and between frames), then concatenated into list_v / list_vi
     LAUNCH(h, "cull_frame", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_frame, h->d_state, (const float4*)h->pc, (float4*)h->pc, (float2*)h->tm, c, make_planes(c), time, h->list_b, h->list_c,
            h->hot_valid ? (Hot*)h->hot : (Hot*)nullptr,   // (the age rule's tombstones go into the gathered copy too while it is valid)
-           h->opt_overdue_rule ? std::max(0, std::min(time, h->last_clean_time)) : -1);   // (the last clean pass any list can have run: the age rule unlisted slots have outlived since)
-    if (h->opt_vlist_one) {
-        LAUNCH(h, "vlist_flatten", dim3(256, 2), dim3(MAP_THREADS), k_vlist_flatten, h->d_state, c, (const float2*)h->tm, h->list_b, h->list_c, h->list_v, h->list_vi);
-        return;
-    }
+           std::max(0, std::min(time, h->last_clean_time)));   // (the last clean pass any list can have run: the age rule unlisted slots have outlived since)
     LAUNCH(h, "vlist_offsets", dim3(1), dim3(64), k_vlist_offsets, h->d_state, c, (const float2*)h->tm);
     LAUNCH(h, "vlist_concat", dim3(256, 2), dim3(MAP_THREADS), k_vlist_concat, (const DevState*)h->d_state, c, h->list_b, h->list_c, h->list_v, h->list_vi);
 }
@@ -3024,12 +2979,8 @@ static void view_clean_append(ifx* h, const Cam& c, int time)
     h->hot_valid = 0;
     LAUNCH(h, "clean_view", dim3(h->opt_clean_blocks > 0 ? h->opt_clean_blocks : 2 * LIST_BLOCKS), dim3(MAP_THREADS), k_clean_view, h->d_state, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm,
            (const float4*)h->index_tap, h->list_v);
-    const int nb_new = cdiv(h->P, NEW_PER_BLOCK);
-    LAUNCH(h, "new_flags_count", dim3(nb_new), dim3(256), k_new_flags_count, h->d_state, (const float*)nullptr, c, time, h->assoc_target, (const float4*)h->meas_pc,
-           (const float4*)h->meas_nr, (const float4*)h->index_tap, h->scan_flags, h->scan_block);
-    LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, time, time, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
-           (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
-           h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, h->own ? (unsigned int*)nullptr : h->list_v, h->labels, h->seq);
+    launch_new_flags_count(h, nullptr, c, time);
+    launch_append_scan(h, c, time, h->own ? (unsigned int*)nullptr : h->list_v);
 }
 
 // EF/ElasticFusion.cpp:620-694 without the loop-closure branches
@@ -3097,12 +3048,11 @@ int ifx_map_predict_loop_closure(ifx* h)
     // both renders see the same map at the same pose and differ only in the time window: one scan of the store, one raster launch (two key images)
     Cam c = make_cam(h);
     c.srank = 0; c.sn = 1;
-    const bool by_view = use_view_list(h) && h->opt_lc_view;
+    const bool by_view = use_view_list(h);
     if (by_view) {   // the frame's view lists hold every stable surfel in view, inside the time window or not: the scan this frame needs anyway, taken first
         view_scan(h, h->tick);
         h->view_scan_tick = h->tick;
-        LAUNCH(h, "raster_view_lc", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<false, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
-               (const float2*)h->tm, c, h->tick, h->tick, LIST_SPLAT | LIST_DUAL, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, 1, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
+        launch_raster_view(h, "raster_view_lc", c, LIST_SPLAT | LIST_DUAL, 1, false, nullptr);
     } else {
     LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, (const float*)nullptr, (const float4*)h->pc, (const float2*)h->tm, c, h->tick, h->tick,
            LIST_SPLAT | LIST_DUAL, h->list_a, (unsigned int*)nullptr, 0);
@@ -3124,8 +3074,7 @@ int ifx_map_predict_loop_closure(ifx* h)
 // ElasticFusion::predict, EF/ElasticFusion.cpp:729-763, fused with renderSurfelIds(GENERAL_AFTER) of :694
 int ifx_map_predict(ifx* h)
 {
-    static const bool no_ids = getenv("IFX_EXPERIMENT_NO_IDS") != nullptr;   // measurement only: what the per-frame id render costs (the id image is then stale)
-    const unsigned int want = LIST_SPLAT | ((h->ids_pending && !no_ids) ? LIST_IDS : 0u);
+    const unsigned int want = LIST_SPLAT | (h->ids_pending ? LIST_IDS : 0u);
     const unsigned int want_walk = (h->opt_id_rule && !h->own) ? (want & ~LIST_IDS) : want;   // option id_rule: the walk draws the splat half, raster_pass adds k_raster_quad's ids
     // the tiled rasteriser only on request: at 1280x960 / 20 M surfels the view-list rasteriser takes 455 us where cull + bin + tile raster take 744 (profiles/archive/r02_o_1280_20m.txt)
     const bool tiles = h->opt_raster_tiles > 0;
@@ -3145,20 +3094,12 @@ int ifx_map_predict(ifx* h)
             CleanArgs ca;
             ca.pc_rw = (float4*)h->pc; ca.tm_rw = (float2*)h->tm; ca.tap = (const float4*)h->index_tap; ca.nf_blocks = nb_new; ca.assoc = h->assoc_target; ca.mpc = (const float4*)h->meas_pc;
             ca.mnr = (const float4*)h->meas_nr; ca.flags = h->scan_flags; ca.block_counts = h->scan_block; ca.hot = (Hot*)h->frame_hot;
-            LAUNCH(h, "clean_raster_view", dim3(nb_new + (h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS)), dim3(MAP_THREADS), (k_raster_view<false, true>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
-                   (const float2*)h->tm, c, h->tick, h->tick, want_walk, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, ca, (const DevState*)h->d_state);
-            LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, h->tick, h->tick, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
-                   (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
-                   h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, h->list_v, h->labels, h->seq, (Hot*)h->frame_hot);
-            raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, h->opt_fold_finish != 0, ids_step, true);
+            launch_raster_view(h, "clean_raster_view", c, want_walk, ids_step, false, &ca);
+            launch_append_scan(h, c, h->tick, h->list_v, (Hot*)h->frame_hot);
+            raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, true, ids_step, true);
         } else {
-        if (h->opt_raster_lds)
-            LAUNCH(h, "raster_view", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<true, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, c, h->tick, h->tick,
-                   want_walk, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
-        else
-            LAUNCH(h, "raster_view", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<false, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, c, h->tick, h->tick,
-                   want_walk, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);
-        raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, h->opt_fold_finish != 0, ids_step);   // resolve + the end-of-pass sums in the same launch
+            launch_raster_view(h, "raster_view", c, want_walk, ids_step, h->opt_raster_lds != 0, nullptr);
+            raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, true, ids_step);   // resolve + the end-of-pass sums in the same launch
         }
     } else {
         if (h->clean_raster_pending) {   // (the host-side conditions of the two functions are the same: never) -- the deferred passes as launches of their own
@@ -3413,9 +3354,7 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
             ca.mnr = (const float4*)h->meas_nr; ca.flags = h->scan_flags; ca.block_counts = h->scan_block; ca.hot = nullptr;
             LAUNCH(h, "clean_raster_view", dim3(nb_new + (h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS)), dim3(MAP_THREADS), (k_raster_view<false, true>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
                    (const float2*)h->tm, c, time, time, LIST_SPLAT | LIST_IDS, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, 0, lat ? OWN_LAT_DS : 1, ca, (const DevState*)h->d_state);
-            LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, time, time, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
-                   (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
-                   h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, h->list_v, h->labels, h->seq);
+            launch_append_scan(h, c, time, h->list_v);
             h->last_clean_time = time;
             h->view_dirty = 1;
             h->own_fast_raster = h->own_fast;
@@ -3426,11 +3365,8 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
         else
         LAUNCH(h, "clean_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_clean_list, h->d_state, (const float*)nullptr, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm,
                (const float4*)h->index_tap, h->list_b, h->list_c);
-        LAUNCH(h, "new_flags_count", dim3(nb_new), dim3(256), k_new_flags_count, h->d_state, (const float*)nullptr, c, time, h->assoc_target, (const float4*)h->meas_pc,
-               (const float4*)h->meas_nr, (const float4*)h->index_tap, h->scan_flags, h->scan_block);
-        LAUNCH(h, "append_scan", dim3(nb_new), dim3(256), k_append_scan, h->d_state, c, time, time, h->scan_flags, h->scan_block, nb_new, (const float4*)h->meas_pc,
-               (const float4*)h->meas_nr, h->meas_col, h->cap, (float4*)h->pc, (float4*)h->nr, (float2*)h->col, (float2*)h->tm, (float4*)h->ic, (float4*)h->votes,
-               h->inst_gt_on ? (const uint8_t*)h->d_inst_gt : (const uint8_t*)nullptr, h->view_frame ? h->list_v : (unsigned int*)nullptr, h->labels, h->seq);
+        launch_new_flags_count(h, nullptr, c, time);
+        launch_append_scan(h, c, time, h->view_frame ? h->list_v : (unsigned int*)nullptr);
         h->last_clean_time = time;
         if (h->view_frame) h->view_dirty = 1;
         if (h->opt_compact_every_frame) ifx_compact_enqueue(h, 0);

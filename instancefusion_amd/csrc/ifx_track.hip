@@ -371,158 +371,6 @@ __global__ void k_model_down(const DevState* __restrict__ st, const float* __res
     model_tail(st, x, y, dw, dh, res[0], res[1], z, o);
 }
 
-// ---- the model side of the frame tracker in ONE launch: levels 0, 1 and 2 of k_model_l0 / k_model_down for an image whose width is a multiple
-// of 32 and height a multiple of 16.  A block owns an 8 x 4 tile of level 2, i.e. 16 x 8 of level 1 and 32 x 16 of level 0; what the two 5 x 5
-// Gaussian pyr-downs read beyond the tile (level-1 region 19 x 11, level-0 region 41 x 25: depth and intensity only) is recomputed into LDS
-// from the prediction images, the 2 x 2 map resizes chain through LDS.  Same per-pixel arithmetic, same
-// clipped windows: the pyramids are bit-identical to the three launches (tests/test_gpu_parity.py::test_tracker_gputest_pair compares every
-// buffer with the oracle).  Three dependent launches (6.7 + 9.8 + 9.8 us) become one.
-#define MP_R0W 41
-#define MP_R0H 25
-#define MP_R1W 19
-#define MP_R1H 11
-template <typename FD, typename FI>
-__device__ __forceinline__ void pyr_gauss5(int x, int y, int sw, int sh, FD depth_at, FI img_at, float& z, uint8_t& lum)
-{
-    const int D = 5;
-    const int tx = min(2 * x - D / 2 + D, sw - 1), ty = min(2 * y - D / 2 + D, sh - 1);
-    float sumf = 0, sumi = 0;
-    int cntf = 0, cnti = 0;
-    for (int cy = max(0, 2 * y - D / 2); cy < ty; ++cy)
-        for (int cx = max(0, 2 * x - D / 2); cx < tx; ++cx) {
-            const float g = c_gauss25[(ty - cy - 1) * 5 + (tx - cx - 1)];
-            const float sf = depth_at(cx, cy);      // pyrDownKernelGaussF :332-363
-            if (!(sf != sf)) { sumf += sf * g; cntf += (int)g; }
-            const int si = img_at(cx, cy);          // pyrDownKernelIntensityGauss :470-500
-            if (si > 0) { sumi += si * g; cnti += (int)g; }
-        }
-    z = (float)(sumf / (float)cntf);
-    lum = cnti ? (uint8_t)f2i_rz(sumi / (float)cnti) : (uint8_t)0;
-}
-__device__ __forceinline__ v3 resize4(float a00, float a01, float a10, float a11, float b00, float b01, float b10, float b11, float c00, float c01, float c10, float c11, bool norm_it)
-{
-    const float qn = qnan_f();
-    v3 n = v3m(qn, qn, qn);
-    if (!((a00 != a00) || (a01 != a01) || (a10 != a10) || (a11 != a11))) {   // resizeMapKernel<normalize>, EF/Cuda/cudafuncs.cu:365-416 (the test looks at the x plane only)
-        n.x = (a00 + a01 + a10 + a11) / 4;
-        n.y = (b00 + b01 + b10 + b11) / 4;
-        n.z = (c00 + c01 + c10 + c11) / 4;
-        if (norm_it) n = normalized(n);
-    }
-    return n;
-}
-struct ModelOut3 { ModelOut l[3]; };
-#ifdef IFX_EXPERIMENTS
-__global__ __launch_bounds__(256) void k_model_pyr3(const DevState* __restrict__ st, const float* __restrict__ pv, const float* __restrict__ pn, const uint8_t* __restrict__ pi,
-                                                    const float* __restrict__ fv, const float* __restrict__ fn, const uint8_t* __restrict__ fi, int w, int h, float cutoff, ModelOut3 o)
-{
-    __shared__ float s_d0[MP_R0H][MP_R0W];
-    __shared__ uint8_t s_i0[MP_R0H][MP_R0W];
-    __shared__ float s_d1[MP_R1H][MP_R1W];
-    __shared__ uint8_t s_i1[MP_R1H][MP_R1W];
-    __shared__ float s_v0[6][16][33];  // level-0 vertex (0..2) and normal (3..5) of the tile (padded rows)
-    __shared__ float s_v1[6][8][16];   // level-1 vertex (0..2) and normal (3..5) of the tile
-    const int tid = threadIdx.x;
-    const int w1 = w / 2, h1 = h / 2, w2 = w / 4, h2 = h / 4;
-    const int x2_0 = blockIdx.x * 8, y2_0 = blockIdx.y * 4, x1_0 = 2 * x2_0, y1_0 = 2 * y2_0, x0_0 = 2 * x1_0, y0_0 = 2 * y1_0;
-    const int r1x = x1_0 - 2, r1y = y1_0 - 2;   // origin of the level-1 region
-    const int r0x = x0_0 - 6, r0y = y0_0 - 6;   // origin of the level-0 region
-    const bool fill = fv && !st->dense_enough;
-    const float* sv = fill ? fv : pv;
-    const float* sn = fill ? fn : pn;
-    const uint8_t* si = fill ? fi : pi;
-    const float qn = qnan_f();
-    // ---- level 0, depth and intensity of the region (k_model_l0's z and luminance)
-    for (int t = tid; t < MP_R0W * MP_R0H; t += 256) {
-        const int ly = t / MP_R0W, lx = t - ly * MP_R0W, x = r0x + lx, y = r0y + ly;
-        float z = qn;
-        uint8_t lum = 0;
-        if (x >= 0 && x < w && y >= 0 && y < h) {
-            const float vz = sv[(size_t)(y * w + x) * 4 + 2];
-            const uint8_t* s = si + (size_t)(y * w + x) * 4;
-            z = (vz > cutoff || vz <= 0) ? qn : vz;
-            lum = (uint8_t)(int)((float)s[0] * 0.114f + (float)s[1] * 0.299f + (float)s[2] * 0.587f);
-        }
-        s_d0[ly][lx] = z;
-        s_i0[ly][lx] = lum;
-    }
-    __syncthreads();
-    // ---- level 0 of the tile: two pixels per thread, row-major (coalesced loads and stores); vertex and normal also go to LDS for the 2 x 2 resize
-    auto d0_at = [&](int cx, int cy) { return s_d0[cy - r0y][cx - r0x]; };
-    auto i0_at = [&](int cx, int cy) { return (int)s_i0[cy - r0y][cx - r0x]; };
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int t = tid + u * 256, lx = t & 31, ly = t >> 5, x = x0_0 + lx, y = y0_0 + ly;
-        const float4 v = reinterpret_cast<const float4*>(sv)[y * w + x];
-        const float4 n = reinterpret_cast<const float4*>(sn)[y * w + x];
-        const bool ok = !(v.z == 0);
-        const v3 vs = v3m(ok ? v.x : qn, ok ? v.y : qn, ok ? v.z : qn), ns = v3m(ok ? n.x : qn, ok ? n.y : qn, ok ? n.z : qn);
-        const ModelOut& o0 = o.l[0];
-        o0.vcam[y * w + x] = vs.x; o0.vcam[(y + h) * w + x] = vs.y; o0.vcam[(y + 2 * h) * w + x] = vs.z;
-        o0.ncam[y * w + x] = ns.x; o0.ncam[(y + h) * w + x] = ns.y; o0.ncam[(y + 2 * h) * w + x] = ns.z;
-        const float z = s_d0[y - r0y][x - r0x];
-        o0.depth[y * w + x] = z;
-        o0.img[y * w + x] = s_i0[y - r0y][x - r0x];
-        model_tail(st, x, y, w, h, vs, ns, z, o0);
-        s_v0[0][ly][lx] = vs.x; s_v0[1][ly][lx] = vs.y; s_v0[2][ly][lx] = vs.z;
-        s_v0[3][ly][lx] = ns.x; s_v0[4][ly][lx] = ns.y; s_v0[5][ly][lx] = ns.z;
-    }
-    __syncthreads();
-    // ---- threads 0..127: level-1 pixel (lx1, ly1) of the tile; 128..255: level-1 depth / intensity of the halo
-    if (tid < 128) {
-        const int lx1 = tid & 15, ly1 = tid >> 4, x1 = x1_0 + lx1, y1 = y1_0 + ly1;
-        const int ax = 2 * lx1, ay = 2 * ly1;
-        const v3 v1 = resize4(s_v0[0][ay][ax], s_v0[0][ay][ax + 1], s_v0[0][ay + 1][ax], s_v0[0][ay + 1][ax + 1], s_v0[1][ay][ax], s_v0[1][ay][ax + 1], s_v0[1][ay + 1][ax], s_v0[1][ay + 1][ax + 1],
-                              s_v0[2][ay][ax], s_v0[2][ay][ax + 1], s_v0[2][ay + 1][ax], s_v0[2][ay + 1][ax + 1], false);
-        const v3 n1 = resize4(s_v0[3][ay][ax], s_v0[3][ay][ax + 1], s_v0[3][ay + 1][ax], s_v0[3][ay + 1][ax + 1], s_v0[4][ay][ax], s_v0[4][ay][ax + 1], s_v0[4][ay + 1][ax], s_v0[4][ay + 1][ax + 1],
-                              s_v0[5][ay][ax], s_v0[5][ay][ax + 1], s_v0[5][ay + 1][ax], s_v0[5][ay + 1][ax + 1], true);
-        float z1;
-        uint8_t l1;
-        pyr_gauss5(x1, y1, w, h, d0_at, i0_at, z1, l1);
-        const ModelOut& o1 = o.l[1];
-        o1.vcam[y1 * w1 + x1] = v1.x; o1.vcam[(y1 + h1) * w1 + x1] = v1.y; o1.vcam[(y1 + 2 * h1) * w1 + x1] = v1.z;
-        o1.ncam[y1 * w1 + x1] = n1.x; o1.ncam[(y1 + h1) * w1 + x1] = n1.y; o1.ncam[(y1 + 2 * h1) * w1 + x1] = n1.z;
-        o1.depth[y1 * w1 + x1] = z1;
-        o1.img[y1 * w1 + x1] = l1;
-        model_tail(st, x1, y1, w1, h1, v1, n1, z1, o1);
-        s_d1[y1 - r1y][x1 - r1x] = z1;
-        s_i1[y1 - r1y][x1 - r1x] = l1;
-        s_v1[0][ly1][lx1] = v1.x; s_v1[1][ly1][lx1] = v1.y; s_v1[2][ly1][lx1] = v1.z;
-        s_v1[3][ly1][lx1] = n1.x; s_v1[4][ly1][lx1] = n1.y; s_v1[5][ly1][lx1] = n1.z;
-    } else {
-        // the 19 x 11 level-1 region minus the 16 x 8 tile: 81 pixels
-        for (int t = tid - 128; t < MP_R1W * MP_R1H; t += 128) {
-            const int ly = t / MP_R1W, lx = t - ly * MP_R1W, x1 = r1x + lx, y1 = r1y + ly;
-            if (lx >= 2 && lx < 18 && ly >= 2 && ly < 10) continue;   // the tile itself (threads 0..127)
-            float z1 = qn;
-            uint8_t l1 = 0;
-            if (x1 >= 0 && x1 < w1 && y1 >= 0 && y1 < h1) pyr_gauss5(x1, y1, w, h, d0_at, i0_at, z1, l1);
-            s_d1[ly][lx] = z1;
-            s_i1[ly][lx] = l1;
-        }
-    }
-    __syncthreads();
-    // ---- level 2: 32 pixels
-    if (tid < 32) {
-        const int lx2 = tid & 7, ly2 = tid >> 3, x2 = x2_0 + lx2, y2 = y2_0 + ly2;
-        const int ax = 2 * lx2, ay = 2 * ly2;
-        const v3 v2 = resize4(s_v1[0][ay][ax], s_v1[0][ay][ax + 1], s_v1[0][ay + 1][ax], s_v1[0][ay + 1][ax + 1], s_v1[1][ay][ax], s_v1[1][ay][ax + 1], s_v1[1][ay + 1][ax], s_v1[1][ay + 1][ax + 1],
-                              s_v1[2][ay][ax], s_v1[2][ay][ax + 1], s_v1[2][ay + 1][ax], s_v1[2][ay + 1][ax + 1], false);
-        const v3 n2 = resize4(s_v1[3][ay][ax], s_v1[3][ay][ax + 1], s_v1[3][ay + 1][ax], s_v1[3][ay + 1][ax + 1], s_v1[4][ay][ax], s_v1[4][ay][ax + 1], s_v1[4][ay + 1][ax], s_v1[4][ay + 1][ax + 1],
-                              s_v1[5][ay][ax], s_v1[5][ay][ax + 1], s_v1[5][ay + 1][ax], s_v1[5][ay + 1][ax + 1], true);
-        float z2;
-        uint8_t l2;
-        pyr_gauss5(x2, y2, w1, h1, [&](int cx, int cy) { return s_d1[cy - r1y][cx - r1x]; }, [&](int cx, int cy) { return (int)s_i1[cy - r1y][cx - r1x]; }, z2, l2);
-        const ModelOut& o2 = o.l[2];
-        o2.vcam[y2 * w2 + x2] = v2.x; o2.vcam[(y2 + h2) * w2 + x2] = v2.y; o2.vcam[(y2 + 2 * h2) * w2 + x2] = v2.z;
-        o2.ncam[y2 * w2 + x2] = n2.x; o2.ncam[(y2 + h2) * w2 + x2] = n2.y; o2.ncam[(y2 + 2 * h2) * w2 + x2] = n2.z;
-        o2.depth[y2 * w2 + x2] = z2;
-        o2.img[y2 * w2 + x2] = l2;
-        model_tail(st, x2, y2, w2, h2, v2, n2, z2, o2);
-    }
-}
-#endif   // IFX_EXPERIMENTS
-
 // ======================================================================= reductions (a4-a7)
 
 #define RED_THREADS 256
@@ -807,79 +655,6 @@ __device__ __forceinline__ void icp_body(int bid, int nblk, const DevState* __re
     }
     block_sum_exact<29>(acc, gacc, bid % IFX_ACC_REPL);
 }
-// The north star's "LDS-staged depth / normal tiles for the ICP reduction", as an option (ifx_set_option("icp_lds", 1); level 0 only):
-// a block owns a 64 x 16 pixel tile, stages the model's vertex and normal maps of the tile plus an 8-pixel halo in LDS (80 x 32 x 24 B =
-// 60 KB, coalesced row loads) and takes a correspondence from LDS when it falls inside, from global memory otherwise.  Same values, same
-// exact sums: bit-identical results.  MEASURED: slower than the plain gathers -- a frame's motion is a few pixels, so
-// neighbouring pixels already gather neighbouring model texels through L1 / L2, and the staging reads 2.5x the bytes the gathers touch.
-#define LT_W 64
-#define LT_H 16
-#define LT_HALO 8
-#define LT_SW (LT_W + 2 * LT_HALO)
-#define LT_SH (LT_H + 2 * LT_HALO)
-#ifdef IFX_EXPERIMENTS
-__device__ __forceinline__ void icp_body_lds(int bid, const DevState* __restrict__ st, const float* __restrict__ vmap_curr, const float* __restrict__ nmap_curr,
-                                             const float* __restrict__ vmap_prev, const float* __restrict__ nmap_prev, float fx, float fy, float cx, float cy,
-                                             float distThres, float angleThres, int w, int h, double* __restrict__ gacc)
-{
-    __shared__ float s_m[6][LT_SH][LT_SW];
-    float Rcurr[9], Rprev_inv[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) { Rcurr[k] = st->Rcurr[k]; Rprev_inv[k] = st->Rprev_inv[k]; }
-    const v3 tc = v3m(st->tcurr[0], st->tcurr[1], st->tcurr[2]), tp = v3m(st->tprev[0], st->tprev[1], st->tprev[2]);
-    const int N = w * h, tiles_x = (w + LT_W - 1) / LT_W;
-    const int x0 = (bid % tiles_x) * LT_W, y0 = (bid / tiles_x) * LT_H;
-    for (int idx = threadIdx.x; idx < LT_SW * LT_SH; idx += RED_THREADS) {
-        const int ly = idx / LT_SW, lx = idx - ly * LT_SW, gx = x0 - LT_HALO + lx, gy = y0 - LT_HALO + ly;
-        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-            const int g = gy * w + gx;
-#pragma unroll
-            for (int q = 0; q < 3; q++) { s_m[q][ly][lx] = vmap_prev[g + q * N]; s_m[3 + q][ly][lx] = nmap_prev[g + q * N]; }
-        }
-    }
-    __syncthreads();
-    double acc[29];
-#pragma unroll
-    for (int k = 0; k < 29; k++) acc[k] = 0.0;
-    const int tx = threadIdx.x & (LT_W - 1), ty0 = threadIdx.x >> 6;   // 256 threads = 64 columns x 4 rows, 4 rounds of rows
-#pragma unroll
-    for (int u = 0; u < LT_H / 4; u++) {
-        const int px = x0 + tx, py = y0 + ty0 + 4 * u;
-        float row[7] = {0, 0, 0, 0, 0, 0, 0};
-        bool found = false;
-        if (px < w && py < h) {
-            const int i = py * w + px;
-            const v3 vcurr = v3m(vmap_curr[i], vmap_curr[i + N], vmap_curr[i + 2 * N]), ncurr = v3m(nmap_curr[i], nmap_curr[i + N], nmap_curr[i + 2 * N]);
-            const v3 vcurr_g = mulp(Rcurr, vcurr) + tc;
-            const v3 vcurr_cp = mulp(Rprev_inv, vcurr_g - tp);
-            const int ux = f2i_rn(vcurr_cp.x * fx / vcurr_cp.z + cx), uy = f2i_rn(vcurr_cp.y * fy / vcurr_cp.z + cy);
-            const bool inb = !(vcurr.x != vcurr.x) && !(ux < 0 || uy < 0 || ux >= w || uy >= h || vcurr_cp.z < 0);
-            if (inb) {
-                v3 vprev, nprev;
-                const int lx = ux - x0 + LT_HALO, ly = uy - y0 + LT_HALO;
-                if (lx >= 0 && lx < LT_SW && ly >= 0 && ly < LT_SH) {
-                    vprev = v3m(s_m[0][ly][lx], s_m[1][ly][lx], s_m[2][ly][lx]);
-                    nprev = v3m(s_m[3][ly][lx], s_m[4][ly][lx], s_m[5][ly][lx]);
-                } else {
-                    const int j = uy * w + ux;
-                    vprev = v3m(vmap_prev[j], vmap_prev[j + N], vmap_prev[j + 2 * N]);
-                    nprev = v3m(nmap_prev[j], nmap_prev[j + N], nmap_prev[j + 2 * N]);
-                }
-                const v3 ncurr_g = mulp(Rcurr, ncurr);
-                const float dist = norm(vprev - vcurr_g), sine = norm(cross(ncurr_g, nprev));
-                found = (sine < angleThres && dist <= distThres && !(ncurr.x != ncurr.x) && !(nprev.x != nprev.x));
-                if (found) {
-                    const v3 s_cp = mulp(Rprev_inv, vcurr_g - tp), d_cp = mulp(Rprev_inv, vprev - tp), n_cp = mulp(Rprev_inv, nprev), c = cross(s_cp, n_cp);
-                    row[0] = n_cp.x; row[1] = n_cp.y; row[2] = n_cp.z; row[3] = c.x; row[4] = c.y; row[5] = c.z;
-                    row[6] = dot(n_cp, s_cp - d_cp);
-                }
-            }
-        }
-        products7<0>(row, found, acc);
-    }
-    block_sum_exact<29>(acc, gacc, bid % IFX_ACC_REPL);
-}
-#endif   // IFX_EXPERIMENTS
 
 __global__ __launch_bounds__(RED_THREADS) void k_icp(const DevState* __restrict__ st, IcpArgs ex, const float* __restrict__ vmap_curr,
                                                      const float* __restrict__ nmap_curr, const float* __restrict__ vmap_prev,
@@ -1011,13 +786,12 @@ struct PairArgs {
     Corres8* corres;
     int w, h, nb_icp, nb_res;
     int check_skip;
-    int lds_tiles;   // ICP half on 64 x 16 tiles with the model maps staged in LDS (option icp_lds, level 0)
 };
 // All kernel-argument words a launch needs are pulled into SGPRs in the entry block (one scalar round trip).  Left to itself the compiler sinks
 // each group of s_loads into the branch that uses it: four to five dependent scalar round trips in front of the first vector load of a
 // latency-bound launch.
 #define IFX_PIN_S(x) asm volatile("" ::"s"(x))
-template <bool LDS_TILES, bool CHECK_SKIP, bool PRO = false>
+template <bool CHECK_SKIP, bool PRO = false>
 __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState* __restrict__ st, int nb_icp, int w, int h, double* __restrict__ gacc, int* __restrict__ gres, PairArgs a, GnPro g,
                                                               double* __restrict__ rrt_store)
 {
@@ -1027,9 +801,6 @@ __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState*
     __builtin_assume(st != nullptr);
     if (CHECK_SKIP && st->skip) return;   // model-to-model instance only: the frame-to-model tracker pays no dependent load for it
     if ((int)blockIdx.x < nb_icp) {
-#ifdef IFX_EXPERIMENTS
-        if (LDS_TILES) { icp_body_lds(blockIdx.x, st, a.vmap_curr, a.nmap_curr, a.vmap_prev, a.nmap_prev, a.fx, a.fy, a.cx, a.cy, a.distThres, a.angleThres, w, h, gacc); return; }
-#endif
         IcpArgs ia;   // unused when st != nullptr
         // PRO: `g` and `rrt_store` (DevState::gnp_RRt of this iteration's parity: block 0 publishes the increment it solved for the launch after the next)
         icp_body<false, true, PRO>(blockIdx.x, nb_icp, st, ia, a.vmap_curr, a.nmap_curr, a.vmap_prev, a.nmap_prev, a.fx, a.fy, a.cx, a.cy, a.distThres, a.angleThres, w, h, gacc, &g,
@@ -1040,127 +811,6 @@ __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState*
                                  h, nullptr, gres, &g, blockIdx.x == 0 ? rrt_store : nullptr);
     }
 }
-
-#ifdef IFX_EXPERIMENTS
-// The two reductions of k_icp_residual on the SAME pixels of one thread: PX pixels per thread, no loop.  Every coalesced load of the thread -- the ICP's
-// vertex / normal and the residual pass's window, gradients, depth, intensity -- leaves in one batch, every gather (model vertex / normal, warped depth
-// and intensity) in a second one: two memory round trips for the whole launch, whatever the level, where the split form runs an ICP block through three
-// pipelined rounds at level 0 and needs 1 656 blocks (more than fit the GPU at once).  Same rows, same exact sums.
-template <int PX, bool CHECK_SKIP>
-__global__ __launch_bounds__(RED_THREADS) void k_icp_residual_px(const DevState* __restrict__ st, int nb, int w, int h, double* __restrict__ gacc, int* __restrict__ gres, PairArgs a)
-{
-    __builtin_assume(st != nullptr);
-    if (CHECK_SKIP && st->skip) return;
-    const int N = w * h, bid = blockIdx.x, tid = threadIdx.x;
-    float Rcurr[9], Rprev_inv[9], krk[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) { Rcurr[k] = st->Rcurr[k]; Rprev_inv[k] = st->Rprev_inv[k]; krk[k] = st->krkinv[k]; }
-    const v3 tc = v3m(st->tcurr[0], st->tcurr[1], st->tcurr[2]), tp = v3m(st->tprev[0], st->tprev[1], st->tprev[2]);
-    const float kt0 = st->kt[0], kt1 = st->kt[1], kt2 = st->kt[2];
-    const int border = 16;
-    // ---- batch 1: everything that is addressed by the pixel itself
-    v3 vcurr[PX], ncurr[PX];
-    float d1[PX], nif[PX];
-    short gx[PX], gy[PX];
-    uint32_t r4[PX][4];
-    bool okb[PX], inp[PX];
-    int xy[PX], pix[PX];
-#pragma unroll
-    for (int u = 0; u < PX; u++) {
-        const int p = (u * nb + bid) * RED_THREADS + tid;
-        inp[u] = p < N;
-        const int pp = inp[u] ? p : 0;
-        pix[u] = p;
-        const int i = pp / w, j0 = pp - i * w;
-        xy[u] = (i << 16) | j0;
-        vcurr[u] = v3m(a.vmap_curr[pp], a.vmap_curr[pp + N], a.vmap_curr[pp + 2 * N]);
-        ncurr[u] = v3m(a.nmap_curr[pp], a.nmap_curr[pp + N], a.nmap_curr[pp + 2 * N]);
-        okb[u] = inp[u] && i >= border && i < h - border && j0 >= border && j0 < w - border && j0 < w - 5 && i < h - 1;
-        const int ci = okb[u] ? i : 16, cj = okb[u] ? j0 : 16;
-#pragma unroll
-        for (int q = 0; q < 4; q++) __builtin_memcpy(&r4[u][q], a.nextImage + (ci + q - 2) * w + cj - 2, 4);
-        gx[u] = a.dIdx[pp]; gy[u] = a.dIdy[pp];
-        d1[u] = a.nextDepth[pp];
-        nif[u] = (float)a.nextImage[pp];
-    }
-    // ---- projections, then batch 2: every gather
-    v3 vcurr_g[PX], vprev[PX], nprev[PX];
-    bool inb[PX], cand[PX];
-    int gj[PX];
-    float td1[PX], d0[PX], lif[PX];
-#pragma unroll
-    for (int u = 0; u < PX; u++) {
-        if (!inp[u]) vcurr[u].x = qnan_f();
-        vcurr_g[u] = mulp(Rcurr, vcurr[u]) + tc;
-        const v3 vcurr_cp = mulp(Rprev_inv, vcurr_g[u] - tp);
-        const int ux = f2i_rn(vcurr_cp.x * a.fx / vcurr_cp.z + a.cx);
-        const int uy = f2i_rn(vcurr_cp.y * a.fy / vcurr_cp.z + a.cy);
-        inb[u] = !(vcurr[u].x != vcurr[u].x) && !(ux < 0 || uy < 0 || ux >= w || uy >= h || vcurr_cp.z < 0);
-        const int j = inb[u] ? uy * w + ux : 0;
-        bool valid = true;
-#pragma unroll
-        for (int q = 0; q < 4; q++) valid = valid & (((r4[u][q] - 0x01010101u) & ~r4[u][q] & 0x80808080u) == 0u);
-        const float mTwo = (float)((gx[u] * gx[u]) + (gy[u] * gy[u]));
-        const bool c0 = okb[u] & valid & (mTwo >= a.minScale) & !(d1[u] != d1[u]);
-        const int y = xy[u] >> 16, x = xy[u] & 0xFFFF;
-        td1[u] = (float)(d1[u] * (krk[6] * x + krk[7] * y + krk[8]) + kt2);
-        const int u0 = f2i_rn((d1[u] * (krk[0] * x + krk[1] * y + krk[2]) + kt0) / td1[u]);
-        const int v0 = f2i_rn((d1[u] * (krk[3] * x + krk[4] * y + krk[5]) + kt1) / td1[u]);
-        cand[u] = c0 & ((u0 >= 0) & (v0 >= 0) & (u0 < w) & (v0 < h));
-        gj[u] = cand[u] ? v0 * w + u0 : 0;
-        vprev[u] = v3m(a.vmap_prev[j], a.vmap_prev[j + N], a.vmap_prev[j + 2 * N]);
-        nprev[u] = v3m(a.nmap_prev[j], a.nmap_prev[j + N], a.nmap_prev[j + 2 * N]);
-        d0[u] = a.lastDepth[gj[u]];
-        lif[u] = (float)a.lastImage[gj[u]];
-    }
-    double acc[29];
-#pragma unroll
-    for (int k = 0; k < 29; k++) acc[k] = 0.0;
-    int cnt = 0, sig = 0;
-#pragma unroll
-    for (int u = 0; u < PX; u++) {
-        float row[7] = {0, 0, 0, 0, 0, 0, 0};
-        bool found = false;
-        if (inb[u]) {
-            const v3 ncurr_g = mulp(Rcurr, ncurr[u]);
-            const float dist = norm(vprev[u] - vcurr_g[u]);
-            const float sine = norm(cross(ncurr_g, nprev[u]));
-            found = (sine < a.angleThres && dist <= a.distThres && !(ncurr[u].x != ncurr[u].x) && !(nprev[u].x != nprev[u].x));
-            if (found) {
-                const v3 s_cp = mulp(Rprev_inv, vcurr_g[u] - tp);
-                const v3 d_cp = mulp(Rprev_inv, vprev[u] - tp);
-                const v3 n_cp = mulp(Rprev_inv, nprev[u]);
-                const v3 c = cross(s_cp, n_cp);
-                row[0] = n_cp.x; row[1] = n_cp.y; row[2] = n_cp.z;
-                row[3] = c.x; row[4] = c.y; row[5] = c.z;
-                row[6] = dot(n_cp, s_cp - d_cp);
-            }
-        }
-        products7<0>(row, found, acc);
-        const bool hit = cand[u] & (d0[u] > 0) & (fabsf(td1[u] - d0[u]) <= a.maxDepthDelta) & (lif[u] != 0.f);
-        const int v0 = gj[u] / w, u0 = gj[u] - v0 * w;
-        const float diff = nif[u] - lif[u];
-        Corres8 c8;
-        c8.zx = hit ? (short)u0 : (short)-1; c8.zy = hit ? (short)v0 : (short)-1;
-        c8.diff = hit ? diff : 0.f;
-        cnt += hit ? 1 : 0;
-        sig += hit ? (int)(diff * diff) : 0;
-        if (inp[u]) a.corres[pix[u]] = c8;
-    }
-    block_sum_exact<29>(acc, gacc, bid % IFX_ACC_REPL);
-    __shared__ int lds2[RED_WAVES][2];
-    const int lane = tid & 63, wid = tid >> 6;
-    cnt = wave_sum_i(cnt);
-    sig = wave_sum_i(sig);
-    if (lane == 0) { lds2[wid][0] = cnt; lds2[wid][1] = sig; }
-    __syncthreads();
-    if (tid < 2) {
-        int s2 = 0;
-        for (int wv = 0; wv < RED_WAVES; wv++) s2 += lds2[wv][tid];
-        if (s2) atomicAdd(&gres[tid], s2);
-    }
-}
-#endif   // IFX_EXPERIMENTS
 
 // RGBReduction, EF/Cuda/reduce.cu:494-619.  sigma is either explicit (stage API) or derived from the
 // residual pass's block partials with the reference's precedence quirk (EF/Utils/RGBDOdometry.cpp:461).
@@ -2647,7 +2297,7 @@ int ifx_alloc_tracker(ifx* h)
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ[3], k_gn_level<4>, RED_THREADS, 0);
         for (int q = 0; q < 4; q++) h->gn_max_blocks[q] = std::max(0, occ[q]) * std::max(0, cus);
         int occ_ir = 0;   // one round of residency of the two-launch form's first launch (its residual half is capped to what the ICP half leaves of it: ifx_tracker_run)
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_ir, k_icp_residual<false, false, true>, RED_THREADS, 0) == hipSuccess && occ_ir > 0 && cus > 0) h->icp_resident_blocks = occ_ir * cus;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_ir, k_icp_residual<false, true>, RED_THREADS, 0) == hipSuccess && occ_ir > 0 && cus > 0) h->icp_resident_blocks = occ_ir * cus;
     }
     h->res_rows = std::max(maxb, cdiv(h->P, RED_THREADS) + 1);   // the residual pass runs one block per 256 pixels
     HIPCHK(h, hipMalloc(&h->res_partials, (size_t)h->res_rows * 2 * 4));
@@ -2733,22 +2383,16 @@ static void tracker_init_model(ifx* h, DevState* st, Pyr& p, float icp_weight, c
     const ifx_config& c = h->cfg;
     const int rgb = icp_weight < 100;
     const int iterations[3] = {c.fast_odom ? 3 : 10, c.pyramid ? 5 : 0, c.pyramid ? 4 : 0};
-    ModelOut3 o3;
+    ModelOut o3[IFX_NUM_PYRS];
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
         const float div = (float)(1 << i);
-        ModelOut& o = o3.l[i];
+        ModelOut& o = o3[i];
         o.vcam = p.vmap_cam[i]; o.ncam = p.nmap_cam[i]; o.depth = p.last_depth[i]; o.img = p.last_img[i];
         o.vprev = p.vmap_prev[i]; o.nprev = p.nmap_prev[i]; o.cloud = (rgb && iterations[i] > 0) ? p.cloud[i] : nullptr;
         o.invFx = 1.0f / (c.fx / div); o.invFy = 1.0f / (c.fy / div); o.cx = c.cx / div; o.cy = c.cy / div;
     }
-#ifdef IFX_EXPERIMENTS
-    if (h->opt_model_fused && IFX_NUM_PYRS == 3 && h->w % 32 == 0 && h->h % 16 == 0 && fv) {   // the three levels in one launch
-        LAUNCH(h, "model_pyr3", dim3(h->w / 32, h->h / 16), dim3(256), k_model_pyr3, st, pv, pn, pi, fv, fn, fi, h->w, h->h, 6.0f, o3);
-        return;
-    }
-#endif
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
-        const ModelOut& o = o3.l[i];
+        const ModelOut& o = o3[i];
         if (i == 0) LAUNCH(h, "model_l0", G2(h->w, h->h), B2, k_model_l0, st, pv, pn, pi, fv, fn, fi, h->w, h->h, 6.0f, o);
         else LAUNCH(h, "model_down", G2(p.w[i], p.h[i]), B2, k_model_down, st, p.vmap_cam[i - 1], p.nmap_cam[i - 1], p.last_depth[i - 1], p.last_img[i - 1], p.w[i - 1], p.h[i - 1], o, (i == IFX_NUM_PYRS - 1 && gbp) ? *gbp : gb_off);
     }
@@ -2837,11 +2481,7 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
     int persist_q[IFX_NUM_PYRS], persist_nb[IFX_NUM_PYRS];
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
         persist_q[i] = -1; persist_nb[i] = 0;
-        bool lds_lvl = false;
-#ifdef IFX_EXPERIMENTS
-        lds_lvl = h->opt_icp_lds && i == 0 && frame_tracker;
-#endif
-        if (frame_tracker && (h->opt_gn_persist & (1 << i)) && iterations[i] > 0 && !lds_lvl && icp && rgb) {
+        if (frame_tracker && (h->opt_gn_persist & (1 << i)) && iterations[i] > 0 && icp && rgb) {
             static const int pxs[4] = {1, 2, 3, 4};
             const int n = p.w[i] * p.h[i];
             for (int t = 0; t < 4 && persist_q[i] < 0; t++) {   // (fewer, fatter blocks at the finer levels -- 4 pixels per thread -- were tried for cheaper meetings: slower)
@@ -2874,7 +2514,7 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
             pa.fx = fx; pa.fy = fy; pa.cx = cx; pa.cy = cy; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
             pa.minScale = (float)(pow(minGrad[i], 2.0) / pow(sobelScale, 2.0)); pa.maxDepthDelta = 0.07f;
             pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
-            pa.lds_tiles = 0; pa.corres = (Corres8*)p.corres[i]; pa.w = lw; pa.h = lh; pa.nb_icp = icp ? nbv : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = 0;
+            pa.corres = (Corres8*)p.corres[i]; pa.w = lw; pa.h = lh; pa.nb_icp = icp ? nbv : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = 0;
             for (int j = 0; j < iterations[i]; j++) {
                 const float nd = (j == iterations[i] - 1) ? ld : div;
                 for (int r = r_lo; r < r_hi; r++)   // (the residual pass once: with the first of the launches)
@@ -2919,9 +2559,6 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
                 if (small) n_pro += iterations[i];
             }
         }
-#ifdef IFX_EXPERIMENTS
-        if (h->opt_icp_lds || h->opt_icp_px) pro = false;
-#endif
         if (n_pro < 2) pro = false;   // (a chain of one has nothing to hand over)
     }
     int persist_iters = 0;
@@ -2953,20 +2590,13 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
         // The residual half of the launch is the slower one and scales with its blocks (its totals go through integer atomics, it has no partial rows for the
         // last block to sum): one pixel per thread, no loop -- 152 blocks 17.5 us, 304 blocks 13.3 us, 1200 blocks 11.3 us per launch at 640x480 (1053 -> 1102 frames/s).
-#ifdef IFX_EXPERIMENTS
-        const bool lds_tiles = h->opt_icp_lds && i == 0 && frame_tracker;
-#else
-        const bool lds_tiles = false;
-#endif
         // One round of residency: the launch's blocks (ICP half + residual half) must all be on the GPU at once.  At 640x480 level 0 they were 456 + 1024 = 1480 against the 1024 the GPU holds
         // (118 VGPRs: 4 blocks per CU), so a third of them started when the first ones left -- and paid the launch's start-up chain (kernel arguments, the previous iteration's totals and
         // 6x6 solve in every block's prologue, the first loads) a second time: 17.2 -> 14.5 us per level-0 launch with the residual half capped to what is left of one round
         // (profiles/r05_ai_ab_tracker_blocks.txt: 1514 -> 1561 frames/s).  The halves loop over their pixels anyway (grid-stride); opt_res_blocks > 0 overrides.
-        const int nbi = lds_tiles ? cdiv(lw, LT_W) * cdiv(lh, LT_H) : nb;
-        const int res_round = std::max(128, h->icp_resident_blocks - (icp ? nbi : 0));
+        const int res_round = std::max(128, h->icp_resident_blocks - (icp ? nb : 0));
         const int nbr = std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : res_round);
-        pa.lds_tiles = lds_tiles ? 1 : 0;
-        pa.corres = (Corres8*)p.corres[i]; pa.w = lw; pa.h = lh; pa.nb_icp = icp ? nbi : 0; pa.nb_res = rgb ? nbr : 0;
+        pa.corres = (Corres8*)p.corres[i]; pa.w = lw; pa.h = lh; pa.nb_icp = icp ? nb : 0; pa.nb_res = rgb ? nbr : 0;
         double* const gacc = (double*)((char*)st + offsetof(DevState, gn_acc));
         int* const gres = (int*)((char*)st + offsetof(DevState, gn_res));
         pa.check_skip = frame_tracker ? 0 : 1;   // (accumulator rows, residual totals, ticket: DevState::gn_acc / gn_res / gn_ticket of `st`)
@@ -2996,39 +2626,26 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
                 continue;
             }
         }
-        // both reductions on the same pixels of one thread (k_icp_residual_px); option bits: 1 = at level 0, 2 = at levels 1 and 2, 4 = one pixel per thread at level 0 too
-#ifdef IFX_EXPERIMENTS
-        const bool px_form = frame_tracker && icp && rgb && !lds_tiles && (i == 0 ? (h->opt_icp_px & 1) : (h->opt_icp_px & 2));
-        const bool px_two = !(h->opt_icp_px & 4);
-#endif
         for (int j = 0; j < iterations[i]; j++) {
             const float nd = (j == iterations[i] - 1) ? ld : div;
-#ifdef IFX_EXPERIMENTS
-            if (px_form && px_two && n > 150000) LAUNCH(h, icp_name[i], dim3(cdiv(n, RED_THREADS * 2)), dim3(RED_THREADS), (k_icp_residual_px<2, false>), st, cdiv(n, RED_THREADS * 2), pa.w, pa.h, gacc, gres, pa);
-            else if (px_form) LAUNCH(h, icp_name[i], dim3(cdiv(n, RED_THREADS)), dim3(RED_THREADS), (k_icp_residual_px<1, false>), st, cdiv(n, RED_THREADS), pa.w, pa.h, gacc, gres, pa);
-            else if (pa.lds_tiles) { GnPro g0; memset(&g0, 0, sizeof(g0)); LAUNCH(h, icp_name[i], dim3(pa.nb_icp + pa.nb_res), dim3(RED_THREADS), (k_icp_residual<true, false, false>), st, pa.nb_icp, pa.w, pa.h, gacc, gres, pa, g0, (double*)nullptr); }   // (its 60 KB of LDS would cost the plain kernel its occupancy: a kernel of its own)
-            else
-#endif
-            {
-                // gn_prologue: iteration tail_k sums into parity tail_k & 1; from the tail's second iteration on, every block first solves the iteration before
-                GnPro gp;
-                gp.k = tail_k; gp.icp = icp; gp.rgb = rgb; gp.icp_weight = icp_weight; gp.nfx = fx; gp.nfy = fy; gp.ncx = cx; gp.ncy = cy; gp.ki = kinv_of(fx, fy, cx, cy);
-                const bool it_pro = pro && tail_k < n_pro;
-                double* const ga = it_pro ? gnp_acc_of(tail_k & 1) : gacc;
-                int* const gr = it_pro ? gnp_res_of(tail_k & 1) : gres;
-                double* const rrt_store = gnp_rrt_of((tail_k + 1) & 1);   // the increment after iteration tail_k - 1
-                const dim3 grid(pa.nb_icp + pa.nb_res);
-                if (it_pro && tail_k > 0) {
-                    if (frame_tracker) LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, false, true>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-                    else LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, true, true>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-                } else {
-                    if (frame_tracker) LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, false, false>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-                    else LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, true, false>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-                }
+            // gn_prologue: iteration tail_k sums into parity tail_k & 1; from the tail's second iteration on, every block first solves the iteration before
+            GnPro gp;
+            gp.k = tail_k; gp.icp = icp; gp.rgb = rgb; gp.icp_weight = icp_weight; gp.nfx = fx; gp.nfy = fy; gp.ncx = cx; gp.ncy = cy; gp.ki = kinv_of(fx, fy, cx, cy);
+            const bool it_pro = pro && tail_k < n_pro;
+            double* const ga = it_pro ? gnp_acc_of(tail_k & 1) : gacc;
+            int* const gr = it_pro ? gnp_res_of(tail_k & 1) : gres;
+            double* const rrt_store = gnp_rrt_of((tail_k + 1) & 1);   // the increment after iteration tail_k - 1
+            const dim3 grid(pa.nb_icp + pa.nb_res);
+            if (it_pro && tail_k > 0) {
+                if (frame_tracker) LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, true>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
+                else LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<true, true>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
+            } else {
+                if (frame_tracker) LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, false>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
+                else LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<true, false>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
             }
             StepArgs sa2;
             sa2.corres = (const Corres8*)p.corres[i]; sa2.cloud = p.cloud[i]; sa2.fx = fx; sa2.fy = fy; sa2.sobelScale = (float)sobelScale;
-            sa2.dIdx = p.didx[i]; sa2.dIdy = p.didy[i]; sa2.w = lw; sa2.h = lh; sa2.nb = nb_rgb; sa2.nb_icp = nbi; sa2.nb_res = nbr;
+            sa2.dIdx = p.didx[i]; sa2.dIdy = p.didy[i]; sa2.w = lw; sa2.h = lh; sa2.nb = nb_rgb; sa2.nb_icp = nb; sa2.nb_res = nbr;
             sa2.icp = icp; sa2.rgb = rgb; sa2.icp_weight = icp_weight; sa2.nfx = c.fx / nd; sa2.nfy = c.fy / nd; sa2.ncx = c.cx / nd; sa2.ncy = c.cy / nd; sa2.ki = kinv_of(sa2.nfx, sa2.nfy, sa2.ncx, sa2.ncy);
             sa2.check_skip = frame_tracker ? 0 : 1;
             {   // is this the run's last iteration?  (no level below this one iterates)
@@ -3080,7 +2697,7 @@ int ifx_tracker_model_side(ifx* h, int fold_begin)
     // fold_begin: the caller runs the frame tracker right behind this (nothing in between touches the pose, and the frame side of the slot is
     // ready): the start of the run rides on the model side's last launch
     const ifx_config& c = h->cfg;
-    const bool fold = fold_begin && !h->opt_model_fused && c.pyramid && IFX_NUM_PYRS == 3;
+    const bool fold = fold_begin && c.pyramid && IFX_NUM_PYRS == 3;
     GnBegin gb = gb_none();
     if (fold) {
         const float div = (float)(1 << (IFX_NUM_PYRS - 1));   // the run starts at the coarsest level (pyramid on: every level iterates)

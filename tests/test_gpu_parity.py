@@ -735,38 +735,6 @@ def test_config3_5m_map_full_instance_path(ifx, orc):
     g.close(); o.close()
 
 
-def _experiments_or_skip(ifx):
-    """The measured alternatives that lost are compiled only with -DIFX_EXPERIMENTS (`make -C instancefusion_amd/csrc experiments`,
-    then IFX_LIB=build/variants/libifx_experiments.so): the product library refuses their options."""
-    g = ifx.ElasticFusion(w=64, h=48, fx=50.0, fy=50.0, cx=32.0, cy=24.0, max_surfels=1000)
-    try:
-        g.set_option("model_fused", 1)
-    except ifx.IfxError as e:
-        assert "IFX_EXPERIMENTS" in str(e)
-        pytest.skip("libifx.so was built without -DIFX_EXPERIMENTS (the default): run with IFX_LIB=build/variants/libifx_experiments.so")
-    finally:
-        g.close()
-
-
-def test_lds_staged_icp_tiles_are_bit_identical(ifx):
-    """The north star's LDS-staged model tiles for the level-0 ICP reduction (option icp_lds): same correspondences, same exact sums --
-    trajectories and maps bit-identical to the plain gathers (it is slower, DESIGN.md section 6, hence an option)."""
-    from instancefusion_amd import synth
-
-    _experiments_or_skip(ifx)
-    W, H = 640, 480
-    K = dict(fx=528.0, fy=528.0, cx=320.0, cy=240.0)
-    st = synth.make_stream(6, W, H, noise=True, loop_len=90, **K)
-    out = []
-    for lds in (0, 1):
-        g = ifx.ElasticFusion(w=W, h=H, max_surfels=1_000_000, **K)
-        g.set_option("icp_lds", lds)
-        out.append((np.stack([g.processFrame(st["rgb"][i], st["depth"][i]) for i in range(6)]), g.download()))
-        g.close()
-    assert np.array_equal(out[0][0], out[1][0])
-    assert all(np.array_equal(out[0][1][k], out[1][1][k]) for k in MAP_KEYS)
-
-
 def _tracker_variants_equal(ifx, variants):
     from instancefusion_amd import synth
 
@@ -833,13 +801,6 @@ def test_gn_prologue_solve_is_bit_identical(ifx):
     # the chain ends where a level's launches get too large for a solve in every block (default 2048 blocks: level 0 of a 1280x960 frame; here lowered so that
     # it ends after the coarsest level / after the two coarse levels of a 640x480 frame): its last iteration in the last-block form, the finer levels as in round 3
     _tracker_variants_equal(ifx, [dict(gn_prologue=0), dict(gn_prologue_blocks=200), dict(gn_prologue_blocks=600), dict(gn_prologue_blocks=200, gn_persist=4)])
-
-
-def test_lost_tracker_experiments_are_bit_identical(ifx):
-    """(experiments build only) the three levels of the model pyramid in one launch (model_fused; k_model_pyr3) and the ICP and residual reductions on the same
-    pixels of one thread (icp_px; k_icp_residual_px): the same pyramids / rows / sums."""
-    _experiments_or_skip(ifx)
-    _tracker_variants_equal(ifx, [dict(), dict(model_fused=1), dict(icp_px=3)])
 
 
 @pytest.mark.parametrize("world,zero_dies,lazy_ids", [(2, 0, 0), (3, 0, 0), (2, 1, 0), (3, 1, 0), (2, -1, 0), (2, 30, 0), (3, 1, 1), (2, 30, 1)] +
