@@ -239,6 +239,8 @@ static Cam make_cam(ifx* h)
     c.age_epoch = h->age_epoch;
     return c;
 }
+// the Cam of a pass over the whole store (everything but the phases of the sharded projection): never sliced
+static Cam whole_cam(ifx* h) { Cam c = make_cam(h); c.srank = 0; c.sn = 1; return c; }
 
 // ------------------------------------------------------------------ exclusive scan of int flags
 #define SCAN_ITEMS 8
@@ -427,6 +429,18 @@ __global__ void k_index_resolve(const DevState* __restrict__ st, const float* __
     if (tap) tap[k] = (id > 0u && p.z > 0.f) ? make_float4(p.x, p.y, (t2.y == (float)time) ? -p.z : p.z, (p4.w > conf_thr) ? t2.x : -t2.x) : make_float4(0, 0, 0, 0);
 }
 
+// What a resolve of key_index leaves: the index map k_associate reads (ids, positions, normals), the same with the colour / time image, or only the clean pass's tap
+// records ("index_resolve_taps").  own_slot: the slot image of a sharded map whose keys were translated; hot: the frame's gathered records.
+enum IndexOut { INDEX_ASSOC, INDEX_ALL, INDEX_TAPS };
+static void launch_index_resolve(ifx* h, const float* d_pose_inv, const Cam& c, int time, IndexOut out, const int32_t* own_slot, const Hot* hot)
+{
+    const bool taps = out == INDEX_TAPS;
+    LAUNCH(h, taps ? "index_resolve_taps" : "index_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_index_resolve, h->d_state, d_pose_inv, h->key_index, (const float4*)h->pc,
+           (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, h->P, taps ? (uint32_t*)nullptr : h->index_id, taps ? (float4*)nullptr : (float4*)h->index_vc,
+           out == INDEX_ALL ? (float4*)h->index_ct : (float4*)nullptr, taps ? (float4*)nullptr : (float4*)h->index_nr, time, h->cfg.confidence,
+           taps ? (float4*)h->index_tap : (float4*)nullptr, c, own_slot, hot);
+}
+
 // for_association: the frame path, where k_associate is the only consumer (it reads ids, positions and normals): the colour /
 // time image is not produced and the winner's colour and times are not fetched
 static void index_pass(ifx* h, const float* d_pose_inv, int time, bool for_association = false, int part = 0, const int32_t* own_slot = nullptr)
@@ -434,9 +448,7 @@ static void index_pass(ifx* h, const float* d_pose_inv, int time, bool for_assoc
     Cam c = make_cam(h);
     if (part == 0) { c.srank = 0; c.sn = 1; }   // a whole pass (stage API, re-render after a compaction) is never sliced
     if (part != 2) LAUNCH(h, "index_project", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_index_project, h->d_state, d_pose_inv, (const float4*)h->pc, (const float2*)h->tm, c, time, h->key_index);
-    if (part != 1) LAUNCH(h, "index_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_index_resolve, h->d_state, d_pose_inv, h->key_index, (const float4*)h->pc, (const float4*)h->nr,
-           (const float2*)h->col, (const float2*)h->tm, h->P, h->index_id, (float4*)h->index_vc, for_association ? (float4*)nullptr : (float4*)h->index_ct, (float4*)h->index_nr, time,
-           h->cfg.confidence, (float4*)nullptr, c, own_slot);
+    if (part != 1) launch_index_resolve(h, d_pose_inv, c, time, for_association ? INDEX_ASSOC : INDEX_ALL, own_slot, nullptr);
 }
 
 // ------------------------------------------------------------------ disc rasteriser (a9, a14)
@@ -2102,19 +2114,95 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
     }
 }
 
+// ------------------------------------------------------------------ launches of the raster passes: one helper per kernel, every kernel argument written out once.
+// A helper reads from the handle what all its sites read from it and takes what differs between them.
 // One walk of the cached view lists at the frame's pose and time (k_raster_view).  clean: the frame's clean pass and its new-surfel flags ride in the walk
-// (k_raster_view<., true>, with CleanArgs::nf_blocks blocks of k_new_flags_count's work in front of the walk's own); lds: the per-wave depth test in LDS.
-static void launch_raster_view(ifx* h, const char* name, const Cam& c, unsigned int want, int ids_step, bool lds, const CleanArgs* clean)
+// (k_raster_view<., true>, with CleanArgs::nf_blocks blocks of k_new_flags_count's work in front of the walk's own); lds: the per-wave depth test in LDS;
+// earlyz: option raster_earlyz on the unsharded map, 0 on the sharded one.
+static void launch_raster_view(ifx* h, const char* name, const Cam& c, unsigned int want, int ids_step, int earlyz, bool lds, const CleanArgs* clean)
 {
     const CleanArgs ca = clean ? *clean : CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const dim3 grid(ca.nf_blocks + (h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS));
     auto go = [&](auto kernel) {
         LAUNCH(h, name, grid, dim3(MAP_THREADS), kernel, h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, c, h->tick, h->tick, want, h->list_v, h->list_vi,
-               h->key_splat, h->key_ids, h->key_both, h->opt_raster_earlyz, ids_step, ca, (const DevState*)h->d_state);
+               h->key_splat, h->key_ids, h->key_both, earlyz, ids_step, ca, (const DevState*)h->d_state);
     };
     if (clean) go(k_raster_view<false, true>);
     else if (lds) go(k_raster_view<true, false>);
     else go(k_raster_view<false, false>);
+}
+// what the clean pass and the new-surfel flags need when they ride in the walk; hot: the frame's gathered records (null: none)
+static CleanArgs frame_clean_args(ifx* h, Hot* hot)
+{
+    CleanArgs ca;
+    ca.pc_rw = (float4*)h->pc; ca.tm_rw = (float2*)h->tm; ca.tap = (const float4*)h->index_tap; ca.nf_blocks = cdiv(h->P, NEW_PER_BLOCK); ca.assoc = h->assoc_target;
+    ca.mpc = (const float4*)h->meas_pc; ca.mnr = (const float4*)h->meas_nr; ca.flags = h->scan_flags; ca.block_counts = h->scan_block; ca.hot = hot;
+    return ca;
+}
+// What the unsharded and the sharded frame both ask before ONE walk of the view list cleans and rasterises (ifx_map_frame has the why): nothing renumbers the store
+// between the frame's passes and its prediction, the prediction takes the view-list raster, and no new surfel can be drawn in the frame that creates it.
+static bool clean_raster_allowed(ifx* h) { return h->opt_clean_raster && !h->opt_compact_every_frame && h->last_compact_tick != h->tick && h->opt_raster_tiles <= 0 && h->cfg.confidence > fmaxf(1.f, h->frame_weight_mult); }
+// zero_buf / zero_n: the tiled rasteriser's per-tile counts, cleared on the way (null: none)
+static void launch_cull_raster(ifx* h, const float* d_pose_inv, const Cam& c, int time, int maxTime, unsigned int want, unsigned int* zero_buf, int zero_n)
+{
+    LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, d_pose_inv, (const float4*)h->pc, (const float2*)h->tm, c, time, maxTime, want, h->list_a, zero_buf, zero_n);
+}
+// dual: list 0 holds the entries of two time windows (LIST_DUAL); gate: the launch only draws when *gate is set (null: always)
+static void launch_raster_list(ifx* h, const float* d_pose_inv, const Cam& c, int dual, const int* gate)
+{
+    LAUNCH(h, "raster_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_raster_list, h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr, c, h->list_a, h->key_splat, h->key_ids, h->key_both, dual, gate);
+}
+// the two loop-closure renders at the current pose -- ACTIVE into key_splat, INACTIVE into key_ids -- from one scan of the store
+static void launch_dual_raster(ifx* h, const Cam& c) { launch_cull_raster(h, nullptr, c, h->tick, h->tick, LIST_SPLAT | LIST_DUAL, nullptr, 0); launch_raster_list(h, nullptr, c, 1, nullptr); }
+// option id_rule: the reference's quads into key_ids; inst: the INSTANCECOMPARE render (k_raster_quad<2>)
+static void launch_raster_quad(ifx* h, const char* name, const float* d_pose_inv, const Cam& c, bool inst, int ids_step)
+{
+    auto go = [&](auto kernel) {
+        LAUNCH(h, name, dim3(MAP_BLOCKS), dim3(MAP_THREADS), kernel, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr, (const float4*)h->votes, c, h->key_ids, ids_step);
+    };
+    if (!inst) go(k_raster_quad<1>);
+    else go(k_raster_quad<2>);
+}
+// the index projection of the cached view list; hot: the frame's gathered records (null: the store's arrays)
+static void launch_index_list(ifx* h, const Cam& c, int time, const Hot* hot)
+{
+    LAUNCH(h, "index_list", dim3(h->opt_index_blocks > 0 ? h->opt_index_blocks : LIST_BLOCKS), dim3(MAP_THREADS), k_index_list, (const DevState*)h->d_state, (const float4*)h->pc, (const float2*)h->tm, c, time, h->list_v,
+           h->key_index, hot);
+}
+static void launch_ids_resolve(ifx* h, int32_t* out) { LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, out); }
+static void launch_clean_list(ifx* h, const float* d_pose_inv, const Cam& c, int time)
+{
+    LAUNCH(h, "clean_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_clean_list, h->d_state, d_pose_inv, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm, (const float4*)h->index_tap, h->list_b, h->list_c);
+}
+// k_splat_resolve: the winners of `to.keys` into the images of `to`; everything else is optional
+struct SplatResolve {
+    const char* name;
+    ResolveTarget to;
+    const float* d_pose_inv = nullptr;
+    bool fill_in = false;                                                         // also the fill_* images (FillIn on the prediction)
+    int32_t* ids_out = nullptr; int ids_step = 1;                                 // the id image from key_ids, on every ids_step-th pixel of both axes
+    FinishFold fold = FinishFold(); FrameOut fo = FrameOut{nullptr, nullptr, 0};  // the end-of-pass sums, and the frame result, in the same launch
+    float* pconf = nullptr; const int32_t* own_slot = nullptr;                    // sharded map: the winner's confidence apart from the vertex; the render's slot image
+    const Hot* hot = nullptr;                                                     // the frame's gathered records
+};
+// the prediction images of the frame-to-model tracker (pred_*) and of the two loop-closure renders (act_*, old_*), with the key image they are resolved from
+static ResolveTarget pred_images(ifx* h) { return ResolveTarget{h->key_splat, (float4*)h->pred_vertex, (float4*)h->pred_normal, (uchar4*)h->pred_image, (uchar4*)h->pred_inst, h->pred_time}; }
+static ResolveTarget act_images(ifx* h, unsigned long long* keys) { return ResolveTarget{keys, (float4*)h->act_vertex, (float4*)h->act_normal, (uchar4*)h->act_image, (uchar4*)h->act_inst, h->act_time}; }
+static ResolveTarget old_images(ifx* h, unsigned long long* keys) { return ResolveTarget{keys, (float4*)h->old_vertex, (float4*)h->old_normal, (uchar4*)h->old_image, (uchar4*)h->old_inst, h->old_time}; }
+static void launch_splat_resolve(ifx* h, const Cam& c, const SplatResolve& a)
+{
+    LAUNCH(h, a.name, dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_splat_resolve, h->d_state, a.d_pose_inv, a.to.keys, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col,
+           (const float2*)h->tm, c, h->rgb, h->depth_filt, a.to.pv, a.to.pn, a.to.pimg, a.to.pinst, a.to.ptime, a.fill_in ? (float4*)h->fill_vertex : (float4*)nullptr,
+           a.fill_in ? (float4*)h->fill_normal : (float4*)nullptr, a.fill_in ? (uchar4*)h->fill_image : (uchar4*)nullptr, h->key_ids, h->key_both, a.ids_out, (int*)nullptr, a.fold, a.pconf,
+           a.ids_step, a.own_slot, a.fo, a.hot);
+}
+// End of a raster pass: re-arms work list 0; do_dense: the dense flag from pred_image; seg_sums: whetherDoSegmentation's sums over the id image's lattice (one more block per 256 lattice
+// pixels).  Sharded map: mass_out = where the owners' vote mass goes (the tail of the prediction block), mass_in = the summed mass, taken into the state; own_slot = the id render's slot image.
+static void launch_raster_finish(ifx* h, int do_dense, bool seg_sums, int* mass_out, int* mass_in, const int32_t* own_slot)
+{
+    const int ds = 10, nseg = seg_sums ? cdiv(cdiv(h->w, ds) * cdiv(h->h, ds), 256) : 0;
+    LAUNCH(h, "raster_finish", dim3(1 + nseg), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, do_dense, h->ids_after, (const float4*)h->votes, h->cap, ds,
+           h->d_list_ctr, ifx_idmap(h), mass_out, mass_in, own_slot);
 }
 
 // splat prediction (want & LIST_SPLAT) and / or id render (want & LIST_IDS) in one cull + one dense raster pass
@@ -2131,8 +2219,8 @@ static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, 
         const bool want_tiles = h->opt_raster_tiles < 0 ? (h->P >= 1000000) : (h->opt_raster_tiles != 0);
         if (want_tiles && !h->tile_recs && hipMalloc(&h->tile_recs, (size_t)h->list_seg_cap * LIST_SEGS * 32) != hipSuccess) h->tile_recs = nullptr;   // 32 B per list entry, on first use
         const bool tiled = want_tiles && tw * th <= TILE_MAX && tw <= 255 && th <= 255 && h->tile_pairs && h->tile_recs;
-        LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, d_pose_inv, (const float4*)h->pc, (const float2*)h->tm, c, time, maxTime, want_r,
-               h->list_a, tiled ? h->tile_n : (unsigned int*)nullptr, tw * th);
+        launch_cull_raster(h, d_pose_inv, c, time, maxTime, want_r, tiled ? h->tile_n : (unsigned int*)nullptr, tw * th);
+        const int* gate = nullptr;   // behind the tiled rasteriser the list launch is the fallback: it only draws when the pair buffer overflowed
         if (tiled) {
             TileArgs ta;
             ta.tile_n = h->tile_n; ta.tile_off = h->tile_n + TILE_MAX; ta.tile_fill = h->tile_n + 2 * TILE_MAX; ta.blk_off = h->tile_n + 3 * TILE_MAX; ta.overflow = (int*)(h->tile_n + 4 * TILE_MAX + 8);
@@ -2142,23 +2230,18 @@ static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, 
             LAUNCH(h, "tile_fill", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_tile_fill, c, h->list_a, ta);
             LAUNCH(h, "tile_raster", dim3(tw * th + h->tile_pair_cap / TILE_CHUNK), dim3(TILE_THREADS), k_tile_raster, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr, c, ta, h->key_splat,
                    h->key_ids, h->key_both);
-            LAUNCH(h, "raster_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_raster_list, h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr, c, h->list_a, h->key_splat,
-                   h->key_ids, h->key_both, 0, (const int*)ta.overflow);
-        } else
-            LAUNCH(h, "raster_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_raster_list, h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr, c, h->list_a, h->key_splat,
-                   h->key_ids, h->key_both, 0, (const int*)nullptr);
+            gate = ta.overflow;
+        }
+        launch_raster_list(h, d_pose_inv, c, 0, gate);
     }
     if (part == 1) return;
-    if (quad)
-        LAUNCH(h, "raster_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster_quad<1>, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
-               (const float4*)h->votes, c, h->key_ids, resolve_ids_step);
+    if (quad) launch_raster_quad(h, "raster_quad", d_pose_inv, c, false, resolve_ids_step);
     if ((want & LIST_SPLAT) && old_target) {   // loop-closure renders: 1 = INACTIVE prediction into the old* images (IndexMap::oldFrameBuffer, EF/IndexMap.cpp:480-483),
         const bool old = old_target == 1;       // 2 = the predict() of EF/ElasticFusion.cpp:453 into the act* images; no fill-in, no dense flag
-        LAUNCH(h, old ? "splat_resolve_old" : "splat_resolve_act", dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_splat_resolve, h->d_state, d_pose_inv, h->key_splat,
-               (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)(old ? h->old_vertex : h->act_vertex),
-               (float4*)(old ? h->old_normal : h->act_normal), (uchar4*)(old ? h->old_image : h->act_image), (uchar4*)(old ? h->old_inst : h->act_inst),
-               old ? h->old_time : h->act_time, (float4*)nullptr, (float4*)nullptr, (uchar4*)nullptr, h->key_ids, h->key_both, (int32_t*)nullptr, (int*)nullptr, FinishFold());
-        LAUNCH(h, "raster_finish", dim3(1), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, 0, h->ids_after, (const float4*)h->votes, h->cap, 10, h->d_list_ctr, ifx_idmap(h));
+        SplatResolve a{old ? "splat_resolve_old" : "splat_resolve_act", old ? old_images(h, h->key_splat) : act_images(h, h->key_splat)};
+        a.d_pose_inv = d_pose_inv;
+        launch_splat_resolve(h, c, a);
+        launch_raster_finish(h, 0, false, nullptr, nullptr, nullptr);
         return;
     }
     if (want & LIST_SPLAT) {
@@ -2174,40 +2257,28 @@ static void raster_pass(ifx* h, const float* d_pose_inv, int time, int maxTime, 
             h->result_folded = 1;
         }
         if (raw_ids) c.raw_slots = 2;   // option clean_raster: the walk drew slot numbers, and the resolve reads the frame's gathered records
-        LAUNCH(h, "splat_resolve", dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_splat_resolve, h->d_state, d_pose_inv, h->key_splat, (const float4*)h->pc,
-               (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)h->pred_vertex, (float4*)h->pred_normal,
-               (uchar4*)h->pred_image, (uchar4*)h->pred_inst, h->pred_time, (float4*)h->fill_vertex, (float4*)h->fill_normal, (uchar4*)h->fill_image, h->key_ids,
-               h->key_both, (want & LIST_IDS) ? ids_out : (int32_t*)nullptr, (int*)nullptr, ff, (float*)nullptr, resolve_ids_step, (const int32_t*)nullptr, fo,
-               raw_ids ? (const Hot*)h->frame_hot : (const Hot*)nullptr);
+        SplatResolve a{"splat_resolve", pred_images(h)};
+        a.d_pose_inv = d_pose_inv; a.fill_in = true; a.ids_out = (want & LIST_IDS) ? ids_out : nullptr; a.ids_step = resolve_ids_step; a.fold = ff; a.fo = fo;
+        a.hot = raw_ids ? (const Hot*)h->frame_hot : nullptr;
+        launch_splat_resolve(h, c, a);
         if (ff.acc) return;   // (the view-list pass leaves list 0 alone: nothing to re-arm)
-    } else if (want & LIST_IDS) LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, ids_out);
-    // dense flag, list re-arm and (frame path: the id image is ids_after) the whetherDoSegmentation sums
-    const int seg = frame_sums && (want & LIST_IDS);   // only the frame's own render feeds whetherDoSegmentation (not the re-render after a compaction)
-    const int ds = 10, nseg = seg ? cdiv(cdiv(h->w, ds) * cdiv(h->h, ds), 256) : 0;
-    LAUNCH(h, "raster_finish", dim3(1 + nseg), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, (want & LIST_SPLAT) ? 1 : 0, h->ids_after,
-           (const float4*)h->votes, h->cap, ds, h->d_list_ctr, ifx_idmap(h));
+    } else if (want & LIST_IDS) launch_ids_resolve(h, ids_out);
+    // dense flag, list re-arm and (frame path: the id image is ids_after) the whetherDoSegmentation sums: only the frame's own render feeds them (not the re-render after a compaction)
+    launch_raster_finish(h, (want & LIST_SPLAT) ? 1 : 0, frame_sums && (want & LIST_IDS), nullptr, nullptr, nullptr);
 }
-static void splat_pass(ifx* h, const float* d_pose_inv, int time, int maxTime) { raster_pass(h, d_pose_inv, time, maxTime, LIST_SPLAT, nullptr); }
 
 static void ids_pass(ifx* h, const float* d_pose_inv, int mode, int32_t* out)
 {
     if (h->opt_id_rule && !h->own) {   // option id_rule: the reference's quads, both modes
-        Cam c = make_cam(h);
-        c.srank = 0; c.sn = 1;
-        if (mode == 1)
-            LAUNCH(h, "ids_raster_quad_inst", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster_quad<2>, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
-                   (const float4*)h->votes, c, h->key_ids, 1);
-        else
-            LAUNCH(h, "ids_raster_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster_quad<1>, (const DevState*)h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
-                   (const float4*)h->votes, c, h->key_ids, 1);
-        LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, out);
+        launch_raster_quad(h, mode == 1 ? "ids_raster_quad_inst" : "ids_raster_quad", d_pose_inv, whole_cam(h), mode == 1, 1);
+        launch_ids_resolve(h, out);
         return;
     }
     if (mode != 1) { raster_pass(h, d_pose_inv, 0, 0, LIST_IDS, out); return; }
     Cam c = make_cam(h);   // INSTANCECOMPARE also reads the 192 B of votes: one-kernel version
     LAUNCH(h, "ids_raster_inst", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_raster<2>, h->d_state, d_pose_inv, (const float4*)h->pc, (const float4*)h->nr,
            (const float2*)h->tm, (const float4*)h->votes, h->cap, c, 0, 0, h->key_ids);
-    LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, out);
+    launch_ids_resolve(h, out);
 }
 
 // The frame path renders the id image on the sampled lattice only (ifx_map_predict); whoever needs the whole image -- a segmentation call, ifx_ids_after,
@@ -2242,10 +2313,8 @@ int ifx_ids_ensure(ifx* h)
         return IFX_OK;
     }
     if (h->ids_view_ok && !h->own && !h->opt_id_rule) {   // nothing touched the store, the pose or the cached view list since the frame drew its lattice from it: the rest of the image from the same list
-        Cam c = make_cam(h);
-        c.srank = 0; c.sn = 1;
-        launch_raster_view(h, "raster_view_ids", c, LIST_IDS, 1, false, nullptr);
-        LAUNCH(h, "ids_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_ids_resolve, h->key_ids, h->P, h->ids_after);
+        launch_raster_view(h, "raster_view_ids", whole_cam(h), LIST_IDS, 1, h->opt_raster_earlyz, false, nullptr);
+        launch_ids_resolve(h, h->ids_after);
     } else
         ids_pass(h, nullptr, 0, h->ids_after);   // (all slots, per-pass cull: unstable surfels -- the only ones the view list's age rule concerns -- are never drawn here)
     h->ids_full_valid = 1;
@@ -2698,7 +2767,15 @@ __global__ void k_compact_count(DevState* st, const int* total)
     if (threadIdx.x == 0) { st->count = *total; st->n_dead = 0; st->vl_valid = 0; st->first_live = 0; }   // slots renumbered: the view list is void
 }
 
-static void ids_pass(ifx* h, const float* d_pose_inv, int mode, int32_t* out);
+// the flagged slots of [0, n) (ranks in scan_out) into the second buffer set, which becomes the store
+static void scatter_and_swap(ifx* h, int n)
+{
+    LAUNCH(h, "compact_scatter", dim3(cdiv(n, 256)), dim3(256), k_compact_scatter, h->scan_flags, h->scan_out, n, (const float4*)h->pc, (const float4*)h->nr,
+           (const float2*)h->col, (const float2*)h->tm, (const float4*)h->ic, (const float4*)h->votes, (const int32_t*)h->labels, (float4*)h->pc2, (float4*)h->nr2,
+           (float2*)h->col2, (float2*)h->tm2, (float4*)h->ic2, (float4*)h->votes2, h->labels2, (const uint32_t*)h->seq, h->seq2);
+    std::swap(h->pc, h->pc2); std::swap(h->nr, h->nr2); std::swap(h->col, h->col2); std::swap(h->tm, h->tm2); std::swap(h->ic, h->ic2); std::swap(h->votes, h->votes2); std::swap(h->labels, h->labels2); std::swap(h->seq, h->seq2);
+}
+static void launch_alive_flags(ifx* h, int n) { LAUNCH(h, "alive_flags", dim3(cdiv(n, 256)), dim3(256), k_alive_flags, h->d_state, (const float2*)h->tm, h->scan_flags, n); }
 int ifx_compact_enqueue(ifx* h, int refresh_ids)
 {
     h->ids_view_ok = 0;
@@ -2706,13 +2783,10 @@ int ifx_compact_enqueue(ifx* h, int refresh_ids)
     ifx_vlist_reap(h);   // slots the view list left out may have outlived the age rule: tombstone them before the live ranks are taken
     // alive flags over the host-known upper bound of slots; scan; scatter into the second buffer set; swap
     int n = h->cap;
-    LAUNCH(h, "alive_flags", dim3(cdiv(n, 256)), dim3(256), k_alive_flags, h->d_state, (const float2*)h->tm, h->scan_flags, n);
+    launch_alive_flags(h, n);
     ifx_scan_exclusive(h, h->scan_flags, n, h->scan_out, &h->d_state->seg_counts[1]);
-    LAUNCH(h, "compact_scatter", dim3(cdiv(n, 256)), dim3(256), k_compact_scatter, h->scan_flags, h->scan_out, n, (const float4*)h->pc, (const float4*)h->nr,
-           (const float2*)h->col, (const float2*)h->tm, (const float4*)h->ic, (const float4*)h->votes, (const int32_t*)h->labels, (float4*)h->pc2, (float4*)h->nr2,
-           (float2*)h->col2, (float2*)h->tm2, (float4*)h->ic2, (float4*)h->votes2, h->labels2, (const uint32_t*)h->seq, h->seq2);
+    scatter_and_swap(h, n);
     LAUNCH(h, "compact_count", dim3(1), dim3(64), k_compact_count, h->d_state, &h->d_state->seg_counts[1]);
-    std::swap(h->pc, h->pc2); std::swap(h->nr, h->nr2); std::swap(h->col, h->col2); std::swap(h->tm, h->tm2); std::swap(h->ic, h->ic2); std::swap(h->votes, h->votes2); std::swap(h->labels, h->labels2); std::swap(h->seq, h->seq2);
     if (refresh_ids && !h->own) { ids_pass(h, nullptr, 0, h->ids_after); h->ids_full_valid = 1; }   // slot numbers changed: re-render the id image (a sharded map's id image holds creation numbers: nothing changed)
     return IFX_OK;
 }
@@ -2914,11 +2988,8 @@ static void clean_pass(ifx* h, const float* d_pose_inv, int time, int part = 0)
     if (part != 2) LAUNCH(h, "cull_clean", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_clean, h->d_state, d_pose_inv, (const float4*)h->pc, (const float2*)h->tm, c, time, h->key_index,
            h->list_b, h->list_c);
     if (part == 1) return;
-    LAUNCH(h, "index_resolve_taps", dim3(cdiv(h->P, 256)), dim3(256), k_index_resolve, h->d_state, d_pose_inv, h->key_index, (const float4*)h->pc, (const float4*)h->nr,
-           (const float2*)h->col, (const float2*)h->tm, h->P, (uint32_t*)nullptr, (float4*)nullptr, (float4*)nullptr, (float4*)nullptr, time, h->cfg.confidence,
-           (float4*)h->index_tap, c);
-    LAUNCH(h, "clean_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_clean_list, h->d_state, d_pose_inv, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm,
-           (const float4*)h->index_tap, h->list_b, h->list_c);
+    launch_index_resolve(h, d_pose_inv, c, time, INDEX_TAPS, nullptr, nullptr);
+    launch_clean_list(h, d_pose_inv, c, time);
     if (deform) {
         LAUNCH_SMEM(h, "deform", dim3(MAP_BLOCKS), dim3(256), (size_t)h->graph_nodes * 64, k_deform, h->d_state, d_pose_inv, h->d_graph, h->graph_nodes, h->graph_is_fern, time, c,
                     (const float4*)h->old_vertex, (float4*)h->pc, (float4*)h->nr, (float2*)h->tm);
@@ -2932,14 +3003,14 @@ static void clean_pass(ifx* h, const float* d_pose_inv, int time, int part = 0)
 // ---- frame path through the cached view list
 __global__ void k_vlist_invalidate(DevState* st) { if (threadIdx.x == 0) st->vl_valid = 0; }
 void hs_invalidate_view(ifx* h) { h->ids_view_ok = 0; LAUNCH(h, "vlist_invalidate", dim3(1), dim3(64), k_vlist_invalidate, h->d_state); }
+static void launch_vlist_decide(ifx* h, int force) { LAUNCH(h, "vlist_decide", dim3(1), dim3(64), k_vlist_decide, h->d_state, h->d_list_ctr, force); }
 static bool use_view_list(ifx* h) { return h->opt_vlist && h->shard_n <= 1 && !h->own && !h->opt_reference_passes && h->graph_nodes == 0 && !h->view_block && h->tick > 1; }
 // the same path for the frames of a spatially sharded map (ifx_map_owner_phase): the lists are per-rank supersets of what the rank's shard can show, every pass re-tests its
 // entries with the per-pass rule, keys carry creation numbers (key_id) -- the exactness argument is the unsharded one
 static bool use_view_list_own(ifx* h) { return h->opt_vlist && h->own && !h->opt_reference_passes && h->graph_nodes == 0 && !h->view_block; }
 static void view_scan(ifx* h, int time)
 {
-    Cam c = make_cam(h);
-    c.srank = 0; c.sn = 1;
+    const Cam c = whole_cam(h);
     // raw output in the clean pass's lists 1, 2 (free at this point of a frame and between frames), then concatenated into list_v / list_vi
     LAUNCH(h, "cull_frame", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_frame, h->d_state, (const float4*)h->pc, (float4*)h->pc, (float2*)h->tm, c, make_planes(c), time, h->list_b, h->list_c,
            h->hot_valid ? (Hot*)h->hot : (Hot*)nullptr,   // (the age rule's tombstones go into the gathered copy too while it is valid)
@@ -2954,33 +3025,25 @@ int ifx_vlist_reap(ifx* h)
     if (!h->view_dirty) return IFX_OK;
     h->view_dirty = 0;
     h->ids_view_ok = 0;
-    LAUNCH(h, "vlist_decide", dim3(1), dim3(64), k_vlist_decide, h->d_state, h->d_list_ctr, 1);
+    launch_vlist_decide(h, 1);
     view_scan(h, h->last_clean_time);
     return IFX_OK;
 }
 static void index_list_pass(ifx* h, int time, bool taps)
 {
-    Cam c = make_cam(h);
-    c.srank = 0; c.sn = 1;
-    LAUNCH(h, "index_list", dim3(h->opt_index_blocks > 0 ? h->opt_index_blocks : LIST_BLOCKS), dim3(MAP_THREADS), k_index_list, (const DevState*)h->d_state, (const float4*)h->pc, (const float2*)h->tm, c, time, h->list_v, h->key_index, (const Hot*)h->frame_hot);
-    if (!taps)
-        LAUNCH(h, "index_resolve", dim3(cdiv(h->P, 256)), dim3(256), k_index_resolve, h->d_state, (const float*)nullptr, h->key_index, (const float4*)h->pc, (const float4*)h->nr,
-               (const float2*)h->col, (const float2*)h->tm, h->P, h->index_id, (float4*)h->index_vc, (float4*)nullptr, (float4*)h->index_nr, time, h->cfg.confidence, (float4*)nullptr, c,
-               (const int32_t*)nullptr, (const Hot*)h->frame_hot);
-    else
-        LAUNCH(h, "index_resolve_taps", dim3(cdiv(h->P, 256)), dim3(256), k_index_resolve, h->d_state, (const float*)nullptr, h->key_index, (const float4*)h->pc, (const float4*)h->nr,
-               (const float2*)h->col, (const float2*)h->tm, h->P, (uint32_t*)nullptr, (float4*)nullptr, (float4*)nullptr, (float4*)nullptr, time, h->cfg.confidence, (float4*)h->index_tap, c,
-               (const int32_t*)nullptr, (const Hot*)h->frame_hot);
+    const Cam c = whole_cam(h);
+    launch_index_list(h, c, time, (const Hot*)h->frame_hot);
+    launch_index_resolve(h, nullptr, c, time, taps ? INDEX_TAPS : INDEX_ASSOC, nullptr, (const Hot*)h->frame_hot);
 }
 
-// the clean pass and the append of a view-list frame as launches of their own (k_clean_view ; k_new_flags_count ; k_append_scan)
+// the clean pass and the append of a view-list frame as launches of their own (k_clean_view ; k_new_flags_count ; k_append_scan), sharded map or not
 static void view_clean_append(ifx* h, const Cam& c, int time)
 {
     h->hot_valid = 0;
     LAUNCH(h, "clean_view", dim3(h->opt_clean_blocks > 0 ? h->opt_clean_blocks : 2 * LIST_BLOCKS), dim3(MAP_THREADS), k_clean_view, h->d_state, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm,
            (const float4*)h->index_tap, h->list_v);
     launch_new_flags_count(h, nullptr, c, time);
-    launch_append_scan(h, c, time, h->own ? (unsigned int*)nullptr : h->list_v);
+    launch_append_scan(h, c, time, h->list_v);
 }
 
 // EF/ElasticFusion.cpp:620-694 without the loop-closure branches
@@ -2991,15 +3054,13 @@ int ifx_map_frame(ifx* h)
     h->ids_view_ok = 0;
     age_epoch_begin(h, h->tick);
     if (use_view_list(h)) {
-        Cam c = make_cam(h);
-        c.srank = 0; c.sn = 1;
+        const Cam c = whole_cam(h);
         const int time = h->tick;
         // Option clean_raster (default): the clean, the new surfels' flags and the append are left to the end-of-frame prediction (ifx_map_predict): ONE walk of the
         // view list cleans and rasterises (+ the flags), then the append, then the resolve.  Only when that prediction will take the view-list raster, and while no new
         // surfel can be drawn in the frame that creates it: its confidence starts at most at max(1, weight multiplier) (confidence_fn, k_track_end), the renders draw
         // from the threshold on (splat.vert:56-65, surfel_ids.vert:45).
-        const bool fused = h->opt_clean_raster && !h->opt_compact_every_frame && h->last_compact_tick != h->tick && h->opt_raster_tiles <= 0 && !h->opt_raster_lds &&
-                           h->cfg.confidence > fmaxf(1.f, h->frame_weight_mult);
+        const bool fused = clean_raster_allowed(h) && !h->opt_raster_lds;
         // the gathered copy of the store ("hot records") serves the frames that take the fused path: rebuilt here when something outside the frame path wrote the store since
         Hot* hot = nullptr;
         if (fused && h->opt_hot) {
@@ -3046,28 +3107,16 @@ int ifx_map_frame(ifx* h)
 int ifx_map_predict_loop_closure(ifx* h)
 {
     // both renders see the same map at the same pose and differ only in the time window: one scan of the store, one raster launch (two key images)
-    Cam c = make_cam(h);
-    c.srank = 0; c.sn = 1;
+    const Cam c = whole_cam(h);
     const bool by_view = use_view_list(h);
     if (by_view) {   // the frame's view lists hold every stable surfel in view, inside the time window or not: the scan this frame needs anyway, taken first
         view_scan(h, h->tick);
         h->view_scan_tick = h->tick;
-        launch_raster_view(h, "raster_view_lc", c, LIST_SPLAT | LIST_DUAL, 1, false, nullptr);
-    } else {
-    LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, (const float*)nullptr, (const float4*)h->pc, (const float2*)h->tm, c, h->tick, h->tick,
-           LIST_SPLAT | LIST_DUAL, h->list_a, (unsigned int*)nullptr, 0);
-    LAUNCH(h, "raster_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_raster_list, h->d_state, (const float*)nullptr, (const float4*)h->pc, (const float4*)h->nr, c, h->list_a, h->key_splat,
-           h->key_ids, h->key_both, 1, (const int*)nullptr);
-    }
-    {
-        ResolveTarget ta, to;
-        ta.keys = h->key_splat; ta.pv = (float4*)h->act_vertex; ta.pn = (float4*)h->act_normal; ta.pimg = (uchar4*)h->act_image; ta.pinst = (uchar4*)h->act_inst; ta.ptime = h->act_time;
-        to.keys = h->key_ids; to.pv = (float4*)h->old_vertex; to.pn = (float4*)h->old_normal; to.pimg = (uchar4*)h->old_image; to.pinst = (uchar4*)h->old_inst; to.ptime = h->old_time;
-        LAUNCH(h, "splat_resolve_lc", dim3(cdiv(h->w, 32), cdiv(h->h, 8), 2), dim3(32, 8), k_splat_resolve_pair, (const DevState*)h->d_state, (const float4*)h->pc, (const float4*)h->nr,
-               (const float2*)h->col, (const float2*)h->tm, c, (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, ta, to);
-    }
-    if (!by_view)   // (re-arms work list 0, which the view-list path does not touch)
-        LAUNCH(h, "raster_finish", dim3(1), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, 0, h->ids_after, (const float4*)h->votes, h->cap, 10, h->d_list_ctr, ifx_idmap(h));
+        launch_raster_view(h, "raster_view_lc", c, LIST_SPLAT | LIST_DUAL, 1, h->opt_raster_earlyz, false, nullptr);
+    } else launch_dual_raster(h, c);
+    LAUNCH(h, "splat_resolve_lc", dim3(cdiv(h->w, 32), cdiv(h->h, 8), 2), dim3(32, 8), k_splat_resolve_pair, (const DevState*)h->d_state, (const float4*)h->pc, (const float4*)h->nr,
+           (const float2*)h->col, (const float2*)h->tm, c, (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, act_images(h, h->key_splat), old_images(h, h->key_ids));
+    if (!by_view) launch_raster_finish(h, 0, false, nullptr, nullptr, nullptr);   // (re-arms work list 0, which the view-list path does not touch)
     return IFX_OK;
 }
 
@@ -3079,8 +3128,7 @@ int ifx_map_predict(ifx* h)
     // the tiled rasteriser only on request: at 1280x960 / 20 M surfels the view-list rasteriser takes 455 us where cull + bin + tile raster take 744 (profiles/archive/r02_o_1280_20m.txt)
     const bool tiles = h->opt_raster_tiles > 0;
     if (h->view_frame && !(h->opt_compact_every_frame || h->last_compact_tick == h->tick) && !tiles) {   // the frame built / checked the view list and nothing renumbered the store since
-        Cam c = make_cam(h);
-        c.srank = 0; c.sn = 1;
+        const Cam c = whole_cam(h);
         // The id image has one consumer per frame -- whetherDoSegmentation's sums over every 10th pixel -- and a full-image consumer only when a segmentation call, a
         // download or the display asks for it: the frame renders the sampled lattice only (the id half of this pass: 71 -> 40 us), ifx_ids_ensure the rest on demand.
         const int ids_step = (h->opt_lazy_ids && !h->ids_full_hint && (want & LIST_IDS)) ? 10 : 1;
@@ -3090,23 +3138,18 @@ int ifx_map_predict(ifx* h)
         h->ids_view_ok = ids_step > 1;
         if (h->clean_raster_pending) {   // the frame's clean + new-surfel flags in the raster's walk, then the append, then the resolve (see ifx_map_frame)
             h->clean_raster_pending = 0;
-            const int nb_new = cdiv(h->P, NEW_PER_BLOCK);
-            CleanArgs ca;
-            ca.pc_rw = (float4*)h->pc; ca.tm_rw = (float2*)h->tm; ca.tap = (const float4*)h->index_tap; ca.nf_blocks = nb_new; ca.assoc = h->assoc_target; ca.mpc = (const float4*)h->meas_pc;
-            ca.mnr = (const float4*)h->meas_nr; ca.flags = h->scan_flags; ca.block_counts = h->scan_block; ca.hot = (Hot*)h->frame_hot;
-            launch_raster_view(h, "clean_raster_view", c, want_walk, ids_step, false, &ca);
+            const CleanArgs ca = frame_clean_args(h, (Hot*)h->frame_hot);
+            launch_raster_view(h, "clean_raster_view", c, want_walk, ids_step, h->opt_raster_earlyz, false, &ca);
             launch_append_scan(h, c, h->tick, h->list_v, (Hot*)h->frame_hot);
             raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, true, ids_step, true);
         } else {
-            launch_raster_view(h, "raster_view", c, want_walk, ids_step, h->opt_raster_lds != 0, nullptr);
+            launch_raster_view(h, "raster_view", c, want_walk, ids_step, h->opt_raster_earlyz, h->opt_raster_lds != 0, nullptr);
             raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true, 2, 0, true, ids_step);   // resolve + the end-of-pass sums in the same launch
         }
     } else {
         if (h->clean_raster_pending) {   // (the host-side conditions of the two functions are the same: never) -- the deferred passes as launches of their own
             h->clean_raster_pending = 0;
-            Cam cc = make_cam(h);
-            cc.srank = 0; cc.sn = 1;
-            view_clean_append(h, cc, h->tick);
+            view_clean_append(h, whole_cam(h), h->tick);
         }
         raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true);
         if (want & LIST_IDS) { h->ids_full_valid = 1; h->ids_sparse_frame = 0; }
@@ -3201,17 +3244,22 @@ __global__ void k_fill_in(Cam c, const uint8_t* __restrict__ rgb, const uint16_t
     } else fn[k] = no;
 }
 
+// sharded map, behind the exchange of the prediction: fill-in and dense flag, replicated; mass_in: the summed vote mass of whetherDoSegmentation (null: none travelled)
+static void launch_fill_in_finish(ifx* h, const Cam& c, int* mass_in)
+{
+    LAUNCH(h, "fill_in", dim3(cdiv(h->w, 32), cdiv(h->h, 8)), dim3(32, 8), k_fill_in, c, (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, (float4*)h->pred_vertex,
+           (const float4*)h->pred_normal, (const uchar4*)h->pred_image, (float4*)h->fill_vertex, (float4*)h->fill_normal, (uchar4*)h->fill_image, (const float*)h->pred_conf);
+    launch_raster_finish(h, 1, false, nullptr, mass_in, nullptr);
+}
+
 // first frame: the dense initialisation is computed by every rank, which then keeps its own surfels (creation numbers = the unsharded slots)
 static void owner_filter(ifx* h)
 {
     const int n = h->cap;
     LAUNCH(h, "owner_flags", dim3(cdiv(n, 256)), dim3(256), k_owner_flags, (const DevState*)h->d_state, (const float4*)h->pc, h->own_g, h->cfg.rank, h->scan_flags, n);
     ifx_scan_exclusive(h, h->scan_flags, n, h->scan_out, &h->d_state->seg_counts[1]);
-    LAUNCH(h, "compact_scatter", dim3(cdiv(n, 256)), dim3(256), k_compact_scatter, h->scan_flags, h->scan_out, n, (const float4*)h->pc, (const float4*)h->nr,
-           (const float2*)h->col, (const float2*)h->tm, (const float4*)h->ic, (const float4*)h->votes, (const int32_t*)h->labels, (float4*)h->pc2, (float4*)h->nr2,
-           (float2*)h->col2, (float2*)h->tm2, (float4*)h->ic2, (float4*)h->votes2, h->labels2, (const uint32_t*)h->seq, h->seq2);
+    scatter_and_swap(h, n);
     LAUNCH(h, "owner_count", dim3(1), dim3(64), k_owner_count, h->d_state, &h->d_state->seg_counts[1]);
-    std::swap(h->pc, h->pc2); std::swap(h->nr, h->nr2); std::swap(h->col, h->col2); std::swap(h->tm, h->tm2); std::swap(h->ic, h->ic2); std::swap(h->votes, h->votes2); std::swap(h->labels, h->labels2); std::swap(h->seq, h->seq2);
 }
 
 // The pixels a surfel covers in BOTH renders of a raster pass went to key_both (one atomic instead of two); before the keys travel they are folded back
@@ -3244,36 +3292,40 @@ __global__ void k_own_merge_translate(unsigned long long* __restrict__ ks, unsig
     else { const unsigned int s_ = (unsigned int)(c & 0xFFFFFFFFull); slot_i[k] = (int32_t)s_; ki[k] = (c & 0xFFFFFFFF00000000ull) | (unsigned long long)seq[s_]; }
 }
 
+#define OWN_FIRST_LIVE(h, out) do { if ((out) && (h)->opt_own_first_live) LAUNCH((h), "own_first_live", dim3(1), dim3(1), k_own_first_live, (const DevState*)(h)->d_state, (const float2*)(h)->tm, (const uint32_t*)(h)->seq, (out)); } while (0)
+#define OWN_GFL(h, out) (const DevState*)(h)->d_state, (const float2*)(h)->tm, ((h)->opt_own_first_live ? (out) : (unsigned long long*)nullptr)
+// The index projection of the view list on a sharded map.  own_fast: the local keys carry slots, and k_own_translate swaps in the creation numbers before they travel.
+// with_word: also the "surfel 0" word that travels with these keys (behind the view-list scan, whose age rule removes surfels).
+static void own_index_list(ifx* h, const Cam& c, int time, bool with_word)
+{
+    Cam cl = c;
+    if (h->own_fast) { cl.own_n = 0; cl.raw_slots = 1; }
+    launch_index_list(h, cl, time, nullptr);
+    if (h->own_fast)
+        LAUNCH(h, "own_translate", dim3(cdiv(h->P, 256)), dim3(256), k_own_translate, h->key_index, h->P, (const uint32_t*)h->seq, h->own_slot_img, with_word ? (const DevState*)h->d_state : nullptr,
+               with_word ? (const float2*)h->tm : nullptr, (with_word && h->opt_own_first_live) ? h->gfl_index : nullptr);
+    else if (with_word) OWN_FIRST_LIVE(h, h->gfl_index);
+}
+// key_both folded back into the two renders' key images before they travel, and the "surfel 0" word behind them
+static void own_merge_both(ifx* h) { LAUNCH(h, "merge_both", dim3(cdiv(h->P, 256)), dim3(256), k_merge_both, h->key_splat, h->key_ids, h->key_both, h->P); OWN_FIRST_LIVE(h, h->gfl_splat); }
+static void launch_own_ids_pack(ifx* h, unsigned long long* dst) { LAUNCH(h, "own_ids_pack", dim3(1), dim3(1024), k_own_ids_pack, (const unsigned long long*)h->key_ids, h->w, h->h, (const unsigned long long*)h->gfl_splat, dst); }
 // phase p of a frame of the sharded map; the buffers ifx_owner_exchange(p) lists are reduced across the ranks before phase p + 1 -- by the library itself
 // on its communicator (ifx_comm.hip: ifx_owner_process_frame_device), or by the caller (the emulation tests).  phase 104..106: ElasticFusion::predict
 // outside a frame (ifx_owner_predict_phase): phases 4..6 without the clean / append and without the whetherDoSegmentation sums.
-#define OWN_FIRST_LIVE(h, out) do { if ((out) && (h)->opt_own_first_live) LAUNCH((h), "own_first_live", dim3(1), dim3(1), k_own_first_live, (const DevState*)(h)->d_state, (const float2*)(h)->tm, (const uint32_t*)(h)->seq, (out)); } while (0)
-#define OWN_GFL(h, out) (const DevState*)(h)->d_state, (const float2*)(h)->tm, ((h)->opt_own_first_live ? (out) : (unsigned long long*)nullptr)
 int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
 {
     h->hot_valid = 0;
-    Cam c = make_cam(h);
-    c.srank = 0; c.sn = 1;
+    Cam c = whole_cam(h);
     if (h->gfl_index && phase >= 1 && phase <= 3) c.first_live = (const int*)h->gfl_index;   // (behind exchanges 0 / 2: the word that came with key_index; everywhere else the one behind [key_splat | key_ids])
     const int time = h->tick;
-    const dim3 b2(32, 8), g2(cdiv(h->w, 32), cdiv(h->h, 8));
     const bool in_frame = phase < 100 || phase >= 300;
     if (phase >= 105 && phase < 300) phase -= 100;
     if (first_frame) {
         switch (phase) {
         case 0: ifx_map_init_first(h); owner_filter(h); break;
         case 4: h->own_ids_lat = 0; raster_pass(h, nullptr, time, time, LIST_SPLAT, h->ids_after, false, 1); break;
-        case 5:
-            LAUNCH(h, "splat_resolve", g2, b2, k_splat_resolve, h->d_state, (const float*)nullptr, h->key_splat, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col,
-                   (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)h->pred_vertex, (float4*)h->pred_normal, (uchar4*)h->pred_image, (uchar4*)h->pred_inst, h->pred_time,
-                   (float4*)nullptr, (float4*)nullptr, (uchar4*)nullptr, h->key_ids, h->key_both, (int32_t*)nullptr, (int*)nullptr, FinishFold(), h->pred_conf);
-            break;
-        case 6:
-            LAUNCH(h, "fill_in", g2, b2, k_fill_in, c, (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, (float4*)h->pred_vertex, (const float4*)h->pred_normal,
-                   (const uchar4*)h->pred_image, (float4*)h->fill_vertex, (float4*)h->fill_normal, (uchar4*)h->fill_image, (const float*)h->pred_conf);
-            LAUNCH(h, "raster_finish", dim3(1), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, 1, h->ids_after, (const float4*)h->votes, h->cap, 10, h->d_list_ctr, ifx_idmap(h),
-                   (int*)nullptr, h->pred_tail);
-            break;
+        case 5: { SplatResolve a{"splat_resolve", pred_images(h)}; a.pconf = h->pred_conf; launch_splat_resolve(h, c, a); break; }
+        case 6: launch_fill_in_finish(h, c, h->pred_tail); break;   // (the tail whatever the caller, unlike phase 6 of a later frame)
         default: break;   // (incl. 7)
         }
         return IFX_OK;
@@ -3283,19 +3335,12 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
     // INACTIVE prediction from one scan of the local shard (as ifx_map_predict_loop_closure), the owners' winners of both renders, then the model-to-model
     // tracker replicated on the exchanged images (ifx_api.hip: owner_frame_phase)
     case 300:                                                                                               // local dual raster | [key_splat (ACTIVE) | key_ids (INACTIVE)]: MIN
-        LAUNCH(h, "cull_raster", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_cull_raster, h->d_state, (const float*)nullptr, (const float4*)h->pc, (const float2*)h->tm, c, time, time,
-               LIST_SPLAT | LIST_DUAL, h->list_a, (unsigned int*)nullptr, 0);
-        LAUNCH(h, "raster_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_raster_list, h->d_state, (const float*)nullptr, (const float4*)h->pc, (const float4*)h->nr, c, h->list_a, h->key_splat,
-               h->key_ids, h->key_both, 1, (const int*)nullptr);
+        launch_dual_raster(h, c);
         break;
     case 301:                                                                                               // owned winners of both renders | [act_* | old_*]: SUM
-        for (int old = 0; old < 2; old++)
-            LAUNCH(h, old ? "splat_resolve_old" : "splat_resolve_act", g2, b2, k_splat_resolve, h->d_state, (const float*)nullptr, old ? h->key_ids : h->key_splat, (const float4*)h->pc,
-                   (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)(old ? h->old_vertex : h->act_vertex),
-                   (float4*)(old ? h->old_normal : h->act_normal), (uchar4*)(old ? h->old_image : h->act_image), (uchar4*)(old ? h->old_inst : h->act_inst),
-                   old ? h->old_time : h->act_time, (float4*)nullptr, (float4*)nullptr, (uchar4*)nullptr, h->key_ids, h->key_both, (int32_t*)nullptr, (int*)nullptr, FinishFold());
-        LAUNCH(h, "raster_finish", dim3(1), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, 0, h->ids_after, (const float4*)h->votes, h->cap, 10, h->d_list_ctr, ifx_idmap(h),
-               (int*)nullptr, (int*)nullptr);
+        launch_splat_resolve(h, c, SplatResolve{"splat_resolve_act", act_images(h, h->key_splat)});
+        launch_splat_resolve(h, c, SplatResolve{"splat_resolve_old", old_images(h, h->key_ids)});
+        launch_raster_finish(h, 0, false, nullptr, nullptr, nullptr);
         break;
     case 0:                                                                                                 // local projection | keys: MIN
         age_epoch_begin(h, time);
@@ -3303,7 +3348,7 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
         h->view_frame = 0;
         h->ids_view_ok = 0;
         if (h->own_need_decide) {   // the pose came from the tracking rank (exchange 310): this rank has not yet asked whether its cached lists still cover it
-            LAUNCH(h, "vlist_decide", dim3(1), dim3(64), k_vlist_decide, h->d_state, h->d_list_ctr, 0);
+            launch_vlist_decide(h, 0);
             h->own_need_decide = 0;
         }
         h->own_fast = 0; h->own_fast_raster = 0;
@@ -3312,11 +3357,7 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
             h->view_frame = 1;
             if (!h->own_slot_img && hipMalloc(&h->own_slot_img, (size_t)h->P * 4 * sizeof(int32_t)) != hipSuccess) h->own_slot_img = nullptr;   // [index | splat | ids | association] slot images
             h->own_fast = h->own_slot_img != nullptr;
-            Cam cl = c;
-            if (h->own_fast) { cl.own_n = 0; cl.raw_slots = 1; }   // local keys carry slots; k_own_translate swaps in the creation numbers before they travel
-            LAUNCH(h, "index_list", dim3(h->opt_index_blocks > 0 ? h->opt_index_blocks : LIST_BLOCKS), dim3(MAP_THREADS), k_index_list, (const DevState*)h->d_state, (const float4*)h->pc, (const float2*)h->tm, cl, time, h->list_v, h->key_index);
-            if (h->own_fast) LAUNCH(h, "own_translate", dim3(cdiv(h->P, 256)), dim3(256), k_own_translate, h->key_index, h->P, (const uint32_t*)h->seq, h->own_slot_img, OWN_GFL(h, h->gfl_index));   // (the word: behind the view-list scan, whose age rule removes surfels)
-            else OWN_FIRST_LIVE(h, h->gfl_index);
+            own_index_list(h, c, time, true);
         } else {
             if (h->opt_vlist) hs_invalidate_view(h);   // no scan this frame: a device-side "valid" must never describe lists the host did not maintain
             index_pass(h, nullptr, time, true, 1);
@@ -3326,56 +3367,37 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
     case 1: index_pass(h, nullptr, time, true, 2, h->own_fast ? h->own_slot_img : nullptr); fuse_pass(h, nullptr, 0.f, time, 1); break;   // attributes of the winners this rank owns, association among them | assoc_key: MIN
     case 2:                                                                                                 // verdicts decoded, update (owned), post-fuse projection | keys: MIN
         fuse_pass(h, nullptr, 0.f, time, 2, h->own_fast ? h->own_slot_img : nullptr);
-        if (h->view_frame) {
-            Cam cl = c;
-            if (h->own_fast) { cl.own_n = 0; cl.raw_slots = 1; }
-            LAUNCH(h, "index_list", dim3(h->opt_index_blocks > 0 ? h->opt_index_blocks : LIST_BLOCKS), dim3(MAP_THREADS), k_index_list, (const DevState*)h->d_state, (const float4*)h->pc, (const float2*)h->tm, cl, time, h->list_v, h->key_index);
-            if (h->own_fast) LAUNCH(h, "own_translate", dim3(cdiv(h->P, 256)), dim3(256), k_own_translate, h->key_index, h->P, (const uint32_t*)h->seq, h->own_slot_img);
-        } else clean_pass(h, nullptr, time, 1);
+        if (h->view_frame) own_index_list(h, c, time, false);
+        else clean_pass(h, nullptr, time, 1);
         break;
     case 3:                                                                                                 // owned tap records | index_tap: SUM
-        LAUNCH(h, "index_resolve_taps", dim3(cdiv(h->P, 256)), dim3(256), k_index_resolve, h->d_state, (const float*)nullptr, h->key_index, (const float4*)h->pc, (const float4*)h->nr,
-               (const float2*)h->col, (const float2*)h->tm, h->P, (uint32_t*)nullptr, (float4*)nullptr, (float4*)nullptr, (float4*)nullptr, time, h->cfg.confidence,
-               (float4*)h->index_tap, c, (h->own_fast && h->view_frame) ? (const int32_t*)h->own_slot_img : (const int32_t*)nullptr);
+        launch_index_resolve(h, nullptr, c, time, INDEX_TAPS, (h->own_fast && h->view_frame) ? (const int32_t*)h->own_slot_img : nullptr, nullptr);
         break;
     case 4: {                                                                                               // clean (local), append (replicated list, owned kept), local raster | [key_splat | key_ids]: MIN
-        const int nb_new = cdiv(h->P, NEW_PER_BLOCK);
         const bool lat = h->opt_own_lazy_ids != 0;   // (a replicated switch: every rank's exchange 4 has the same form, whichever way its local raster went)
         bool whole_drawn = false;
         h->own_ids_lat = lat;
         // ONE walk of the view list cleans and rasterises (+ the new surfels' flags), then the append -- the single-GPU frame's form (ifx_map_frame, option clean_raster), under the
         // same conditions: the list is this frame's, nothing renumbers the shard in between, and no new surfel can be drawn in the frame that creates it.  The walk draws slots
         // (k_own_translate swaps in the creation numbers); its new-surfel blocks keep the owner filter of the Cam.
-        const bool fused = h->opt_clean_raster && h->view_frame && h->own_fast && !h->opt_compact_every_frame && h->last_compact_tick != h->tick && h->opt_raster_tiles <= 0 &&
-                           h->cfg.confidence > fmaxf(1.f, h->frame_weight_mult);
+        const bool fused = clean_raster_allowed(h) && h->view_frame && h->own_fast;
         if (fused) {
-            CleanArgs ca;
-            ca.pc_rw = (float4*)h->pc; ca.tm_rw = (float2*)h->tm; ca.tap = (const float4*)h->index_tap; ca.nf_blocks = nb_new; ca.assoc = h->assoc_target; ca.mpc = (const float4*)h->meas_pc;
-            ca.mnr = (const float4*)h->meas_nr; ca.flags = h->scan_flags; ca.block_counts = h->scan_block; ca.hot = nullptr;
-            LAUNCH(h, "clean_raster_view", dim3(nb_new + (h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS)), dim3(MAP_THREADS), (k_raster_view<false, true>), h->d_state, (const float4*)h->pc, (const float4*)h->nr,
-                   (const float2*)h->tm, c, time, time, LIST_SPLAT | LIST_IDS, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, 0, lat ? OWN_LAT_DS : 1, ca, (const DevState*)h->d_state);
+            const CleanArgs ca = frame_clean_args(h, nullptr);
+            launch_raster_view(h, "clean_raster_view", c, LIST_SPLAT | LIST_IDS, lat ? OWN_LAT_DS : 1, 0, false, &ca);
             launch_append_scan(h, c, time, h->list_v);
             h->last_clean_time = time;
             h->view_dirty = 1;
             h->own_fast_raster = h->own_fast;
         } else {
-        if (h->view_frame)
-            LAUNCH(h, "clean_view", dim3(h->opt_clean_blocks > 0 ? h->opt_clean_blocks : 2 * LIST_BLOCKS), dim3(MAP_THREADS), k_clean_view, h->d_state, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm,
-                   (const float4*)h->index_tap, h->list_v);
-        else
-        LAUNCH(h, "clean_list", dim3(LIST_BLOCKS), dim3(MAP_THREADS), k_clean_list, h->d_state, (const float*)nullptr, c, time, (float4*)h->pc, (const float4*)h->nr, (float2*)h->tm,
-               (const float4*)h->index_tap, h->list_b, h->list_c);
-        launch_new_flags_count(h, nullptr, c, time);
-        launch_append_scan(h, c, time, h->view_frame ? h->list_v : (unsigned int*)nullptr);
+        if (h->view_frame) view_clean_append(h, c, time);
+        else { launch_clean_list(h, nullptr, c, time); launch_new_flags_count(h, nullptr, c, time); launch_append_scan(h, c, time, nullptr); }
         h->last_clean_time = time;
         if (h->view_frame) h->view_dirty = 1;
         if (h->opt_compact_every_frame) ifx_compact_enqueue(h, 0);
         if (h->view_frame && !(h->opt_compact_every_frame || h->last_compact_tick == h->tick)) {   // the lists were built / checked by this frame and nothing renumbered the shard since
-            Cam cl = make_cam(h);   // (the store's arrays may have been swapped by a compaction earlier in this phase: taken afresh)
-            cl.srank = 0; cl.sn = 1;
+            Cam cl = whole_cam(h);   // (the store's arrays may have been swapped by a compaction earlier in this phase: taken afresh)
             if (h->own_fast) { cl.own_n = 0; cl.raw_slots = 1; }
-            LAUNCH(h, "raster_view", dim3(h->opt_view_blocks > 0 ? h->opt_view_blocks : 4 * LIST_BLOCKS), dim3(MAP_THREADS), (k_raster_view<false, false>), h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->tm, cl, time, time,
-                   LIST_SPLAT | LIST_IDS, h->list_v, h->list_vi, h->key_splat, h->key_ids, h->key_both, 0, lat ? OWN_LAT_DS : 1, CleanArgs{nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (const DevState*)h->d_state);   // (the whole id image travels with the splat keys; option own_lazy_ids: the sampled lattice)
+            launch_raster_view(h, "raster_view", cl, LIST_SPLAT | LIST_IDS, lat ? OWN_LAT_DS : 1, 0, false, nullptr);   // (the whole id image travels with the splat keys; option own_lazy_ids: the sampled lattice)
             h->own_fast_raster = h->own_fast;
         } else {
             raster_pass(h, nullptr, time, time, LIST_SPLAT | LIST_IDS, h->ids_after, false, 1);
@@ -3386,16 +3408,13 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
         if (h->own_fast_raster) {   // key_both folded into the two renders' images and the slots swapped for creation numbers, pixel by pixel (the slot images of the two renders follow the index pass's)
             LAUNCH(h, "own_merge_translate", dim3(cdiv(h->P, 256)), dim3(256), k_own_merge_translate, h->key_splat, h->key_ids, h->key_both, h->P, (const uint32_t*)h->seq, h->own_slot_img + (size_t)h->P,
                    h->own_slot_img + 2 * (size_t)h->P, OWN_GFL(h, h->gfl_splat));   // (the word: behind the clean and the append)
-        } else {
-            LAUNCH(h, "merge_both", dim3(cdiv(h->P, 256)), dim3(256), k_merge_both, h->key_splat, h->key_ids, h->key_both, h->P);
-            OWN_FIRST_LIVE(h, h->gfl_splat);
-        }
+        } else own_merge_both(h);
         if (lat) {   // [key_splat | the lattice's id keys | word]: packed in front of key_ids
-            if (!whole_drawn) LAUNCH(h, "own_ids_pack", dim3(1), dim3(1024), k_own_ids_pack, (const unsigned long long*)h->key_ids, h->w, h->h, (const unsigned long long*)h->gfl_splat, h->key_ids);
+            if (!whole_drawn) launch_own_ids_pack(h, h->key_ids);
             else {   // the per-pass raster drew every pixel: the rest of the image must be empty again before the next frame draws into it
                 const size_t L = (size_t)ifx_own_lattice(h);
                 if (!h->own_lat_tmp && hipMalloc(&h->own_lat_tmp, (L + 1) * 8) != hipSuccess) { h->err = "hipMalloc (own_lat_tmp)"; return IFX_E_HIP; }
-                LAUNCH(h, "own_ids_pack", dim3(1), dim3(1024), k_own_ids_pack, (const unsigned long long*)h->key_ids, h->w, h->h, (const unsigned long long*)h->gfl_splat, h->own_lat_tmp);
+                launch_own_ids_pack(h, h->own_lat_tmp);
                 HIPCHK(h, hipMemsetAsync(h->key_ids, 0xFF, (size_t)h->P * 8, h->cur));
                 HIPCHK(h, hipMemcpyAsync(h->key_ids, h->own_lat_tmp, (L + 1) * 8, hipMemcpyDeviceToDevice, h->cur));
             }
@@ -3405,29 +3424,22 @@ int ifx_map_owner_phase(ifx* h, int phase, bool first_frame)
     case 104:                                                                                               // ifx_owner_predict_phase: the local raster alone
         h->own_ids_lat = 0;
         raster_pass(h, nullptr, time, time, LIST_SPLAT | LIST_IDS, h->ids_after, false, 1);
-        LAUNCH(h, "merge_both", dim3(cdiv(h->P, 256)), dim3(256), k_merge_both, h->key_splat, h->key_ids, h->key_both, h->P);
-        OWN_FIRST_LIVE(h, h->gfl_splat);   // (an upload / a deformation may have come in between)
+        own_merge_both(h);   // (the word again: an upload / a deformation may have come in between)
         break;
     case 5: {                                                                                               // owned winners of the prediction; ids_after = creation numbers, from the keys; vote mass of the owned surfels under it | [pred_* | tail]: SUM
         const int lat = h->own_ids_lat;
         if (lat) LAUNCH(h, "own_ids_unpack", dim3(1), dim3(1024), k_own_ids_unpack, h->key_ids, h->w, h->h, h->gfl_splat);
         h->ids_full_valid = !lat; h->ids_sparse_frame = lat; h->ids_view_ok = 0;
-        LAUNCH(h, "splat_resolve", g2, b2, k_splat_resolve, h->d_state, (const float*)nullptr, h->key_splat, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col,
-               (const float2*)h->tm, c, h->rgb, h->depth_filt, (float4*)h->pred_vertex, (float4*)h->pred_normal, (uchar4*)h->pred_image, (uchar4*)h->pred_inst, h->pred_time,
-               (float4*)nullptr, (float4*)nullptr, (uchar4*)nullptr, h->key_ids, h->key_both, h->ids_after, (int*)nullptr, FinishFold(), h->pred_conf, lat ? OWN_LAT_DS : 1,
-               (in_frame && h->own_fast_raster) ? (const int32_t*)(h->own_slot_img + (size_t)h->P) : (const int32_t*)nullptr);
-        if (in_frame) {   // whetherDoSegmentation sums: empty pixels replicated, vote mass by the owners -> the tail of the prediction block
-            const int ds = 10, nseg = cdiv(cdiv(h->w, ds) * cdiv(h->h, ds), 256);
-            LAUNCH(h, "raster_finish", dim3(1 + nseg), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, 0, h->ids_after, (const float4*)h->votes, h->cap, ds, h->d_list_ctr, ifx_idmap(h),
-                   h->pred_tail, (int*)nullptr, h->own_fast_raster ? (const int32_t*)(h->own_slot_img + 2 * (size_t)h->P) : (const int32_t*)nullptr);
-        }
+        SplatResolve a{"splat_resolve", pred_images(h)};
+        a.ids_out = h->ids_after; a.ids_step = lat ? OWN_LAT_DS : 1; a.pconf = h->pred_conf;
+        a.own_slot = (in_frame && h->own_fast_raster) ? (const int32_t*)(h->own_slot_img + (size_t)h->P) : nullptr;
+        launch_splat_resolve(h, c, a);
+        if (in_frame)   // whetherDoSegmentation sums: empty pixels replicated, vote mass by the owners -> the tail of the prediction block
+            launch_raster_finish(h, 0, true, h->pred_tail, nullptr, h->own_fast_raster ? (const int32_t*)(h->own_slot_img + 2 * (size_t)h->P) : nullptr);
         break;
     }
     case 6:                                                                                                 // fill-in and dense flag on the exchanged prediction (replicated); takes the summed vote mass
-        LAUNCH(h, "fill_in", g2, b2, k_fill_in, c, (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, (float4*)h->pred_vertex, (const float4*)h->pred_normal,
-               (const uchar4*)h->pred_image, (float4*)h->fill_vertex, (float4*)h->fill_normal, (uchar4*)h->fill_image, (const float*)h->pred_conf);
-        LAUNCH(h, "raster_finish", dim3(1), dim3(256), k_raster_finish, h->d_state, (const uchar4*)h->pred_image, h->w, h->h, 1, h->ids_after, (const float4*)h->votes, h->cap, 10, h->d_list_ctr, ifx_idmap(h),
-               (int*)nullptr, in_frame ? h->pred_tail : (int*)nullptr);
+        launch_fill_in_finish(h, c, in_frame ? h->pred_tail : nullptr);
         break;
     case 7: break;                                                                                          // (the frame result is published by ifx_owner_frame_phase)
     default: return IFX_E_INVALID;
@@ -3467,7 +3479,7 @@ extern "C" int ifx_combined_predict(ifx_t* h, const float* pose16, int time, int
     float *dp, *di;
     int r = upload_pose(h, pose16, &dp, &di);
     if (r) return r;
-    splat_pass(h, di, time, max_time);
+    raster_pass(h, di, time, max_time, LIST_SPLAT, nullptr);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return IFX_OK;
 }
@@ -3517,7 +3529,7 @@ extern "C" int ifx_sample_graph_model(ifx_t* h, float* out_xyzt, int max_n)
     if (!h->d_sample) HIPCHK(h, hipMalloc(&h->d_sample, (size_t)cap_s * 16));
     if (max_n > cap_s) max_n = cap_s;
     const int n = h->cap;
-    LAUNCH(h, "alive_flags", dim3(cdiv(n, 256)), dim3(256), k_alive_flags, h->d_state, (const float2*)h->tm, h->scan_flags, n);
+    launch_alive_flags(h, n);
     ifx_scan_exclusive(h, h->scan_flags, n, h->scan_out, &h->d_state->seg_counts[1]);
     LAUNCH(h, "sample_graph", dim3(cdiv(n, 256)), dim3(256), k_sample_graph, h->d_state, h->scan_flags, h->scan_out, (const float4*)h->pc, (const float2*)h->tm,
            (float4*)h->d_sample, max_n);
@@ -3589,6 +3601,16 @@ __global__ void k_fern_resize(const uchar4* __restrict__ img, const float4* __re
     o_vert[t] = vo;
     o_norm[t] = no;
 }
+// The last predict() resampled into d_fern: [vertex | normal | rgb | instance rgb], n entries each.  tracked: the predict at the tracked pose (act* images, fill-in evaluated
+// at the samples: inside the fern callback), else the end-of-frame one.
+static void launch_fern_resize(ifx* h, int n, bool tracked)
+{
+    float4 *dv = (float4*)h->d_fern, *dn = dv + n;
+    uint8_t *di = (uint8_t*)(dn + n), *ds = di + (size_t)n * 3;
+    LAUNCH(h, "fern_resize", dim3(cdiv(n, 64)), dim3(64), k_fern_resize, (const uchar4*)(tracked ? h->act_image : h->fill_image), (const float4*)(tracked ? h->act_vertex : h->fill_vertex),
+           (const float4*)(tracked ? h->act_normal : h->fill_normal), (const uchar4*)(tracked ? h->act_inst : h->pred_inst), h->w, h->h, di, dv, dn, ds, tracked ? 1 : 0, make_cam(h),
+           (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt);
+}
 extern "C" int ifx_fern_frame(ifx_t* h, uint8_t* img_rgb, float* verts4, float* norms4, uint8_t* inst_rgb)
 {
     if (!h || !img_rgb || !verts4 || !norms4 || !inst_rgb) return IFX_E_INVALID;
@@ -3599,13 +3621,7 @@ extern "C" int ifx_fern_frame(ifx_t* h, uint8_t* img_rgb, float* verts4, float* 
     float4* dn = dv + n;
     uint8_t* di = (uint8_t*)(dn + n);
     uint8_t* ds = di + (size_t)n * 3;
-    // the last predict(): inside the fern callback the one at the tracked pose (act* images, fill-in evaluated at the samples), else the end-of-frame one
-    if (h->in_fern_cb)
-        LAUNCH(h, "fern_resize", dim3(cdiv(n, 64)), dim3(64), k_fern_resize, (const uchar4*)h->act_image, (const float4*)h->act_vertex, (const float4*)h->act_normal,
-               (const uchar4*)h->act_inst, h->w, h->h, di, dv, dn, ds, 1, make_cam(h), (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt);
-    else
-        LAUNCH(h, "fern_resize", dim3(cdiv(n, 64)), dim3(64), k_fern_resize, (const uchar4*)h->fill_image, (const float4*)h->fill_vertex, (const float4*)h->fill_normal,
-               (const uchar4*)h->pred_inst, h->w, h->h, di, dv, dn, ds, 0, make_cam(h), (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt);
+    launch_fern_resize(h, n, h->in_fern_cb != 0);
     HIPCHK(h, hipMemcpyAsync(verts4, dv, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(norms4, dn, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(img_rgb, di, (size_t)n * 3, hipMemcpyDeviceToHost, h->stream));
@@ -3624,13 +3640,7 @@ extern "C" int ifx_fern_frame_async(ifx_t* h)
     const size_t bytes = (size_t)n * (3 + 16 + 16 + 3);
     if (!h->d_fern) HIPCHK(h, hipMalloc(&h->d_fern, bytes + 64));
     if (!h->h_fern) { HIPCHK(h, hipHostMalloc((void**)&h->h_fern, bytes + 64)); HIPCHK(h, hipEventCreateWithFlags(&h->ev_fern, hipEventDisableTiming)); }
-    uint8_t* base = (uint8_t*)h->d_fern;
-    float4* dv = (float4*)base;
-    float4* dn = dv + n;
-    uint8_t* di = (uint8_t*)(dn + n);
-    uint8_t* ds = di + (size_t)n * 3;
-    LAUNCH(h, "fern_resize", dim3(cdiv(n, 64)), dim3(64), k_fern_resize, (const uchar4*)h->fill_image, (const float4*)h->fill_vertex, (const float4*)h->fill_normal,
-           (const uchar4*)h->pred_inst, h->w, h->h, di, dv, dn, ds, 0, make_cam(h), (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt);
+    launch_fern_resize(h, n, false);
     HIPCHK(h, hipMemcpyAsync(h->h_fern, h->d_fern, bytes, hipMemcpyDeviceToHost, h->stream));   // one copy: the staging buffer has the layout of the pinned one
     HIPCHK(h, hipEventRecord(h->ev_fern, h->stream));
     h->fern_pending = 1;

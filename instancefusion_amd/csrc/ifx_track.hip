@@ -2490,45 +2490,59 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
             }
         }
     }
+    // per level: does a finer level still iterate (if none does, the level's last iteration ends the run), and the scale of the level the iteration after its last one runs at
+    // (for the warp matrices the solve emits)
+    bool finer[IFX_NUM_PYRS];
+    float next_div[IFX_NUM_PYRS];
+    for (int i = 0, nl = -1; i < IFX_NUM_PYRS; i++) {   // nl: the nearest level below i that iterates
+        finer[i] = nl >= 0; next_div[i] = (float)(1 << (nl < 0 ? 0 : nl));
+        if (iterations[i] > 0) nl = i;
+    }
+    double* const gacc = (double*)((char*)st + offsetof(DevState, gn_acc));   // (accumulator rows, residual totals, ticket: DevState::gn_acc / gn_res / gn_ticket of `st`)
+    int* const gres = (int*)((char*)st + offsetof(DevState, gn_res));
+    // The arguments of level i's correspondence / residual launch and of the step of its iteration j.  What differs between the forms of the run is set by the caller:
+    // the block counts (nb*), check_skip, lctr, pro / pro_k.
+    auto pair_args = [&](int i) {
+        const float div = (float)(1 << i);
+        PairArgs pa;
+        pa.vmap_curr = p.vmap_curr[i]; pa.nmap_curr = p.nmap_curr[i]; pa.vmap_prev = p.vmap_prev[i]; pa.nmap_prev = p.nmap_prev[i];
+        pa.fx = c.fx / div; pa.fy = c.fy / div; pa.cx = c.cx / div; pa.cy = c.cy / div; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
+        pa.minScale = (float)(pow(minGrad[i], 2.0) / pow(sobelScale, 2.0)); pa.maxDepthDelta = 0.07f;
+        pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
+        pa.corres = (Corres8*)p.corres[i]; pa.w = p.w[i]; pa.h = p.h[i];
+        return pa;
+    };
+    auto step_args = [&](int i, int j) {
+        const float div = (float)(1 << i);
+        const bool last = j == iterations[i] - 1;
+        const float nd = last ? next_div[i] : div;
+        StepArgs sa;
+        sa.corres = (const Corres8*)p.corres[i]; sa.cloud = p.cloud[i]; sa.fx = c.fx / div; sa.fy = c.fy / div; sa.sobelScale = (float)sobelScale;
+        sa.dIdx = p.didx[i]; sa.dIdy = p.didy[i]; sa.w = p.w[i]; sa.h = p.h[i];
+        sa.icp = icp; sa.rgb = rgb; sa.icp_weight = icp_weight; sa.nfx = c.fx / nd; sa.nfy = c.fy / nd; sa.ncx = c.cx / nd; sa.ncy = c.cy / nd; sa.ki = kinv_of(sa.nfx, sa.nfy, sa.ncx, sa.ncy);
+        sa.final_iter = (last && !finer[i]) ? 1 : 0;   // the run's last iteration
+        sa.end_run = sa.final_iter; sa.commit = commit; sa.weight_mult = weight_mult;
+        return sa;
+    };
     if (frame_tracker && h->own && h->opt_own_track_rows && ifx_comm_ready(h) && h->own_track_rank < 0) {
         // the reductions over this rank's blocks + all-reduce + one-workgroup solve (k_icp_residual_rows above).  opt_own_track_rows_emulate = G > 1 (test switch): this ONE rank
         // plays G in turn into the same accumulator rows -- the partition's cover, without a second GPU
         const int Ge = h->opt_own_track_rows_emulate > 1 ? h->opt_own_track_rows_emulate : 0;
         const int sn = Ge ? Ge : h->own_g, r_lo = Ge ? 0 : h->cfg.rank, r_hi = Ge ? Ge : h->cfg.rank + 1;
-        double* const gacc = (double*)((char*)st + offsetof(DevState, gn_acc));
-        int* const gres = (int*)((char*)st + offsetof(DevState, gn_res));
         const int row = IFX_ACC_REPL * IFX_ACC_STRIDE;
         for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) {
             if (i == 0) ifx_enqueue_hinted_frame_side(h);
-            const float div = (float)(1 << i);
-            const float fx = c.fx / div, fy = c.fy / div, cx = c.cx / div, cy = c.cy / div;
             const int lw = p.w[i], lh = p.h[i], n = lw * lh;
             const int nbv = cdiv(red_blocks(h, n), sn), nbr = std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows);
             const int nb_rgb_v = cdiv(std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192), sn);
-            int nl = i - 1;
-            while (nl >= 0 && iterations[nl] == 0) nl--;
-            if (nl < 0) nl = 0;
-            const float ld = (float)(1 << nl);
-            PairArgs pa;
-            pa.vmap_curr = p.vmap_curr[i]; pa.nmap_curr = p.nmap_curr[i]; pa.vmap_prev = p.vmap_prev[i]; pa.nmap_prev = p.nmap_prev[i];
-            pa.fx = fx; pa.fy = fy; pa.cx = cx; pa.cy = cy; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
-            pa.minScale = (float)(pow(minGrad[i], 2.0) / pow(sobelScale, 2.0)); pa.maxDepthDelta = 0.07f;
-            pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
-            pa.corres = (Corres8*)p.corres[i]; pa.w = lw; pa.h = lh; pa.nb_icp = icp ? nbv : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = 0;
+            PairArgs pa = pair_args(i);
+            pa.nb_icp = icp ? nbv : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = 0;
             for (int j = 0; j < iterations[i]; j++) {
-                const float nd = (j == iterations[i] - 1) ? ld : div;
                 for (int r = r_lo; r < r_hi; r++)   // (the residual pass once: with the first of the launches)
                     LAUNCH(h, icp_name_rows(i), dim3(pa.nb_icp + (r == r_lo ? pa.nb_res : 0)), dim3(RED_THREADS), k_icp_residual_rows, (const DevState*)st, pa.nb_icp, lw, lh, gacc, gres, pa, r, sn);
                 if (icp && h->track_rc == IFX_OK) h->track_rc = ifx_comm_allreduce_f64(h, gacc, row);
-                StepArgs sa2;
-                sa2.corres = (const Corres8*)p.corres[i]; sa2.cloud = p.cloud[i]; sa2.fx = fx; sa2.fy = fy; sa2.sobelScale = (float)sobelScale;
-                sa2.dIdx = p.didx[i]; sa2.dIdy = p.didy[i]; sa2.w = lw; sa2.h = lh; sa2.nb = nb_rgb_v; sa2.nb_icp = pa.nb_icp; sa2.nb_res = pa.nb_res;
-                sa2.icp = icp; sa2.rgb = rgb; sa2.icp_weight = icp_weight; sa2.nfx = c.fx / nd; sa2.nfy = c.fy / nd; sa2.ncx = c.cx / nd; sa2.ncy = c.cy / nd; sa2.ki = kinv_of(sa2.nfx, sa2.nfy, sa2.ncx, sa2.ncy);
-                sa2.check_skip = 0;
-                bool later = false;
-                for (int q = i - 1; q >= 0; q--) later = later || iterations[q] > 0;
-                sa2.final_iter = (j == iterations[i] - 1 && !later) ? 1 : 0;
-                sa2.end_run = sa2.final_iter; sa2.commit = commit; sa2.weight_mult = weight_mult; sa2.lctr = h->d_list_ctr; sa2.pro = 0; sa2.pro_k = 0;
+                StepArgs sa2 = step_args(i, j);
+                sa2.nb = nb_rgb_v; sa2.nb_icp = pa.nb_icp; sa2.nb_res = pa.nb_res; sa2.check_skip = 0; sa2.lctr = h->d_list_ctr; sa2.pro = 0; sa2.pro_k = 0;
                 ended = ended || sa2.end_run;
                 if (rgb) {
                     for (int r = r_lo; r < r_hi; r++) LAUNCH(h, "rgb_step_rows", dim3(nb_rgb_v), dim3(RED_THREADS), k_rgb_step_rows, st, nb_rgb_v, lw, lh, sa2, r, sn);
@@ -2578,16 +2592,8 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         float div = (float)(1 << i);
         float fx = c.fx / div, fy = c.fy / div, cx = c.cx / div, cy = c.cy / div;
         int lw = p.w[i], lh = p.h[i], n = lw * lh, nb = red_blocks(h, n), nb_rgb = std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192);   // the photometric step's launch is dominated by the last block's hand-off and solve: fewer blocks, fewer partial rows (64: 16.9, 192: 15.3, 304: 16.1, 608: 18.5 us per launch)
-        // intrinsics of the level the iteration after this level's last one runs at (for the warp matrices the solve emits)
-        int nl = i - 1;
-        while (nl >= 0 && iterations[nl] == 0) nl--;
-        if (nl < 0) nl = 0;
-        const float ld = (float)(1 << nl);
-        PairArgs pa;
-        pa.vmap_curr = p.vmap_curr[i]; pa.nmap_curr = p.nmap_curr[i]; pa.vmap_prev = p.vmap_prev[i]; pa.nmap_prev = p.nmap_prev[i];
-        pa.fx = fx; pa.fy = fy; pa.cx = cx; pa.cy = cy; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
-        pa.minScale = (float)(pow(minGrad[i], 2.0) / pow(sobelScale, 2.0)); pa.maxDepthDelta = 0.07f;
-        pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
+        const float ld = next_div[i];   // the level the iteration after this level's last one runs at
+        PairArgs pa = pair_args(i);
         // The residual half of the launch is the slower one and scales with its blocks (its totals go through integer atomics, it has no partial rows for the
         // last block to sum): one pixel per thread, no loop -- 152 blocks 17.5 us, 304 blocks 13.3 us, 1200 blocks 11.3 us per launch at 640x480 (1053 -> 1102 frames/s).
         // One round of residency: the launch's blocks (ICP half + residual half) must all be on the GPU at once.  At 640x480 level 0 they were 456 + 1024 = 1480 against the 1024 the GPU holds
@@ -2596,38 +2602,31 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         // (profiles/r05_ai_ab_tracker_blocks.txt: 1514 -> 1561 frames/s).  The halves loop over their pixels anyway (grid-stride); opt_res_blocks > 0 overrides.
         const int res_round = std::max(128, h->icp_resident_blocks - (icp ? nb : 0));
         const int nbr = std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : res_round);
-        pa.corres = (Corres8*)p.corres[i]; pa.w = lw; pa.h = lh; pa.nb_icp = icp ? nb : 0; pa.nb_res = rgb ? nbr : 0;
-        double* const gacc = (double*)((char*)st + offsetof(DevState, gn_acc));
-        int* const gres = (int*)((char*)st + offsetof(DevState, gn_res));
-        pa.check_skip = frame_tracker ? 0 : 1;   // (accumulator rows, residual totals, ticket: DevState::gn_acc / gn_res / gn_ticket of `st`)
+        pa.nb_icp = icp ? nb : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = frame_tracker ? 0 : 1;
         if (persist_q[i] >= 0) {   // all iterations of the level in one persistent launch
             const int q = persist_q[i], nbp = persist_nb[i];
-            {
-                LevelArgs la;
-                la.vmap_curr = pa.vmap_curr; la.nmap_curr = pa.nmap_curr; la.vmap_prev = pa.vmap_prev; la.nmap_prev = pa.nmap_prev;
-                la.dIdx = pa.dIdx; la.dIdy = pa.dIdy; la.lastDepth = pa.lastDepth; la.nextDepth = pa.nextDepth; la.lastImage = pa.lastImage; la.nextImage = pa.nextImage;
-                la.cloud = p.cloud[i]; la.corres = (Corres8*)p.corres[i];
-                la.fx = fx; la.fy = fy; la.cx = cx; la.cy = cy; la.distThres = pa.distThres; la.angleThres = pa.angleThres; la.minScale = pa.minScale; la.maxDepthDelta = pa.maxDepthDelta;
-                la.sobelScale = (float)sobelScale;
-                la.w = lw; la.h = lh; la.iters = iterations[i]; la.icp = icp; la.rgb = rgb; la.icp_weight = icp_weight;
-                la.nfx = c.fx / ld; la.nfy = c.fy / ld; la.ncx = c.cx / ld; la.ncy = c.cy / ld;
-                la.ki_same = kinv_of(fx, fy, cx, cy); la.ki_next = kinv_of(la.nfx, la.nfy, la.ncx, la.ncy);
-                la.acc_base = persist_iters; la.level = i;   // (parity of the persistent kernel's double buffers: continuous over ITS launches, whatever two-launch levels lie between them)
-                persist_iters += iterations[i];
-                bool later = false;
-                for (int q2 = i - 1; q2 >= 0; q2--) later = later || iterations[q2] > 0;
-                la.final_level = later ? 0 : 1; la.commit = commit; la.weight_mult = weight_mult; la.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
-                if (q == 0) LAUNCH(h, "gn_level", dim3(nbp), dim3(RED_THREADS), k_gn_level<1>, st, la);
-                else if (q == 1) LAUNCH(h, "gn_level", dim3(nbp), dim3(RED_THREADS), k_gn_level<2>, st, la);
-                else if (q == 2) LAUNCH(h, "gn_level", dim3(nbp), dim3(RED_THREADS), k_gn_level<3>, st, la);
-                else LAUNCH(h, "gn_level", dim3(nbp), dim3(RED_THREADS), k_gn_level<4>, st, la);
-                LAUNCH(h, "gn_level_solo", dim3(1), dim3(RED_THREADS), k_gn_level_solo, st, la);   // the safety net: a no-op unless a meeting of the launch above did not happen
-                ended = ended || la.final_level;
-                continue;
-            }
+            LevelArgs la;
+            la.vmap_curr = pa.vmap_curr; la.nmap_curr = pa.nmap_curr; la.vmap_prev = pa.vmap_prev; la.nmap_prev = pa.nmap_prev;
+            la.dIdx = pa.dIdx; la.dIdy = pa.dIdy; la.lastDepth = pa.lastDepth; la.nextDepth = pa.nextDepth; la.lastImage = pa.lastImage; la.nextImage = pa.nextImage;
+            la.cloud = p.cloud[i]; la.corres = (Corres8*)p.corres[i];
+            la.fx = fx; la.fy = fy; la.cx = cx; la.cy = cy; la.distThres = pa.distThres; la.angleThres = pa.angleThres; la.minScale = pa.minScale; la.maxDepthDelta = pa.maxDepthDelta;
+            la.sobelScale = (float)sobelScale;
+            la.w = lw; la.h = lh; la.iters = iterations[i]; la.icp = icp; la.rgb = rgb; la.icp_weight = icp_weight;
+            la.nfx = c.fx / ld; la.nfy = c.fy / ld; la.ncx = c.cx / ld; la.ncy = c.cy / ld;
+            la.ki_same = kinv_of(fx, fy, cx, cy); la.ki_next = kinv_of(la.nfx, la.nfy, la.ncx, la.ncy);
+            la.acc_base = persist_iters; la.level = i;   // (parity of the persistent kernel's double buffers: continuous over ITS launches, whatever two-launch levels lie between them)
+            persist_iters += iterations[i];
+            la.final_level = finer[i] ? 0 : 1; la.commit = commit; la.weight_mult = weight_mult; la.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
+            auto go = [&](auto kernel) { LAUNCH(h, "gn_level", dim3(nbp), dim3(RED_THREADS), kernel, st, la); };
+            if (q == 0) go(k_gn_level<1>);   // (pixels per thread)
+            else if (q == 1) go(k_gn_level<2>);
+            else if (q == 2) go(k_gn_level<3>);
+            else go(k_gn_level<4>);
+            LAUNCH(h, "gn_level_solo", dim3(1), dim3(RED_THREADS), k_gn_level_solo, st, la);   // the safety net: a no-op unless a meeting of the launch above did not happen
+            ended = ended || la.final_level;
+            continue;
         }
         for (int j = 0; j < iterations[i]; j++) {
-            const float nd = (j == iterations[i] - 1) ? ld : div;
             // gn_prologue: iteration tail_k sums into parity tail_k & 1; from the tail's second iteration on, every block first solves the iteration before
             GnPro gp;
             gp.k = tail_k; gp.icp = icp; gp.rgb = rgb; gp.icp_weight = icp_weight; gp.nfx = fx; gp.nfy = fy; gp.ncx = cx; gp.ncy = cy; gp.ki = kinv_of(fx, fy, cx, cy);
@@ -2635,30 +2634,18 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
             double* const ga = it_pro ? gnp_acc_of(tail_k & 1) : gacc;
             int* const gr = it_pro ? gnp_res_of(tail_k & 1) : gres;
             double* const rrt_store = gnp_rrt_of((tail_k + 1) & 1);   // the increment after iteration tail_k - 1
-            const dim3 grid(pa.nb_icp + pa.nb_res);
-            if (it_pro && tail_k > 0) {
-                if (frame_tracker) LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, true>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-                else LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<true, true>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-            } else {
-                if (frame_tracker) LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<false, false>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-                else LAUNCH(h, icp_name[i], grid, dim3(RED_THREADS), (k_icp_residual<true, false>), st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store);
-            }
-            StepArgs sa2;
-            sa2.corres = (const Corres8*)p.corres[i]; sa2.cloud = p.cloud[i]; sa2.fx = fx; sa2.fy = fy; sa2.sobelScale = (float)sobelScale;
-            sa2.dIdx = p.didx[i]; sa2.dIdy = p.didy[i]; sa2.w = lw; sa2.h = lh; sa2.nb = nb_rgb; sa2.nb_icp = nb; sa2.nb_res = nbr;
-            sa2.icp = icp; sa2.rgb = rgb; sa2.icp_weight = icp_weight; sa2.nfx = c.fx / nd; sa2.nfy = c.fy / nd; sa2.ncx = c.cx / nd; sa2.ncy = c.cy / nd; sa2.ki = kinv_of(sa2.nfx, sa2.nfy, sa2.ncx, sa2.ncy);
-            sa2.check_skip = frame_tracker ? 0 : 1;
-            {   // is this the run's last iteration?  (no level below this one iterates)
-                bool later = false;
-                for (int q = i - 1; q >= 0; q--) later = later || iterations[q] > 0;
-                sa2.final_iter = (j == iterations[i] - 1 && !later) ? 1 : 0;
-            }
-            sa2.end_run = sa2.final_iter; sa2.commit = commit; sa2.weight_mult = weight_mult; sa2.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
+            // <CHECK_SKIP, PRO>: the model-to-model tracker checks the skip flag; from the prologue chain's second iteration on every block first solves the iteration before
+            auto go_icp = [&](auto kernel) { LAUNCH(h, icp_name[i], dim3(pa.nb_icp + pa.nb_res), dim3(RED_THREADS), kernel, st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store); };
+            if (it_pro && tail_k > 0) { if (frame_tracker) go_icp(k_icp_residual<false, true>); else go_icp(k_icp_residual<true, true>); }
+            else { if (frame_tracker) go_icp(k_icp_residual<false, false>); else go_icp(k_icp_residual<true, false>); }
+            StepArgs sa2 = step_args(i, j);
+            sa2.nb = nb_rgb; sa2.nb_icp = nb; sa2.nb_res = nbr; sa2.check_skip = frame_tracker ? 0 : 1; sa2.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
             sa2.pro = (pro && tail_k < n_pro) ? (tail_k == n_pro - 1 ? 2 : 1) : 0; sa2.pro_k = tail_k;   // (the chain's last iteration: last-block form; it is the run's last too unless finer levels were too large for the prologue)
             tail_k++;
             ended = ended || sa2.end_run;
-            if (frame_tracker) LAUNCH(h, rgb_name[i], dim3(nb_rgb), dim3(RED_THREADS), k_rgb_step_solve<false>, st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2);
-            else LAUNCH(h, rgb_name[i], dim3(nb_rgb), dim3(RED_THREADS), k_rgb_step_solve<true>, st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2);
+            auto go_rgb = [&](auto kernel) { LAUNCH(h, rgb_name[i], dim3(nb_rgb), dim3(RED_THREADS), kernel, st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2); };
+            if (frame_tracker) go_rgb(k_rgb_step_solve<false>);
+            else go_rgb(k_rgb_step_solve<true>);
         }
     }
     if (!ended)   // (no iteration ran at all: every level has zero iterations)
