@@ -384,6 +384,7 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *   "clean_raster" 0, "hot_records" 0 -- round 5's map-pass forms off: the clean pass and the prediction's raster as ONE walk of the view list; the
  *                           gathered 64-byte copy of the hot fields.  Identical results
  *   "host_entry_async" 1  -- ifx_process_frame returns when the frame's POSE is known (see there)
+ *   "seg_snapshots" n     -- outstanding tickets of ifx_segmentation_snapshot allowed at a time, 1..8 (default 4)
  *   "own_first_live" 0    -- test switch: the sharded map's "surfel 0" fixed at creation number 0 (round 4's behaviour: results then differ from the
  *                           reference's in the cases test_owner_sharded_map_emulated holds)
  * An unknown name is refused (IFX_E_INVALID); ifx_create reports each entry of IFX_OPTS that is refused on stderr and goes on. */
@@ -486,6 +487,34 @@ int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth
 enum { IFX_MASK_U8 = 0, IFX_MASK_F32 = 1 };
 int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
                                     void* stream);
+/* ---- deferred segmentation: a detector slower than the frame loop (no counterpart in the reference, whose detector thread is switched off at IF/main.cpp:83, so that
+ * its masks always belong to the frame processed last).  ifx_process_segmentation[_device] reads the CURRENT id image, the CURRENT pose and the RESIDENT frame; a real
+ * Mask R-CNN needs tens of milliseconds per image, i.e. dozens of frames.  The pair below makes a late call well-defined without stalling the frame loop; nobody who
+ * does not call it sees any difference.
+ * ifx_segmentation_snapshot: pins what a call reads of the frame processed last -- its whole id image (whatever "id_rule" / "lazy_ids" drew), held as CREATION NUMBERS
+ *   (ifx_map_seq: ascending in map order, carried by compaction, never reused), its pose, and with flags bit 1 its raw rgb / depth for the superpixel refinement (copied
+ *   device to device; 8 + 5 bytes per pixel and snapshot).  Enqueue-only on the handle's main stream: no host synchronisation.  Returns a ticket >= 0.  Buffers for the
+ *   outstanding tickets are allocated on first use; option "seg_snapshots" (1..8, default 4) is the limit; one more returns IFX_E_CAPACITY.
+ * ifx_process_segmentation_deferred[_device]: at any later time, the ordinary call's pipeline, unchanged, on the map as it is NOW (votes, positions, instance table, label
+ *   state), with three inputs replaced.  (1) The id image is the snapshot's, re-addressed in today's slots: a pixel keeps its surfel if that surfel is still in the store;
+ *   it reads 0 ("no surfel") if the surfel was compacted away, is a tombstone, or is today's first live slot (the reference's "surfel 0" is never voted for).  Surfels
+ *   created since are in no pixel of that image and get no votes.  (2) The camera centre of the model-depth step (getProjectDepthMap, IF/Core/InstanceFusion.cpp:977-996)
+ *   is the snapshot's pose.  (3) The superpixels (flags bit 1) are cut from the snapshot's frame.  masks / class_ids / n / frame / flags and d_masks ... stream: as for
+ *   ifx_process_segmentation / _device, with the same argument checks.  With no frame in between the result is bit for bit the ordinary call's.  The device schedule is
+ *   used whatever "seg_device" says (identical results).  A successful call releases its ticket; n == 0 or an empty map releases it and is a no-op.
+ * ifx_segmentation_snapshot_release: gives a ticket back without a call.
+ * ifx_segmentation_snapshot_stats: out4 = the tick the ticket pinned (what ifx_tick returned when it was taken), its pixels that name a surfel, how many of those lost their surfel at the
+ *   last deferred call (-1: none yet), tickets in use.  Synchronises.  A released ticket's figures stay readable until a new snapshot takes its buffers.
+ * Refusals.  IFX_E_INVALID: an unknown or released ticket (_stats: unknown), bad arguments.  IFX_E_STATE, with nothing enqueued and the handle still usable: a sharded
+ *   handle (n_ranks > 1 or -1, ifx_set_shard); more than one camera context; no frame processed yet; flags bit 1 on a ticket taken without it; a ticket taken before an
+ *   ifx_map_upload, which renumbers the creation numbers (a generation counter on the host detects it).  A deformation (ifx_set_deformation) keeps identities: the ticket
+ *   stays valid. */
+int ifx_segmentation_snapshot(ifx_t* h, int flags);
+int ifx_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks, const int32_t* class_ids, int n, int frame, int flags);
+int ifx_process_segmentation_deferred_device(ifx_t* h, int ticket, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
+                                             void* stream);
+int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
+int ifx_segmentation_snapshot_stats(ifx_t* h, int ticket, int32_t* out4);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

@@ -156,6 +156,11 @@ _SIGS = {
     "ifx_should_segment": (C.c_int, [_P, C.c_int]),
     "ifx_process_segmentation": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "ifx_process_segmentation_device": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_segmentation_snapshot": (C.c_int, [_P, C.c_int]),
+    "ifx_process_segmentation_deferred": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "ifx_process_segmentation_deferred_device": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
+    "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
     "ifx_render_project_map": (C.c_int, [_P, _P, _P]),
     "ifx_set_instance_gt": (C.c_int, [_P, _P]),
@@ -630,11 +635,8 @@ class InstanceFusion:
         self.ef._chk(self.L.ifx_process_segmentation(self.ef.handle, _ptr(rgb), _ptr(depth), _ptr(masks), _ptr(cls), int(masks.shape[0]), int(frame), flags),
                      "ifx_process_segmentation")
 
-    def process_segmentation_device(self, masks, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
-        """ProcessSegmentation on a detector's raw output already on the handle's GPU (ifx_process_segmentation_device): no download, no host sort.
-        masks: torch tensor [N,H,W] or [N,1,H,W] on the handle's device, in any order; bool / uint8 (inside iff non-zero) or float32 (inside iff > threshold).
-        class_ids: N integers (tensor or sequence), each following its mask.  The library applies the bridge's binarisation and stable area sort itself.
-        stream: the torch stream the masks were written on (default: the current stream); the call waits for it on the device.  Always the resident frame."""
+    def _device_masks(self, masks, class_ids, stream):
+        """validates a detector's tensors for the two device entries: (contiguous masks, int32 class ids on the device, format, n, stream)"""
         import torch
 
         dev = torch.device("cuda", int(self.ef.cfgd["device"]))
@@ -667,11 +669,50 @@ class InstanceFusion:
                 cls = torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)   # (no host synchronisation on the stream)
         if int(cls.numel()) != n:
             raise ValueError(f"class_ids: {int(cls.numel())} entries for {n} masks")
+        return m, cls, fmt, n, stream
+
+    def process_segmentation_device(self, masks, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
+        """ProcessSegmentation on a detector's raw output already on the handle's GPU (ifx_process_segmentation_device): no download, no host sort.
+        masks: torch tensor [N,H,W] or [N,1,H,W] on the handle's device, in any order; bool / uint8 (inside iff non-zero) or float32 (inside iff > threshold).
+        class_ids: N integers (tensor or sequence), each following its mask.  The library applies the bridge's binarisation and stable area sort itself.
+        stream: the torch stream the masks were written on (default: the current stream); the call waits for it on the device.  Always the resident frame."""
+        m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
         flags = (1 if isflann else 0) | (2 if superpixels else 0)
         self.ef._chk(self.L.ifx_process_segmentation_device(self.ef.handle, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None), n,
                                                             int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
                      "ifx_process_segmentation_device")
         # (the call returned after its work finished: m and cls may go; they were used on the handle's streams only behind `stream`)
+
+    # -- a detector slower than the frame loop: snapshot at the frame the masks belong to, deferred call when they arrive (include/ifx_c_api.h)
+    def snapshot(self, superpixels=False):
+        """ifx_segmentation_snapshot: pins the id image (as creation numbers), the pose and -- superpixels=True -- the raw frame of the frame just processed, without
+        synchronising; returns a ticket for process_segmentation_deferred[_device] / release_snapshot."""
+        return self.ef._chk(self.L.ifx_segmentation_snapshot(self.ef.handle, 2 if superpixels else 0), "ifx_segmentation_snapshot")
+
+    def process_segmentation_deferred(self, ticket, masks, class_ids, frame, isflann=False, superpixels=False):
+        """ProcessSegmentation of the masks a detector made of the snapshot's frame, on the map as it is now (ifx_process_segmentation_deferred); releases the ticket."""
+        masks = np.ascontiguousarray(masks, np.uint8)
+        cls = np.ascontiguousarray(class_ids, np.int32)
+        flags = (1 if isflann else 0) | (2 if superpixels else 0)
+        self.ef._chk(self.L.ifx_process_segmentation_deferred(self.ef.handle, int(ticket), _ptr(masks), _ptr(cls), int(masks.shape[0]), int(frame), flags),
+                     "ifx_process_segmentation_deferred")
+
+    def process_segmentation_deferred_device(self, ticket, masks, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
+        """The deferred call on a detector's raw output on the handle's GPU: tensors and stream exactly as for process_segmentation_device."""
+        m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
+        flags = (1 if isflann else 0) | (2 if superpixels else 0)
+        self.ef._chk(self.L.ifx_process_segmentation_deferred_device(self.ef.handle, int(ticket), C.c_void_p(m.data_ptr() or None), fmt, float(threshold),
+                                                                     C.c_void_p(cls.data_ptr() or None), n, int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
+                     "ifx_process_segmentation_deferred_device")
+
+    def release_snapshot(self, ticket):
+        self.ef._chk(self.L.ifx_segmentation_snapshot_release(self.ef.handle, int(ticket)), "ifx_segmentation_snapshot_release")
+
+    def snapshot_stats(self, ticket):
+        """ifx_segmentation_snapshot_stats: the tick pinned, its pixels with a surfel, of those lost at the last deferred call (-1: none yet), tickets in use"""
+        out = np.zeros(4, np.int32)
+        self.ef._chk(self.L.ifx_segmentation_snapshot_stats(self.ef.handle, int(ticket), _ptr(out)), "ifx_segmentation_snapshot_stats")
+        return dict(tick=int(out[0]), pixels=int(out[1]), lost=int(out[2]), in_use=int(out[3]))
 
     def labels(self):
         n = self.ef.getMapSurfelCount()

@@ -383,6 +383,7 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
     else if (s == "pace") h->opt_pace = value;
     else if (s == "lazy_ids") { ifx_ids_ensure(h); h->opt_lazy_ids = value; }
     else if (s == "seg_device") h->opt_seg_device = value;
+    else if (s == "seg_snapshots") { if (value < 1 || value > 8) { h->err = "seg_snapshots must be in [1, 8]"; return IFX_E_INVALID; } h->opt_seg_snapshots = value; }
     else if (s == "ff_rounds") h->opt_ff_rounds = value;
     else if (s == "gn_persist_blocks") { if (value < 1) return IFX_E_INVALID; ifx_drop_tracked(h); h->opt_gn_persist_blocks = value; }
     else if (s == "gn_persist") {   // a bit per pyramid level: that level's Gauss-Newton iterations in one persistent launch (k_gn_level); default 4 = the coarsest level only
@@ -429,6 +430,7 @@ static int enqueue_frame_side(ifx* h, int s, int tick, const uint8_t* rgb, const
     const int bound = h->cur_slot;
     hipStream_t q = h->opt_two_streams ? h->stream_b : h->stream;
     if (q != h->stream) HIPCHK(h, hipStreamWaitEvent(q, f.released, 0));   // the frame that last used this slot (two frames ago) is done
+    if (f.snap_pending) { if (q != h->stream) HIPCHK(h, hipStreamWaitEvent(q, f.snap_read, 0)); f.snap_pending = 0; }   // ... and so is a snapshot's copy of its raw images (ifx_segmentation_snapshot)
     h->cur = q;
     ifx_bind_slot(h, s);
     hipMemcpyKind kind = src_kind ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -1674,6 +1676,7 @@ extern "C" int ifx_map_upload(ifx_t* h, int n, const float* pc, const float* nr,
     HIPCHK(h, hipMemset(h->upd_owner, 0xFF, (size_t)h->cap * 4));
     HIPCHK(h, hipMemset(h->labels, 0xFF, (size_t)h->cap * 4));
     h->labels_stale_all = 1;   // uploaded votes: the next segmentation call scans the labels of the whole map
+    h->seq_generation++;       // creation numbers renumbered: tickets of ifx_segmentation_snapshot taken before this are void
     return IFX_OK;
 }
 

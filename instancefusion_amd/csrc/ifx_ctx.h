@@ -190,6 +190,8 @@ struct FrameSlot {
     DevState* so3 = nullptr;          // shadow state: only the SO(3) fields are used
     hipEvent_t ready = nullptr;       // recorded on the side stream when the slot is complete
     hipEvent_t released = nullptr;    // recorded on the main stream when the frame that used the slot is done
+    hipEvent_t snap_read = nullptr;   // recorded on the main stream behind a snapshot's copy of the raw images (ifx_segmentation_snapshot, flags bit 1)
+    int snap_pending = 0;             // ... and not yet waited for by the side stream's next copy-in
     const void *src_rgb = nullptr, *src_depth = nullptr;
     int for_tick = -1;                // frame the slot was prepared for
 };
@@ -488,6 +490,12 @@ struct ifx {
     uint8_t* h_masks_stage = nullptr; size_t h_masks_cap = 0;    // pinned staging of the caller's masks
     int* d_mask_rank = nullptr;        // masks already on the device (ifx_process_segmentation_device): [256] inside-pixel counts (zero between calls), [256] order, [256] class ids in that order
     int opt_seg_device = 1;            // segmentation call without the host in the middle (0: the host-driven schedule of round 2)
+    // deferred segmentation (ifx_segmentation_snapshot / ifx_process_segmentation_deferred, ifx_instance.hip)
+    void* seg_snaps = nullptr;         // the ticket table and its device buffers, allocated by the first snapshot
+    int opt_seg_snapshots = 4;         // outstanding tickets allowed (option seg_snapshots, 1..8)
+    int snap_next_ticket = 0;
+    unsigned int seq_generation = 0;   // counts the events that renumber creation numbers (ifx_map_upload): a ticket taken before one is refused
+    int32_t* d_snap_ids = nullptr;     // [P] a snapshot's id image in today's slots (k_seg_translate): what a deferred call reads instead of ids_after
     int opt_ff_rounds = 0;             // relaxation launches of the flood fill's fixed schedule (0: 24)
     int last_seg_frame = -1;
     int seg_counts_valid = 0;          // h_result->seg_counts describe the current ids_after / votes

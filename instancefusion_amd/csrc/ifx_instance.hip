@@ -18,6 +18,7 @@
 
 int ifx_superpixel_refine(ifx* h, const uint8_t* rgb, const uint16_t* depth, int nm, int frame);
 int ifx_superpixel_begin(ifx* h, const uint8_t* rgb, const uint16_t* depth);
+int ifx_superpixel_begin_device(ifx* h, const uint8_t* d_rgb, const uint16_t* d_depth);
 int ifx_superpixel_filter(ifx* h, int nm, bool prepared = false);
 int ifx_superpixel_filter_prepare(ifx* h, int nm);
 int ifx_superpixel_ahead(ifx* h);
@@ -241,7 +242,8 @@ __device__ __forceinline__ void bbox_extend_box(int* b, const int* sb)
 // depth under every pixel on the way: getProjectDepthMapKernel reads the same id); MODE 2, the mask boxes, follows the masks and needs one vote float4 per pixel.
 template <int MODE>
 __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ votes, int cap, const uint8_t* __restrict__ masks,
-                               int nm, int w, int h, int* __restrict__ bbox, IdMap im, const float4* __restrict__ pc = nullptr, uint16_t* __restrict__ pdm = nullptr)
+                               int nm, int w, int h, int* __restrict__ bbox, IdMap im, const float4* __restrict__ pc = nullptr, uint16_t* __restrict__ pdm = nullptr,
+                               const float* __restrict__ cam = nullptr)   // cam: the row-major pose whose translation is the camera centre (SegView::cam; MODE 1 only)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     const int lane = (threadIdx.y * blockDim.x + threadIdx.x) & 63;
@@ -262,7 +264,7 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
         uint16_t o = 0;
         if (id >= 0) {
             const float4 p = pc[id];
-            const float dx = st->pose[3] - p.x, dy = st->pose[7] - p.y, dz = st->pose[11] - p.z;
+            const float dx = cam[3] - p.x, dy = cam[7] - p.y, dz = cam[11] - p.z;
             o = (uint16_t)(sqrtf(dx * dx + dy * dy + dz * dz) * 1186);
         }
         pdm[k] = o;
@@ -320,7 +322,8 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
 }
 
 // getProjectDepthMapKernel, IF/Core/InstanceFusionCuda.cu:977-996
-__global__ void k_project_depth(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ pc, int P, int ratio, uint16_t* __restrict__ pdm, IdMap im)
+__global__ void k_project_depth(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ pc, int P, int ratio, uint16_t* __restrict__ pdm, IdMap im,
+                                const float* __restrict__ cam)   // cam: the row-major pose whose translation is the camera centre (SegView::cam)
 {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
@@ -328,7 +331,7 @@ __global__ void k_project_depth(const DevState* __restrict__ st, const int32_t* 
     uint16_t o = 0;
     if (id >= 0) {
         float4 p = pc[id];
-        float dx = st->pose[3] - p.x, dy = st->pose[7] - p.y, dz = st->pose[11] - p.z;
+        float dx = cam[3] - p.x, dy = cam[7] - p.y, dz = cam[11] - p.z;
         o = (uint16_t)(sqrtf(dx * dx + dy * dy + dz * dz) * ratio);
     }
     pdm[k] = o;
@@ -534,10 +537,12 @@ int ifx_alloc_instance(ifx* h)
     HIPCHK(h, hipMalloc(&h->d_clean_list, NI * 4));
     return IFX_OK;
 }
+void ifx_free_snapshots(ifx* h);
 void ifx_free_instance(ifx* h)
 {
     hipFree(h->d_inst_color); hipFree(h->d_masks); hipFree(h->d_masks_ori); hipFree(h->d_unavail); hipFree(h->d_ff_label); hipFree(h->d_pdm); hipFree(h->d_bbox); hipFree(h->d_inst_stats); hipFree(h->d_clean_list);
     hipFree(h->d_segctl); hipFree(h->d_mask_rank);
+    ifx_free_snapshots(h);
     if (h->h_segctl) hipHostFree(h->h_segctl);
     if (h->h_masks_stage) hipHostFree(h->h_masks_stage);
 }
@@ -1022,10 +1027,16 @@ static int first_not_used(ifx* h)
     return -1;
 }
 
-static int run_bboxes(ifx* h, int nm, std::vector<int>& bbox)
+// What a segmentation call reads of "the frame it belongs to": the id image, the pose whose translation is the camera centre of the model-depth kernels, and the
+// frame the superpixels are cut from.  The ordinary entries fill it with the handle's current id image, the state's pose and no frame pointers (the caller's host
+// images, or the resident frame slot); the deferred entry with the snapshot's translated id image, pinned pose and pinned frame (seg_view_snapshot).
+struct SegView { const int32_t* ids; const float* cam; const uint8_t* d_rgb; const uint16_t* d_depth; };
+static SegView seg_view_current(const ifx* h) { return SegView{h->ids_after, h->d_state->pose, nullptr, nullptr}; }
+
+static int run_bboxes(ifx* h, const SegView& v, int nm, std::vector<int>& bbox)
 {
     LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
-    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
+    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, v.ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
            h->d_bbox, ifx_idmap(h));
     bbox.resize((size_t)(NI + nm) * 4);
     HIPCHK(h, hipMemcpyAsync(bbox.data(), h->d_bbox, bbox.size() * 4, hipMemcpyDeviceToHost, h->cur));
@@ -1167,7 +1178,7 @@ static int oseg_resume(ifx* h)
         return oseg_launch_bboxes(h);
     case 1:   // boxes merged -> compare map; model depth of the owned surfels
         if ((r = oseg_read_bboxes(h))) return r;
-        LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, h->ids_after, (const float4*)h->pc, P, 1186, h->d_pdm, ifx_idmap(h));
+        LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, h->ids_after, (const float4*)h->pc, P, 1186, h->d_pdm, ifx_idmap(h), (const float*)h->d_state->pose);
         h->oseg_state = 2; h->oseg_pending = 2;
         return 1;
     case 2:   // model depth merged -> flood fill (replicated), then the masks
@@ -1209,9 +1220,12 @@ static int oseg_resume(ifx* h)
 // the masks of ifx_process_segmentation_device: the caller's n x P elements in device memory, their format, the class ids (device), and an event recorded on the
 // producer's stream at entry (the ingestion waits for it; nothing before the ingestion does)
 struct DevMasks { const void* d; int fmt; float thr; const int32_t* d_cls; hipEvent_t ready; };
+struct SegSnap;   // a pinned frame of ifx_segmentation_snapshot (below): null for the ordinary entries
 static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
-static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
-static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
+static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
+                                       SegSnap* snap);
+static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
+                                SegSnap* snap = nullptr);
 extern "C" int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
 {
     if (!h || nm < 0 || (nm > 0 && (!masks_in || !class_ids))) return IFX_E_INVALID;
@@ -1232,7 +1246,39 @@ extern "C" int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, in
     h->event_pool.push_back(dm.ready);
     return r;
 }
-static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags)
+static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
+extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
+extern "C" int ifx_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
+{
+    if (!h || nm < 0 || (nm > 0 && (!masks_in || !class_ids))) return IFX_E_INVALID;
+    if (nm > 256) { h->err = "too many masks"; return IFX_E_INVALID; }
+    SegSnap* q = nullptr;
+    int r = snap_for_call(h, "ifx_process_segmentation_deferred", ticket, flags, &q);
+    if (r) return r;
+    r = process_segmentation(h, nullptr, nullptr, masks_in, class_ids, nullptr, nm, frame, flags, q);
+    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
+    return r;
+}
+extern "C" int ifx_process_segmentation_deferred_device(ifx_t* h, int ticket, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
+                                                        void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || n > 256) { h->err = "ifx_process_segmentation_deferred_device: n must be 0 .. 256"; return IFX_E_INVALID; }
+    if (mask_format != IFX_MASK_U8 && mask_format != IFX_MASK_F32) { h->err = "ifx_process_segmentation_deferred_device: unknown mask format"; return IFX_E_INVALID; }
+    if (n > 0 && (!d_masks || !d_class_ids)) { h->err = "ifx_process_segmentation_deferred_device: null masks or class ids"; return IFX_E_INVALID; }
+    SegSnap* q = nullptr;
+    int r = snap_for_call(h, "ifx_process_segmentation_deferred_device", ticket, flags, &q);
+    if (r) return r;
+    DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_deferred_device: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
+    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags, q);
+    h->event_pool.push_back(dm.ready);
+    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
+    return r;
+}
+static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
+                                SegSnap* snap)
 {
     // The next frame's tracker is already queued on the main stream (enqueue_frame, "tracked ahead") and touches nothing this call does: the call's ~60 short
     // launches then go to the handle's third stream (the loop-closure tracker's: four streams is what the runtime's hardware queues hold) and run beside the tracker's 170 instead of behind them.  The call ends with the host waiting for its stream,
@@ -1243,8 +1289,9 @@ static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* de
         if (h->ev_result) HIPCHK(h, hipStreamWaitEvent(h->stream_c, h->ev_result, 0));   // behind the frame the call belongs to
         h->cur = h->stream_c;
     }
-    const int r = h->opt_seg_device ? process_segmentation_device(h, rgb, depth, masks_in, class_ids, dm, nm, frame, flags)
-                                    : process_segmentation_host(h, rgb, depth, masks_in, class_ids, dm, nm, frame, flags);
+    // (a deferred call always takes the device schedule: both give identical results, and only this one reads through the view everywhere)
+    const int r = (h->opt_seg_device || snap) ? process_segmentation_device(h, rgb, depth, masks_in, class_ids, dm, nm, frame, flags, snap)
+                                              : process_segmentation_host(h, rgb, depth, masks_in, class_ids, dm, nm, frame, flags);
     if (aside) { hipStreamSynchronize(h->stream_c); h->cur = h->stream; }
     // a call that failed part-way may have updated votes without the label scan that follows them: the incremental scan of the next call assumes
     // that votes outside its own id image are unchanged since the last scan, so the next call scans everything
@@ -1254,7 +1301,7 @@ static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* de
 
 // step 3 of processInstance (IF/Core/InstanceFusion.cpp:955-1040) from mask m_start on, driven by the host: registration, the eviction of a full table
 // (computeMaxCountInMap, getInstanceTableCleanList, cleanInstanceTableMap, boxes and compare map again), one vote launch per (mask, instance)
-static int seg_host_mask_loop(ifx* h, int nm, const int32_t* class_ids, int m_start, std::vector<int>& cmp, std::vector<uint8_t>& unavailable, std::vector<int>& bbox)
+static int seg_host_mask_loop(ifx* h, const SegView& v, int nm, const int32_t* class_ids, int m_start, std::vector<int>& cmp, std::vector<uint8_t>& unavailable, std::vector<int>& bbox)
 {
     const int P = h->P;
     int r;
@@ -1284,7 +1331,7 @@ static int seg_host_mask_loop(ifx* h, int nm, const int32_t* class_ids, int m_st
                 LAUNCH(h, "clean_table", dim3(1024), dim3(256), k_clean_table, h->d_state, h->votes, h->cap, h->d_clean_list);
                 h->labels_stale_all = 1;   // votes of every surfel that carried an evicted instance changed
                 HIPCHK(h, hipStreamSynchronize(h->cur));
-                r = run_bboxes(h, nm, bbox);
+                r = run_bboxes(h, v, nm, bbox);
                 if (r) return r;
                 std::fill(cmp.begin(), cmp.end(), 0);
                 compare_map(h, &bbox[NI * 4], &bbox[0], class_ids, nm, unavailable, cmp);
@@ -1294,7 +1341,7 @@ static int seg_host_mask_loop(ifx* h, int nm, const int32_t* class_ids, int m_st
         }
         for (int q = 0; q < NI; q++)
             if (cmp[q + m * NI] == 1)
-                LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update, h->d_state, h->ids_after, h->d_masks + (size_t)m * P, P, h->cap, q, m + 1, h->votes, ifx_idmap(h));
+                LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update, h->d_state, v.ids, h->d_masks + (size_t)m * P, P, h->cap, q, m + 1, h->votes, ifx_idmap(h));
     }
     return IFX_OK;
 }
@@ -1302,12 +1349,12 @@ static int seg_host_mask_loop(ifx* h, int nm, const int32_t* class_ids, int m_st
 // `gate`: device pointer to (ff_incomplete, evict_at) of the device-side call, or null.  Returns 1 when the scan enqueued was the full one.
 // default_done: the caller already ran k_colour_default in this call (it reads nothing a call changes -- a surfel whose votes the call then touches is recoloured by
 // k_count_colour_px, which treats the default colour as "none yet" -- so the device-scheduled call enqueues it before the masks are staged)
-static int seg_label_scan(ifx* h, const int* gate = nullptr, bool default_done = false)
+static int seg_label_scan(ifx* h, const SegView& v, const int* gate = nullptr, bool default_done = false)
 {
     const int P = h->P;
     if (!h->labels_stale_all) {
         if (!default_done) LAUNCH(h, "colour_default", dim3(2048), dim3(256), k_colour_default, h->d_state, (const float2*)h->tm, (float2*)h->col, h->labels, gate);
-        LAUNCH(h, "count_colour_px", dim3(cdiv(P, 256)), dim3(256), k_count_colour_px, h->d_state, h->ids_after, P, (const float4*)h->votes, h->cap, (const float2*)h->tm, (float2*)h->col,
+        LAUNCH(h, "count_colour_px", dim3(cdiv(P, 256)), dim3(256), k_count_colour_px, h->d_state, v.ids, P, (const float4*)h->votes, h->cap, (const float2*)h->tm, (float2*)h->col,
                h->d_inst_color, h->labels, ifx_idmap(h), gate);
         return 0;
     }
@@ -1380,23 +1427,24 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
         if (r) return r;
     }
     // steps 1, 2
+    const SegView v = seg_view_current(h);
     std::vector<int> bbox;
-    r = run_bboxes(h, nm, bbox);
+    r = run_bboxes(h, v, nm, bbox);
     if (r) return r;
     std::vector<int> cmp((size_t)nm * NI, 0);
     compare_map(h, &bbox[NI * 4], &bbox[0], class_ids, nm, unavailable, cmp);
     // step 3_0: model depth under the camera, then the flood fill of every usable mask (device)
-    LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, h->ids_after, (const float4*)h->pc, P, 1186, h->d_pdm, ifx_idmap(h));
+    LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, v.ids, (const float4*)h->pc, P, 1186, h->d_pdm, ifx_idmap(h), v.cam);
     HIPCHK(h, hipMemcpyAsync(h->d_unavail, unavailable.data(), nm, hipMemcpyHostToDevice, h->cur));
     r = mask_geometric_filter_device(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm, h->d_unavail);
     if (r) return r;
     HIPCHK(h, hipMemcpyAsync(unavailable.data(), h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));
     HIPCHK(h, hipStreamSynchronize(h->cur));
     // step 3
-    r = seg_host_mask_loop(h, nm, class_ids, 0, cmp, unavailable, bbox);
+    r = seg_host_mask_loop(h, v, nm, class_ids, 0, cmp, unavailable, bbox);
     if (r) return r;
     // step 4
-    seg_label_scan(h);
+    seg_label_scan(h, v);
     // flannKnnVoteSurfelMap (isflann, :1051)
     if (flags & 1) { r = ifx_knn_vote(h, nullptr); if (r) return r; }
     hipEvent_t eb = ifx_event_get(h);
@@ -1542,7 +1590,209 @@ static int seg_ensure_ctl(ifx* h, size_t mask_bytes)
     return IFX_OK;
 }
 
-static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags)
+// ------------------------------------------------------------------ deferred segmentation: a slow detector's masks of frame t, applied at frame t + k
+// (ifx_segmentation_snapshot / ifx_process_segmentation_deferred[_device]; the reference has no counterpart: its detector thread is off, IF/main.cpp:83).
+// A snapshot pins what a call reads of ITS frame -- the id image, the pose, optionally the raw frame -- and names every surfel by its creation number (ifx::seq:
+// ascending in slot order, carried by the compaction, never reused), so that the image can be re-addressed in whatever slots the map has when the masks arrive.
+struct SnapHdr { float pose[16]; int tick, pad[15]; };   // what one lane copies out of the state: the host reads nothing at snapshot time
+#define SNAP_NONE 0xFFFFFFFFu
+// id -> {creation number, slot as a hint}: 8 bytes per pixel.  have[block]: pixels of the block that name a surfel (ifx_segmentation_snapshot_stats).
+__global__ void __launch_bounds__(256) k_seg_snapshot(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const uint32_t* __restrict__ seq, int P, int tick,
+                                                      uint2* __restrict__ px, SnapHdr* __restrict__ hdr, int* __restrict__ have)
+{
+    const int count = st->count;   // launch-uniform: read once, before the first store
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int id = k < P ? ids[k] : 0;
+    const bool has = id > 0 && id < count;
+    if (k < P) px[k] = has ? make_uint2(seq[id], (unsigned int)id) : make_uint2(0u, SNAP_NONE);
+    __shared__ int s_n[4];
+    const unsigned long long bal = __ballot(has);
+    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) have[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    if (blockIdx.x == 0 && threadIdx.x == 64) {
+        for (int q = 0; q < 16; q++) hdr->pose[q] = st->pose[q];
+        hdr->tick = tick;
+    }
+}
+// The pinned image in today's slots.  Compaction only moves a surfel DOWN and creation numbers ascend with the slots, so the surfel of a pixel sits at or below
+// its old slot: the first probe, seq[min(hint, count - 1)], is the only load while nothing was compacted since the snapshot (the normal case with lazy compaction);
+// otherwise a gallop downwards with doubling steps brackets the number and a bisection of the bracket finds it (a full bisection of 5 M slots is 23 dependent loads
+// per pixel: DESIGN.md section 7 has what that costs).  A pixel keeps its surfel if it is still in the store, alive, and not today's "surfel 0" (first_live: never
+// voted for); everything else reads 0 = no surfel.  lost[block]: pixels of the block that named a surfel and lost it.
+__global__ void __launch_bounds__(256) k_seg_translate(const DevState* __restrict__ st, const uint2* __restrict__ px, const uint32_t* __restrict__ seq, const float2* __restrict__ tm, int P,
+                                                       int32_t* __restrict__ out, int* __restrict__ lost)
+{
+    const int count = st->count, fl = st->first_live;   // launch-uniform words: read once, before the first store ("Uniform loads")
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    int slot = 0;
+    bool had = false;
+    if (k < P) {
+        const uint2 e = px[k];
+        had = e.y != SNAP_NONE;
+        if (had && count > 0) {
+            const unsigned int want = e.x;
+            const int j = min((int)e.y, count - 1);
+            unsigned int v = seq[j];
+            int found = -1;
+            if (v == want) found = j;
+            else if (v > want) {
+                int hi = j, lo = j - 1, step = 1;   // seq[hi] > want throughout
+                while (lo >= 0 && (v = seq[lo]) > want) { hi = lo; step <<= 1; lo -= step; }
+                if (lo >= 0 && v == want) found = lo;
+                else {
+                    int a = lo < 0 ? -1 : lo;       // seq[a] < want (or a = -1), seq[hi] > want: the number, if still stored, lies strictly between
+                    while (hi - a > 1) {
+                        const int mid = (a + hi) >> 1;
+                        v = seq[mid];
+                        if (v == want) { found = mid; break; }
+                        if (v < want) a = mid; else hi = mid;
+                    }
+                }
+            }   // (v < want: every slot up to j carries a smaller number and the surfel cannot sit above its old slot -- compacted away)
+            if (found > 0 && found != fl && tm[found].y > DEAD_TIME) slot = found;
+        }
+        out[k] = slot;
+    }
+    __shared__ int s_n[4];
+    const unsigned long long bal = __ballot(had && slot == 0);
+    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) lost[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+}
+
+#define SNAP_MAX 8
+struct SegSnap {
+    int ticket = -1, in_use = 0, flags = 0, translated = 0;
+    unsigned int generation = 0;       // ifx::seq_generation when it was taken
+    uint2* px = nullptr;               // [P] creation number, slot hint
+    SnapHdr* hdr = nullptr;
+    int* counts = nullptr;             // [2][blocks]: pixels with a surfel (snapshot), pixels that lost it (last translate)
+    uint8_t* rgb = nullptr;            // [P][3], [P]: the raw frame, allocated by the first snapshot of this slot that keeps one
+    uint16_t* depth = nullptr;
+    hipEvent_t ev = nullptr;           // behind the snapshot on the frame's stream
+};
+struct SegSnapSet { SegSnap s[SNAP_MAX]; };
+static SegSnap* snap_find(ifx* h, int ticket, bool released_too = false)
+{
+    SegSnapSet* set = (SegSnapSet*)h->seg_snaps;
+    if (!set || ticket < 0) return nullptr;
+    for (SegSnap& q : set->s) if (q.ticket == ticket && (q.in_use || released_too)) return &q;
+    return nullptr;
+}
+static int snap_in_use(const ifx* h)
+{
+    const SegSnapSet* set = (const SegSnapSet*)h->seg_snaps;
+    int n = 0;
+    if (set) for (const SegSnap& q : set->s) n += q.in_use;
+    return n;
+}
+void ifx_free_snapshots(ifx* h)
+{
+    SegSnapSet* set = (SegSnapSet*)h->seg_snaps;
+    if (set) {
+        for (SegSnap& q : set->s) { hipFree(q.px); hipFree(q.hdr); hipFree(q.counts); hipFree(q.rgb); hipFree(q.depth); if (q.ev) hipEventDestroy(q.ev); }
+        delete set;
+    }
+    h->seg_snaps = nullptr;
+    hipFree(h->d_snap_ids); h->d_snap_ids = nullptr;
+    for (FrameSlot& f : h->slot) if (f.snap_read) { hipEventDestroy(f.snap_read); f.snap_read = nullptr; }
+}
+// what every snapshot entry refuses alike (nothing enqueued, the handle stays usable)
+static int snap_refuse_mode(ifx* h, const char* who)
+{
+    if (h->own || h->shard_n > 1) { h->err = std::string(who) + ": not offered on a sharded map"; return IFX_E_STATE; }
+    if (h->cams.size() > 1) { h->err = std::string(who) + ": not offered with more than one camera context"; return IFX_E_STATE; }
+    return IFX_OK;
+}
+extern "C" int ifx_segmentation_snapshot(ifx_t* h, int flags)
+{
+    if (!h) return IFX_E_INVALID;
+    if (flags & ~2) { h->err = "ifx_segmentation_snapshot: unknown flags (bit 1: keep the frame for the superpixels)"; return IFX_E_INVALID; }
+    int r = snap_refuse_mode(h, "ifx_segmentation_snapshot");
+    if (r) return r;
+    if (h->tick < 2) { h->err = "ifx_segmentation_snapshot: no frame has been processed yet"; return IFX_E_STATE; }
+    if (snap_in_use(h) >= h->opt_seg_snapshots) { h->err = "ifx_segmentation_snapshot: every ticket is in use (option seg_snapshots)"; return IFX_E_CAPACITY; }
+    if (!h->seg_snaps) h->seg_snaps = new SegSnapSet();
+    SegSnapSet* set = (SegSnapSet*)h->seg_snaps;
+    SegSnap* q = nullptr;   // the free slot released longest ago: a released ticket's figures stay readable (ifx_segmentation_snapshot_stats) until its buffers are taken again
+    for (SegSnap& c_ : set->s) if (!c_.in_use && (!q || c_.ticket < q->ticket)) q = &c_;
+    if (!q) { h->err = "ifx_segmentation_snapshot: every ticket is in use"; return IFX_E_CAPACITY; }
+    const int P = h->P, nb = cdiv(P, 256);
+    // (each buffer on its own: an allocation that fails leaves the slot free and the ones before it in place for the next attempt)
+    if (!q->px) HIPCHK(h, hipMalloc((void**)&q->px, (size_t)P * sizeof(uint2)));
+    if (!q->hdr) HIPCHK(h, hipMalloc((void**)&q->hdr, sizeof(SnapHdr)));
+    if (!q->counts) HIPCHK(h, hipMalloc((void**)&q->counts, (size_t)2 * nb * sizeof(int)));
+    if (!q->ev) HIPCHK(h, hipEventCreateWithFlags(&q->ev, hipEventDisableTiming));
+    if ((flags & 2) && !q->rgb) HIPCHK(h, hipMalloc((void**)&q->rgb, (size_t)P * 3));
+    if ((flags & 2) && !q->depth) HIPCHK(h, hipMalloc((void**)&q->depth, (size_t)P * 2));
+    if ((r = ifx_ids_ensure(h))) return r;   // the whole id image, whatever id_rule / lazy_ids drew
+    LAUNCH(h, "seg_snapshot", dim3(nb), dim3(256), k_seg_snapshot, (const DevState*)h->d_state, (const int32_t*)h->ids_after, (const uint32_t*)h->seq, P, h->tick, q->px, q->hdr, q->counts);
+    if (flags & 2) {
+        // the raw frame, device to device, out of its frame slot; the side stream reuses the slot two frames on and waits for the FRAME that used it only
+        // (FrameSlot::released), so it is told about this reader too (enqueue_frame_side)
+        FrameSlot& f = h->slot[(size_t)h->last_frame_slot];
+        HIPCHK(h, hipMemcpyAsync(q->rgb, f.rgb, (size_t)P * 3, hipMemcpyDeviceToDevice, h->cur));
+        HIPCHK(h, hipMemcpyAsync(q->depth, f.depth_raw, (size_t)P * 2, hipMemcpyDeviceToDevice, h->cur));
+        if (!f.snap_read) HIPCHK(h, hipEventCreateWithFlags(&f.snap_read, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(f.snap_read, h->cur));
+        f.snap_pending = 1;
+    }
+    HIPCHK(h, hipEventRecord(q->ev, h->cur));
+    q->ticket = h->snap_next_ticket++; q->in_use = 1; q->flags = flags; q->translated = 0; q->generation = h->seq_generation;
+    return q->ticket;
+}
+extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket)
+{
+    if (!h) return IFX_E_INVALID;
+    SegSnap* q = snap_find(h, ticket);
+    if (!q) { h->err = "ifx_segmentation_snapshot_release: unknown or released ticket"; return IFX_E_INVALID; }
+    q->in_use = 0;   // (buffers stay: whoever takes the slot next enqueues behind whatever still reads them, on the same stream or behind a synchronous call)
+    return IFX_OK;
+}
+extern "C" int ifx_segmentation_snapshot_stats(ifx_t* h, int ticket, int32_t* out4)
+{
+    if (!h || !out4) return IFX_E_INVALID;
+    SegSnap* q = snap_find(h, ticket, true);
+    if (!q) { h->err = "ifx_segmentation_snapshot_stats: unknown ticket"; return IFX_E_INVALID; }
+    const int nb = cdiv(h->P, 256);
+    std::vector<int> c((size_t)2 * nb);
+    SnapHdr hd;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(&hd, q->hdr, sizeof(hd), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(c.data(), q->counts, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    int have = 0, lost = 0;
+    for (int b = 0; b < nb; b++) { have += c[b]; lost += c[nb + b]; }
+    out4[0] = hd.tick; out4[1] = have; out4[2] = q->translated ? lost : -1; out4[3] = snap_in_use(h);
+    return IFX_OK;
+}
+// the view of a deferred call: behind the snapshot, the pinned image re-addressed in today's slots (a buffer of its own: ifx::ids_after is not touched)
+static int seg_view_snapshot(ifx* h, SegSnap* q, SegView* v)
+{
+    const int P = h->P, nb = cdiv(P, 256);
+    if (!h->d_snap_ids) HIPCHK(h, hipMalloc((void**)&h->d_snap_ids, (size_t)P * 4));
+    HIPCHK(h, hipStreamWaitEvent(h->cur, q->ev, 0));   // (the call may run on the third stream)
+    LAUNCH(h, "seg_translate", dim3(nb), dim3(256), k_seg_translate, (const DevState*)h->d_state, (const uint2*)q->px, (const uint32_t*)h->seq, (const float2*)h->tm, P, h->d_snap_ids, q->counts + nb);
+    q->translated = 1;
+    v->ids = h->d_snap_ids; v->cam = q->hdr->pose; v->d_rgb = q->rgb; v->d_depth = q->depth;
+    if (!(q->flags & 2)) { v->d_rgb = nullptr; v->d_depth = nullptr; }
+    return IFX_OK;
+}
+// the checks of the two deferred entries that need the ticket; *out: the snapshot
+static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out)
+{
+    int r = snap_refuse_mode(h, who);
+    if (r) return r;
+    SegSnap* q = snap_find(h, ticket);
+    if (!q) { h->err = std::string(who) + ": unknown or released ticket"; return IFX_E_INVALID; }
+    if ((flags & 2) && !(q->flags & 2)) { h->err = std::string(who) + ": superpixels need a ticket taken with the frame (ifx_segmentation_snapshot flags bit 1)"; return IFX_E_STATE; }
+    if (q->generation != h->seq_generation) { h->err = std::string(who) + ": the map was uploaded since the ticket was taken (creation numbers renumbered)"; return IFX_E_STATE; }
+    *out = q;
+    return IFX_OK;
+}
+
+static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
+                                       SegSnap* snap)
 {
     static const bool trace = getenv("IFX_SEG_TRACE") != nullptr;   // diagnostic: where the host is inside a call (us since entry, to stderr)
     const auto t_in = std::chrono::steady_clock::now();
@@ -1556,7 +1806,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     h->seg_counts_valid = 0;
     if (nm == 0 || n == 0) return IFX_OK;
     t_res = us();
-    ifx_ids_ensure(h);   // the call reads the id image under every mask pixel: the whole image, if the frame rendered only the sampled lattice
+    if (!snap) ifx_ids_ensure(h);   // the call reads the id image under every mask pixel: the whole image, if the frame rendered only the sampled lattice (a snapshot pinned the whole one)
     t_ids = us();
     const int P = h->P;
     const size_t mbytes = (size_t)nm * P;
@@ -1566,14 +1816,16 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     SegCtl* hc = (SegCtl*)h->h_segctl;
     hipEvent_t ea = ifx_event_get(h);
     hipEventRecord(ea, h->cur);
+    SegView v = seg_view_current(h);
+    if (snap && (r = seg_view_snapshot(h, snap, &v))) { h->event_pool.push_back(ea); return r; }   // (deferred call: the pinned id image re-addressed in today's slots, the pinned pose and frame)
     if (flags & 2) {   // superpixels and their merge: on the queue before the masks are even copied (they need the frame only)
-        if ((r = ifx_superpixel_begin(h, rgb, depth))) { h->event_pool.push_back(ea); return r; }
+        if ((r = v.d_rgb ? ifx_superpixel_begin_device(h, v.d_rgb, v.d_depth) : ifx_superpixel_begin(h, rgb, depth))) { h->event_pool.push_back(ea); return r; }
     }
     // what needs the map and the id image but not the masks -- the boxes of the projected instances (the twelve vote float4 under every pixel: the heavy half of
     // getProjectInstanceList / computeProjectBoundingBox) and the model depth under every pixel -- runs while the host copies the masks into pinned memory
     LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
-    LAUNCH(h, "project_bbox_inst", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<1>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr, nm,
-           h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)h->pc, h->d_pdm);
+    LAUNCH(h, "project_bbox_inst", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<1>, h->d_state, v.ids, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr, nm,
+           h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)h->pc, h->d_pdm, v.cam);
     const bool default_early = !h->labels_stale_all;
     if (default_early) LAUNCH(h, "colour_default", dim3(2048), dim3(256), k_colour_default, h->d_state, (const float2*)h->tm, (float2*)h->col, h->labels, (const int*)nullptr);
     if (flags & 2) { if ((r = ifx_superpixel_filter_prepare(h, nm))) return r; }
@@ -1596,7 +1848,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         r = ifx_superpixel_filter(h, nm, true);
         if (r) return r;
     }
-    LAUNCH(h, "project_bbox_mask", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<2>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
+    LAUNCH(h, "project_bbox_mask", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<2>, h->d_state, v.ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
            h->d_bbox, ifx_idmap(h));
     LAUNCH(h, "seg_compare", dim3(1), dim3(256), k_seg_compare, dc, (const int*)h->d_bbox, h->d_unavail);
     const int rounds = h->opt_ff_rounds > 0 ? h->opt_ff_rounds : 4;   // (after the union-find start the first relaxation normally finds the fixpoint: the rest are spares for one-way edges)
@@ -1606,10 +1858,10 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     const int* gate = fa.changed + (std::min(rounds, FF_SLOTS) - 1);
     LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, gate, (const int*)fa.meta, fa.skip);
     for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
-            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, h->ids_after, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
+            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, v.ids, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
     // the scan kernels look at the control block themselves: when the call has to be finished by the host (fill incomplete / table full) they return at once and
     // the ONE scan of the call runs behind the host-driven tail, after every mask and the eviction -- colours are assigned once, so an early scan would be visible
-    const int full_scan = seg_label_scan(h, (const int*)dc, default_early);
+    const int full_scan = seg_label_scan(h, v, (const int*)dc, default_early);
     uint8_t* h_un = (uint8_t*)h->h_segctl + sizeof(SegCtl);
     HIPCHK(h, hipMemcpyAsync(hc, dc, sizeof(SegCtl), hipMemcpyDeviceToHost, h->cur));
     HIPCHK(h, hipMemcpyAsync(h_un, h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));
@@ -1623,8 +1875,8 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         if (r) return r;
         LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, (const int*)nullptr, (const int*)nullptr, (const uint8_t*)nullptr);
         for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
-            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, h->ids_after, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
-        const int full2 = seg_label_scan(h, (const int*)dc);   // (gated again: the table may turn out full at some mask)
+            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, v.ids, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
+        const int full2 = seg_label_scan(h, v, (const int*)dc);   // (gated again: the table may turn out full at some mask)
         HIPCHK(h, hipMemcpyAsync(hc, dc, sizeof(SegCtl), hipMemcpyDeviceToHost, h->cur));
         HIPCHK(h, hipMemcpyAsync(h_un, h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));
         HIPCHK(h, hipStreamSynchronize(h->cur));
@@ -1635,9 +1887,9 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         std::vector<uint8_t> unavailable(h_un, h_un + nm);
         std::vector<int> cmp((size_t)nm * NI, 0), bbox;
         for (int m = 0; m < nm; m++) if (hc->best[m] > 0) cmp[hc->best[m] + m * NI] = 1;
-        r = seg_host_mask_loop(h, nm, dm ? hc->cls : class_ids, hc->evict_at, cmp, unavailable, bbox);   // (device masks: the class ids in sorted order, as read back)
+        r = seg_host_mask_loop(h, v, nm, dm ? hc->cls : class_ids, hc->evict_at, cmp, unavailable, bbox);   // (device masks: the class ids in sorted order, as read back)
         if (r) return r;
-        seg_label_scan(h);
+        seg_label_scan(h, v);
     }
     if (flags & 1) { r = ifx_knn_vote(h, nullptr); if (r) return r; }
     hipEvent_t eb = ifx_event_get(h);

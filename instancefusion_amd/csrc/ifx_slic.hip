@@ -870,6 +870,17 @@ int ifx_superpixel_begin(ifx* h, const uint8_t* rgb, const uint16_t* depth)
     if ((r = slic_run(h, b))) return r;
     return merge_run(h, b);
 }
+// The same with the frame in device memory the caller keeps alive until the call is over (a deferred call's pinned frame, ifx_segmentation_snapshot): read in place.
+// Superpixels run ahead belong to the resident frame, never to this one (slic_buffers queues behind an unclaimed run).
+int ifx_superpixel_begin_device(ifx* h, const uint8_t* d_rgb, const uint16_t* d_depth)
+{
+    SlicBuf* b;
+    int r = slic_buffers(h, &b);
+    if (r) return r;
+    b->cur_rgb = d_rgb; b->cur_depth = d_depth;
+    if ((r = slic_run(h, b))) return r;
+    return merge_run(h, b);
+}
 // Look-ahead of a segmentation call (ifx_should_segment: "not this frame, but the cadence says the next one").  SLIC and the superpixel merge read the frame only
 // -- 27 dispatches, about half of a call -- and the announced next frame's raw images are already in their frame slot (copied there by its frame side, on the side
 // stream): the same stream runs them now, under the next frame's tracker and map passes, and the call that comes waits for one event instead.  The same kernels on

@@ -939,6 +939,48 @@ public:
         segmentations_++;
     }
 
+    // ---- a detector slower than the frame loop (ifx_segmentation_snapshot / ifx_process_segmentation_deferred; the reference's detector thread is off, IF/main.cpp:83).
+    // SnapshotSegmentation pins, without stalling the frame loop, what a call reads of the frame just processed -- id image, pose and (with the superpixel refinement on)
+    // the raw frame -- and returns a ticket; frames go on; ProcessSegmentationDeferred[Device] applies the masks the detector made of THAT frame to the map as it is
+    // then (surfels gone since get no votes, surfels created since are in no pixel) and releases the ticket.  detect(): the mask source's answer for a frame, for the
+    // caller to hold until then.  Not on a sharded map.
+    int SnapshotSegmentation(const std::unique_ptr<ElasticFusionInterface>& map)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::SnapshotSegmentation: the map has no handle (") + ifx_global_error() + ")");
+        const int t = ifx_segmentation_snapshot(h, superpixels_ ? 2 : 0);
+        if (t < 0) throw std::runtime_error(std::string("ifx_segmentation_snapshot: ") + ifx_last_error(h));
+        return t;
+    }
+    bool detect(int frame_num, const ImagePtr rgb, MaskResult* out)
+    {
+        if (!source_) throw std::runtime_error("InstanceFusion::detect: no mask source");
+        return source_->detect(frame_num, rgb, width, height, out);
+    }
+    void ProcessSegmentationDeferred(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const MaskResult& res, int frame_num, bool isflann)
+    {
+        ifx_t* h = map->handle();
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        const int r = ifx_process_segmentation_deferred(h, ticket, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+    }
+    void ProcessSegmentationDeferredDevice(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const void* d_masks, int format, float threshold, const int32_t* d_class_ids,
+                                           int n, int frame_num, bool isflann, void* stream)
+    {
+        ifx_t* h = map->handle();
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        const int r = ifx_process_segmentation_deferred_device(h, ticket, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_device: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+    }
+    void ReleaseSnapshot(const std::unique_ptr<ElasticFusionInterface>& map, int ticket)
+    {
+        if (ifx_segmentation_snapshot_release(map->handle(), ticket) < 0) throw std::runtime_error(std::string("ifx_segmentation_snapshot_release: ") + ifx_last_error(map->handle()));
+    }
+
     // IF/Core/InstanceTable.cpp:336-445: precision / recall against the ground-truth ids the surfels carry (processFrame's instanceGT); appends to `path` the
     // rows the reference appends to ./temp/Precision_Recall_RAW.txt.  inUse: instance slots in use (+ evicted ones) as the reference's summary row reports them.
     void evaluateAndSave(const std::unique_ptr<ElasticFusionInterface>& map, const std::string& fileName, const std::string& path = "./Precision_Recall_RAW.txt")

@@ -5,7 +5,7 @@
 // (map->SavePly(), IF/main.cpp:300-305), and optionally the per-surfel instance labels.
 //
 //   ifx_replay LOG.klg|data.txt [--width 640 --height 480 --fx 528 --fy 528 --cx 320 --cy 240] [--masks DIR] [--out PREFIX]
-//              [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--device K] [--gt-dir DIR --eval FILE]
+//              [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--device K] [--gt-dir DIR --eval FILE] [--mask-lag K]
 #include <chrono>
 #include <cstdlib>
 #include <iostream>
@@ -23,6 +23,7 @@ struct Args {
     float fx = 528.f, fy = 528.f, cx = 320.f, cy = 240.f;
     bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false;
     int decode_threads = 4;
+    int mask_lag = -1;   // --mask-lag K: the masks recorded for frame t arrive K frames later (a detector slower than the frame loop) and are applied through a snapshot of frame t
     float confidence = 10.f;
     Sharding shard;   // --shard-ranks G --shard-rank r --shard-id FILE: this process is rank r of G over one spatially sharded map (one process per GPU)
 };
@@ -31,7 +32,7 @@ int usage(const char* argv0)
 {
     std::fprintf(stderr,
                  "usage: %s LOG.klg|data.txt [--width W --height H --fx F --fy F --cx C --cy C] [--masks DIR] [--out PREFIX]\n"
-                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids]\n"
+                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K]\n"
                  "       [--gt-dir DIR (DIR/<frame, 6 digits>.png, 8-bit instance ground truth)] [--eval FILE (precision / recall rows, needs --gt-dir)]\n"
                  "       [--shard-ranks G --shard-rank r --shard-id FILE [--shard-nonce N] (one process per GPU over one spatially sharded map; every rank replays the same log; -1: a world of one)]\n",
                  argv0);
@@ -70,6 +71,7 @@ int main(int argc, char** argv)
         else if (s == "--confidence") a.confidence = (float)std::atof(val("--confidence"));
         else if (s == "--flip-colors") a.flip = true;
         else if (s == "--reference-ids") a.reference_ids = true;   // id images by the reference's screen-space quad rule (option "id_rule" = 1; not on a sharded map)
+        else if (s == "--mask-lag") a.mask_lag = std::atoi(val("--mask-lag"));   // snapshot at the frame the masks belong to, deferred call K frames later (one detection in flight, as with one detector)
         else if (s == "--no-lookahead") a.lookahead = false;   // frames are handed over one at a time, as the reference's loop does
         else if (s == "--shard-ranks") a.shard.ranks = std::atoi(val("--shard-ranks"));   // -1: a world of one on the sharded path
         else if (s == "--shard-rank") a.shard.rank = std::atoi(val("--shard-rank"));
@@ -113,6 +115,13 @@ int main(int argc, char** argv)
         if (!a.deform) map->elasticFusion().setDeformOnLoopClosure(false);
         if (a.reference_ids) map->elasticFusion().setReferenceIdRule(true);
 
+        if (a.mask_lag >= 0 && a.shard.on()) { std::fprintf(stderr, "--mask-lag is not available on a sharded map\n"); return 2; }
+        struct { bool busy = false; int ticket = -1, frame = 0; bool flann = false, has = false; MaskResult res; } pending;   // the detection in flight (--mask-lag)
+        auto apply_pending = [&]() {
+            if (pending.has) instancefusion->ProcessSegmentationDeferred(map, pending.ticket, pending.res, pending.frame, pending.flann);
+            else instancefusion->ReleaseSnapshot(map, pending.ticket);   // the detector had nothing for that frame
+            pending.busy = false;
+        };
         int frame_Fusion = 0, lastTimeFlann = -1;
         std::vector<int> instanceTableLoopClosure((size_t)instancefusion->getInstanceNum() * 5);
         const auto t0 = std::chrono::steady_clock::now();
@@ -141,16 +150,24 @@ int main(int argc, char** argv)
                 std::cout << "Elastic fusion lost!" << a.log << std::endl;
                 return 1;
             }
-            if (frame_Fusion >= cnn_start_frames && !a.masks.empty() && instancefusion->whetherDoSegmentation(map, frame_Fusion)) {
+            if (pending.busy && frame_Fusion - pending.frame >= a.mask_lag) apply_pending();   // the masks of frame t arrive at frame t + K
+            if (frame_Fusion >= cnn_start_frames && !a.masks.empty() && !pending.busy && instancefusion->whetherDoSegmentation(map, frame_Fusion)) {   // (a busy detector is not asked)
                 bool flannFlag = false;
                 if (frame_Fusion - lastTimeFlann > flann_skip_frames) {
                     lastTimeFlann = frame_Fusion;
                     flannFlag = true;
                 }
-                instancefusion->ProcessSegmentation(log_reader->rgb, log_reader->depth, map, frame_Fusion, flannFlag);
+                if (a.mask_lag < 0) instancefusion->ProcessSegmentation(log_reader->rgb, log_reader->depth, map, frame_Fusion, flannFlag);
+                else {
+                    pending.ticket = instancefusion->SnapshotSegmentation(map);
+                    pending.busy = true; pending.frame = frame_Fusion; pending.flann = flannFlag;
+                    pending.has = instancefusion->detect(frame_Fusion, log_reader->rgb, &pending.res);
+                    if (a.mask_lag == 0) apply_pending();
+                }
             }
             frame_Fusion++;
         }
+        if (pending.busy) apply_pending();   // the log ended under a detection: its masks still count
         ifx_sync(map->handle());
         const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
