@@ -515,6 +515,36 @@ int ifx_process_segmentation_deferred_device(ifx_t* h, int ticket, const void* d
                                              void* stream);
 int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
 int ifx_segmentation_snapshot_stats(ifx_t* h, int ticket, int32_t* out4);
+/* ---- the mask head's own output: ROI masks and boxes, pasted on the device.  A maskrcnn-benchmark / detectron-style mask head yields n x 1 x M x M probabilities
+ * (M = 28) and n boxes; the reference's bridge (build/mask_benchmark.py through COCODemo.compute_prediction) turns them into image-sized masks with
+ * maskrcnn-benchmark's Masker on the CPU, one mask at a time: paste_mask_in_image with expand_masks and expand_boxes,
+ * deps/maskrcnn-benchmark-master/maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:91-154.  These entries take the n x (M^2 + 4) floats as they are.
+ * d_roi_masks: n x M x M f32 (device), contiguous ([N,1,M,M] is the same layout), roi_size = M in 1 .. 64.  d_boxes: n x 4 f32 (device), (x0, y0, x1, y1) in
+ * FRAME pixel coordinates.  threshold: a pixel is inside iff its interpolated value is > threshold (the Masker's default 0.5; NaN is outside).
+ * The paste rule, every operation rounded to f32 and none fused (S = M + 2):
+ *   the ROI mask inside a border of one zero sample (padding = 1); scale = f32(double(S) / M);
+ *   wh = (x1 - x0) * 0.5, hh = (y1 - y0) * 0.5, xc = (x1 + x0) * 0.5, yc = (y1 + y0) * 0.5, wh *= scale, hh *= scale;
+ *   (b0, b1, b2, b3) = (xc - wh, yc - hh, xc + wh, yc + hh) truncated toward zero to int32;  w = max(b2 - b0 + 1, 1), h = max(b3 - b1 + 1, 1);
+ *   sx = f32(S) / f32(w), sy = f32(S) / f32(h);  clip rectangle x in [max(b0, 0), min(b2 + 1, W)), y in [max(b1, 0), min(b3 + 1, H));
+ *   per pixel and axis, d = x - b0:  r = max(sx * (f32(d) + 0.5) - 0.5, 0), i0 = min(int(r), S - 1), i1 = min(i0 + 1, S - 1), l1 = r - f32(i0), l0 = 1 - l1;
+ *   v = yl0 * (xl0 * pm[yi0][xi0] + xl1 * pm[yi0][xi1]) + yl1 * (xl0 * pm[yi1][xi0] + xl1 * pm[yi1][xi1]);  inside iff v > threshold.
+ * Held against the reference's own functions pixel for pixel except where |v - threshold| <= 2^-22 (its vectorised resize fuses multiply-adds):
+ * tests/test_roi_paste_cpu.py.  Where the reference raises, the mask is empty and the call goes on: a box with no pixel in the image, a non-finite coordinate,
+ * a coordinate beyond +-2^24.  Behind the paste come the bridge's two steps as for ifx_process_segmentation_device (binarise, STABLE sort by area, descending).
+ * ifx_process_segmentation_rois: everything else as ifx_process_segmentation_device -- any input order, event wait on `stream`, the resident frame, n <= 256, flags.
+ *   Result: bit for bit that of ifx_process_segmentation_device on the n x H x W masks the rule above gives.
+ * ifx_process_segmentation_deferred_rois: the deferred call fed the same way; ticket rules as ifx_process_segmentation_deferred_device.
+ * ifx_paste_roi_masks: the ingestion alone, as a stage -- what the calls above would hand on.  Downloads, each to a HOST pointer that may be NULL: the 0/255 masks
+ *   in the bridge's order (n x H x W), the same after the overlap clean (maskCleanOverlap), the order (n input indices) and the class ids in that order.
+ *   Synchronises.  n == 0 writes nothing.
+ * Refusals (nothing enqueued, the handle stays usable): IFX_E_INVALID for roi_size outside 1 .. 64, n < 0, n > 256 or NULL device pointers with n > 0;
+ * IFX_E_STATE on a sharded handle; the deferred entry refuses as ifx_process_segmentation_deferred_device does. */
+int ifx_process_segmentation_rois(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
+                                  void* stream);
+int ifx_process_segmentation_deferred_rois(ifx_t* h, int ticket, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n,
+                                           int frame, int flags, void* stream);
+int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
+                        uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

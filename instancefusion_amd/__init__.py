@@ -159,6 +159,9 @@ _SIGS = {
     "ifx_segmentation_snapshot": (C.c_int, [_P, C.c_int]),
     "ifx_process_segmentation_deferred": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]),
     "ifx_process_segmentation_deferred_device": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_process_segmentation_rois": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_process_segmentation_deferred_rois": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_paste_roi_masks": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
@@ -704,6 +707,77 @@ class InstanceFusion:
         self.ef._chk(self.L.ifx_process_segmentation_deferred_device(self.ef.handle, int(ticket), C.c_void_p(m.data_ptr() or None), fmt, float(threshold),
                                                                      C.c_void_p(cls.data_ptr() or None), n, int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
                      "ifx_process_segmentation_deferred_device")
+
+    # -- the mask head's own output: [N,1,M,M] probabilities and N boxes, pasted on the GPU as maskrcnn-benchmark's Masker does on the CPU (include/ifx_c_api.h)
+    def _device_rois(self, roi_masks, boxes, class_ids, stream):
+        """validates a mask head's tensors for the ROI entries: (contiguous ROI masks, M, contiguous boxes, int32 class ids on the device, n, stream)"""
+        import torch
+
+        dev = torch.device("cuda", int(self.ef.cfgd["device"]))
+        for name, t in (("roi_masks", roi_masks), ("boxes", boxes)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch tensor on the handle's device")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name}: dtype {t.dtype} is not supported (float32)")
+            if t.device != dev:
+                raise ValueError(f"{name} are on {t.device}, the handle on {dev}")
+        sh = tuple(roi_masks.shape)
+        if not ((len(sh) == 3 and sh[1] == sh[2]) or (len(sh) == 4 and sh[1] == 1 and sh[2] == sh[3])):
+            raise ValueError(f"roi_masks: shape {sh}, expected [N,M,M] or [N,1,M,M]")
+        n, M = int(sh[0]), int(sh[-1])
+        if not 1 <= M <= 64:
+            raise ValueError(f"roi_masks: M = {M}, expected 1 .. 64")
+        if tuple(boxes.shape) != (n, 4):
+            raise ValueError(f"boxes: shape {tuple(boxes.shape)}, expected [{n},4]")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(stream):          # whatever has to be made on the way is made on the producer's stream
+            m = roi_masks.contiguous()
+            bx = boxes.contiguous()
+            if isinstance(class_ids, torch.Tensor):
+                if class_ids.dtype.is_floating_point or class_ids.dtype.is_complex or class_ids.dtype == torch.bool:
+                    raise TypeError(f"class_ids: dtype {class_ids.dtype} is not an integer type")
+                cls = class_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+            else:
+                a = np.asarray(class_ids)
+                if a.size and not np.issubdtype(a.dtype, np.integer):
+                    raise TypeError(f"class_ids: {a.dtype} is not an integer type")
+                cls = torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)   # (no host synchronisation on the stream)
+        if int(cls.numel()) != n:
+            raise ValueError(f"class_ids: {int(cls.numel())} entries for {n} ROI masks")
+        return m, M, bx, cls, n, stream
+
+    def process_segmentation_rois(self, roi_masks, boxes, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
+        """ProcessSegmentation on a mask head's own output on the handle's GPU (ifx_process_segmentation_rois): the Masker's paste, the bridge's binarisation and
+        its stable area sort all run there.  roi_masks: float32 [N,M,M] or [N,1,M,M] probabilities, M in 1 .. 64; boxes: float32 [N,4] (x0, y0, x1, y1) in frame
+        pixel coordinates; class_ids, stream and the resident frame as for process_segmentation_device."""
+        m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
+        flags = (1 if isflann else 0) | (2 if superpixels else 0)
+        self.ef._chk(self.L.ifx_process_segmentation_rois(self.ef.handle, C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None), float(threshold),
+                                                          C.c_void_p(cls.data_ptr() or None), n, int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
+                     "ifx_process_segmentation_rois")
+
+    def process_segmentation_deferred_rois(self, ticket, roi_masks, boxes, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
+        """The deferred call on a mask head's own output: tensors and stream exactly as for process_segmentation_rois."""
+        m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
+        flags = (1 if isflann else 0) | (2 if superpixels else 0)
+        self.ef._chk(self.L.ifx_process_segmentation_deferred_rois(self.ef.handle, int(ticket), C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None),
+                                                                   float(threshold), C.c_void_p(cls.data_ptr() or None), n, int(frame), flags,
+                                                                   C.c_void_p(stream.cuda_stream or None)),
+                     "ifx_process_segmentation_deferred_rois")
+
+    def paste_roi_masks(self, roi_masks, boxes, class_ids, threshold=0.5, stream=None):
+        """The ingestion of process_segmentation_rois alone (ifx_paste_roi_masks): (the pasted 0/255 masks [N,H,W] in the bridge's order, the same after the
+        overlap clean, the order as input indices, the class ids in that order), as numpy arrays."""
+        m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
+        ori = np.zeros((n, self.ef.h, self.ef.w), np.uint8)
+        clean = np.zeros_like(ori)
+        order, out_cls = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.ef._chk(self.L.ifx_paste_roi_masks(self.ef.handle, C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None), float(threshold),
+                                                C.c_void_p(cls.data_ptr() or None), n, C.c_void_p(stream.cuda_stream or None), _ptr(ori), _ptr(clean), _ptr(order),
+                                                _ptr(out_cls)),
+                     "ifx_paste_roi_masks")
+        return ori, clean, order, out_cls
 
     def release_snapshot(self, ticket):
         self.ef._chk(self.L.ifx_segmentation_snapshot_release(self.ef.handle, int(ticket)), "ifx_segmentation_snapshot_release")

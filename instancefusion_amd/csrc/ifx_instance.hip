@@ -177,6 +177,143 @@ __global__ void __launch_bounds__(MI_THREADS) k_mask_gather(const T* __restrict_
     }
 }
 
+// ---- the mask head's own output (ifx_process_segmentation_rois): n ROI masks of M x M probabilities and n boxes, pasted into the image as maskrcnn-benchmark's
+// Masker does on the CPU (paste_mask_in_image with expand_masks / expand_boxes, maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:91-154: one sample of
+// zero padding, the box grown by (M + 2) / M and truncated to integers, bilinear resize with align_corners = False to the box, > threshold, clip to the image).
+// The arithmetic is the CPU statement's (tests/roi_paste_numpy.py), operation for operation in f32 with no contraction, so both kernels here and that statement
+// decide every pixel alike.  Where the reference raises -- a box with no pixel in the image, a non-finite coordinate, one beyond +-2^24 -- the mask is empty.
+#define ROI_M_MAX 64
+#define ROI_PX 16      // consecutive pixels per thread
+struct RoiRec { int b0, b1, X0, X1, Y0, Y1; float sx, sy; };   // the expanded integer box's corner, the clip rectangle [X0,X1) x [Y0,Y1) (empty: all zero), S / w and S / h
+__device__ __forceinline__ RoiRec roi_record(const float* __restrict__ box, int S, float scale, int W, int H)
+{
+    const float x0 = box[0], y0 = box[1], x1 = box[2], y1 = box[3];
+    RoiRec r = {0, 0, 0, 0, 0, 0, 0.f, 0.f};
+    const float lim = 16777216.f;
+    if (!(fabsf(x0) <= lim && fabsf(y0) <= lim && fabsf(x1) <= lim && fabsf(y1) <= lim)) return r;   // (NaN fails every comparison)
+    float wh = (x1 - x0) * 0.5f, hh = (y1 - y0) * 0.5f;
+    const float xc = (x1 + x0) * 0.5f, yc = (y1 + y0) * 0.5f;
+    wh *= scale; hh *= scale;
+    const int b0 = (int)(xc - wh), b1 = (int)(yc - hh), b2 = (int)(xc + wh), b3 = (int)(yc + hh);   // toward zero, as Tensor.to(int32); |b| < 2^26
+    const int w = max(b2 - b0 + 1, 1), h = max(b3 - b1 + 1, 1);
+    const int X0 = max(b0, 0), X1 = min(b2 + 1, W), Y0 = max(b1, 0), Y1 = min(b3 + 1, H);
+    if (X1 <= X0 || Y1 <= Y0) return r;
+    r.b0 = b0; r.b1 = b1; r.X0 = X0; r.X1 = X1; r.Y0 = Y0; r.Y1 = Y1;
+    r.sx = __fdiv_rn((float)S, (float)w); r.sy = __fdiv_rn((float)S, (float)h);
+    return r;
+}
+// source samples and weights of destination offset d on one axis (the resize's area_pixel source index, clamped at 0)
+struct RoiAxis { int i0, i1; float l0, l1; };
+__device__ __forceinline__ RoiAxis roi_axis(float s, int d, int S)
+{
+    const float r = fmaxf(s * ((float)d + 0.5f) - 0.5f, 0.f);
+    RoiAxis a;
+    a.i0 = min((int)r, S - 1);
+    a.i1 = min(a.i0 + 1, S - 1);
+    a.l1 = r - (float)a.i0;
+    a.l0 = 1.f - a.l1;
+    return a;
+}
+__device__ __forceinline__ float roi_blend(const RoiAxis& ay, const RoiAxis& ax, float p00, float p01, float p10, float p11)
+{
+    return ay.l0 * (ax.l0 * p00 + ax.l1 * p01) + ay.l1 * (ax.l0 * p10 + ax.l1 * p11);
+}
+// Inside pixels per ROI: grid (chunks, n), a block takes MI_THREADS * ROI_PX pixels of its ROI's clip rectangle in row-major order.  The rectangle is only known
+// here, so the grid covers a whole image per ROI and the blocks past the rectangle leave at once.  The padded mask is staged in LDS, its border written here.
+// Sums as k_mask_area: per wave, per block in LDS, one atomic per block; the counters are zero on entry.
+__global__ void __launch_bounds__(MI_THREADS) k_roi_area(const float* __restrict__ rois, int M, const float* __restrict__ boxes, float scale, float thr, int W, int H, int* __restrict__ area)
+{
+    __shared__ float s_pm[(ROI_M_MAX + 2) * (ROI_M_MAX + 2)];
+    __shared__ int s_c[MI_THREADS / 64];
+    const int m = blockIdx.y, tid = threadIdx.x, S = M + 2;
+    const RoiRec rc = roi_record(boxes + 4 * m, S, scale, W, H);
+    const int rw = rc.X1 - rc.X0, n_px = rw * (rc.Y1 - rc.Y0);
+    if (blockIdx.x * (MI_THREADS * ROI_PX) >= n_px) return;   // (the whole block)
+    const float* src = rois + (size_t)m * M * M;
+    for (int t = tid; t < S * S; t += MI_THREADS) {
+        const int r = t / S, c = t - r * S;
+        s_pm[t] = (r == 0 || r == S - 1 || c == 0 || c == S - 1) ? 0.f : src[(r - 1) * M + (c - 1)];
+    }
+    __syncthreads();
+    int c = 0;
+    const int i0 = (blockIdx.x * MI_THREADS + tid) * ROI_PX;
+    if (i0 < n_px) {
+        const int cnt = min(ROI_PX, n_px - i0);
+        int ry = i0 / rw, rx = i0 - ry * rw;
+        RoiAxis ay = roi_axis(rc.sy, rc.Y0 + ry - rc.b1, S);
+        for (int j = 0; j < cnt; j++) {
+            const RoiAxis ax = roi_axis(rc.sx, rc.X0 + rx - rc.b0, S);
+            const float* r0 = s_pm + ay.i0 * S;
+            const float* r1 = s_pm + ay.i1 * S;
+            c += roi_blend(ay, ax, r0[ax.i0], r0[ax.i1], r1[ax.i0], r1[ax.i1]) > thr ? 1 : 0;
+            if (++rx == rw) { rx = 0; ry++; ay = roi_axis(rc.sy, rc.Y0 + ry - rc.b1, S); }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((tid & 63) == 0) s_c[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int w = 0; w < MI_THREADS / 64; w++) sum += s_c[w];
+        if (sum) atomicAdd(&area[m], sum);
+    }
+}
+// k_mask_gather's pass with the paste in place of the load: the ROIs in sorted order from the last to the first, a thread owns ROI_PX consecutive pixels (they
+// may run over the end of a row; P is a multiple of 16 because width and height are multiples of 4, ifx_create), writes the 0/255 masks in sorted order and the overlap-cleaned copy, and the verdict bytes are cleared.  The per-ROI records sit
+// in LDS in sorted order; a group that misses a ROI's clip rectangle stores zeros without evaluating anything; otherwise the y terms are shared along the row.
+// The samples come through the cache (all ROIs of a call: a few KB to 4 MB); the border of the padded mask is never read.
+__global__ void __launch_bounds__(MI_THREADS) k_roi_gather(const float* __restrict__ rois, int M, const float* __restrict__ boxes, float scale, float thr, int W, int H,
+                                                           const int* __restrict__ order, int nm, uint8_t* __restrict__ ori, uint8_t* __restrict__ masks,
+                                                           uint8_t* __restrict__ unavail)
+{
+    __shared__ RoiRec s_rec[256];
+    __shared__ int s_src[256];
+    const int P = W * H, S = M + 2, MM = M * M;
+    const int g = blockIdx.x * MI_THREADS + threadIdx.x;
+    for (int t = threadIdx.x; t < nm; t += MI_THREADS) {
+        const int src = order[t];
+        s_src[t] = src;
+        s_rec[t] = roi_record(boxes + 4 * src, S, scale, W, H);
+    }
+    if (unavail && g < nm) unavail[g] = 0;
+    __syncthreads();
+    const int p0 = g * ROI_PX;
+    if (p0 >= P) return;
+    constexpr int np = ROI_PX;
+    const int ya = p0 / W, xa = p0 - ya * W, yb = (p0 + np - 1) / W;
+    uint32_t flag = 0;   // bit j: pixel p0 + j lies in a mask later in the sorted order
+    for (int s = nm - 1; s >= 0; s--) {
+        const RoiRec rc = s_rec[s];
+        uint32_t in = 0;
+        const bool miss = yb < rc.Y0 || ya >= rc.Y1 || (ya == yb && (xa + np <= rc.X0 || xa >= rc.X1));
+        if (!miss) {
+            const float* src = rois + (size_t)s_src[s] * MM;
+            auto sample = [&](int yi, int xi) { return (yi >= 1 && yi <= M && xi >= 1 && xi <= M) ? src[(yi - 1) * M + (xi - 1)] : 0.f; };
+            int x = xa, y = ya;
+            bool yin = y >= rc.Y0 && y < rc.Y1;
+            RoiAxis ay = roi_axis(rc.sy, yin ? y - rc.b1 : 0, S);
+            for (int j = 0; j < np; j++) {
+                if (yin && x >= rc.X0 && x < rc.X1) {
+                    const RoiAxis ax = roi_axis(rc.sx, x - rc.b0, S);
+                    in |= (roi_blend(ay, ax, sample(ay.i0, ax.i0), sample(ay.i0, ax.i1), sample(ay.i1, ax.i0), sample(ay.i1, ax.i1)) > thr ? 1u : 0u) << j;
+                }
+                if (++x == W) { x = 0; y++; yin = y >= rc.Y0 && y < rc.Y1; ay = roi_axis(rc.sy, yin ? y - rc.b1 : 0, S); }
+            }
+        }
+        const uint32_t kept = in & ~flag;
+        flag |= in;
+        uint8_t* o = ori + (size_t)s * P + p0;
+        uint8_t* w = masks + (size_t)s * P + p0;
+        uint32_t wo[4] = {0, 0, 0, 0}, ww[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < ROI_PX; j++) { wo[j >> 2] |= ((in >> j) & 1u) * (0xffu << (8 * (j & 3))); ww[j >> 2] |= ((kept >> j) & 1u) * (0xffu << (8 * (j & 3))); }
+        *(uint4*)o = make_uint4(wo[0], wo[1], wo[2], wo[3]);
+        *(uint4*)w = make_uint4(ww[0], ww[1], ww[2], ww[3]);
+    }
+}
+
 // checkProjectDepthAndInstanceKernel, IF/Core/InstanceFusionCuda.cu:736-760
 __global__ void k_check_project(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ votes, int cap, int w, int h, int downsample,
                                 int* __restrict__ counts)
@@ -1219,7 +1356,8 @@ static int oseg_resume(ifx* h)
 
 // the masks of ifx_process_segmentation_device: the caller's n x P elements in device memory, their format, the class ids (device), and an event recorded on the
 // producer's stream at entry (the ingestion waits for it; nothing before the ingestion does)
-struct DevMasks { const void* d; int fmt; float thr; const int32_t* d_cls; hipEvent_t ready; };
+// ifx_process_segmentation_rois: roi = M > 0, d = n x M x M f32 ROI masks, d_boxes = n x 4 f32 (xyxy) -- pasted on the device in place of the n x P elements
+struct DevMasks { const void* d; int fmt; float thr; const int32_t* d_cls; hipEvent_t ready; const float* d_boxes = nullptr; int roi = 0; };
 struct SegSnap;   // a pinned frame of ifx_segmentation_snapshot (below): null for the ordinary entries
 static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
 static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
@@ -1245,6 +1383,52 @@ extern "C" int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, in
     const int r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags);
     h->event_pool.push_back(dm.ready);
     return r;
+}
+// The mask head's ROI masks and boxes (maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:91-154): argument checks shared by the three ROI entries
+static int roi_args_check(ifx* h, const char* who, const float* d_roi_masks, int roi_size, const float* d_boxes, const int32_t* d_class_ids, int n)
+{
+    if (n < 0 || n > 256) { h->err = std::string(who) + ": n must be 0 .. 256"; return IFX_E_INVALID; }
+    if (roi_size < 1 || roi_size > ROI_M_MAX) { h->err = std::string(who) + ": roi_size must be 1 .. 64"; return IFX_E_INVALID; }
+    if (n > 0 && (!d_roi_masks || !d_boxes || !d_class_ids)) { h->err = std::string(who) + ": null ROI masks, boxes or class ids"; return IFX_E_INVALID; }
+    return IFX_OK;
+}
+extern "C" int ifx_process_segmentation_rois(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
+                                             void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = roi_args_check(h, "ifx_process_segmentation_rois", d_roi_masks, roi_size, d_boxes, d_class_ids, n);
+    if (r) return r;
+    if (h->own || h->shard_n > 1) { h->err = "ifx_process_segmentation_rois: a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
+    DevMasks dm{d_roi_masks, IFX_MASK_F32, threshold, d_class_ids, ifx_event_get(h), d_boxes, roi_size};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_rois: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
+    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags);
+    h->event_pool.push_back(dm.ready);
+    return r;
+}
+static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail);
+extern "C" int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
+                                   uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = roi_args_check(h, "ifx_paste_roi_masks", d_roi_masks, roi_size, d_boxes, d_class_ids, n);
+    if (r) return r;
+    if (h->own || h->shard_n > 1) { h->err = "ifx_paste_roi_masks: not on a sharded map"; return IFX_E_STATE; }
+    if (n == 0) return IFX_OK;
+    const size_t bytes = (size_t)n * h->P;
+    if ((r = ifx_ensure_masks(h, bytes))) return r;
+    DevMasks dm{d_roi_masks, IFX_MASK_F32, threshold, d_class_ids, ifx_event_get(h), d_boxes, roi_size};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_paste_roi_masks: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
+    r = seg_ingest_device(h, &dm, n, nullptr, nullptr);
+    h->event_pool.push_back(dm.ready);
+    if (r) return r;
+    if (out_ori) HIPCHK(h, hipMemcpyAsync(out_ori, h->d_masks_ori, bytes, hipMemcpyDeviceToHost, h->cur));
+    if (out_clean) HIPCHK(h, hipMemcpyAsync(out_clean, h->d_masks, bytes, hipMemcpyDeviceToHost, h->cur));
+    if (out_order) HIPCHK(h, hipMemcpyAsync(out_order, h->d_mask_rank + 256, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
+    if (out_class_ids) HIPCHK(h, hipMemcpyAsync(out_class_ids, h->d_mask_rank + 512, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return IFX_OK;
 }
 static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
 extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
@@ -1272,6 +1456,22 @@ extern "C" int ifx_process_segmentation_deferred_device(ifx_t* h, int ticket, co
     DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
     const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
     if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_deferred_device: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
+    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags, q);
+    h->event_pool.push_back(dm.ready);
+    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
+    return r;
+}
+extern "C" int ifx_process_segmentation_deferred_rois(ifx_t* h, int ticket, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n,
+                                                      int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = roi_args_check(h, "ifx_process_segmentation_deferred_rois", d_roi_masks, roi_size, d_boxes, d_class_ids, n);
+    if (r) return r;
+    SegSnap* q = nullptr;
+    if ((r = snap_for_call(h, "ifx_process_segmentation_deferred_rois", ticket, flags, &q))) return r;
+    DevMasks dm{d_roi_masks, IFX_MASK_F32, threshold, d_class_ids, ifx_event_get(h), d_boxes, roi_size};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_deferred_rois: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
     r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags, q);
     h->event_pool.push_back(dm.ready);
     if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
@@ -1378,6 +1578,23 @@ static int seg_ingest_launch(ifx* h, const T* src, float thr, const int32_t* d_c
     LAUNCH(h, "mask_gather", dim3(cdiv(cdiv(P, V), MI_THREADS)), dim3(MI_THREADS), k_mask_gather<T>, src, P, thr, (const int*)order, nm, vec, h->d_masks_ori, h->d_masks, unavail);
     return IFX_OK;
 }
+// The same three steps on ROI masks and boxes: k_roi_area counts what k_roi_gather will paste, k_mask_order as it is.  (M + 2) / M in double, rounded once, as
+// expand_masks computes it in Python.
+static int seg_ingest_rois(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail)
+{
+    const int P = h->P, M = dm->roi;
+    const float* rois = (const float*)dm->d;
+    const float scale = (float)((double)(M + 2) / (double)M);
+    static_assert(ROI_PX == 16, "k_roi_gather stores its group as one 16-B word");
+    if (P % ROI_PX) { h->err = "ROI paste: width x height is not a multiple of 16"; return IFX_E_STATE; }   // (ifx_create admits multiples of 4 only: every group of the outputs starts on a 16-B boundary)
+    int* area = h->d_mask_rank;
+    int* order = area + 256;
+    LAUNCH(h, "roi_area", dim3(cdiv(P, MI_THREADS * ROI_PX), nm), dim3(MI_THREADS), k_roi_area, rois, M, dm->d_boxes, scale, dm->thr, h->w, h->h, area);
+    LAUNCH(h, "mask_order", dim3(1), dim3(256), k_mask_order, area, dm->d_cls, nm, order, cls_out);
+    LAUNCH(h, "roi_gather", dim3(cdiv(P / ROI_PX, MI_THREADS)), dim3(MI_THREADS), k_roi_gather, rois, M, dm->d_boxes, scale, dm->thr, h->w, h->h, (const int*)order, nm,
+           h->d_masks_ori, h->d_masks, unavail);
+    return IFX_OK;
+}
 static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail)
 {
     if (!h->d_mask_rank) {
@@ -1386,6 +1603,7 @@ static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, u
     }
     HIPCHK(h, hipStreamWaitEvent(h->cur, dm->ready, 0));   // behind what the producer enqueued before the call (no host synchronisation)
     if (!cls_out) cls_out = h->d_mask_rank + 512;
+    if (dm->roi) return seg_ingest_rois(h, dm, nm, cls_out, unavail);
     return dm->fmt == IFX_MASK_F32 ? seg_ingest_launch(h, (const float*)dm->d, dm->thr, dm->d_cls, nm, cls_out, unavail)
                                    : seg_ingest_launch(h, (const uint8_t*)dm->d, dm->thr, dm->d_cls, nm, cls_out, unavail);
 }

@@ -976,6 +976,35 @@ public:
         handle_ = h;
         segmentations_++;
     }
+    // ---- the mask head's own output (ifx_process_segmentation_rois): d_roi_masks n x M x M f32 probabilities and d_boxes n x 4 f32 (x0, y0, x1, y1, frame pixels) in
+    // device memory of the map's GPU, pasted there as maskrcnn-benchmark's Masker pastes them on the CPU (paste_mask_in_image,
+    // maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:91-154), then binarised and sorted as the bridge does.  Everything else as ProcessSegmentationDevice.
+    void ProcessSegmentationRois(const std::unique_ptr<ElasticFusionInterface>& map, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold,
+                                 const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationRois: the map has no handle (") + ifx_global_error() + ")");
+        if (map->elasticFusion().sharding().on())
+            throw std::runtime_error("InstanceFusion::ProcessSegmentationRois: a sharded map takes its masks from the host (ProcessSegmentation)");
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        const int r = ifx_process_segmentation_rois(h, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_rois: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+    }
+    void ProcessSegmentationDeferredRois(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold,
+                                         const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDeferredRois: the map has no handle (") + ifx_global_error() + ")");
+        if (map->elasticFusion().sharding().on())
+            throw std::runtime_error("InstanceFusion::ProcessSegmentationDeferredRois: a sharded map takes its masks from the host (ProcessSegmentation)");
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        const int r = ifx_process_segmentation_deferred_rois(h, ticket, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_rois: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+    }
     void ReleaseSnapshot(const std::unique_ptr<ElasticFusionInterface>& map, int ticket)
     {
         if (ifx_segmentation_snapshot_release(map->handle(), ticket) < 0) throw std::runtime_error(std::string("ifx_segmentation_snapshot_release: ") + ifx_last_error(map->handle()));
