@@ -487,6 +487,10 @@ int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth
 enum { IFX_MASK_U8 = 0, IFX_MASK_F32 = 1 };
 int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
                                     void* stream);
+/* ifx_ingest_masks: the ingestion of ifx_process_segmentation_device alone, as a stage (the twin of ifx_paste_roi_masks below): same arguments, checks and
+ * launches; downloads to HOST pointers that may be NULL: the 0/255 masks in the bridge's order, the same after the overlap clean, the order, the class ids. */
+int ifx_ingest_masks(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
+                     uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids);
 /* ---- deferred segmentation: a detector slower than the frame loop (no counterpart in the reference, whose detector thread is switched off at IF/main.cpp:83, so that
  * its masks always belong to the frame processed last).  ifx_process_segmentation[_device] reads the CURRENT id image, the CURRENT pose and the RESIDENT frame; a real
  * Mask R-CNN needs tens of milliseconds per image, i.e. dozens of frames.  The pair below makes a late call well-defined without stalling the frame loop; nobody who

@@ -161,6 +161,7 @@ _SIGS = {
     "ifx_process_segmentation_deferred_device": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_process_segmentation_rois": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_process_segmentation_deferred_rois": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_ingest_masks": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]),
     "ifx_paste_roi_masks": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
@@ -685,6 +686,18 @@ class InstanceFusion:
                                                             int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
                      "ifx_process_segmentation_device")
         # (the call returned after its work finished: m and cls may go; they were used on the handle's streams only behind `stream`)
+
+    def ingest_masks(self, masks, class_ids, threshold=0.5, stream=None):
+        """The ingestion of process_segmentation_device alone (ifx_ingest_masks): (the 0/255 masks [N,H,W] in the bridge's order, the same after the overlap
+        clean, the order as input indices, the class ids in that order), as numpy arrays."""
+        m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
+        ori = np.zeros((n, self.ef.h, self.ef.w), np.uint8)
+        clean = np.zeros_like(ori)
+        order, out_cls = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self.ef._chk(self.L.ifx_ingest_masks(self.ef.handle, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None), n,
+                                             C.c_void_p(stream.cuda_stream or None), _ptr(ori), _ptr(clean), _ptr(order), _ptr(out_cls)),
+                     "ifx_ingest_masks")
+        return ori, clean, order, out_cls
 
     # -- a detector slower than the frame loop: snapshot at the frame the masks belong to, deferred call when they arrive (include/ifx_c_api.h)
     def snapshot(self, superpixels=False):

@@ -1430,6 +1430,32 @@ extern "C" int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_s
     HIPCHK(h, hipStreamSynchronize(h->cur));
     return IFX_OK;
 }
+// the same stage for the image-sized masks of ifx_process_segmentation_device: k_mask_area, k_mask_order and k_mask_gather as the full call launches them
+extern "C" int ifx_ingest_masks(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori, uint8_t* out_clean,
+                                int32_t* out_order, int32_t* out_class_ids)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || n > 256) { h->err = "ifx_ingest_masks: n must be 0 .. 256"; return IFX_E_INVALID; }
+    if (mask_format != IFX_MASK_U8 && mask_format != IFX_MASK_F32) { h->err = "ifx_ingest_masks: unknown mask format"; return IFX_E_INVALID; }
+    if (n > 0 && (!d_masks || !d_class_ids)) { h->err = "ifx_ingest_masks: null masks or class ids"; return IFX_E_INVALID; }
+    if (h->own || h->shard_n > 1) { h->err = "ifx_ingest_masks: not on a sharded map"; return IFX_E_STATE; }
+    if (n == 0) return IFX_OK;
+    const size_t bytes = (size_t)n * h->P;
+    int r = ifx_ensure_masks(h, bytes);
+    if (r) return r;
+    DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_ingest_masks: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
+    r = seg_ingest_device(h, &dm, n, nullptr, nullptr);
+    h->event_pool.push_back(dm.ready);
+    if (r) return r;
+    if (out_ori) HIPCHK(h, hipMemcpyAsync(out_ori, h->d_masks_ori, bytes, hipMemcpyDeviceToHost, h->cur));
+    if (out_clean) HIPCHK(h, hipMemcpyAsync(out_clean, h->d_masks, bytes, hipMemcpyDeviceToHost, h->cur));
+    if (out_order) HIPCHK(h, hipMemcpyAsync(out_order, h->d_mask_rank + 256, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
+    if (out_class_ids) HIPCHK(h, hipMemcpyAsync(out_class_ids, h->d_mask_rank + 512, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return IFX_OK;
+}
 static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
 extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
 extern "C" int ifx_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
