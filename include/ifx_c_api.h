@@ -549,6 +549,41 @@ int ifx_process_segmentation_deferred_rois(ifx_t* h, int ticket, const float* d_
                                            int frame, int flags, void* stream);
 int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
                         uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids);
+/* ---- the detector's input, made on the device from the frame that is already there.  The reference makes it on the CPU: COCODemo.build_transform
+ * (deps/maskrcnn-benchmark-master/demo/predictor.py:132-160: ToPILImage, Resize(min_image_size), ToTensor, x255 or channel flip, Normalize), then
+ * to_image_list(image, SIZE_DIVISIBILITY) (predictor.py:198-202, maskrcnn_benchmark/structures/image_list.py:29-66) pads it and .to(device) uploads 3 * H' * W' * 4
+ * bytes.  These entries write the same floats, bit for bit, from the u8 frame in device memory: planar [1][3][H'][W'] f32.
+ * The rule (stated once more, with Pillow's tap arithmetic in full, in instancefusion_amd/host/ifx_detector_prep.hpp; in numpy in tests/detector_input_numpy.py):
+ *   Size (Resize.get_size, maskrcnn_benchmark/data/transforms/transforms.py:35-55; f64, Python semantics): size = min_size; with max_size > 0 (<= 0: none), if
+ *     f64(max(w,h)) / f64(min(w,h)) * size > max_size then size = (int)rint(max_size * min(w,h) / max(w,h)), half to even.  (w <= h and w == size) or (h <= w and
+ *     h == size): kept as it is.  Else w < h: ow = size, oh = (int)(f64(size * h) / w); otherwise oh = size, ow = (int)(f64(size * w) / h).
+ *     Padded (image_list.py:54-61): size_divisible = d > 0: W' = ceil(ow / d) * d, H' = ceil(oh / d) * d; d == 0: W' = ow, H' = oh.
+ *   Resize: Pillow's 8-bit bilinear resampling (what torchvision's Resize does to a PIL image), 22-bit integer taps, horizontal pass first and then vertical, each
+ *     clip8(((1 << 21) + sum v * k) >> 22) per channel with a uint8 intermediate, each skipped when its axis keeps its size.
+ *   Float tail, per OUTPUT channel c with source channel s = (flags & IFX_DET_SWAP_RB) ? 2 - c : c: t = f32(byte) / 255.f; with IFX_DET_SCALE_255 t = t * 255.f;
+ *     out = (t - mean[c]) / std[c]; every operation rounded to f32, none fused, true divisions (predictor.py:142-145: x255 without a flip, or a flip alone;
+ *     transforms.py:86-90: both).  mean / std follow the flip, as T.Normalize is applied behind it.
+ *   Padding: samples with x >= ow or y >= oh are 0.0f (to_image_list zero-fills behind the normalisation).
+ * ifx_detector_input_size (host only: no handle, no GPU): out4 = ow, oh, W', H' by the size rule above (transforms.py:35-55, image_list.py:54-61).
+ * ifx_detector_resize_taps (host only): Pillow's taps of one axis -- first[out_size], count[out_size], coeff[out_size][ksize], zero behind count; returns
+ *   ksize = 2 * ceil(max(in / out, 1)) + 1, or IFX_E_INVALID (nothing written) for sizes < 1, NULL pointers or ksize > max_ksize.
+ * ifx_detector_input: the frame processed last (ticket < 0: the resident frame slot, also while the next frame is announced and its copy-in under way) or the
+ *   frame of a snapshot (a ticket of ifx_segmentation_snapshot taken with flags bit 1; the call orders itself behind the snapshot and does NOT release the ticket).
+ *   d_out: out_floats >= 3 * H' * W' floats in device memory.  stream is the CONSUMER's stream (the detector's; NULL = the null stream): the call is enqueue-only on
+ *   the handle's main stream -- at entry it records an event on `stream` and lets the main stream wait for it (an earlier forward pass may still read d_out), behind
+ *   the kernel it records an event on the main stream and lets `stream` wait for it.  No host synchronisation.  The side stream's next copy-in into the frame slot is
+ *   held off behind the read, as for a snapshot.  The tap tables are made on the host and cached in the handle per (w, h, ow, oh).
+ * ifx_detector_input_image: the same kernel on any u8 H x W x 3 image in device memory (width x height need not be the handle's), as a stage.
+ * Refusals (nothing enqueued, the handle stays usable).  IFX_E_INVALID: NULL pointers, min_size < 1, size_divisible < 0, unknown flag bits, a std entry of 0,
+ *   out_floats < 3 * H' * W', an unknown or released ticket, a resize scale above 8 on either axis (an output smaller than an eighth of the frame: this bounds the
+ *   taps at 17).  IFX_E_STATE (ifx_detector_input only): no frame processed yet, a ticket taken without its frame, a ticket taken before an ifx_map_upload, a sharded
+ *   handle or more than one camera context (as the snapshot entries refuse). */
+enum { IFX_DET_SWAP_RB = 1, IFX_DET_SCALE_255 = 2 };
+typedef struct ifx_detector_prep { int32_t min_size, max_size, size_divisible, flags; float mean[3], std[3]; } ifx_detector_prep;
+int ifx_detector_input_size(int width, int height, const ifx_detector_prep* p, int32_t* out4);
+int ifx_detector_resize_taps(int in_size, int out_size, int32_t* first, int32_t* count, int32_t* coeff, int max_ksize);
+int ifx_detector_input(ifx_t* h, int ticket, const ifx_detector_prep* p, float* d_out, int64_t out_floats, void* stream);
+int ifx_detector_input_image(ifx_t* h, const uint8_t* d_rgb, int width, int height, const ifx_detector_prep* p, float* d_out, int64_t out_floats, void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

@@ -47,6 +47,11 @@ class Pyramids(C.Structure):
     _fields_ = [(n, C.c_void_p * 3) for n in ("depth", "vmap_curr", "nmap_curr", "next_img", "didx", "didy", "vmap_g_prev", "nmap_g_prev", "last_depth", "last_img", "cloud")]
 
 
+class DetectorPrep(C.Structure):
+    """ifx_detector_prep: the parameters of the detector-input stage (include/ifx_c_api.h)"""
+    _fields_ = [("min_size", C.c_int32), ("max_size", C.c_int32), ("size_divisible", C.c_int32), ("flags", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
 class SoaView(C.Structure):
     _fields_ = [("count", C.c_int32), ("capacity", C.c_int32), ("d_pos_conf", C.c_void_p), ("d_norm_rad", C.c_void_p),
                 ("d_color", C.c_void_p), ("d_times", C.c_void_p), ("d_img_corr", C.c_void_p), ("d_votes", C.c_void_p)]
@@ -163,6 +168,10 @@ _SIGS = {
     "ifx_process_segmentation_deferred_rois": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_ingest_masks": (C.c_int, [_P, _P, C.c_int, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]),
     "ifx_paste_roi_masks": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "ifx_detector_input_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(DetectorPrep), _P]),
+    "ifx_detector_resize_taps": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int]),
+    "ifx_detector_input": (C.c_int, [_P, C.c_int, C.POINTER(DetectorPrep), _P, C.c_int64, _P]),
+    "ifx_detector_input_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(DetectorPrep), _P, C.c_int64, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
@@ -233,9 +242,99 @@ CORRES_DTYPE = np.dtype([("zx", np.int16), ("zy", np.int16), ("diff", np.float32
 MASK_U8 = 0     # inside iff the byte is non-zero (torch bool / uint8, the host entry's 0/255)
 MASK_F32 = 1    # inside iff the value is > threshold (mask probabilities; NaN is outside)
 
+# flags of ifx_detector_prep (include/ifx_c_api.h)
+DET_SWAP_RB = 1      # output channel c reads source channel 2 - c
+DET_SCALE_255 = 2    # ToTensor's [0, 1] back to [0, 255] before the normalisation
+
 # option "id_rule" (include/ifx_c_api.h): which rule draws the surfel-id images
 ID_RULE_RAY_DISC = 0     # default: a ray through each pixel centre against the disc, f32 depth keys
 ID_RULE_REFERENCE = 1    # the reference's surfel_ids.geom / .frag: screen-space quads, 24-bit depth
+
+
+def detector_prep(min_size=800, max_size=None, size_divisible=0, mean=(102.9801, 115.9465, 122.7717), std=(1., 1., 1.), to_bgr255=True, swap_rb=False):
+    """The ifx_detector_prep of the detector-input calls.  The defaults are maskrcnn-benchmark's (INPUT.MIN_SIZE_TEST, PIXEL_MEAN, PIXEL_STD, TO_BGR255,
+    maskrcnn_benchmark/config/defaults.py:47-55; DATALOADER.SIZE_DIVISIBILITY is 0 there and 32 in the FPN configurations).  to_bgr255: multiply ToTensor's [0, 1]
+    by 255 (IFX_DET_SCALE_255); swap_rb: output channel c reads source channel 2 - c (IFX_DET_SWAP_RB).  demo/predictor.py:142-145 on the RGB frame the map holds is
+    to_bgr255=True, swap_rb=True (BGR x 255, what the released weights expect) or to_bgr255=False, swap_rb=False; max_size None or <= 0: no upper bound."""
+    mean = [float(v) for v in mean]
+    std = [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std have three entries each")
+    p = DetectorPrep()
+    p.min_size, p.max_size, p.size_divisible = int(min_size), int(max_size) if max_size else 0, int(size_divisible)
+    p.flags = (DET_SCALE_255 if to_bgr255 else 0) | (DET_SWAP_RB if swap_rb else 0)
+    p.mean[:] = mean
+    p.std[:] = std
+    return p
+
+
+def detector_input_size(width, height, min_size=800, max_size=None, size_divisible=0):
+    """ifx_detector_input_size (host only, no GPU): (ow, oh, W', H') of a width x height frame -- the resized size by maskrcnn-benchmark's Resize.get_size and the
+    size padded to a multiple of size_divisible."""
+    out = np.zeros(4, np.int32)
+    p = detector_prep(min_size, max_size, size_divisible)
+    if lib().ifx_detector_input_size(int(width), int(height), C.byref(p), _ptr(out)) < 0:
+        raise IfxError(f"ifx_detector_input_size: refused ({width} x {height}, min_size {min_size}, max_size {max_size}, size_divisible {size_divisible})")
+    return tuple(int(v) for v in out)
+
+
+def detector_resize_taps(in_size, out_size, max_ksize=None):
+    """ifx_detector_resize_taps (host only): Pillow's 8-bit bilinear taps of one axis: (first [out], count [out], coeff [out, ksize] int32)"""
+    ks = 2 * int(np.ceil(max(in_size / out_size, 1.0))) + 1 if max_ksize is None else int(max_ksize)
+    first, count, coeff = np.zeros(out_size, np.int32), np.zeros(out_size, np.int32), np.zeros((out_size, ks), np.int32)
+    r = lib().ifx_detector_resize_taps(int(in_size), int(out_size), _ptr(first), _ptr(count), _ptr(coeff), ks)
+    if r < 0:
+        raise IfxError(f"ifx_detector_resize_taps: refused ({in_size} -> {out_size}, max_ksize {ks})")
+    return first, count, coeff.reshape(-1)[:out_size * r].reshape(out_size, r)
+
+
+def _detector_out(ef, size, out, stream):
+    """the output tensor of the detector-input calls ([1,3,H',W'] float32 on the handle's device, made on the consumer's stream) and that stream"""
+    import torch
+
+    dev = torch.device("cuda", int(ef.cfgd["device"]))
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    shape = (1, 3, size[3], size[2])
+    if out is None:
+        with torch.cuda.stream(stream):
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch tensor on the handle's device")
+        if out.dtype != torch.float32:
+            raise TypeError(f"out: dtype {out.dtype} is not supported (float32)")
+        if out.device != dev:
+            raise ValueError(f"out is on {out.device}, the handle on {dev}")
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out: shape {tuple(out.shape)}, expected a contiguous {list(shape)}")
+    return out, stream
+
+
+def detector_input_image(ef, rgb, min_size=800, max_size=None, size_divisible=0, mean=(102.9801, 115.9465, 122.7717), std=(1., 1., 1.), to_bgr255=True, swap_rb=False,
+                         out=None, stream=None):
+    """ifx_detector_input_image: InstanceFusion.detector_input's kernel on any uint8 [H,W,3] torch tensor on the handle's device (the stage call).  `rgb` must be
+    complete on `stream` (default: the current stream), the consumer's.  Returns (tensor [1,3,H',W'] float32, (oh, ow))."""
+    import torch
+
+    dev = torch.device("cuda", int(ef.cfgd["device"]))
+    if not isinstance(rgb, torch.Tensor):
+        raise TypeError("rgb must be a torch tensor on the handle's device")
+    if rgb.dtype != torch.uint8:
+        raise TypeError(f"rgb: dtype {rgb.dtype} is not supported (uint8)")
+    if rgb.device != dev:
+        raise ValueError(f"rgb is on {rgb.device}, the handle on {dev}")
+    if rgb.dim() != 3 or rgb.shape[2] != 3 or not rgb.is_contiguous():
+        raise ValueError(f"rgb: shape {tuple(rgb.shape)}, expected a contiguous [H,W,3]")
+    hh, w = int(rgb.shape[0]), int(rgb.shape[1])
+    p = detector_prep(min_size, max_size, size_divisible, mean, std, to_bgr255, swap_rb)
+    size = np.zeros(4, np.int32)
+    if ef.L.ifx_detector_input_size(w, hh, C.byref(p), _ptr(size)) < 0:
+        raise IfxError(f"ifx_detector_input_size: refused ({w} x {hh}, min_size {min_size}, max_size {max_size}, size_divisible {size_divisible}, std {tuple(std)})")
+    out, stream = _detector_out(ef, size, out, stream)
+    ef._chk(ef.L.ifx_detector_input_image(ef.handle, C.c_void_p(rgb.data_ptr()), w, hh, C.byref(p), C.c_void_p(out.data_ptr()), int(out.numel()),
+                                          C.c_void_p(stream.cuda_stream or None)), "ifx_detector_input_image")
+    return out, (int(size[1]), int(size[0]))
 
 
 class ElasticFusion:
@@ -791,6 +890,28 @@ class InstanceFusion:
                                                 _ptr(out_cls)),
                      "ifx_paste_roi_masks")
         return ori, clean, order, out_cls
+
+    # -- the opposite direction: the detector's input tensor from the frame that is already on the device (include/ifx_c_api.h)
+    def detector_input_size(self, min_size=800, max_size=None, size_divisible=0):
+        """(ow, oh, W', H') of detector_input for this handle's frame size (ifx_detector_input_size: host only)"""
+        return detector_input_size(self.ef.w, self.ef.h, min_size, max_size, size_divisible)
+
+    def detector_input(self, ticket=None, min_size=800, max_size=None, size_divisible=0, mean=(102.9801, 115.9465, 122.7717), std=(1., 1., 1.), to_bgr255=True,
+                       swap_rb=False, out=None, stream=None):
+        """ifx_detector_input: what maskrcnn-benchmark's COCODemo.build_transform + to_image_list make of a frame on the CPU (Pillow's bilinear resize to min_size /
+        max_size, ToTensor, x255 and / or channel flip, Normalize, zero padding to a multiple of size_divisible), bit for bit, from the frame processed last
+        (ticket=None) or the frame of a snapshot(superpixels=True) ticket, which is NOT released.  Parameters: see detector_prep.
+        stream: the CONSUMER's torch stream, the one the detector runs on (default: the current stream).  The call is enqueue-only: the kernel runs on the handle's
+        main stream behind whatever `stream` holds so far (an earlier forward pass may still read `out`), and `stream` waits for it on the device; no host
+        synchronisation.  out: a [1,3,H',W'] float32 tensor to reuse.  Returns (tensor [1,3,H',W'] float32 on the handle's device, (oh, ow))."""
+        p = detector_prep(min_size, max_size, size_divisible, mean, std, to_bgr255, swap_rb)
+        size = np.zeros(4, np.int32)
+        if self.L.ifx_detector_input_size(self.ef.w, self.ef.h, C.byref(p), _ptr(size)) < 0:
+            raise IfxError(f"ifx_detector_input_size: refused (min_size {min_size}, max_size {max_size}, size_divisible {size_divisible}, std {tuple(std)})")
+        out, stream = _detector_out(self.ef, size, out, stream)
+        self.ef._chk(self.L.ifx_detector_input(self.ef.handle, -1 if ticket is None else int(ticket), C.byref(p), C.c_void_p(out.data_ptr()), int(out.numel()),
+                                               C.c_void_p(stream.cuda_stream or None)), "ifx_detector_input")
+        return out, (int(size[1]), int(size[0]))
 
     def release_snapshot(self, ticket):
         self.ef._chk(self.L.ifx_segmentation_snapshot_release(self.ef.handle, int(ticket)), "ifx_segmentation_snapshot_release")

@@ -496,6 +496,7 @@ struct ifx {
     int snap_next_ticket = 0;
     unsigned int seq_generation = 0;   // counts the events that renumber creation numbers (ifx_map_upload): a ticket taken before one is refused
     int32_t* d_snap_ids = nullptr;     // [P] a snapshot's id image in today's slots (k_seg_translate): what a deferred call reads instead of ids_after
+    void* det_prep = nullptr;          // the detector-input stage (ifx_detector.hip): its two events and the cached tap tables, allocated by the first call
     int opt_ff_rounds = 0;             // relaxation launches of the flood fill's fixed schedule (0: 24)
     int last_seg_frame = -1;
     int seg_counts_valid = 0;          // h_result->seg_counts describe the current ids_after / votes
@@ -560,6 +561,8 @@ void ifx_knn_free(ifx* h);
 void ifx_knn_free_all(ifx* h);
 int ifx_knn_vote(ifx* h, int32_t* d_nbr_out);
 int ifx_ensure_masks(ifx* h, size_t bytes);
+int ifx_frame_for_reader(ifx* h, const char* who, int ticket, const uint8_t** rgb, hipEvent_t* ev, FrameSlot** slot);   // ifx_instance.hip: the frame ifx_detector_input reads
+void ifx_detector_free(ifx* h);
 int ifx_preprocess(ifx* h);                                   // bilateral + metric
 int ifx_tracker_init_first(ifx* h);
 int ifx_tracker_run_frame(ifx* h, int commit = 1, int keep_last = 0);                            // model pyramid + GN loops (all on device); the frame side is in the slot

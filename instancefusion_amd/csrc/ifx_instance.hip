@@ -680,6 +680,7 @@ void ifx_free_instance(ifx* h)
     hipFree(h->d_inst_color); hipFree(h->d_masks); hipFree(h->d_masks_ori); hipFree(h->d_unavail); hipFree(h->d_ff_label); hipFree(h->d_pdm); hipFree(h->d_bbox); hipFree(h->d_inst_stats); hipFree(h->d_clean_list);
     hipFree(h->d_segctl); hipFree(h->d_mask_rank);
     ifx_free_snapshots(h);
+    ifx_detector_free(h);
     if (h->h_segctl) hipHostFree(h->h_segctl);
     if (h->h_masks_stage) hipHostFree(h->h_masks_stage);
 }
@@ -2032,6 +2033,26 @@ static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap
     if ((flags & 2) && !(q->flags & 2)) { h->err = std::string(who) + ": superpixels need a ticket taken with the frame (ifx_segmentation_snapshot flags bit 1)"; return IFX_E_STATE; }
     if (q->generation != h->seq_generation) { h->err = std::string(who) + ": the map was uploaded since the ticket was taken (creation numbers renumbered)"; return IFX_E_STATE; }
     *out = q;
+    return IFX_OK;
+}
+// what ifx_detector_input (ifx_detector.hip) reads: the frame a ticket kept (ticket >= 0: *ev is the event behind the snapshot, the ticket stays in use) or the
+// resident frame slot (*slot, whose next copy-in the caller holds off as the snapshot above does).  Refuses as the snapshot entries do.
+int ifx_frame_for_reader(ifx* h, const char* who, int ticket, const uint8_t** rgb, hipEvent_t* ev, FrameSlot** slot)
+{
+    int r = snap_refuse_mode(h, who);
+    if (r) return r;
+    *ev = nullptr; *slot = nullptr;
+    if (ticket >= 0) {
+        SegSnap* q = snap_find(h, ticket);
+        if (!q) { h->err = std::string(who) + ": unknown or released ticket"; return IFX_E_INVALID; }
+        if (!(q->flags & 2)) { h->err = std::string(who) + ": the ticket was taken without its frame (ifx_segmentation_snapshot flags bit 1)"; return IFX_E_STATE; }
+        if (q->generation != h->seq_generation) { h->err = std::string(who) + ": the map was uploaded since the ticket was taken"; return IFX_E_STATE; }
+        *rgb = q->rgb; *ev = q->ev;
+        return IFX_OK;
+    }
+    if (h->tick < 2) { h->err = std::string(who) + ": no frame has been processed yet"; return IFX_E_STATE; }
+    *slot = &h->slot[(size_t)h->last_frame_slot];
+    *rgb = (*slot)->rgb;
     return IFX_OK;
 }
 

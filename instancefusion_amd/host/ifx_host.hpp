@@ -1005,6 +1005,28 @@ public:
         handle_ = h;
         segmentations_++;
     }
+    // ---- the opposite direction: the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input).  What
+    // COCODemo.build_transform and to_image_list make of a frame on the CPU (deps/maskrcnn-benchmark-master/demo/predictor.py:132-160, 198-202: Pillow's bilinear
+    // Resize to min_size / max_size, ToTensor, x255 and / or channel flip, Normalize, zero padding to a multiple of size_divisible), bit for bit, as planar
+    // [1][3][H'][W'] f32 in d_out (device memory of the map's GPU, out_floats >= 3 * H' * W').  ticket < 0: the frame processed last; otherwise the frame of a
+    // SnapshotSegmentation ticket taken with the superpixel refinement on, which is not released.  stream: the CONSUMER's HIP stream (as a void*), the one the
+    // detector runs on: the kernel runs on the map's main stream behind what that stream holds so far, and that stream waits for it on the device; the host is
+    // not synchronised.  DetectorPrep(): maskrcnn-benchmark's defaults (config/defaults.py:47-55).  DetectorInputSize: out4 = ow, oh, W', H' (host only).
+    static ifx_detector_prep DetectorPrep(int min_size = 800, int max_size = 0, int size_divisible = 0, bool to_bgr255 = true, bool swap_rb = false)
+    {
+        ifx_detector_prep p = {min_size, max_size, size_divisible, (to_bgr255 ? IFX_DET_SCALE_255 : 0) | (swap_rb ? IFX_DET_SWAP_RB : 0), {102.9801f, 115.9465f, 122.7717f}, {1.f, 1.f, 1.f}};
+        return p;
+    }
+    static void DetectorInputSize(int w, int h, const ifx_detector_prep& prep, int32_t* out4)
+    {
+        if (ifx_detector_input_size(w, h, &prep, out4) < 0) throw std::runtime_error("ifx_detector_input_size: refused (min_size < 1, size_divisible < 0, unknown flags, a std of 0 or an empty output)");
+    }
+    void DetectorInput(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const ifx_detector_prep& prep, float* d_out, int64_t out_floats, void* stream)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::DetectorInput: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_detector_input(h, ticket, &prep, d_out, out_floats, stream) < 0) throw std::runtime_error(std::string("ifx_detector_input: ") + ifx_last_error(h));
+    }
     void ReleaseSnapshot(const std::unique_ptr<ElasticFusionInterface>& map, int ticket)
     {
         if (ifx_segmentation_snapshot_release(map->handle(), ticket) < 0) throw std::runtime_error(std::string("ifx_segmentation_snapshot_release: ") + ifx_last_error(map->handle()));
