@@ -584,6 +584,41 @@ int ifx_detector_input_size(int width, int height, const ifx_detector_prep* p, i
 int ifx_detector_resize_taps(int in_size, int out_size, int32_t* first, int32_t* count, int32_t* coeff, int max_ksize);
 int ifx_detector_input(ifx_t* h, int ticket, const ifx_detector_prep* p, float* d_out, int64_t out_floats, void* stream);
 int ifx_detector_input_image(ifx_t* h, const uint8_t* d_rgb, int width, int height, const ifx_detector_prep* p, float* d_out, int64_t out_floats, void* stream);
+/* ---- the detector's two operators of its own.  Between the input above and the ROI masks further up, maskrcnn-benchmark's forward pass is stock tensor algebra
+ * except for two operators of its extension module maskrcnn_benchmark._C, which exist as CUDA and CPU sources only: _C.roi_align_forward (csrc/cuda/ROIAlign_cuda.cu,
+ * the Pooler of the box and the mask head) and _C.nms (csrc/cuda/nms.cu, the RPN's proposal selection and the box head's per-class loop).  Both f32, inference only.
+ * Both calls read and write the caller's device buffers, touch no frame or map state, are enqueue-only on `stream` itself (NULL = the null stream; no host
+ * synchronisation) and are allowed on any handle, a sharded one included.  In numpy: tests/detector_ops_numpy.py, held against the reference's CPU operators.
+ * ifx_roi_align_forward: d_input [batch][channels][height][width], d_rois n x 5 (batch index, x0, y0, x1, y1), d_out [n][channels][pooled_h][pooled_w].
+ *   The rule: the loop of RoIAlignForward (ROIAlign_cuda.cu:65-122, bilinear_interpolate :16-62) in the operation order of ROIAlign_cpu.cpp, every operation
+ *   rounded to f32 and none fused:
+ *     sw = x0 * scale, sh = y0 * scale, ew = x1 * scale, eh = y1 * scale (no rounding of the ROI); rw = max(ew - sw, 1), rh = max(eh - sh, 1);
+ *     bw = rw / pooled_w, bh = rh / pooled_h; grid per axis: sampling_ratio if > 0, else ceil(rh / pooled_h), ceil(rw / pooled_w), per ROI and unbounded
+ *     (the cost of an ROI grows with its grid, as in the reference);
+ *     sample (iy, ix) of bin (ph, pw): y = (sh + ph * bh) + ((iy + 0.5) * bh) / grid_h, x = (sw + pw * bw) + ((ix + 0.5) * bw) / grid_w;
+ *     y < -1, y > height, x < -1 or x > width: the sample contributes +0 (the CUDA kernel's choice);  y <= 0 -> 0, x <= 0 -> 0;
+ *     yl = (int)y; yl >= height - 1: yh = yl = height - 1, y = yl, else yh = yl + 1 (x likewise); ly = y - yl, lx = x - xl, hy = 1 - ly, hx = 1 - lx;
+ *     val = ((hy * hx * v(yl, xl) + hy * lx * v(yl, xh)) + ly * hx * v(yh, xl)) + ly * lx * v(yh, xh), each weight one product;
+ *     acc starts at +0 and adds val with iy outer and ix inner; out = acc / f32(grid_h * grid_w).
+ *   The batch index is (int) of the float; outside 0 .. batch - 1 the ROI's outputs are 0 and the input is not read.
+ *   Refusals (nothing enqueued, the handle stays usable): IFX_E_INVALID for NULL pointers with n > 0, n < 0, batch / channels / height / width / pooled_h /
+ *   pooled_w < 1, sampling_ratio < 0, a non-finite spatial_scale (and sizes beyond the launch: n x ceil(channels / 64) or height x width above 2^31 - 1).
+ *   n == 0 succeeds and writes nothing.
+ * ifx_nms: d_boxes n x 4 (x0, y0, x1, y1), d_scores n, d_groups NULL or n int32, d_keep n int64, d_count one int32; n <= 8192.
+ *   The rule (nms.cu): boxes are visited in descending score, equal scores (-0 == +0) by ascending index, a NaN score behind every number.  A visited box that is
+ *   not suppressed is kept and suppresses every later box j of its own group (no groups: one group) with IoU > threshold -- strictly; a NaN IoU suppresses
+ *   nothing; a suppressed box suppresses nothing.  IoU, f32 and unfused, max / min as fmaxf / fminf: Sa = (x1 - x0 + 1) * (y1 - y0 + 1);
+ *   w = max(min(ax1, bx1) - max(ax0, bx0) + 1, 0), h likewise; inter = w * h; IoU = inter / (Sa + Sb - inter).
+ *   Output: the kept indices ascending in d_keep[0 .. count), -1 behind them up to n, count in d_count[0].  With groups = class, one call is the box head's
+ *   per-class loop (box_head/inference.py:119-132): the concatenation of the per-group results, sorted by index.
+ *   Order (one-block sort in LDS), pair mask (64 x 64 tiles of 64-bit words, upper triangle) and reduction all run on the device.  The scratch (order, sorted
+ *   boxes, mask words: 8 MB at the cap) lives in the handle, is allocated by the first call and grown on demand; a call on another stream than the last one
+ *   waits for the previous call's event on the device.
+ *   Refusals: IFX_E_INVALID for n < 0, n > 8192, NULL pointers (d_groups may be NULL; d_boxes / d_scores / d_keep only with n > 0), a NaN threshold.
+ *   n == 0 writes count = 0. */
+int ifx_roi_align_forward(ifx_t* h, const float* d_input, int batch, int channels, int height, int width, const float* d_rois, int n, float spatial_scale, int pooled_h,
+                          int pooled_w, int sampling_ratio, float* d_out, void* stream);
+int ifx_nms(ifx_t* h, const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

@@ -172,6 +172,8 @@ _SIGS = {
     "ifx_detector_resize_taps": (C.c_int, [C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "ifx_detector_input": (C.c_int, [_P, C.c_int, C.POINTER(DetectorPrep), _P, C.c_int64, _P]),
     "ifx_detector_input_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(DetectorPrep), _P, C.c_int64, _P]),
+    "ifx_roi_align_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ifx_nms": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
@@ -337,6 +339,48 @@ def detector_input_image(ef, rgb, min_size=800, max_size=None, size_divisible=0,
     return out, (int(size[1]), int(size[0]))
 
 
+def _ops_tensor(ef, t, name, dtype, what):
+    """the argument checks of the detector operators, as detector_input_image's: TypeError for the dtype, ValueError for device / layout"""
+    import torch
+
+    dev = torch.device("cuda", int(ef.cfgd["device"]))
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor on the handle's device")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: dtype {t.dtype} is not supported ({what})")
+    if t.device != dev:
+        raise ValueError(f"{name} is on {t.device}, the handle on {dev}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    return t
+
+
+class _DetectorOps:
+    """What detector_ops() returns: the two inference operators of maskrcnn_benchmark._C on this library's kernels, in _C's argument order."""
+    def __init__(self, ef):
+        self.ef = ef
+
+    def nms(self, dets, scores, threshold):
+        return self.ef.nms(dets, scores, threshold)
+
+    def roi_align_forward(self, input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio):
+        return self.ef.roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio)
+
+    def __getattr__(self, name):
+        if name.startswith(("roi_", "sigmoid_focal_loss_")):     # roi_align_backward, roi_pool_*, sigmoid_focal_loss_*: the rest of _C
+            def refuse(*a, **k):
+                raise NotImplementedError(f"{name}: this library provides the detector's operators for inference only (nms, roi_align_forward)")
+            return refuse
+        raise AttributeError(name)
+
+
+def detector_ops(ef):
+    """An object that stands in for maskrcnn_benchmark._C at inference time: nms(dets, scores, threshold) and roi_align_forward(input, rois, spatial_scale,
+    pooled_h, pooled_w, sampling_ratio) run ifx_nms / ifx_roi_align_forward on `ef`'s device and the current stream; every other _C name (roi_align_backward,
+    roi_pool_*, sigmoid_focal_loss_*) raises NotImplementedError."""
+    return _DetectorOps(ef)
+
+
 class ElasticFusion:
     """Mirror of ``ElasticFusion`` / ``ElasticFusionInterface`` for the hot path.  ``id_rule``: ID_RULE_REFERENCE draws the id images with the reference's
     screen-space quad rule (option "id_rule"); None leaves the library's default."""
@@ -373,6 +417,63 @@ class ElasticFusion:
 
     def set_option(self, name, value):
         self._chk(self.L.ifx_set_option(self.handle, name.encode(), int(value)), "ifx_set_option")
+
+    # -- the detector's operators (maskrcnn_benchmark._C.roi_align_forward / _C.nms): caller's tensors, caller's stream, no frame or map state
+    def roi_align_forward(self, input, rois, spatial_scale, pooled_h, pooled_w, sampling_ratio, out=None, stream=None):
+        """ifx_roi_align_forward: input [B,C,H,W] float32, rois [n,5] float32 (batch index, x0, y0, x1, y1) -> [n,C,pooled_h,pooled_w] float32, bit for bit the
+        rule of include/ifx_c_api.h.  Enqueue-only on `stream` (default: the current stream)."""
+        import torch
+
+        _ops_tensor(self, input, "input", torch.float32, "float32")
+        _ops_tensor(self, rois, "rois", torch.float32, "float32")
+        if input.dim() != 4:
+            raise ValueError(f"input: shape {tuple(input.shape)}, expected [B,C,H,W]")
+        if rois.dim() != 2 or rois.shape[1] != 5:
+            raise ValueError(f"rois: shape {tuple(rois.shape)}, expected [n,5]")
+        B, Cn, H, W = (int(v) for v in input.shape)
+        n, ph, pw = int(rois.shape[0]), int(pooled_h), int(pooled_w)
+        if stream is None:
+            stream = torch.cuda.current_stream(input.device)
+        shape = (n, Cn, max(ph, 0), max(pw, 0))
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(shape, dtype=torch.float32, device=input.device)
+        else:
+            _ops_tensor(self, out, "out", torch.float32, "float32")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(shape)}")
+        self._chk(self.L.ifx_roi_align_forward(self.handle, C.c_void_p(input.data_ptr()), B, Cn, H, W, C.c_void_p(rois.data_ptr()), n, float(spatial_scale), ph, pw,
+                                               int(sampling_ratio), C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_roi_align_forward")
+        return out
+
+    def nms(self, boxes, scores, threshold, groups=None, stream=None, padded=False):
+        """ifx_nms: boxes [n,4] float32 (x0, y0, x1, y1), scores [n] float32, groups None or [n] int32 -> the kept indices, ascending (int64 tensor); a box
+        suppresses the later boxes of its own group whose IoU is > threshold.  Order, pair mask and reduction run on the device; the 4-byte read of the count is
+        this method's only synchronisation, and padded=True returns (keep [n] with -1 behind the kept indices, count [1] int32) without it."""
+        import torch
+
+        _ops_tensor(self, boxes, "boxes", torch.float32, "float32")
+        _ops_tensor(self, scores, "scores", torch.float32, "float32")
+        if boxes.dim() != 2 or boxes.shape[1] != 4:
+            raise ValueError(f"boxes: shape {tuple(boxes.shape)}, expected [n,4]")
+        n = int(boxes.shape[0])
+        if scores.dim() != 1 or int(scores.shape[0]) != n:
+            raise ValueError(f"scores: shape {tuple(scores.shape)}, expected [{n}]")
+        if groups is not None:
+            _ops_tensor(self, groups, "groups", torch.int32, "int32")
+            if groups.dim() != 1 or int(groups.shape[0]) != n:
+                raise ValueError(f"groups: shape {tuple(groups.shape)}, expected [{n}]")
+        if stream is None:
+            stream = torch.cuda.current_stream(boxes.device)
+        with torch.cuda.stream(stream):
+            keep = torch.empty(n, dtype=torch.int64, device=boxes.device)
+            count = torch.empty(1, dtype=torch.int32, device=boxes.device)
+        self._chk(self.L.ifx_nms(self.handle, C.c_void_p(boxes.data_ptr()), C.c_void_p(scores.data_ptr()), None if groups is None else C.c_void_p(groups.data_ptr()), n,
+                                 float(threshold), C.c_void_p(keep.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_nms")
+        if padded:
+            return keep, count
+        with torch.cuda.stream(stream):
+            return keep[:int(count.item())]
 
     # -- frame entry (ElasticFusion::processFrame)
     def set_instance_gt(self, gt):

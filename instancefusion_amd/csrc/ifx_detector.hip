@@ -12,6 +12,7 @@
 #include "ifx_dev.h"
 #include "../host/ifx_detector_prep.hpp"
 #include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -229,10 +230,292 @@ int det_run(ifx* h, const uint8_t* d_rgb, int w, int hh, const ifx_detector_prep
     return IFX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The detector's two operators of its own: ifx_roi_align_forward and ifx_nms (maskrcnn_benchmark._C.roi_align_forward / _C.nms; the rules in full: include/ifx_c_api.h,
+// in numpy: tests/detector_ops_numpy.py).  They read and write the caller's buffers on the caller's stream and touch no frame or map state.
+
+constexpr int RA_CH = 64;      // the run of channels a 256-thread block walks for its ROI
+constexpr int RA_TAB = 512;    // axis samples (pooled * grid) an axis table holds in LDS; a longer axis (an adaptive grid on a huge ROI) is computed per use by the same function
+
+// One sample position of one axis: the two texels and their weights (l: of hi, h: of lo); lo < 0: outside, the sample contributes +0.
+struct RaSample { int lo, hi; float l, h; };
+
+// bilinear_interpolate of ROIAlign_cuda.cu:16-62 / pre_calc_for_bilinear_interpolate of ROIAlign_cpu.cpp, one axis.  The position and the weights of a sample
+// separate into a y part of (ph, iy) and an x part of (pw, ix): w1 = hy * hx and so on are formed from them where they are used, in the CPU file's order.
+__device__ __forceinline__ RaSample ra_axis(float start, float bin, int p, int i, int grid, int size)
+{
+    float y = (start + (float)p * bin) + (((float)i + 0.5f) * bin) / (float)grid;
+    RaSample s;
+    if (y < -1.0f || y > (float)size) { s.lo = -1; s.hi = 0; s.l = 0.f; s.h = 0.f; return s; }
+    if (y <= 0.f) y = 0.f;
+    int lo = y == y ? (int)y : 0;      // y in [0, size] here (NaN: 0, as the conversion instruction gives)
+    int hi;
+    if (lo >= size - 1) { hi = lo = size - 1; y = (float)lo; }
+    else hi = lo + 1;
+    s.lo = lo; s.hi = hi;
+    s.l = y - (float)lo;
+    s.h = 1.f - s.l;
+    return s;
+}
+
+// ceil(extent / pooled) as an int: >= 1 for every number (the extent is >= 1); NaN: 0 samples, and the division by a count of 0 makes the outputs NaN
+__device__ __forceinline__ int ra_grid(float extent, int pooled)
+{
+    const float g = ceilf(extent / (float)pooled);
+    if (!(g == g)) return 0;
+    return g >= 1073741824.f ? (1 << 30) : (int)g;
+}
+
+struct RaArgs {
+    const float* in;      // [batch][channels][height][width]
+    const float* rois;    // [n][5]
+    float* out;           // [n][channels][ph][pw]
+    int batch, channels, height, width, ph, pw, ratio, chunks;
+    float scale;
+};
+
+// A block owns one ROI and RA_CH channels.  Phase 1: the ROI's two axis tables into LDS, ph * grid_h + pw * grid_w entries (the CUDA layout recomputes all of a
+// sample's arithmetic per output and channel).  Phase 2: consecutive lanes take consecutive outputs of the block's [channel][ph][pw] run, which is contiguous in the
+// output (coalesced stores) and keeps a wave's gathers inside one or two channel planes.  A sample outside contributes +0 and is skipped: the accumulator starts at
+// +0 and can never be -0 (x + -x and +0 + -0 are +0 in round-to-nearest), so acc + (+0) == acc bit for bit.
+__global__ void __launch_bounds__(256) k_roi_align(const RaArgs a)
+{
+    __shared__ RaSample s_y[RA_TAB], s_x[RA_TAB];
+    const int t = threadIdx.x;
+    const int roi = blockIdx.x / a.chunks, c0 = (blockIdx.x - roi * a.chunks) * RA_CH;
+    const int bins = a.ph * a.pw, total = min(RA_CH, a.channels - c0) * bins;
+    const float* r = a.rois + (size_t)roi * 5;
+    float* out = a.out + ((size_t)roi * a.channels + c0) * bins;
+    const float fb = r[0];
+    if (!(fb > -1.f && fb < (float)a.batch)) {       // (int)fb outside 0 .. batch - 1: zeros, and no read of the input
+        for (int o = t; o < total; o += 256) out[o] = 0.f;
+        return;
+    }
+    const int b = (int)fb;
+    const float sw = r[1] * a.scale, sh = r[2] * a.scale, ew = r[3] * a.scale, eh = r[4] * a.scale;
+    const float dw = ew - sw, dh = eh - sh;
+    const float rw = dw < 1.f ? 1.f : dw, rh = dh < 1.f ? 1.f : dh;     // std::max(d, 1): malformed ROIs are 1 x 1
+    const float bh = rh / (float)a.ph, bw = rw / (float)a.pw;
+    const int gh = a.ratio > 0 ? a.ratio : ra_grid(rh, a.ph), gw = a.ratio > 0 ? a.ratio : ra_grid(rw, a.pw);
+    const bool tab_y = (long long)a.ph * gh <= RA_TAB, tab_x = (long long)a.pw * gw <= RA_TAB;
+    if (tab_y) for (int i = t; i < a.ph * gh; i += 256) { const int p = i / gh; s_y[i] = ra_axis(sh, bh, p, i - p * gh, gh, a.height); }
+    if (tab_x) for (int i = t; i < a.pw * gw; i += 256) { const int p = i / gw; s_x[i] = ra_axis(sw, bw, p, i - p * gw, gw, a.width); }
+    __syncthreads();
+    const float count = (float)(int)((unsigned)gh * (unsigned)gw);
+    const size_t plane = (size_t)a.height * a.width;
+    const float* base = a.in + ((size_t)b * a.channels + c0) * plane;
+    for (int o = t; o < total; o += 256) {
+        const int c = o / bins, bin = o - c * bins, py = bin / a.pw, px = bin - py * a.pw;
+        const float* img = base + (size_t)c * plane;
+        float acc = 0.f;
+        for (int iy = 0; iy < gh; iy++) {
+            const RaSample y = tab_y ? s_y[py * gh + iy] : ra_axis(sh, bh, py, iy, gh, a.height);
+            if (y.lo < 0) continue;
+            const float *r0 = img + (size_t)y.lo * a.width, *r1 = img + (size_t)y.hi * a.width;
+            for (int ix = 0; ix < gw; ix++) {
+                const RaSample x = tab_x ? s_x[px * gw + ix] : ra_axis(sw, bw, px, ix, gw, a.width);
+                if (x.lo < 0) continue;
+                const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;
+                acc += ((w1 * r0[x.lo] + w2 * r0[x.hi]) + w3 * r1[x.lo]) + w4 * r1[x.hi];
+            }
+        }
+        out[o] = acc / count;
+    }
+}
+
+constexpr int NMS_MAX = 8192;          // boxes of one call: the sort's keys (64 KB) and the kept flags live in one block's LDS
+constexpr int NMS_BLOCKS = NMS_MAX / 64;
+
+// The order as one ascending 64-bit key: score descending (-0 == +0), a NaN score behind every number, equal scores by ascending index.  No number maps to the
+// NaN's high word (all ones would need the bit pattern 0xFFFFFFFF, which is a NaN), and the padding key ~0 lies behind every box.
+__device__ __forceinline__ unsigned long long nms_key(float s, int i)
+{
+    uint32_t k = 0xFFFFFFFFu;
+    if (s == s) {
+        uint32_t u = s == 0.f ? 0u : __float_as_uint(s);
+        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);    // ascending in the float's order
+        k = ~u;
+    }
+    return ((unsigned long long)k << 32) | (uint32_t)i;
+}
+
+// One block: a bitonic sort of P = 2^k >= n keys in LDS (the key is a total order: stability is not needed), then the boxes and groups gathered into that order.
+__global__ void __launch_bounds__(1024) k_nms_sort(const float* boxes, const float* scores, const int32_t* groups, int n, int P, int32_t* order, float4* sboxes, int32_t* sgroups)
+{
+    __shared__ unsigned long long s_key[NMS_MAX];
+    const int t = threadIdx.x;
+    for (int i = t; i < P; i += 1024) s_key[i] = i < n ? nms_key(scores[i], i) : ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < (P >> 1); i += 1024) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+                const unsigned long long x = s_key[lo], y = s_key[hi];
+                if ((x > y) == ((lo & k) == 0)) { s_key[lo] = y; s_key[hi] = x; }
+            }
+            __syncthreads();
+        }
+    for (int i = t; i < n; i += 1024) {
+        const int idx = (int)(uint32_t)s_key[i];
+        order[i] = idx;
+        sboxes[i] = make_float4(boxes[4 * (size_t)idx], boxes[4 * (size_t)idx + 1], boxes[4 * (size_t)idx + 2], boxes[4 * (size_t)idx + 3]);   // (the caller's pointer need not be 16-B aligned)
+        sgroups[i] = groups ? groups[idx] : 0;
+    }
+}
+
+// The pair mask, nms.cu:26-68: one wave per 64 x 64 tile of the upper triangle, bit j of word (row, cb) = row suppresses box cb * 64 + j (IoU > threshold, strictly;
+// a NaN IoU compares false; same group; on the diagonal tile only j > row's lane).  max / min as fmaxf / fminf, every operation f32 and unfused, a true division.
+__global__ void __launch_bounds__(64) k_nms_mask(const float4* sboxes, const int32_t* sgroups, int n, int nb, float thr, unsigned long long* mask)
+{
+    const int cb = blockIdx.x, rb = blockIdx.y, t = threadIdx.x;
+    if (cb < rb) return;
+    __shared__ float4 s_box[64];
+    __shared__ int s_grp[64];
+    const int cn = min(64, n - cb * 64), rn = min(64, n - rb * 64);
+    if (t < cn) { s_box[t] = sboxes[cb * 64 + t]; s_grp[t] = sgroups[cb * 64 + t]; }
+    __syncthreads();
+    if (t >= rn) return;
+    const int row = rb * 64 + t;
+    const float4 a = sboxes[row];
+    const int ga = sgroups[row];
+    const float sa = (a.z - a.x + 1.f) * (a.w - a.y + 1.f);
+    const int first = rb == cb ? t + 1 : 0;
+    unsigned long long word = 0;
+    for (int j = 0; j < cn; j++) {
+        const float4 b = s_box[j];
+        const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z), top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
+        const float w = fmaxf(right - left + 1.f, 0.f), hh = fmaxf(bottom - top + 1.f, 0.f);
+        const float inter = w * hh;
+        const float sb = (b.z - b.x + 1.f) * (b.w - b.y + 1.f);
+        const float iou = inter / (sa + sb - inter);
+        if (iou > thr && s_grp[j] == ga && j >= first) word |= 1ull << j;
+    }
+    mask[(size_t)row * nb + cb] = word;
+}
+
+// The reduction nms.cu:99-123 does on the host, in one block, and the output.  Per 64-box block b: wave 0 takes the 64 diagonal words with one load per lane and
+// resolves them in registers (64 steps of two lane reads, no memory in between); then all 16 waves OR the kept rows' words of the columns behind b into the removal
+// words in LDS, 128 columns x 8 row groups, consecutive lanes on consecutive words of a row.  Two global round trips per 64 boxes, none per box.
+// Then the kept flags by ORIGINAL index (LDS), a block scan, and the kept indices in ascending order, -1 behind them, the count.
+__global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* mask, const int32_t* order, int n, int nb, long long* keep, int32_t* count)
+{
+    __shared__ unsigned long long s_remv[NMS_BLOCKS];
+    __shared__ unsigned long long s_keepw;
+    __shared__ uint8_t s_flag[NMS_MAX];
+    __shared__ int s_wsum[16];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t < NMS_BLOCKS) s_remv[t] = 0;
+    for (int i = t; i < n; i += 1024) s_flag[i] = 0;
+    __syncthreads();
+    for (int b = 0; b < nb; b++) {
+        if (wave == 0) {
+            const int row = b * 64 + lane;
+            const unsigned long long d = row < n ? mask[(size_t)row * nb + b] : 0ull;
+            const uint32_t dlo = (uint32_t)d, dhi = (uint32_t)(d >> 32);
+            unsigned long long removed = s_remv[b], kw = 0;
+#pragma unroll
+            for (int i = 0; i < 64; i++) {
+                const unsigned long long di = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, i) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)dlo, i);
+                const unsigned long long m = ((removed >> i) & 1ull) ? 0ull : ~0ull;    // box i is kept: a suppressed box suppresses nothing
+                kw |= (1ull << i) & m;
+                removed |= di & m;
+            }
+            const int rows = min(64, n - b * 64);
+            if (rows < 64) kw &= (1ull << rows) - 1ull;
+            if (lane == 0) s_keepw = kw;
+            if (row < n && ((kw >> lane) & 1ull)) s_flag[order[row]] = 1;
+        }
+        __syncthreads();
+        const unsigned long long kw = s_keepw;
+        const int cg = t & (NMS_BLOCKS - 1), rg = t >> 7, c = b + 1 + cg;
+        if (c < nb) {
+            unsigned long long acc = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int i = rg * 8 + k;
+                if ((kw >> i) & 1ull) acc |= mask[(size_t)(b * 64 + i) * nb + c];    // kept rows are < n, columns behind b are in the upper triangle: all written
+            }
+            if (acc) atomicOr(&s_remv[c], acc);
+        }
+        __syncthreads();
+    }
+    // eight consecutive original indices per thread
+    int mine = 0;
+    uint32_t bits = 0;
+    for (int k = 0; k < 8; k++) {
+        const int i = t * 8 + k;
+        if (i < n && s_flag[i]) { bits |= 1u << k; mine++; }
+    }
+    int incl = mine;
+    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    int pos = incl - mine, total = 0;
+    for (int w = 0; w < 16; w++) { const int v = s_wsum[w]; if (w < wave) pos += v; total += v; }
+    for (int k = 0; k < 8; k++)
+        if (bits & (1u << k)) keep[pos++] = t * 8 + k;
+    for (int i = total + t; i < n; i += 1024) keep[i] = -1;
+    if (t == 0) count[0] = total;
+}
+
+// the stream the LAUNCH macro and the kernel timing use, for the length of a call on the caller's stream
+struct StreamScope {
+    ifx* h; hipStream_t old;
+    StreamScope(ifx* hh, hipStream_t s) : h(hh), old(hh->cur) { hh->cur = s; }
+    ~StreamScope() { h->cur = old; }
+};
+
+// the scratch of ifx_nms: order, sorted groups, sorted boxes, mask words; allocated by the first call, grown on demand (hipFree waits for its readers), and
+// ordered across streams by an event
+struct DetOps {
+    void* buf = nullptr;
+    int cap = 0;
+    hipEvent_t ev = nullptr;
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+
+int nms_run(ifx* h, const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, hipStream_t stream)
+{
+    if (!h->det_ops) h->det_ops = new DetOps();
+    DetOps* ops = (DetOps*)h->det_ops;
+    if (!ops->ev) HIPCHK(h, hipEventCreateWithFlags(&ops->ev, hipEventDisableTiming));
+    if (n > ops->cap) {
+        int cap = 1024;
+        while (cap < n) cap <<= 1;
+        if (ops->buf) { hipFree(ops->buf); ops->buf = nullptr; ops->cap = 0; }
+        const size_t bytes = (size_t)cap * (4 + 4 + 16) + (size_t)cap * (cap / 64) * 8;
+        if (hipMalloc(&ops->buf, bytes) != hipSuccess) { h->err = "ifx_nms: hipMalloc of the scratch failed"; return IFX_E_HIP; }
+        ops->cap = cap;
+    }
+    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first
+    unsigned long long* mask = (unsigned long long*)(sboxes + ops->cap);
+    int32_t* order = (int32_t*)(mask + (size_t)ops->cap * (ops->cap / 64));
+    int32_t* sgroups = order + ops->cap;
+    if (ops->used && ops->last != stream) HIPCHK(h, hipStreamWaitEvent(stream, ops->ev, 0));   // the previous call may still be using the scratch on its stream
+    StreamScope scope(h, stream);
+    int P = 2;
+    while (P < n) P <<= 1;
+    const int nb = cdiv(n, 64);
+    LAUNCH(h, "nms_sort", dim3(1), dim3(1024), k_nms_sort, d_boxes, d_scores, d_groups, n, P, order, sboxes, sgroups);
+    LAUNCH(h, "nms_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_nms_mask, (const float4*)sboxes, (const int32_t*)sgroups, n, nb, threshold, mask);
+    LAUNCH(h, "nms_reduce", dim3(1), dim3(1024), k_nms_reduce, (const unsigned long long*)mask, (const int32_t*)order, n, nb, (long long*)d_keep, d_count);
+    HIPCHK(h, hipEventRecord(ops->ev, stream));
+    ops->used = true;
+    ops->last = stream;
+    return IFX_OK;
+}
+
 }   // namespace
 
 void ifx_detector_free(ifx* h)
 {
+    if (DetOps* ops = (DetOps*)h->det_ops) {
+        if (ops->buf) hipFree(ops->buf);
+        if (ops->ev) hipEventDestroy(ops->ev);
+        delete ops;
+        h->det_ops = nullptr;
+    }
     DetPrep* dp = (DetPrep*)h->det_prep;
     if (!dp) return;
     for (DetTable& t : dp->tabs) { hipFree(t.dev); hipHostFree(t.host); }
@@ -275,4 +558,37 @@ extern "C" int ifx_detector_input(ifx_t* h, int ticket, const ifx_detector_prep*
     FrameSlot* slot = nullptr;
     if ((r = ifx_frame_for_reader(h, "ifx_detector_input", ticket, &rgb, &ev, &slot))) return r;
     return det_run(h, rgb, h->w, h->h, p, sz, d_out, stream, ev, slot);
+}
+
+extern "C" int ifx_roi_align_forward(ifx_t* h, const float* d_input, int batch, int channels, int height, int width, const float* d_rois, int n, float spatial_scale,
+                                     int pooled_h, int pooled_w, int sampling_ratio, float* d_out, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || batch < 1 || channels < 1 || height < 1 || width < 1 || pooled_h < 1 || pooled_w < 1 || sampling_ratio < 0) {
+        h->err = "ifx_roi_align_forward: n < 0, a size < 1 or sampling_ratio < 0"; return IFX_E_INVALID;
+    }
+    if (!std::isfinite(spatial_scale)) { h->err = "ifx_roi_align_forward: spatial_scale is not finite"; return IFX_E_INVALID; }
+    if (n == 0) return IFX_OK;
+    if (!d_input || !d_rois || !d_out) { h->err = "ifx_roi_align_forward: NULL pointer"; return IFX_E_INVALID; }
+    const int chunks = cdiv(channels, RA_CH);
+    if ((int64_t)n * chunks > 0x7FFFFFFF || (int64_t)pooled_h * pooled_w > (1 << 24) || (int64_t)height * width > 0x7FFFFFFF) {
+        h->err = "ifx_roi_align_forward: more than 2^31 - 1 blocks (n x ceil(channels / 64)), more than 2^24 bins or more than 2^31 - 1 texels per plane"; return IFX_E_INVALID;
+    }
+    RaArgs a;
+    a.in = d_input; a.rois = d_rois; a.out = d_out;
+    a.batch = batch; a.channels = channels; a.height = height; a.width = width; a.ph = pooled_h; a.pw = pooled_w; a.ratio = sampling_ratio; a.chunks = chunks;
+    a.scale = spatial_scale;
+    StreamScope scope(h, (hipStream_t)stream);
+    LAUNCH(h, "roi_align", dim3((unsigned)(n * chunks)), dim3(256), k_roi_align, a);
+    return IFX_OK;
+}
+
+extern "C" int ifx_nms(ifx_t* h, const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || n > NMS_MAX) { h->err = "ifx_nms: n outside 0 .. 8192"; return IFX_E_INVALID; }
+    if (threshold != threshold) { h->err = "ifx_nms: the threshold is NaN"; return IFX_E_INVALID; }
+    if (!d_count || (n > 0 && (!d_boxes || !d_scores || !d_keep))) { h->err = "ifx_nms: NULL pointer"; return IFX_E_INVALID; }
+    if (n == 0) { HIPCHK(h, hipMemsetAsync(d_count, 0, 4, (hipStream_t)stream)); return IFX_OK; }
+    return nms_run(h, d_boxes, d_scores, d_groups, n, threshold, d_keep, d_count, (hipStream_t)stream);
 }

@@ -440,6 +440,24 @@ public:
         if (ifx_adopt_estimated_pose(h_) != IFX_OK) throw std::runtime_error(std::string("ifx_adopt_estimated_pose: ") + ifx_last_error(h_));
     }
 
+    // ---- the detector's two operators of its own (maskrcnn_benchmark._C.roi_align_forward / _C.nms; the rules: ifx_c_api.h).  Device pointers of this map's GPU,
+    // f32; `stream` is the caller's HIP stream (as a void*, nullptr = the null stream): the calls are enqueue-only on it, do not synchronise the host and touch
+    // no frame or map state.  RoiAlignForward: d_input [batch][channels][height][width], d_rois n x 5 (batch index, x0, y0, x1, y1) -> d_out [n][channels][ph][pw].
+    // Nms: d_boxes n x 4, d_scores n, d_groups nullptr or n int32 (a box suppresses only boxes of its own group), n <= 8192 -> the kept indices ascending in
+    // d_keep[0 .. count), -1 behind them, count in d_count[0].
+    void RoiAlignForward(const float* d_input, int batch, int channels, int height, int width, const float* d_rois, int n, float spatial_scale, int pooled_h, int pooled_w,
+                         int sampling_ratio, float* d_out, void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::RoiAlignForward: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_roi_align_forward(h_, d_input, batch, channels, height, width, d_rois, n, spatial_scale, pooled_h, pooled_w, sampling_ratio, d_out, stream) < 0)
+            throw std::runtime_error(std::string("ifx_roi_align_forward: ") + ifx_last_error(h_));
+    }
+    void Nms(const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::Nms: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_nms(h_, d_boxes, d_scores, d_groups, n, threshold, d_keep, d_count, stream) < 0) throw std::runtime_error(std::string("ifx_nms: ") + ifx_last_error(h_));
+    }
+
     int getMapSurfelCount() { return ifx_map_count(h_); }
     ifx_t* handle() { return h_; }
     const ifx_config& config() const { return cfg_; }
