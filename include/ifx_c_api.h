@@ -619,6 +619,51 @@ int ifx_detector_input_image(ifx_t* h, const uint8_t* d_rgb, int width, int heig
 int ifx_roi_align_forward(ifx_t* h, const float* d_input, int batch, int channels, int height, int width, const float* d_rois, int n, float spatial_scale, int pooled_h,
                           int pooled_w, int sampling_ratio, float* d_out, void* stream);
 int ifx_nms(ifx_t* h, const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, void* stream);
+/* ---- the RPN's proposal stage and box decoding.  Between the RPN head and the box head the reference runs RPNPostProcessor.forward_for_single_feature_map
+ * (maskrcnn_benchmark/modeling/rpn/inference.py:74-121): about forty stock launches and two host synchronisations per level and image.  ifx_rpn_proposals is that
+ * stage for ONE level of ONE image in one call: select, decode, clip, filter, suppress, truncate; the output stays on the device and no count is read back.
+ * ifx_box_decode is BoxCoder.decode (modeling/box_coder.py:52-95) alone, which the box head's PostProcessor needs a second time.  Both as the operators above:
+ * f32, the caller's buffers on the caller's stream, no frame or map state, any handle.  In numpy: tests/rpn_proposals_numpy.py, held against the reference's
+ * own Python through tests/golden/rpn_proposals_ref.npz.
+ * ifx_rpn_proposals.  Inputs as the RPN head emits them with N = 1 dropped: d_objectness [A][H][W], d_regression [4A][H][W], d_anchors [H W A][4] (x0, y0, x1, y1) in
+ *   the reference's order, anchor a of cell (y, x) at row i = (y W + x) A + a.  permute_and_flatten (rpn/utils.py) is done by indexing: the logit of i is
+ *   objectness[a][y][x], its code c is regression[4a + c][y][x].  n = A H W <= 2^24.
+ *   Order (inference.py:86-93, topk on the sigmoid): a higher LOGIT first (the sigmoid is monotone), -0 == +0, a NaN behind every number, equal logits by ascending
+ *     i -- ifx_nms's order.  The candidates are the first min(pre_nms_top_n, n) in this order.
+ *   Decode (box_coder.py:62-93, operation for operation, f32, none fused): w = x1 - x0 + 1, h likewise; cx = x0 + 0.5 w; dx = code0 / wx, dy = code1 / wy (true
+ *     divisions); dw = min(code2 / ww, xform_clip), dh likewise, a NaN stays NaN; pcx = dx w + cx; pw = EXP(dw) w; x0' = pcx - 0.5 pw;
+ *     x1' = (pcx + 0.5 pw) - 1; y likewise.
+ *   EXP is this library's own exponential, no library exp on either side: a NaN gives a NaN; x to f64, clamped into [-104, 90]; k = rint(x * 1.4426950408889634);
+ *     r = (x - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10; p = the Horner sum of r^i / i! for i = 13 .. 0 in f64 with the coefficients
+ *     1.0 / i!, each step p * r + c as a separate multiplication and addition; the result is (float) ldexp(p, k).
+ *   Clip (BoxList.clip_to_image, structures/bounding_box.py:214-219): x0', x1' into [0, image_w - 1], y0', y1' into [0, image_h - 1]; a NaN stays NaN.
+ *   Small boxes (remove_small_boxes, structures/boxlist_ops.py:34-48): a candidate stays iff x1' - x0' + 1 >= min_size and y1' - y0' + 1 >= min_size (a NaN compares
+ *     false); the survivors keep their order.
+ *   Suppression (boxlist_nms, boxlist_ops.py:9-31): exactly ifx_nms's rule, one group, on the survivors in the order they have; the first post_nms_top_n kept boxes
+ *     in that order are the result.
+ *   Output: d_boxes [post_nms_top_n][4], d_logits [post_nms_top_n] (the logits; the reference's "objectness" field is their sigmoid), d_index [post_nms_top_n] int64
+ *     (the flat anchor index i), d_count one int32; behind the count boxes and logits are 0 and indices -1.  d_logits and d_index may be NULL.
+ *   How: n <= 8192: one block sorts every key in LDS.  Above: a radix select over the key's 32 bits (three multi-block histogram passes, 11 + 11 + 10 bits) finds the
+ *     key of rank pre_nms_top_n, ties at it go to the lowest i, a counting pass and a compaction gather the winners, and the same one-block sort orders them.  That
+ *     kernel also decodes, clips, filters and compacts; ifx_nms's pair mask and reduction follow, the reduction stopping once post_nms_top_n boxes are kept.
+ *     The scratch is ifx_nms's (grown on demand, ordered across streams by its event): no host synchronisation, no allocation on a repeated call of the same size.
+ *   Refusals (nothing enqueued, the handle stays usable), IFX_E_INVALID: NULL p, d_boxes or d_count (the inputs only with n > 0), A, H or W < 0, n > 2^24,
+ *     pre_nms_top_n or post_nms_top_n outside 1 .. 8192, a NaN nms_thresh, a weight that is 0 or not finite, image_w or image_h < 1.  n == 0 sets the count to 0
+ *     and writes the padding.  xform_clip <= 0 or NaN: the reference's default (float) log(1000 / 16).
+ * ifx_box_decode: d_codes [n][4k], d_boxes [n][4] -> d_out [n][4k]: the decode above of code j of row r against box r, k = 81 in the box head with the weights
+ *   (10, 10, 5, 5); clip_w, clip_h >= 1: the clip above, 0, 0: none.  Refusals: n < 0, k < 1, n k > 2^31 - 1, NULL pointers (the buffers only with n > 0), a weight
+ *   that is 0 or not finite, one of clip_w, clip_h 0 and the other not, or one < 0.  n == 0 succeeds and writes nothing. */
+typedef struct ifx_rpn_params {
+  int32_t pre_nms_top_n, post_nms_top_n;   /* 1 .. 8192 each */
+  float   nms_thresh, min_size;
+  float   weights[4];                       /* wx, wy, ww, wh; each finite and != 0 */
+  float   xform_clip;                       /* <= 0 or NaN: (float)log(1000/16) */
+  int32_t image_w, image_h;                 /* >= 1 */
+} ifx_rpn_params;
+int ifx_rpn_proposals(ifx_t* h, const float* d_objectness, const float* d_regression, const float* d_anchors, int A, int H, int W,
+                      const ifx_rpn_params* p, float* d_boxes, float* d_logits, int64_t* d_index, int32_t* d_count, void* stream);
+int ifx_box_decode(ifx_t* h, const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip,
+                   int clip_w, int clip_h /* 0, 0: no clip */, float* d_out, void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

@@ -15,6 +15,7 @@ handle without a MI355X raises :class:`IfxError`.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -50,6 +51,12 @@ class Pyramids(C.Structure):
 class DetectorPrep(C.Structure):
     """ifx_detector_prep: the parameters of the detector-input stage (include/ifx_c_api.h)"""
     _fields_ = [("min_size", C.c_int32), ("max_size", C.c_int32), ("size_divisible", C.c_int32), ("flags", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
+class RpnParams(C.Structure):
+    """ifx_rpn_params: the parameters of the proposal stage (include/ifx_c_api.h)"""
+    _fields_ = [("pre_nms_top_n", C.c_int32), ("post_nms_top_n", C.c_int32), ("nms_thresh", C.c_float), ("min_size", C.c_float), ("weights", C.c_float * 4),
+                ("xform_clip", C.c_float), ("image_w", C.c_int32), ("image_h", C.c_int32)]
 
 
 class SoaView(C.Structure):
@@ -174,6 +181,8 @@ _SIGS = {
     "ifx_detector_input_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(DetectorPrep), _P, C.c_int64, _P]),
     "ifx_roi_align_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P]),
     "ifx_nms": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
+    "ifx_rpn_proposals": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(RpnParams), _P, _P, _P, _P, _P]),
+    "ifx_box_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float * 4), C.c_float, C.c_int, C.c_int, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
@@ -374,6 +383,51 @@ class _DetectorOps:
         raise AttributeError(name)
 
 
+@functools.lru_cache(maxsize=None)
+def _rpn_post_processor_class():
+    """the nn.Module behind rpn_post_processor, made on first use: the package imports torch lazily"""
+    import torch
+
+    class RpnPostProcessor(torch.nn.Module):
+        def __init__(self, ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, fpn_post_nms_top_n):
+            super().__init__()
+            self.ef = ef
+            self.pre_nms_top_n, self.post_nms_top_n, self.nms_thresh, self.min_size = int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh), float(min_size)
+            self.fpn_post_nms_top_n = self.post_nms_top_n if fpn_post_nms_top_n is None else int(fpn_post_nms_top_n)
+
+        def forward(self, anchors, objectness, box_regression, targets=None):
+            if self.training:
+                raise RuntimeError("rpn_post_processor: inference only (the module is in training mode)")
+            out = []
+            for img, per_level in enumerate(anchors):
+                boxes, scores = [], []
+                for lvl, a in enumerate(per_level):
+                    b, s, _ = self.ef.rpn_proposals(objectness[lvl][img], box_regression[lvl][img], a.bbox.contiguous(), a.size, self.pre_nms_top_n,
+                                                    self.post_nms_top_n, self.nms_thresh, self.min_size)
+                    boxes.append(b)
+                    scores.append(s)
+                boxes, scores = (boxes[0], scores[0]) if len(boxes) == 1 else (torch.cat(boxes), torch.cat(scores))
+                if len(per_level) > 1:
+                    _, top = torch.topk(scores, min(self.fpn_post_nms_top_n, int(scores.numel())), dim=0, sorted=True)
+                    boxes, scores = boxes[top], scores[top]
+                r = type(per_level[0])(boxes, per_level[0].size, mode="xyxy")
+                r.add_field("objectness", scores)
+                out.append(r)
+            return out
+
+    return RpnPostProcessor
+
+
+def rpn_post_processor(ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, fpn_post_nms_top_n=None):
+    """An nn.Module that stands in for maskrcnn-benchmark's RPNPostProcessor (modeling/rpn/inference.py) at inference time: forward(anchors, objectness,
+    box_regression, targets=None) with anchors a list (per image) of lists (per level) of box lists, objectness / box_regression lists (per level) of [N,A,H,W] /
+    [N,4A,H,W], makes one ElasticFusion.rpn_proposals call per level and image and returns one box list per image with the field "objectness".  The result is
+    built with the class of the anchor lists it is given -- type(anchors[0][0])(bbox, size, mode="xyxy") and add_field -- so nothing of the reference is imported.
+    Several levels: the best fpn_post_nms_top_n (default: post_nms_top_n) of an image over all its levels by torch.topk, as select_over_all_levels does when not
+    training.  Box weights are RPNPostProcessor's default (1, 1, 1, 1).  It raises in training mode."""
+    return _rpn_post_processor_class()(ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, fpn_post_nms_top_n)
+
+
 def detector_ops(ef):
     """An object that stands in for maskrcnn_benchmark._C at inference time: nms(dets, scores, threshold) and roi_align_forward(input, rois, spatial_scale,
     pooled_h, pooled_w, sampling_ratio) run ifx_nms / ifx_roi_align_forward on `ef`'s device and the current stream; every other _C name (roi_align_backward,
@@ -474,6 +528,78 @@ class ElasticFusion:
             return keep, count
         with torch.cuda.stream(stream):
             return keep[:int(count.item())]
+
+    # -- the RPN's proposal stage and box decoding (RPNPostProcessor.forward_for_single_feature_map / BoxCoder.decode): caller's tensors, caller's stream
+    def rpn_proposals(self, objectness, box_regression, anchors, image_size, pre_nms_top_n=6000, post_nms_top_n=1000, nms_thresh=0.7, min_size=0, weights=(1, 1, 1, 1),
+                      padded=False, stream=None):
+        """ifx_rpn_proposals, one level of one image: objectness [A,H,W] (or [1,A,H,W]), box_regression [4A,H,W] (or [1,4A,H,W]), anchors [H*W*A,4] in the
+        reference's order, image_size (width, height) -> (boxes [c,4], objectness [c], index [c] int64): the proposals in descending objectness, torch.sigmoid of
+        their logits, and their flat anchor indices, by the rule of include/ifx_c_api.h.  Everything runs on the device; the 4-byte read of the count is this
+        method's only synchronisation, and padded=True returns the uncut [post_nms_top_n] tensors and a fourth value count [1] int32 without it."""
+        import torch
+
+        _ops_tensor(self, objectness, "objectness", torch.float32, "float32")
+        _ops_tensor(self, box_regression, "box_regression", torch.float32, "float32")
+        _ops_tensor(self, anchors, "anchors", torch.float32, "float32")
+        if objectness.dim() == 4 and objectness.shape[0] == 1:
+            objectness = objectness[0]
+        if box_regression.dim() == 4 and box_regression.shape[0] == 1:
+            box_regression = box_regression[0]
+        if objectness.dim() != 3:
+            raise ValueError(f"objectness: shape {tuple(objectness.shape)}, expected [A,H,W] or [1,A,H,W]")
+        A, H, W = (int(v) for v in objectness.shape)
+        if tuple(box_regression.shape) != (4 * A, H, W):
+            raise ValueError(f"box_regression: shape {tuple(box_regression.shape)}, expected [{4 * A},{H},{W}]")
+        if tuple(anchors.shape) != (A * H * W, 4):
+            raise ValueError(f"anchors: shape {tuple(anchors.shape)}, expected [{A * H * W},4]")
+        p = RpnParams()
+        p.pre_nms_top_n, p.post_nms_top_n, p.nms_thresh, p.min_size = int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh), float(min_size)
+        p.weights[:] = [float(v) for v in weights]
+        p.xform_clip = 0.0
+        p.image_w, p.image_h = int(image_size[0]), int(image_size[1])
+        post = max(p.post_nms_top_n, 0)
+        if stream is None:
+            stream = torch.cuda.current_stream(objectness.device)
+        with torch.cuda.stream(stream):
+            boxes = torch.empty((post, 4), dtype=torch.float32, device=objectness.device)
+            logits = torch.empty(post, dtype=torch.float32, device=objectness.device)
+            index = torch.empty(post, dtype=torch.int64, device=objectness.device)
+            count = torch.empty(1, dtype=torch.int32, device=objectness.device)
+        self._chk(self.L.ifx_rpn_proposals(self.handle, C.c_void_p(objectness.data_ptr()), C.c_void_p(box_regression.data_ptr()), C.c_void_p(anchors.data_ptr()), A, H, W,
+                                           C.byref(p), C.c_void_p(boxes.data_ptr()), C.c_void_p(logits.data_ptr()), C.c_void_p(index.data_ptr()),
+                                           C.c_void_p(count.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_rpn_proposals")
+        with torch.cuda.stream(stream):
+            if padded:
+                return boxes, torch.sigmoid(logits), index, count
+            c = int(count.item())
+            return boxes[:c], torch.sigmoid(logits[:c]), index[:c]
+
+    def box_decode(self, codes, boxes, weights=(1, 1, 1, 1), clip_to=None, out=None, stream=None):
+        """ifx_box_decode: codes [n,4k] float32 against boxes [n,4] float32 -> [n,4k] float32, BoxCoder.decode by the rule of include/ifx_c_api.h (k = 81 and
+        weights (10, 10, 5, 5): the box head).  clip_to (width, height): BoxList.clip_to_image on top.  Enqueue-only on `stream` (default: the current stream)."""
+        import torch
+
+        _ops_tensor(self, codes, "codes", torch.float32, "float32")
+        _ops_tensor(self, boxes, "boxes", torch.float32, "float32")
+        if boxes.dim() != 2 or boxes.shape[1] != 4:
+            raise ValueError(f"boxes: shape {tuple(boxes.shape)}, expected [n,4]")
+        n = int(boxes.shape[0])
+        if codes.dim() != 2 or int(codes.shape[0]) != n or codes.shape[1] % 4 or codes.shape[1] == 0:
+            raise ValueError(f"codes: shape {tuple(codes.shape)}, expected [{n},4k]")
+        if stream is None:
+            stream = torch.cuda.current_stream(codes.device)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty_like(codes)
+        else:
+            _ops_tensor(self, out, "out", torch.float32, "float32")
+            if tuple(out.shape) != tuple(codes.shape):
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(codes.shape)}")
+        w = (C.c_float * 4)(*[float(v) for v in weights])
+        cw, ch = (0, 0) if clip_to is None else (int(clip_to[0]), int(clip_to[1]))
+        self._chk(self.L.ifx_box_decode(self.handle, C.c_void_p(codes.data_ptr()), C.c_void_p(boxes.data_ptr()), n, int(codes.shape[1]) // 4, C.byref(w), 0.0, cw, ch,
+                                        C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_box_decode")
+        return out
 
     # -- frame entry (ElasticFusion::processFrame)
     def set_instance_gt(self, gt):

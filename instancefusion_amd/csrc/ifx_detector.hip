@@ -339,12 +339,9 @@ __device__ __forceinline__ unsigned long long nms_key(float s, int i)
     return ((unsigned long long)k << 32) | (uint32_t)i;
 }
 
-// One block: a bitonic sort of P = 2^k >= n keys in LDS (the key is a total order: stability is not needed), then the boxes and groups gathered into that order.
-__global__ void __launch_bounds__(1024) k_nms_sort(const float* boxes, const float* scores, const int32_t* groups, int n, int P, int32_t* order, float4* sboxes, int32_t* sgroups)
+// The sorting network of a 1024-thread block on P = 2^k keys in LDS, ascending; the keys written before the call need no barrier of their own.
+__device__ __forceinline__ void nms_bitonic(unsigned long long* s_key, int P, int t)
 {
-    __shared__ unsigned long long s_key[NMS_MAX];
-    const int t = threadIdx.x;
-    for (int i = t; i < P; i += 1024) s_key[i] = i < n ? nms_key(scores[i], i) : ~0ull;
     __syncthreads();
     for (int k = 2; k <= P; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -355,6 +352,15 @@ __global__ void __launch_bounds__(1024) k_nms_sort(const float* boxes, const flo
             }
             __syncthreads();
         }
+}
+
+// One block: a bitonic sort of P = 2^k >= n keys in LDS (the key is a total order: stability is not needed), then the boxes and groups gathered into that order.
+__global__ void __launch_bounds__(1024) k_nms_sort(const float* boxes, const float* scores, const int32_t* groups, int n, int P, int32_t* order, float4* sboxes, int32_t* sgroups)
+{
+    __shared__ unsigned long long s_key[NMS_MAX];
+    const int t = threadIdx.x;
+    for (int i = t; i < P; i += 1024) s_key[i] = i < n ? nms_key(scores[i], i) : ~0ull;
+    nms_bitonic(s_key, P, t);
     for (int i = t; i < n; i += 1024) {
         const int idx = (int)(uint32_t)s_key[i];
         order[i] = idx;
@@ -365,19 +371,20 @@ __global__ void __launch_bounds__(1024) k_nms_sort(const float* boxes, const flo
 
 // The pair mask, nms.cu:26-68: one wave per 64 x 64 tile of the upper triangle, bit j of word (row, cb) = row suppresses box cb * 64 + j (IoU > threshold, strictly;
 // a NaN IoU compares false; same group; on the diagonal tile only j > row's lane).  max / min as fmaxf / fminf, every operation f32 and unfused, a true division.
-__global__ void __launch_bounds__(64) k_nms_mask(const float4* sboxes, const int32_t* sgroups, int n, int nb, float thr, unsigned long long* mask)
+// (sgroups NULL: one group -- the proposal stage)
+__device__ __forceinline__ void nms_mask_tile(const float4* sboxes, const int32_t* sgroups, int n, int nb, float thr, unsigned long long* mask)
 {
     const int cb = blockIdx.x, rb = blockIdx.y, t = threadIdx.x;
     if (cb < rb) return;
     __shared__ float4 s_box[64];
     __shared__ int s_grp[64];
     const int cn = min(64, n - cb * 64), rn = min(64, n - rb * 64);
-    if (t < cn) { s_box[t] = sboxes[cb * 64 + t]; s_grp[t] = sgroups[cb * 64 + t]; }
+    if (t < cn) { s_box[t] = sboxes[cb * 64 + t]; s_grp[t] = sgroups ? sgroups[cb * 64 + t] : 0; }
     __syncthreads();
     if (t >= rn) return;
     const int row = rb * 64 + t;
     const float4 a = sboxes[row];
-    const int ga = sgroups[row];
+    const int ga = sgroups ? sgroups[row] : 0;
     const float sa = (a.z - a.x + 1.f) * (a.w - a.y + 1.f);
     const int first = rb == cb ? t + 1 : 0;
     unsigned long long word = 0;
@@ -393,21 +400,26 @@ __global__ void __launch_bounds__(64) k_nms_mask(const float4* sboxes, const int
     mask[(size_t)row * nb + cb] = word;
 }
 
+__global__ void __launch_bounds__(64) k_nms_mask(const float4* sboxes, const int32_t* sgroups, int n, int nb, float thr, unsigned long long* mask)
+{
+    nms_mask_tile(sboxes, sgroups, n, nb, thr, mask);
+}
+
 // The reduction nms.cu:99-123 does on the host, in one block, and the output.  Per 64-box block b: wave 0 takes the 64 diagonal words with one load per lane and
 // resolves them in registers (64 steps of two lane reads, no memory in between); then all 16 waves OR the kept rows' words of the columns behind b into the removal
 // words in LDS, 128 columns x 8 row groups, consecutive lanes on consecutive words of a row.  Two global round trips per 64 boxes, none per box.
 // Then the kept flags by ORIGINAL index (LDS), a block scan, and the kept indices in ascending order, -1 behind them, the count.
-__global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* mask, const int32_t* order, int n, int nb, long long* keep, int32_t* count)
+// The walk over the 64-box blocks, for a 1024-thread block: on return s_flag[order ? order[row] : row] is 1 for every kept row in front of the block the walk
+// stopped at.  It stops behind the block in which the kept rows reach `limit` (the proposal stage wants the first few hundred kept of thousands).
+__device__ __forceinline__ void nms_walk(const unsigned long long* mask, const int32_t* order, int n, int nb, int limit, unsigned long long* s_remv, unsigned long long* s_keepw,
+                                         int* s_kept, uint8_t* s_flag)
 {
-    __shared__ unsigned long long s_remv[NMS_BLOCKS];
-    __shared__ unsigned long long s_keepw;
-    __shared__ uint8_t s_flag[NMS_MAX];
-    __shared__ int s_wsum[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (t < NMS_BLOCKS) s_remv[t] = 0;
+    if (t == 0) *s_kept = 0;
     for (int i = t; i < n; i += 1024) s_flag[i] = 0;
     __syncthreads();
-    for (int b = 0; b < nb; b++) {
+    for (int b = 0; b * 64 < n; b++) {
         if (wave == 0) {
             const int row = b * 64 + lane;
             const unsigned long long d = row < n ? mask[(size_t)row * nb + b] : 0ull;
@@ -422,13 +434,14 @@ __global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* m
             }
             const int rows = min(64, n - b * 64);
             if (rows < 64) kw &= (1ull << rows) - 1ull;
-            if (lane == 0) s_keepw = kw;
-            if (row < n && ((kw >> lane) & 1ull)) s_flag[order[row]] = 1;
+            if (lane == 0) { *s_keepw = kw; *s_kept += __popcll(kw); }
+            if (row < n && ((kw >> lane) & 1ull)) s_flag[order ? order[row] : row] = 1;
         }
         __syncthreads();
-        const unsigned long long kw = s_keepw;
+        const unsigned long long kw = *s_keepw;
+        if (*s_kept >= limit) break;           // (uniform: every thread reads the same word behind the barrier, and nothing writes it before the next one)
         const int cg = t & (NMS_BLOCKS - 1), rg = t >> 7, c = b + 1 + cg;
-        if (c < nb) {
+        if (c * 64 < n) {
             unsigned long long acc = 0;
 #pragma unroll
             for (int k = 0; k < 8; k++) {
@@ -439,9 +452,14 @@ __global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* m
         }
         __syncthreads();
     }
-    // eight consecutive original indices per thread
+}
+
+// Eight consecutive flags per thread of a 1024-thread block: the thread's set flags as bits, the rank of its first one among all set flags, and their number.
+__device__ __forceinline__ void nms_flag_scan(const uint8_t* s_flag, int n, int* s_wsum, uint32_t& bits, int& pos, int& total)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     int mine = 0;
-    uint32_t bits = 0;
+    bits = 0;
     for (int k = 0; k < 8; k++) {
         const int i = t * 8 + k;
         if (i < n && s_flag[i]) { bits |= 1u << k; mine++; }
@@ -450,11 +468,325 @@ __global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* m
     for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
     if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
-    int pos = incl - mine, total = 0;
+    pos = incl - mine; total = 0;
     for (int w = 0; w < 16; w++) { const int v = s_wsum[w]; if (w < wave) pos += v; total += v; }
+}
+
+__global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* mask, const int32_t* order, int n, int nb, long long* keep, int32_t* count)
+{
+    __shared__ unsigned long long s_remv[NMS_BLOCKS];
+    __shared__ unsigned long long s_keepw;
+    __shared__ uint8_t s_flag[NMS_MAX];
+    __shared__ int s_wsum[16];
+    __shared__ int s_kept;
+    const int t = threadIdx.x;
+    nms_walk(mask, order, n, nb, 0x7FFFFFFF, s_remv, &s_keepw, &s_kept, s_flag);
+    uint32_t bits;
+    int pos, total;
+    nms_flag_scan(s_flag, n, s_wsum, bits, pos, total);      // by ORIGINAL index
     for (int k = 0; k < 8; k++)
         if (bits & (1u << k)) keep[pos++] = t * 8 + k;
     for (int i = total + t; i < n; i += 1024) keep[i] = -1;
+    if (t == 0) count[0] = total;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The RPN's proposal stage of one level of one image and the box decoding it contains: ifx_rpn_proposals and ifx_box_decode (RPNPostProcessor.
+// forward_for_single_feature_map, maskrcnn_benchmark/modeling/rpn/inference.py:74-121; BoxCoder.decode, modeling/box_coder.py:52-95; the rule in full:
+// include/ifx_c_api.h, in numpy: tests/rpn_proposals_numpy.py).  Select, decode, clip, filter, suppress, truncate: everything stays on the device.
+
+// EXP of the rule: f64, exp(x) = 2^k * p(r) with Cody-Waite's two-word ln 2 and the Taylor sum to r^13 (|r| <= 0.35: the tail is below 2^-60), then ONE rounding
+// to f32.  Every step a separate multiplication and addition (the build has -ffp-contract=off).
+__device__ __forceinline__ float rpn_exp(float xf)
+{
+    if (xf != xf) return xf;
+    double x = (double)xf;
+    x = x < -104.0 ? -104.0 : (x > 90.0 ? 90.0 : x);
+    const double k = rint(x * 1.4426950408889634);
+    const double r = (x - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
+    double p = 1.0 / 6227020800.0;
+    p = p * r + 1.0 / 479001600.0;
+    p = p * r + 1.0 / 39916800.0;
+    p = p * r + 1.0 / 3628800.0;
+    p = p * r + 1.0 / 362880.0;
+    p = p * r + 1.0 / 40320.0;
+    p = p * r + 1.0 / 5040.0;
+    p = p * r + 1.0 / 720.0;
+    p = p * r + 1.0 / 120.0;
+    p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0;
+    p = p * r + 1.0 / 2.0;
+    p = p * r + 1.0;
+    p = p * r + 1.0;
+    return (float)ldexp(p, (int)k);
+}
+
+struct BoxCode { float wx, wy, ww, wh, xform_clip, xmax, ymax; int clip; };   // xmax, ymax: image_w - 1, image_h - 1 of the clip (clip != 0)
+
+// BoxCoder.decode of one box (box_coder.py:62-93, operation for operation) and BoxList.clip_to_image (bounding_box.py:214-219); a NaN stays a NaN in both
+__device__ __forceinline__ float4 box_decode_one(const float4 b, float c0, float c1, float c2, float c3, const BoxCode& q)
+{
+    const float w = b.z - b.x + 1.f, h = b.w - b.y + 1.f;
+    const float cx = b.x + 0.5f * w, cy = b.y + 0.5f * h;
+    const float dx = c0 / q.wx, dy = c1 / q.wy;
+    float dw = c2 / q.ww, dh = c3 / q.wh;
+    dw = dw > q.xform_clip ? q.xform_clip : dw;
+    dh = dh > q.xform_clip ? q.xform_clip : dh;
+    const float pcx = dx * w + cx, pcy = dy * h + cy;
+    const float pw = rpn_exp(dw) * w, ph = rpn_exp(dh) * h;
+    float4 o = make_float4(pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw - 1.f, pcy + 0.5f * ph - 1.f);
+    if (q.clip) {
+        o.x = o.x < 0.f ? 0.f : (o.x > q.xmax ? q.xmax : o.x);
+        o.y = o.y < 0.f ? 0.f : (o.y > q.ymax ? q.ymax : o.y);
+        o.z = o.z < 0.f ? 0.f : (o.z > q.xmax ? q.xmax : o.z);
+        o.w = o.w < 0.f ? 0.f : (o.w > q.ymax ? q.ymax : o.w);
+    }
+    return o;
+}
+
+// ifx_box_decode: one thread, one output box; codes and out [n][4k], boxes [n][4]
+__global__ void __launch_bounds__(256) k_box_decode(const float* codes, const float* boxes, long long total, int k, const BoxCode q, float* out)
+{
+    const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    const long long row = o / k;
+    const float4 b = make_float4(boxes[4 * row], boxes[4 * row + 1], boxes[4 * row + 2], boxes[4 * row + 3]);
+    const float* c = codes + 4 * o;
+    const float4 r = box_decode_one(b, c[0], c[1], c[2], c[3], q);
+    out[4 * o] = r.x; out[4 * o + 1] = r.y; out[4 * o + 2] = r.z; out[4 * o + 3] = r.w;
+}
+
+// ---- selection: the K <= 8192 best of n > 8192 logits.  The order is nms_key's: its high word k32 ascending, then the flat anchor index ascending.
+// A radix select finds T, the k32 of rank K, in three histogram passes over 11 + 11 + 10 bits (k_rpn_hist<0..2>: a block counts 2048 keys into LDS and adds its
+// non-empty bins to the pass's global histogram; each later launch first picks the previous pass's digit out of that histogram, every block for itself).
+// Winners: every key with k32 < T, and of those with k32 == T the first K - #less by ascending index.  k_rpn_count counts both kinds per block of 2048
+// CONSECUTIVE anchor indices, k_rpn_compact turns the counts in front of a block and a scan inside it into each winner's place: no atomics, a fixed layout.
+constexpr int RPN_CHUNK = 2048;       // keys of a 256-thread block: eight per thread
+constexpr int RPN_BINS = 2048;
+constexpr int RPN_MAX_N = 1 << 24;
+
+__device__ __forceinline__ uint32_t rpn_key32(float s) { return (uint32_t)(nms_key(s, 0) >> 32); }
+
+// the logit of flat anchor index i = (y * W + x) * A + a out of [A][H][W]: permute_and_flatten's indexing (rpn/utils.py), nothing is permuted in memory
+__device__ __forceinline__ float rpn_logit(const float* obj, int i, int A, int HW) { const int cell = i / A; return obj[(size_t)(i - cell * A) * HW + cell]; }
+
+// 256 threads: the bin that holds rank `rank` (0-based) of a 2048-bin histogram, and the rank inside that bin.  The histogram's total is > rank.
+__device__ __forceinline__ void rpn_pick(const uint32_t* hist, uint32_t rank, uint32_t* s_w, uint32_t* s_out, uint32_t& digit, uint32_t& rest)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    uint32_t c[8], mine = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { c[k] = hist[t * 8 + k]; mine += c[k]; }
+    uint32_t incl = mine;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t excl = incl - mine;
+    for (int w = 0; w < wave; w++) excl += s_w[w];
+    if (excl <= rank && rank < excl + mine) {          // one thread
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            if (rank < excl + c[k]) { s_out[0] = (uint32_t)(t * 8 + k); s_out[1] = rank - excl; break; }
+            excl += c[k];
+        }
+    }
+    __syncthreads();
+    digit = s_out[0]; rest = s_out[1];
+}
+
+// state[2p], state[2p + 1], p = 1 .. 3: the key's leading bits fixed by the first p passes and the rank among the keys that share them
+template <int PASS>
+__global__ void __launch_bounds__(256) k_rpn_hist(const float* obj, int n, uint32_t K, uint32_t* hist, uint32_t* state)
+{
+    __shared__ uint32_t s_hist[RPN_BINS];
+    __shared__ uint32_t s_w[4], s_out[2];
+    const int t = threadIdx.x;
+    for (int i = t; i < RPN_BINS; i += 256) s_hist[i] = 0;
+    uint32_t prefix = 0;
+    if (PASS > 0) {
+        const uint32_t rank = PASS == 1 ? K - 1 : state[2 * (PASS - 1) + 1], lead = PASS == 1 ? 0u : state[2 * (PASS - 1)];
+        uint32_t d, rest;
+        rpn_pick(hist + (PASS - 1) * RPN_BINS, rank, s_w, s_out, d, rest);
+        prefix = (lead << 11) | d;
+        if (blockIdx.x == 0 && t == 0) { state[2 * PASS] = prefix; state[2 * PASS + 1] = rest; }
+    } else __syncthreads();
+    const int base = blockIdx.x * RPN_CHUNK;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int m = base + k * 256 + t;              // memory order: the histogram does not care, and the loads are contiguous
+        if (m < n) {
+            const uint32_t key = rpn_key32(obj[m]);
+            if (PASS == 0) atomicAdd(&s_hist[key >> 21], 1u);
+            else if (PASS == 1) { if ((key >> 21) == prefix) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u); }
+            else if ((key >> 10) == prefix) atomicAdd(&s_hist[key & 1023u], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < RPN_BINS; i += 256) { const uint32_t v = s_hist[i]; if (v) atomicAdd(&hist[PASS * RPN_BINS + i], v); }
+}
+
+// a thread's eight consecutive anchor indices against T: bit k of less / equal
+__device__ __forceinline__ uint2 rpn_classify(const float* obj, int n, int A, int HW, int first, uint32_t T)
+{
+    uint32_t less = 0, equal = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int i = first + k;
+        if (i < n) {
+            const uint32_t key = rpn_key32(rpn_logit(obj, i, A, HW));
+            if (key < T) less |= 1u << k;
+            else if (key == T) equal |= 1u << k;
+        }
+    }
+    return make_uint2(less, equal);
+}
+
+// blk[b], blk[nblk + b]: how many keys of block b's 2048 anchor indices lie in front of T and on T
+__global__ void __launch_bounds__(256) k_rpn_count(const float* obj, int n, int A, int HW, const uint32_t* hist, uint32_t* state, uint32_t* blk, int nblk)
+{
+    __shared__ uint32_t s_w[4], s_out[2], s_sum[2];
+    const int t = threadIdx.x;
+    if (t < 2) s_sum[t] = 0;
+    uint32_t d, rest;
+    rpn_pick(hist + 2 * RPN_BINS, state[5], s_w, s_out, d, rest);
+    const uint32_t T = (state[4] << 10) | d;
+    if (blockIdx.x == 0 && t == 0) { state[6] = T; state[7] = rest; }
+    const uint2 le = rpn_classify(obj, n, A, HW, blockIdx.x * RPN_CHUNK + t * 8, T);
+    const uint32_t less = le.x, equal = le.y;
+    if (less) atomicAdd(&s_sum[0], (uint32_t)__popc(less));
+    if (equal) atomicAdd(&s_sum[1], (uint32_t)__popc(equal));
+    __syncthreads();
+    if (t < 2) blk[t * nblk + blockIdx.x] = s_sum[t];
+}
+
+// cand[0 .. K): the winners' 64-bit keys -- those in front of T in index order, then the first state[7] + 1 of those on T in index order
+__global__ void __launch_bounds__(256) k_rpn_compact(const float* obj, int n, int A, int HW, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk,
+                                                      unsigned long long* cand)
+{
+    __shared__ uint32_t s_before[2], s_w[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
+    if (t < 2) s_before[t] = 0;
+    __syncthreads();
+    uint32_t bl = 0, be = 0;
+    for (int i = t; i < b; i += 256) { bl += blk[i]; be += blk[nblk + i]; }
+    if (bl) atomicAdd(&s_before[0], bl);
+    if (be) atomicAdd(&s_before[1], be);
+    const uint32_t T = state[6], take = state[7] + 1u;
+    const uint2 le = rpn_classify(obj, n, A, HW, b * RPN_CHUNK + t * 8, T);
+    const uint32_t less = le.x, equal = le.y;
+    const uint32_t mine = (uint32_t)__popc(less) | ((uint32_t)__popc(equal) << 16);     // both counts of a block are <= 2048: one scan for the two
+    uint32_t incl = mine;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t excl = incl - mine;
+    for (int w = 0; w < wave; w++) excl += s_w[w];
+    uint32_t pl = s_before[0] + (excl & 0xFFFFu), pe = s_before[1] + (excl >> 16);
+    const uint32_t base = take <= K ? K - take : 0u;   // the keys in front of T: exactly K - take of them
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int i = b * RPN_CHUNK + t * 8 + k;
+        if (less & (1u << k)) { if (pl < base) cand[pl] = ((unsigned long long)rpn_key32(rpn_logit(obj, i, A, HW)) << 32) | (uint32_t)i; pl++; }
+        else if (equal & (1u << k)) { if (pe < take && base + pe < K) cand[base + pe] = ((unsigned long long)T << 32) | (uint32_t)i; pe++; }
+    }
+}
+
+struct RpnArgs {
+    const float *obj, *reg, *anc;                      // [A][H][W], [4A][H][W], [H W A][4]
+    const unsigned long long* cand;                    // the selection's winners, NULL: every anchor is a candidate (n <= 8192)
+    int n, A, HW, m, P;                                // m = min(pre_nms_top_n, n) candidates, P = 2^k >= the keys sorted
+    BoxCode q;
+    float min_size;
+    float4* sboxes; float* slogit; int32_t* sindex; int32_t* ns;
+};
+
+// One block: the candidates into the order (k_nms_sort's network), then per thread eight consecutive candidates: the code and the anchor gathered through the
+// [A][H][W] indexing, decode, clip, the small-box test; a block scan keeps the survivors in the candidates' order.  They are the sorted boxes the pair mask reads.
+__global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
+{
+    __shared__ unsigned long long s_key[NMS_MAX];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (a.cand) for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.m ? a.cand[i] : ~0ull;
+    else for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.n ? nms_key(rpn_logit(a.obj, i, a.A, a.HW), i) : ~0ull;
+    nms_bitonic(s_key, a.P, t);
+    int idx[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int c = t * 8 + k;
+        const uint32_t i = c < a.m ? (uint32_t)s_key[c] : 0xFFFFFFFFu;
+        idx[k] = i < (uint32_t)a.n ? (int)i : -1;      // (every key holds an anchor index; the test keeps the gathers inside the inputs whatever the keys are)
+    }
+    __syncthreads();
+    int* s_wsum = (int*)s_key;                         // (the keys are in registers: their LDS holds the scan's wave sums from here on)
+    float4 box[8];
+    uint32_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        if (idx[k] < 0) continue;
+        const int i = idx[k], cell = i / a.A, an = i - cell * a.A;
+        const float* c = a.reg + (size_t)(4 * an) * a.HW + cell;
+        const float4 b = make_float4(a.anc[4 * (size_t)i], a.anc[4 * (size_t)i + 1], a.anc[4 * (size_t)i + 2], a.anc[4 * (size_t)i + 3]);
+        box[k] = box_decode_one(b, c[0], c[a.HW], c[2 * (size_t)a.HW], c[3 * (size_t)a.HW], a.q);
+        if (box[k].z - box[k].x + 1.f >= a.min_size && box[k].w - box[k].y + 1.f >= a.min_size) bits |= 1u << k;     // remove_small_boxes (boxlist_ops.py:34-48): a NaN is false
+    }
+    const int mine = __popc(bits);
+    int incl = mine;
+    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    if (lane == 63) s_wsum[wave] = incl;
+    __syncthreads();
+    int pos = incl - mine, total = 0;
+    for (int w = 0; w < 16; w++) { const int v = s_wsum[w]; if (w < wave) pos += v; total += v; }
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (bits & (1u << k)) {
+            a.sboxes[pos] = box[k];
+            a.slogit[pos] = rpn_logit(a.obj, idx[k], a.A, a.HW);
+            a.sindex[pos] = idx[k];
+            pos++;
+        }
+    if (t == 0) a.ns[0] = total;
+}
+
+// k_nms_mask on the survivors: their number is on the device, the grid is sized for the candidates
+__global__ void __launch_bounds__(64) k_rpn_mask(const float4* sboxes, const int32_t* ns, int nb, float thr, unsigned long long* mask)
+{
+    const int n = ns[0];
+    if ((int)blockIdx.x * 64 >= n) return;             // (the column block; the row block is not behind it where the tile is computed)
+    nms_mask_tile(sboxes, nullptr, n, nb, thr, mask);
+}
+
+// k_nms_reduce's walk, stopped once `post` boxes are kept, and the output in the candidates' order: the first min(kept, post) kept rows with box, logit and index;
+// zeros and -1 behind them up to post; the count
+__global__ void __launch_bounds__(1024) k_rpn_reduce(const unsigned long long* mask, const float4* sboxes, const float* slogit, const int32_t* sindex, const int32_t* ns, int nb,
+                                                     int post, float* boxes, float* logits, long long* index, int32_t* count)
+{
+    __shared__ unsigned long long s_remv[NMS_BLOCKS];
+    __shared__ unsigned long long s_keepw;
+    __shared__ uint8_t s_flag[NMS_MAX];
+    __shared__ int s_wsum[16];
+    __shared__ int s_kept;
+    const int t = threadIdx.x, n = ns[0];
+    nms_walk(mask, nullptr, n, nb, post, s_remv, &s_keepw, &s_kept, s_flag);
+    uint32_t bits;
+    int pos, total;
+    nms_flag_scan(s_flag, n, s_wsum, bits, pos, total);      // by sorted row
+    for (int k = 0; k < 8; k++)
+        if (bits & (1u << k)) {
+            if (pos < post) {
+                const int row = t * 8 + k;
+                const float4 b = sboxes[row];
+                boxes[4 * pos] = b.x; boxes[4 * pos + 1] = b.y; boxes[4 * pos + 2] = b.z; boxes[4 * pos + 3] = b.w;
+                if (logits) logits[pos] = slogit[row];
+                if (index) index[pos] = sindex[row];
+            }
+            pos++;
+        }
+    total = min(total, post);
+    for (int i = total + t; i < post; i += 1024) {
+        boxes[4 * i] = 0.f; boxes[4 * i + 1] = 0.f; boxes[4 * i + 2] = 0.f; boxes[4 * i + 3] = 0.f;
+        if (logits) logits[i] = 0.f;
+        if (index) index[i] = -1;
+    }
     if (t == 0) count[0] = total;
 }
 
@@ -465,34 +797,43 @@ struct StreamScope {
     ~StreamScope() { h->cur = old; }
 };
 
-// the scratch of ifx_nms: order, sorted groups, sorted boxes, mask words; allocated by the first call, grown on demand (hipFree waits for its readers), and
-// ordered across streams by an event
+// the scratch of ifx_nms (order, sorted groups, sorted boxes, mask words) and of ifx_rpn_proposals: allocated by the first call, grown on demand (hipFree waits for
+// its readers), and ordered across streams by an event
 struct DetOps {
     void* buf = nullptr;
-    int cap = 0;
+    size_t bytes = 0;
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
 };
 
-int nms_run(ifx* h, const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, hipStream_t stream)
+// at least `bytes` of scratch for a call on `stream`, behind the previous call's use of it
+int ops_scratch(ifx* h, const char* who, size_t bytes, hipStream_t stream, DetOps** out)
 {
     if (!h->det_ops) h->det_ops = new DetOps();
     DetOps* ops = (DetOps*)h->det_ops;
     if (!ops->ev) HIPCHK(h, hipEventCreateWithFlags(&ops->ev, hipEventDisableTiming));
-    if (n > ops->cap) {
-        int cap = 1024;
-        while (cap < n) cap <<= 1;
-        if (ops->buf) { hipFree(ops->buf); ops->buf = nullptr; ops->cap = 0; }
-        const size_t bytes = (size_t)cap * (4 + 4 + 16) + (size_t)cap * (cap / 64) * 8;
-        if (hipMalloc(&ops->buf, bytes) != hipSuccess) { h->err = "ifx_nms: hipMalloc of the scratch failed"; return IFX_E_HIP; }
-        ops->cap = cap;
+    if (bytes > ops->bytes) {
+        if (ops->buf) { hipFree(ops->buf); ops->buf = nullptr; ops->bytes = 0; }
+        if (hipMalloc(&ops->buf, bytes) != hipSuccess) { h->err = std::string(who) + ": hipMalloc of the scratch failed"; return IFX_E_HIP; }
+        ops->bytes = bytes;
     }
-    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first
-    unsigned long long* mask = (unsigned long long*)(sboxes + ops->cap);
-    int32_t* order = (int32_t*)(mask + (size_t)ops->cap * (ops->cap / 64));
-    int32_t* sgroups = order + ops->cap;
     if (ops->used && ops->last != stream) HIPCHK(h, hipStreamWaitEvent(stream, ops->ev, 0));   // the previous call may still be using the scratch on its stream
+    *out = ops;
+    return IFX_OK;
+}
+
+int nms_run(ifx* h, const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, hipStream_t stream)
+{
+    int cap = 1024;
+    while (cap < n) cap <<= 1;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, "ifx_nms", (size_t)cap * (4 + 4 + 16) + (size_t)cap * (cap / 64) * 8, stream, &ops);
+    if (r) return r;
+    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first
+    unsigned long long* mask = (unsigned long long*)(sboxes + cap);
+    int32_t* order = (int32_t*)(mask + (size_t)cap * (cap / 64));
+    int32_t* sgroups = order + cap;
     StreamScope scope(h, stream);
     int P = 2;
     while (P < n) P <<= 1;
@@ -504,6 +845,68 @@ int nms_run(ifx* h, const float* d_boxes, const float* d_scores, const int32_t* 
     ops->used = true;
     ops->last = stream;
     return IFX_OK;
+}
+
+
+// The proposal stage's launches.  Scratch, in the handle's buffer behind nms_run's convention: sorted boxes, mask words, the winners' keys, sorted logits and
+// indices, the per-block counts, and -- zeroed by one memset per call -- the three histograms, the selection's state and the survivors' count.
+int rpn_run(ifx* h, const float* d_obj, const float* d_reg, const float* d_anc, int A, int HW, const ifx_rpn_params* p, const BoxCode& q, float* d_boxes, float* d_logits,
+            int64_t* d_index, int32_t* d_count, hipStream_t stream)
+{
+    const int n = A * HW, m = std::min(p->pre_nms_top_n, n), mc = cdiv(m, 64) * 64, nb = mc / 64, nblk = cdiv(n, RPN_CHUNK);
+    const bool select = n > NMS_MAX;
+    const size_t zero_words = 3 * RPN_BINS + 8 + 8;    // histograms, state, the survivors' count (and padding)
+    const size_t bytes = (size_t)mc * 16 + (size_t)mc * nb * 8 + (size_t)mc * 8 + (size_t)mc * 8 + (size_t)nblk * 8 + zero_words * 4;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, "ifx_rpn_proposals", bytes, stream, &ops);
+    if (r) return r;
+    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first, then 8-B, then 4-B
+    unsigned long long* mask = (unsigned long long*)(sboxes + mc);
+    unsigned long long* cand = mask + (size_t)mc * nb;
+    float* slogit = (float*)(cand + mc);
+    int32_t* sindex = (int32_t*)(slogit + mc);
+    uint32_t* blk = (uint32_t*)(sindex + mc);
+    uint32_t* hist = blk + 2 * (size_t)nblk;
+    uint32_t* state = hist + 3 * RPN_BINS;
+    int32_t* ns = (int32_t*)(state + 8);
+    StreamScope scope(h, stream);
+    const uint32_t K = (uint32_t)m;
+    if (select) {
+        HIPCHK(h, hipMemsetAsync(hist, 0, zero_words * 4, stream));
+        LAUNCH(h, "rpn_hist", dim3((unsigned)nblk), dim3(256), k_rpn_hist<0>, d_obj, n, K, hist, state);
+        LAUNCH(h, "rpn_hist", dim3((unsigned)nblk), dim3(256), k_rpn_hist<1>, d_obj, n, K, hist, state);
+        LAUNCH(h, "rpn_hist", dim3((unsigned)nblk), dim3(256), k_rpn_hist<2>, d_obj, n, K, hist, state);
+        LAUNCH(h, "rpn_count", dim3((unsigned)nblk), dim3(256), k_rpn_count, d_obj, n, A, HW, (const uint32_t*)hist, state, blk, nblk);
+        LAUNCH(h, "rpn_compact", dim3((unsigned)nblk), dim3(256), k_rpn_compact, d_obj, n, A, HW, K, (const uint32_t*)state, (const uint32_t*)blk, nblk, cand);
+    }
+    RpnArgs a;
+    a.obj = d_obj; a.reg = d_reg; a.anc = d_anc; a.cand = select ? cand : nullptr;
+    a.n = n; a.A = A; a.HW = HW; a.m = m;
+    a.P = 2;
+    while (a.P < (select ? m : n)) a.P <<= 1;
+    a.q = q; a.min_size = p->min_size;
+    a.sboxes = sboxes; a.slogit = slogit; a.sindex = sindex; a.ns = ns;
+    LAUNCH(h, "rpn_sort_decode", dim3(1), dim3(1024), k_rpn_sort_decode, a);
+    LAUNCH(h, "rpn_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_rpn_mask, (const float4*)sboxes, (const int32_t*)ns, nb, p->nms_thresh, mask);
+    LAUNCH(h, "rpn_reduce", dim3(1), dim3(1024), k_rpn_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const float*)slogit, (const int32_t*)sindex,
+           (const int32_t*)ns, nb, p->post_nms_top_n, d_boxes, d_logits, (long long*)d_index, d_count);
+    HIPCHK(h, hipEventRecord(ops->ev, stream));
+    ops->used = true;
+    ops->last = stream;
+    return IFX_OK;
+}
+
+// weights and the clip of BoxCoder into the kernels' record; NULL: fine, else what is wrong
+const char* box_code(const float weights[4], float xform_clip, int clip_w, int clip_h, BoxCode* q)
+{
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(weights[i]) || weights[i] == 0.f) return "a weight is 0 or not finite";
+    if ((clip_w == 0) != (clip_h == 0) || clip_w < 0 || clip_h < 0) return "clip_w, clip_h: both 0 (no clip) or both >= 1";
+    q->wx = weights[0]; q->wy = weights[1]; q->ww = weights[2]; q->wh = weights[3];
+    q->xform_clip = xform_clip > 0.f ? xform_clip : (float)std::log(1000.0 / 16.0);      // (a NaN compares false: the default)
+    q->clip = clip_w > 0;
+    q->xmax = (float)(clip_w - 1); q->ymax = (float)(clip_h - 1);
+    return nullptr;
 }
 
 }   // namespace
@@ -591,4 +994,46 @@ extern "C" int ifx_nms(ifx_t* h, const float* d_boxes, const float* d_scores, co
     if (!d_count || (n > 0 && (!d_boxes || !d_scores || !d_keep))) { h->err = "ifx_nms: NULL pointer"; return IFX_E_INVALID; }
     if (n == 0) { HIPCHK(h, hipMemsetAsync(d_count, 0, 4, (hipStream_t)stream)); return IFX_OK; }
     return nms_run(h, d_boxes, d_scores, d_groups, n, threshold, d_keep, d_count, (hipStream_t)stream);
+}
+
+extern "C" int ifx_rpn_proposals(ifx_t* h, const float* d_objectness, const float* d_regression, const float* d_anchors, int A, int H, int W, const ifx_rpn_params* p,
+                                 float* d_boxes, float* d_logits, int64_t* d_index, int32_t* d_count, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!p || !d_boxes || !d_count) { h->err = "ifx_rpn_proposals: NULL pointer"; return IFX_E_INVALID; }
+    if (A < 0 || H < 0 || W < 0 || (int64_t)A * H * W > RPN_MAX_N || (int64_t)H * W > RPN_MAX_N) { h->err = "ifx_rpn_proposals: a size < 0 or A x H x W above 2^24"; return IFX_E_INVALID; }
+    if (p->pre_nms_top_n < 1 || p->pre_nms_top_n > NMS_MAX || p->post_nms_top_n < 1 || p->post_nms_top_n > NMS_MAX) {
+        h->err = "ifx_rpn_proposals: pre_nms_top_n or post_nms_top_n outside 1 .. 8192"; return IFX_E_INVALID;
+    }
+    if (p->nms_thresh != p->nms_thresh) { h->err = "ifx_rpn_proposals: the threshold is NaN"; return IFX_E_INVALID; }
+    if (p->image_w < 1 || p->image_h < 1) { h->err = "ifx_rpn_proposals: image_w or image_h < 1"; return IFX_E_INVALID; }
+    BoxCode q;
+    if (const char* bad = box_code(p->weights, p->xform_clip, p->image_w, p->image_h, &q)) { h->err = std::string("ifx_rpn_proposals: ") + bad; return IFX_E_INVALID; }
+    const int n = A * H * W;
+    if (n > 0 && (!d_objectness || !d_regression || !d_anchors)) { h->err = "ifx_rpn_proposals: NULL pointer"; return IFX_E_INVALID; }
+    if (n == 0) {                                      // no anchors: the padding alone
+        hipStream_t s = (hipStream_t)stream;
+        HIPCHK(h, hipMemsetAsync(d_boxes, 0, (size_t)p->post_nms_top_n * 16, s));
+        if (d_logits) HIPCHK(h, hipMemsetAsync(d_logits, 0, (size_t)p->post_nms_top_n * 4, s));
+        if (d_index) HIPCHK(h, hipMemsetAsync(d_index, 0xFF, (size_t)p->post_nms_top_n * 8, s));
+        HIPCHK(h, hipMemsetAsync(d_count, 0, 4, s));
+        return IFX_OK;
+    }
+    return rpn_run(h, d_objectness, d_regression, d_anchors, A, H * W, p, q, d_boxes, d_logits, d_index, d_count, (hipStream_t)stream);
+}
+
+extern "C" int ifx_box_decode(ifx_t* h, const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip, int clip_w, int clip_h,
+                              float* d_out, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || k < 1 || (int64_t)n * k > 0x7FFFFFFF) { h->err = "ifx_box_decode: n < 0, k < 1 or more than 2^31 - 1 boxes"; return IFX_E_INVALID; }
+    if (!weights) { h->err = "ifx_box_decode: NULL pointer"; return IFX_E_INVALID; }
+    BoxCode q;
+    if (const char* bad = box_code(weights, xform_clip, clip_w, clip_h, &q)) { h->err = std::string("ifx_box_decode: ") + bad; return IFX_E_INVALID; }
+    if (n == 0) return IFX_OK;
+    if (!d_codes || !d_boxes || !d_out) { h->err = "ifx_box_decode: NULL pointer"; return IFX_E_INVALID; }
+    const long long total = (long long)n * k;
+    StreamScope scope(h, (hipStream_t)stream);
+    LAUNCH(h, "box_decode", dim3((unsigned)((total + 255) / 256)), dim3(256), k_box_decode, d_codes, d_boxes, total, k, q, d_out);
+    return IFX_OK;
 }

@@ -458,6 +458,24 @@ public:
         if (ifx_nms(h_, d_boxes, d_scores, d_groups, n, threshold, d_keep, d_count, stream) < 0) throw std::runtime_error(std::string("ifx_nms: ") + ifx_last_error(h_));
     }
 
+    // ---- the RPN's proposal stage of one level of one image and BoxCoder.decode (the rules: ifx_c_api.h), under the same conditions as the two operators above.
+    // RpnProposals: d_objectness [A][H][W], d_regression [4A][H][W], d_anchors [H W A][4] -> d_boxes [post_nms_top_n][4], d_logits / d_index [post_nms_top_n]
+    // (either may be nullptr), count in d_count[0]; zeros and -1 behind the count.  BoxDecode: d_codes [n][4k] against d_boxes [n][4] -> d_out [n][4k];
+    // clip_w = clip_h = 0: no clip.
+    void RpnProposals(const float* d_objectness, const float* d_regression, const float* d_anchors, int A, int H, int W, const ifx_rpn_params& p, float* d_boxes,
+                      float* d_logits, int64_t* d_index, int32_t* d_count, void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::RpnProposals: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_rpn_proposals(h_, d_objectness, d_regression, d_anchors, A, H, W, &p, d_boxes, d_logits, d_index, d_count, stream) < 0)
+            throw std::runtime_error(std::string("ifx_rpn_proposals: ") + ifx_last_error(h_));
+    }
+    void BoxDecode(const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip, int clip_w, int clip_h, float* d_out, void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::BoxDecode: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_box_decode(h_, d_codes, d_boxes, n, k, weights, xform_clip, clip_w, clip_h, d_out, stream) < 0)
+            throw std::runtime_error(std::string("ifx_box_decode: ") + ifx_last_error(h_));
+    }
+
     int getMapSurfelCount() { return ifx_map_count(h_); }
     ifx_t* handle() { return h_; }
     const ifx_config& config() const { return cfg_; }
