@@ -664,6 +664,50 @@ int ifx_rpn_proposals(ifx_t* h, const float* d_objectness, const float* d_regres
                       const ifx_rpn_params* p, float* d_boxes, float* d_logits, int64_t* d_index, int32_t* d_count, void* stream);
 int ifx_box_decode(ifx_t* h, const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip,
                    int clip_w, int clip_h /* 0, 0: no clip */, float* d_out, void* stream);
+/* ---- the box head's post-processing.  Behind the box head the reference runs PostProcessor.forward with filter_results (maskrcnn_benchmark/modeling/roi_heads/
+ * box_head/inference.py:43-146): a softmax, BoxCoder.decode over [R, 4 C], a clip, then a Python loop over the classes with a nonzero, two gathers and boxlist_nms
+ * each, and a kthvalue on the host -- about 160 host round trips per image.  ifx_box_detections is that stage for ONE image in one call: class logits, box
+ * regression and proposals in, final boxes, scores, labels and proposal rows out; enqueue only, nothing is read back.  As the operators above: f32, the caller's
+ * buffers on the caller's stream, no frame or map state, any handle (a sharded one too).  In numpy: tests/box_detections_numpy.py, held against the reference's
+ * own Python through tests/golden/box_detections_ref.npz.
+ *   Inputs: d_logits [R][C]; d_regression [R][4 Creg], Creg == C, or Creg == 1 (cls_agnostic_bbox_reg: the code of every class is columns 0 .. 3; the caller has
+ *     taken the reference's [:, -4:] slice); d_proposals [R][4] (x0, y0, x1, y1).  2 <= C <= 1024, R >= 0, R C <= 2^24.
+ *   Softmax (F.softmax(class_logits, -1)), per row: m = the row's maximum in f32.  A NaN in the row, or m not finite: every probability of the row is NaN and the
+ *     row yields no candidate (torch gives NaNs for the whole row).  Otherwise d_j = x_j - m rounded to f32; e_j = EXP(d_j), the exponential of ifx_rpn_proposals
+ *     above (e at the maximum is exactly 1); s = sum_j (double) e_j in f64 with j ascending from 0, each addition rounded once -- the order is part of the rule;
+ *     p_j = (float) ((double) e_j / s).  Against exp(d_j) / sum exp(d_i) in f64 the golden cases' probabilities are within 1.443 ulp (bound 3: one rounding each
+ *     from EXP, s and the conversion); torch's CPU softmax reaches 3.224 ulp there, and the two differ by at most 4.000 ulp.
+ *   Candidates: the pairs (r, j), j = 1 .. C - 1, with p[r][j] > score_thresh (strictly; a NaN compares false).  The box of a candidate: the decode of code j (code 0
+ *     with Creg == 1) of row r against proposal r with the given weights and xform_clip, clipped to image_w x image_h -- decode and clip as stated for
+ *     ifx_rpn_proposals.  Candidate order is class-major: j ascending, r ascending within a class (the order of the reference's concatenation).  K = their number.
+ *   Overflow: K > 8192: the call writes the padding only, d_count[0] = -1 and d_stats = {K, 0}.  The reference has no such cap; a caller meets it by raising
+ *     score_thresh (with the released 0.05 a row gives at most 19 candidates; K is typically in the hundreds).
+ *   Suppression: ifx_nms's rule with group = class on the candidates, threshold nms: visited by descending score, equal scores by ascending candidate position.
+ *     D = the number kept; the kept candidates stay in candidate order (boxlist_nms returns ascending indices per class, cat_boxlist concatenates by class).
+ *   Limit (inference.py:137-145): detections_per_img = M > 0 and D > M: t = the M-th largest kept score; every kept candidate with score >= t stays, in candidate
+ *     order.  Ties at t all stay: the result can exceed M, as in the reference.  M <= 0: no limit.
+ *   Output: d_boxes [max_out][4], d_scores [max_out] (the probabilities), d_labels [max_out] int64 (j), d_index [max_out] int64 (the proposal row r), d_count one
+ *     int32, d_stats two int32 {K, D}; d_scores, d_labels, d_index and d_stats may be NULL.  d_count[0] is the number the rule keeps -- it may exceed max_out (ties,
+ *     or M <= 0); the first min(count, max_out) detections are written, behind them boxes and scores are 0, labels and indices -1.
+ *   How: one wave per row for the softmax (every lane runs the same ascending f64 sum out of LDS) writing p, or a NaN for "no candidate", into a class-major plane;
+ *     per-block counts and a scan compact the candidates in class-major order without atomics that could show, K stays on the device; one block sorts the
+ *     candidates (ifx_nms's network) and decodes and clips each one's box; ifx_nms's pair mask with groups; one block walks the mask, finds t at the M-th kept row
+ *     of the sorted order, moves the flags to candidate order and writes the outputs.  The scratch is ifx_nms's (grown on demand, ordered across streams by its
+ *     event): no host synchronisation, no allocation on a repeated call of the same size.
+ *   Refusals (nothing enqueued, the handle stays usable), IFX_E_INVALID: NULL p, d_boxes or d_count; NULL inputs with R > 0; R < 0, C outside 2 .. 1024,
+ *     R C > 2^24, Creg not in {1, C}; max_out outside 1 .. 8192, detections_per_img > max_out; a NaN score_thresh or nms; a weight that is 0 or not finite; image_w
+ *     or image_h < 1.  R == 0 writes count 0, stats {0, 0} and the padding.  xform_clip <= 0 or NaN: the default, as above. */
+typedef struct ifx_box_det_params {
+  float   score_thresh, nms;                /* neither a NaN */
+  int32_t detections_per_img;               /* M; <= 0: no limit; <= max_out */
+  int32_t max_out;                          /* 1 .. 8192: the rows of the output buffers */
+  float   weights[4];                       /* wx, wy, ww, wh; each finite and != 0 */
+  float   xform_clip;                       /* <= 0 or NaN: (float)log(1000/16) */
+  int32_t image_w, image_h;                 /* >= 1 */
+} ifx_box_det_params;
+int ifx_box_detections(ifx_t* h, const float* d_logits, const float* d_regression, const float* d_proposals, int R, int C, int Creg,
+                       const ifx_box_det_params* p, float* d_boxes, float* d_scores, int64_t* d_labels, int64_t* d_index, int32_t* d_count,
+                       int32_t* d_stats, void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

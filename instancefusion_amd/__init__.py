@@ -59,6 +59,12 @@ class RpnParams(C.Structure):
                 ("xform_clip", C.c_float), ("image_w", C.c_int32), ("image_h", C.c_int32)]
 
 
+class BoxDetParams(C.Structure):
+    """ifx_box_det_params: the parameters of the box head's post-processing (include/ifx_c_api.h)"""
+    _fields_ = [("score_thresh", C.c_float), ("nms", C.c_float), ("detections_per_img", C.c_int32), ("max_out", C.c_int32), ("weights", C.c_float * 4),
+                ("xform_clip", C.c_float), ("image_w", C.c_int32), ("image_h", C.c_int32)]
+
+
 class SoaView(C.Structure):
     _fields_ = [("count", C.c_int32), ("capacity", C.c_int32), ("d_pos_conf", C.c_void_p), ("d_norm_rad", C.c_void_p),
                 ("d_color", C.c_void_p), ("d_times", C.c_void_p), ("d_img_corr", C.c_void_p), ("d_votes", C.c_void_p)]
@@ -183,6 +189,7 @@ _SIGS = {
     "ifx_nms": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
     "ifx_rpn_proposals": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(RpnParams), _P, _P, _P, _P, _P]),
     "ifx_box_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float * 4), C.c_float, C.c_int, C.c_int, _P, _P]),
+    "ifx_box_detections": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(BoxDetParams), _P, _P, _P, _P, _P, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
@@ -428,6 +435,48 @@ def rpn_post_processor(ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, 
     return _rpn_post_processor_class()(ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, fpn_post_nms_top_n)
 
 
+@functools.lru_cache(maxsize=None)
+def _box_post_processor_class():
+    """the nn.Module behind box_post_processor, made on first use: the package imports torch lazily"""
+    import torch
+
+    class PostProcessor(torch.nn.Module):
+        def __init__(self, ef, score_thresh, nms, detections_per_img, weights, cls_agnostic_bbox_reg):
+            super().__init__()
+            self.ef = ef
+            self.score_thresh, self.nms, self.detections_per_img = float(score_thresh), float(nms), int(detections_per_img)
+            self.weights, self.cls_agnostic_bbox_reg = tuple(float(v) for v in weights), bool(cls_agnostic_bbox_reg)
+
+        def forward(self, x, boxes):
+            if self.training:
+                raise RuntimeError("box_post_processor: inference only (the module is in training mode)")
+            class_logits, box_regression = x
+            if self.cls_agnostic_bbox_reg:
+                box_regression = box_regression[:, -4:]
+            out, first = [], 0
+            for box in boxes:
+                rows = slice(first, first + len(box))
+                first += len(box)
+                b, s, l, _ = self.ef.box_detections(class_logits[rows].contiguous(), box_regression[rows].contiguous(), box.bbox.contiguous(), box.size,
+                                                    self.score_thresh, self.nms, self.detections_per_img, self.weights)
+                r = type(box)(b, box.size, mode="xyxy")
+                r.add_field("scores", s)
+                r.add_field("labels", l)
+                out.append(r)
+            return out
+
+    return PostProcessor
+
+
+def box_post_processor(ef, score_thresh, nms, detections_per_img, weights=(10, 10, 5, 5), cls_agnostic_bbox_reg=False):
+    """An nn.Module that stands in for maskrcnn-benchmark's box-head PostProcessor (modeling/roi_heads/box_head/inference.py) at inference time:
+    forward((class_logits, box_regression), boxes) with class_logits [sum R, C], box_regression [sum R, 4C] and boxes a list of box lists, one per image, splits the
+    rows by len(box), makes one ElasticFusion.box_detections call per image and returns one box list per image in mode "xyxy" with the image's size and the fields
+    "scores" and "labels" (int64).  The result is built with the class of the box lists it is given -- type(boxes[0])(bbox, size, mode="xyxy") and add_field -- so
+    nothing of the reference is imported.  cls_agnostic_bbox_reg: the last four columns of box_regression are every class's code.  It raises in training mode."""
+    return _box_post_processor_class()(ef, score_thresh, nms, detections_per_img, weights, cls_agnostic_bbox_reg)
+
+
 def detector_ops(ef):
     """An object that stands in for maskrcnn_benchmark._C at inference time: nms(dets, scores, threshold) and roi_align_forward(input, rois, spatial_scale,
     pooled_h, pooled_w, sampling_ratio) run ifx_nms / ifx_roi_align_forward on `ef`'s device and the current stream; every other _C name (roi_align_backward,
@@ -600,6 +649,57 @@ class ElasticFusion:
         self._chk(self.L.ifx_box_decode(self.handle, C.c_void_p(codes.data_ptr()), C.c_void_p(boxes.data_ptr()), n, int(codes.shape[1]) // 4, C.byref(w), 0.0, cw, ch,
                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_box_decode")
         return out
+
+    # -- the box head's post-processing (PostProcessor.forward / filter_results): caller's tensors, caller's stream
+    def box_detections(self, class_logits, box_regression, proposals, image_size, score_thresh=0.05, nms=0.5, detections_per_img=100, weights=(10, 10, 5, 5),
+                       max_out=None, padded=False, stream=None):
+        """ifx_box_detections, one image: class_logits [R,C], box_regression [R,4C] (or [R,4]: one class-agnostic code per row), proposals [R,4], image_size
+        (width, height) -> (boxes [c,4], scores [c], labels [c] int64, index [c] int64): the detections in class-major order, their softmax probabilities, classes
+        and proposal rows, by the rule of include/ifx_c_api.h.  Everything runs on the device; the 4-byte read of the count is this method's only synchronisation,
+        and padded=True returns the uncut [max_out] tensors plus count [1] int32 and stats [2] int32 (K candidates, D kept) without it.  max_out defaults to
+        detections_per_img when that is > 0, else 8192; ties at the limit beyond max_out are counted, not written.  More than 8192 candidates: IfxError in the cut
+        form, count -1 in the padded form (raise score_thresh)."""
+        import torch
+
+        _ops_tensor(self, class_logits, "class_logits", torch.float32, "float32")
+        _ops_tensor(self, box_regression, "box_regression", torch.float32, "float32")
+        _ops_tensor(self, proposals, "proposals", torch.float32, "float32")
+        if class_logits.dim() != 2:
+            raise ValueError(f"class_logits: shape {tuple(class_logits.shape)}, expected [R,C]")
+        R, Cn = (int(v) for v in class_logits.shape)
+        if box_regression.dim() != 2 or int(box_regression.shape[0]) != R or int(box_regression.shape[1]) not in (4, 4 * Cn):
+            raise ValueError(f"box_regression: shape {tuple(box_regression.shape)}, expected [{R},{4 * Cn}] or [{R},4]")
+        if tuple(proposals.shape) != (R, 4):
+            raise ValueError(f"proposals: shape {tuple(proposals.shape)}, expected [{R},4]")
+        p = BoxDetParams()
+        p.score_thresh, p.nms, p.detections_per_img = float(score_thresh), float(nms), int(detections_per_img)
+        p.max_out = int(max_out) if max_out is not None else (p.detections_per_img if p.detections_per_img > 0 else 8192)
+        p.weights[:] = [float(v) for v in weights]
+        p.xform_clip = 0.0
+        p.image_w, p.image_h = int(image_size[0]), int(image_size[1])
+        rows = max(p.max_out, 0)
+        if stream is None:
+            stream = torch.cuda.current_stream(class_logits.device)
+        with torch.cuda.stream(stream):
+            dev = class_logits.device
+            boxes = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+            scores = torch.empty(rows, dtype=torch.float32, device=dev)
+            labels = torch.empty(rows, dtype=torch.int64, device=dev)
+            index = torch.empty(rows, dtype=torch.int64, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            stats = torch.empty(2, dtype=torch.int32, device=dev)
+        self._chk(self.L.ifx_box_detections(self.handle, C.c_void_p(class_logits.data_ptr()), C.c_void_p(box_regression.data_ptr()), C.c_void_p(proposals.data_ptr()),
+                                            R, Cn, int(box_regression.shape[1]) // 4, C.byref(p), C.c_void_p(boxes.data_ptr()), C.c_void_p(scores.data_ptr()),
+                                            C.c_void_p(labels.data_ptr()), C.c_void_p(index.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                            C.c_void_p(stream.cuda_stream or None)), "ifx_box_detections")
+        if padded:
+            return boxes, scores, labels, index, count, stats
+        with torch.cuda.stream(stream):
+            c = int(count.item())
+            if c < 0:
+                raise IfxError(f"ifx_box_detections: {int(stats[0].item())} candidates, above the cap of 8192: raise score_thresh")
+            c = min(c, rows)
+            return boxes[:c], scores[:c], labels[:c], index[:c]
 
     # -- frame entry (ElasticFusion::processFrame)
     def set_instance_gt(self, gt):

@@ -790,6 +790,208 @@ __global__ void __launch_bounds__(1024) k_rpn_reduce(const unsigned long long* m
     if (t == 0) count[0] = total;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The box head's post-processing of one image: ifx_box_detections (PostProcessor.forward / filter_results, maskrcnn_benchmark/modeling/roi_heads/box_head/
+// inference.py:43-146; the rule in full: include/ifx_c_api.h, in numpy: tests/box_detections_numpy.py).  Softmax, threshold, decode, clip, per-class suppression,
+// the limit to detections_per_img: everything stays on the device, the number of candidates K included.
+constexpr int BD_MAX_C = 1024;
+constexpr int BD_CHUNK = 2048;         // plane positions of a 256-thread block of the count and the compaction: eight consecutive ones per thread
+
+// One wave per row, four rows per block.  The lanes find the row's maximum (exact in any order) and a NaN, park e_j = EXP(x_j - m) in LDS, and then EVERY lane runs
+// the same f64 sum over j = 0 .. C - 1 out of LDS (a broadcast read per step): the order of the additions is the rule, so no tree and no cross-lane reduction.
+// Each lane forms p_j of its own j and writes it -- or a NaN where (r, j) is no candidate -- into the class-major plane [(C - 1)][R].
+__global__ void __launch_bounds__(256) k_bd_softmax(const float* logits, int R, int C, float thresh, float* plane)
+{
+    __shared__ float s_e[4][BD_MAX_C];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
+    const bool live = r < R;
+    const float* x = logits + (size_t)(live ? r : 0) * C;
+    float m = -INFINITY;
+    bool nan = false;
+    if (live)
+        for (int j = lane; j < C; j += 64) { const float v = x[j]; nan |= v != v; m = fmaxf(m, v); }
+    for (int d = 32; d > 0; d >>= 1) m = fmaxf(m, __shfl_xor(m, d));
+    const bool bad = __any(nan) || !(fabsf(m) < INFINITY);
+    if (live && !bad)
+        for (int j = lane; j < C; j += 64) s_e[wave][j] = rpn_exp(x[j] - m);
+    __syncthreads();
+    if (!live) return;
+    double s = 0.0;
+    if (!bad)
+        for (int j = 0; j < C; j++) s = s + (double)s_e[wave][j];
+    for (int j = lane; j < C; j += 64) {
+        if (j == 0) continue;
+        float p = __uint_as_float(0x7FC00000u);
+        if (!bad) { const float q = (float)((double)s_e[wave][j] / s); if (q > thresh) p = q; }
+        plane[(size_t)(j - 1) * R + r] = p;
+    }
+}
+
+// bit k: position first + k of the plane holds a candidate (a number)
+__device__ __forceinline__ uint32_t bd_classify(const float* plane, int n, int first)
+{
+    uint32_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int i = first + k;
+        if (i < n) { const float v = plane[i]; if (v == v) bits |= 1u << k; }
+    }
+    return bits;
+}
+
+// blk[b]: the candidates among block b's 2048 consecutive plane positions
+__global__ void __launch_bounds__(256) k_bd_count(const float* plane, int n, uint32_t* blk)
+{
+    __shared__ uint32_t s_sum;
+    const int t = threadIdx.x;
+    if (t == 0) s_sum = 0;
+    __syncthreads();
+    const uint32_t bits = bd_classify(plane, n, blockIdx.x * BD_CHUNK + t * 8);
+    if (bits) atomicAdd(&s_sum, (uint32_t)__popc(bits));       // (a sum of integers: the arrival order cannot show)
+    __syncthreads();
+    if (t == 0) blk[blockIdx.x] = s_sum;
+}
+
+// cand[c]: the plane position of candidate c, c < 8192 -- the counts in front of a block and a scan inside it give every candidate its place (k_rpn_compact's
+// pattern: no atomics that could show, a fixed layout); the last block leaves K in ktot[0]
+__global__ void __launch_bounds__(256) k_bd_compact(const float* plane, int n, const uint32_t* blk, uint32_t* cand, int32_t* ktot)
+{
+    __shared__ uint32_t s_before, s_w[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
+    if (t == 0) s_before = 0;
+    __syncthreads();
+    uint32_t bl = 0;
+    for (int i = t; i < b; i += 256) bl += blk[i];
+    if (bl) atomicAdd(&s_before, bl);
+    const uint32_t bits = bd_classify(plane, n, b * BD_CHUNK + t * 8);
+    const uint32_t mine = (uint32_t)__popc(bits);
+    uint32_t incl = mine;
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    uint32_t pos = s_before + incl - mine;
+    for (int w = 0; w < wave; w++) pos += s_w[w];
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (bits & (1u << k)) { if (pos < (uint32_t)NMS_MAX) cand[pos] = (uint32_t)(b * BD_CHUNK + t * 8 + k); pos++; }
+    if (b == (int)gridDim.x - 1 && t == 255) ktot[0] = (int32_t)pos;      // (the last thread of the last block: everything in front of it and its own)
+}
+
+struct BdArgs {
+    const float *plane, *reg, *prop;                   // [(C-1)][R], [R][4 Creg], [R][4]
+    const uint32_t* cand;
+    const int32_t* ktot;
+    int R, C, Creg, n;                                 // n = (C - 1) R plane positions
+    BoxCode q;
+    float4* sboxes; int32_t* sgroups; float* sscore; int32_t* spos; int32_t* srow;
+};
+
+// One block: the K <= 8192 candidates into ifx_nms's order (k_nms_sort's network on (score, candidate position)), then per sorted row the decode of the class's
+// code against the row's proposal and the clip.  Above the cap nothing is done: k_bd_reduce reports it.
+__global__ void __launch_bounds__(1024) k_bd_sort_decode(const BdArgs a)
+{
+    __shared__ unsigned long long s_key[NMS_MAX];
+    const int t = threadIdx.x, K = a.ktot[0];
+    if (K > NMS_MAX) return;
+    int P = 2;
+    while (P < K) P <<= 1;
+    for (int i = t; i < P; i += 1024) {
+        unsigned long long key = ~0ull;
+        if (i < K) { const uint32_t f = a.cand[i]; if (f < (uint32_t)a.n) key = nms_key(a.plane[f], i); }
+        s_key[i] = key;
+    }
+    nms_bitonic(s_key, P, t);
+    for (int c = t; c < K; c += 1024) {
+        const uint32_t i = (uint32_t)s_key[c];
+        const uint32_t f = i < (uint32_t)K ? a.cand[i] : 0xFFFFFFFFu;
+        if (f >= (uint32_t)a.n) {                          // (cannot happen: every key holds a candidate; the test keeps the gathers inside the inputs whatever the keys are)
+            a.sboxes[c] = make_float4(0.f, 0.f, 0.f, 0.f); a.sgroups[c] = -1 - c; a.sscore[c] = 0.f; a.spos[c] = 0; a.srow[c] = 0;
+            continue;
+        }
+        const int j = (int)(f / (uint32_t)a.R) + 1, r = (int)(f - (uint32_t)(j - 1) * (uint32_t)a.R);
+        const float* code = a.reg + (size_t)r * 4 * a.Creg + (a.Creg == 1 ? 0 : 4 * j);
+        const float4 b = make_float4(a.prop[4 * (size_t)r], a.prop[4 * (size_t)r + 1], a.prop[4 * (size_t)r + 2], a.prop[4 * (size_t)r + 3]);
+        a.sboxes[c] = box_decode_one(b, code[0], code[1], code[2], code[3], a.q);
+        a.sgroups[c] = j;
+        a.sscore[c] = a.plane[f];
+        a.spos[c] = (int32_t)i;
+        a.srow[c] = r;
+    }
+}
+
+// k_nms_mask with the class as the group; the number of candidates is on the device, the grid is sized for what the host knows of it
+__global__ void __launch_bounds__(64) k_bd_mask(const float4* sboxes, const int32_t* sgroups, const int32_t* ktot, int nb, float thr, unsigned long long* mask)
+{
+    const int n = ktot[0];
+    if (n > NMS_MAX || (int)blockIdx.x * 64 >= n) return;
+    nms_mask_tile(sboxes, sgroups, n, nb, thr, mask);
+}
+
+struct BdOut {
+    float* boxes; float* scores; long long* labels; long long* index; int32_t* count; int32_t* stats;
+    int max_out, limit;
+};
+
+// One block: the walk over all candidates, the limit, the output in candidate order.  t, the M-th largest kept score, is the score of the M-th kept row -- the rows
+// are already in descending score; every kept row with score >= t stays.  The kept flags move from the sorted rows to the candidate positions, a scan over those
+// gives each detection its place.
+__global__ void __launch_bounds__(1024) k_bd_reduce(const unsigned long long* mask, const float4* sboxes, const int32_t* sgroups, const float* sscore, const int32_t* spos,
+                                                    const int32_t* srow, const int32_t* ktot, int nb, const BdOut o)
+{
+    __shared__ unsigned long long s_remv[NMS_BLOCKS];
+    __shared__ unsigned long long s_keepw;
+    __shared__ uint8_t s_flag[NMS_MAX], s_stay[NMS_MAX];
+    __shared__ uint16_t s_rowof[NMS_MAX];
+    __shared__ int s_wsum[16];
+    __shared__ int s_kept;
+    __shared__ float s_t;
+    const int t = threadIdx.x, K = ktot[0];
+    const bool over = K > NMS_MAX;
+    const int n = over ? 0 : K;
+    nms_walk(mask, nullptr, n, nb, 0x7FFFFFFF, s_remv, &s_keepw, &s_kept, s_flag);
+    uint32_t bits;
+    int pos, total;
+    nms_flag_scan(s_flag, n, s_wsum, bits, pos, total);      // by sorted row; total = D
+    const int D = total;
+    const bool cut = o.limit > 0 && D > o.limit;
+    if (cut)
+        for (int k = 0; k < 8; k++)
+            if (bits & (1u << k)) { if (pos == o.limit - 1) s_t = sscore[t * 8 + k]; pos++; }
+    for (int i = t; i < n; i += 1024) s_stay[i] = 0;
+    __syncthreads();
+    const float thr = cut ? s_t : 0.f;
+    for (int row = t; row < n; row += 1024) {
+        const int i = spos[row];
+        if ((uint32_t)i >= (uint32_t)n) continue;          // (a candidate position: always inside)
+        s_rowof[i] = (uint16_t)row;
+        if (s_flag[row] && (!cut || sscore[row] >= thr)) s_stay[i] = 1;
+    }
+    __syncthreads();
+    nms_flag_scan(s_stay, n, s_wsum, bits, pos, total);      // by candidate position
+    for (int k = 0; k < 8; k++)
+        if (bits & (1u << k)) {
+            if (pos < o.max_out) {
+                const int row = s_rowof[t * 8 + k];
+                const float4 b = sboxes[row];
+                o.boxes[4 * pos] = b.x; o.boxes[4 * pos + 1] = b.y; o.boxes[4 * pos + 2] = b.z; o.boxes[4 * pos + 3] = b.w;
+                if (o.scores) o.scores[pos] = sscore[row];
+                if (o.labels) o.labels[pos] = sgroups[row];
+                if (o.index) o.index[pos] = srow[row];
+            }
+            pos++;
+        }
+    for (int i = min(total, o.max_out) + t; i < o.max_out; i += 1024) {
+        o.boxes[4 * i] = 0.f; o.boxes[4 * i + 1] = 0.f; o.boxes[4 * i + 2] = 0.f; o.boxes[4 * i + 3] = 0.f;
+        if (o.scores) o.scores[i] = 0.f;
+        if (o.labels) o.labels[i] = -1;
+        if (o.index) o.index[i] = -1;
+    }
+    if (t == 0) {
+        o.count[0] = over ? -1 : total;
+        if (o.stats) { o.stats[0] = K; o.stats[1] = D; }
+    }
+}
+
 // the stream the LAUNCH macro and the kernel timing use, for the length of a call on the caller's stream
 struct StreamScope {
     ifx* h; hipStream_t old;
@@ -890,6 +1092,45 @@ int rpn_run(ifx* h, const float* d_obj, const float* d_reg, const float* d_anc, 
     LAUNCH(h, "rpn_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_rpn_mask, (const float4*)sboxes, (const int32_t*)ns, nb, p->nms_thresh, mask);
     LAUNCH(h, "rpn_reduce", dim3(1), dim3(1024), k_rpn_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const float*)slogit, (const int32_t*)sindex,
            (const int32_t*)ns, nb, p->post_nms_top_n, d_boxes, d_logits, (long long*)d_index, d_count);
+    HIPCHK(h, hipEventRecord(ops->ev, stream));
+    ops->used = true;
+    ops->last = stream;
+    return IFX_OK;
+}
+
+// The box head's post-processing: six launches.  Scratch, in the handle's buffer behind nms_run's convention: sorted boxes, mask words, then the 4-byte arrays --
+// the plane of probabilities, the candidates' plane positions, the sorted groups / scores / candidate positions / rows, the per-block counts and K.  Every word a
+// kernel reads is written by a kernel in front of it in the same call: nothing is zeroed.
+int bd_run(ifx* h, const float* d_logits, const float* d_reg, const float* d_prop, int R, int C, int Creg, const ifx_box_det_params* p, const BoxCode& q, const BdOut& out,
+           hipStream_t stream)
+{
+    const int n = (C - 1) * R, mc = cdiv(std::min(n, NMS_MAX), 64) * 64, nb = mc / 64, nblk = cdiv(n, BD_CHUNK);
+    const size_t bytes = (size_t)mc * 16 + (size_t)mc * nb * 8 + ((size_t)n + 5 * (size_t)mc + (size_t)nblk + 4) * 4;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, "ifx_box_detections", bytes, stream, &ops);
+    if (r) return r;
+    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first, then 8-B, then 4-B
+    unsigned long long* mask = (unsigned long long*)(sboxes + mc);
+    float* plane = (float*)(mask + (size_t)mc * nb);
+    uint32_t* cand = (uint32_t*)(plane + n);
+    int32_t* sgroups = (int32_t*)(cand + mc);
+    float* sscore = (float*)(sgroups + mc);
+    int32_t* spos = (int32_t*)(sscore + mc);
+    int32_t* srow = spos + mc;
+    uint32_t* blk = (uint32_t*)(srow + mc);
+    int32_t* ktot = (int32_t*)(blk + nblk);
+    StreamScope scope(h, stream);
+    LAUNCH(h, "bd_softmax", dim3((unsigned)cdiv(R, 4)), dim3(256), k_bd_softmax, d_logits, R, C, p->score_thresh, plane);
+    LAUNCH(h, "bd_count", dim3((unsigned)nblk), dim3(256), k_bd_count, (const float*)plane, n, blk);
+    LAUNCH(h, "bd_compact", dim3((unsigned)nblk), dim3(256), k_bd_compact, (const float*)plane, n, (const uint32_t*)blk, cand, ktot);
+    BdArgs a;
+    a.plane = plane; a.reg = d_reg; a.prop = d_prop; a.cand = cand; a.ktot = ktot;
+    a.R = R; a.C = C; a.Creg = Creg; a.n = n; a.q = q;
+    a.sboxes = sboxes; a.sgroups = sgroups; a.sscore = sscore; a.spos = spos; a.srow = srow;
+    LAUNCH(h, "bd_sort_decode", dim3(1), dim3(1024), k_bd_sort_decode, a);
+    LAUNCH(h, "bd_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_bd_mask, (const float4*)sboxes, (const int32_t*)sgroups, (const int32_t*)ktot, nb, p->nms, mask);
+    LAUNCH(h, "bd_reduce", dim3(1), dim3(1024), k_bd_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const int32_t*)sgroups, (const float*)sscore,
+           (const int32_t*)spos, (const int32_t*)srow, (const int32_t*)ktot, nb, out);
     HIPCHK(h, hipEventRecord(ops->ev, stream));
     ops->used = true;
     ops->last = stream;
@@ -1036,4 +1277,35 @@ extern "C" int ifx_box_decode(ifx_t* h, const float* d_codes, const float* d_box
     StreamScope scope(h, (hipStream_t)stream);
     LAUNCH(h, "box_decode", dim3((unsigned)((total + 255) / 256)), dim3(256), k_box_decode, d_codes, d_boxes, total, k, q, d_out);
     return IFX_OK;
+}
+
+extern "C" int ifx_box_detections(ifx_t* h, const float* d_logits, const float* d_regression, const float* d_proposals, int R, int C, int Creg, const ifx_box_det_params* p,
+                                  float* d_boxes, float* d_scores, int64_t* d_labels, int64_t* d_index, int32_t* d_count, int32_t* d_stats, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!p || !d_boxes || !d_count) { h->err = "ifx_box_detections: NULL pointer"; return IFX_E_INVALID; }
+    if (R < 0 || C < 2 || C > BD_MAX_C || (int64_t)R * C > RPN_MAX_N) { h->err = "ifx_box_detections: R < 0, C outside 2 .. 1024 or R x C above 2^24"; return IFX_E_INVALID; }
+    if (Creg != 1 && Creg != C) { h->err = "ifx_box_detections: Creg is neither C nor 1"; return IFX_E_INVALID; }
+    if (p->max_out < 1 || p->max_out > NMS_MAX || p->detections_per_img > p->max_out) {
+        h->err = "ifx_box_detections: max_out outside 1 .. 8192 or detections_per_img above max_out"; return IFX_E_INVALID;
+    }
+    if (p->score_thresh != p->score_thresh || p->nms != p->nms) { h->err = "ifx_box_detections: score_thresh or nms is NaN"; return IFX_E_INVALID; }
+    if (p->image_w < 1 || p->image_h < 1) { h->err = "ifx_box_detections: image_w or image_h < 1"; return IFX_E_INVALID; }
+    BoxCode q;
+    if (const char* bad = box_code(p->weights, p->xform_clip, p->image_w, p->image_h, &q)) { h->err = std::string("ifx_box_detections: ") + bad; return IFX_E_INVALID; }
+    if (R > 0 && (!d_logits || !d_regression || !d_proposals)) { h->err = "ifx_box_detections: NULL pointer"; return IFX_E_INVALID; }
+    if (R == 0) {                                      // no rows: the padding alone
+        hipStream_t s = (hipStream_t)stream;
+        HIPCHK(h, hipMemsetAsync(d_boxes, 0, (size_t)p->max_out * 16, s));
+        if (d_scores) HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)p->max_out * 4, s));
+        if (d_labels) HIPCHK(h, hipMemsetAsync(d_labels, 0xFF, (size_t)p->max_out * 8, s));
+        if (d_index) HIPCHK(h, hipMemsetAsync(d_index, 0xFF, (size_t)p->max_out * 8, s));
+        HIPCHK(h, hipMemsetAsync(d_count, 0, 4, s));
+        if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, 8, s));
+        return IFX_OK;
+    }
+    BdOut o;
+    o.boxes = d_boxes; o.scores = d_scores; o.labels = (long long*)d_labels; o.index = (long long*)d_index; o.count = d_count; o.stats = d_stats;
+    o.max_out = p->max_out; o.limit = p->detections_per_img;
+    return bd_run(h, d_logits, d_regression, d_proposals, R, C, Creg, p, q, o, (hipStream_t)stream);
 }

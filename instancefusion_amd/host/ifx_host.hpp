@@ -475,6 +475,16 @@ public:
         if (ifx_box_decode(h_, d_codes, d_boxes, n, k, weights, xform_clip, clip_w, clip_h, d_out, stream) < 0)
             throw std::runtime_error(std::string("ifx_box_decode: ") + ifx_last_error(h_));
     }
+    // BoxDetections: the box head's post-processing of one image (the rule: ifx_c_api.h).  d_logits [R][C], d_regression [R][4 Creg] (Creg == C or 1), d_proposals
+    // [R][4] -> d_boxes [max_out][4], d_scores / d_labels / d_index [max_out] and d_stats {K, D} (each may be nullptr), the count in d_count[0] (-1: more than 8192
+    // candidates); zeros and -1 behind the count.  Enqueue only.
+    void BoxDetections(const float* d_logits, const float* d_regression, const float* d_proposals, int R, int C, int Creg, const ifx_box_det_params& p, float* d_boxes,
+                       float* d_scores, int64_t* d_labels, int64_t* d_index, int32_t* d_count, int32_t* d_stats, void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::BoxDetections: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_box_detections(h_, d_logits, d_regression, d_proposals, R, C, Creg, &p, d_boxes, d_scores, d_labels, d_index, d_count, d_stats, stream) < 0)
+            throw std::runtime_error(std::string("ifx_box_detections: ") + ifx_last_error(h_));
+    }
 
     int getMapSurfelCount() { return ifx_map_count(h_); }
     ifx_t* handle() { return h_; }
