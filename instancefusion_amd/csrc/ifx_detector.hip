@@ -1,4 +1,10 @@
-// ifx_detector.hip -- the detector's input tensor, made on the device from the frame that is already there.
+// ifx_detector.hip -- the detector's side of the library, in four sections:
+//   1. the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input[_image]; described below)
+//   2. ROIAlign forward and box NMS (ifx_roi_align_forward, ifx_nms)
+//   3. the RPN's proposal stage of one level and the box decoding it contains (ifx_rpn_proposals, ifx_box_decode)
+//   4. the box head's post-processing (ifx_box_detections)
+// Sections 2 to 4 run on the caller's stream and touch no frame or map state; the three calls with an NMS in them share one block scan (block_excl_scan), one
+// walk state (NmsWalk), one device-count mask kernel (k_nms_mask_dev) and the handle's one scratch buffer, carved by one Carver (ops_scratch).
 //
 //   ifx_detector_input[_image]  <-  COCODemo.build_transform       deps/maskrcnn-benchmark-master/demo/predictor.py:132-160
 //                                   Resize.get_size / Normalize    maskrcnn_benchmark/data/transforms/transforms.py:35-55, 86-90
@@ -405,26 +411,61 @@ __global__ void __launch_bounds__(64) k_nms_mask(const float4* sboxes, const int
     nms_mask_tile(sboxes, sgroups, n, nb, thr, mask);
 }
 
+// k_nms_mask where the number of boxes is on the device and the grid is sized for what the host knows of it: the proposal stage's survivors (one group: sgroups
+// NULL; at most 8192 of them, the first test never fires) and the box head's candidates (the class as the group; above the cap nothing is done)
+__global__ void __launch_bounds__(64) k_nms_mask_dev(const float4* sboxes, const int32_t* sgroups, const int32_t* n_dev, int nb, float thr, unsigned long long* mask)
+{
+    const int n = n_dev[0];
+    if (n > NMS_MAX || (int)blockIdx.x * 64 >= n) return;      // (the column block; the row block is not behind it where the tile is computed)
+    nms_mask_tile(sboxes, sgroups, n, nb, thr, mask);
+}
+
+// Exclusive scan of one value per thread over a block of W waves (64 W threads, every one of them calls): __shfl_up inside the wave, the wave sums through the W
+// words s_w, one barrier.  *total (may be NULL): the sum over the block.  The reuse rule, for every caller: s_w may be written again -- by a second scan through the
+// same words as by anything aliased onto them -- only behind a barrier that FOLLOWS the return, since a wave may still be reading the sums when another has returned.
+template <int W, class T>
+__device__ __forceinline__ T block_excl_scan(T mine, T* s_w, T* total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T incl = mine;
+    for (int d = 1; d < 64; d <<= 1) { const T v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    if (lane == 63) s_w[wave] = incl;
+    __syncthreads();
+    T excl = incl - mine, sum = 0;
+    for (int w = 0; w < W; w++) { const T v = s_w[w]; if (w < wave) excl += v; sum += v; }
+    if (total) *total = sum;
+    return excl;
+}
+
+// The LDS state of the walk and of the scan behind it: one instance per reduce kernel.  The arrays come first so that each starts on a multiple of 16 bytes
+// (the wave sums are read as four 16-byte words).  The number of rows kept so far is no member: every thread adds up the same keepw words in a register; as a
+// fifth member it would round the struct up to 9296 bytes and k_bd_reduce's LDS up by 8.
+struct NmsWalk {
+    unsigned long long remv[NMS_BLOCKS];   // per 64-box block: the boxes the kept rows in front of it suppress
+    uint8_t flag[NMS_MAX];                 // the kept flags
+    int wsum[16];                          // block_excl_scan's wave sums
+    unsigned long long keepw;              // the kept rows of the block the walk is at
+};
+
 // The reduction nms.cu:99-123 does on the host, in one block, and the output.  Per 64-box block b: wave 0 takes the 64 diagonal words with one load per lane and
 // resolves them in registers (64 steps of two lane reads, no memory in between); then all 16 waves OR the kept rows' words of the columns behind b into the removal
 // words in LDS, 128 columns x 8 row groups, consecutive lanes on consecutive words of a row.  Two global round trips per 64 boxes, none per box.
 // Then the kept flags by ORIGINAL index (LDS), a block scan, and the kept indices in ascending order, -1 behind them, the count.
-// The walk over the 64-box blocks, for a 1024-thread block: on return s_flag[order ? order[row] : row] is 1 for every kept row in front of the block the walk
+// The walk over the 64-box blocks, for a 1024-thread block: on return s.flag[order ? order[row] : row] is 1 for every kept row in front of the block the walk
 // stopped at.  It stops behind the block in which the kept rows reach `limit` (the proposal stage wants the first few hundred kept of thousands).
-__device__ __forceinline__ void nms_walk(const unsigned long long* mask, const int32_t* order, int n, int nb, int limit, unsigned long long* s_remv, unsigned long long* s_keepw,
-                                         int* s_kept, uint8_t* s_flag)
+__device__ __forceinline__ void nms_walk(const unsigned long long* mask, const int32_t* order, int n, int nb, int limit, NmsWalk& s)
 {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t < NMS_BLOCKS) s_remv[t] = 0;
-    if (t == 0) *s_kept = 0;
-    for (int i = t; i < n; i += 1024) s_flag[i] = 0;
+    int kept = 0;
+    if (t < NMS_BLOCKS) s.remv[t] = 0;
+    for (int i = t; i < n; i += 1024) s.flag[i] = 0;
     __syncthreads();
     for (int b = 0; b * 64 < n; b++) {
         if (wave == 0) {
             const int row = b * 64 + lane;
             const unsigned long long d = row < n ? mask[(size_t)row * nb + b] : 0ull;
             const uint32_t dlo = (uint32_t)d, dhi = (uint32_t)(d >> 32);
-            unsigned long long removed = s_remv[b], kw = 0;
+            unsigned long long removed = s.remv[b], kw = 0;
 #pragma unroll
             for (int i = 0; i < 64; i++) {
                 const unsigned long long di = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, i) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)dlo, i);
@@ -434,12 +475,13 @@ __device__ __forceinline__ void nms_walk(const unsigned long long* mask, const i
             }
             const int rows = min(64, n - b * 64);
             if (rows < 64) kw &= (1ull << rows) - 1ull;
-            if (lane == 0) { *s_keepw = kw; *s_kept += __popcll(kw); }
-            if (row < n && ((kw >> lane) & 1ull)) s_flag[order ? order[row] : row] = 1;
+            if (lane == 0) s.keepw = kw;
+            if (row < n && ((kw >> lane) & 1ull)) s.flag[order ? order[row] : row] = 1;
         }
         __syncthreads();
-        const unsigned long long kw = *s_keepw;
-        if (*s_kept >= limit) break;           // (uniform: every thread reads the same word behind the barrier, and nothing writes it before the next one)
+        const unsigned long long kw = s.keepw;
+        kept += __popcll(kw);
+        if (kept >= limit) break;              // (uniform: every thread reads the same word behind the barrier, and nothing writes it before the next one)
         const int cg = t & (NMS_BLOCKS - 1), rg = t >> 7, c = b + 1 + cg;
         if (c * 64 < n) {
             unsigned long long acc = 0;
@@ -448,42 +490,34 @@ __device__ __forceinline__ void nms_walk(const unsigned long long* mask, const i
                 const int i = rg * 8 + k;
                 if ((kw >> i) & 1ull) acc |= mask[(size_t)(b * 64 + i) * nb + c];    // kept rows are < n, columns behind b are in the upper triangle: all written
             }
-            if (acc) atomicOr(&s_remv[c], acc);
+            if (acc) atomicOr(&s.remv[c], acc);
         }
         __syncthreads();
     }
 }
 
 // Eight consecutive flags per thread of a 1024-thread block: the thread's set flags as bits, the rank of its first one among all set flags, and their number.
-__device__ __forceinline__ void nms_flag_scan(const uint8_t* s_flag, int n, int* s_wsum, uint32_t& bits, int& pos, int& total)
+// (flags: s.flag, or the caller's own array of n flags; the scan goes through s.wsum either way -- block_excl_scan's reuse rule)
+__device__ __forceinline__ void nms_flag_scan(NmsWalk& s, const uint8_t* flags, int n, uint32_t& bits, int& pos, int& total)
 {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     int mine = 0;
     bits = 0;
     for (int k = 0; k < 8; k++) {
         const int i = t * 8 + k;
-        if (i < n && s_flag[i]) { bits |= 1u << k; mine++; }
+        if (i < n && flags[i]) { bits |= 1u << k; mine++; }
     }
-    int incl = mine;
-    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    pos = incl - mine; total = 0;
-    for (int w = 0; w < 16; w++) { const int v = s_wsum[w]; if (w < wave) pos += v; total += v; }
+    pos = block_excl_scan<16>(mine, s.wsum, &total);
 }
 
 __global__ void __launch_bounds__(1024) k_nms_reduce(const unsigned long long* mask, const int32_t* order, int n, int nb, long long* keep, int32_t* count)
 {
-    __shared__ unsigned long long s_remv[NMS_BLOCKS];
-    __shared__ unsigned long long s_keepw;
-    __shared__ uint8_t s_flag[NMS_MAX];
-    __shared__ int s_wsum[16];
-    __shared__ int s_kept;
+    __shared__ NmsWalk s;
     const int t = threadIdx.x;
-    nms_walk(mask, order, n, nb, 0x7FFFFFFF, s_remv, &s_keepw, &s_kept, s_flag);
+    nms_walk(mask, order, n, nb, 0x7FFFFFFF, s);
     uint32_t bits;
     int pos, total;
-    nms_flag_scan(s_flag, n, s_wsum, bits, pos, total);      // by ORIGINAL index
+    nms_flag_scan(s, s.flag, n, bits, pos, total);           // by ORIGINAL index
     for (int k = 0; k < 8; k++)
         if (bits & (1u << k)) keep[pos++] = t * 8 + k;
     for (int i = total + t; i < n; i += 1024) keep[i] = -1;
@@ -573,16 +607,11 @@ __device__ __forceinline__ float rpn_logit(const float* obj, int i, int A, int H
 // 256 threads: the bin that holds rank `rank` (0-based) of a 2048-bin histogram, and the rank inside that bin.  The histogram's total is > rank.
 __device__ __forceinline__ void rpn_pick(const uint32_t* hist, uint32_t rank, uint32_t* s_w, uint32_t* s_out, uint32_t& digit, uint32_t& rest)
 {
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     uint32_t c[8], mine = 0;
 #pragma unroll
     for (int k = 0; k < 8; k++) { c[k] = hist[t * 8 + k]; mine += c[k]; }
-    uint32_t incl = mine;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t excl = incl - mine;
-    for (int w = 0; w < wave; w++) excl += s_w[w];
+    uint32_t excl = block_excl_scan<4, uint32_t>(mine, s_w, nullptr);
     if (excl <= rank && rank < excl + mine) {          // one thread
 #pragma unroll
         for (int k = 0; k < 8; k++) {
@@ -659,28 +688,33 @@ __global__ void __launch_bounds__(256) k_rpn_count(const float* obj, int n, int 
     if (t < 2) blk[t * nblk + blockIdx.x] = s_sum[t];
 }
 
+// M lists of per-block counts, `stride` apart: the sums of list m's blk[0 .. b) into s_sum[m], for a 256-thread block.  They are complete behind the caller's next
+// barrier (sums of integers: the arrival order cannot show).
+template <int M>
+__device__ __forceinline__ void block_sum_before(const uint32_t* blk, int stride, int b, uint32_t* s_sum)
+{
+    const int t = threadIdx.x;
+    if (t < M) s_sum[t] = 0;
+    __syncthreads();
+    uint32_t v[M] = {};
+    for (int i = t; i < b; i += 256)
+        for (int m = 0; m < M; m++) v[m] += blk[m * stride + i];
+    for (int m = 0; m < M; m++)
+        if (v[m]) atomicAdd(&s_sum[m], v[m]);
+}
+
 // cand[0 .. K): the winners' 64-bit keys -- those in front of T in index order, then the first state[7] + 1 of those on T in index order
 __global__ void __launch_bounds__(256) k_rpn_compact(const float* obj, int n, int A, int HW, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk,
                                                       unsigned long long* cand)
 {
     __shared__ uint32_t s_before[2], s_w[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
-    if (t < 2) s_before[t] = 0;
-    __syncthreads();
-    uint32_t bl = 0, be = 0;
-    for (int i = t; i < b; i += 256) { bl += blk[i]; be += blk[nblk + i]; }
-    if (bl) atomicAdd(&s_before[0], bl);
-    if (be) atomicAdd(&s_before[1], be);
+    const int t = threadIdx.x, b = blockIdx.x;
+    block_sum_before<2>(blk, nblk, b, s_before);
     const uint32_t T = state[6], take = state[7] + 1u;
     const uint2 le = rpn_classify(obj, n, A, HW, b * RPN_CHUNK + t * 8, T);
     const uint32_t less = le.x, equal = le.y;
     const uint32_t mine = (uint32_t)__popc(less) | ((uint32_t)__popc(equal) << 16);     // both counts of a block are <= 2048: one scan for the two
-    uint32_t incl = mine;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t excl = incl - mine;
-    for (int w = 0; w < wave; w++) excl += s_w[w];
+    const uint32_t excl = block_excl_scan<4, uint32_t>(mine, s_w, nullptr);
     uint32_t pl = s_before[0] + (excl & 0xFFFFu), pe = s_before[1] + (excl >> 16);
     const uint32_t base = take <= K ? K - take : 0u;   // the keys in front of T: exactly K - take of them
 #pragma unroll
@@ -705,7 +739,7 @@ struct RpnArgs {
 __global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
 {
     __shared__ unsigned long long s_key[NMS_MAX];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     if (a.cand) for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.m ? a.cand[i] : ~0ull;
     else for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.n ? nms_key(rpn_logit(a.obj, i, a.A, a.HW), i) : ~0ull;
     nms_bitonic(s_key, a.P, t);
@@ -729,13 +763,8 @@ __global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
         box[k] = box_decode_one(b, c[0], c[a.HW], c[2 * (size_t)a.HW], c[3 * (size_t)a.HW], a.q);
         if (box[k].z - box[k].x + 1.f >= a.min_size && box[k].w - box[k].y + 1.f >= a.min_size) bits |= 1u << k;     // remove_small_boxes (boxlist_ops.py:34-48): a NaN is false
     }
-    const int mine = __popc(bits);
-    int incl = mine;
-    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int pos = incl - mine, total = 0;
-    for (int w = 0; w < 16; w++) { const int v = s_wsum[w]; if (w < wave) pos += v; total += v; }
+    int total;
+    int pos = block_excl_scan<16>((int)__popc(bits), s_wsum, &total);
 #pragma unroll
     for (int k = 0; k < 8; k++)
         if (bits & (1u << k)) {
@@ -747,29 +776,17 @@ __global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
     if (t == 0) a.ns[0] = total;
 }
 
-// k_nms_mask on the survivors: their number is on the device, the grid is sized for the candidates
-__global__ void __launch_bounds__(64) k_rpn_mask(const float4* sboxes, const int32_t* ns, int nb, float thr, unsigned long long* mask)
-{
-    const int n = ns[0];
-    if ((int)blockIdx.x * 64 >= n) return;             // (the column block; the row block is not behind it where the tile is computed)
-    nms_mask_tile(sboxes, nullptr, n, nb, thr, mask);
-}
-
 // k_nms_reduce's walk, stopped once `post` boxes are kept, and the output in the candidates' order: the first min(kept, post) kept rows with box, logit and index;
 // zeros and -1 behind them up to post; the count
 __global__ void __launch_bounds__(1024) k_rpn_reduce(const unsigned long long* mask, const float4* sboxes, const float* slogit, const int32_t* sindex, const int32_t* ns, int nb,
                                                      int post, float* boxes, float* logits, long long* index, int32_t* count)
 {
-    __shared__ unsigned long long s_remv[NMS_BLOCKS];
-    __shared__ unsigned long long s_keepw;
-    __shared__ uint8_t s_flag[NMS_MAX];
-    __shared__ int s_wsum[16];
-    __shared__ int s_kept;
+    __shared__ NmsWalk s;
     const int t = threadIdx.x, n = ns[0];
-    nms_walk(mask, nullptr, n, nb, post, s_remv, &s_keepw, &s_kept, s_flag);
+    nms_walk(mask, nullptr, n, nb, post, s);
     uint32_t bits;
     int pos, total;
-    nms_flag_scan(s_flag, n, s_wsum, bits, pos, total);      // by sorted row
+    nms_flag_scan(s, s.flag, n, bits, pos, total);           // by sorted row
     for (int k = 0; k < 8; k++)
         if (bits & (1u << k)) {
             if (pos < post) {
@@ -857,20 +874,11 @@ __global__ void __launch_bounds__(256) k_bd_count(const float* plane, int n, uin
 __global__ void __launch_bounds__(256) k_bd_compact(const float* plane, int n, const uint32_t* blk, uint32_t* cand, int32_t* ktot)
 {
     __shared__ uint32_t s_before, s_w[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
-    if (t == 0) s_before = 0;
-    __syncthreads();
-    uint32_t bl = 0;
-    for (int i = t; i < b; i += 256) bl += blk[i];
-    if (bl) atomicAdd(&s_before, bl);
+    const int t = threadIdx.x, b = blockIdx.x;
+    block_sum_before<1>(blk, 0, b, &s_before);
     const uint32_t bits = bd_classify(plane, n, b * BD_CHUNK + t * 8);
-    const uint32_t mine = (uint32_t)__popc(bits);
-    uint32_t incl = mine;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t pos = s_before + incl - mine;
-    for (int w = 0; w < wave; w++) pos += s_w[w];
+    uint32_t pos = block_excl_scan<4, uint32_t>((uint32_t)__popc(bits), s_w, nullptr);
+    pos += s_before;                                   // (behind the scan's barrier: the sum is complete)
 #pragma unroll
     for (int k = 0; k < 8; k++)
         if (bits & (1u << k)) { if (pos < (uint32_t)NMS_MAX) cand[pos] = (uint32_t)(b * BD_CHUNK + t * 8 + k); pos++; }
@@ -919,14 +927,6 @@ __global__ void __launch_bounds__(1024) k_bd_sort_decode(const BdArgs a)
     }
 }
 
-// k_nms_mask with the class as the group; the number of candidates is on the device, the grid is sized for what the host knows of it
-__global__ void __launch_bounds__(64) k_bd_mask(const float4* sboxes, const int32_t* sgroups, const int32_t* ktot, int nb, float thr, unsigned long long* mask)
-{
-    const int n = ktot[0];
-    if (n > NMS_MAX || (int)blockIdx.x * 64 >= n) return;
-    nms_mask_tile(sboxes, sgroups, n, nb, thr, mask);
-}
-
 struct BdOut {
     float* boxes; float* scores; long long* labels; long long* index; int32_t* count; int32_t* stats;
     int max_out, limit;
@@ -938,20 +938,17 @@ struct BdOut {
 __global__ void __launch_bounds__(1024) k_bd_reduce(const unsigned long long* mask, const float4* sboxes, const int32_t* sgroups, const float* sscore, const int32_t* spos,
                                                     const int32_t* srow, const int32_t* ktot, int nb, const BdOut o)
 {
-    __shared__ unsigned long long s_remv[NMS_BLOCKS];
-    __shared__ unsigned long long s_keepw;
-    __shared__ uint8_t s_flag[NMS_MAX], s_stay[NMS_MAX];
+    __shared__ NmsWalk s;
+    __shared__ uint8_t s_stay[NMS_MAX];
     __shared__ uint16_t s_rowof[NMS_MAX];
-    __shared__ int s_wsum[16];
-    __shared__ int s_kept;
     __shared__ float s_t;
     const int t = threadIdx.x, K = ktot[0];
     const bool over = K > NMS_MAX;
     const int n = over ? 0 : K;
-    nms_walk(mask, nullptr, n, nb, 0x7FFFFFFF, s_remv, &s_keepw, &s_kept, s_flag);
+    nms_walk(mask, nullptr, n, nb, 0x7FFFFFFF, s);
     uint32_t bits;
     int pos, total;
-    nms_flag_scan(s_flag, n, s_wsum, bits, pos, total);      // by sorted row; total = D
+    nms_flag_scan(s, s.flag, n, bits, pos, total);           // by sorted row; total = D
     const int D = total;
     const bool cut = o.limit > 0 && D > o.limit;
     if (cut)
@@ -964,10 +961,10 @@ __global__ void __launch_bounds__(1024) k_bd_reduce(const unsigned long long* ma
         const int i = spos[row];
         if ((uint32_t)i >= (uint32_t)n) continue;          // (a candidate position: always inside)
         s_rowof[i] = (uint16_t)row;
-        if (s_flag[row] && (!cut || sscore[row] >= thr)) s_stay[i] = 1;
+        if (s.flag[row] && (!cut || sscore[row] >= thr)) s_stay[i] = 1;
     }
-    __syncthreads();
-    nms_flag_scan(s_stay, n, s_wsum, bits, pos, total);      // by candidate position
+    __syncthreads();                                         // (with the one above: between the two scans through s.wsum)
+    nms_flag_scan(s, s_stay, n, bits, pos, total);           // by candidate position
     for (int k = 0; k < 8; k++)
         if (bits & (1u << k)) {
             if (pos < o.max_out) {
@@ -999,8 +996,8 @@ struct StreamScope {
     ~StreamScope() { h->cur = old; }
 };
 
-// the scratch of ifx_nms (order, sorted groups, sorted boxes, mask words) and of ifx_rpn_proposals: allocated by the first call, grown on demand (hipFree waits for
-// its readers), and ordered across streams by an event
+// the one scratch buffer of ifx_nms, ifx_rpn_proposals and ifx_box_detections: allocated by the first call, grown on demand (hipFree waits for its readers), and
+// ordered across streams by an event
 struct DetOps {
     void* buf = nullptr;
     size_t bytes = 0;
@@ -1009,9 +1006,27 @@ struct DetOps {
     bool used = false;
 };
 
-// at least `bytes` of scratch for a call on `stream`, behind the previous call's use of it
-int ops_scratch(ifx* h, const char* who, size_t bytes, hipStream_t stream, DetOps** out)
+// A bump carver over the scratch: take<T>(count) returns base + offset (NULL while base is NULL: the sizing pass) and advances the offset, which stays a multiple
+// of 16 bytes.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    template <class T> T* take(size_t count)
+    {
+        T* p = base ? (T*)(base + off) : nullptr;
+        off += (count * sizeof(T) + 15) & ~(size_t)15;
+        return p;
+    }
+};
+
+// The scratch of a call on `stream`, behind the previous call's use of it.  `layout` carves the call's arrays out of a Carver and is the ONE statement of where they
+// lie: it runs on a NULL base for the size the buffer must have, then on the buffer, and a second pass that ends beyond the buffer is refused, not run.
+template <class F>
+int ops_scratch(ifx* h, const char* who, F layout, hipStream_t stream, DetOps** out)
 {
+    Carver size{nullptr};
+    layout(size);
+    const size_t bytes = size.off;
     if (!h->det_ops) h->det_ops = new DetOps();
     DetOps* ops = (DetOps*)h->det_ops;
     if (!ops->ev) HIPCHK(h, hipEventCreateWithFlags(&ops->ev, hipEventDisableTiming));
@@ -1020,8 +1035,20 @@ int ops_scratch(ifx* h, const char* who, size_t bytes, hipStream_t stream, DetOp
         if (hipMalloc(&ops->buf, bytes) != hipSuccess) { h->err = std::string(who) + ": hipMalloc of the scratch failed"; return IFX_E_HIP; }
         ops->bytes = bytes;
     }
+    Carver c{(char*)ops->buf};
+    layout(c);
+    if (c.off > ops->bytes) { h->err = std::string(who) + ": the scratch layout ends beyond the buffer"; return IFX_E_STATE; }
     if (ops->used && ops->last != stream) HIPCHK(h, hipStreamWaitEvent(stream, ops->ev, 0));   // the previous call may still be using the scratch on its stream
     *out = ops;
+    return IFX_OK;
+}
+
+// the end of a call that went through: the next call on another stream waits for this event
+int ops_done(ifx* h, DetOps* ops, hipStream_t stream)
+{
+    HIPCHK(h, hipEventRecord(ops->ev, stream));
+    ops->used = true;
+    ops->last = stream;
     return IFX_OK;
 }
 
@@ -1029,13 +1056,15 @@ int nms_run(ifx* h, const float* d_boxes, const float* d_scores, const int32_t* 
 {
     int cap = 1024;
     while (cap < n) cap <<= 1;
+    float4* sboxes; unsigned long long* mask; int32_t *order, *sgroups;
     DetOps* ops = nullptr;
-    int r = ops_scratch(h, "ifx_nms", (size_t)cap * (4 + 4 + 16) + (size_t)cap * (cap / 64) * 8, stream, &ops);
+    int r = ops_scratch(h, "ifx_nms", [&](Carver& c) {
+        sboxes = c.take<float4>(cap);
+        mask = c.take<unsigned long long>((size_t)cap * (cap / 64));
+        order = c.take<int32_t>(cap);
+        sgroups = c.take<int32_t>(cap);
+    }, stream, &ops);
     if (r) return r;
-    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first
-    unsigned long long* mask = (unsigned long long*)(sboxes + cap);
-    int32_t* order = (int32_t*)(mask + (size_t)cap * (cap / 64));
-    int32_t* sgroups = order + cap;
     StreamScope scope(h, stream);
     int P = 2;
     while (P < n) P <<= 1;
@@ -1043,14 +1072,11 @@ int nms_run(ifx* h, const float* d_boxes, const float* d_scores, const int32_t* 
     LAUNCH(h, "nms_sort", dim3(1), dim3(1024), k_nms_sort, d_boxes, d_scores, d_groups, n, P, order, sboxes, sgroups);
     LAUNCH(h, "nms_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_nms_mask, (const float4*)sboxes, (const int32_t*)sgroups, n, nb, threshold, mask);
     LAUNCH(h, "nms_reduce", dim3(1), dim3(1024), k_nms_reduce, (const unsigned long long*)mask, (const int32_t*)order, n, nb, (long long*)d_keep, d_count);
-    HIPCHK(h, hipEventRecord(ops->ev, stream));
-    ops->used = true;
-    ops->last = stream;
-    return IFX_OK;
+    return ops_done(h, ops, stream);
 }
 
 
-// The proposal stage's launches.  Scratch, in the handle's buffer behind nms_run's convention: sorted boxes, mask words, the winners' keys, sorted logits and
+// The proposal stage's launches.  Scratch, out of the handle's buffer: sorted boxes, mask words, the winners' keys, sorted logits and
 // indices, the per-block counts, and -- zeroed by one memset per call -- the three histograms, the selection's state and the survivors' count.
 int rpn_run(ifx* h, const float* d_obj, const float* d_reg, const float* d_anc, int A, int HW, const ifx_rpn_params* p, const BoxCode& q, float* d_boxes, float* d_logits,
             int64_t* d_index, int32_t* d_count, hipStream_t stream)
@@ -1058,17 +1084,18 @@ int rpn_run(ifx* h, const float* d_obj, const float* d_reg, const float* d_anc, 
     const int n = A * HW, m = std::min(p->pre_nms_top_n, n), mc = cdiv(m, 64) * 64, nb = mc / 64, nblk = cdiv(n, RPN_CHUNK);
     const bool select = n > NMS_MAX;
     const size_t zero_words = 3 * RPN_BINS + 8 + 8;    // histograms, state, the survivors' count (and padding)
-    const size_t bytes = (size_t)mc * 16 + (size_t)mc * nb * 8 + (size_t)mc * 8 + (size_t)mc * 8 + (size_t)nblk * 8 + zero_words * 4;
+    float4* sboxes; unsigned long long *mask, *cand; float* slogit; int32_t* sindex; uint32_t *blk, *hist;
     DetOps* ops = nullptr;
-    int r = ops_scratch(h, "ifx_rpn_proposals", bytes, stream, &ops);
+    int r = ops_scratch(h, "ifx_rpn_proposals", [&](Carver& c) {
+        sboxes = c.take<float4>(mc);
+        mask = c.take<unsigned long long>((size_t)mc * nb);
+        cand = c.take<unsigned long long>(mc);
+        slogit = c.take<float>(mc);
+        sindex = c.take<int32_t>(mc);
+        blk = c.take<uint32_t>(2 * (size_t)nblk);
+        hist = c.take<uint32_t>(zero_words);           // one take: one memset zeroes the histograms, the state and the count behind them
+    }, stream, &ops);
     if (r) return r;
-    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first, then 8-B, then 4-B
-    unsigned long long* mask = (unsigned long long*)(sboxes + mc);
-    unsigned long long* cand = mask + (size_t)mc * nb;
-    float* slogit = (float*)(cand + mc);
-    int32_t* sindex = (int32_t*)(slogit + mc);
-    uint32_t* blk = (uint32_t*)(sindex + mc);
-    uint32_t* hist = blk + 2 * (size_t)nblk;
     uint32_t* state = hist + 3 * RPN_BINS;
     int32_t* ns = (int32_t*)(state + 8);
     StreamScope scope(h, stream);
@@ -1089,36 +1116,34 @@ int rpn_run(ifx* h, const float* d_obj, const float* d_reg, const float* d_anc, 
     a.q = q; a.min_size = p->min_size;
     a.sboxes = sboxes; a.slogit = slogit; a.sindex = sindex; a.ns = ns;
     LAUNCH(h, "rpn_sort_decode", dim3(1), dim3(1024), k_rpn_sort_decode, a);
-    LAUNCH(h, "rpn_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_rpn_mask, (const float4*)sboxes, (const int32_t*)ns, nb, p->nms_thresh, mask);
+    LAUNCH(h, "rpn_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_nms_mask_dev, (const float4*)sboxes, (const int32_t*)nullptr, (const int32_t*)ns, nb, p->nms_thresh, mask);
     LAUNCH(h, "rpn_reduce", dim3(1), dim3(1024), k_rpn_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const float*)slogit, (const int32_t*)sindex,
            (const int32_t*)ns, nb, p->post_nms_top_n, d_boxes, d_logits, (long long*)d_index, d_count);
-    HIPCHK(h, hipEventRecord(ops->ev, stream));
-    ops->used = true;
-    ops->last = stream;
-    return IFX_OK;
+    return ops_done(h, ops, stream);
 }
 
-// The box head's post-processing: six launches.  Scratch, in the handle's buffer behind nms_run's convention: sorted boxes, mask words, then the 4-byte arrays --
+// The box head's post-processing: six launches.  Scratch, out of the handle's buffer: sorted boxes, mask words, then the 4-byte arrays --
 // the plane of probabilities, the candidates' plane positions, the sorted groups / scores / candidate positions / rows, the per-block counts and K.  Every word a
 // kernel reads is written by a kernel in front of it in the same call: nothing is zeroed.
 int bd_run(ifx* h, const float* d_logits, const float* d_reg, const float* d_prop, int R, int C, int Creg, const ifx_box_det_params* p, const BoxCode& q, const BdOut& out,
            hipStream_t stream)
 {
     const int n = (C - 1) * R, mc = cdiv(std::min(n, NMS_MAX), 64) * 64, nb = mc / 64, nblk = cdiv(n, BD_CHUNK);
-    const size_t bytes = (size_t)mc * 16 + (size_t)mc * nb * 8 + ((size_t)n + 5 * (size_t)mc + (size_t)nblk + 4) * 4;
+    float4* sboxes; unsigned long long* mask; float *plane, *sscore; uint32_t *cand, *blk; int32_t *sgroups, *spos, *srow, *ktot;
     DetOps* ops = nullptr;
-    int r = ops_scratch(h, "ifx_box_detections", bytes, stream, &ops);
+    int r = ops_scratch(h, "ifx_box_detections", [&](Carver& c) {
+        sboxes = c.take<float4>(mc);
+        mask = c.take<unsigned long long>((size_t)mc * nb);
+        plane = c.take<float>(n);
+        cand = c.take<uint32_t>(mc);
+        sgroups = c.take<int32_t>(mc);
+        sscore = c.take<float>(mc);
+        spos = c.take<int32_t>(mc);
+        srow = c.take<int32_t>(mc);
+        blk = c.take<uint32_t>(nblk);
+        ktot = c.take<int32_t>(4);                     // K (and padding)
+    }, stream, &ops);
     if (r) return r;
-    float4* sboxes = (float4*)ops->buf;                                   // 16-B records first, then 8-B, then 4-B
-    unsigned long long* mask = (unsigned long long*)(sboxes + mc);
-    float* plane = (float*)(mask + (size_t)mc * nb);
-    uint32_t* cand = (uint32_t*)(plane + n);
-    int32_t* sgroups = (int32_t*)(cand + mc);
-    float* sscore = (float*)(sgroups + mc);
-    int32_t* spos = (int32_t*)(sscore + mc);
-    int32_t* srow = spos + mc;
-    uint32_t* blk = (uint32_t*)(srow + mc);
-    int32_t* ktot = (int32_t*)(blk + nblk);
     StreamScope scope(h, stream);
     LAUNCH(h, "bd_softmax", dim3((unsigned)cdiv(R, 4)), dim3(256), k_bd_softmax, d_logits, R, C, p->score_thresh, plane);
     LAUNCH(h, "bd_count", dim3((unsigned)nblk), dim3(256), k_bd_count, (const float*)plane, n, blk);
@@ -1128,12 +1153,20 @@ int bd_run(ifx* h, const float* d_logits, const float* d_reg, const float* d_pro
     a.R = R; a.C = C; a.Creg = Creg; a.n = n; a.q = q;
     a.sboxes = sboxes; a.sgroups = sgroups; a.sscore = sscore; a.spos = spos; a.srow = srow;
     LAUNCH(h, "bd_sort_decode", dim3(1), dim3(1024), k_bd_sort_decode, a);
-    LAUNCH(h, "bd_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_bd_mask, (const float4*)sboxes, (const int32_t*)sgroups, (const int32_t*)ktot, nb, p->nms, mask);
+    LAUNCH(h, "bd_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_nms_mask_dev, (const float4*)sboxes, (const int32_t*)sgroups, (const int32_t*)ktot, nb, p->nms, mask);
     LAUNCH(h, "bd_reduce", dim3(1), dim3(1024), k_bd_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const int32_t*)sgroups, (const float*)sscore,
            (const int32_t*)spos, (const int32_t*)srow, (const int32_t*)ktot, nb, out);
-    HIPCHK(h, hipEventRecord(ops->ev, stream));
-    ops->used = true;
-    ops->last = stream;
+    return ops_done(h, ops, stream);
+}
+
+// no input: the padding alone -- `rows` zero boxes, zeros in the f32 array, -1 in the int64 arrays (each where it is given), a count of 0
+int ops_padding(ifx* h, size_t rows, float* boxes, float* f32, int64_t* ia, int64_t* ib, int32_t* count, hipStream_t s)
+{
+    HIPCHK(h, hipMemsetAsync(boxes, 0, rows * 16, s));
+    if (f32) HIPCHK(h, hipMemsetAsync(f32, 0, rows * 4, s));
+    if (ia) HIPCHK(h, hipMemsetAsync(ia, 0xFF, rows * 8, s));
+    if (ib) HIPCHK(h, hipMemsetAsync(ib, 0xFF, rows * 8, s));
+    HIPCHK(h, hipMemsetAsync(count, 0, 4, s));
     return IFX_OK;
 }
 
@@ -1252,14 +1285,7 @@ extern "C" int ifx_rpn_proposals(ifx_t* h, const float* d_objectness, const floa
     if (const char* bad = box_code(p->weights, p->xform_clip, p->image_w, p->image_h, &q)) { h->err = std::string("ifx_rpn_proposals: ") + bad; return IFX_E_INVALID; }
     const int n = A * H * W;
     if (n > 0 && (!d_objectness || !d_regression || !d_anchors)) { h->err = "ifx_rpn_proposals: NULL pointer"; return IFX_E_INVALID; }
-    if (n == 0) {                                      // no anchors: the padding alone
-        hipStream_t s = (hipStream_t)stream;
-        HIPCHK(h, hipMemsetAsync(d_boxes, 0, (size_t)p->post_nms_top_n * 16, s));
-        if (d_logits) HIPCHK(h, hipMemsetAsync(d_logits, 0, (size_t)p->post_nms_top_n * 4, s));
-        if (d_index) HIPCHK(h, hipMemsetAsync(d_index, 0xFF, (size_t)p->post_nms_top_n * 8, s));
-        HIPCHK(h, hipMemsetAsync(d_count, 0, 4, s));
-        return IFX_OK;
-    }
+    if (n == 0) return ops_padding(h, (size_t)p->post_nms_top_n, d_boxes, d_logits, d_index, nullptr, d_count, (hipStream_t)stream);   // no anchors
     return rpn_run(h, d_objectness, d_regression, d_anchors, A, H * W, p, q, d_boxes, d_logits, d_index, d_count, (hipStream_t)stream);
 }
 
@@ -1294,15 +1320,9 @@ extern "C" int ifx_box_detections(ifx_t* h, const float* d_logits, const float* 
     BoxCode q;
     if (const char* bad = box_code(p->weights, p->xform_clip, p->image_w, p->image_h, &q)) { h->err = std::string("ifx_box_detections: ") + bad; return IFX_E_INVALID; }
     if (R > 0 && (!d_logits || !d_regression || !d_proposals)) { h->err = "ifx_box_detections: NULL pointer"; return IFX_E_INVALID; }
-    if (R == 0) {                                      // no rows: the padding alone
-        hipStream_t s = (hipStream_t)stream;
-        HIPCHK(h, hipMemsetAsync(d_boxes, 0, (size_t)p->max_out * 16, s));
-        if (d_scores) HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)p->max_out * 4, s));
-        if (d_labels) HIPCHK(h, hipMemsetAsync(d_labels, 0xFF, (size_t)p->max_out * 8, s));
-        if (d_index) HIPCHK(h, hipMemsetAsync(d_index, 0xFF, (size_t)p->max_out * 8, s));
-        HIPCHK(h, hipMemsetAsync(d_count, 0, 4, s));
-        if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, 8, s));
-        return IFX_OK;
+    if (R == 0) {                                      // no rows
+        if (d_stats) HIPCHK(h, hipMemsetAsync(d_stats, 0, 8, (hipStream_t)stream));
+        return ops_padding(h, (size_t)p->max_out, d_boxes, d_scores, d_labels, d_index, d_count, (hipStream_t)stream);
     }
     BdOut o;
     o.boxes = d_boxes; o.scores = d_scores; o.labels = (long long*)d_labels; o.index = (long long*)d_index; o.count = d_count; o.stats = d_stats;
