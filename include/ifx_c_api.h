@@ -708,6 +708,39 @@ typedef struct ifx_box_det_params {
 int ifx_box_detections(ifx_t* h, const float* d_logits, const float* d_regression, const float* d_proposals, int R, int C, int Creg,
                        const ifx_box_det_params* p, float* d_boxes, float* d_scores, int64_t* d_labels, int64_t* d_index, int32_t* d_count,
                        int32_t* d_stats, void* stream);
+/* ---- multi-level ROI pooling.  In front of the box head and of the mask head the reference runs the FPN Pooler (maskrcnn_benchmark/modeling/poolers.py:11-121):
+ * LevelMapper in about ten stock launches, then per level a nonzero (a host synchronisation), a gather, _C.roi_align_forward and an index_put into a zero-filled
+ * result.  ifx_fpn_roi_align is Pooler.forward behind convert_to_roi_format in ONE launch: every block finds its ROI's level and runs ifx_roi_align_forward's body
+ * against that level's map.  As the operators above: f32, the caller's buffers on the caller's stream, enqueue only, no scratch, no allocation, no frame, map or
+ * handle state, any handle (a sharded one too).  In numpy: tests/fpn_pooler_numpy.py, held against the reference's own Pooler.forward and LevelMapper through
+ * tests/golden/fpn_pooler_ref.npz.
+ *   Inputs: d_features, heights, widths, scales: HOST arrays of `levels` entries (1 <= levels <= 8), d_features[l] the device pointer of level l's map
+ *     [batch][channels][heights[l]][widths[l]]; d_rois n x 5 (batch index, x0, y0, x1, y1); d_out [n][channels][pooled_h][pooled_w]; d_levels NULL or n int32.
+ *   Scales: scales[l] == 2^-(k_min + l) exactly, for an integer k_min >= 0 (the Pooler's own assumption, poolers.py:72-76: its k_min and k_max are -log2 of the
+ *     first and the last scale); k_max = k_min + levels - 1 <= 126.
+ *   Level of an ROI (LevelMapper, poolers.py:31-42, with BoxList.area, structures/bounding_box.py:226-236), every operation rounded to f32 and none fused:
+ *     area = (x1 - x0 + 1) * (y1 - y0 + 1);  s = sqrt(area), correctly rounded;  v = s / canonical_scale + eps (a true division; defaults 224 and 1e-6f);
+ *     L = log2(v) evaluated in f64 and rounded once to f32;  t = f32(canonical_level + L) (default 4);  level = clamp(floor(t), k_min, k_max) - k_min.
+ *     The two roundings of L and t are part of the rule: just below a power of two, canonical_level + L rounds up to the integer, as torch.floor(4 + torch.log2(v))
+ *     does on the CPU.  A NaN t -- a negative or NaN area (a non-finite coordinate), or a v < 0, which only a negative eps can give -- is NO level: the ROI's outputs
+ *     are zeros, no map is read and d_levels is -1 (the reference's `levels == level` never matches it, so its row of the zero-filled result stays).  An area of 0
+ *     goes to level 0, +inf to the last level.
+ *     How: the level is monotone in v, so the host finds per call the levels - 1 thresholds T_j = the smallest f32 v >= 0 whose rule value reaches level j, by
+ *     bisection over f32 bit patterns with the host's f64 log2, and passes them by value with the level table; on the device one lane computes v (a correctly
+ *     rounded square root, an IEEE division, an addition), counts the T_j that v reaches and hands the level to its block through LDS.
+ *     ifx_fpn_level_thresholds (host only, no handle): out[j - 1] = T_j for j = 1 .. levels - 1; returns k_min, or IFX_E_INVALID for NULL pointers, levels outside
+ *     1 .. 8 or scales that are not the ladder.
+ *   levels == 1: no mapping at all (poolers.py:101-102): the call is ifx_roi_align_forward on that map, NaN-area ROIs included, and d_levels is 0.
+ *   Pooling: ifx_roi_align_forward's rule with the level's map, height, width and scale; the batch rule too (an index outside 0 .. batch - 1: zeros).
+ *   d_levels (optional) receives the level index of every ROI, -1 for no level.
+ *   Refusals (nothing enqueued, the handle stays usable), IFX_E_INVALID: levels outside 1 .. 8; NULL d_features, heights, widths, scales or an entry of d_features;
+ *     NULL d_rois or d_out with n > 0; n < 0, batch / channels / a height / a width / pooled_h / pooled_w < 1, sampling_ratio < 0; scales that are not the ladder;
+ *     a canonical_scale that is not a positive finite number; a non-finite eps; sizes beyond the launch, as ifx_roi_align_forward.  n == 0 succeeds and writes
+ *     nothing. */
+int ifx_fpn_level_thresholds(const float* scales, int levels, int canonical_level, float* out);
+int ifx_fpn_roi_align(ifx_t* h, const float* const* d_features, const int32_t* heights, const int32_t* widths, const float* scales, int levels, int batch, int channels,
+                      const float* d_rois, int n, float canonical_scale, int canonical_level, float eps, int pooled_h, int pooled_w, int sampling_ratio, float* d_out,
+                      int32_t* d_levels, void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

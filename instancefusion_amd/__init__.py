@@ -187,6 +187,8 @@ _SIGS = {
     "ifx_detector_input_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(DetectorPrep), _P, C.c_int64, _P]),
     "ifx_roi_align_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P]),
     "ifx_nms": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P]),
+    "ifx_fpn_level_thresholds": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "ifx_fpn_roi_align": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ifx_rpn_proposals": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(RpnParams), _P, _P, _P, _P, _P]),
     "ifx_box_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float * 4), C.c_float, C.c_int, C.c_int, _P, _P]),
     "ifx_box_detections": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(BoxDetParams), _P, _P, _P, _P, _P, _P, _P]),
@@ -477,6 +479,50 @@ def box_post_processor(ef, score_thresh, nms, detections_per_img, weights=(10, 1
     return _box_post_processor_class()(ef, score_thresh, nms, detections_per_img, weights, cls_agnostic_bbox_reg)
 
 
+@functools.lru_cache(maxsize=None)
+def _pooler_class():
+    """the nn.Module behind pooler, made on first use: the package imports torch lazily"""
+    import torch
+
+    class Pooler(torch.nn.Module):
+        def __init__(self, ef, output_size, scales, sampling_ratio):
+            super().__init__()
+            self.ef = ef
+            self.output_size = (int(output_size), int(output_size)) if isinstance(output_size, int) else (int(output_size[0]), int(output_size[1]))
+            self.scales, self.sampling_ratio = tuple(float(s) for s in scales), int(sampling_ratio)
+
+        def convert_to_roi_format(self, boxes):
+            bbox = [b.bbox for b in boxes]
+            ids = [torch.full((len(b), 1), i, dtype=b.bbox.dtype, device=b.bbox.device) for i, b in enumerate(boxes)]
+            return torch.cat([torch.cat(ids, dim=0), torch.cat(bbox, dim=0)], dim=1)
+
+        def forward(self, x, boxes):
+            rois = self.convert_to_roi_format(boxes)
+            return self.ef.fpn_roi_align([f.contiguous() for f in x], rois, self.scales, self.output_size[0], self.output_size[1], self.sampling_ratio)
+
+    return Pooler
+
+
+def pooler(ef, output_size, scales, sampling_ratio):
+    """An nn.Module that stands in for maskrcnn-benchmark's Pooler (modeling/poolers.py) at inference time: forward(x, boxes) with x a list (per level) of
+    [N,C,H_l,W_l] feature maps and boxes a list (per image) of box lists does convert_to_roi_format (the image's position in the list as the batch index in front of
+    .bbox) and ONE ElasticFusion.fpn_roi_align call -- LevelMapper with its defaults (224, 4, 1e-6) and ROIAlign on the chosen level -- and returns
+    [sum R, C, output_size[0], output_size[1]].  The box lists are duck-typed (.bbox, len), so nothing of the reference is imported.  scales must be the ladder
+    2^-k_min, 2^-(k_min + 1), ... the Pooler itself assumes."""
+    return _pooler_class()(ef, output_size, scales, sampling_ratio)
+
+
+def fpn_level_thresholds(scales, canonical_level=4):
+    """ifx_fpn_level_thresholds (host only, no GPU): (k_min, T) with T[j - 1] the smallest float32 v = sqrt(area) / canonical_scale + eps that ifx_fpn_roi_align
+    maps to level j, j = 1 .. len(scales) - 1."""
+    sc = np.ascontiguousarray(scales, np.float32).reshape(-1)
+    out = np.zeros(max(sc.size - 1, 0), np.float32)
+    r = lib().ifx_fpn_level_thresholds(_ptr(sc), int(sc.size), int(canonical_level), _ptr(np.zeros(1, np.float32)) if out.size == 0 else _ptr(out))
+    if r < 0:
+        raise IfxError(f"ifx_fpn_level_thresholds: refused (scales {[float(v) for v in sc]})")
+    return r, out
+
+
 def detector_ops(ef):
     """An object that stands in for maskrcnn_benchmark._C at inference time: nms(dets, scores, threshold) and roi_align_forward(input, rois, spatial_scale,
     pooled_h, pooled_w, sampling_ratio) run ifx_nms / ifx_roi_align_forward on `ef`'s device and the current stream; every other _C name (roi_align_backward,
@@ -547,6 +593,57 @@ class ElasticFusion:
                 raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(shape)}")
         self._chk(self.L.ifx_roi_align_forward(self.handle, C.c_void_p(input.data_ptr()), B, Cn, H, W, C.c_void_p(rois.data_ptr()), n, float(spatial_scale), ph, pw,
                                                int(sampling_ratio), C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_roi_align_forward")
+        return out
+
+    def fpn_roi_align(self, features, rois, scales, pooled_h, pooled_w, sampling_ratio, canonical_scale=224, canonical_level=4, eps=1e-6, out=None, levels_out=None,
+                      stream=None):
+        """ifx_fpn_roi_align, the FPN Pooler in one launch: features a list of contiguous [B,C,H_l,W_l] float32 maps, rois [n,5] float32 (batch index, x0, y0, x1,
+        y1), scales[l] == 2^-(k_min + l) -> [n,C,pooled_h,pooled_w] float32: every ROI pooled from the level LevelMapper gives it, bit for bit the rule of
+        include/ifx_c_api.h.  levels_out: an int32 [n] tensor that receives each ROI's level index (-1: no level, a row of zeros).  Enqueue-only on `stream`
+        (default: the current stream)."""
+        import torch
+
+        features = list(features)
+        if not features:
+            raise ValueError("features: an empty list")
+        for l, f in enumerate(features):
+            _ops_tensor(self, f, f"features[{l}]", torch.float32, "float32")
+            if f.dim() != 4:
+                raise ValueError(f"features[{l}]: shape {tuple(f.shape)}, expected [B,C,H,W]")
+            if tuple(f.shape[:2]) != tuple(features[0].shape[:2]):
+                raise ValueError(f"features[{l}]: shape {tuple(f.shape)}, expected the batch and channels of features[0], {list(features[0].shape[:2])}")
+        _ops_tensor(self, rois, "rois", torch.float32, "float32")
+        if rois.dim() != 2 or rois.shape[1] != 5:
+            raise ValueError(f"rois: shape {tuple(rois.shape)}, expected [n,5]")
+        scales = [float(s) for s in scales]
+        if len(scales) != len(features):
+            raise ValueError(f"scales: {len(scales)} entries for {len(features)} feature maps")
+        nl = len(features)
+        B, Cn = int(features[0].shape[0]), int(features[0].shape[1])
+        n, ph, pw = int(rois.shape[0]), int(pooled_h), int(pooled_w)
+        dev = features[0].device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        shape = (n, Cn, max(ph, 0), max(pw, 0))
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            _ops_tensor(self, out, "out", torch.float32, "float32")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(shape)}")
+        if levels_out is not None:
+            _ops_tensor(self, levels_out, "levels_out", torch.int32, "int32")
+            if tuple(levels_out.shape) != (n,):
+                raise ValueError(f"levels_out: shape {tuple(levels_out.shape)}, expected [{n}]")
+        ptrs = (C.c_void_p * nl)(*[f.data_ptr() for f in features])
+        hs = (C.c_int32 * nl)(*[int(f.shape[2]) for f in features])
+        ws = (C.c_int32 * nl)(*[int(f.shape[3]) for f in features])
+        sc = (C.c_float * nl)(*scales)
+        self._chk(self.L.ifx_fpn_roi_align(self.handle, ptrs, hs, ws, sc, nl, B, Cn, C.c_void_p(rois.data_ptr()), n, float(canonical_scale), int(canonical_level),
+                                           float(eps), ph, pw, int(sampling_ratio), C.c_void_p(out.data_ptr()),
+                                           None if levels_out is None else C.c_void_p(levels_out.data_ptr()), C.c_void_p(stream.cuda_stream or None)),
+                  "ifx_fpn_roi_align")
         return out
 
     def nms(self, boxes, scores, threshold, groups=None, stream=None, padded=False):

@@ -19,6 +19,7 @@
 #include "../host/ifx_detector_prep.hpp"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace {
 
@@ -284,42 +285,41 @@ struct RaArgs {
 // sample's arithmetic per output and channel).  Phase 2: consecutive lanes take consecutive outputs of the block's [channel][ph][pw] run, which is contiguous in the
 // output (coalesced stores) and keeps a wave's gathers inside one or two channel planes.  A sample outside contributes +0 and is skipped: the accumulator starts at
 // +0 and can never be -0 (x + -x and +0 + -0 are +0 in round-to-nearest), so acc + (+0) == acc bit for bit.
-__global__ void __launch_bounds__(256) k_roi_align(const RaArgs a)
+// The body of both ROIAlign kernels: ROI `r` (5 floats) against the map `in` [batch][channels][height][width] at `scale`, channels c0 .. c0 + RA_CH - 1 into `out`
+// (the ROI's [channels][ph][pw] run from c0 on).  Every thread of the block calls it (it holds a barrier).
+__device__ __forceinline__ void ra_block(const float* in, int batch, int channels, int height, int width, float scale, const float* r, int ph, int pw, int ratio, int c0,
+                                         float* out, RaSample* s_y, RaSample* s_x)
 {
-    __shared__ RaSample s_y[RA_TAB], s_x[RA_TAB];
     const int t = threadIdx.x;
-    const int roi = blockIdx.x / a.chunks, c0 = (blockIdx.x - roi * a.chunks) * RA_CH;
-    const int bins = a.ph * a.pw, total = min(RA_CH, a.channels - c0) * bins;
-    const float* r = a.rois + (size_t)roi * 5;
-    float* out = a.out + ((size_t)roi * a.channels + c0) * bins;
+    const int bins = ph * pw, total = min(RA_CH, channels - c0) * bins;
     const float fb = r[0];
-    if (!(fb > -1.f && fb < (float)a.batch)) {       // (int)fb outside 0 .. batch - 1: zeros, and no read of the input
+    if (!(fb > -1.f && fb < (float)batch)) {       // (int)fb outside 0 .. batch - 1: zeros, and no read of the input
         for (int o = t; o < total; o += 256) out[o] = 0.f;
         return;
     }
     const int b = (int)fb;
-    const float sw = r[1] * a.scale, sh = r[2] * a.scale, ew = r[3] * a.scale, eh = r[4] * a.scale;
+    const float sw = r[1] * scale, sh = r[2] * scale, ew = r[3] * scale, eh = r[4] * scale;
     const float dw = ew - sw, dh = eh - sh;
     const float rw = dw < 1.f ? 1.f : dw, rh = dh < 1.f ? 1.f : dh;     // std::max(d, 1): malformed ROIs are 1 x 1
-    const float bh = rh / (float)a.ph, bw = rw / (float)a.pw;
-    const int gh = a.ratio > 0 ? a.ratio : ra_grid(rh, a.ph), gw = a.ratio > 0 ? a.ratio : ra_grid(rw, a.pw);
-    const bool tab_y = (long long)a.ph * gh <= RA_TAB, tab_x = (long long)a.pw * gw <= RA_TAB;
-    if (tab_y) for (int i = t; i < a.ph * gh; i += 256) { const int p = i / gh; s_y[i] = ra_axis(sh, bh, p, i - p * gh, gh, a.height); }
-    if (tab_x) for (int i = t; i < a.pw * gw; i += 256) { const int p = i / gw; s_x[i] = ra_axis(sw, bw, p, i - p * gw, gw, a.width); }
+    const float bh = rh / (float)ph, bw = rw / (float)pw;
+    const int gh = ratio > 0 ? ratio : ra_grid(rh, ph), gw = ratio > 0 ? ratio : ra_grid(rw, pw);
+    const bool tab_y = (long long)ph * gh <= RA_TAB, tab_x = (long long)pw * gw <= RA_TAB;
+    if (tab_y) for (int i = t; i < ph * gh; i += 256) { const int p = i / gh; s_y[i] = ra_axis(sh, bh, p, i - p * gh, gh, height); }
+    if (tab_x) for (int i = t; i < pw * gw; i += 256) { const int p = i / gw; s_x[i] = ra_axis(sw, bw, p, i - p * gw, gw, width); }
     __syncthreads();
     const float count = (float)(int)((unsigned)gh * (unsigned)gw);
-    const size_t plane = (size_t)a.height * a.width;
-    const float* base = a.in + ((size_t)b * a.channels + c0) * plane;
+    const size_t plane = (size_t)height * width;
+    const float* base = in + ((size_t)b * channels + c0) * plane;
     for (int o = t; o < total; o += 256) {
-        const int c = o / bins, bin = o - c * bins, py = bin / a.pw, px = bin - py * a.pw;
+        const int c = o / bins, bin = o - c * bins, py = bin / pw, px = bin - py * pw;
         const float* img = base + (size_t)c * plane;
         float acc = 0.f;
         for (int iy = 0; iy < gh; iy++) {
-            const RaSample y = tab_y ? s_y[py * gh + iy] : ra_axis(sh, bh, py, iy, gh, a.height);
+            const RaSample y = tab_y ? s_y[py * gh + iy] : ra_axis(sh, bh, py, iy, gh, height);
             if (y.lo < 0) continue;
-            const float *r0 = img + (size_t)y.lo * a.width, *r1 = img + (size_t)y.hi * a.width;
+            const float *r0 = img + (size_t)y.lo * width, *r1 = img + (size_t)y.hi * width;
             for (int ix = 0; ix < gw; ix++) {
-                const RaSample x = tab_x ? s_x[px * gw + ix] : ra_axis(sw, bw, px, ix, gw, a.width);
+                const RaSample x = tab_x ? s_x[px * gw + ix] : ra_axis(sw, bw, px, ix, gw, width);
                 if (x.lo < 0) continue;
                 const float w1 = y.h * x.h, w2 = y.h * x.l, w3 = y.l * x.h, w4 = y.l * x.l;
                 acc += ((w1 * r0[x.lo] + w2 * r0[x.hi]) + w3 * r1[x.lo]) + w4 * r1[x.hi];
@@ -327,6 +327,61 @@ __global__ void __launch_bounds__(256) k_roi_align(const RaArgs a)
         }
         out[o] = acc / count;
     }
+}
+
+__global__ void __launch_bounds__(256) k_roi_align(const RaArgs a)
+{
+    __shared__ RaSample s_y[RA_TAB], s_x[RA_TAB];
+    const int roi = blockIdx.x / a.chunks, c0 = (blockIdx.x - roi * a.chunks) * RA_CH;
+    ra_block(a.in, a.batch, a.channels, a.height, a.width, a.scale, a.rois + (size_t)roi * 5, a.ph, a.pw, a.ratio, c0,
+             a.out + ((size_t)roi * a.channels + c0) * ((size_t)a.ph * a.pw), s_y, s_x);
+}
+
+// ifx_fpn_roi_align: the FPN Pooler in one launch.  The level table travels by value; thr[j], j = 1 .. levels - 1, is the smallest v = sqrt(area) / s0 + eps that
+// reaches level j (made on the host: fpn_thresholds), so the device needs a correctly rounded sqrt, an IEEE division, an addition and the compares.
+constexpr int FPN_MAX = 8;
+struct FpnArgs {
+    const float* in[FPN_MAX];      // per level [batch][channels][height[l]][width[l]]
+    int height[FPN_MAX], width[FPN_MAX];
+    float scale[FPN_MAX], thr[FPN_MAX];
+    const float* rois;             // [n][5]
+    float* out;                    // [n][channels][ph][pw]
+    int32_t* lev_out;              // NULL or [n]
+    int levels, batch, channels, ph, pw, ratio, chunks;
+    float s0, eps;
+};
+
+// k_roi_align's grid and body; in front of it lane 0 finds the ROI's level and LDS hands it to the block.  No level (-1): zeros, and no map is read.
+__global__ void __launch_bounds__(256) k_fpn_roi_align(const FpnArgs a)
+{
+    __shared__ RaSample s_y[RA_TAB], s_x[RA_TAB];
+    __shared__ int s_level;
+    const int t = threadIdx.x;
+    const int roi = blockIdx.x / a.chunks, c0 = (blockIdx.x - roi * a.chunks) * RA_CH;
+    const float* r = a.rois + (size_t)roi * 5;
+    float* out = a.out + ((size_t)roi * a.channels + c0) * ((size_t)a.ph * a.pw);
+    if (t == 0) {
+        int lv = 0;
+        if (a.levels > 1) {                        // one level: no mapping at all
+            const float area = (r[3] - r[1] + 1.f) * (r[4] - r[2] + 1.f);
+            const float v = sqrtf(area) / a.s0 + a.eps;
+            if (!(v >= 0.f)) lv = -1;              // a NaN or negative area, a negative v: log2 is NaN
+            else {
+#pragma unroll
+                for (int j = 1; j < FPN_MAX; j++) lv += (j < a.levels && v >= a.thr[j]) ? 1 : 0;
+            }
+        }
+        s_level = lv;
+        if (c0 == 0 && a.lev_out) a.lev_out[roi] = lv;
+    }
+    __syncthreads();
+    const int lv = __builtin_amdgcn_readfirstlane(s_level);
+    if (lv < 0) {
+        const int total = min(RA_CH, a.channels - c0) * a.ph * a.pw;
+        for (int o = t; o < total; o += 256) out[o] = 0.f;
+        return;
+    }
+    ra_block(a.in[lv], a.batch, a.channels, a.height[lv], a.width[lv], a.scale[lv], r, a.ph, a.pw, a.ratio, c0, out, s_y, s_x);
 }
 
 constexpr int NMS_MAX = 8192;          // boxes of one call: the sort's keys (64 KB) and the kept flags live in one block's LDS
@@ -1257,6 +1312,91 @@ extern "C" int ifx_roi_align_forward(ifx_t* h, const float* d_input, int batch, 
     a.scale = spatial_scale;
     StreamScope scope(h, (hipStream_t)stream);
     LAUNCH(h, "roi_align", dim3((unsigned)(n * chunks)), dim3(256), k_roi_align, a);
+    return IFX_OK;
+}
+
+// k_min of the ladder scales[l] == 2^-(k_min + l), k_min >= 0 and every entry a normal number; -1 for any other list
+static int fpn_ladder(const float* scales, int levels)
+{
+    int k = 0;
+    while (k <= 126 && scales[0] != std::ldexp(1.f, -k)) k++;
+    if (k + levels - 1 > 126) return -1;
+    for (int l = 0; l < levels; l++)
+        if (scales[l] != std::ldexp(1.f, -(k + l))) return -1;
+    return k;
+}
+
+// floor(f32(lvl0 + f32(log2(v)))) >= target, the rule's two roundings included
+static bool fpn_reaches(float v, float lvl0, float target)
+{
+    const float L = (float)std::log2((double)v);
+    const float t = lvl0 + L;
+    return std::floor(t) >= target;
+}
+
+// thr[j], j = 1 .. levels - 1: the smallest f32 v >= 0 that reaches level k_min + j, by bisection over the bit patterns 0 (-inf: reaches nothing) .. +inf
+static void fpn_thresholds(int levels, int k_min, int canonical_level, float* thr)
+{
+    thr[0] = 0.f;
+    for (int j = 1; j < levels; j++) {
+        uint32_t lo = 0u, hi = 0x7F800000u;
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            float v;
+            std::memcpy(&v, &mid, 4);
+            if (fpn_reaches(v, (float)canonical_level, (float)(k_min + j))) hi = mid; else lo = mid;
+        }
+        std::memcpy(&thr[j], &hi, 4);
+    }
+}
+
+extern "C" int ifx_fpn_level_thresholds(const float* scales, int levels, int canonical_level, float* out)
+{
+    if (!scales || !out || levels < 1 || levels > FPN_MAX) return IFX_E_INVALID;
+    const int k_min = fpn_ladder(scales, levels);
+    if (k_min < 0) return IFX_E_INVALID;
+    float thr[FPN_MAX];
+    fpn_thresholds(levels, k_min, canonical_level, thr);
+    for (int j = 1; j < levels; j++) out[j - 1] = thr[j];
+    return k_min;
+}
+
+extern "C" int ifx_fpn_roi_align(ifx_t* h, const float* const* d_features, const int32_t* heights, const int32_t* widths, const float* scales, int levels, int batch,
+                                 int channels, const float* d_rois, int n, float canonical_scale, int canonical_level, float eps, int pooled_h, int pooled_w,
+                                 int sampling_ratio, float* d_out, int32_t* d_levels, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (levels < 1 || levels > FPN_MAX) { h->err = "ifx_fpn_roi_align: levels outside 1 .. 8"; return IFX_E_INVALID; }
+    if (!d_features || !heights || !widths || !scales) { h->err = "ifx_fpn_roi_align: NULL pointer"; return IFX_E_INVALID; }
+    if (n < 0 || batch < 1 || channels < 1 || pooled_h < 1 || pooled_w < 1 || sampling_ratio < 0) {
+        h->err = "ifx_fpn_roi_align: n < 0, a size < 1 or sampling_ratio < 0"; return IFX_E_INVALID;
+    }
+    for (int l = 0; l < levels; l++)
+        if (heights[l] < 1 || widths[l] < 1) { h->err = "ifx_fpn_roi_align: n < 0, a size < 1 or sampling_ratio < 0"; return IFX_E_INVALID; }
+    const int k_min = fpn_ladder(scales, levels);
+    if (k_min < 0) { h->err = "ifx_fpn_roi_align: the scales are not 2^-k_min, 2^-(k_min + 1), ... for an integer k_min >= 0"; return IFX_E_INVALID; }
+    if (!(canonical_scale > 0.f) || !std::isfinite(canonical_scale)) { h->err = "ifx_fpn_roi_align: canonical_scale is not a positive finite number"; return IFX_E_INVALID; }
+    if (!std::isfinite(eps)) { h->err = "ifx_fpn_roi_align: eps is not finite"; return IFX_E_INVALID; }
+    if (n == 0) return IFX_OK;
+    if (!d_rois || !d_out) { h->err = "ifx_fpn_roi_align: NULL pointer"; return IFX_E_INVALID; }
+    const int chunks = cdiv(channels, RA_CH);
+    if ((int64_t)n * chunks > 0x7FFFFFFF || (int64_t)pooled_h * pooled_w > (1 << 24)) {
+        h->err = "ifx_fpn_roi_align: more than 2^31 - 1 blocks (n x ceil(channels / 64)) or more than 2^24 bins"; return IFX_E_INVALID;
+    }
+    FpnArgs a;
+    for (int l = 0; l < FPN_MAX; l++) {
+        const int s = l < levels ? l : levels - 1;     // the unused entries repeat the last level
+        if (!d_features[s]) { h->err = "ifx_fpn_roi_align: NULL pointer"; return IFX_E_INVALID; }
+        if ((int64_t)heights[s] * widths[s] > 0x7FFFFFFF) { h->err = "ifx_fpn_roi_align: more than 2^31 - 1 texels per plane"; return IFX_E_INVALID; }
+        a.in[l] = d_features[s]; a.height[l] = heights[s]; a.width[l] = widths[s]; a.scale[l] = scales[s];
+        a.thr[l] = 0.f;
+    }
+    if (levels > 1) fpn_thresholds(levels, k_min, canonical_level, a.thr);
+    a.rois = d_rois; a.out = d_out; a.lev_out = d_levels;
+    a.levels = levels; a.batch = batch; a.channels = channels; a.ph = pooled_h; a.pw = pooled_w; a.ratio = sampling_ratio; a.chunks = chunks;
+    a.s0 = canonical_scale; a.eps = eps;
+    StreamScope scope(h, (hipStream_t)stream);
+    LAUNCH(h, "fpn_roi_align", dim3((unsigned)(n * chunks)), dim3(256), k_fpn_roi_align, a);
     return IFX_OK;
 }
 

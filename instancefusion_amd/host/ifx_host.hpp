@@ -458,6 +458,20 @@ public:
         if (ifx_nms(h_, d_boxes, d_scores, d_groups, n, threshold, d_keep, d_count, stream) < 0) throw std::runtime_error(std::string("ifx_nms: ") + ifx_last_error(h_));
     }
 
+    // ---- multi-level ROI pooling: the FPN Pooler (LevelMapper, then ROIAlign on the ROI's own level) in one launch (the rule: ifx_c_api.h), under the same
+    // conditions as the two operators above.  d_features, heights, widths, scales: host arrays of `levels` entries (1 .. 8), d_features[l] the device pointer of
+    // [batch][channels][heights[l]][widths[l]], scales[l] == 2^-(k_min + l); d_rois n x 5 -> d_out [n][channels][ph][pw]; d_levels nullptr or n int32 (the level
+    // index of every ROI, -1: no level and a row of zeros).  The defaults are LevelMapper's.
+    void FpnRoiAlign(const float* const* d_features, const int32_t* heights, const int32_t* widths, const float* scales, int levels, int batch, int channels,
+                     const float* d_rois, int n, int pooled_h, int pooled_w, int sampling_ratio, float* d_out, int32_t* d_levels, void* stream,
+                     float canonical_scale = 224.f, int canonical_level = 4, float eps = 1e-6f)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::FpnRoiAlign: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_fpn_roi_align(h_, d_features, heights, widths, scales, levels, batch, channels, d_rois, n, canonical_scale, canonical_level, eps, pooled_h, pooled_w,
+                              sampling_ratio, d_out, d_levels, stream) < 0)
+            throw std::runtime_error(std::string("ifx_fpn_roi_align: ") + ifx_last_error(h_));
+    }
+
     // ---- the RPN's proposal stage of one level of one image and BoxCoder.decode (the rules: ifx_c_api.h), under the same conditions as the two operators above.
     // RpnProposals: d_objectness [A][H][W], d_regression [4A][H][W], d_anchors [H W A][4] -> d_boxes [post_nms_top_n][4], d_logits / d_index [post_nms_top_n]
     // (either may be nullptr), count in d_count[0]; zeros and -1 behind the count.  BoxDecode: d_codes [n][4k] against d_boxes [n][4] -> d_out [n][4k];
