@@ -664,6 +664,37 @@ int ifx_rpn_proposals(ifx_t* h, const float* d_objectness, const float* d_regres
                       const ifx_rpn_params* p, float* d_boxes, float* d_logits, int64_t* d_index, int32_t* d_count, void* stream);
 int ifx_box_decode(ifx_t* h, const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip,
                    int clip_w, int clip_h /* 0, 0: no clip */, float* d_out, void* stream);
+/* ---- the RPN's proposal stage over all levels of an FPN.  For a model with a feature pyramid the reference runs forward_for_single_feature_map once per level and
+ * then RPNPostProcessor.select_over_all_levels (modeling/rpn/inference.py:152-179, the branch that is not training): the levels' results concatenated in ascending
+ * level order, topk on the sigmoid, a gather.  ifx_rpn_proposals_fpn is both for ALL levels of ONE image in one call: the per-level stages run side by side in the
+ * same launches with the level as a grid dimension, the selection over the levels runs on the device, nothing is read back, and the number of enqueued operations
+ * (one memset, at most nine launches) does not depend on the number of levels.  As the operators above: f32, the caller's buffers on the caller's stream, enqueue
+ * only, no frame or map state, any handle (a sharded one too).  In numpy: tests/rpn_fpn_numpy.py, held against the reference's own RPNPostProcessor.forward through
+ * tests/golden/rpn_fpn_ref.npz.
+ *   Inputs: levels: a HOST array of n_levels entries (1 <= n_levels <= 8), each with the device pointers and A, H, W of ifx_rpn_proposals' inputs for that level;
+ *     p: the parameters shared by every level.
+ *   Per level l = 0 .. L - 1: (boxes_l, logits_l, index_l, c_l) is exactly what ifx_rpn_proposals gives for that level with p: select, decode, clip, small-box
+ *     filter, suppression, the cut at post_nms_top_n.  A level with A H W == 0 contributes nothing (c_l = 0).
+ *   Selection over the levels: the concatenation in ascending level order has T = sum c_l rows, row r of level l at position off_l + r, off_l = sum of c_l' over
+ *     l' < l.  The order: a higher LOGIT first, -0 == +0, a NaN behind every number, equal logits by ascending position -- ifx_nms's order on (logit, position).
+ *     The result is the first min(fpn_post_nms_top_n, T) rows in that order.  The reference orders by the sigmoid, which is monotone but not injective in f32, and
+ *     torch's topk does not define the order among equal values: this rule is one of the results the reference permits, fixed.
+ *   Output, F = fpn_post_nms_top_n: d_boxes [F][4], d_logits [F] (the logits; the reference's "objectness" field is their sigmoid), d_level [F] int32 (l),
+ *     d_index [F] int64 (the flat anchor index i inside its level), d_count one int32 = min(F, T), d_level_counts [n_levels] int32 (c_l).  Behind the count boxes and
+ *     logits are 0, level and index -1.  d_logits, d_level, d_index and d_level_counts may be NULL.  T == 0 writes the padding and the count 0.  There is no cap
+ *     on T.
+ *   How: a table of the levels (pointers, sizes, each level's slices of the scratch, every slice sized from the level's own min(pre_nms_top_n, n)) travels by value
+ *     in the kernel arguments.  The radix select's five kernels take the level from blockIdx.y (blocks of a level with n <= 8192 leave at once; with no such level
+ *     the memset and the five launches are skipped); one 1024-thread block per level sorts, decodes and filters; one launch computes every level's pair mask; one
+ *     block per level walks its mask up to post_nms_top_n kept rows and writes the level's kept list.  Every list is already in the rule's order, so the selection
+ *     needs no sort: a row's rank is its row number plus, per other level, the number of that level's rows in front of it (a binary search with the 64-bit key
+ *     (logit key, position)); the ranks are a permutation of 0 .. T - 1 and rank < F writes its output row.  The scratch is ifx_nms's: no allocation on a repeated
+ *     call of the same sizes.
+ *   Refusals (nothing enqueued, the handle stays usable), IFX_E_INVALID: n_levels outside 1 .. 8; fpn_post_nms_top_n outside 1 .. 8192; NULL levels, p, d_boxes
+ *     or d_count; a level with NULL inputs and n > 0; a negative A, H or W; a level with n > 2^24; everything ifx_rpn_proposals refuses in p. */
+typedef struct ifx_rpn_level { const float *objectness, *regression, *anchors; int32_t A, H, W; } ifx_rpn_level;   /* as ifx_rpn_proposals' inputs */
+int ifx_rpn_proposals_fpn(ifx_t* h, const ifx_rpn_level* levels, int n_levels, const ifx_rpn_params* p, int fpn_post_nms_top_n,
+                          float* d_boxes, float* d_logits, int32_t* d_level, int64_t* d_index, int32_t* d_count, int32_t* d_level_counts, void* stream);
 /* ---- the box head's post-processing.  Behind the box head the reference runs PostProcessor.forward with filter_results (maskrcnn_benchmark/modeling/roi_heads/
  * box_head/inference.py:43-146): a softmax, BoxCoder.decode over [R, 4 C], a clip, then a Python loop over the classes with a nonzero, two gathers and boxlist_nms
  * each, and a kthvalue on the host -- about 160 host round trips per image.  ifx_box_detections is that stage for ONE image in one call: class logits, box

@@ -59,6 +59,11 @@ class RpnParams(C.Structure):
                 ("xform_clip", C.c_float), ("image_w", C.c_int32), ("image_h", C.c_int32)]
 
 
+class RpnLevel(C.Structure):
+    """ifx_rpn_level: one level's inputs of ifx_rpn_proposals_fpn (include/ifx_c_api.h)"""
+    _fields_ = [("objectness", C.c_void_p), ("regression", C.c_void_p), ("anchors", C.c_void_p), ("A", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 class BoxDetParams(C.Structure):
     """ifx_box_det_params: the parameters of the box head's post-processing (include/ifx_c_api.h)"""
     _fields_ = [("score_thresh", C.c_float), ("nms", C.c_float), ("detections_per_img", C.c_int32), ("max_out", C.c_int32), ("weights", C.c_float * 4),
@@ -190,6 +195,7 @@ _SIGS = {
     "ifx_fpn_level_thresholds": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ifx_fpn_roi_align": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ifx_rpn_proposals": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(RpnParams), _P, _P, _P, _P, _P]),
+    "ifx_rpn_proposals_fpn": (C.c_int, [_P, C.POINTER(RpnLevel), C.c_int, C.POINTER(RpnParams), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "ifx_box_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float * 4), C.c_float, C.c_int, C.c_int, _P, _P]),
     "ifx_box_detections": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(BoxDetParams), _P, _P, _P, _P, _P, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
@@ -409,16 +415,13 @@ def _rpn_post_processor_class():
                 raise RuntimeError("rpn_post_processor: inference only (the module is in training mode)")
             out = []
             for img, per_level in enumerate(anchors):
-                boxes, scores = [], []
-                for lvl, a in enumerate(per_level):
-                    b, s, _ = self.ef.rpn_proposals(objectness[lvl][img], box_regression[lvl][img], a.bbox.contiguous(), a.size, self.pre_nms_top_n,
-                                                    self.post_nms_top_n, self.nms_thresh, self.min_size)
-                    boxes.append(b)
-                    scores.append(s)
-                boxes, scores = (boxes[0], scores[0]) if len(boxes) == 1 else (torch.cat(boxes), torch.cat(scores))
-                if len(per_level) > 1:
-                    _, top = torch.topk(scores, min(self.fpn_post_nms_top_n, int(scores.numel())), dim=0, sorted=True)
-                    boxes, scores = boxes[top], scores[top]
+                if len(per_level) == 1:
+                    boxes, scores, _ = self.ef.rpn_proposals(objectness[0][img], box_regression[0][img], per_level[0].bbox.contiguous(), per_level[0].size,
+                                                             self.pre_nms_top_n, self.post_nms_top_n, self.nms_thresh, self.min_size)
+                else:
+                    boxes, scores, _, _ = self.ef.rpn_proposals_fpn([o[img] for o in objectness], [b[img] for b in box_regression],
+                                                                    [a.bbox.contiguous() for a in per_level], per_level[0].size, self.pre_nms_top_n,
+                                                                    self.post_nms_top_n, self.nms_thresh, self.min_size, self.fpn_post_nms_top_n)
                 r = type(per_level[0])(boxes, per_level[0].size, mode="xyxy")
                 r.add_field("objectness", scores)
                 out.append(r)
@@ -430,10 +433,11 @@ def _rpn_post_processor_class():
 def rpn_post_processor(ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, fpn_post_nms_top_n=None):
     """An nn.Module that stands in for maskrcnn-benchmark's RPNPostProcessor (modeling/rpn/inference.py) at inference time: forward(anchors, objectness,
     box_regression, targets=None) with anchors a list (per image) of lists (per level) of box lists, objectness / box_regression lists (per level) of [N,A,H,W] /
-    [N,4A,H,W], makes one ElasticFusion.rpn_proposals call per level and image and returns one box list per image with the field "objectness".  The result is
-    built with the class of the anchor lists it is given -- type(anchors[0][0])(bbox, size, mode="xyxy") and add_field -- so nothing of the reference is imported.
-    Several levels: the best fpn_post_nms_top_n (default: post_nms_top_n) of an image over all its levels by torch.topk, as select_over_all_levels does when not
-    training.  Box weights are RPNPostProcessor's default (1, 1, 1, 1).  It raises in training mode."""
+    [N,4A,H,W], makes one call per image -- ElasticFusion.rpn_proposals for one level, ElasticFusion.rpn_proposals_fpn for several -- and returns one box list
+    per image with the field "objectness".  The result is built with the class of the anchor lists it is given -- type(anchors[0][0])(bbox, size, mode="xyxy")
+    and add_field -- so nothing of the reference is imported.  Several levels: the best fpn_post_nms_top_n (default: post_nms_top_n) of an image over all its
+    levels, selected on the device by the rule of include/ifx_c_api.h (select_over_all_levels when not training; equal logits by level, then by row).  Box
+    weights are RPNPostProcessor's default (1, 1, 1, 1).  It raises in training mode."""
     return _rpn_post_processor_class()(ef, pre_nms_top_n, post_nms_top_n, nms_thresh, min_size, fpn_post_nms_top_n)
 
 
@@ -719,6 +723,67 @@ class ElasticFusion:
                 return boxes, torch.sigmoid(logits), index, count
             c = int(count.item())
             return boxes[:c], torch.sigmoid(logits[:c]), index[:c]
+
+    def rpn_proposals_fpn(self, objectness, box_regression, anchors, image_size, pre_nms_top_n=1000, post_nms_top_n=1000, nms_thresh=0.7, min_size=0,
+                          fpn_post_nms_top_n=None, weights=(1, 1, 1, 1), padded=False, stream=None):
+        """ifx_rpn_proposals_fpn, all levels of one image: objectness, box_regression and anchors are lists with one entry per level, each entry shaped as
+        rpn_proposals' argument ([A,H,W] or [1,A,H,W], [4A,H,W] or [1,4A,H,W], [H*W*A,4]); image_size (width, height) -> (boxes [c,4], objectness [c], level [c]
+        int32, index [c] int64): per level what rpn_proposals gives, then the best fpn_post_nms_top_n (None: post_nms_top_n) over all levels in descending
+        objectness, torch.sigmoid of their logits, each one's level and its flat anchor index inside that level, by the rule of include/ifx_c_api.h.  One memset
+        and at most nine launches whatever the number of levels; the 4-byte read of the count is this method's only synchronisation, and padded=True returns the
+        uncut [fpn_post_nms_top_n] tensors and count [1] int32, level_counts [L] int32 (the proposals each level contributed to the selection) without it."""
+        import torch
+
+        objectness, box_regression, anchors = list(objectness), list(box_regression), list(anchors)
+        nl = len(objectness)
+        if nl == 0:
+            raise ValueError("objectness: an empty list")
+        if len(box_regression) != nl or len(anchors) != nl:
+            raise ValueError(f"{nl} levels of objectness, {len(box_regression)} of box_regression, {len(anchors)} of anchors")
+        lv = (RpnLevel * nl)()
+        for l in range(nl):
+            o, r, a = objectness[l], box_regression[l], anchors[l]
+            _ops_tensor(self, o, f"objectness[{l}]", torch.float32, "float32")
+            _ops_tensor(self, r, f"box_regression[{l}]", torch.float32, "float32")
+            _ops_tensor(self, a, f"anchors[{l}]", torch.float32, "float32")
+            if o.dim() == 4 and o.shape[0] == 1:
+                o = o[0]
+            if r.dim() == 4 and r.shape[0] == 1:
+                r = r[0]
+            if o.dim() != 3:
+                raise ValueError(f"objectness[{l}]: shape {tuple(o.shape)}, expected [A,H,W] or [1,A,H,W]")
+            A, H, W = (int(v) for v in o.shape)
+            if tuple(r.shape) != (4 * A, H, W):
+                raise ValueError(f"box_regression[{l}]: shape {tuple(r.shape)}, expected [{4 * A},{H},{W}]")
+            if tuple(a.shape) != (A * H * W, 4):
+                raise ValueError(f"anchors[{l}]: shape {tuple(a.shape)}, expected [{A * H * W},4]")
+            lv[l].objectness, lv[l].regression, lv[l].anchors = o.data_ptr() or None, r.data_ptr() or None, a.data_ptr() or None
+            lv[l].A, lv[l].H, lv[l].W = A, H, W
+        p = RpnParams()
+        p.pre_nms_top_n, p.post_nms_top_n, p.nms_thresh, p.min_size = int(pre_nms_top_n), int(post_nms_top_n), float(nms_thresh), float(min_size)
+        p.weights[:] = [float(v) for v in weights]
+        p.xform_clip = 0.0
+        p.image_w, p.image_h = int(image_size[0]), int(image_size[1])
+        F = p.post_nms_top_n if fpn_post_nms_top_n is None else int(fpn_post_nms_top_n)
+        rows = max(F, 0)
+        dev = objectness[0].device
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        with torch.cuda.stream(stream):
+            boxes = torch.empty((rows, 4), dtype=torch.float32, device=dev)
+            logits = torch.empty(rows, dtype=torch.float32, device=dev)
+            level = torch.empty(rows, dtype=torch.int32, device=dev)
+            index = torch.empty(rows, dtype=torch.int64, device=dev)
+            count = torch.empty(1, dtype=torch.int32, device=dev)
+            level_counts = torch.empty(nl, dtype=torch.int32, device=dev)
+        self._chk(self.L.ifx_rpn_proposals_fpn(self.handle, lv, nl, C.byref(p), F, C.c_void_p(boxes.data_ptr()), C.c_void_p(logits.data_ptr()),
+                                               C.c_void_p(level.data_ptr()), C.c_void_p(index.data_ptr()), C.c_void_p(count.data_ptr()),
+                                               C.c_void_p(level_counts.data_ptr()), C.c_void_p(stream.cuda_stream or None)), "ifx_rpn_proposals_fpn")
+        with torch.cuda.stream(stream):
+            if padded:
+                return boxes, torch.sigmoid(logits), level, index, count, level_counts
+            c = int(count.item())
+            return boxes[:c], torch.sigmoid(logits[:c]), level[:c], index[:c]
 
     def box_decode(self, codes, boxes, weights=(1, 1, 1, 1), clip_to=None, out=None, stream=None):
         """ifx_box_decode: codes [n,4k] float32 against boxes [n,4] float32 -> [n,4k] float32, BoxCoder.decode by the rule of include/ifx_c_api.h (k = 81 and

@@ -679,8 +679,9 @@ __device__ __forceinline__ void rpn_pick(const uint32_t* hist, uint32_t rank, ui
 }
 
 // state[2p], state[2p + 1], p = 1 .. 3: the key's leading bits fixed by the first p passes and the rank among the keys that share them
+// (the bodies of the selection's kernels are device functions of one 256-thread block: the single-level kernels and the level-batched ones further down call them)
 template <int PASS>
-__global__ void __launch_bounds__(256) k_rpn_hist(const float* obj, int n, uint32_t K, uint32_t* hist, uint32_t* state)
+__device__ __forceinline__ void rpn_hist_block(const float* obj, int n, uint32_t K, uint32_t* hist, uint32_t* state)
 {
     __shared__ uint32_t s_hist[RPN_BINS];
     __shared__ uint32_t s_w[4], s_out[2];
@@ -709,6 +710,12 @@ __global__ void __launch_bounds__(256) k_rpn_hist(const float* obj, int n, uint3
     for (int i = t; i < RPN_BINS; i += 256) { const uint32_t v = s_hist[i]; if (v) atomicAdd(&hist[PASS * RPN_BINS + i], v); }
 }
 
+template <int PASS>
+__global__ void __launch_bounds__(256) k_rpn_hist(const float* obj, int n, uint32_t K, uint32_t* hist, uint32_t* state)
+{
+    rpn_hist_block<PASS>(obj, n, K, hist, state);
+}
+
 // a thread's eight consecutive anchor indices against T: bit k of less / equal
 __device__ __forceinline__ uint2 rpn_classify(const float* obj, int n, int A, int HW, int first, uint32_t T)
 {
@@ -726,7 +733,7 @@ __device__ __forceinline__ uint2 rpn_classify(const float* obj, int n, int A, in
 }
 
 // blk[b], blk[nblk + b]: how many keys of block b's 2048 anchor indices lie in front of T and on T
-__global__ void __launch_bounds__(256) k_rpn_count(const float* obj, int n, int A, int HW, const uint32_t* hist, uint32_t* state, uint32_t* blk, int nblk)
+__device__ __forceinline__ void rpn_count_block(const float* obj, int n, int A, int HW, const uint32_t* hist, uint32_t* state, uint32_t* blk, int nblk)
 {
     __shared__ uint32_t s_w[4], s_out[2], s_sum[2];
     const int t = threadIdx.x;
@@ -741,6 +748,11 @@ __global__ void __launch_bounds__(256) k_rpn_count(const float* obj, int n, int 
     if (equal) atomicAdd(&s_sum[1], (uint32_t)__popc(equal));
     __syncthreads();
     if (t < 2) blk[t * nblk + blockIdx.x] = s_sum[t];
+}
+
+__global__ void __launch_bounds__(256) k_rpn_count(const float* obj, int n, int A, int HW, const uint32_t* hist, uint32_t* state, uint32_t* blk, int nblk)
+{
+    rpn_count_block(obj, n, A, HW, hist, state, blk, nblk);
 }
 
 // M lists of per-block counts, `stride` apart: the sums of list m's blk[0 .. b) into s_sum[m], for a 256-thread block.  They are complete behind the caller's next
@@ -759,8 +771,8 @@ __device__ __forceinline__ void block_sum_before(const uint32_t* blk, int stride
 }
 
 // cand[0 .. K): the winners' 64-bit keys -- those in front of T in index order, then the first state[7] + 1 of those on T in index order
-__global__ void __launch_bounds__(256) k_rpn_compact(const float* obj, int n, int A, int HW, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk,
-                                                      unsigned long long* cand)
+__device__ __forceinline__ void rpn_compact_block(const float* obj, int n, int A, int HW, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk,
+                                                  unsigned long long* cand)
 {
     __shared__ uint32_t s_before[2], s_w[4];
     const int t = threadIdx.x, b = blockIdx.x;
@@ -780,6 +792,12 @@ __global__ void __launch_bounds__(256) k_rpn_compact(const float* obj, int n, in
     }
 }
 
+__global__ void __launch_bounds__(256) k_rpn_compact(const float* obj, int n, int A, int HW, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk,
+                                                      unsigned long long* cand)
+{
+    rpn_compact_block(obj, n, A, HW, K, state, blk, nblk, cand);
+}
+
 struct RpnArgs {
     const float *obj, *reg, *anc;                      // [A][H][W], [4A][H][W], [H W A][4]
     const unsigned long long* cand;                    // the selection's winners, NULL: every anchor is a candidate (n <= 8192)
@@ -791,7 +809,7 @@ struct RpnArgs {
 
 // One block: the candidates into the order (k_nms_sort's network), then per thread eight consecutive candidates: the code and the anchor gathered through the
 // [A][H][W] indexing, decode, clip, the small-box test; a block scan keeps the survivors in the candidates' order.  They are the sorted boxes the pair mask reads.
-__global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
+__device__ __forceinline__ void rpn_sort_decode_block(const RpnArgs& a)
 {
     __shared__ unsigned long long s_key[NMS_MAX];
     const int t = threadIdx.x;
@@ -831,10 +849,15 @@ __global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
     if (t == 0) a.ns[0] = total;
 }
 
+__global__ void __launch_bounds__(1024) k_rpn_sort_decode(const RpnArgs a)
+{
+    rpn_sort_decode_block(a);
+}
+
 // k_nms_reduce's walk, stopped once `post` boxes are kept, and the output in the candidates' order: the first min(kept, post) kept rows with box, logit and index;
 // zeros and -1 behind them up to post; the count
-__global__ void __launch_bounds__(1024) k_rpn_reduce(const unsigned long long* mask, const float4* sboxes, const float* slogit, const int32_t* sindex, const int32_t* ns, int nb,
-                                                     int post, float* boxes, float* logits, long long* index, int32_t* count)
+__device__ __forceinline__ void rpn_reduce_block(const unsigned long long* mask, const float4* sboxes, const float* slogit, const int32_t* sindex, const int32_t* ns, int nb,
+                                                 int post, float* boxes, float* logits, long long* index, int32_t* count)
 {
     __shared__ NmsWalk s;
     const int t = threadIdx.x, n = ns[0];
@@ -860,6 +883,152 @@ __global__ void __launch_bounds__(1024) k_rpn_reduce(const unsigned long long* m
         if (index) index[i] = -1;
     }
     if (t == 0) count[0] = total;
+}
+
+__global__ void __launch_bounds__(1024) k_rpn_reduce(const unsigned long long* mask, const float4* sboxes, const float* slogit, const int32_t* sindex, const int32_t* ns, int nb,
+                                                     int post, float* boxes, float* logits, long long* index, int32_t* count)
+{
+    rpn_reduce_block(mask, sboxes, slogit, sindex, ns, nb, post, boxes, logits, index, count);
+}
+
+// ---- the proposal stage over all levels of an FPN in one call: ifx_rpn_proposals_fpn (the rule: include/ifx_c_api.h, in numpy: tests/rpn_fpn_numpy.py).  The
+// kernels above run per level side by side -- the level is a grid dimension, every block takes its level's entry of a table that travels in the kernel arguments
+// -- and one more kernel merges the levels' kept lists (RPNPostProcessor.select_over_all_levels, inference.py:152-179).  The number of launches does not depend on
+// the number of levels.
+constexpr int RPN_MAX_LEVELS = 8;
+constexpr size_t RPN_ZERO_WORDS = 3 * RPN_BINS + 8;    // of a level that selects: the three histograms and the selection's state
+
+struct RpnLevel {
+    const float *obj, *reg, *anc;                      // as RpnArgs
+    int n, A, HW, m, P, nb;                            // nb: the 64-box blocks of the level's mask, m rounded up
+    int nblk;                                          // 2048-key blocks of the selection, 0: n <= 8192, the level does not select
+    int cap;                                           // min(post_nms_top_n, m): the rows of the kept lists
+    unsigned long long *cand, *mask;                   // the level's slices of the scratch, each sized from its own m
+    float4* sboxes; float* slogit; int32_t* sindex;
+    uint32_t *blk, *hist;                              // hist: histograms and state, zeroed per call (NULL: the level does not select)
+    float *kbox, *klogit; long long* kindex;           // the kept rows in the level's order: what ifx_rpn_proposals writes for the level, cap rows
+};
+
+struct RpnFpn {
+    RpnLevel lv[RPN_MAX_LEVELS];
+    int32_t *ns, *cnt;                                 // per level: the survivors in front of the suppression, and c_l
+    int L;
+};
+
+// the selection's five kernels, blockIdx.y = the level, gridDim.x = the largest nblk: a block of a level that does not select, or behind its level's blocks,
+// leaves before the first barrier (block-uniform)
+template <int PASS>
+__global__ void __launch_bounds__(256) k_rpn_fpn_hist(const RpnFpn f)
+{
+    const RpnLevel& v = f.lv[blockIdx.y];
+    if ((int)blockIdx.x >= v.nblk) return;
+    rpn_hist_block<PASS>(v.obj, v.n, (uint32_t)v.m, v.hist, v.hist + 3 * RPN_BINS);
+}
+
+__global__ void __launch_bounds__(256) k_rpn_fpn_count(const RpnFpn f)
+{
+    const RpnLevel& v = f.lv[blockIdx.y];
+    if ((int)blockIdx.x >= v.nblk) return;
+    rpn_count_block(v.obj, v.n, v.A, v.HW, v.hist, v.hist + 3 * RPN_BINS, v.blk, v.nblk);
+}
+
+__global__ void __launch_bounds__(256) k_rpn_fpn_compact(const RpnFpn f)
+{
+    const RpnLevel& v = f.lv[blockIdx.y];
+    if ((int)blockIdx.x >= v.nblk) return;
+    rpn_compact_block(v.obj, v.n, v.A, v.HW, (uint32_t)v.m, v.hist + 3 * RPN_BINS, v.blk, v.nblk, v.cand);
+}
+
+// one block per level: k_rpn_sort_decode on the level's entry (a level without anchors sorts two padding keys and counts no survivor)
+__global__ void __launch_bounds__(1024) k_rpn_fpn_sort_decode(const RpnFpn f, const BoxCode q, float min_size)
+{
+    const RpnLevel& v = f.lv[blockIdx.x];
+    RpnArgs a;
+    a.obj = v.obj; a.reg = v.reg; a.anc = v.anc; a.cand = v.nblk ? v.cand : nullptr;
+    a.n = v.n; a.A = v.A; a.HW = v.HW; a.m = v.m; a.P = v.P;
+    a.q = q; a.min_size = min_size;
+    a.sboxes = v.sboxes; a.slogit = v.slogit; a.sindex = v.sindex; a.ns = f.ns + blockIdx.x;
+    rpn_sort_decode_block(a);
+}
+
+// grid (largest nb, largest nb, levels): k_nms_mask_dev per level; a tile beyond its level's blocks or survivors leaves
+__global__ void __launch_bounds__(64) k_rpn_fpn_mask(const RpnFpn f, float thr)
+{
+    const RpnLevel& v = f.lv[blockIdx.z];
+    const int n = f.ns[blockIdx.z];
+    if ((int)blockIdx.x >= v.nb || (int)blockIdx.y >= v.nb || (int)blockIdx.x * 64 >= n) return;
+    nms_mask_tile(v.sboxes, nullptr, n, v.nb, thr, v.mask);
+}
+
+// one block per level: k_rpn_reduce into the level's kept lists, c_l into cnt
+__global__ void __launch_bounds__(1024) k_rpn_fpn_reduce(const RpnFpn f)
+{
+    const int l = blockIdx.x;
+    const RpnLevel& v = f.lv[l];
+    rpn_reduce_block(v.mask, v.sboxes, v.slogit, v.sindex, f.ns + l, v.nb, v.cap, v.kbox, v.klogit, v.kindex, f.cnt + l);
+}
+
+// The selection over the levels.  Every level's list is in the rule's order already: row r of level l, at position off_l + r of the concatenation, has the 64-bit
+// key (k32 of its logit, off_l + r), a total order in which each list ascends.  Its rank is r plus, for every other level, the number of that level's rows with a
+// smaller key: one binary search per other level, no sort, no atomics, no LDS.  The ranks are a permutation of 0 .. T - 1; rank < F writes output row rank.
+// One thread per row of the lists' capacity (and per output row: rows T .. F - 1 are the padding); thread 0 writes the counts.
+__global__ void __launch_bounds__(256) k_rpn_fpn_merge(const RpnFpn f, int F, float* boxes, float* logits, int32_t* level, long long* index, int32_t* count,
+                                                       int32_t* level_counts)
+{
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    int mine = -1, r = 0, T = 0, capoff = 0;
+    unsigned long long key = 0;
+    float lg = 0.f;
+    const float* kbox = nullptr;
+    const long long* kindex = nullptr;
+#pragma unroll
+    for (int l = 0; l < RPN_MAX_LEVELS; l++) {
+        if (l >= f.L) break;
+        const int c = f.cnt[l], cap = f.lv[l].cap;
+        if (g >= capoff && g - capoff < c) {           // (c <= cap: the row lies in level l's list)
+            mine = l; r = g - capoff;
+            lg = f.lv[l].klogit[r];
+            key = ((unsigned long long)rpn_key32(lg) << 32) | (uint32_t)(T + r);
+            kbox = f.lv[l].kbox; kindex = f.lv[l].kindex;
+        }
+        capoff += cap; T += c;
+    }
+    if (mine >= 0) {
+        int rank = r, off = 0;
+#pragma unroll
+        for (int l = 0; l < RPN_MAX_LEVELS; l++) {
+            if (l >= f.L) break;
+            const int c = f.cnt[l];
+            if (l != mine) {
+                const float* kl = f.lv[l].klogit;
+                int lo = 0, hi = c;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    const unsigned long long k = ((unsigned long long)rpn_key32(kl[mid]) << 32) | (uint32_t)(off + mid);
+                    if (k < key) lo = mid + 1; else hi = mid;
+                }
+                rank += lo;
+            }
+            off += c;
+        }
+        if (rank < F) {
+            boxes[4 * rank] = kbox[4 * r]; boxes[4 * rank + 1] = kbox[4 * r + 1]; boxes[4 * rank + 2] = kbox[4 * r + 2]; boxes[4 * rank + 3] = kbox[4 * r + 3];
+            if (logits) logits[rank] = lg;
+            if (level) level[rank] = mine;
+            if (index) index[rank] = kindex[r];
+        }
+    }
+    if (g >= T && g < F) {
+        boxes[4 * g] = 0.f; boxes[4 * g + 1] = 0.f; boxes[4 * g + 2] = 0.f; boxes[4 * g + 3] = 0.f;
+        if (logits) logits[g] = 0.f;
+        if (level) level[g] = -1;
+        if (index) index[g] = -1;
+    }
+    if (g == 0) {
+        count[0] = min(T, F);
+        if (level_counts)
+            for (int l = 0; l < f.L; l++) level_counts[l] = f.cnt[l];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------------
@@ -1177,6 +1346,71 @@ int rpn_run(ifx* h, const float* d_obj, const float* d_reg, const float* d_anc, 
     return ops_done(h, ops, stream);
 }
 
+// The proposal stage over the levels: one memset and nine launches whatever the number of levels (no level selects: four launches).  Scratch: per level the slices
+// rpn_run takes, each sized from the level's own m, and the level's kept lists; behind them ns and c_l of all levels, and -- ONE take, zeroed by one memset per
+// call -- the histograms and the state of the levels that select.
+int rpn_fpn_run(ifx* h, const ifx_rpn_level* levels, int n_levels, const ifx_rpn_params* p, const BoxCode& q, int F, float* d_boxes, float* d_logits, int32_t* d_level,
+                int64_t* d_index, int32_t* d_count, int32_t* d_level_counts, hipStream_t stream)
+{
+    RpnFpn f = {};
+    f.L = n_levels;
+    int nsel = 0, nblk_max = 0, nb_max = 1, rows = 0;
+    for (int l = 0; l < n_levels; l++) {
+        RpnLevel& v = f.lv[l];
+        v.obj = levels[l].objectness; v.reg = levels[l].regression; v.anc = levels[l].anchors;
+        v.A = levels[l].A; v.HW = levels[l].H * levels[l].W; v.n = v.A * v.HW;
+        v.m = std::min(p->pre_nms_top_n, v.n);
+        v.nb = cdiv(v.m, 64);
+        v.nblk = v.n > NMS_MAX ? cdiv(v.n, RPN_CHUNK) : 0;
+        v.cap = std::min(p->post_nms_top_n, v.m);
+        v.P = 2;
+        while (v.P < (v.nblk ? v.m : v.n)) v.P <<= 1;
+        nsel += v.nblk > 0;
+        nblk_max = std::max(nblk_max, v.nblk);
+        nb_max = std::max(nb_max, v.nb);
+        rows += v.cap;
+    }
+    uint32_t* zero = nullptr;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, "ifx_rpn_proposals_fpn", [&](Carver& c) {
+        for (int l = 0; l < n_levels; l++) {
+            RpnLevel& v = f.lv[l];
+            const size_t mc = (size_t)v.nb * 64;
+            v.sboxes = c.take<float4>(mc);
+            v.mask = c.take<unsigned long long>(mc * v.nb);
+            v.cand = c.take<unsigned long long>(mc);
+            v.slogit = c.take<float>(mc);
+            v.sindex = c.take<int32_t>(mc);
+            v.blk = c.take<uint32_t>(2 * (size_t)v.nblk);
+            v.kbox = c.take<float>(4 * (size_t)v.cap);
+            v.klogit = c.take<float>(v.cap);
+            v.kindex = c.take<long long>(v.cap);
+        }
+        f.ns = c.take<int32_t>(2 * RPN_MAX_LEVELS);
+        f.cnt = f.ns + RPN_MAX_LEVELS;
+        zero = c.take<uint32_t>(nsel * RPN_ZERO_WORDS); // one take: one memset zeroes every selecting level's histograms and state
+        for (int l = 0, s = 0; l < n_levels; l++) f.lv[l].hist = zero && f.lv[l].nblk ? zero + (s++) * RPN_ZERO_WORDS : nullptr;
+    }, stream, &ops);
+    if (r) return r;
+    StreamScope scope(h, stream);
+    const unsigned L = (unsigned)n_levels;
+    if (nsel) {
+        HIPCHK(h, hipMemsetAsync(zero, 0, nsel * RPN_ZERO_WORDS * 4, stream));
+        const dim3 grid((unsigned)nblk_max, L);
+        LAUNCH(h, "rpn_fpn_hist", grid, dim3(256), k_rpn_fpn_hist<0>, f);
+        LAUNCH(h, "rpn_fpn_hist", grid, dim3(256), k_rpn_fpn_hist<1>, f);
+        LAUNCH(h, "rpn_fpn_hist", grid, dim3(256), k_rpn_fpn_hist<2>, f);
+        LAUNCH(h, "rpn_fpn_count", grid, dim3(256), k_rpn_fpn_count, f);
+        LAUNCH(h, "rpn_fpn_compact", grid, dim3(256), k_rpn_fpn_compact, f);
+    }
+    LAUNCH(h, "rpn_fpn_sort_decode", dim3(L), dim3(1024), k_rpn_fpn_sort_decode, f, q, p->min_size);
+    LAUNCH(h, "rpn_fpn_mask", dim3((unsigned)nb_max, (unsigned)nb_max, L), dim3(64), k_rpn_fpn_mask, f, p->nms_thresh);
+    LAUNCH(h, "rpn_fpn_reduce", dim3(L), dim3(1024), k_rpn_fpn_reduce, f);
+    LAUNCH(h, "rpn_fpn_merge", dim3((unsigned)cdiv(std::max(rows, F), 256)), dim3(256), k_rpn_fpn_merge, f, F, d_boxes, d_logits, d_level, (long long*)d_index, d_count,
+           d_level_counts);
+    return ops_done(h, ops, stream);
+}
+
 // The box head's post-processing: six launches.  Scratch, out of the handle's buffer: sorted boxes, mask words, then the 4-byte arrays --
 // the plane of probabilities, the candidates' plane positions, the sorted groups / scores / candidate positions / rows, the per-block counts and K.  Every word a
 // kernel reads is written by a kernel in front of it in the same call: nothing is zeroed.
@@ -1427,6 +1661,30 @@ extern "C" int ifx_rpn_proposals(ifx_t* h, const float* d_objectness, const floa
     if (n > 0 && (!d_objectness || !d_regression || !d_anchors)) { h->err = "ifx_rpn_proposals: NULL pointer"; return IFX_E_INVALID; }
     if (n == 0) return ops_padding(h, (size_t)p->post_nms_top_n, d_boxes, d_logits, d_index, nullptr, d_count, (hipStream_t)stream);   // no anchors
     return rpn_run(h, d_objectness, d_regression, d_anchors, A, H * W, p, q, d_boxes, d_logits, d_index, d_count, (hipStream_t)stream);
+}
+
+extern "C" int ifx_rpn_proposals_fpn(ifx_t* h, const ifx_rpn_level* levels, int n_levels, const ifx_rpn_params* p, int fpn_post_nms_top_n, float* d_boxes, float* d_logits,
+                                     int32_t* d_level, int64_t* d_index, int32_t* d_count, int32_t* d_level_counts, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!levels || !p || !d_boxes || !d_count) { h->err = "ifx_rpn_proposals_fpn: NULL pointer"; return IFX_E_INVALID; }
+    if (n_levels < 1 || n_levels > RPN_MAX_LEVELS) { h->err = "ifx_rpn_proposals_fpn: n_levels outside 1 .. 8"; return IFX_E_INVALID; }
+    if (fpn_post_nms_top_n < 1 || fpn_post_nms_top_n > NMS_MAX) { h->err = "ifx_rpn_proposals_fpn: fpn_post_nms_top_n outside 1 .. 8192"; return IFX_E_INVALID; }
+    if (p->pre_nms_top_n < 1 || p->pre_nms_top_n > NMS_MAX || p->post_nms_top_n < 1 || p->post_nms_top_n > NMS_MAX) {
+        h->err = "ifx_rpn_proposals_fpn: pre_nms_top_n or post_nms_top_n outside 1 .. 8192"; return IFX_E_INVALID;
+    }
+    if (p->nms_thresh != p->nms_thresh) { h->err = "ifx_rpn_proposals_fpn: the threshold is NaN"; return IFX_E_INVALID; }
+    if (p->image_w < 1 || p->image_h < 1) { h->err = "ifx_rpn_proposals_fpn: image_w or image_h < 1"; return IFX_E_INVALID; }
+    BoxCode q;
+    if (const char* bad = box_code(p->weights, p->xform_clip, p->image_w, p->image_h, &q)) { h->err = std::string("ifx_rpn_proposals_fpn: ") + bad; return IFX_E_INVALID; }
+    for (int l = 0; l < n_levels; l++) {
+        const ifx_rpn_level& v = levels[l];
+        if (v.A < 0 || v.H < 0 || v.W < 0 || (int64_t)v.A * v.H * v.W > RPN_MAX_N || (int64_t)v.H * v.W > RPN_MAX_N) {
+            h->err = "ifx_rpn_proposals_fpn: a level with a size < 0 or A x H x W above 2^24"; return IFX_E_INVALID;
+        }
+        if (v.A && v.H && v.W && (!v.objectness || !v.regression || !v.anchors)) { h->err = "ifx_rpn_proposals_fpn: NULL pointer in a level with anchors"; return IFX_E_INVALID; }
+    }
+    return rpn_fpn_run(h, levels, n_levels, p, q, fpn_post_nms_top_n, d_boxes, d_logits, d_level, d_index, d_count, d_level_counts, (hipStream_t)stream);
 }
 
 extern "C" int ifx_box_decode(ifx_t* h, const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip, int clip_w, int clip_h,

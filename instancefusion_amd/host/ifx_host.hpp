@@ -483,6 +483,16 @@ public:
         if (ifx_rpn_proposals(h_, d_objectness, d_regression, d_anchors, A, H, W, &p, d_boxes, d_logits, d_index, d_count, stream) < 0)
             throw std::runtime_error(std::string("ifx_rpn_proposals: ") + ifx_last_error(h_));
     }
+    // RpnProposalsFpn: the proposal stage over all levels of one image and the selection over the levels (the rule: ifx_c_api.h).  levels: a host array of
+    // n_levels entries -> d_boxes [F][4], d_logits / d_level / d_index [F], d_level_counts [n_levels] (each may be nullptr), F = fpn_post_nms_top_n, the count in
+    // d_count[0]; zeros and -1 behind the count.  Enqueue only.
+    void RpnProposalsFpn(const ifx_rpn_level* levels, int n_levels, const ifx_rpn_params& p, int fpn_post_nms_top_n, float* d_boxes, float* d_logits, int32_t* d_level,
+                         int64_t* d_index, int32_t* d_count, int32_t* d_level_counts, void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::RpnProposalsFpn: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_rpn_proposals_fpn(h_, levels, n_levels, &p, fpn_post_nms_top_n, d_boxes, d_logits, d_level, d_index, d_count, d_level_counts, stream) < 0)
+            throw std::runtime_error(std::string("ifx_rpn_proposals_fpn: ") + ifx_last_error(h_));
+    }
     void BoxDecode(const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip, int clip_w, int clip_h, float* d_out, void* stream)
     {
         if (!h_) throw std::runtime_error(std::string("ElasticFusion::BoxDecode: the map has no handle (") + ifx_global_error() + ")");
