@@ -369,6 +369,8 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           most "gn_persist_blocks" blocks (default 128).  Default 0 below 1280x960 (the two-launch form with the solve in the next launch's
  *                           prologue is within 0.7 % there and needs no co-resident grid), 4 = the coarsest level from 1280x960 on (+5 %).  A meeting of its
  *                           blocks that does not happen is re-run by one workgroup inside the frame (ifx_tracker_fallbacks counts them): slower, never wrong.
+ *   "rgb_cand" 0          -- the photometric term of the frame-to-model tracker over every pixel (the dense passes) instead of over the frame slot's candidate
+ *                           list; same bits.  A run with a persistent level ("gn_persist") or row-sharded reductions is dense whatever the option says
  *   "gn_prologue" 0       -- the 6x6 solve of an iteration by the last block of its second launch (round 3's form) instead of by every block of the next
  *                           iteration's first launch; "gn_prologue_blocks" n -- the prologue form only for launches of at most n blocks (default 2048)
  *   "fold_result" 0       -- the frame result by a launch of its own instead of the last block of the prediction's resolve
@@ -459,7 +461,9 @@ int ifx_track_pair(ifx_t* h, const float* model_v4, const float* model_n4, const
                    float* pose16_inout, float* diag8);
 /* Host copy of a tracker pyramid buffer; names as in the reference's members
  * (EF/Utils/RGBDOdometry.h:80-121): "vmap_curr","nmap_curr","vmap_prev","nmap_prev","last_depth",
- * "last_img","next_img","lastnext_img","didx","didy","cloud","corres","depth_tmp". */
+ * "last_img","next_img","lastnext_img","didx","didy","cloud","corres","depth_tmp"; and of the bound frame slot "cand_n" (4 bytes: the number of candidate
+ * pixels of the photometric term at this level) and "cand" (w * h entries of 8 bytes {uint32 pixel, int16 gx, int16 gy}, the first cand_n valid, in no
+ * particular order; with option "rgb_cand" the frame-to-model tracker's "corres" holds record t for entry t). */
 int ifx_tracker_buffer_download(ifx_t* h, const char* name, int level, void* out, int64_t max_bytes);
 
 /* ---- instance layer (replaces InstanceFusion::whetherDoSegmentation / ProcessSegmentation /

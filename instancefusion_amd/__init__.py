@@ -262,6 +262,7 @@ _TRK_SPECS = {
     "depth_tmp": (np.uint16, 1, False),
 }
 CORRES_DTYPE = np.dtype([("zx", np.int16), ("zy", np.int16), ("diff", np.float32)])
+CAND_DTYPE = np.dtype([("pixel", np.uint32), ("gx", np.int16), ("gy", np.int16)])   # an entry of a frame slot's candidate list (ifx_ctx.h CandEntry)
 
 
 # mask formats of ifx_process_segmentation_device (include/ifx_c_api.h)
@@ -1174,6 +1175,12 @@ class ElasticFusion:
         w, h = self.w >> level, self.h >> level
         if name == "corres":
             a = np.zeros((h, w), CORRES_DTYPE)
+        elif name == "cand_n":     # number of valid entries of the bound frame slot's candidate list at this level
+            a = np.zeros(1, np.uint32)
+        elif name == "cand":       # the valid entries, in the order the device appended them (none in particular)
+            a = np.zeros(h * w, CAND_DTYPE)
+            self._chk(self.L.ifx_tracker_buffer_download(self.handle, name.encode(), level, _ptr(a), a.nbytes), "ifx_tracker_buffer_download")
+            return a[: int(self._tracker_buffer("cand_n", level)[0])].copy()
         else:
             dt, ch, planar = _TRK_SPECS[name]
             a = np.zeros((ch, h, w) if planar else ((h, w, ch) if ch > 1 else (h, w)), dt)

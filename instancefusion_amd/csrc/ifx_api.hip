@@ -398,6 +398,9 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
         HIPCHK(h, hipMemcpy((char*)h->d_state + (s == "gn_fault" ? offsetof(DevState, gn_fault) : offsetof(DevState, gn_spin_limit)), &value, sizeof(int), hipMemcpyHostToDevice));
     }
     else if (s == "gn_prologue") { ifx_drop_tracked(h); h->opt_gn_prologue = value ? 1 : 0; }
+    // the photometric term of the frame-to-model tracker over the frame slot's candidate list (1, default) or over every pixel (0: the dense bodies, bit for bit as they
+    // were).  Where a dense form and the list form would share `corres` within one run -- a persistent level (gn_persist), own_track_rows -- the dense one wins for that run.
+    else if (s == "rgb_cand") { ifx_drop_tracked(h); h->opt_rgb_cand = value ? 1 : 0; }
     else if (s == "raster_lds") h->opt_raster_lds = value;
     else if (s == "raster_earlyz") h->opt_raster_earlyz = value;
     // ElasticFusion::setPyramid / setFastOdom / setSo3 / setIcpWeight (EF/ElasticFusion.h:153-176): tracker configuration from the next frame on;

@@ -157,6 +157,11 @@ __device__ __forceinline__ void frame_result_wave(DevState* st, FrameResult* out
     out->gn_timeout = st->gn_timeout;
 }
 
+// One pixel that passes the pose-independent part of the photometric residual's gate (16-pixel border, 4x4 block of the frame's intensity image non-zero, gradient
+// magnitude against the level's minimum): its index in the level's image and its two Sobel values.  k_frame_maps appends them once per frame, in no particular order.
+struct CandEntry { uint32_t pixel; int16_t gx, gy; };
+static_assert(sizeof(CandEntry) == 8, "CandEntry is one 8-byte load");
+
 struct Pyr {
     int w[IFX_NUM_PYRS], h[IFX_NUM_PYRS];
     uint16_t* depth_tmp[IFX_NUM_PYRS];
@@ -171,8 +176,10 @@ struct Pyr {
     unsigned int* ticket = nullptr;                           // [0] last-block ticket of k_rgb_step_solve, [8..9] residual totals
     uint8_t *last_img[IFX_NUM_PYRS], *next_img[IFX_NUM_PYRS], *lastnext_img[IFX_NUM_PYRS];
     int16_t *didx[IFX_NUM_PYRS], *didy[IFX_NUM_PYRS];
+    CandEntry* cand[IFX_NUM_PYRS] = {};                       // the bound frame slot's candidate pixels of the photometric term and their count (FrameSlot::cand); nullptr in the
+    unsigned int* cand_n[IFX_NUM_PYRS] = {};                  // model-to-model instance, whose frame side is a render: it keeps the dense passes
     float* cloud[IFX_NUM_PYRS];
-    void* corres[IFX_NUM_PYRS];                               // 8 B per pixel: short zx, zy; float diff
+    void* corres[IFX_NUM_PYRS];                               // 8 B per pixel: short zx, zy; float diff (option rgb_cand: per candidate, record t belongs to cand[t])
 };
 
 // Everything that depends only on the input frame (the "frame side" of a frame): copies of the images, the
@@ -187,6 +194,8 @@ struct FrameSlot {
     float *vmap_curr[IFX_NUM_PYRS] = {}, *nmap_curr[IFX_NUM_PYRS] = {};
     uint8_t* next_img[IFX_NUM_PYRS] = {};
     int16_t *didx[IFX_NUM_PYRS] = {}, *didy[IFX_NUM_PYRS] = {};
+    CandEntry* cand[IFX_NUM_PYRS] = {};       // candidate pixels of the photometric term, capacity w_l * h_l, written with didx / didy by k_frame_maps
+    unsigned int* cand_n[IFX_NUM_PYRS] = {};  // their count, on the device only (one allocation of IFX_NUM_PYRS words 64 bytes apart, owned by level 0)
     DevState* so3 = nullptr;          // shadow state: only the SO(3) fields are used
     hipEvent_t ready = nullptr;       // recorded on the side stream when the slot is complete
     hipEvent_t released = nullptr;    // recorded on the main stream when the frame that used the slot is done
@@ -375,7 +384,10 @@ struct ifx {
     int opt_raster_lds = 0;          // view raster: per-wave depth test in LDS before the global atomics (k_raster_view<true>)
     int opt_view_blocks = 0, opt_clean_blocks = 0, opt_index_blocks = 0;   // grids of the view-list kernels (0: LIST_BLOCKS)
     int icp_resident_blocks = 1024;   // blocks of k_icp_residual the GPU holds at once (occupancy query at tracker allocation: 4 per CU x 256 CUs on MI355X)
-    int opt_res_blocks = 0;          // cap on the blocks of the residual half of k_icp_residual (0: one block per 256 pixels)
+    int opt_res_blocks = 0;          // cap on the blocks of the residual half of k_icp_residual (0: one block per 256 pixels; over the candidate list: rgb_cand_blocks())
+    int opt_rgb_cand = 1;            // frame-to-model tracker, two-launch form: the residual pass and the photometric step run over the frame slot's candidate list (FrameSlot::cand) and
+                                     // the level's `corres` holds one record per candidate.  0: the dense bodies, bit for bit what they were.  A run in which a dense form would
+                                     // share `corres` with the list form (a persistent level: gn_persist; the row-sharded reductions: own_track_rows) is dense as a whole
     int opt_icp_blocks = 0;          // cap on the blocks of a tracker reduction launch; 0 = by image size (ifx_track.hip red_blocks)
     int opt_raster_tiles = -1;       // tiled rasteriser (k_tile_*: key tiles resolved in LDS) instead of global atomics: 0 off, 1 on, -1 by image size (on from 1 Mpixel:
                                      // at 640x480 / 5M surfels the binning passes cost what the LDS tiles save, at 1280x960 / 20M the frame rate gains 12 %)

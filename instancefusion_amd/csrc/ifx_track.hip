@@ -178,9 +178,12 @@ __global__ void k_pyrdown_gauss_u8(const uint8_t* __restrict__ src, int sw, int 
 // ---- frame side in 4 launches (was 12): intensity of level 0; one launch per coarser level for BOTH pyr-downs (depth: the
 // bilateral-like pyrDownGaussKernel, intensity: the 5x5 Gaussian); one launch for the vertex/normal maps and the Sobel
 // gradients of all three levels (each needs its level's complete depth / intensity image, nothing of another level).
-__global__ void k_frame_down(const uint16_t* __restrict__ dsrc, const uint8_t* __restrict__ isrc, int sw, int sh, uint16_t* __restrict__ ddst, uint8_t* __restrict__ idst)
+// `cand_n` (nullptr: nothing to clear): the slot's candidate counts, IFX_NUM_PYRS words 16 apart, cleared here for the k_frame_maps launch that follows in the stream
+__global__ void k_frame_down(const uint16_t* __restrict__ dsrc, const uint8_t* __restrict__ isrc, int sw, int sh, uint16_t* __restrict__ ddst, uint8_t* __restrict__ idst,
+                             unsigned int* __restrict__ cand_n)
 {
     const int dw = sw / 2, dh = sh / 2;
+    if (cand_n && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.y == 0 && threadIdx.x < IFX_NUM_PYRS) cand_n[threadIdx.x * 16] = 0u;
     int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     if (x >= dw || y >= dh) return;
     const int D = 5;
@@ -217,7 +220,10 @@ __global__ void k_frame_down(const uint16_t* __restrict__ dsrc, const uint8_t* _
         idst[y * dw + x] = count ? (uint8_t)f2i_rz(sum / (float)count) : (uint8_t)0;
     }
 }
-struct FrameLevel { const uint16_t* depth; const uint8_t* img; float *vmap, *nmap; int16_t *dx, *dy; int w, h, tiles_x, first_block; float fx_inv, fy_inv, cx, cy; };
+struct FrameLevel {
+    const uint16_t* depth; const uint8_t* img; float *vmap, *nmap; int16_t *dx, *dy; int w, h, tiles_x, first_block; float fx_inv, fy_inv, cx, cy;
+    CandEntry* cand; unsigned int* cand_n; float minScale;   // the level's candidate list of the photometric term (nullptr: none is built), its count, rgb_min_scale(level)
+};
 struct FrameLevels { FrameLevel l[IFX_NUM_PYRS]; float cutoff; };
 __global__ void __launch_bounds__(256) k_frame_maps(FrameLevels a)
 {
@@ -257,8 +263,39 @@ __global__ void __launch_bounds__(256) k_frame_maps(FrameLevels a)
                 dyVal += (float)L.img[j * w + i] * gsy[k];
                 --k;
             }
-        L.dx[v * w + u] = (int16_t)dxVal;
-        L.dy[v * w + u] = (int16_t)dyVal;
+        const int16_t sx = (int16_t)dxVal, sy = (int16_t)dyVal;
+        L.dx[v * w + u] = sx;
+        L.dy[v * w + u] = sy;
+        if (!L.cand) return;   // (uniform over the launch)
+        // The pose-independent part of the photometric residual's gate (residual_body, stage 1: border, "all 16 pixels of the 4x4 block non-zero", gradient magnitude),
+        // decided here once per frame instead of in every Gauss-Newton iteration: the pixels that pass go into the level's list, compacted by a ballot and ONE atomic per
+        // wave.  No order is kept -- the sums the list feeds are exact, any order gives the same bits.  At most w * h entries, the list's capacity.
+        const int i = v, j0 = u;
+        const bool ok = i >= 16 && i < h - 16 && j0 >= 16 && j0 < w - 16 && j0 < w - 5 && i < h - 1;
+        bool valid = ok;
+        if (ok) {   // inside the 16-px border the 4x4 block [i-2,i+2) x [j0-2,j0+2) is always in the image
+#pragma unroll
+            for (int a4 = -2; a4 < 2; a4++) {
+                uint32_t r4;
+                __builtin_memcpy(&r4, L.img + (i + a4) * w + j0 - 2, 4);
+                valid = valid & (((r4 - 0x01010101u) & ~r4 & 0x80808080u) == 0u);
+            }
+        }
+        const float mTwo = (float)((sx * sx) + (sy * sy));
+        const bool pass = valid & (mTwo >= L.minScale);
+        const unsigned long long m = __ballot(pass);
+        if (m) {   // (uniform over the wave)
+            const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
+            unsigned int base = 0;
+            if (lane == lead) base = atomicAdd(L.cand_n, (unsigned int)__popcll(m));
+            base = __shfl(base, lead);
+            const unsigned int at = base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
+            if (pass && at < (unsigned int)(w * h)) {   // (a pixel passes once and the count starts at zero: the bound holds by construction and is checked all the same)
+                CandEntry e;
+                e.pixel = (uint32_t)(i * w + j0); e.gx = sx; e.gy = sy;
+                L.cand[at] = e;
+            }
+        }
     }
 }
 
@@ -774,6 +811,78 @@ __global__ __launch_bounds__(RED_THREADS) void k_rgb_residual(const DevState* __
     residual_body(blockIdx.x, gridDim.x, st, ex, minScale, dIdx, dIdy, lastDepth, nextDepth, lastImage, nextImage, corres, maxDepthDelta, w, h, partials);
 }
 
+// The residual pass over the frame slot's candidate list (option rgb_cand; frame-to-model tracker, two-launch form).  residual_body above spends its stage 1 on a gate
+// that does not depend on the pose -- 33 B read and a record written per pixel, candidate or not, in every iteration -- and that few pixels pass (level 0: minScale =
+// 1600).  k_frame_maps has decided that gate once for the frame: entry t of `cand` is a pixel that passed, with its gradients.  Here thread t takes entry t: what is
+// left of stage 1 is the model depth's NaN test (d1 is the MODEL's depth in this tracker, so it stays per iteration), stages 2 to 4 are residual_body's, and the record
+// goes to corres[t] -- one record per candidate, which the list form of the photometric step reads back by the same t.  The count lives on the device only: the grid is
+// fixed per level and strides over the list; a block past the count still runs the prologue (its barriers, block 0's hand-off of the increment) and adds nothing.
+// Three entries deep: the gathers of this round, the own-pixel loads of the next and the entry of the round after are in flight together; no load sits behind a branch.
+template <bool PRO>
+__device__ __forceinline__ void residual_cand_body(int bid, int nblk, const DevState* __restrict__ st, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n,
+                                                   const float* __restrict__ lastDepth, const float* __restrict__ nextDepth, const uint8_t* __restrict__ lastImage,
+                                                   const uint8_t* __restrict__ nextImage, Corres8* __restrict__ corres, float maxDepthDelta, int w, int h,
+                                                   int* __restrict__ res_total, const GnPro* pro, double* __restrict__ rrt_out)
+{
+    const int N = w * h;   // the list's capacity
+    const int stride = nblk * RED_THREADS;
+    int t = bid * RED_THREADS + threadIdx.x;
+    // in flight before the warp matrices are known (PRO: under the prologue's solve): the count, the first two entries, then the first entry's own pixel
+    const int n = min((int)cand_n[0], N);
+    const CandEntry e0 = cand[t < N ? t : 0];
+    CandEntry e1 = cand[t + stride < N ? t + stride : 0];
+    int pix = t < n ? (int)min(e0.pixel, (uint32_t)(N - 1)) : 0;   // (an entry names a pixel of the level by construction; the clamp keeps a wrong one inside the images)
+    float d1 = nextDepth[pix];
+    uint8_t ni = nextImage[pix];
+    const float* kk = st->krkinv;
+    const float* ktp = st->kt;
+    if (PRO) { const float* sp = gn_prologue(st, *pro, rrt_out); kk = sp + 12; ktp = sp + 21; }
+    float krk[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) krk[k] = kk[k];
+    const float kt0 = ktp[0], kt1 = ktp[1], kt2 = ktp[2];
+    int cnt = 0, sig = 0;
+    while (t < n) {
+        // stage 2: warp into the last image
+        const int i = pix / w, j0 = pix - i * w;
+        const int y = i, x = j0;
+        const float td1 = (float)(d1 * (krk[6] * x + krk[7] * y + krk[8]) + kt2);
+        const int u0 = f2i_rn((d1 * (krk[0] * x + krk[1] * y + krk[2]) + kt0) / td1);
+        const int v0 = f2i_rn((d1 * (krk[3] * x + krk[4] * y + krk[5]) + kt1) / td1);
+        const bool c0 = !(d1 != d1) & ((u0 >= 0) & (v0 >= 0) & (u0 < w) & (v0 < h));
+        const int gj = c0 ? v0 * w + u0 : 0;
+        // stage 3: gathers; behind them the next round's own pixel and the entry of the round after (past the count: pixel 0 / entry 0, dropped)
+        const float d0 = lastDepth[gj];
+        const uint8_t li = lastImage[gj];
+        const int tn = t + stride, tnn = tn + stride;
+        const int pixn = tn < n ? (int)min(e1.pixel, (uint32_t)(N - 1)) : 0;
+        const float d1n = nextDepth[pixn];
+        const uint8_t nin = nextImage[pixn];
+        const CandEntry e2 = cand[tnn < N ? tnn : 0];
+        // stage 4
+        Corres8 c;
+        const bool hit = c0 & (d0 > 0) & (fabsf(td1 - d0) <= maxDepthDelta) & (li != 0);
+        const float diff = (float)ni - (float)li;
+        c.zx = hit ? (short)u0 : (short)-1; c.zy = hit ? (short)v0 : (short)-1;
+        c.diff = hit ? diff : 0.f;
+        cnt += hit ? 1 : 0;
+        sig += hit ? (int)(diff * diff) : 0;
+        corres[t] = c;
+        t = tn; pix = pixn; d1 = d1n; ni = nin; e1 = e2;
+    }
+    __shared__ int lds[RED_WAVES][2];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    cnt = wave_sum_i(cnt);
+    sig = wave_sum_i(sig);
+    if (lane == 0) { lds[wid][0] = cnt; lds[wid][1] = sig; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        int s = 0;
+        for (int wv = 0; wv < RED_WAVES; wv++) s += lds[wv][threadIdx.x];
+        if (s) atomicAdd(&res_total[threadIdx.x], s);   // grand totals by integer atomics (exact in any order)
+    }
+}
+
 // One launch for the two independent reductions of a Gauss-Newton iteration: blocks [0, nb_icp) run the
 // ICP reduction, blocks [nb_icp, nb_icp + nb_res) the photometric residual pass.
 struct PairArgs {
@@ -791,9 +900,10 @@ struct PairArgs {
 // each group of s_loads into the branch that uses it: four to five dependent scalar round trips in front of the first vector load of a
 // latency-bound launch.
 #define IFX_PIN_S(x) asm volatile("" ::"s"(x))
-template <bool CHECK_SKIP, bool PRO = false>
+// LIST (option rgb_cand): the residual half runs over the frame slot's candidate list `cand` / `cand_n` (residual_cand_body); the two arguments are unused otherwise
+template <bool CHECK_SKIP, bool PRO = false, bool LIST = false>
 __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState* __restrict__ st, int nb_icp, int w, int h, double* __restrict__ gacc, int* __restrict__ gres, PairArgs a, GnPro g,
-                                                              double* __restrict__ rrt_store)
+                                                              double* __restrict__ rrt_store, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n)
 {
     // `st`, `nb_icp`, `w`, `h` and the two hand-off pointers (DevState::gn_acc / gn_res of `st`: separate arguments, so that the state itself stays
     // read-only here and its fields come through the scalar cache) arrive preloaded: the branch below is decided without a load, and each half then fetches its argument words and its
@@ -805,6 +915,9 @@ __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState*
         // PRO: `g` and `rrt_store` (DevState::gnp_RRt of this iteration's parity: block 0 publishes the increment it solved for the launch after the next)
         icp_body<false, true, PRO>(blockIdx.x, nb_icp, st, ia, a.vmap_curr, a.nmap_curr, a.vmap_prev, a.nmap_prev, a.fx, a.fy, a.cx, a.cy, a.distThres, a.angleThres, w, h, gacc, &g,
                                    blockIdx.x == 0 ? rrt_store : nullptr);
+    } else if (LIST) {
+        residual_cand_body<PRO>(blockIdx.x - nb_icp, a.nb_res, st, cand, cand_n, a.lastDepth, a.nextDepth, a.lastImage, a.nextImage, a.corres, a.maxDepthDelta, w, h, gres, &g,
+                                blockIdx.x == 0 ? rrt_store : nullptr);
     } else {
         ResArgs ra;
         residual_body<true, PRO>(blockIdx.x - nb_icp, a.nb_res, st, ra, a.minScale, a.dIdx, a.dIdy, a.lastDepth, a.nextDepth, a.lastImage, a.nextImage, a.corres, a.maxDepthDelta, w,
@@ -920,6 +1033,88 @@ __device__ __forceinline__ void rgb_step_body(int bid, int nblk, const Corres8* 
     g_ts[2] = clock64();
     if (threadIdx.x == 0) { s_dbg_blk[0] = ts_local[0] - ts_start; s_dbg_blk[1] = ts_local[1] - ts_local[0]; s_dbg_blk[2] = ts_local[2] - ts_local[1]; }
 #endif
+}
+// The photometric step over the candidate list (option rgb_cand): record t and entry t (the gradients travel in the entry) instead of the records and the two gradient
+// images of every pixel; rounds, rows, products and the exact block sum are rgb_step_body's.  A block whose first record is past the count has nothing to add.
+// The count is read again here, one launch after the residual pass read it.  They agree unless the slot is being rewritten under the run: a tracker enqueued ahead for
+// a frame that was announced wrongly keeps running on the main stream while the side stream already prepares the slot for the frame that came (its result is dropped,
+// ifx_drop_tracked).  Such a run may then see records here that no residual pass wrote, so a record counts only if its coordinates lie in the image: the run's sums are
+// worthless either way, but its gathers stay inside the point cloud.  (The dense form never met this: its residual pass writes a record for every pixel.)
+__device__ __forceinline__ void rgb_step_cand_body(int bid, int nblk, const Corres8* __restrict__ corres, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n,
+                                                   const float* __restrict__ cloud, float fx, float fy, float sobelScale, int w, int h, double* __restrict__ gacc,
+                                                   const int* __restrict__ res_total)
+{
+    const int N = w * h;
+    const int base0 = bid * (RED_THREADS * RED_IT_RGB) + threadIdx.x;
+    // first round's records and entries: requested beside the count and the residual totals
+    Corres8 c[RED_IT_RGB];
+    CandEntry e[RED_IT_RGB];
+#pragma unroll
+    for (int u = 0; u < RED_IT_RGB; u++) {
+        const int k = base0 + u * RED_THREADS;
+        const int kk = k < N ? k : 0;
+        c[u] = corres[kk];
+        e[u] = cand[kk];
+    }
+    const int n = min((int)cand_n[0], N);
+    if (bid * (RED_THREADS * RED_IT_RGB) >= n) return;   // (uniform over the block)
+#pragma unroll
+    for (int u = 0; u < RED_IT_RGB; u++) if (base0 + u * RED_THREADS >= n) c[u].zx = -1;   // (past the count: a record of another frame or none at all)
+    float sigma;
+    {
+        int cnt = res_total[0], sg = res_total[1];
+        float q = (float)sg / (float)cnt;
+        sigma = (float)sqrt((double)((q == 0) ? 1 : cnt));
+    }
+    double acc[29];
+#pragma unroll
+    for (int k = 0; k < 29; k++) acc[k] = 0.0;
+    const int stride = nblk * RED_THREADS * RED_IT_RGB;
+    for (int base = base0; base < n; base += stride) {
+        float X[RED_IT_RGB], Y[RED_IT_RGB], Z[RED_IT_RGB];
+#pragma unroll
+        for (int u = 0; u < RED_IT_RGB; u++) {
+            if (!((c[u].zx >= 0) & (c[u].zx < w) & (c[u].zy >= 0) & (c[u].zy < h))) c[u].zx = -1;   // (see above: changes no record that this iteration's residual pass wrote)
+            int g = (c[u].zx >= 0) ? ((int)c[u].zy * w + (int)c[u].zx) * 3 : 0;
+            X[u] = cloud[g]; Y[u] = cloud[g + 1]; Z[u] = cloud[g + 2];
+        }
+        Corres8 cn[RED_IT_RGB];
+        CandEntry en[RED_IT_RGB];
+#pragma unroll
+        for (int u = 0; u < RED_IT_RGB; u++) {   // (a thread past its last round reads record 0 and drops it: no branch around the loads)
+            const int k = base + stride + u * RED_THREADS;
+            const bool in = k < n;
+            const int kk = in ? k : 0;
+            cn[u] = corres[kk];
+            en[u] = cand[kk];
+            if (!in) cn[u].zx = -1;
+        }
+#pragma unroll
+        for (int u = 0; u < RED_IT_RGB; u++) {
+            float row[7] = {0, 0, 0, 0, 0, 0, 0};
+            bool found = c[u].zx >= 0;
+            if (found) {
+                float wgt = sigma + fabsf(c[u].diff);
+                wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
+                if (sigma == -1) wgt = 1;
+                row[6] = -wgt * c[u].diff;
+                float invz = (float)(1.0 / Z[u]);
+                float dI_dx = wgt * sobelScale * e[u].gx;
+                float dI_dy = wgt * sobelScale * e[u].gy;
+                float v0 = dI_dx * fx * invz;
+                float v1 = dI_dy * fy * invz;
+                float v2 = -(v0 * X[u] + v1 * Y[u]) * invz;
+                row[0] = v0; row[1] = v1; row[2] = v2;
+                row[3] = -Z[u] * v1 + Y[u] * v2;
+                row[4] = Z[u] * v0 - X[u] * v2;
+                row[5] = -Y[u] * v0 + X[u] * v1;
+            }
+            products7<1>(row, found, acc);
+        }
+#pragma unroll
+        for (int u = 0; u < RED_IT_RGB; u++) { c[u] = cn[u]; e[u] = en[u]; }
+    }
+    block_sum_exact<29>(acc, gacc, bid % IFX_ACC_REPL);
 }
 __global__ __launch_bounds__(RED_THREADS) void k_rgb_step(const Corres8* __restrict__ corres, float sigma_explicit, const int* __restrict__ res_partials,
                                                           int res_blocks, const float* __restrict__ cloud, float fx, float fy,
@@ -1725,8 +1920,9 @@ struct StepArgs {
     unsigned int* lctr;
     int pro, pro_k;        // option gn_prologue: 0 = round 3's form; 1 = sums only (the next launch's prologue solves); 2 = the run's last iteration (last-block form on the parity buffers).  pro_k: position in the two-launch tail
 };
-template <bool CHECK_SKIP>
-__global__ __launch_bounds__(RED_THREADS) void k_rgb_step_solve(DevState* st, int nb, int rgb, int w, int h, StepArgs a)
+// LIST (option rgb_cand): the sums run over the candidate list and its records (rgb_step_cand_body); `cand` / `cand_n` are unused otherwise
+template <bool CHECK_SKIP, bool LIST = false>
+__global__ __launch_bounds__(RED_THREADS) void k_rgb_step_solve(DevState* st, int nb, int rgb, int w, int h, StepArgs a, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n)
 {
     __builtin_assume(st != nullptr);
     if (CHECK_SKIP && st->skip) return;   // (model-to-model instance only) uniform over the grid: the last-block ticket stays armed
@@ -1750,7 +1946,10 @@ __global__ __launch_bounds__(RED_THREADS) void k_rgb_step_solve(DevState* st, in
 #ifdef IFX_STAMPS
     long long t0 = clock64();
 #endif
-    if (rgb) rgb_step_body(blockIdx.x, nb, a.corres, 0.f, nullptr, 0, a.cloud, a.fx, a.fy, a.dIdx, a.dIdy, a.sobelScale, w, h, rgb_acc, res_total);
+    if (rgb) {
+        if (LIST) rgb_step_cand_body(blockIdx.x, nb, a.corres, cand, cand_n, a.cloud, a.fx, a.fy, a.sobelScale, w, h, rgb_acc, res_total);
+        else rgb_step_body(blockIdx.x, nb, a.corres, 0.f, nullptr, 0, a.cloud, a.fx, a.fy, a.dIdx, a.dIdy, a.sobelScale, w, h, rgb_acc, res_total);
+    }
     if (a.pro == 1) return;   // sums only: every block of the next launch reads the totals and solves (gn_prologue)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -2263,9 +2462,38 @@ __global__ void k_commit_pose(DevState* st, unsigned int* lctr)
 static const dim3 B2(32, 8);
 static inline dim3 G2(int w, int h) { return dim3(cdiv(w, 32), cdiv(h, 8)); }
 
+// the photometric term's threshold on the squared gradient magnitude at a pyramid level (EF/Utils/RGBDOdometry.cpp:45-48, 436): ONE float for the side that builds the
+// candidate list (k_frame_maps) and the side that gates per iteration (residual_body)
+static inline float rgb_min_scale(int level)
+{
+    static const float minGrad[3] = {5, 3, 1};
+    static_assert(IFX_NUM_PYRS == 3, "minimum gradients per level");
+    const double sobelScale = 1.0 / 8.0;
+    return (float)(pow(minGrad[level], 2.0) / pow(sobelScale, 2.0));
+}
+// candidate lists of a frame slot: one entry of capacity per pixel and level; the counts are zero until the slot's first k_frame_maps
+static int slot_cand_alloc(ifx* h, FrameSlot& f)
+{
+    unsigned int* counts = nullptr;
+    HIPCHK(h, hipMalloc(&counts, IFX_NUM_PYRS * 16 * sizeof(unsigned int)));
+    HIPCHK(h, hipMemset(counts, 0, IFX_NUM_PYRS * 16 * sizeof(unsigned int)));
+    for (int i = 0; i < IFX_NUM_PYRS; i++) {
+        f.cand_n[i] = counts + i * 16;
+        HIPCHK(h, hipMalloc(&f.cand[i], (size_t)(h->w >> i) * (h->h >> i) * sizeof(CandEntry)));
+    }
+    return IFX_OK;
+}
+static void slot_cand_free(FrameSlot& f)
+{
+    for (int i = 0; i < IFX_NUM_PYRS; i++) { hipFree(f.cand[i]); f.cand[i] = nullptr; }
+    hipFree(f.cand_n[0]);
+    for (int i = 0; i < IFX_NUM_PYRS; i++) f.cand_n[i] = nullptr;
+}
+
 int ifx_alloc_tracker(ifx* h)
 {
     Pyr& p = h->pyr;
+    for (int q = 0; q < 2; q++) { const int r = slot_cand_alloc(h, h->slot[q]); if (r) return r; }
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
         p.w[i] = h->w >> i; p.h[i] = h->h >> i;
         size_t n = (size_t)p.w[i] * p.h[i];
@@ -2323,7 +2551,7 @@ void ifx_bind_slot(ifx* h, int s)
     h->rgb = f.rgb; h->depth_raw = f.depth_raw; h->depth_filt = f.depth_filt; h->dm = f.dm; h->dmf = f.dmf;
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
         p.depth_tmp[i] = (i == 0) ? f.depth_filt : f.depth_tmp[i]; p.vmap_curr[i] = f.vmap_curr[i]; p.nmap_curr[i] = f.nmap_curr[i];
-        p.next_img[i] = f.next_img[i]; p.didx[i] = f.didx[i]; p.didy[i] = f.didy[i];
+        p.next_img[i] = f.next_img[i]; p.didx[i] = f.didx[i]; p.didy[i] = f.didy[i]; p.cand[i] = f.cand[i]; p.cand_n[i] = f.cand_n[i];
         p.lastnext_img[i] = h->slot[s < 2 ? (s ^ 1) : 0].next_img[i];   // (slots 3.., a camera's run-ahead frame: the caller points it at the camera's parked pyramid)
     }
 }
@@ -2340,7 +2568,7 @@ void ifx_free_tracker(ifx* h)
         hipFree(p.vmap_cam[i]); hipFree(p.nmap_cam[i]); hipFree(p.vmap_prev[i]); hipFree(p.nmap_prev[i]); hipFree(p.last_depth[i]); hipFree(p.last_img[i]);
         hipFree(p.cloud[i]); hipFree(p.corres[i]);
     }
-    for (size_t q = 0; q < h->slot.size(); q++) hipFree(h->slot[q].so3);
+    for (size_t q = 0; q < h->slot.size(); q++) { hipFree(h->slot[q].so3); slot_cand_free(h->slot[q]); }
     if (h->d_cam_trk) {
         Pyr& cp = h->cam_pyr;
         for (int i = 0; i < IFX_NUM_PYRS; i++) { hipFree(cp.vmap_cam[i]); hipFree(cp.nmap_cam[i]); hipFree(cp.vmap_prev[i]); hipFree(cp.nmap_prev[i]); hipFree(cp.last_depth[i]); hipFree(cp.last_img[i]); hipFree(cp.cloud[i]); hipFree(cp.corres[i]); }
@@ -2354,6 +2582,16 @@ void ifx_free_tracker(ifx* h)
     hipFree(h->pyr.acc); hipFree(h->res_partials); hipFree(h->d_out29); hipFree(h->d_ticket);
 }
 
+// Grids of the list forms of the photometric term (option rgb_cand).  The number of candidates is known on the device only, so the grids are fixed per level and stride
+// over the list: one thread per EIGHT / FOUR / TWO pixels of level 0 / 1 / 2 in the residual half -- the levels' gates (minimum gradient 5 / 3 / 1) pass about 2 % / 5 % /
+// 40 % of the pixels of a plain scene, so that one round covers the list there and a fully textured frame takes eight pipelined rounds at level 0 -- and a quarter of
+// that in the step, whose threads take four records a round.  opt_res_blocks / opt_rgb_blocks override (profiles/r18_rgb_candidates.txt has the A/B lines).
+static inline int rgb_cand_blocks(const ifx* h, int n, int level, bool step)
+{
+    const int per_thread = 8 >> std::min(level, 2), opt = step ? h->opt_rgb_blocks : h->opt_res_blocks;
+    const int b = opt > 0 ? std::min(opt, cdiv(n, RED_THREADS)) : cdiv(n, RED_THREADS * per_thread * (step ? RED_IT_RGB : 1));
+    return std::max(1, b);
+}
 static inline int red_blocks(ifx* h, int n, int it = RED_IT)
 {
     int b = cdiv(n, RED_THREADS * it);
@@ -2441,7 +2679,9 @@ static void tracker_init_frame(ifx* h, const uint16_t* depth_filt, const uint8_t
     (void)depth_filt;   // level 0 of the depth pyramid IS the filtered depth (ifx_bind_slot aliases it; the reference copies it)
     LAUNCH(h, "intensity", dim3(cdiv(h->P, 256)), dim3(256), k_intensity, rgb, 3, h->P, p.next_img[0]);
     for (int i = 1; i < IFX_NUM_PYRS; i++)
-        LAUNCH(h, "frame_down", G2(p.w[i], p.h[i]), B2, k_frame_down, p.depth_tmp[i - 1], p.next_img[i - 1], p.w[i - 1], p.h[i - 1], p.depth_tmp[i], p.next_img[i]);
+        LAUNCH(h, "frame_down", G2(p.w[i], p.h[i]), B2, k_frame_down, p.depth_tmp[i - 1], p.next_img[i - 1], p.w[i - 1], p.h[i - 1], p.depth_tmp[i], p.next_img[i],
+               i == 1 ? p.cand_n[0] : (unsigned int*)nullptr);   // (the first of them also clears the slot's candidate counts, for k_frame_maps below: no launch or memset node of its own)
+    static_assert(IFX_NUM_PYRS >= 2, "the candidate counts are cleared by the level-1 launch");
     FrameLevels fl;
     int blocks = 0;
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
@@ -2451,6 +2691,7 @@ static void tracker_init_frame(ifx* h, const uint16_t* depth_filt, const uint8_t
         L.depth = p.depth_tmp[i]; L.img = p.next_img[i]; L.vmap = p.vmap_curr[i]; L.nmap = p.nmap_curr[i]; L.dx = p.didx[i]; L.dy = p.didy[i];
         L.w = p.w[i]; L.h = p.h[i]; L.tiles_x = cdiv(p.w[i], 32); L.first_block = blocks;
         L.fx_inv = 1.f / fx; L.fy_inv = 1.f / fy; L.cx = h->cfg.cx / div; L.cy = h->cfg.cy / div;
+        L.cand = p.cand[i]; L.cand_n = p.cand_n[i]; L.minScale = rgb_min_scale(i);   // (built whatever option rgb_cand says: the slot may be tracked after the option changes)
         blocks += L.tiles_x * cdiv(p.h[i], 8);
     }
     fl.cutoff = h->cfg.max_depth_processed;
@@ -2474,7 +2715,6 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         const float div = (float)(1 << (first < 0 ? 0 : first));
         LAUNCH(h, "track_gn_begin", dim3(1), dim3(64), k_track_gn_begin, st, h->slot[h->cur_slot].so3, so3, c.fx / div, c.fy / div, c.cx / div, c.cy / div, keep_last, h->opt_gn_persist ? 1 : 0);
     }
-    static const float minGrad[3] = {5, 3, 1};
     const double sobelScale = 1.0 / 8.0;
     bool ended = false;
     // which levels run in the persistent kernel, and whether the two-launch iterations form the run's tail (then their solves move into the next launch's prologue: gn_prologue)
@@ -2507,7 +2747,7 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         PairArgs pa;
         pa.vmap_curr = p.vmap_curr[i]; pa.nmap_curr = p.nmap_curr[i]; pa.vmap_prev = p.vmap_prev[i]; pa.nmap_prev = p.nmap_prev[i];
         pa.fx = c.fx / div; pa.fy = c.fy / div; pa.cx = c.cx / div; pa.cy = c.cy / div; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
-        pa.minScale = (float)(pow(minGrad[i], 2.0) / pow(sobelScale, 2.0)); pa.maxDepthDelta = 0.07f;
+        pa.minScale = rgb_min_scale(i); pa.maxDepthDelta = 0.07f;
         pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
         pa.corres = (Corres8*)p.corres[i]; pa.w = p.w[i]; pa.h = p.h[i];
         return pa;
@@ -2554,6 +2794,11 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         if (!ended) LAUNCH(h, "track_end", dim3(1), dim3(64), k_track_end, st, rgb, 1, weight_mult, commit, h->d_list_ctr);
         return;
     }
+    // Option rgb_cand: the residual half and the photometric step of the two-launch iterations run over the bound frame slot's candidate list, and `corres` holds one record
+    // per candidate.  Frame-to-model runs only (the live tracker, looked-ahead or not, and a camera's run ahead: `cand` is set and the next depth is the model's); a run
+    // with a persistent level stays dense as a whole -- the dense forms index `corres` by pixel, and where both would meet in one run the dense one wins.
+    bool cand_run = h->opt_rgb_cand != 0 && rgb;
+    for (int i = 0; i < IFX_NUM_PYRS; i++) cand_run = cand_run && p.cand[i] && p.cand_n[i] && !p.next_depth[i] && persist_q[i] < 0;
     bool pro = h->opt_gn_prologue != 0;
     // The prologue solve is repeated by every block of a launch: free while the grid is one wave of blocks, 4-6 us per launch at 4800 + 304 blocks (level 0 of a
     // 1280x960 frame: 516 against 540 frames/s, profiles/r04_z2_*).  n_pro: the leading iterations of the tail (coarse levels first) whose launches stay under
@@ -2568,7 +2813,7 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
             else {
                 seen_two_launch = true;
                 const int n = p.w[i] * p.h[i];
-                const int blocks = (icp ? red_blocks(h, n) : 0) + (rgb ? std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : (1 << 30)) : 0);
+                const int blocks = (icp ? red_blocks(h, n) : 0) + (cand_run ? rgb_cand_blocks(h, n, i, false) : rgb ? std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : (1 << 30)) : 0);
                 small = small && blocks <= h->opt_gn_prologue_blocks;
                 if (small) n_pro += iterations[i];
             }
@@ -2591,7 +2836,7 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         if (i == 0 && frame_tracker) ifx_enqueue_hinted_frame_side(h);
         float div = (float)(1 << i);
         float fx = c.fx / div, fy = c.fy / div, cx = c.cx / div, cy = c.cy / div;
-        int lw = p.w[i], lh = p.h[i], n = lw * lh, nb = red_blocks(h, n), nb_rgb = std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192);   // the photometric step's launch is dominated by the last block's hand-off and solve: fewer blocks, fewer partial rows (64: 16.9, 192: 15.3, 304: 16.1, 608: 18.5 us per launch)
+        int lw = p.w[i], lh = p.h[i], n = lw * lh, nb = red_blocks(h, n), nb_rgb = cand_run ? rgb_cand_blocks(h, n, i, true) : std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192);   // the photometric step's launch is dominated by the last block's hand-off and solve: fewer blocks, fewer partial rows (64: 16.9, 192: 15.3, 304: 16.1, 608: 18.5 us per launch)
         const float ld = next_div[i];   // the level the iteration after this level's last one runs at
         PairArgs pa = pair_args(i);
         // The residual half of the launch is the slower one and scales with its blocks (its totals go through integer atomics, it has no partial rows for the
@@ -2601,7 +2846,9 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
         // 6x6 solve in every block's prologue, the first loads) a second time: 17.2 -> 14.5 us per level-0 launch with the residual half capped to what is left of one round
         // (profiles/r05_ai_ab_tracker_blocks.txt: 1514 -> 1561 frames/s).  The halves loop over their pixels anyway (grid-stride); opt_res_blocks > 0 overrides.
         const int res_round = std::max(128, h->icp_resident_blocks - (icp ? nb : 0));
-        const int nbr = std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : res_round);
+        const int nbr = cand_run ? rgb_cand_blocks(h, n, i, false) : std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : res_round);
+        const CandEntry* const cl = cand_run ? p.cand[i] : nullptr;
+        const unsigned int* const cln = cand_run ? p.cand_n[i] : nullptr;
         pa.nb_icp = icp ? nb : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = frame_tracker ? 0 : 1;
         if (persist_q[i] >= 0) {   // all iterations of the level in one persistent launch
             const int q = persist_q[i], nbp = persist_nb[i];
@@ -2635,17 +2882,23 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
             int* const gr = it_pro ? gnp_res_of(tail_k & 1) : gres;
             double* const rrt_store = gnp_rrt_of((tail_k + 1) & 1);   // the increment after iteration tail_k - 1
             // <CHECK_SKIP, PRO>: the model-to-model tracker checks the skip flag; from the prologue chain's second iteration on every block first solves the iteration before
-            auto go_icp = [&](auto kernel) { LAUNCH(h, icp_name[i], dim3(pa.nb_icp + pa.nb_res), dim3(RED_THREADS), kernel, st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store); };
-            if (it_pro && tail_k > 0) { if (frame_tracker) go_icp(k_icp_residual<false, true>); else go_icp(k_icp_residual<true, true>); }
-            else { if (frame_tracker) go_icp(k_icp_residual<false, false>); else go_icp(k_icp_residual<true, false>); }
+            // ... and over the candidate list when the run is a list run (LIST)
+            auto go_icp = [&](auto kernel) { LAUNCH(h, icp_name[i], dim3(pa.nb_icp + pa.nb_res), dim3(RED_THREADS), kernel, st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store, cl, cln); };
+            if (it_pro && tail_k > 0) {
+                if (frame_tracker) { if (cand_run) go_icp(k_icp_residual<false, true, true>); else go_icp(k_icp_residual<false, true>); }
+                else { if (cand_run) go_icp(k_icp_residual<true, true, true>); else go_icp(k_icp_residual<true, true>); }
+            } else {
+                if (frame_tracker) { if (cand_run) go_icp(k_icp_residual<false, false, true>); else go_icp(k_icp_residual<false, false>); }
+                else { if (cand_run) go_icp(k_icp_residual<true, false, true>); else go_icp(k_icp_residual<true, false>); }
+            }
             StepArgs sa2 = step_args(i, j);
             sa2.nb = nb_rgb; sa2.nb_icp = nb; sa2.nb_res = nbr; sa2.check_skip = frame_tracker ? 0 : 1; sa2.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
             sa2.pro = (pro && tail_k < n_pro) ? (tail_k == n_pro - 1 ? 2 : 1) : 0; sa2.pro_k = tail_k;   // (the chain's last iteration: last-block form; it is the run's last too unless finer levels were too large for the prologue)
             tail_k++;
             ended = ended || sa2.end_run;
-            auto go_rgb = [&](auto kernel) { LAUNCH(h, rgb_name[i], dim3(nb_rgb), dim3(RED_THREADS), kernel, st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2); };
-            if (frame_tracker) go_rgb(k_rgb_step_solve<false>);
-            else go_rgb(k_rgb_step_solve<true>);
+            auto go_rgb = [&](auto kernel) { LAUNCH(h, rgb_name[i], dim3(nb_rgb), dim3(RED_THREADS), kernel, st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2, cl, cln); };
+            if (frame_tracker) { if (cand_run) go_rgb(k_rgb_step_solve<false, true>); else go_rgb(k_rgb_step_solve<false>); }
+            else { if (cand_run) go_rgb(k_rgb_step_solve<true, true>); else go_rgb(k_rgb_step_solve<true>); }
         }
     }
     if (!ended)   // (no iteration ran at all: every level has zero iterations)
@@ -2729,6 +2982,7 @@ static int cam_slot_alloc(ifx* h, int cam)
     if (h->slot.size() <= idx) h->slot.resize(idx + 1);
     FrameSlot& f = h->slot[idx];
     if (f.rgb) return IFX_OK;
+    { const int r = slot_cand_alloc(h, f); if (r) return r; }
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
         const size_t n = (size_t)(h->w >> i) * (h->h >> i);
         HIPCHK(h, hipMalloc(&f.depth_tmp[i], n * 2));
@@ -2769,6 +3023,7 @@ int ifx_tracker_camera_ahead(ifx* h, int cam, const uint8_t* d_rgb, const uint16
     }
     for (int i = 0; i < IFX_NUM_PYRS; i++) {   // the instance tracks the frame in the camera's slot
         p.vmap_curr[i] = h->pyr.vmap_curr[i]; p.nmap_curr[i] = h->pyr.nmap_curr[i]; p.next_img[i] = h->pyr.next_img[i]; p.didx[i] = h->pyr.didx[i]; p.didy[i] = h->pyr.didy[i];
+        p.cand[i] = h->pyr.cand[i]; p.cand_n[i] = h->pyr.cand_n[i];
         p.depth_tmp[i] = h->pyr.depth_tmp[i]; p.lastnext_img[i] = cc.img[i];
     }
     HIPCHK(h, hipMemcpyAsync((void*)st, cc.state, IFX_CAM_STATE_BYTES, hipMemcpyDeviceToDevice, h->cur));   // the camera's pose block: the run starts from ITS pose
@@ -3223,6 +3478,8 @@ extern "C" int ifx_tracker_buffer_download(ifx_t* h, const char* name, int l, vo
     else if (s == "cloud") { src = p.cloud[l]; bytes = n * 12; }
     else if (s == "corres") { src = p.corres[l]; bytes = n * 8; }
     else if (s == "depth_tmp") { src = p.depth_tmp[l]; bytes = n * 2; }
+    else if (s == "cand" && p.cand[l]) { src = p.cand[l]; bytes = n * sizeof(CandEntry); }   // the bound frame slot's candidate list (capacity; "cand_n" entries are valid, in no particular order)
+    else if (s == "cand_n" && p.cand_n[l]) { src = p.cand_n[l]; bytes = 4; }
     else { h->err = "unknown tracker buffer " + s; return IFX_E_INVALID; }
     if ((int64_t)bytes > max_bytes) return IFX_E_INVALID;
     HIPCHK(h, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, h->stream));
