@@ -776,6 +776,64 @@ int ifx_fpn_level_thresholds(const float* scales, int levels, int canonical_leve
 int ifx_fpn_roi_align(ifx_t* h, const float* const* d_features, const int32_t* heights, const int32_t* widths, const float* scales, int levels, int batch, int channels,
                       const float* d_rois, int n, float canonical_scale, int canonical_level, float eps, int pooled_h, int pooled_w, int sampling_ratio, float* d_out,
                       int32_t* d_levels, void* stream);
+/* ---- the mask head's logits to the map's votes: select, sigmoid, paste.  Between the mask head's last convolution and the map the reference runs
+ * MaskPostProcessor.forward (maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:27-61: a sigmoid over all [R, C, M, M] logits of which C - 1 of every C
+ * are thrown away, an arange and an advanced-index gather), prediction.resize((width, height)) (demo/predictor.py:213 with BoxList.resize, structures/
+ * bounding_box.py:91-127) and COCODemo.select_top_predictions (demo/predictor.py:224-243: a compare, a nonzero that makes the host wait, a gather of every field,
+ * a sort by score and a second gather); the bridge (build/mask_benchmark.py:54-82) then sorts the pasted masks by area.  ifx_mask_head_select is that stretch for
+ * ONE image in two launches, ifx_process_segmentation_detections runs it in front of ifx_process_segmentation_rois.  In numpy: tests/mask_head_numpy.py, held
+ * against the reference's own Python through tests/golden/mask_head_ref.npz (tests/test_mask_head_cpu.py).
+ *   Inputs: d_mask_logits [R][C][M][M] f32; d_boxes [R][4] f32 (x0, y0, x1, y1) in the coordinates of the network's input, BoxList.size = (in_w, in_h);
+ *     d_scores [R] f32; d_labels [R] int64, as ifx_box_detections emits them; d_count one int32 on the device or NULL: the valid rows are the first
+ *     min(max(count, 0), R), NULL: all R (a padded ifx_box_detections result goes in without a read-back); d_class_map int32 [C] on the device or NULL: the class id
+ *     handed on for label j, NULL: the label itself.  1 <= M <= 64, 1 <= C <= 1024, 0 <= R <= 1024.
+ *   Kept rows: a valid row r is kept iff scores[r] > score_thresh (strictly; a NaN score compares false) and 0 <= labels[r] < C.  The reference would raise on a
+ *     label outside the range; here the row is dropped.  score_thresh == -inf: the score is not examined at all and every valid row with a good label is kept, a
+ *     score of -inf or NaN too -- MaskPostProcessor.forward, which has no score test.  A NaN score_thresh is refused.
+ *   Order: sort_by_score != 0: select_top_predictions' -- a higher score first, -0 == +0, equal scores by ascending row (a NaN, which only score_thresh == -inf
+ *     lets through, behind every number): ifx_nms's key order and its sort network.  torch's descending sort is not stable: among equal scores this rule is one of
+ *     the orders the reference permits, fixed.  sort_by_score == 0: ascending row, a stable compaction -- MaskPostProcessor's own order.
+ *   Boxes (BoxList.resize): rw = (float)((double)out_w / (double)in_w), rh likewise; x' = x * rw, y' = y * rh, one f32 multiplication each.  The reference forms
+ *     the ratios as Python floats and multiplies the f32 tensor by them -- `bbox * ratio` when the two ratios are equal, per-coordinate products otherwise; torch
+ *     rounds the scalar to f32 before the multiplication on both branches.  Held bit for bit against BoxList.resize on the CPU for equal and unequal ratios.
+ *   Probabilities: only the kept row's own channel is read: x = logits[r][labels[r]][y][x];  e = EXP(-x), d = 1.0f + e, p = 1.0f / d, each step rounded to f32,
+ *     none fused, a true division; EXP is the exponential stated under ifx_rpn_proposals.  A NaN gives a NaN, which the paste treats as outside.  EXP's clamp makes
+ *     p exactly 1 far to the right (EXP(-x) rounds to +0 from x = 104 on, and 1 + e rounds to 1 long before; +inf too) and exactly 0 far to the left (EXP(-x)
+ *     overflows to +inf below x = -88.8; -inf too).  Against torch's CPU sigmoid the golden cases' samples
+ *     differ by at most 1.192093e-07 (2.000 ulp of torch's value): measured by tools/make_golden_mask_head.py, which writes the figures here and into the fixture.
+ *   Output, R rows each: d_roi_masks [R][M][M], d_boxes_out [R][4], d_class_ids [R] int32, d_rows [R] int32 (the input row of each kept detection; may be NULL),
+ *     d_kept one int32.  Behind kept, masks and boxes are 0, class ids and rows -1.
+ *   How: one block of 1024 threads, one thread per row, reads the count from the device, tests the row, scans (the detector operators' block scan) and, with
+ *     sort_by_score, sorts the keys in LDS; thread k then writes output row k -- the resized box, the class id, the row -- or the padding.  One launch of R blocks
+ *     follows: block k leaves after writing zeros if k >= kept, otherwise it reads the M^2 logits of (rows[k], label) and writes the M^2 probabilities.  The row
+ *     travels from the first launch to the second in the first word of the output mask it belongs to, so a NULL d_rows needs no scratch.
+ * ifx_mask_head_select: the stage on the caller's buffers and stream: enqueue only, no host synchronisation, no allocation, no frame or map state, any handle (a
+ *   sharded one too).  R == 0 writes kept = 0 and nothing else.
+ * ifx_process_segmentation_detections: the stage into scratch of the handle (the detector operators' buffer, grown on demand: a repeated call of the same size
+ *   allocates nothing) on `stream`, the producer's, with out_w x out_h = the handle's frame size (the struct's out_w, out_h are ignored); one 4-byte read of kept,
+ *   the only wait the call adds in front of the one at its end; then exactly ifx_process_segmentation_rois on the kept ROI masks, boxes and class ids with
+ *   `threshold` (the Masker's, 0.5), frame and flags.  *out_kept (host, may be NULL) receives kept.  kept > 256: IFX_E_CAPACITY, nothing is applied, the handle
+ *   stays usable.  kept == 0 is the ROI entry's n == 0.  The result is bit for bit that of ifx_process_segmentation_rois fed the stage's outputs.
+ * ifx_process_segmentation_deferred_detections: the same behind a snapshot ticket; ticket rules as ifx_process_segmentation_deferred_rois (a call that fails,
+ *   IFX_E_CAPACITY included, keeps the ticket).
+ * Refusals (nothing enqueued, the handle stays usable): IFX_E_INVALID for M, C or R outside their ranges, NULL p, d_kept or output buffers, NULL inputs with
+ *   R > 0, a NaN score_thresh, in_w, in_h, out_w or out_h < 1 (out_w, out_h: the stage entry only); IFX_E_STATE on a sharded handle for the two process entries;
+ *   the deferred entry refuses as ifx_process_segmentation_deferred_rois does. */
+typedef struct ifx_mask_head_params {
+  float   score_thresh;                     /* not a NaN; -inf: no score test */
+  int32_t in_w, in_h;                       /* >= 1: the size the boxes are given in */
+  int32_t out_w, out_h;                     /* >= 1: the size they are resized to */
+  int32_t sort_by_score;                    /* != 0: select_top_predictions' order; 0: ascending row */
+} ifx_mask_head_params;
+int ifx_mask_head_select(ifx_t* h, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
+                         const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float* d_roi_masks, float* d_boxes_out,
+                         int32_t* d_class_ids, int32_t* d_rows, int32_t* d_kept, void* stream);
+int ifx_process_segmentation_detections(ifx_t* h, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels,
+                                        const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold,
+                                        int frame, int flags, void* stream, int32_t* out_kept);
+int ifx_process_segmentation_deferred_detections(ifx_t* h, int ticket, const float* d_mask_logits, const float* d_boxes, const float* d_scores,
+                                                 const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
+                                                 const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

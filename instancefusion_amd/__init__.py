@@ -70,6 +70,11 @@ class BoxDetParams(C.Structure):
                 ("xform_clip", C.c_float), ("image_w", C.c_int32), ("image_h", C.c_int32)]
 
 
+class MaskHeadParams(C.Structure):
+    """ifx_mask_head_params: the parameters of the mask head's select / sigmoid stage (include/ifx_c_api.h)"""
+    _fields_ = [("score_thresh", C.c_float), ("in_w", C.c_int32), ("in_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("sort_by_score", C.c_int32)]
+
+
 class SoaView(C.Structure):
     _fields_ = [("count", C.c_int32), ("capacity", C.c_int32), ("d_pos_conf", C.c_void_p), ("d_norm_rad", C.c_void_p),
                 ("d_color", C.c_void_p), ("d_times", C.c_void_p), ("d_img_corr", C.c_void_p), ("d_votes", C.c_void_p)]
@@ -198,6 +203,10 @@ _SIGS = {
     "ifx_rpn_proposals_fpn": (C.c_int, [_P, C.POINTER(RpnLevel), C.c_int, C.POINTER(RpnParams), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "ifx_box_decode": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_float * 4), C.c_float, C.c_int, C.c_int, _P, _P]),
     "ifx_box_detections": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(BoxDetParams), _P, _P, _P, _P, _P, _P, _P]),
+    "ifx_mask_head_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), _P, _P, _P, _P, _P, _P]),
+    "ifx_process_segmentation_detections": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float, C.c_int, C.c_int, _P, _P]),
+    "ifx_process_segmentation_deferred_detections": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float, C.c_int,
+                                                               C.c_int, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
@@ -482,6 +491,47 @@ def box_post_processor(ef, score_thresh, nms, detections_per_img, weights=(10, 1
     "scores" and "labels" (int64).  The result is built with the class of the box lists it is given -- type(boxes[0])(bbox, size, mode="xyxy") and add_field -- so
     nothing of the reference is imported.  cls_agnostic_bbox_reg: the last four columns of box_regression are every class's code.  It raises in training mode."""
     return _box_post_processor_class()(ef, score_thresh, nms, detections_per_img, weights, cls_agnostic_bbox_reg)
+
+
+@functools.lru_cache(maxsize=None)
+def _mask_post_processor_class():
+    """the nn.Module behind mask_post_processor, made on first use: the package imports torch lazily"""
+    import torch
+
+    class MaskPostProcessor(torch.nn.Module):
+        def __init__(self, ef):
+            super().__init__()
+            self.ef = ef
+            self.masker = None
+
+        def forward(self, x, boxes):
+            out, first = [], 0
+            for box in boxes:
+                n = len(box)
+                rows = slice(first, first + n)
+                first += n
+                labels = box.get_field("labels")
+                scores = torch.zeros(n, dtype=torch.float32, device=x.device)      # (score_thresh = -inf: the scores are not examined)
+                masks, _, _, _, _ = self.ef.mask_head_select(x[rows].contiguous(), box.bbox.contiguous(), scores, labels.to(torch.int64).contiguous(), box.size, box.size,
+                                                                score_thresh=float("-inf"), sort_by_score=False, padded=True)
+                r = type(box)(box.bbox, box.size, mode="xyxy")
+                for field in box.fields():
+                    r.add_field(field, box.get_field(field))
+                r.add_field("mask", masks[:, None])
+                out.append(r)
+            return out
+
+    return MaskPostProcessor
+
+
+def mask_post_processor(ef):
+    """An nn.Module that stands in for maskrcnn-benchmark's MaskPostProcessor (modeling/roi_heads/mask_head/inference.py) with masker=None: forward(x, boxes) with
+    x the mask logits [sum R, C, M, M] and boxes a list of box lists with the field "labels", one per image, splits the rows by len(box), makes one
+    ElasticFusion.mask_head_select call per image (score_thresh=-inf, no sort, out_size == in_size: every row in its own place, nothing read back) and returns one
+    box list per image with the given boxes, every field copied and the field "mask" [n,1,M,M]: the sigmoid of each row's own channel by the rule of
+    include/ifx_c_api.h.  A row whose label is outside 0 .. C - 1 -- the reference raises there -- leaves the rows behind it one place up and zeros at the end.
+    The result is built with the class of the box lists it is given, as box_post_processor does, so nothing of the reference is imported."""
+    return _mask_post_processor_class()(ef)
 
 
 @functools.lru_cache(maxsize=None)
@@ -863,6 +913,76 @@ class ElasticFusion:
                 raise IfxError(f"ifx_box_detections: {int(stats[0].item())} candidates, above the cap of 8192: raise score_thresh")
             c = min(c, rows)
             return boxes[:c], scores[:c], labels[:c], index[:c]
+
+    # -- the mask head's logits to ROI masks, resized boxes and class ids (MaskPostProcessor.forward, BoxList.resize, select_top_predictions)
+    def _mask_head_args(self, mask_logits, boxes, scores, labels, in_size, out_size, score_thresh, sort_by_score, count, class_map, stream):
+        """validates the mask head's tensors and parameters: (R, C, M, ifx_mask_head_params, stream)"""
+        import torch
+
+        _ops_tensor(self, mask_logits, "mask_logits", torch.float32, "float32")
+        _ops_tensor(self, boxes, "boxes", torch.float32, "float32")
+        _ops_tensor(self, scores, "scores", torch.float32, "float32")
+        _ops_tensor(self, labels, "labels", torch.int64, "int64, as box_detections returns them")
+        if mask_logits.dim() != 4 or mask_logits.shape[2] != mask_logits.shape[3]:
+            raise ValueError(f"mask_logits: shape {tuple(mask_logits.shape)}, expected [R,C,M,M]")
+        R, Cn, M = int(mask_logits.shape[0]), int(mask_logits.shape[1]), int(mask_logits.shape[3])
+        if not (1 <= M <= 64 and 1 <= Cn <= 1024 and R <= 1024):
+            raise ValueError(f"mask_logits: shape {tuple(mask_logits.shape)}, expected R <= 1024, C in 1 .. 1024, M in 1 .. 64")
+        if tuple(boxes.shape) != (R, 4):
+            raise ValueError(f"boxes: shape {tuple(boxes.shape)}, expected [{R},4]")
+        if tuple(scores.shape) != (R,):
+            raise ValueError(f"scores: shape {tuple(scores.shape)}, expected [{R}]")
+        if tuple(labels.shape) != (R,):
+            raise ValueError(f"labels: shape {tuple(labels.shape)}, expected [{R}]")
+        if count is not None:
+            _ops_tensor(self, count, "count", torch.int32, "int32, as box_detections(padded=True) returns it")
+            if int(count.numel()) != 1:
+                raise ValueError(f"count: shape {tuple(count.shape)}, expected one element")
+        if class_map is not None:
+            _ops_tensor(self, class_map, "class_map", torch.int32, "int32")
+            if tuple(class_map.shape) != (Cn,):
+                raise ValueError(f"class_map: shape {tuple(class_map.shape)}, expected [{Cn}]")
+        p = MaskHeadParams()
+        p.score_thresh = float(score_thresh)
+        if p.score_thresh != p.score_thresh:
+            raise ValueError("score_thresh is NaN")
+        p.in_w, p.in_h, p.out_w, p.out_h = int(in_size[0]), int(in_size[1]), int(out_size[0]), int(out_size[1])
+        if min(p.in_w, p.in_h, p.out_w, p.out_h) < 1:
+            raise ValueError(f"in_size {tuple(in_size)}, out_size {tuple(out_size)}: a size < 1")
+        p.sort_by_score = 1 if sort_by_score else 0
+        if stream is None:
+            stream = torch.cuda.current_stream(mask_logits.device)
+        return R, Cn, M, p, stream
+
+    def mask_head_select(self, mask_logits, boxes, scores, labels, in_size, out_size, score_thresh=0.7, sort_by_score=True, count=None, class_map=None, padded=False,
+                         stream=None):
+        """ifx_mask_head_select, one image: mask_logits [R,C,M,M], boxes [R,4] in the coordinates of in_size = (width, height), scores [R], labels [R] int64 ->
+        (roi_masks [k,M,M] probabilities of each kept row's own channel, boxes [k,4] resized to out_size, class_ids [k] int32, rows [k] int32): the rows with
+        score > score_thresh and a label in 0 .. C - 1, by descending score (sort_by_score) or in their own order, by the rule of include/ifx_c_api.h.  count: an
+        int32 device tensor of one element -- only the first count rows are valid (box_detections(padded=True)'s count goes in as it is); class_map: an int32 device
+        tensor [C], class id per label.  Everything runs on the device; the 4-byte read of kept is this method's only synchronisation, and padded=True returns the
+        uncut [R] tensors plus kept [1] int32 without it (zeros and -1 behind kept)."""
+        import torch
+
+        R, Cn, M, p, stream = self._mask_head_args(mask_logits, boxes, scores, labels, in_size, out_size, score_thresh, sort_by_score, count, class_map, stream)
+        with torch.cuda.stream(stream):
+            dev = mask_logits.device
+            masks = torch.empty((R, M, M), dtype=torch.float32, device=dev)
+            bout = torch.empty((R, 4), dtype=torch.float32, device=dev)
+            cls = torch.empty(R, dtype=torch.int32, device=dev)
+            rows = torch.empty(R, dtype=torch.int32, device=dev)
+            kept = torch.empty(1, dtype=torch.int32, device=dev)
+        self._chk(self.L.ifx_mask_head_select(self.handle, C.c_void_p(mask_logits.data_ptr() or None), C.c_void_p(boxes.data_ptr() or None),
+                                              C.c_void_p(scores.data_ptr() or None), C.c_void_p(labels.data_ptr() or None),
+                                              None if count is None else C.c_void_p(count.data_ptr()), None if class_map is None else C.c_void_p(class_map.data_ptr()),
+                                              R, Cn, M, C.byref(p), C.c_void_p(masks.data_ptr() or None), C.c_void_p(bout.data_ptr() or None),
+                                              C.c_void_p(cls.data_ptr() or None), C.c_void_p(rows.data_ptr() or None), C.c_void_p(kept.data_ptr()),
+                                              C.c_void_p(stream.cuda_stream or None)), "ifx_mask_head_select")
+        if padded:
+            return masks, bout, cls, rows, kept
+        with torch.cuda.stream(stream):
+            k = int(kept.item())
+            return masks[:k], bout[:k], cls[:k], rows[:k]
 
     # -- frame entry (ElasticFusion::processFrame)
     def set_instance_gt(self, gt):
@@ -1373,6 +1493,33 @@ class InstanceFusion:
                                                                    float(threshold), C.c_void_p(cls.data_ptr() or None), n, int(frame), flags,
                                                                    C.c_void_p(stream.cuda_stream or None)),
                      "ifx_process_segmentation_deferred_rois")
+
+    # -- the mask head's logits and the box head's detections: select, sigmoid, paste, votes in one call (include/ifx_c_api.h)
+    def _detections_call(self, fn, name, lead, mask_logits, boxes, scores, labels, in_size, frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream):
+        ef = self.ef
+        R, Cn, M, p, stream = ef._mask_head_args(mask_logits, boxes, scores, labels, in_size, (ef.w, ef.h), score_thresh, True, count, class_map, stream)
+        flags = (1 if isflann else 0) | (2 if superpixels else 0)
+        kept = C.c_int32(0)
+        ef._chk(fn(ef.handle, *lead, C.c_void_p(mask_logits.data_ptr() or None), C.c_void_p(boxes.data_ptr() or None), C.c_void_p(scores.data_ptr() or None),
+                   C.c_void_p(labels.data_ptr() or None), None if count is None else C.c_void_p(count.data_ptr()),
+                   None if class_map is None else C.c_void_p(class_map.data_ptr()), R, Cn, M, C.byref(p), float(threshold), int(frame), flags,
+                   C.c_void_p(stream.cuda_stream or None), C.byref(kept)), name)
+        return int(kept.value)
+
+    def process_segmentation_detections(self, mask_logits, boxes, scores, labels, in_size, frame, score_thresh=0.7, class_map=None, count=None, isflann=False,
+                                        superpixels=False, threshold=0.5, stream=None):
+        """ProcessSegmentation on the mask head's logits and the box head's detections on the handle's GPU (ifx_process_segmentation_detections):
+        ElasticFusion.mask_head_select with sort_by_score and out_size = the frame's size, then process_segmentation_rois on what it keeps -- the reference's
+        MaskPostProcessor, resize, select_top_predictions, Masker and bridge.  Tensors as for mask_head_select, written on `stream` (default: the current one);
+        threshold is the Masker's.  Returns kept, the number of detections that reached the map; more than 256 raise IfxError (IFX_E_CAPACITY)."""
+        return self._detections_call(self.L.ifx_process_segmentation_detections, "ifx_process_segmentation_detections", (), mask_logits, boxes, scores, labels, in_size,
+                                     frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream)
+
+    def process_segmentation_deferred_detections(self, ticket, mask_logits, boxes, scores, labels, in_size, frame, score_thresh=0.7, class_map=None, count=None,
+                                                 isflann=False, superpixels=False, threshold=0.5, stream=None):
+        """The deferred call on the mask head's logits: tensors and stream exactly as for process_segmentation_detections; releases the ticket."""
+        return self._detections_call(self.L.ifx_process_segmentation_deferred_detections, "ifx_process_segmentation_deferred_detections", (int(ticket),), mask_logits,
+                                     boxes, scores, labels, in_size, frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream)
 
     def paste_roi_masks(self, roi_masks, boxes, class_ids, threshold=0.5, stream=None):
         """The ingestion of process_segmentation_rois alone (ifx_paste_roi_masks): (the pasted 0/255 masks [N,H,W] in the bridge's order, the same after the

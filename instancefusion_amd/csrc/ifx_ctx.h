@@ -576,6 +576,13 @@ int ifx_knn_vote(ifx* h, int32_t* d_nbr_out);
 int ifx_ensure_masks(ifx* h, size_t bytes);
 int ifx_frame_for_reader(ifx* h, const char* who, int ticket, const uint8_t** rgb, hipEvent_t* ev, FrameSlot** slot);   // ifx_instance.hip: the frame ifx_detector_input reads
 void ifx_detector_free(ifx* h);
+// ifx_detector.hip: the mask head's stage for ifx_process_segmentation_[deferred_]detections (ifx_instance.hip) -- the argument checks, and the stage into the
+// detector operators' scratch on the producer's stream followed by the 4-byte read of kept
+int ifx_mask_head_check(ifx* h, const char* who, const float* d_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, int R, int C, int M,
+                        const ifx_mask_head_params* p, bool own_out);
+int ifx_mask_head_stage(ifx* h, const char* who, const float* d_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
+                        const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, void* stream, const float** roi_masks, const float** boxes,
+                        const int32_t** class_ids, int* kept);
 int ifx_preprocess(ifx* h);                                   // bilateral + metric
 int ifx_tracker_init_first(ifx* h);
 int ifx_tracker_run_frame(ifx* h, int commit = 1, int keep_last = 0);                            // model pyramid + GN loops (all on device); the frame side is in the slot

@@ -1,9 +1,10 @@
-// ifx_detector.hip -- the detector's side of the library, in four sections:
+// ifx_detector.hip -- the detector's side of the library, in five sections:
 //   1. the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input[_image]; described below)
 //   2. ROIAlign forward and box NMS (ifx_roi_align_forward, ifx_nms)
 //   3. the RPN's proposal stage of one level and the box decoding it contains (ifx_rpn_proposals, ifx_box_decode)
 //   4. the box head's post-processing (ifx_box_detections)
-// Sections 2 to 4 run on the caller's stream and touch no frame or map state; the three calls with an NMS in them share one block scan (block_excl_scan), one
+//   5. the mask head's logits to ROI masks, resized boxes and class ids (ifx_mask_head_select; as a stage of ifx_process_segmentation_detections, ifx_instance.hip)
+// Sections 2 to 5 run on the caller's stream and touch no frame or map state; the three calls with an NMS in them share one block scan (block_excl_scan), one
 // walk state (NmsWalk), one device-count mask kernel (k_nms_mask_dev) and the handle's one scratch buffer, carved by one Carver (ops_scratch).
 //
 //   ifx_detector_input[_image]  <-  COCODemo.build_transform       deps/maskrcnn-benchmark-master/demo/predictor.py:132-160
@@ -1213,6 +1214,93 @@ __global__ void __launch_bounds__(1024) k_bd_reduce(const unsigned long long* ma
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The mask head's logits to ROI masks, boxes and class ids: ifx_mask_head_select (MaskPostProcessor.forward, maskrcnn_benchmark/modeling/roi_heads/mask_head/
+// inference.py:27-61; BoxList.resize, structures/bounding_box.py:91-127; COCODemo.select_top_predictions, demo/predictor.py:224-243; the rule in full:
+// include/ifx_c_api.h, in numpy: tests/mask_head_numpy.py).  Two launches; the number of kept rows stays on the device.
+constexpr int MH_MAX_R = 1024;         // one thread of the select block per row
+constexpr int MH_MAX_C = 1024;
+constexpr int MH_MAX_M = 64;
+
+struct MhArgs {
+    const float *logits, *boxes, *scores;              // [R][C][M][M], [R][4], [R]
+    const long long* labels;                           // [R]
+    const int32_t *count, *class_map;                  // one int32 or NULL, [C] or NULL
+    int R, C, MM, sort, P;                             // P: the power of two >= max(R, 2) the sort network runs on
+    float thresh, rw, rh;
+    float *masks, *boxes_out;                          // [R][M][M], [R][4]
+    int32_t *class_ids, *rows, *kept;                  // [R], [R] or NULL, one
+};
+
+// One block, thread t on input row t and then on output row t.  The kept flags go through the block scan: its total is `kept`, and without the sort its
+// exclusive sum is the row's place (a stable compaction).  With the sort the kept rows' keys (nms_key on (score, row)) and ~0 for every other thread go through
+// ifx_nms's network; no key of a row equals ~0 (the low word is a row < 1024), so the first `kept` keys are the kept rows in the rule's order.
+// The input row of output row k also goes into the first word of mask k (-1 behind kept): k_mh_sigmoid reads it there, whether or not the caller wants d_rows.
+__global__ void __launch_bounds__(1024) k_mh_select(const MhArgs a)
+{
+    __shared__ unsigned long long s_key[MH_MAX_R];
+    __shared__ int s_row[MH_MAX_R];
+    __shared__ int s_w[16];
+    const int t = threadIdx.x;
+    int valid = a.R;
+    if (a.count) { const int c = a.count[0]; valid = min(max(c, 0), a.R); }
+    bool keep = false;
+    float s = 0.f;
+    if (t < valid) {
+        s = a.scores[t];
+        const long long lab = a.labels[t];
+        keep = (a.thresh == -INFINITY || s > a.thresh) && lab >= 0 && lab < (long long)a.C;
+    }
+    int kept;
+    const int pos = block_excl_scan<16, int>(keep ? 1 : 0, s_w, &kept);
+    if (a.sort) {
+        s_key[t] = keep ? nms_key(s, t) : ~0ull;
+        nms_bitonic(s_key, a.P, t);                                 // (rows and kept keys are below R <= P; every key from R on is ~0)
+        s_row[t] = (int)(uint32_t)s_key[t] & (MH_MAX_R - 1);       // (a row, whatever the key: the gathers below stay inside the inputs)
+    } else if (keep) s_row[pos] = t;
+    __syncthreads();
+    if (t == 0) a.kept[0] = kept;
+    if (t >= a.R) return;
+    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+    int cls = -1, row = -1;
+    if (t < kept) {
+        row = min(s_row[t], a.R - 1);
+        const int lab = (int)a.labels[row];                          // (0 .. C - 1: the row was kept)
+        cls = a.class_map ? a.class_map[min(max(lab, 0), a.C - 1)] : lab;
+        const float* q = a.boxes + 4 * (size_t)row;
+        b = make_float4(q[0] * a.rw, q[1] * a.rh, q[2] * a.rw, q[3] * a.rh);
+    }
+    float* o = a.boxes_out + 4 * (size_t)t;
+    o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w;
+    a.class_ids[t] = cls;
+    if (a.rows) a.rows[t] = row;
+    a.masks[(size_t)t * a.MM] = __int_as_float(row);
+}
+
+// Block k: the M^2 probabilities of output row k out of the one channel the row's label names -- SIGMOID of the rule, three f32 steps behind the library's EXP --
+// or M^2 zeros behind kept.  Consecutive threads on consecutive samples: the channel is contiguous in the input, the mask in the output.
+__global__ void __launch_bounds__(256) k_mh_sigmoid(const MhArgs a)
+{
+    __shared__ int s_src;
+    const int t = threadIdx.x, k = blockIdx.x;
+    float* out = a.masks + (size_t)k * a.MM;
+    if (t == 0) s_src = __float_as_int(out[0]);
+    __syncthreads();                                                 // (every thread has the row before the first sample is overwritten)
+    const int row = s_src;
+    long long lab = -1;
+    if (row >= 0 && row < a.R) lab = a.labels[row];
+    if (lab < 0 || lab >= (long long)a.C) {
+        for (int i = t; i < a.MM; i += 256) out[i] = 0.f;
+        return;
+    }
+    const float* x = a.logits + ((size_t)row * a.C + (size_t)lab) * a.MM;
+    for (int i = t; i < a.MM; i += 256) {
+        const float e = rpn_exp(-x[i]);
+        const float d = 1.0f + e;
+        out[i] = 1.0f / d;
+    }
+}
+
 // the stream the LAUNCH macro and the kernel timing use, for the length of a call on the caller's stream
 struct StreamScope {
     ifx* h; hipStream_t old;
@@ -1446,6 +1534,25 @@ int bd_run(ifx* h, const float* d_logits, const float* d_reg, const float* d_pro
     LAUNCH(h, "bd_reduce", dim3(1), dim3(1024), k_bd_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const int32_t*)sgroups, (const float*)sscore,
            (const int32_t*)spos, (const int32_t*)srow, (const int32_t*)ktot, nb, out);
     return ops_done(h, ops, stream);
+}
+
+// The stage's two launches on `stream` (R >= 1; the outputs are the caller's or the handle's scratch).
+int mh_launch(ifx* h, const float* d_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map,
+              int R, int C, int M, const ifx_mask_head_params* p, int out_w, int out_h, float* d_masks, float* d_boxes_out, int32_t* d_class_ids, int32_t* d_rows,
+              int32_t* d_kept, hipStream_t stream)
+{
+    MhArgs a;
+    a.logits = d_logits; a.boxes = d_boxes; a.scores = d_scores; a.labels = (const long long*)d_labels; a.count = d_count; a.class_map = d_class_map;
+    a.R = R; a.C = C; a.MM = M * M; a.sort = p->sort_by_score != 0;
+    a.P = 2;
+    while (a.P < R) a.P <<= 1;
+    a.thresh = p->score_thresh;
+    a.rw = (float)((double)out_w / (double)p->in_w); a.rh = (float)((double)out_h / (double)p->in_h);
+    a.masks = d_masks; a.boxes_out = d_boxes_out; a.class_ids = d_class_ids; a.rows = d_rows; a.kept = d_kept;
+    StreamScope scope(h, stream);
+    LAUNCH(h, "mh_select", dim3(1), dim3(1024), k_mh_select, a);
+    LAUNCH(h, "mh_sigmoid", dim3((unsigned)R), dim3(256), k_mh_sigmoid, a);
+    return IFX_OK;
 }
 
 // no input: the padding alone -- `rows` zero boxes, zeros in the f32 array, -1 in the int64 arrays (each where it is given), a count of 0
@@ -1726,4 +1833,57 @@ extern "C" int ifx_box_detections(ifx_t* h, const float* d_logits, const float* 
     o.boxes = d_boxes; o.scores = d_scores; o.labels = (long long*)d_labels; o.index = (long long*)d_index; o.count = d_count; o.stats = d_stats;
     o.max_out = p->max_out; o.limit = p->detections_per_img;
     return bd_run(h, d_logits, d_regression, d_proposals, R, C, Creg, p, q, o, (hipStream_t)stream);
+}
+
+// the argument checks the three mask-head entries share; they touch nothing (`own_out`: the stage entry, whose out_w, out_h count; the two process entries of
+// ifx_instance.hip take the frame's size)
+int ifx_mask_head_check(ifx* h, const char* who, const float* d_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, int R, int C, int M,
+                        const ifx_mask_head_params* p, bool own_out)
+{
+    if (!p) { h->err = std::string(who) + ": NULL pointer"; return IFX_E_INVALID; }
+    if (M < 1 || M > MH_MAX_M || C < 1 || C > MH_MAX_C || R < 0 || R > MH_MAX_R) { h->err = std::string(who) + ": M outside 1 .. 64, C outside 1 .. 1024 or R outside 0 .. 1024"; return IFX_E_INVALID; }
+    if (R > 0 && (!d_logits || !d_boxes || !d_scores || !d_labels)) { h->err = std::string(who) + ": NULL pointer"; return IFX_E_INVALID; }
+    if (p->score_thresh != p->score_thresh) { h->err = std::string(who) + ": score_thresh is NaN"; return IFX_E_INVALID; }
+    if (p->in_w < 1 || p->in_h < 1 || (own_out && (p->out_w < 1 || p->out_h < 1))) { h->err = std::string(who) + ": in_w, in_h, out_w or out_h < 1"; return IFX_E_INVALID; }
+    return IFX_OK;
+}
+
+extern "C" int ifx_mask_head_select(ifx_t* h, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
+                                    const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float* d_roi_masks, float* d_boxes_out,
+                                    int32_t* d_class_ids, int32_t* d_rows, int32_t* d_kept, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = ifx_mask_head_check(h, "ifx_mask_head_select", d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, true);
+    if (r) return r;
+    if (!d_kept || (R > 0 && (!d_roi_masks || !d_boxes_out || !d_class_ids))) { h->err = "ifx_mask_head_select: NULL pointer"; return IFX_E_INVALID; }
+    if (R == 0) { HIPCHK(h, hipMemsetAsync(d_kept, 0, 4, (hipStream_t)stream)); return IFX_OK; }
+    return mh_launch(h, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, p->out_w, p->out_h, d_roi_masks, d_boxes_out, d_class_ids, d_rows,
+                     d_kept, (hipStream_t)stream);
+}
+
+// The stage of ifx_process_segmentation_[deferred_]detections (ifx_instance.hip): into the detector operators' scratch on the producer's stream at the handle's frame size, then the one 4-byte read of kept.
+// The pointers stay good until the next detector operator on this handle; the segmentation call that reads them ends with the host waiting for its stream.
+int ifx_mask_head_stage(ifx* h, const char* who, const float* d_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
+                        const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, void* stream, const float** roi_masks, const float** boxes,
+                        const int32_t** class_ids, int* kept)
+{
+    *roi_masks = nullptr; *boxes = nullptr; *class_ids = nullptr; *kept = 0;
+    if (R == 0) return IFX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    float *masks, *bout; int32_t *cls, *dkept;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, who, [&](Carver& c) {
+        masks = c.take<float>((size_t)R * M * M);
+        bout = c.take<float>(4 * (size_t)R);
+        cls = c.take<int32_t>(R);
+        dkept = c.take<int32_t>(4);                    // kept (and padding)
+    }, s, &ops);
+    if (r) return r;
+    if ((r = mh_launch(h, d_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, h->w, h->h, masks, bout, cls, nullptr, dkept, s))) return r;
+    if ((r = ops_done(h, ops, s))) return r;
+    int32_t n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, dkept, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    *roi_masks = masks; *boxes = bout; *class_ids = cls; *kept = n;
+    return IFX_OK;
 }

@@ -1504,6 +1504,51 @@ extern "C" int ifx_process_segmentation_deferred_rois(ifx_t* h, int ticket, cons
     if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
     return r;
 }
+// The mask head's logits (ifx_mask_head_select's inputs): the stage runs into the handle's scratch on the producer's stream, kept comes back, and the ROI entry's
+// path takes the scratch pointers -- seg_ingest_rois, k_roi_area, k_roi_gather and k_mask_order as they are.  snap: the deferred entry's pinned frame, or null.
+static int process_segmentation_detections(ifx* h, const char* who, SegSnap* snap, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels,
+                                           const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold, int frame,
+                                           int flags, void* stream, int32_t* out_kept)
+{
+    const float *rois = nullptr, *boxes = nullptr;
+    const int32_t* cls = nullptr;
+    int kept = 0;
+    int r = ifx_mask_head_stage(h, who, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, stream, &rois, &boxes, &cls, &kept);
+    if (r) return r;
+    if (out_kept) *out_kept = kept;
+    if (kept > 256) { h->err = std::string(who) + ": more than 256 detections kept (raise score_thresh)"; return IFX_E_CAPACITY; }
+    DevMasks dm{rois, IFX_MASK_F32, threshold, cls, ifx_event_get(h), boxes, M};
+    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // the stage, and what the producer enqueued before this call
+    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string(who) + ": hipEventRecord on the producer's stream: " + hipGetErrorString(e); return IFX_E_HIP; }
+    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, kept, frame, flags, snap);
+    h->event_pool.push_back(dm.ready);
+    return r;
+}
+extern "C" int ifx_process_segmentation_detections(ifx_t* h, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
+                                                   const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream,
+                                                   int32_t* out_kept)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = ifx_mask_head_check(h, "ifx_process_segmentation_detections", d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, false);
+    if (r) return r;
+    if (h->own || h->shard_n > 1) { h->err = "ifx_process_segmentation_detections: a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
+    return process_segmentation_detections(h, "ifx_process_segmentation_detections", nullptr, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold,
+                                           frame, flags, stream, out_kept);
+}
+extern "C" int ifx_process_segmentation_deferred_detections(ifx_t* h, int ticket, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels,
+                                                            const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold,
+                                                            int frame, int flags, void* stream, int32_t* out_kept)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = ifx_mask_head_check(h, "ifx_process_segmentation_deferred_detections", d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, false);
+    if (r) return r;
+    SegSnap* q = nullptr;
+    if ((r = snap_for_call(h, "ifx_process_segmentation_deferred_detections", ticket, flags, &q))) return r;
+    r = process_segmentation_detections(h, "ifx_process_segmentation_deferred_detections", q, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p,
+                                        threshold, frame, flags, stream, out_kept);
+    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
+    return r;
+}
 static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
                                 SegSnap* snap)
 {

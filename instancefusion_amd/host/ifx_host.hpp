@@ -510,6 +510,20 @@ public:
             throw std::runtime_error(std::string("ifx_box_detections: ") + ifx_last_error(h_));
     }
 
+    // MaskHeadSelect: the mask head's logits to ROI masks, resized boxes and class ids of one image (the rule: ifx_c_api.h; MaskPostProcessor.forward,
+    // BoxList.resize and select_top_predictions of the reference).  d_mask_logits [R][C][M][M], d_boxes [R][4], d_scores [R], d_labels [R] int64, d_count one int32
+    // or nullptr, d_class_map [C] int32 or nullptr -> d_roi_masks [R][M][M], d_boxes_out [R][4], d_class_ids [R], d_rows [R] (may be nullptr), kept in d_kept[0];
+    // zeros and -1 behind kept.  Enqueue only.
+    void MaskHeadSelect(const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map,
+                        int R, int C, int M, const ifx_mask_head_params& p, float* d_roi_masks, float* d_boxes_out, int32_t* d_class_ids, int32_t* d_rows, int32_t* d_kept,
+                        void* stream)
+    {
+        if (!h_) throw std::runtime_error(std::string("ElasticFusion::MaskHeadSelect: the map has no handle (") + ifx_global_error() + ")");
+        if (ifx_mask_head_select(h_, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, d_roi_masks, d_boxes_out, d_class_ids, d_rows, d_kept,
+                                 stream) < 0)
+            throw std::runtime_error(std::string("ifx_mask_head_select: ") + ifx_last_error(h_));
+    }
+
     int getMapSurfelCount() { return ifx_map_count(h_); }
     ifx_t* handle() { return h_; }
     const ifx_config& config() const { return cfg_; }
@@ -1074,6 +1088,44 @@ public:
         if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_rois: ") + ifx_last_error(h));
         handle_ = h;
         segmentations_++;
+    }
+    // ---- the mask head's logits and the box head's detections (ifx_process_segmentation_detections): ElasticFusion::MaskHeadSelect's inputs in device memory of the
+    // map's GPU, p.out_w x p.out_h taken from the map's frame size.  The stage (MaskPostProcessor.forward, BoxList.resize, select_top_predictions,
+    // maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:27-61 and demo/predictor.py:213-243) runs on `stream`, the producer's; then everything as
+    // ProcessSegmentationRois on what it keeps.  Returns kept; more than 256 throw (IFX_E_CAPACITY) and apply nothing.
+    int ProcessSegmentationDetections(const std::unique_ptr<ElasticFusionInterface>& map, const float* d_mask_logits, const float* d_boxes, const float* d_scores,
+                                      const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params& p,
+                                      float threshold, int frame_num, bool isflann, void* stream)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDetections: the map has no handle (") + ifx_global_error() + ")");
+        if (map->elasticFusion().sharding().on())
+            throw std::runtime_error("InstanceFusion::ProcessSegmentationDetections: a sharded map takes its masks from the host (ProcessSegmentation)");
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        int32_t kept = 0;
+        const int r = ifx_process_segmentation_detections(h, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, threshold, frame_num, flags, stream,
+                                                          &kept);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_detections: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+        return kept;
+    }
+    int ProcessSegmentationDeferredDetections(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const float* d_mask_logits, const float* d_boxes,
+                                              const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
+                                              const ifx_mask_head_params& p, float threshold, int frame_num, bool isflann, void* stream)
+    {
+        ifx_t* h = map ? map->handle() : nullptr;
+        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDeferredDetections: the map has no handle (") + ifx_global_error() + ")");
+        if (map->elasticFusion().sharding().on())
+            throw std::runtime_error("InstanceFusion::ProcessSegmentationDeferredDetections: a sharded map takes its masks from the host (ProcessSegmentation)");
+        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
+        int32_t kept = 0;
+        const int r = ifx_process_segmentation_deferred_detections(h, ticket, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, threshold,
+                                                                   frame_num, flags, stream, &kept);
+        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_detections: ") + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+        return kept;
     }
     // ---- the opposite direction: the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input).  What
     // COCODemo.build_transform and to_image_list make of a frame on the CPU (deps/maskrcnn-benchmark-master/demo/predictor.py:132-160, 198-202: Pillow's bilinear
