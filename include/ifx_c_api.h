@@ -473,7 +473,9 @@ int ifx_should_segment(ifx_t* h, int frame);
  * build/mask_ori.py:117); class_ids: n COCO indices.  flags bit0: kNN smoothing of the instance colours
  * (isflann: flannKnnVoteSurfelMap, IF/Core/InstanceFusion.cpp:1070-1163), bit1: superpixel refinement (needs rgb and depth of the frame: host pointers, as
  * InstanceFusion::ProcessSegmentation takes them -- or BOTH NULL = the frame most recently processed, whose raw images are still resident in their frame slot:
- * no staging copy, no upload). */
+ * no staging copy, no upload).
+ * Refusals (this entry and ifx_process_segmentation_deferred alike): IFX_E_INVALID with ifx_last_error "<entry>: n must be 0 .. 256" for n < 0 or n > 256, and
+ * "<entry>: null masks or class ids" for a NULL pointer with n > 0. */
 int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth,
                              const uint8_t* masks, const int32_t* class_ids, int n, int frame,
                              int flags);

@@ -1348,17 +1348,70 @@ class InstanceFusion:
         """InstanceFusion::ProcessSegmentation.  rgb = depth = None: the frame most recently processed (still resident on the device) instead of host copies."""
         rgb = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
         depth = None if depth is None else np.ascontiguousarray(depth, np.uint16)
+        self._host_call("ifx_process_segmentation", (_ptr(rgb), _ptr(depth)), masks, class_ids, frame, isflann, superpixels)
+
+    # -- what the entries share: one call shape (a deferred wrapper is its twin with lead=(int(ticket),)), the flags, the producer's stream, class ids on the device
+    def _seg_call(self, name, lead, *args):
+        return self.ef._chk(getattr(self.L, name)(self.ef.handle, *lead, *args), name)
+
+    @staticmethod
+    def _seg_flags(isflann, superpixels):
+        return (1 if isflann else 0) | (2 if superpixels else 0)
+
+    def _host_call(self, name, lead, masks, class_ids, frame, isflann, superpixels):
         masks = np.ascontiguousarray(masks, np.uint8)
         cls = np.ascontiguousarray(class_ids, np.int32)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
-        self.ef._chk(self.L.ifx_process_segmentation(self.ef.handle, _ptr(rgb), _ptr(depth), _ptr(masks), _ptr(cls), int(masks.shape[0]), int(frame), flags),
-                     "ifx_process_segmentation")
+        self._seg_call(name, lead, _ptr(masks), _ptr(cls), int(masks.shape[0]), int(frame), self._seg_flags(isflann, superpixels))
 
-    def _device_masks(self, masks, class_ids, stream):
-        """validates a detector's tensors for the two device entries: (contiguous masks, int32 class ids on the device, format, n, stream)"""
+    def _image_call(self, name, lead, masks, class_ids, frame, isflann, superpixels, threshold, stream):
+        m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
+        self._seg_call(name, lead, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None), n, int(frame),
+                       self._seg_flags(isflann, superpixels), C.c_void_p(stream.cuda_stream or None))
+        # (the call returned after its work finished: m and cls may go; they were used on the handle's streams only behind `stream`)
+
+    def _rois_call(self, name, lead, roi_masks, boxes, class_ids, frame, isflann, superpixels, threshold, stream):
+        m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
+        self._seg_call(name, lead, C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None), float(threshold), C.c_void_p(cls.data_ptr() or None), n, int(frame),
+                       self._seg_flags(isflann, superpixels), C.c_void_p(stream.cuda_stream or None))
+
+    def _stage_call(self, name, n, stream, *args):
+        """the ingestion alone: (masks in the bridge's order, the same after the overlap clean, the order as input indices, the class ids in that order)"""
+        ori = np.zeros((n, self.ef.h, self.ef.w), np.uint8)
+        clean = np.zeros_like(ori)
+        order, out_cls = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        self._seg_call(name, (), *args, n, C.c_void_p(stream.cuda_stream or None), _ptr(ori), _ptr(clean), _ptr(order), _ptr(out_cls))
+        return ori, clean, order, out_cls
+
+    def _producer_stream(self, stream):
+        """(the handle's torch device, the stream the caller's tensors were written on: the current one by default)"""
         import torch
 
         dev = torch.device("cuda", int(self.ef.cfgd["device"]))
+        return dev, torch.cuda.current_stream(dev) if stream is None else stream
+
+    @staticmethod
+    def _device_class_ids(class_ids, dev, n, what):
+        """class ids (tensor or sequence) as an int32 [n] tensor on the device; made on the current stream, which the caller has set to the producer's"""
+        import torch
+
+        if isinstance(class_ids, torch.Tensor):
+            if class_ids.dtype.is_floating_point or class_ids.dtype.is_complex or class_ids.dtype == torch.bool:
+                raise TypeError(f"class_ids: dtype {class_ids.dtype} is not an integer type")
+            cls = class_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        else:
+            a = np.asarray(class_ids)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise TypeError(f"class_ids: {a.dtype} is not an integer type")
+            cls = torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)   # (no host synchronisation on the stream)
+        if int(cls.numel()) != n:
+            raise ValueError(f"class_ids: {int(cls.numel())} entries for {n} {what}")
+        return cls
+
+    def _device_masks(self, masks, class_ids, stream):
+        """validates a detector's tensors for the image-mask entries: (contiguous masks, int32 class ids on the device, format, n, stream)"""
+        import torch
+
+        dev, stream = self._producer_stream(stream)
         if not isinstance(masks, torch.Tensor):
             raise TypeError("masks must be a torch tensor on the handle's device")
         if masks.dtype in (torch.bool, torch.uint8):
@@ -1373,21 +1426,9 @@ class InstanceFusion:
         if not ((masks.dim() == 3 and tuple(masks.shape[1:]) == hw) or (masks.dim() == 4 and masks.shape[1] == 1 and tuple(masks.shape[2:]) == hw)):
             raise ValueError(f"masks: shape {tuple(masks.shape)}, expected [N,{hw[0]},{hw[1]}] or [N,1,{hw[0]},{hw[1]}]")
         n = int(masks.shape[0])
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):          # whatever has to be made on the way is made on the producer's stream
             m = masks.contiguous()
-            if isinstance(class_ids, torch.Tensor):
-                if class_ids.dtype.is_floating_point or class_ids.dtype.is_complex or class_ids.dtype == torch.bool:
-                    raise TypeError(f"class_ids: dtype {class_ids.dtype} is not an integer type")
-                cls = class_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-            else:
-                a = np.asarray(class_ids)
-                if a.size and not np.issubdtype(a.dtype, np.integer):
-                    raise TypeError(f"class_ids: {a.dtype} is not an integer type")
-                cls = torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)   # (no host synchronisation on the stream)
-        if int(cls.numel()) != n:
-            raise ValueError(f"class_ids: {int(cls.numel())} entries for {n} masks")
+            cls = self._device_class_ids(class_ids, dev, n, "masks")
         return m, cls, fmt, n, stream
 
     def process_segmentation_device(self, masks, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
@@ -1395,24 +1436,13 @@ class InstanceFusion:
         masks: torch tensor [N,H,W] or [N,1,H,W] on the handle's device, in any order; bool / uint8 (inside iff non-zero) or float32 (inside iff > threshold).
         class_ids: N integers (tensor or sequence), each following its mask.  The library applies the bridge's binarisation and stable area sort itself.
         stream: the torch stream the masks were written on (default: the current stream); the call waits for it on the device.  Always the resident frame."""
-        m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
-        self.ef._chk(self.L.ifx_process_segmentation_device(self.ef.handle, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None), n,
-                                                            int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
-                     "ifx_process_segmentation_device")
-        # (the call returned after its work finished: m and cls may go; they were used on the handle's streams only behind `stream`)
+        self._image_call("ifx_process_segmentation_device", (), masks, class_ids, frame, isflann, superpixels, threshold, stream)
 
     def ingest_masks(self, masks, class_ids, threshold=0.5, stream=None):
         """The ingestion of process_segmentation_device alone (ifx_ingest_masks): (the 0/255 masks [N,H,W] in the bridge's order, the same after the overlap
         clean, the order as input indices, the class ids in that order), as numpy arrays."""
         m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
-        ori = np.zeros((n, self.ef.h, self.ef.w), np.uint8)
-        clean = np.zeros_like(ori)
-        order, out_cls = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        self.ef._chk(self.L.ifx_ingest_masks(self.ef.handle, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None), n,
-                                             C.c_void_p(stream.cuda_stream or None), _ptr(ori), _ptr(clean), _ptr(order), _ptr(out_cls)),
-                     "ifx_ingest_masks")
-        return ori, clean, order, out_cls
+        return self._stage_call("ifx_ingest_masks", n, stream, C.c_void_p(m.data_ptr() or None), fmt, float(threshold), C.c_void_p(cls.data_ptr() or None))
 
     # -- a detector slower than the frame loop: snapshot at the frame the masks belong to, deferred call when they arrive (include/ifx_c_api.h)
     def snapshot(self, superpixels=False):
@@ -1422,26 +1452,18 @@ class InstanceFusion:
 
     def process_segmentation_deferred(self, ticket, masks, class_ids, frame, isflann=False, superpixels=False):
         """ProcessSegmentation of the masks a detector made of the snapshot's frame, on the map as it is now (ifx_process_segmentation_deferred); releases the ticket."""
-        masks = np.ascontiguousarray(masks, np.uint8)
-        cls = np.ascontiguousarray(class_ids, np.int32)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
-        self.ef._chk(self.L.ifx_process_segmentation_deferred(self.ef.handle, int(ticket), _ptr(masks), _ptr(cls), int(masks.shape[0]), int(frame), flags),
-                     "ifx_process_segmentation_deferred")
+        self._host_call("ifx_process_segmentation_deferred", (int(ticket),), masks, class_ids, frame, isflann, superpixels)
 
     def process_segmentation_deferred_device(self, ticket, masks, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
         """The deferred call on a detector's raw output on the handle's GPU: tensors and stream exactly as for process_segmentation_device."""
-        m, cls, fmt, n, stream = self._device_masks(masks, class_ids, stream)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
-        self.ef._chk(self.L.ifx_process_segmentation_deferred_device(self.ef.handle, int(ticket), C.c_void_p(m.data_ptr() or None), fmt, float(threshold),
-                                                                     C.c_void_p(cls.data_ptr() or None), n, int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
-                     "ifx_process_segmentation_deferred_device")
+        self._image_call("ifx_process_segmentation_deferred_device", (int(ticket),), masks, class_ids, frame, isflann, superpixels, threshold, stream)
 
     # -- the mask head's own output: [N,1,M,M] probabilities and N boxes, pasted on the GPU as maskrcnn-benchmark's Masker does on the CPU (include/ifx_c_api.h)
     def _device_rois(self, roi_masks, boxes, class_ids, stream):
         """validates a mask head's tensors for the ROI entries: (contiguous ROI masks, M, contiguous boxes, int32 class ids on the device, n, stream)"""
         import torch
 
-        dev = torch.device("cuda", int(self.ef.cfgd["device"]))
+        dev, stream = self._producer_stream(stream)
         for name, t in (("roi_masks", roi_masks), ("boxes", boxes)):
             if not isinstance(t, torch.Tensor):
                 raise TypeError(f"{name} must be a torch tensor on the handle's device")
@@ -1457,53 +1479,31 @@ class InstanceFusion:
             raise ValueError(f"roi_masks: M = {M}, expected 1 .. 64")
         if tuple(boxes.shape) != (n, 4):
             raise ValueError(f"boxes: shape {tuple(boxes.shape)}, expected [{n},4]")
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
         with torch.cuda.stream(stream):          # whatever has to be made on the way is made on the producer's stream
             m = roi_masks.contiguous()
             bx = boxes.contiguous()
-            if isinstance(class_ids, torch.Tensor):
-                if class_ids.dtype.is_floating_point or class_ids.dtype.is_complex or class_ids.dtype == torch.bool:
-                    raise TypeError(f"class_ids: dtype {class_ids.dtype} is not an integer type")
-                cls = class_ids.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-            else:
-                a = np.asarray(class_ids)
-                if a.size and not np.issubdtype(a.dtype, np.integer):
-                    raise TypeError(f"class_ids: {a.dtype} is not an integer type")
-                cls = torch.from_numpy(np.ascontiguousarray(a, np.int32).reshape(-1)).pin_memory().to(dev, non_blocking=True)   # (no host synchronisation on the stream)
-        if int(cls.numel()) != n:
-            raise ValueError(f"class_ids: {int(cls.numel())} entries for {n} ROI masks")
+            cls = self._device_class_ids(class_ids, dev, n, "ROI masks")
         return m, M, bx, cls, n, stream
 
     def process_segmentation_rois(self, roi_masks, boxes, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
         """ProcessSegmentation on a mask head's own output on the handle's GPU (ifx_process_segmentation_rois): the Masker's paste, the bridge's binarisation and
         its stable area sort all run there.  roi_masks: float32 [N,M,M] or [N,1,M,M] probabilities, M in 1 .. 64; boxes: float32 [N,4] (x0, y0, x1, y1) in frame
         pixel coordinates; class_ids, stream and the resident frame as for process_segmentation_device."""
-        m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
-        self.ef._chk(self.L.ifx_process_segmentation_rois(self.ef.handle, C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None), float(threshold),
-                                                          C.c_void_p(cls.data_ptr() or None), n, int(frame), flags, C.c_void_p(stream.cuda_stream or None)),
-                     "ifx_process_segmentation_rois")
+        self._rois_call("ifx_process_segmentation_rois", (), roi_masks, boxes, class_ids, frame, isflann, superpixels, threshold, stream)
 
     def process_segmentation_deferred_rois(self, ticket, roi_masks, boxes, class_ids, frame, isflann=False, superpixels=False, threshold=0.5, stream=None):
         """The deferred call on a mask head's own output: tensors and stream exactly as for process_segmentation_rois."""
-        m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
-        self.ef._chk(self.L.ifx_process_segmentation_deferred_rois(self.ef.handle, int(ticket), C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None),
-                                                                   float(threshold), C.c_void_p(cls.data_ptr() or None), n, int(frame), flags,
-                                                                   C.c_void_p(stream.cuda_stream or None)),
-                     "ifx_process_segmentation_deferred_rois")
+        self._rois_call("ifx_process_segmentation_deferred_rois", (int(ticket),), roi_masks, boxes, class_ids, frame, isflann, superpixels, threshold, stream)
 
     # -- the mask head's logits and the box head's detections: select, sigmoid, paste, votes in one call (include/ifx_c_api.h)
-    def _detections_call(self, fn, name, lead, mask_logits, boxes, scores, labels, in_size, frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream):
+    def _detections_call(self, name, lead, mask_logits, boxes, scores, labels, in_size, frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream):
         ef = self.ef
         R, Cn, M, p, stream = ef._mask_head_args(mask_logits, boxes, scores, labels, in_size, (ef.w, ef.h), score_thresh, True, count, class_map, stream)
-        flags = (1 if isflann else 0) | (2 if superpixels else 0)
         kept = C.c_int32(0)
-        ef._chk(fn(ef.handle, *lead, C.c_void_p(mask_logits.data_ptr() or None), C.c_void_p(boxes.data_ptr() or None), C.c_void_p(scores.data_ptr() or None),
-                   C.c_void_p(labels.data_ptr() or None), None if count is None else C.c_void_p(count.data_ptr()),
-                   None if class_map is None else C.c_void_p(class_map.data_ptr()), R, Cn, M, C.byref(p), float(threshold), int(frame), flags,
-                   C.c_void_p(stream.cuda_stream or None), C.byref(kept)), name)
+        self._seg_call(name, lead, C.c_void_p(mask_logits.data_ptr() or None), C.c_void_p(boxes.data_ptr() or None), C.c_void_p(scores.data_ptr() or None),
+                       C.c_void_p(labels.data_ptr() or None), None if count is None else C.c_void_p(count.data_ptr()),
+                       None if class_map is None else C.c_void_p(class_map.data_ptr()), R, Cn, M, C.byref(p), float(threshold), int(frame),
+                       self._seg_flags(isflann, superpixels), C.c_void_p(stream.cuda_stream or None), C.byref(kept))
         return int(kept.value)
 
     def process_segmentation_detections(self, mask_logits, boxes, scores, labels, in_size, frame, score_thresh=0.7, class_map=None, count=None, isflann=False,
@@ -1512,27 +1512,21 @@ class InstanceFusion:
         ElasticFusion.mask_head_select with sort_by_score and out_size = the frame's size, then process_segmentation_rois on what it keeps -- the reference's
         MaskPostProcessor, resize, select_top_predictions, Masker and bridge.  Tensors as for mask_head_select, written on `stream` (default: the current one);
         threshold is the Masker's.  Returns kept, the number of detections that reached the map; more than 256 raise IfxError (IFX_E_CAPACITY)."""
-        return self._detections_call(self.L.ifx_process_segmentation_detections, "ifx_process_segmentation_detections", (), mask_logits, boxes, scores, labels, in_size,
-                                     frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream)
+        return self._detections_call("ifx_process_segmentation_detections", (), mask_logits, boxes, scores, labels, in_size, frame, score_thresh, class_map, count,
+                                     isflann, superpixels, threshold, stream)
 
     def process_segmentation_deferred_detections(self, ticket, mask_logits, boxes, scores, labels, in_size, frame, score_thresh=0.7, class_map=None, count=None,
                                                  isflann=False, superpixels=False, threshold=0.5, stream=None):
         """The deferred call on the mask head's logits: tensors and stream exactly as for process_segmentation_detections; releases the ticket."""
-        return self._detections_call(self.L.ifx_process_segmentation_deferred_detections, "ifx_process_segmentation_deferred_detections", (int(ticket),), mask_logits,
-                                     boxes, scores, labels, in_size, frame, score_thresh, class_map, count, isflann, superpixels, threshold, stream)
+        return self._detections_call("ifx_process_segmentation_deferred_detections", (int(ticket),), mask_logits, boxes, scores, labels, in_size, frame, score_thresh,
+                                     class_map, count, isflann, superpixels, threshold, stream)
 
     def paste_roi_masks(self, roi_masks, boxes, class_ids, threshold=0.5, stream=None):
         """The ingestion of process_segmentation_rois alone (ifx_paste_roi_masks): (the pasted 0/255 masks [N,H,W] in the bridge's order, the same after the
         overlap clean, the order as input indices, the class ids in that order), as numpy arrays."""
         m, M, bx, cls, n, stream = self._device_rois(roi_masks, boxes, class_ids, stream)
-        ori = np.zeros((n, self.ef.h, self.ef.w), np.uint8)
-        clean = np.zeros_like(ori)
-        order, out_cls = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        self.ef._chk(self.L.ifx_paste_roi_masks(self.ef.handle, C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None), float(threshold),
-                                                C.c_void_p(cls.data_ptr() or None), n, C.c_void_p(stream.cuda_stream or None), _ptr(ori), _ptr(clean), _ptr(order),
-                                                _ptr(out_cls)),
-                     "ifx_paste_roi_masks")
-        return ori, clean, order, out_cls
+        return self._stage_call("ifx_paste_roi_masks", n, stream, C.c_void_p(m.data_ptr() or None), M, C.c_void_p(bx.data_ptr() or None), float(threshold),
+                                C.c_void_p(cls.data_ptr() or None))
 
     # -- the opposite direction: the detector's input tensor from the frame that is already on the device (include/ifx_c_api.h)
     def detector_input_size(self, min_size=800, max_size=None, size_divisible=0):

@@ -544,6 +544,23 @@ static inline IdMap ifx_idmap(const ifx* h) { IdMap m; m.seq = h->seq; m.own_n =
 
 // kernel launch with optional per-kernel event timing
 hipEvent_t ifx_event_get(ifx* h);
+// An event of the handle's pool for the length of a scope (used like StageTimer): taken on construction, given back on destruction -- on every early return --
+// unless release() handed it on.
+struct PoolEvent {
+    ifx* h; hipEvent_t ev;
+    explicit PoolEvent(ifx* h_) : h(h_), ev(ifx_event_get(h_)) {}
+    ~PoolEvent() { if (ev) h->event_pool.push_back(ev); }
+    PoolEvent(const PoolEvent&) = delete;
+    PoolEvent& operator=(const PoolEvent&) = delete;
+    hipEvent_t release() { hipEvent_t e = ev; ev = nullptr; return e; }
+};
+// the end of a timed span that began at `a`: stage_pending takes both events (stage_flush returns them to the pool)
+static inline void ifx_stage_span_end(ifx* h, int id, PoolEvent& a)
+{
+    PoolEvent b(h);
+    hipEventRecord(b.ev, h->cur);
+    h->stage_pending.push_back({id, {a.release(), b.release()}});
+}
 void ifx_ktime_begin(ifx* h, const char* name, hipEvent_t* a);
 void ifx_ktime_end(ifx* h, const char* name, hipEvent_t a);
 

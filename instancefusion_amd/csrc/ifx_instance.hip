@@ -1171,13 +1171,41 @@ static int first_not_used(ifx* h)
 struct SegView { const int32_t* ids; const float* cam; const uint8_t* d_rgb; const uint16_t* d_depth; };
 static SegView seg_view_current(const ifx* h) { return SegView{h->ids_after, h->d_state->pose, nullptr, nullptr}; }
 
-static int run_bboxes(ifx* h, const SegView& v, int nm, std::vector<int>& bbox)
+// the boxes of the projected instances and of the nm masks under the id image `ids` (the host-driven loop and the owners' call read them back differently)
+static void launch_bboxes(ifx* h, const int32_t* ids, int nm)
 {
     LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
-    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, v.ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
+    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
            h->d_bbox, ifx_idmap(h));
+}
+static int run_bboxes(ifx* h, const SegView& v, int nm, std::vector<int>& bbox)
+{
+    launch_bboxes(h, v.ids, nm);
     bbox.resize((size_t)(NI + nm) * 4);
     HIPCHK(h, hipMemcpyAsync(bbox.data(), h->d_bbox, bbox.size() * 4, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return IFX_OK;
+}
+
+// The eviction of a full instance table, behind k_max_count's statistics in d_inst_stats (max row, sum row): getInstanceTableCleanList
+// (IF/Core/InstanceTable.cpp:185-224) -- the reference's selection sort on the sums as floats, all three arrays swapped, the first twenty of the result (ties fall
+// as they fall there) -- then the table entries cleared and cleanInstanceTableMap on the votes.  Returns with the stream drained.
+static int seg_evict_weakest(ifx* h)
+{
+    int stats[NI * 2];
+    HIPCHK(h, hipMemcpyAsync(stats, h->d_inst_stats, sizeof(stats), hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    int* maxv = stats; int* sumv = stats + NI;
+    int order[NI], cl[NI];
+    for (int i = 0; i < NI; i++) order[i] = i;
+    for (int i = 0; i < NI; i++)
+        for (int j = i + 1; j < NI; j++)
+            if ((float)sumv[j] < (float)sumv[i]) { std::swap(maxv[i], maxv[j]); std::swap(order[i], order[j]); std::swap(sumv[i], sumv[j]); }
+    for (int i = 0; i < NI; i++) cl[i] = 0;
+    for (int i = 0; i < 20; i++) cl[order[i]] = 1;
+    for (int q = 0; q < NI; q++) if (cl[q] == 1) h->inst_class[q] = -1;
+    HIPCHK(h, hipMemcpyAsync(h->d_clean_list, cl, sizeof(cl), hipMemcpyHostToDevice, h->cur));
+    LAUNCH(h, "clean_table", dim3(1024), dim3(256), k_clean_table, h->d_state, h->votes, h->cap, h->d_clean_list);
     HIPCHK(h, hipStreamSynchronize(h->cur));
     return IFX_OK;
 }
@@ -1201,9 +1229,7 @@ __global__ void k_bbox_flip(int* __restrict__ bbox, int nboxes)
 static int oseg_launch_bboxes(ifx* h)
 {
     const int nm = h->oseg_nm;
-    LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
-    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, h->ids_after, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
-           h->d_bbox, ifx_idmap(h));
+    launch_bboxes(h, h->ids_after, nm);
     LAUNCH(h, "bbox_flip", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_bbox_flip, h->d_bbox, NI + nm);
     h->oseg_pending = 1;
     return 1;
@@ -1326,25 +1352,10 @@ static int oseg_resume(ifx* h)
         HIPCHK(h, hipStreamSynchronize(h->cur));
         h->oseg_state = 5;
         return oseg_mask_loop(h, false);
-    case 3: {   // eviction statistics merged -> getInstanceTableCleanList (IF/Core/InstanceTable.cpp:185-224), clean, the boxes again
-        int stats[NI * 2];
-        HIPCHK(h, hipMemcpyAsync(stats, h->d_inst_stats, sizeof(stats), hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
-        int* maxv = stats; int* sumv = stats + NI;
-        int order[NI], cl[NI];
-        for (int i = 0; i < NI; i++) order[i] = i;
-        for (int i = 0; i < NI; i++)
-            for (int j = i + 1; j < NI; j++)
-                if ((float)sumv[j] < (float)sumv[i]) { std::swap(maxv[i], maxv[j]); std::swap(order[i], order[j]); std::swap(sumv[i], sumv[j]); }
-        for (int i = 0; i < NI; i++) cl[i] = 0;
-        for (int i = 0; i < 20; i++) cl[order[i]] = 1;
-        for (int q = 0; q < NI; q++) if (cl[q] == 1) h->inst_class[q] = -1;
-        HIPCHK(h, hipMemcpyAsync(h->d_clean_list, cl, sizeof(cl), hipMemcpyHostToDevice, h->cur));
-        LAUNCH(h, "clean_table", dim3(1024), dim3(256), k_clean_table, h->d_state, h->votes, h->cap, h->d_clean_list);
-        HIPCHK(h, hipStreamSynchronize(h->cur));
+    case 3:   // eviction statistics merged -> the twenty weakest leave the table, the boxes again
+        if ((r = seg_evict_weakest(h))) return r;
         h->oseg_state = 4;
         return oseg_launch_bboxes(h);
-    }
     case 4:   // boxes after the eviction merged -> compare map again, the mask that asked for room goes on
         if ((r = oseg_read_bboxes(h))) return r;
         h->oseg_state = 5;
@@ -1359,195 +1370,172 @@ static int oseg_resume(ifx* h)
 // producer's stream at entry (the ingestion waits for it; nothing before the ingestion does)
 // ifx_process_segmentation_rois: roi = M > 0, d = n x M x M f32 ROI masks, d_boxes = n x 4 f32 (xyxy) -- pasted on the device in place of the n x P elements
 struct DevMasks { const void* d; int fmt; float thr; const int32_t* d_cls; hipEvent_t ready; const float* d_boxes = nullptr; int roi = 0; };
+// What a segmentation entry was handed, whichever form it came in: n masks on the host (0/255 bytes, sorted by the caller's bridge, with the optional host frame)
+// or on the device (dm: image-sized masks, or ROI masks with boxes when dm.roi > 0; dm.ready is filled in by the entry body).
+struct MaskSource {
+    enum Kind { HOST, IMAGE, ROIS };
+    int n; Kind kind;
+    DevMasks dm;
+    const uint8_t* rgb; const uint16_t* depth; const uint8_t* masks; const int32_t* cls;   // host form
+};
+static MaskSource src_host(const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks, const int32_t* cls, int n) { return MaskSource{n, MaskSource::HOST, DevMasks{}, rgb, depth, masks, cls}; }
+static MaskSource src_image(const void* d_masks, int fmt, float thr, const int32_t* d_cls, int n) { return MaskSource{n, MaskSource::IMAGE, DevMasks{d_masks, fmt, thr, d_cls, nullptr}, nullptr, nullptr, nullptr, nullptr}; }
+static MaskSource src_rois(const float* d_rois, int M, const float* d_boxes, float thr, const int32_t* d_cls, int n)
+{
+    return MaskSource{n, MaskSource::ROIS, DevMasks{d_rois, IFX_MASK_F32, thr, d_cls, nullptr, d_boxes, M}, nullptr, nullptr, nullptr, nullptr};
+}
 struct SegSnap;   // a pinned frame of ifx_segmentation_snapshot (below): null for the ordinary entries
 static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
 static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
                                        SegSnap* snap);
 static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
                                 SegSnap* snap = nullptr);
+static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail);
+static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
+extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
+
+// ---- the one body behind the segmentation entries.  Its steps keep this order (the order decides which error a doubly-bad call reports): the arguments of the
+// source's form, the refusal by mode, the producer's event, the call, the ticket's release.
+static int seg_check_args(ifx* h, const char* who, const MaskSource& s)
+{
+    const char* bad = nullptr;
+    if (s.n < 0 || s.n > 256) bad = ": n must be 0 .. 256";
+    else if (s.kind == MaskSource::HOST) { if (s.n > 0 && (!s.masks || !s.cls)) bad = ": null masks or class ids"; }
+    else if (s.kind == MaskSource::ROIS) {   // the mask head's ROI masks and boxes (maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:91-154)
+        if (s.dm.roi < 1 || s.dm.roi > ROI_M_MAX) bad = ": roi_size must be 1 .. 64";
+        else if (s.n > 0 && (!s.dm.d || !s.dm.d_boxes || !s.dm.d_cls)) bad = ": null ROI masks, boxes or class ids";
+    }
+    else if (s.dm.fmt != IFX_MASK_U8 && s.dm.fmt != IFX_MASK_F32) bad = ": unknown mask format";
+    else if (s.n > 0 && (!s.dm.d || !s.dm.d_cls)) bad = ": null masks or class ids";
+    if (bad) { h->err = std::string(who) + bad; return IFX_E_INVALID; }
+    return IFX_OK;
+}
+// ticket: the deferred entries' (snap_for_call refuses by mode and finds the pinned frame), null for the resident ones, of which only the device forms refuse a sharded map
+static int seg_refuse_mode(ifx* h, const char* who, bool device, const int* ticket, int flags, SegSnap** snap)
+{
+    if (ticket) return snap_for_call(h, who, *ticket, flags, snap);
+    if (device && (h->own || h->shard_n > 1)) { h->err = std::string(who) + ": a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
+    return IFX_OK;
+}
+static int seg_record_ready(ifx* h, const char* who, DevMasks* dm, const PoolEvent& ready, void* stream)
+{
+    const hipError_t e = hipEventRecord(ready.ev, (hipStream_t)stream);   // what the producer enqueued before this call
+    if (e != hipSuccess) { h->err = std::string(who) + ": hipEventRecord on the producer's stream: " + hipGetErrorString(e); return IFX_E_HIP; }
+    dm->ready = ready.ev;
+    return IFX_OK;
+}
+static int seg_run(ifx* h, const char* who, MaskSource& s, SegSnap* snap, const int* ticket, int frame, int flags, void* stream)
+{
+    int r;
+    if (s.kind == MaskSource::HOST) r = process_segmentation(h, s.rgb, s.depth, s.masks, s.cls, nullptr, s.n, frame, flags, snap);
+    else {
+        PoolEvent ready(h);
+        if ((r = seg_record_ready(h, who, &s.dm, ready, stream))) return r;
+        r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &s.dm, s.n, frame, flags, snap);
+    }
+    if (ticket && r == IFX_OK) ifx_segmentation_snapshot_release(h, *ticket);
+    return r;
+}
+static int seg_entry(ifx* h, const char* who, MaskSource s, const int* ticket, int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    SegSnap* snap = nullptr;
+    int r = seg_check_args(h, who, s);
+    if (r || (r = seg_refuse_mode(h, who, s.kind != MaskSource::HOST, ticket, flags, &snap))) return r;
+    return seg_run(h, who, s, snap, ticket, frame, flags, stream);
+}
+// the ingestion alone (ifx_ingest_masks / ifx_paste_roi_masks): k_mask_area / k_roi_area, k_mask_order and the gather as the full call launches them, then what the caller asked to see
+static int seg_stage_entry(ifx* h, const char* who, MaskSource s, void* stream, uint8_t* out_ori, uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = seg_check_args(h, who, s);
+    if (r) return r;
+    if (h->own || h->shard_n > 1) { h->err = std::string(who) + ": not on a sharded map"; return IFX_E_STATE; }
+    const int n = s.n;
+    if (n == 0) return IFX_OK;
+    const size_t bytes = (size_t)n * h->P;
+    if ((r = ifx_ensure_masks(h, bytes))) return r;
+    {
+        PoolEvent ready(h);
+        if ((r = seg_record_ready(h, who, &s.dm, ready, stream)) || (r = seg_ingest_device(h, &s.dm, n, nullptr, nullptr))) return r;
+    }
+    if (out_ori) HIPCHK(h, hipMemcpyAsync(out_ori, h->d_masks_ori, bytes, hipMemcpyDeviceToHost, h->cur));
+    if (out_clean) HIPCHK(h, hipMemcpyAsync(out_clean, h->d_masks, bytes, hipMemcpyDeviceToHost, h->cur));
+    if (out_order) HIPCHK(h, hipMemcpyAsync(out_order, h->d_mask_rank + 256, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
+    if (out_class_ids) HIPCHK(h, hipMemcpyAsync(out_class_ids, h->d_mask_rank + 512, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return IFX_OK;
+}
+// The mask head's logits (ifx_mask_head_select's inputs): behind the checks, the stage runs into the handle's scratch on the producer's stream, kept comes back, and
+// the ROI form's path takes the scratch pointers -- seg_ingest_rois, k_roi_area, k_roi_gather and k_mask_order as they are.
+static int seg_entry_detections(ifx* h, const char* who, const int* ticket, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels,
+                                const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold, int frame, int flags,
+                                void* stream, int32_t* out_kept)
+{
+    if (!h) return IFX_E_INVALID;
+    SegSnap* snap = nullptr;
+    int r = ifx_mask_head_check(h, who, d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, false);
+    if (r || (r = seg_refuse_mode(h, who, true, ticket, flags, &snap))) return r;
+    const float *rois = nullptr, *boxes = nullptr;
+    const int32_t* cls = nullptr;
+    int kept = 0;
+    if ((r = ifx_mask_head_stage(h, who, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, stream, &rois, &boxes, &cls, &kept))) return r;
+    if (out_kept) *out_kept = kept;
+    if (kept > 256) { h->err = std::string(who) + ": more than 256 detections kept (raise score_thresh)"; return IFX_E_CAPACITY; }
+    MaskSource s = src_rois(rois, M, boxes, threshold, cls, kept);
+    return seg_run(h, who, s, snap, ticket, frame, flags, stream);   // (the event: the stage, and what the producer enqueued before this call)
+}
+
 extern "C" int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
 {
-    if (!h || nm < 0 || (nm > 0 && (!masks_in || !class_ids))) return IFX_E_INVALID;
-    if (nm > 256) { h->err = "too many masks"; return IFX_E_INVALID; }
-    return process_segmentation(h, rgb, depth, masks_in, class_ids, nullptr, nm, frame, flags);
+    return seg_entry(h, "ifx_process_segmentation", src_host(rgb, depth, masks_in, class_ids, nm), nullptr, frame, flags, nullptr);
 }
 extern "C" int ifx_process_segmentation_device(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream)
 {
-    if (!h) return IFX_E_INVALID;
-    if (n < 0 || n > 256) { h->err = "ifx_process_segmentation_device: n must be 0 .. 256"; return IFX_E_INVALID; }
-    if (mask_format != IFX_MASK_U8 && mask_format != IFX_MASK_F32) { h->err = "ifx_process_segmentation_device: unknown mask format"; return IFX_E_INVALID; }
-    if (n > 0 && (!d_masks || !d_class_ids)) { h->err = "ifx_process_segmentation_device: null masks or class ids"; return IFX_E_INVALID; }
-    if (h->own || h->shard_n > 1) { h->err = "ifx_process_segmentation_device: a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
-    DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_device: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
-    const int r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags);
-    h->event_pool.push_back(dm.ready);
-    return r;
-}
-// The mask head's ROI masks and boxes (maskrcnn_benchmark/modeling/roi_heads/mask_head/inference.py:91-154): argument checks shared by the three ROI entries
-static int roi_args_check(ifx* h, const char* who, const float* d_roi_masks, int roi_size, const float* d_boxes, const int32_t* d_class_ids, int n)
-{
-    if (n < 0 || n > 256) { h->err = std::string(who) + ": n must be 0 .. 256"; return IFX_E_INVALID; }
-    if (roi_size < 1 || roi_size > ROI_M_MAX) { h->err = std::string(who) + ": roi_size must be 1 .. 64"; return IFX_E_INVALID; }
-    if (n > 0 && (!d_roi_masks || !d_boxes || !d_class_ids)) { h->err = std::string(who) + ": null ROI masks, boxes or class ids"; return IFX_E_INVALID; }
-    return IFX_OK;
+    return seg_entry(h, "ifx_process_segmentation_device", src_image(d_masks, mask_format, threshold, d_class_ids, n), nullptr, frame, flags, stream);
 }
 extern "C" int ifx_process_segmentation_rois(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
                                              void* stream)
 {
-    if (!h) return IFX_E_INVALID;
-    int r = roi_args_check(h, "ifx_process_segmentation_rois", d_roi_masks, roi_size, d_boxes, d_class_ids, n);
-    if (r) return r;
-    if (h->own || h->shard_n > 1) { h->err = "ifx_process_segmentation_rois: a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
-    DevMasks dm{d_roi_masks, IFX_MASK_F32, threshold, d_class_ids, ifx_event_get(h), d_boxes, roi_size};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_rois: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
-    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags);
-    h->event_pool.push_back(dm.ready);
-    return r;
-}
-static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail);
-extern "C" int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
-                                   uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids)
-{
-    if (!h) return IFX_E_INVALID;
-    int r = roi_args_check(h, "ifx_paste_roi_masks", d_roi_masks, roi_size, d_boxes, d_class_ids, n);
-    if (r) return r;
-    if (h->own || h->shard_n > 1) { h->err = "ifx_paste_roi_masks: not on a sharded map"; return IFX_E_STATE; }
-    if (n == 0) return IFX_OK;
-    const size_t bytes = (size_t)n * h->P;
-    if ((r = ifx_ensure_masks(h, bytes))) return r;
-    DevMasks dm{d_roi_masks, IFX_MASK_F32, threshold, d_class_ids, ifx_event_get(h), d_boxes, roi_size};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_paste_roi_masks: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
-    r = seg_ingest_device(h, &dm, n, nullptr, nullptr);
-    h->event_pool.push_back(dm.ready);
-    if (r) return r;
-    if (out_ori) HIPCHK(h, hipMemcpyAsync(out_ori, h->d_masks_ori, bytes, hipMemcpyDeviceToHost, h->cur));
-    if (out_clean) HIPCHK(h, hipMemcpyAsync(out_clean, h->d_masks, bytes, hipMemcpyDeviceToHost, h->cur));
-    if (out_order) HIPCHK(h, hipMemcpyAsync(out_order, h->d_mask_rank + 256, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
-    if (out_class_ids) HIPCHK(h, hipMemcpyAsync(out_class_ids, h->d_mask_rank + 512, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
-    HIPCHK(h, hipStreamSynchronize(h->cur));
-    return IFX_OK;
-}
-// the same stage for the image-sized masks of ifx_process_segmentation_device: k_mask_area, k_mask_order and k_mask_gather as the full call launches them
-extern "C" int ifx_ingest_masks(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori, uint8_t* out_clean,
-                                int32_t* out_order, int32_t* out_class_ids)
-{
-    if (!h) return IFX_E_INVALID;
-    if (n < 0 || n > 256) { h->err = "ifx_ingest_masks: n must be 0 .. 256"; return IFX_E_INVALID; }
-    if (mask_format != IFX_MASK_U8 && mask_format != IFX_MASK_F32) { h->err = "ifx_ingest_masks: unknown mask format"; return IFX_E_INVALID; }
-    if (n > 0 && (!d_masks || !d_class_ids)) { h->err = "ifx_ingest_masks: null masks or class ids"; return IFX_E_INVALID; }
-    if (h->own || h->shard_n > 1) { h->err = "ifx_ingest_masks: not on a sharded map"; return IFX_E_STATE; }
-    if (n == 0) return IFX_OK;
-    const size_t bytes = (size_t)n * h->P;
-    int r = ifx_ensure_masks(h, bytes);
-    if (r) return r;
-    DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_ingest_masks: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
-    r = seg_ingest_device(h, &dm, n, nullptr, nullptr);
-    h->event_pool.push_back(dm.ready);
-    if (r) return r;
-    if (out_ori) HIPCHK(h, hipMemcpyAsync(out_ori, h->d_masks_ori, bytes, hipMemcpyDeviceToHost, h->cur));
-    if (out_clean) HIPCHK(h, hipMemcpyAsync(out_clean, h->d_masks, bytes, hipMemcpyDeviceToHost, h->cur));
-    if (out_order) HIPCHK(h, hipMemcpyAsync(out_order, h->d_mask_rank + 256, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
-    if (out_class_ids) HIPCHK(h, hipMemcpyAsync(out_class_ids, h->d_mask_rank + 512, (size_t)n * 4, hipMemcpyDeviceToHost, h->cur));
-    HIPCHK(h, hipStreamSynchronize(h->cur));
-    return IFX_OK;
-}
-static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
-extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
-extern "C" int ifx_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
-{
-    if (!h || nm < 0 || (nm > 0 && (!masks_in || !class_ids))) return IFX_E_INVALID;
-    if (nm > 256) { h->err = "too many masks"; return IFX_E_INVALID; }
-    SegSnap* q = nullptr;
-    int r = snap_for_call(h, "ifx_process_segmentation_deferred", ticket, flags, &q);
-    if (r) return r;
-    r = process_segmentation(h, nullptr, nullptr, masks_in, class_ids, nullptr, nm, frame, flags, q);
-    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
-    return r;
-}
-extern "C" int ifx_process_segmentation_deferred_device(ifx_t* h, int ticket, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
-                                                        void* stream)
-{
-    if (!h) return IFX_E_INVALID;
-    if (n < 0 || n > 256) { h->err = "ifx_process_segmentation_deferred_device: n must be 0 .. 256"; return IFX_E_INVALID; }
-    if (mask_format != IFX_MASK_U8 && mask_format != IFX_MASK_F32) { h->err = "ifx_process_segmentation_deferred_device: unknown mask format"; return IFX_E_INVALID; }
-    if (n > 0 && (!d_masks || !d_class_ids)) { h->err = "ifx_process_segmentation_deferred_device: null masks or class ids"; return IFX_E_INVALID; }
-    SegSnap* q = nullptr;
-    int r = snap_for_call(h, "ifx_process_segmentation_deferred_device", ticket, flags, &q);
-    if (r) return r;
-    DevMasks dm{d_masks, mask_format, threshold, d_class_ids, ifx_event_get(h)};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_deferred_device: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
-    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags, q);
-    h->event_pool.push_back(dm.ready);
-    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
-    return r;
-}
-extern "C" int ifx_process_segmentation_deferred_rois(ifx_t* h, int ticket, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n,
-                                                      int frame, int flags, void* stream)
-{
-    if (!h) return IFX_E_INVALID;
-    int r = roi_args_check(h, "ifx_process_segmentation_deferred_rois", d_roi_masks, roi_size, d_boxes, d_class_ids, n);
-    if (r) return r;
-    SegSnap* q = nullptr;
-    if ((r = snap_for_call(h, "ifx_process_segmentation_deferred_rois", ticket, flags, &q))) return r;
-    DevMasks dm{d_roi_masks, IFX_MASK_F32, threshold, d_class_ids, ifx_event_get(h), d_boxes, roi_size};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // what the producer enqueued before this call
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string("ifx_process_segmentation_deferred_rois: hipEventRecord on the producer's stream: ") + hipGetErrorString(e); return IFX_E_HIP; }
-    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, n, frame, flags, q);
-    h->event_pool.push_back(dm.ready);
-    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
-    return r;
-}
-// The mask head's logits (ifx_mask_head_select's inputs): the stage runs into the handle's scratch on the producer's stream, kept comes back, and the ROI entry's
-// path takes the scratch pointers -- seg_ingest_rois, k_roi_area, k_roi_gather and k_mask_order as they are.  snap: the deferred entry's pinned frame, or null.
-static int process_segmentation_detections(ifx* h, const char* who, SegSnap* snap, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels,
-                                           const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold, int frame,
-                                           int flags, void* stream, int32_t* out_kept)
-{
-    const float *rois = nullptr, *boxes = nullptr;
-    const int32_t* cls = nullptr;
-    int kept = 0;
-    int r = ifx_mask_head_stage(h, who, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, stream, &rois, &boxes, &cls, &kept);
-    if (r) return r;
-    if (out_kept) *out_kept = kept;
-    if (kept > 256) { h->err = std::string(who) + ": more than 256 detections kept (raise score_thresh)"; return IFX_E_CAPACITY; }
-    DevMasks dm{rois, IFX_MASK_F32, threshold, cls, ifx_event_get(h), boxes, M};
-    const hipError_t e = hipEventRecord(dm.ready, (hipStream_t)stream);   // the stage, and what the producer enqueued before this call
-    if (e != hipSuccess) { h->event_pool.push_back(dm.ready); h->err = std::string(who) + ": hipEventRecord on the producer's stream: " + hipGetErrorString(e); return IFX_E_HIP; }
-    r = process_segmentation(h, nullptr, nullptr, nullptr, nullptr, &dm, kept, frame, flags, snap);
-    h->event_pool.push_back(dm.ready);
-    return r;
+    return seg_entry(h, "ifx_process_segmentation_rois", src_rois(d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n), nullptr, frame, flags, stream);
 }
 extern "C" int ifx_process_segmentation_detections(ifx_t* h, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
                                                    const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream,
                                                    int32_t* out_kept)
 {
-    if (!h) return IFX_E_INVALID;
-    int r = ifx_mask_head_check(h, "ifx_process_segmentation_detections", d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, false);
-    if (r) return r;
-    if (h->own || h->shard_n > 1) { h->err = "ifx_process_segmentation_detections: a sharded map takes its masks from the host (ifx_owner_process_segmentation)"; return IFX_E_STATE; }
-    return process_segmentation_detections(h, "ifx_process_segmentation_detections", nullptr, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold,
-                                           frame, flags, stream, out_kept);
+    return seg_entry_detections(h, "ifx_process_segmentation_detections", nullptr, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold, frame, flags,
+                                stream, out_kept);
+}
+extern "C" int ifx_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
+{
+    return seg_entry(h, "ifx_process_segmentation_deferred", src_host(nullptr, nullptr, masks_in, class_ids, nm), &ticket, frame, flags, nullptr);
+}
+extern "C" int ifx_process_segmentation_deferred_device(ifx_t* h, int ticket, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, int frame, int flags,
+                                                        void* stream)
+{
+    return seg_entry(h, "ifx_process_segmentation_deferred_device", src_image(d_masks, mask_format, threshold, d_class_ids, n), &ticket, frame, flags, stream);
+}
+extern "C" int ifx_process_segmentation_deferred_rois(ifx_t* h, int ticket, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n,
+                                                      int frame, int flags, void* stream)
+{
+    return seg_entry(h, "ifx_process_segmentation_deferred_rois", src_rois(d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n), &ticket, frame, flags, stream);
 }
 extern "C" int ifx_process_segmentation_deferred_detections(ifx_t* h, int ticket, const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels,
                                                             const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold,
                                                             int frame, int flags, void* stream, int32_t* out_kept)
 {
-    if (!h) return IFX_E_INVALID;
-    int r = ifx_mask_head_check(h, "ifx_process_segmentation_deferred_detections", d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, false);
-    if (r) return r;
-    SegSnap* q = nullptr;
-    if ((r = snap_for_call(h, "ifx_process_segmentation_deferred_detections", ticket, flags, &q))) return r;
-    r = process_segmentation_detections(h, "ifx_process_segmentation_deferred_detections", q, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p,
-                                        threshold, frame, flags, stream, out_kept);
-    if (r == IFX_OK) ifx_segmentation_snapshot_release(h, ticket);
-    return r;
+    return seg_entry_detections(h, "ifx_process_segmentation_deferred_detections", &ticket, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold, frame,
+                                flags, stream, out_kept);
+}
+extern "C" int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
+                                   uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids)
+{
+    return seg_stage_entry(h, "ifx_paste_roi_masks", src_rois(d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n), stream, out_ori, out_clean, out_order, out_class_ids);
+}
+extern "C" int ifx_ingest_masks(ifx_t* h, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori, uint8_t* out_clean,
+                                int32_t* out_order, int32_t* out_class_ids)
+{
+    return seg_stage_entry(h, "ifx_ingest_masks", src_image(d_masks, mask_format, threshold, d_class_ids, n), stream, out_ori, out_clean, out_order, out_class_ids);
 }
 static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
                                 SegSnap* snap)
@@ -1586,23 +1574,8 @@ static int seg_host_mask_loop(ifx* h, const SegView& v, int nm, const int32_t* c
                 h->clean_times++;
                 HIPCHK(h, hipMemsetAsync(h->d_inst_stats, 0, NI * 2 * 4, h->cur));
                 LAUNCH(h, "max_count", dim3(1024), dim3(256), k_max_count, h->d_state, (const float4*)h->votes, h->cap, (const float2*)h->tm, h->d_inst_stats, h->d_inst_stats + NI);
-                int stats[NI * 2];
-                HIPCHK(h, hipMemcpyAsync(stats, h->d_inst_stats, sizeof(stats), hipMemcpyDeviceToHost, h->cur));
-                HIPCHK(h, hipStreamSynchronize(h->cur));
-                // getInstanceTableCleanList, IF/Core/InstanceTable.cpp:185-224
-                int* maxv = stats; int* sumv = stats + NI;
-                int order[NI], cl[NI];
-                for (int i = 0; i < NI; i++) order[i] = i;
-                for (int i = 0; i < NI; i++)
-                    for (int j = i + 1; j < NI; j++)
-                        if ((float)sumv[j] < (float)sumv[i]) { std::swap(maxv[i], maxv[j]); std::swap(order[i], order[j]); std::swap(sumv[i], sumv[j]); }
-                for (int i = 0; i < NI; i++) cl[i] = 0;
-                for (int i = 0; i < 20; i++) cl[order[i]] = 1;
-                for (int q = 0; q < NI; q++) if (cl[q] == 1) h->inst_class[q] = -1;
-                HIPCHK(h, hipMemcpyAsync(h->d_clean_list, cl, sizeof(cl), hipMemcpyHostToDevice, h->cur));
-                LAUNCH(h, "clean_table", dim3(1024), dim3(256), k_clean_table, h->d_state, h->votes, h->cap, h->d_clean_list);
+                if ((r = seg_evict_weakest(h))) return r;
                 h->labels_stale_all = 1;   // votes of every surfel that carried an evicted instance changed
-                HIPCHK(h, hipStreamSynchronize(h->cur));
                 r = run_bboxes(h, v, nm, bbox);
                 if (r) return r;
                 std::fill(cmp.begin(), cmp.end(), 0);
@@ -1687,12 +1660,12 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
     // (ifx_map.hip "View list") is unstable, so it was never in an id image, carries no votes and takes part in nothing else of this call.
     if (flags & 1) ifx_vlist_reap(h);
     h->seg_counts_valid = 0;
-    hipEvent_t ea = ifx_event_get(h);
-    hipEventRecord(ea, h->cur);
+    PoolEvent ea(h);   // (given back on every return but the last, where stage_pending takes it)
+    hipEventRecord(ea.ev, h->cur);
     HIPCHK(h, hipStreamSynchronize(h->cur));
     int n = 0;
     HIPCHK(h, hipMemcpy(&n, &h->d_state->count, sizeof(int), hipMemcpyDeviceToHost));
-    if (nm == 0 || n == 0) { h->event_pool.push_back(ea); return IFX_OK; }
+    if (nm == 0 || n == 0) return IFX_OK;
     const int P = h->P;
     size_t mbytes = (size_t)nm * P;
     std::vector<uint8_t> unavailable(nm, 0);
@@ -1737,9 +1710,7 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
     seg_label_scan(h, v);
     // flannKnnVoteSurfelMap (isflann, :1051)
     if (flags & 1) { r = ifx_knn_vote(h, nullptr); if (r) return r; }
-    hipEvent_t eb = ifx_event_get(h);
-    hipEventRecord(eb, h->cur);
-    h->stage_pending.push_back({2, {ea, eb}});
+    ifx_stage_span_end(h, 2, ea);
     HIPCHK(h, hipStreamSynchronize(h->cur));
     return IFX_OK;
 }
@@ -2101,6 +2072,29 @@ int ifx_frame_for_reader(ifx* h, const char* who, int ticket, const uint8_t** rg
     return IFX_OK;
 }
 
+// The tail of the device schedule: registration, the votes in mask order, the gated label scan, the control block and the verdict bytes read back into the pinned
+// block (SegCtl, then nm bytes), and the wait for them.  gate / meta / skip: the flood fill's counters for the first pass (k_seg_register), nulls for the pass after
+// the host finished an incomplete fill.  enqueued(): called between the last enqueue and the wait (IFX_SEG_TRACE).  Returns 1 when the scan enqueued was the full one.
+template <typename F>
+static int seg_device_tail(ifx* h, const SegView& v, int nm, const int* gate, const int* meta, const uint8_t* skip, bool default_done, F&& enqueued)
+{
+    const int P = h->P;
+    SegCtl* hc = (SegCtl*)h->h_segctl;
+    SegCtl* dc = (SegCtl*)h->d_segctl;
+    LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, gate, meta, skip);
+    for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
+        LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, v.ids, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
+    // the scan kernels look at the control block themselves: when the call has to be finished by the host (fill incomplete / table full) they return at once and
+    // the ONE scan of the call runs behind the host-driven tail, after every mask and the eviction -- colours are assigned once, so an early scan would be visible
+    const int full_scan = seg_label_scan(h, v, (const int*)dc, default_done);
+    uint8_t* h_un = (uint8_t*)h->h_segctl + sizeof(SegCtl);
+    HIPCHK(h, hipMemcpyAsync(hc, dc, sizeof(SegCtl), hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipMemcpyAsync(h_un, h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));
+    enqueued();
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return full_scan;
+}
+
 static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
                                        SegSnap* snap)
 {
@@ -2124,12 +2118,12 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     if (r) return r;
     if ((r = seg_ensure_ctl(h, dm ? 0 : mbytes))) return r;   // (device masks: no staging)
     SegCtl* hc = (SegCtl*)h->h_segctl;
-    hipEvent_t ea = ifx_event_get(h);
-    hipEventRecord(ea, h->cur);
+    PoolEvent ea(h);   // (given back on every return but the last, where stage_pending takes it)
+    hipEventRecord(ea.ev, h->cur);
     SegView v = seg_view_current(h);
-    if (snap && (r = seg_view_snapshot(h, snap, &v))) { h->event_pool.push_back(ea); return r; }   // (deferred call: the pinned id image re-addressed in today's slots, the pinned pose and frame)
+    if (snap && (r = seg_view_snapshot(h, snap, &v))) return r;   // (deferred call: the pinned id image re-addressed in today's slots, the pinned pose and frame)
     if (flags & 2) {   // superpixels and their merge: on the queue before the masks are even copied (they need the frame only)
-        if ((r = v.d_rgb ? ifx_superpixel_begin_device(h, v.d_rgb, v.d_depth) : ifx_superpixel_begin(h, rgb, depth))) { h->event_pool.push_back(ea); return r; }
+        if ((r = v.d_rgb ? ifx_superpixel_begin_device(h, v.d_rgb, v.d_depth) : ifx_superpixel_begin(h, rgb, depth))) return r;
     }
     // what needs the map and the id image but not the masks -- the boxes of the projected instances (the twelve vote float4 under every pixel: the heavy half of
     // getProjectInstanceList / computeProjectBoundingBox) and the model depth under every pixel -- runs while the host copies the masks into pinned memory
@@ -2166,30 +2160,17 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     if (r) return r;
     const FFArgs fa = ff_args(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm);
     const int* gate = fa.changed + (std::min(rounds, FF_SLOTS) - 1);
-    LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, gate, (const int*)fa.meta, fa.skip);
-    for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
-            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, v.ids, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
-    // the scan kernels look at the control block themselves: when the call has to be finished by the host (fill incomplete / table full) they return at once and
-    // the ONE scan of the call runs behind the host-driven tail, after every mask and the eviction -- colours are assigned once, so an early scan would be visible
-    const int full_scan = seg_label_scan(h, v, (const int*)dc, default_early);
-    uint8_t* h_un = (uint8_t*)h->h_segctl + sizeof(SegCtl);
-    HIPCHK(h, hipMemcpyAsync(hc, dc, sizeof(SegCtl), hipMemcpyDeviceToHost, h->cur));
-    HIPCHK(h, hipMemcpyAsync(h_un, h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));
-    t_enq = us();
-    HIPCHK(h, hipStreamSynchronize(h->cur));
+    const int full_scan = seg_device_tail(h, v, nm, gate, (const int*)fa.meta, fa.skip, default_early, [&] { t_enq = us(); });
+    if (full_scan < 0) return full_scan;
+    const uint8_t* h_un = (const uint8_t*)h->h_segctl + sizeof(SegCtl);
     t_sync = us();
     if (trace) fprintf(stderr, "seg call: result %.0f  ids %.0f  staged %.0f  enqueued %.0f  synced %.0f us (nm %d)\n", t_res, t_ids, t_stage, t_enq, t_sync, nm);
     if ((hc->ff_incomplete || hc->evict_at >= 0) && full_scan) h->labels_stale_all = 1;   // the gated scan did not run: whatever made it a full one still holds
     if (hc->ff_incomplete) {   // the fill needs more relaxations than the schedule holds: finish it with the host looking, then the tail again (nothing was voted yet)
         r = mask_geometric_filter_device(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm, h->d_unavail, 0, true);
         if (r) return r;
-        LAUNCH(h, "seg_register", dim3(1), dim3(64), k_seg_register, dc, h->d_unavail, (const int*)nullptr, (const int*)nullptr, (const uint8_t*)nullptr);
-        for (int m_ = 0; m_ < nm; m_++)   // (mask order is part of the result: see k_vote_update_mask)
-            LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update_mask, h->d_state, v.ids, (const uint8_t*)h->d_masks, P, h->cap, (const SegCtl*)dc, nm, h->votes, ifx_idmap(h), m_);
-        const int full2 = seg_label_scan(h, v, (const int*)dc);   // (gated again: the table may turn out full at some mask)
-        HIPCHK(h, hipMemcpyAsync(hc, dc, sizeof(SegCtl), hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipMemcpyAsync(h_un, h->d_unavail, nm, hipMemcpyDeviceToHost, h->cur));
-        HIPCHK(h, hipStreamSynchronize(h->cur));
+        const int full2 = seg_device_tail(h, v, nm, nullptr, nullptr, nullptr, false, [] {});   // (gated again: the table may turn out full at some mask)
+        if (full2 < 0) return full2;
         if (hc->evict_at >= 0 && full2) h->labels_stale_all = 1;
     }
     for (int i = 0; i < NI; i++) h->inst_class[i] = hc->inst_class[i];
@@ -2202,9 +2183,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         seg_label_scan(h, v);
     }
     if (flags & 1) { r = ifx_knn_vote(h, nullptr); if (r) return r; }
-    hipEvent_t eb = ifx_event_get(h);
-    hipEventRecord(eb, h->cur);
-    h->stage_pending.push_back({2, {ea, eb}});
+    ifx_stage_span_end(h, 2, ea);
     HIPCHK(h, hipStreamSynchronize(h->cur));
     return IFX_OK;
 }

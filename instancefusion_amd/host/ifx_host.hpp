@@ -204,6 +204,12 @@ struct Sharding {
 };
 
 // ------------------------------------------------------------------------------------------------ ElasticFusion
+// what every entry that needs the map's handle says when there is none (ifx_create failed: ifx_global_error() has the reason)
+inline ifx_t* require_handle(ifx_t* h, const char* who)
+{
+    if (!h) throw std::runtime_error(std::string(who) + ": the map has no handle (" + ifx_global_error() + ")");
+    return h;
+}
 class ElasticFusion {
 public:
     // EF/ElasticFusion.h:47-62, same order and defaults.  closeLoops turns the local loop-closure DETECTION on (ifx_set_loop_closure with
@@ -448,13 +454,13 @@ public:
     void RoiAlignForward(const float* d_input, int batch, int channels, int height, int width, const float* d_rois, int n, float spatial_scale, int pooled_h, int pooled_w,
                          int sampling_ratio, float* d_out, void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::RoiAlignForward: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::RoiAlignForward");
         if (ifx_roi_align_forward(h_, d_input, batch, channels, height, width, d_rois, n, spatial_scale, pooled_h, pooled_w, sampling_ratio, d_out, stream) < 0)
             throw std::runtime_error(std::string("ifx_roi_align_forward: ") + ifx_last_error(h_));
     }
     void Nms(const float* d_boxes, const float* d_scores, const int32_t* d_groups, int n, float threshold, int64_t* d_keep, int32_t* d_count, void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::Nms: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::Nms");
         if (ifx_nms(h_, d_boxes, d_scores, d_groups, n, threshold, d_keep, d_count, stream) < 0) throw std::runtime_error(std::string("ifx_nms: ") + ifx_last_error(h_));
     }
 
@@ -466,7 +472,7 @@ public:
                      const float* d_rois, int n, int pooled_h, int pooled_w, int sampling_ratio, float* d_out, int32_t* d_levels, void* stream,
                      float canonical_scale = 224.f, int canonical_level = 4, float eps = 1e-6f)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::FpnRoiAlign: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::FpnRoiAlign");
         if (ifx_fpn_roi_align(h_, d_features, heights, widths, scales, levels, batch, channels, d_rois, n, canonical_scale, canonical_level, eps, pooled_h, pooled_w,
                               sampling_ratio, d_out, d_levels, stream) < 0)
             throw std::runtime_error(std::string("ifx_fpn_roi_align: ") + ifx_last_error(h_));
@@ -479,7 +485,7 @@ public:
     void RpnProposals(const float* d_objectness, const float* d_regression, const float* d_anchors, int A, int H, int W, const ifx_rpn_params& p, float* d_boxes,
                       float* d_logits, int64_t* d_index, int32_t* d_count, void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::RpnProposals: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::RpnProposals");
         if (ifx_rpn_proposals(h_, d_objectness, d_regression, d_anchors, A, H, W, &p, d_boxes, d_logits, d_index, d_count, stream) < 0)
             throw std::runtime_error(std::string("ifx_rpn_proposals: ") + ifx_last_error(h_));
     }
@@ -489,13 +495,13 @@ public:
     void RpnProposalsFpn(const ifx_rpn_level* levels, int n_levels, const ifx_rpn_params& p, int fpn_post_nms_top_n, float* d_boxes, float* d_logits, int32_t* d_level,
                          int64_t* d_index, int32_t* d_count, int32_t* d_level_counts, void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::RpnProposalsFpn: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::RpnProposalsFpn");
         if (ifx_rpn_proposals_fpn(h_, levels, n_levels, &p, fpn_post_nms_top_n, d_boxes, d_logits, d_level, d_index, d_count, d_level_counts, stream) < 0)
             throw std::runtime_error(std::string("ifx_rpn_proposals_fpn: ") + ifx_last_error(h_));
     }
     void BoxDecode(const float* d_codes, const float* d_boxes, int n, int k, const float weights[4], float xform_clip, int clip_w, int clip_h, float* d_out, void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::BoxDecode: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::BoxDecode");
         if (ifx_box_decode(h_, d_codes, d_boxes, n, k, weights, xform_clip, clip_w, clip_h, d_out, stream) < 0)
             throw std::runtime_error(std::string("ifx_box_decode: ") + ifx_last_error(h_));
     }
@@ -505,7 +511,7 @@ public:
     void BoxDetections(const float* d_logits, const float* d_regression, const float* d_proposals, int R, int C, int Creg, const ifx_box_det_params& p, float* d_boxes,
                        float* d_scores, int64_t* d_labels, int64_t* d_index, int32_t* d_count, int32_t* d_stats, void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::BoxDetections: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::BoxDetections");
         if (ifx_box_detections(h_, d_logits, d_regression, d_proposals, R, C, Creg, &p, d_boxes, d_scores, d_labels, d_index, d_count, d_stats, stream) < 0)
             throw std::runtime_error(std::string("ifx_box_detections: ") + ifx_last_error(h_));
     }
@@ -518,7 +524,7 @@ public:
                         int R, int C, int M, const ifx_mask_head_params& p, float* d_roi_masks, float* d_boxes_out, int32_t* d_class_ids, int32_t* d_rows, int32_t* d_kept,
                         void* stream)
     {
-        if (!h_) throw std::runtime_error(std::string("ElasticFusion::MaskHeadSelect: the map has no handle (") + ifx_global_error() + ")");
+        require_handle(h_, "ElasticFusion::MaskHeadSelect");
         if (ifx_mask_head_select(h_, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, d_roi_masks, d_boxes_out, d_class_ids, d_rows, d_kept,
                                  stream) < 0)
             throw std::runtime_error(std::string("ifx_mask_head_select: ") + ifx_last_error(h_));
@@ -998,13 +1004,11 @@ public:
         if (!source_) throw std::runtime_error("InstanceFusion::ProcessSegmentation: no mask source");
         MaskResult res;
         if (!source_->detect(frame_num, rgb, width, height, &res)) return;
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
-        const bool sharded = map->elasticFusion().sharding().on();   // the owners' boxes / model depth / eviction statistics are merged inside the library
-        const int r = sharded ? ifx_owner_process_segmentation(map->handle(), rgb, depth, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags)
-                              : ifx_process_segmentation(map->handle(), rgb, depth, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
-        if (r < 0) throw std::runtime_error(std::string(sharded ? "ifx_owner_process_segmentation: " : "ifx_process_segmentation: ") + ifx_last_error(map->handle()));
-        handle_ = map->handle();
-        segmentations_++;
+        // (a sharded map: the owners' boxes / model depth / eviction statistics are merged inside the library)
+        seg_call("InstanceFusion::ProcessSegmentation", "ifx_process_segmentation", "ifx_owner_process_segmentation", map, isflann, [&](ifx_t* h, int flags) {
+            return map->elasticFusion().sharding().on() ? ifx_owner_process_segmentation(h, rgb, depth, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags)
+                                                        : ifx_process_segmentation(h, rgb, depth, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
+        });
     }
     // The same call on a detector's raw output already in device memory of the map's GPU (ifx_process_segmentation_device): d_masks n x H x W in any order,
     // format IFX_MASK_U8 (inside iff non-zero) or IFX_MASK_F32 (inside iff > threshold), d_class_ids n int32 on the device, stream the HIP stream the detector
@@ -1012,15 +1016,9 @@ public:
     void ProcessSegmentationDevice(const std::unique_ptr<ElasticFusionInterface>& map, const void* d_masks, int format, float threshold, const int32_t* d_class_ids, int n,
                                    int frame_num, bool isflann, void* stream)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDevice: the map has no handle (") + ifx_global_error() + ")");
-        if (map->elasticFusion().sharding().on())
-            throw std::runtime_error("InstanceFusion::ProcessSegmentationDevice: a sharded map takes its masks from the host (ProcessSegmentation)");
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
-        const int r = ifx_process_segmentation_device(h, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_device: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationDevice", "ifx_process_segmentation_device", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_device(h, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
     }
 
     // ---- a detector slower than the frame loop (ifx_segmentation_snapshot / ifx_process_segmentation_deferred; the reference's detector thread is off, IF/main.cpp:83).
@@ -1030,8 +1028,7 @@ public:
     // caller to hold until then.  Not on a sharded map.
     int SnapshotSegmentation(const std::unique_ptr<ElasticFusionInterface>& map)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::SnapshotSegmentation: the map has no handle (") + ifx_global_error() + ")");
+        ifx_t* h = require_handle(map ? map->handle() : nullptr, "InstanceFusion::SnapshotSegmentation");
         const int t = ifx_segmentation_snapshot(h, superpixels_ ? 2 : 0);
         if (t < 0) throw std::runtime_error(std::string("ifx_segmentation_snapshot: ") + ifx_last_error(h));
         return t;
@@ -1043,22 +1040,16 @@ public:
     }
     void ProcessSegmentationDeferred(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const MaskResult& res, int frame_num, bool isflann)
     {
-        ifx_t* h = map->handle();
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
-        const int r = ifx_process_segmentation_deferred(h, ticket, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationDeferred", "ifx_process_segmentation_deferred", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_deferred(h, ticket, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
+        });
     }
     void ProcessSegmentationDeferredDevice(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const void* d_masks, int format, float threshold, const int32_t* d_class_ids,
                                            int n, int frame_num, bool isflann, void* stream)
     {
-        ifx_t* h = map->handle();
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
-        const int r = ifx_process_segmentation_deferred_device(h, ticket, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_device: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationDeferredDevice", "ifx_process_segmentation_deferred_device", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_deferred_device(h, ticket, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
     }
     // ---- the mask head's own output (ifx_process_segmentation_rois): d_roi_masks n x M x M f32 probabilities and d_boxes n x 4 f32 (x0, y0, x1, y1, frame pixels) in
     // device memory of the map's GPU, pasted there as maskrcnn-benchmark's Masker pastes them on the CPU (paste_mask_in_image,
@@ -1066,28 +1057,16 @@ public:
     void ProcessSegmentationRois(const std::unique_ptr<ElasticFusionInterface>& map, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold,
                                  const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationRois: the map has no handle (") + ifx_global_error() + ")");
-        if (map->elasticFusion().sharding().on())
-            throw std::runtime_error("InstanceFusion::ProcessSegmentationRois: a sharded map takes its masks from the host (ProcessSegmentation)");
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
-        const int r = ifx_process_segmentation_rois(h, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_rois: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationRois", "ifx_process_segmentation_rois", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_rois(h, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
     }
     void ProcessSegmentationDeferredRois(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold,
                                          const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDeferredRois: the map has no handle (") + ifx_global_error() + ")");
-        if (map->elasticFusion().sharding().on())
-            throw std::runtime_error("InstanceFusion::ProcessSegmentationDeferredRois: a sharded map takes its masks from the host (ProcessSegmentation)");
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
-        const int r = ifx_process_segmentation_deferred_rois(h, ticket, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_rois: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationDeferredRois", "ifx_process_segmentation_deferred_rois", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_deferred_rois(h, ticket, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
     }
     // ---- the mask head's logits and the box head's detections (ifx_process_segmentation_detections): ElasticFusion::MaskHeadSelect's inputs in device memory of the
     // map's GPU, p.out_w x p.out_h taken from the map's frame size.  The stage (MaskPostProcessor.forward, BoxList.resize, select_top_predictions,
@@ -1097,34 +1076,21 @@ public:
                                       const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params& p,
                                       float threshold, int frame_num, bool isflann, void* stream)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDetections: the map has no handle (") + ifx_global_error() + ")");
-        if (map->elasticFusion().sharding().on())
-            throw std::runtime_error("InstanceFusion::ProcessSegmentationDetections: a sharded map takes its masks from the host (ProcessSegmentation)");
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
         int32_t kept = 0;
-        const int r = ifx_process_segmentation_detections(h, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, threshold, frame_num, flags, stream,
-                                                          &kept);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_detections: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationDetections", "ifx_process_segmentation_detections", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_detections(h, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, threshold, frame_num, flags, stream, &kept);
+        });
         return kept;
     }
     int ProcessSegmentationDeferredDetections(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const float* d_mask_logits, const float* d_boxes,
                                               const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
                                               const ifx_mask_head_params& p, float threshold, int frame_num, bool isflann, void* stream)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::ProcessSegmentationDeferredDetections: the map has no handle (") + ifx_global_error() + ")");
-        if (map->elasticFusion().sharding().on())
-            throw std::runtime_error("InstanceFusion::ProcessSegmentationDeferredDetections: a sharded map takes its masks from the host (ProcessSegmentation)");
-        const int flags = (isflann ? 1 : 0) | (superpixels_ ? 2 : 0);
         int32_t kept = 0;
-        const int r = ifx_process_segmentation_deferred_detections(h, ticket, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, threshold,
-                                                                   frame_num, flags, stream, &kept);
-        if (r < 0) throw std::runtime_error(std::string("ifx_process_segmentation_deferred_detections: ") + ifx_last_error(h));
-        handle_ = h;
-        segmentations_++;
+        seg_call("InstanceFusion::ProcessSegmentationDeferredDetections", "ifx_process_segmentation_deferred_detections", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_deferred_detections(h, ticket, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, &p, threshold,
+                                                                frame_num, flags, stream, &kept);
+        });
         return kept;
     }
     // ---- the opposite direction: the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input).  What
@@ -1145,8 +1111,7 @@ public:
     }
     void DetectorInput(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const ifx_detector_prep& prep, float* d_out, int64_t out_floats, void* stream)
     {
-        ifx_t* h = map ? map->handle() : nullptr;
-        if (!h) throw std::runtime_error(std::string("InstanceFusion::DetectorInput: the map has no handle (") + ifx_global_error() + ")");
+        ifx_t* h = require_handle(map ? map->handle() : nullptr, "InstanceFusion::DetectorInput");
         if (ifx_detector_input(h, ticket, &prep, d_out, out_floats, stream) < 0) throw std::runtime_error(std::string("ifx_detector_input: ") + ifx_last_error(h));
     }
     void ReleaseSnapshot(const std::unique_ptr<ElasticFusionInterface>& map, int ticket)
@@ -1277,6 +1242,18 @@ public:
     }
 
 private:
+    // One segmentation entry of the C ABI: the handle (a null map included), the refusal of a sharded map unless the entry has an owners' form (owner_cname), the
+    // flags, the call, the library's message under the C name on failure, the two counters.
+    template <typename F>
+    void seg_call(const char* who, const char* cname, const char* owner_cname, const std::unique_ptr<ElasticFusionInterface>& map, bool isflann, F&& call)
+    {
+        ifx_t* h = require_handle(map ? map->handle() : nullptr, who);
+        const bool sharded = map->elasticFusion().sharding().on();
+        if (sharded && !owner_cname) throw std::runtime_error(std::string(who) + ": a sharded map takes its masks from the host (ProcessSegmentation)");
+        if (call(h, (isflann ? 1 : 0) | (superpixels_ ? 2 : 0)) < 0) throw std::runtime_error(std::string(sharded ? owner_cname : cname) + ": " + ifx_last_error(h));
+        handle_ = h;
+        segmentations_++;
+    }
     int instanceNum, width, height;
     std::shared_ptr<MaskSource> source_;
     ifx_t* handle_ = nullptr;
