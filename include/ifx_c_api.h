@@ -836,6 +836,53 @@ int ifx_process_segmentation_detections(ifx_t* h, const float* d_mask_logits, co
 int ifx_process_segmentation_deferred_detections(ifx_t* h, int ticket, const float* d_mask_logits, const float* d_boxes, const float* d_scores,
                                                  const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
                                                  const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept);
+/* ---- the three device forms on a spatially sharded map: a deployment has ONE detector, on one rank's GPU (no counterpart in the reference: one GPU, host masks).
+ * ifx_owner_segmentation_begin_device / _rois / _detections join the state machine of ifx_owner_segmentation_begin: 1 = an exchange point is pending (reduce what
+ * ifx_owner_exchange(h, 200, ...) lists, then ifx_owner_segmentation_resume), 0 = complete.  ifx_owner_process_segmentation_device / _rois / _detections are the
+ * same in one call each, the exchanges done on the handle's communicator (flags bit 0 then runs ifx_owner_knn_vote_colour, as ifx_owner_process_segmentation does).
+ *   rgb, depth     host pointers for the superpixel refinement (flags bit 1), exactly as ifx_owner_segmentation_begin takes them; read before the begin form returns.
+ *   tensors        as the unsharded entry of the same name documents them: formats, the threshold rule, the ROI paste, roi_size 1 .. 64, the mask head's stage.
+ *   root = -1      every rank holds the tensors and ingests its own copy; no record, no extra exchange point; n == 0 returns 0 at once.
+ *   root = r       (0 <= r < n_ranks; 0 for n_ranks = -1) only rank r's tensor pointers, n, d_count, R, C, p and stream are read; the other ranks may pass NULL / 0.
+ *                  max_n (1 .. 256), roi_size / M, the form, threshold (ROI and detections forms: every rank applies its own to the record's ROI masks) and the
+ *                  flags must be equal on all ranks.  max_n is the record's capacity: n > max_n on rank r is IFX_E_INVALID.
+ * With root = r the call's FIRST exchange point is the record: ifx_owner_exchange(h, 200, ...) lists exactly one buffer, the record, with its size in bytes (a
+ * multiple of 4, a function of form, max_n, M and the frame size only) and op 4 | r << 8 (broadcast from rank r).  Rank r wrote it on its main stream behind an
+ * event recorded on `stream`: no host synchronisation.  The first resume reads the header (one 32-byte copy), checks it against this rank's arguments -- a wrong
+ * magic, form, M, P or max_n means the ranks disagree: IFX_E_STATE, the call is over --, ingests from the record on every rank, rank r included (identical kernels
+ * on identical bytes), and goes on into the exchange points of the host form (option own_lazy_ids' keys, the boxes, ...).  n == 0 in the header ends the call with
+ * 0 on every rank after that one exchange.  The record is one allocation per handle, grown on demand: a repeated call of the same sizes allocates nothing.
+ * The record, int32 words (P = width x height):
+ *   header[8]   magic 0x49465852, form (1 image bits, 2 ROI masks), n, M (form 1: 0), P, max_n, 0, 0
+ *   cls[max_n]  the caller's class ids in the caller's order (detections form: of the kept rows, after d_class_map); rows >= n are zero
+ *   form 2      boxes f32[max_n][4], rois f32[max_n][M][M]; rows >= n are zero
+ *   form 1      bits u32[max_n][ceil(P / 32)]: bit b of word j of mask m = pixel 32 j + b of mask m, binarised by the bridge's rule (u8 / bool: non-zero;
+ *               f32: > threshold, a NaN is outside); bits past P and rows >= n are zero
+ * The ingest from bits (popcount areas, the bridge's stable order, the gather with the overlap clean) leaves byte for byte the masks and sorted class ids that
+ * ifx_process_segmentation_device's ingestion makes of the same tensors; form 2 runs the ROI entry's ingestion on pointers into the record.
+ * Detections form: the mask head's stage runs on the reading rank(s) only; *out_kept is written there.  More kept rows than max_n: IFX_E_CAPACITY -- from the begin
+ * form with root = -1; with root = r the record carries the count and no rows, so that EVERY rank's first resume returns IFX_E_CAPACITY and the call is over everywhere.
+ * Refusals (nothing enqueued, the handle stays usable, ifx_last_error starts with the entry's name): IFX_E_STATE for a handle not created for a sharded map and for
+ * a call already in flight; IFX_E_INVALID for flags bit 0 on a begin form, root outside -1 .. n_ranks - 1, max_n outside 1 .. 256, roi_size / M outside 1 .. 64
+ * (every rank), n > max_n and whatever the unsharded entry of the form refuses in its arguments (the reading rank).  A refusal on rank r alone leaves the other
+ * ranks waiting at the record's exchange point, and a header mismatch ends the call only on the ranks that see it (rank r's own header always matches): a rank
+ * whose peers' call is over ends its own with ifx_owner_segmentation_abort (any form of the call, the host form too; 0 when nothing is in flight; the next call's
+ * label scan then covers every surfel). */
+int ifx_owner_segmentation_abort(ifx_t* h);
+int ifx_owner_segmentation_begin_device(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const void* d_masks, int mask_format, float threshold,
+                                        const int32_t* d_class_ids, int n, int frame, int flags, void* stream);
+int ifx_owner_segmentation_begin_rois(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_roi_masks, int roi_size, const float* d_boxes,
+                                      float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream);
+int ifx_owner_segmentation_begin_detections(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_mask_logits, const float* d_boxes,
+                                            const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
+                                            const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept);
+int ifx_owner_process_segmentation_device(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const void* d_masks, int mask_format, float threshold,
+                                          const int32_t* d_class_ids, int n, int frame, int flags, void* stream);
+int ifx_owner_process_segmentation_rois(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_roi_masks, int roi_size, const float* d_boxes,
+                                        float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream);
+int ifx_owner_process_segmentation_detections(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_mask_logits, const float* d_boxes,
+                                              const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
+                                              const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

@@ -109,6 +109,7 @@ _SIGS = {
     "ifx_owner_of": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ifx_owner_segmentation_begin": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
     "ifx_owner_segmentation_resume": (C.c_int, [_P]),
+    "ifx_owner_segmentation_abort": (C.c_int, [_P]),
     "ifx_owner_ids_begin": (C.c_int, [_P]),
     "ifx_owner_ids_resume": (C.c_int, [_P]),
     "ifx_owner_knn_export": (C.c_int, [_P, _P, _P, _P]),
@@ -207,6 +208,15 @@ _SIGS = {
     "ifx_process_segmentation_detections": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float, C.c_int, C.c_int, _P, _P]),
     "ifx_process_segmentation_deferred_detections": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float, C.c_int,
                                                                C.c_int, _P, _P]),
+    # the device forms on a sharded map: (h, root, max_n, rgb, depth) in front of the unsharded entry's arguments
+    "ifx_owner_segmentation_begin_device": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_owner_segmentation_begin_rois": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_owner_segmentation_begin_detections": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float,
+                                                          C.c_int, C.c_int, _P, _P]),
+    "ifx_owner_process_segmentation_device": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_owner_process_segmentation_rois": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_owner_process_segmentation_detections": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float,
+                                                          C.c_int, C.c_int, _P, _P]),
     "ifx_segmentation_snapshot_release": (C.c_int, [_P, C.c_int]),
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),

@@ -1177,6 +1177,7 @@ extern "C" int ifx_owner_exchange(ifx_t* h, int phase, void** ptrs, int64_t* byt
         case 1: add(h->d_bbox, (size_t)(96 + h->oseg_nm) * 4 * 4, 2); break;                       // boxes, maxima negated: MIN of 32-bit words
         case 2: add(h->d_pdm, P * 2, 1); break;                                                     // model depth under the camera: disjoint supports
         case 3: add(h->d_inst_stats, 96 * 4, 3); add(h->d_inst_stats + 96, 96 * 4, 1); break;      // per-instance maximum (MAX) and sum (SUM) of the vote counters
+        case 4: add(h->oseg_rec, h->oseg_rec_bytes, 4 | (h->oseg_root << 8)); break;               // the record of a device form, broadcast from the detector's rank
         default: break;
         }
         break;

@@ -310,15 +310,9 @@ extern "C" int ifx_owner_knn_vote_colour(ifx_t* h)
     return ifx_owner_knn_vote(h, allp, alll, (int)total, (int)my_off);
 }
 
-// InstanceFusion::processInstance on the sharded map in one call: the begin / resume state machine of ifx_instance.hip with the exchanges done here.
-// flags bit 0 (kNN smoothing of the colours) runs ifx_owner_knn_vote_colour after the call.
-extern "C" int ifx_owner_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks, const int32_t* class_ids, int nm, int frame, int flags)
+// r: what a begin form returned -- the exchange points of the call until it is complete, then the kNN smoothing (flags bit 0)
+static int comm_seg_run(ifx* h, int r, int flags)
 {
-    if (!h) return IFX_E_INVALID;
-    int r = comm_check(h, "ifx_owner_process_segmentation");
-    if (r) return r;
-    if (!ifx_comm_ready(h)) { h->err = "no communicator: ifx_owner_init_comm / ifx_owner_set_comm first"; return IFX_E_STATE; }
-    r = ifx_owner_segmentation_begin(h, rgb, depth, masks, class_ids, nm, frame, flags & ~1);
     while (r == 1) {
         r = ifx_comm_exchange(h, 200);
         if (r) { h->oseg_state = 0; h->oseg_pending = 0; return r; }   // a failed call is over: the next one starts from scratch
@@ -327,4 +321,49 @@ extern "C" int ifx_owner_process_segmentation(ifx_t* h, const uint8_t* rgb, cons
     if (r) return r;
     if (flags & 1) return ifx_owner_knn_vote_colour(h);
     return IFX_OK;
+}
+// InstanceFusion::processInstance on the sharded map in one call: the begin / resume state machine of ifx_instance.hip with the exchanges done here.
+// flags bit 0 (kNN smoothing of the colours) runs ifx_owner_knn_vote_colour after the call.
+extern "C" int ifx_owner_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks, const int32_t* class_ids, int nm, int frame, int flags)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = comm_check(h, "ifx_owner_process_segmentation");
+    if (r) return r;
+    if (!ifx_comm_ready(h)) { h->err = "no communicator: ifx_owner_init_comm / ifx_owner_set_comm first"; return IFX_E_STATE; }
+    return comm_seg_run(h, ifx_owner_segmentation_begin(h, rgb, depth, masks, class_ids, nm, frame, flags & ~1), flags);
+}
+// The device forms (ifx_owner_segmentation_begin_device / _rois / _detections, ifx_instance.hip) in one call each: with root >= 0 the record's broadcast is the first of
+// the exchanges done here.
+static int comm_seg_ready(ifx* h, const char* who)
+{
+    int r = comm_check(h, who);
+    if (r) return r;
+    if (!ifx_comm_ready(h)) { h->err = std::string(who) + ": no communicator: ifx_owner_init_comm / ifx_owner_set_comm first"; return IFX_E_STATE; }
+    return IFX_OK;
+}
+extern "C" int ifx_owner_process_segmentation_device(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const void* d_masks, int mask_format, float threshold,
+                                                     const int32_t* d_class_ids, int n, int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    const int r = comm_seg_ready(h, "ifx_owner_process_segmentation_device");
+    if (r) return r;
+    return comm_seg_run(h, ifx_owner_segmentation_begin_device(h, root, max_n, rgb, depth, d_masks, mask_format, threshold, d_class_ids, n, frame, flags & ~1, stream), flags);
+}
+extern "C" int ifx_owner_process_segmentation_rois(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_roi_masks, int roi_size, const float* d_boxes,
+                                                   float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    const int r = comm_seg_ready(h, "ifx_owner_process_segmentation_rois");
+    if (r) return r;
+    return comm_seg_run(h, ifx_owner_segmentation_begin_rois(h, root, max_n, rgb, depth, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame, flags & ~1, stream), flags);
+}
+extern "C" int ifx_owner_process_segmentation_detections(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_mask_logits, const float* d_boxes,
+                                                         const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
+                                                         const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept)
+{
+    if (!h) return IFX_E_INVALID;
+    const int r = comm_seg_ready(h, "ifx_owner_process_segmentation_detections");
+    if (r) return r;
+    return comm_seg_run(h, ifx_owner_segmentation_begin_detections(h, root, max_n, rgb, depth, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold,
+                                                                   frame, flags & ~1, stream, out_kept), flags);
 }

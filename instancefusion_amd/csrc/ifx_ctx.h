@@ -378,6 +378,13 @@ struct ifx {
     std::vector<uint8_t> oseg_unavail;
     std::vector<int> oseg_cmp, oseg_bbox, oseg_class;
     hipEvent_t oseg_ev = nullptr;
+    // its device forms (ifx_owner_segmentation_begin_device / _rois / _detections): the record the root's rank packs and one broadcast carries (layout: include/ifx_c_api.h),
+    // one allocation grown on demand, and what the first resume checks the record's header against
+    int32_t* oseg_rec = nullptr;
+    size_t oseg_rec_cap = 0, oseg_rec_bytes = 0;
+    int oseg_root = -1, oseg_form = 0, oseg_M = 0, oseg_maxn = 0;
+    float oseg_thr = 0.f;
+    const char* oseg_who = "";
     void* d_kexp = nullptr;            // ifx_owner_knn_export: [cap] float4 (x, y, z, creation number) + [cap] int32 labels
     int gn_begin_folded = 0;         // the start of the next frame-tracker run was done by the model side's last launch
     int labels_stale_all = 1;        // the next segmentation call re-scans the labels of ALL surfels (after create / upload / table eviction); otherwise only what the call can have changed

@@ -314,6 +314,105 @@ __global__ void __launch_bounds__(MI_THREADS) k_roi_gather(const float* __restri
     }
 }
 
+// ---- the device forms of a segmentation call on a sharded map (ifx_owner_segmentation_begin_device / _rois / _detections): the detector's rank packs what the
+// other ranks need into one record of int32 words (layout: include/ifx_c_api.h), one broadcast carries it, every rank ingests from it.
+//   header[8] | cls[max_n] | form 2: boxes f32[max_n][4], rois f32[max_n][M][M] | form 1: bits u32[max_n][ceil(P / 32)]
+#define OSEG_MAGIC 0x49465852   // "IFXR"
+#define OSEG_HDR 8
+// header and class ids (the caller's order; rows >= n are zero).  n_hdr is n, or -- the detections form with more kept rows than the record holds -- that number with no rows
+__global__ void __launch_bounds__(256) k_oseg_head(int32_t* __restrict__ rec, int form, int n_hdr, int n, int M, int P, int max_n, const int32_t* __restrict__ cls)
+{
+    const int hdr[OSEG_HDR] = {OSEG_MAGIC, form, n_hdr, M, P, max_n, 0, 0};
+    for (int t = threadIdx.x; t < OSEG_HDR + max_n; t += 256) {
+        int v = 0;
+        if (t < OSEG_HDR) {
+#pragma unroll
+            for (int k = 0; k < OSEG_HDR; k++) if (t == k) v = hdr[k];
+        } else if (t - OSEG_HDR < n) v = cls[t - OSEG_HDR];
+        rec[t] = v;
+    }
+}
+// form 2: n rows of boxes and ROI masks as they are, the tail zero.  dst = the record behind the class ids: [max_n * 4 | max_n * MM] words
+__global__ void __launch_bounds__(256) k_oseg_pack_rois(uint32_t* __restrict__ dst, int n, int max_n, int MM, const uint32_t* __restrict__ boxes, const uint32_t* __restrict__ rois)
+{
+    const size_t nb = (size_t)max_n * 4, total = nb + (size_t)max_n * MM;
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        uint32_t v = 0;
+        if (t < nb) { if (t < (size_t)n * 4) v = boxes[t]; }
+        else if (t - nb < (size_t)n * MM) v = rois[t - nb];
+        dst[t] = v;
+    }
+}
+// form 1: one pass over the caller's n x P elements to one bit per pixel, binarised by the bridge's rule (mask_inside); grid (chunks, max_n), rows >= n come out zero
+// without a load.  Every lane of a wave stays to the end (ballot and shuffles).  vec: every row starts on a 16-B boundary -- a lane loads 16 B (V elements, V bits),
+// the 32 / V lanes of a word OR their bits together and the first of them stores the word; otherwise a lane takes one pixel and the wave's ballot over its 64
+// consecutive pixels is two words, stored by lanes 0 and 32 (the upper one only where the row still has it: P % 64 may be 32 or less).  Pixels past P give zero bits.
+template <typename T>
+__global__ void __launch_bounds__(MI_THREADS) k_oseg_pack_bits(const T* __restrict__ src, int P, float thr, int n, int vec, uint32_t* __restrict__ bits)
+{
+    constexpr int V = 16 / sizeof(T), LPW = 32 / V;
+    const int m = blockIdx.y, NW = (P + 31) >> 5;
+    const int g = blockIdx.x * MI_THREADS + threadIdx.x, lane = threadIdx.x & 63;
+    uint32_t* out = bits + (size_t)m * NW;
+    const T* row = src + (size_t)m * P;
+    if (vec) {
+        uint32_t b = 0;
+        if (m < n && g < P / V) b = mask_bits(*(const uint4*)(row + (size_t)g * V), thr, (const T*)nullptr) << (V * (lane % LPW));
+#pragma unroll
+        for (int o = 1; o < LPW; o <<= 1) b |= __shfl_xor(b, o, 64);
+        const int j = g / LPW;
+        if (lane % LPW == 0 && j < NW) out[j] = b;
+    } else {
+        const bool in = m < n && g < P && mask_inside(row[g], thr);
+        const unsigned long long w = __ballot(in);
+        const int j = (g - lane) >> 5;   // the wave's first word
+        if (lane == 0 && j < NW) out[j] = (uint32_t)w;
+        if (lane == 32 && j + 1 < NW) out[j + 1] = (uint32_t)(w >> 32);
+    }
+}
+// ingest from the bits: the areas are popcounts (sums as k_mask_area: per wave, per block in LDS, one atomic per block; the counters are zero on entry) ...
+__global__ void __launch_bounds__(MI_THREADS) k_bits_area(const uint32_t* __restrict__ bits, int NW, int* __restrict__ area)
+{
+    __shared__ int s_c[MI_THREADS / 64];
+    const int m = blockIdx.y, tid = threadIdx.x, j = blockIdx.x * MI_THREADS + tid;
+    int c = j < NW ? __popc(bits[(size_t)m * NW + j]) : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((tid & 63) == 0) s_c[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int sum = 0;
+#pragma unroll
+        for (int w = 0; w < MI_THREADS / 64; w++) sum += s_c[w];
+        if (sum) atomicAdd(&area[m], sum);
+    }
+}
+// ... and k_mask_gather's pass with half a word in place of the load: a thread owns 16 consecutive pixels (P is a multiple of 16, ifx_create), the masks in sorted
+// order from the last to the first, 0/255 in sorted order and the overlap-cleaned copy as one 16-B store each, the verdict bytes cleared.
+__global__ void __launch_bounds__(MI_THREADS) k_bits_gather(const uint32_t* __restrict__ bits, int NW, int P, const int* __restrict__ order, int nm,
+                                                            uint8_t* __restrict__ ori, uint8_t* __restrict__ masks, uint8_t* __restrict__ unavail)
+{
+    __shared__ int s_ord[256];
+    const int g = blockIdx.x * MI_THREADS + threadIdx.x;
+    for (int t = threadIdx.x; t < nm; t += MI_THREADS) s_ord[t] = order[t];
+    if (unavail && g < nm) unavail[g] = 0;
+    __syncthreads();
+    const int p0 = g * 16;
+    if (p0 >= P) return;
+    const int j = g >> 1, sh = (g & 1) * 16;
+    uint32_t flag = 0;   // bit k: pixel p0 + k lies in a mask later in the sorted order
+    for (int s = nm - 1; s >= 0; s--) {
+        const uint32_t in = (bits[(size_t)s_ord[s] * NW + j] >> sh) & 0xffffu;
+        const uint32_t kept = in & ~flag;
+        flag |= in;
+        uint32_t wo[4] = {0, 0, 0, 0}, ww[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 16; k++) { wo[k >> 2] |= ((in >> k) & 1u) * (0xffu << (8 * (k & 3))); ww[k >> 2] |= ((kept >> k) & 1u) * (0xffu << (8 * (k & 3))); }
+        *(uint4*)(ori + (size_t)s * P + p0) = make_uint4(wo[0], wo[1], wo[2], wo[3]);
+        *(uint4*)(masks + (size_t)s * P + p0) = make_uint4(ww[0], ww[1], ww[2], ww[3]);
+    }
+}
+
 // checkProjectDepthAndInstanceKernel, IF/Core/InstanceFusionCuda.cu:736-760
 __global__ void k_check_project(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ votes, int cap, int w, int h, int downsample,
                                 int* __restrict__ counts)
@@ -678,7 +777,7 @@ void ifx_free_snapshots(ifx* h);
 void ifx_free_instance(ifx* h)
 {
     hipFree(h->d_inst_color); hipFree(h->d_masks); hipFree(h->d_masks_ori); hipFree(h->d_unavail); hipFree(h->d_ff_label); hipFree(h->d_pdm); hipFree(h->d_bbox); hipFree(h->d_inst_stats); hipFree(h->d_clean_list);
-    hipFree(h->d_segctl); hipFree(h->d_mask_rank);
+    hipFree(h->d_segctl); hipFree(h->d_mask_rank); hipFree(h->oseg_rec);
     ifx_free_snapshots(h);
     ifx_detector_free(h);
     if (h->h_segctl) hipHostFree(h->h_segctl);
@@ -1283,6 +1382,17 @@ static int oseg_mask_loop(ifx* h, bool after_eviction)
     h->oseg_state = 0; h->oseg_pending = 0;
     return 0;
 }
+// behind the masks and their refinement, the exchange points every form of the call shares
+static int oseg_first_exchange(ifx* h)
+{
+    int r = ifx_owner_ids_begin_impl(h);   // option own_lazy_ids: the frame exchanged the sampled lattice only -- the exchange point in front of the boxes is the whole id image's keys
+    if (r == 1) { h->oseg_state = 6; h->oseg_pending = 0; return 1; }
+    if (r < 0) { h->oseg_state = 0; h->oseg_pending = 0; return r; }
+    h->oseg_state = 1;
+    r = oseg_launch_bboxes(h);
+    if (r < 0) { h->oseg_state = 0; h->oseg_pending = 0; }
+    return r;
+}
 extern "C" int ifx_owner_segmentation_begin(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
 {
     if (!h || nm < 0 || (nm > 0 && (!masks_in || !class_ids))) return IFX_E_INVALID;
@@ -1311,15 +1421,10 @@ extern "C" int ifx_owner_segmentation_begin(ifx_t* h, const uint8_t* rgb, const 
         r = ifx_superpixel_refine(h, rgb, depth, nm, frame);
         if (r) return r;
     }
-    r = ifx_owner_ids_begin_impl(h);   // option own_lazy_ids: the frame exchanged the sampled lattice only -- the call's first exchange point is the whole id image's keys
-    if (r == 1) { h->oseg_state = 6; h->oseg_pending = 0; return 1; }
-    if (r < 0) { h->oseg_state = 0; h->oseg_pending = 0; return r; }
-    h->oseg_state = 1;
-    r = oseg_launch_bboxes(h);
-    if (r < 0) { h->oseg_state = 0; h->oseg_pending = 0; }
-    return r;
+    return oseg_first_exchange(h);
 }
 static int oseg_resume(ifx* h);
+static int oseg_resume_record(ifx* h);
 extern "C" int ifx_owner_segmentation_resume(ifx_t* h)
 {
     if (!h) return IFX_E_INVALID;
@@ -1336,6 +1441,8 @@ static int oseg_resume(ifx* h)
     const int nm = h->oseg_nm, P = h->P;
     int r;
     switch (h->oseg_state) {
+    case 7:   // the record arrived (device forms, root >= 0) -> the masks from it, then the exchange points of every form
+        return oseg_resume_record(h);
     case 6:   // the id image's keys merged -> the image, then the boxes
         if ((r = ifx_owner_ids_resume_impl(h))) return r;
         h->oseg_state = 1;
@@ -1651,6 +1758,208 @@ static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, u
     if (dm->roi) return seg_ingest_rois(h, dm, nm, cls_out, unavail);
     return dm->fmt == IFX_MASK_F32 ? seg_ingest_launch(h, (const float*)dm->d, dm->thr, dm->d_cls, nm, cls_out, unavail)
                                    : seg_ingest_launch(h, (const uint8_t*)dm->d, dm->thr, dm->d_cls, nm, cls_out, unavail);
+}
+
+// ------------------------------------------------------------------ the device forms of a segmentation call on a sharded map
+// ifx_owner_segmentation_begin_device / _rois / _detections (include/ifx_c_api.h).  root = -1: every rank holds the tensors and ingests its own copy, the call goes on
+// as the host form does behind its upload and overlap clean.  root = r: rank r packs the record on its main stream behind an event on the producer's stream (no host
+// synchronisation), the call's first exchange point broadcasts it (ifx_owner_exchange(h, 200): op 4 | r << 8), and the first resume ingests from it on every rank,
+// rank r included: identical kernels on identical bytes.
+static size_t oseg_record_words(int form, int max_n, int M, int P)
+{
+    return OSEG_HDR + (size_t)max_n + (form == 2 ? (size_t)max_n * 4 + (size_t)max_n * M * M : (size_t)max_n * ((P + 31) / 32));
+}
+// the call is over before its end (a failure, or no masks): the event goes back, the state is cleared
+static int oseg_end(ifx* h, int r)
+{
+    if (h->oseg_ev) { h->event_pool.push_back(h->oseg_ev); h->oseg_ev = nullptr; }
+    h->oseg_state = 0; h->oseg_pending = 0;
+    return r;
+}
+// n masks are coming: the buffers and the host state of a call, as ifx_owner_segmentation_begin sets them
+static int oseg_prepare(ifx* h, int n)
+{
+    int r = ifx_ensure_masks(h, (size_t)n * h->P);
+    if (r) return r;
+    h->oseg_nm = n; h->oseg_m = 0;
+    h->oseg_unavail.assign(n, 0);
+    h->oseg_cmp.assign((size_t)n * NI, 0);
+    h->oseg_class.assign(n, 0);
+    if (!h->d_mask_rank) {
+        HIPCHK(h, hipMalloc(&h->d_mask_rank, 3 * 256 * sizeof(int)));
+        HIPCHK(h, hipMemsetAsync(h->d_mask_rank, 0, 256 * sizeof(int), h->cur));   // the counters; k_mask_order leaves them zero for the next call
+    }
+    return IFX_OK;
+}
+// the class ids in sorted order, for the compare map (oseg_read_bboxes synchronises before it reads them)
+static int oseg_read_classes(ifx* h)
+{
+    HIPCHK(h, hipMemcpyAsync(h->oseg_class.data(), h->d_mask_rank + 512, (size_t)h->oseg_nm * 4, hipMemcpyDeviceToHost, h->cur));
+    return IFX_OK;
+}
+// s: the tensors of the reading rank (root = -1: every rank; otherwise rank root) -- ignored on the others; form 1 image masks, 2 ROI masks (M = roi_size)
+static int oseg_begin_dev(ifx* h, const char* who, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, MaskSource s, int n_hdr, int form, int M, float thr, int frame,
+                          int flags, void* stream)
+{
+    const int P = h->P, n = s.n;
+    const bool reader = root < 0 || root == h->cfg.rank;
+    h->seg_counts_valid = 0;
+    ifx_vlist_reap(h);
+    h->oseg_ev = ifx_event_get(h);
+    hipEventRecord(h->oseg_ev, h->cur);
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    h->oseg_flags = flags; h->oseg_root = root; h->oseg_form = form; h->oseg_M = form == 2 ? M : 0; h->oseg_maxn = max_n; h->oseg_thr = thr; h->oseg_who = who;
+    int r;
+    if (root < 0) {
+        if (n == 0) return oseg_end(h, 0);
+        if ((r = oseg_prepare(h, n))) return oseg_end(h, r);
+        {
+            PoolEvent ready(h);
+            if ((r = seg_record_ready(h, who, &s.dm, ready, stream)) || (r = seg_ingest_device(h, &s.dm, n, nullptr, nullptr))) return oseg_end(h, r);
+        }
+        if ((r = oseg_read_classes(h))) return oseg_end(h, r);
+        if ((flags & 2) && (r = ifx_superpixel_refine(h, rgb, depth, n, frame))) return oseg_end(h, r);
+        r = oseg_first_exchange(h);
+        return r < 0 ? oseg_end(h, r) : r;
+    }
+    const size_t words = oseg_record_words(form, max_n, h->oseg_M, P);
+    if (words > h->oseg_rec_cap) {
+        if (h->oseg_rec) hipFree(h->oseg_rec);
+        h->oseg_rec = nullptr; h->oseg_rec_cap = 0;
+        hipError_t e = hipMalloc(&h->oseg_rec, words * 4);
+        if (e != hipSuccess) { h->err = std::string(who) + ": the record: " + hipGetErrorString(e); return oseg_end(h, IFX_E_HIP); }
+        h->oseg_rec_cap = words;
+    }
+    h->oseg_rec_bytes = words * 4;
+    if (reader) {
+        PoolEvent ready(h);
+        if ((r = seg_record_ready(h, who, &s.dm, ready, stream))) return oseg_end(h, r);
+        HIPCHK(h, hipStreamWaitEvent(h->cur, ready.ev, 0));   // behind what the producer enqueued before the call (no host synchronisation)
+        int32_t* rec = h->oseg_rec;
+        LAUNCH(h, "oseg_head", dim3(1), dim3(256), k_oseg_head, rec, form, n_hdr, n, h->oseg_M, P, max_n, s.dm.d_cls);
+        uint32_t* body = (uint32_t*)rec + OSEG_HDR + max_n;
+        if (form == 2) {
+            const size_t total = (size_t)max_n * (4 + (size_t)M * M);
+            LAUNCH(h, "oseg_pack_rois", dim3((unsigned)std::min<size_t>((total + 255) / 256, 1024)), dim3(256), k_oseg_pack_rois, body, n, max_n, M * M, (const uint32_t*)s.dm.d_boxes,
+                   (const uint32_t*)s.dm.d);
+        } else {
+            const int NW = (P + 31) / 32;
+            if (s.dm.fmt == IFX_MASK_F32) {
+                const int vec = ((uintptr_t)s.dm.d % 16 == 0 && P % 4 == 0) ? 1 : 0;
+                LAUNCH(h, "oseg_pack_bits", dim3(cdiv(vec ? NW * 8 : NW * 32, MI_THREADS), max_n), dim3(MI_THREADS), k_oseg_pack_bits<float>, (const float*)s.dm.d, P, thr, n, vec, body);
+            } else {
+                const int vec = ((uintptr_t)s.dm.d % 16 == 0 && P % 16 == 0) ? 1 : 0;
+                LAUNCH(h, "oseg_pack_bits", dim3(cdiv(vec ? NW * 2 : NW * 32, MI_THREADS), max_n), dim3(MI_THREADS), k_oseg_pack_bits<uint8_t>, (const uint8_t*)s.dm.d, P, thr, n, vec, body);
+            }
+        }
+    }
+    if ((flags & 2) && (r = ifx_superpixel_begin(h, rgb, depth))) return oseg_end(h, r);   // (the frame's superpixels need no mask: the host pointers are done with when this returns)
+    h->oseg_state = 7; h->oseg_pending = 4;
+    return 1;
+}
+// the first resume of a call with root >= 0: the header in one 32-byte copy, checked against this rank's arguments; then the ingestion from the record
+static int oseg_resume_record(ifx* h)
+{
+    const int P = h->P, max_n = h->oseg_maxn, M = h->oseg_M;
+    const std::string who = h->oseg_who;
+    int32_t hdr[OSEG_HDR];
+    HIPCHK(h, hipMemcpyAsync(hdr, h->oseg_rec, sizeof(hdr), hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    if (hdr[0] != OSEG_MAGIC || hdr[1] != h->oseg_form || hdr[3] != M || hdr[4] != P || hdr[5] != max_n || hdr[2] < 0) {
+        h->err = who + ": the record's header does not match this rank's arguments (the form, roi_size / M, max_n and the frame size must be equal on all ranks)";
+        return IFX_E_STATE;
+    }
+    const int n = hdr[2];
+    if (n > max_n) { h->err = who + ": more than max_n detections kept (raise score_thresh)"; return IFX_E_CAPACITY; }
+    if (n == 0) return oseg_end(h, 0);
+    int r = oseg_prepare(h, n);
+    if (r) return r;
+    const int32_t* cls = h->oseg_rec + OSEG_HDR;
+    int* area = h->d_mask_rank;
+    int* order = area + 256;
+    int* cls_out = area + 512;
+    if (h->oseg_form == 2) {
+        DevMasks dm{h->oseg_rec + OSEG_HDR + max_n + (size_t)max_n * 4, IFX_MASK_F32, h->oseg_thr, cls, nullptr, (const float*)(h->oseg_rec + OSEG_HDR + max_n), M};
+        if ((r = seg_ingest_rois(h, &dm, n, cls_out, nullptr))) return r;
+    } else {
+        if (P % 16) { h->err = who + ": width x height is not a multiple of 16"; return IFX_E_STATE; }   // (ifx_create admits multiples of 4 only)
+        const int NW = (P + 31) / 32;
+        const uint32_t* bits = (const uint32_t*)h->oseg_rec + OSEG_HDR + max_n;
+        LAUNCH(h, "bits_area", dim3(cdiv(NW, MI_THREADS), n), dim3(MI_THREADS), k_bits_area, bits, NW, area);
+        LAUNCH(h, "mask_order", dim3(1), dim3(256), k_mask_order, area, cls, n, order, cls_out);
+        LAUNCH(h, "bits_gather", dim3(cdiv(P / 16, MI_THREADS)), dim3(MI_THREADS), k_bits_gather, bits, NW, P, (const int*)order, n, h->d_masks_ori, h->d_masks, (uint8_t*)nullptr);
+    }
+    if ((r = oseg_read_classes(h))) return r;
+    if ((h->oseg_flags & 2) && (r = ifx_superpixel_filter(h, n))) return r;
+    return oseg_first_exchange(h);
+}
+// what every device form refuses before it touches anything; who leads the message
+static int oseg_refuse(ifx* h, const char* who, int root, int max_n, int flags)
+{
+    const char* bad = nullptr;
+    int code = IFX_E_INVALID;
+    if (!h->own) { bad = ": the handle was not created for a sharded map"; code = IFX_E_STATE; }
+    else if (h->oseg_state) { bad = ": a segmentation call is already in flight"; code = IFX_E_STATE; }
+    else if (flags & 1) bad = ": kNN smoothing is not offered on a sharded map's begin / resume (it needs every rank's positions)";
+    else if (root < -1 || root >= h->own_g) bad = ": root must be -1 or a rank of the map";
+    else if (max_n < 1 || max_n > 256) bad = ": max_n must be 1 .. 256";
+    if (bad) { h->err = std::string(who) + bad; return code; }
+    return IFX_OK;
+}
+static int oseg_entry(ifx* h, const char* who, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, MaskSource s, float thr, int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = oseg_refuse(h, who, root, max_n, flags);
+    if (r) return r;
+    const bool rois = s.kind == MaskSource::ROIS;
+    if (rois && (s.dm.roi < 1 || s.dm.roi > ROI_M_MAX)) { h->err = std::string(who) + ": roi_size must be 1 .. 64"; return IFX_E_INVALID; }   // (every rank: the record's size depends on it)
+    if (root < 0 || root == h->cfg.rank) {
+        if ((r = seg_check_args(h, who, s))) return r;
+        if (s.n > max_n) { h->err = std::string(who) + ": n is larger than max_n"; return IFX_E_INVALID; }
+    } else s.n = 0;
+    return oseg_begin_dev(h, who, root, max_n, rgb, depth, s, s.n, rois ? 2 : 1, s.dm.roi, thr, frame, flags, stream);
+}
+// A call in flight ends here on this rank: what a rank does whose peers' call is over (their begin refused, their resume failed) while it waits at an exchange point
+extern "C" int ifx_owner_segmentation_abort(ifx_t* h)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!h->own) { h->err = "ifx_owner_segmentation_abort: the handle was not created for a sharded map"; return IFX_E_STATE; }
+    if (!h->oseg_state) return IFX_OK;
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    h->labels_stale_all = 1;   // (votes may have been updated without the label scan that follows them)
+    return oseg_end(h, IFX_OK);
+}
+extern "C" int ifx_owner_segmentation_begin_device(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const void* d_masks, int mask_format, float threshold,
+                                                   const int32_t* d_class_ids, int n, int frame, int flags, void* stream)
+{
+    return oseg_entry(h, "ifx_owner_segmentation_begin_device", root, max_n, rgb, depth, src_image(d_masks, mask_format, threshold, d_class_ids, n), threshold, frame, flags, stream);
+}
+extern "C" int ifx_owner_segmentation_begin_rois(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_roi_masks, int roi_size, const float* d_boxes,
+                                                 float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream)
+{
+    return oseg_entry(h, "ifx_owner_segmentation_begin_rois", root, max_n, rgb, depth, src_rois(d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n), threshold, frame, flags, stream);
+}
+// the mask head's stage runs on the reading rank (into the handle's scratch, on the producer's stream; kept comes back), its kept rows are the ROI form's tensors.  More
+// kept rows than the record holds: with root = -1 every rank refuses alike; with a root the record carries the count and no rows, and every rank refuses at its first resume.
+extern "C" int ifx_owner_segmentation_begin_detections(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_mask_logits, const float* d_boxes,
+                                                       const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
+                                                       const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept)
+{
+    const char* who = "ifx_owner_segmentation_begin_detections";
+    if (!h) return IFX_E_INVALID;
+    int r = oseg_refuse(h, who, root, max_n, flags);
+    if (r) return r;
+    if (M < 1 || M > ROI_M_MAX) { h->err = std::string(who) + ": M must be 1 .. 64"; return IFX_E_INVALID; }
+    const float *rois = nullptr, *boxes = nullptr;
+    const int32_t* cls = nullptr;
+    int kept = 0;
+    if (root < 0 || root == h->cfg.rank) {
+        if ((r = ifx_mask_head_check(h, who, d_mask_logits, d_boxes, d_scores, d_labels, R, C, M, p, false))) return r;
+        if ((r = ifx_mask_head_stage(h, who, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, stream, &rois, &boxes, &cls, &kept))) return r;
+        if (out_kept) *out_kept = kept;
+        if (kept > max_n && root < 0) { h->err = std::string(who) + ": more than max_n detections kept (raise score_thresh)"; return IFX_E_CAPACITY; }
+    }
+    return oseg_begin_dev(h, who, root, max_n, rgb, depth, src_rois(rois, M, boxes, threshold, cls, kept > max_n ? 0 : kept), kept, 2, M, threshold, frame, flags, stream);
 }
 
 static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags)

@@ -1093,6 +1093,39 @@ public:
         });
         return kept;
     }
+    // ---- the device forms on a sharded map (ifx_owner_process_segmentation_device / _rois / _detections): the detector runs on rank `root`'s GPU, only that rank's
+    // tensors, n and stream are read (the others pass null / 0), the library packs what the other ranks need into one record and broadcasts it on the handle's
+    // communicator; root = -1: every rank holds the tensors.  max_n (1 .. 256, equal on all ranks) is the record's capacity.  rgb, depth: the host frame for the
+    // superpixel refinement, as ProcessSegmentation takes it.  Tensors as the methods of the same name above.
+    void OwnerProcessSegmentationDevice(const std::unique_ptr<ElasticFusionInterface>& map, int root, int max_n, const ImagePtr rgb, const DepthPtr depth, const void* d_masks,
+                                        int format, float threshold, const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
+    {
+        const char* c = "ifx_owner_process_segmentation_device";
+        seg_call("InstanceFusion::OwnerProcessSegmentationDevice", c, c, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_owner_process_segmentation_device(h, root, max_n, rgb, depth, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
+    }
+    void OwnerProcessSegmentationRois(const std::unique_ptr<ElasticFusionInterface>& map, int root, int max_n, const ImagePtr rgb, const DepthPtr depth, const float* d_roi_masks,
+                                      int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
+    {
+        const char* c = "ifx_owner_process_segmentation_rois";
+        seg_call("InstanceFusion::OwnerProcessSegmentationRois", c, c, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_owner_process_segmentation_rois(h, root, max_n, rgb, depth, d_roi_masks, roi_size, d_boxes, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
+    }
+    int OwnerProcessSegmentationDetections(const std::unique_ptr<ElasticFusionInterface>& map, int root, int max_n, const ImagePtr rgb, const DepthPtr depth,
+                                           const float* d_mask_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
+                                           const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, float threshold, int frame_num, bool isflann,
+                                           void* stream)
+    {
+        int32_t kept = 0;
+        const char* c = "ifx_owner_process_segmentation_detections";
+        seg_call("InstanceFusion::OwnerProcessSegmentationDetections", c, c, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_owner_process_segmentation_detections(h, root, max_n, rgb, depth, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold,
+                                                             frame_num, flags, stream, &kept);
+        });
+        return kept;
+    }
     // ---- the opposite direction: the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input).  What
     // COCODemo.build_transform and to_image_list make of a frame on the CPU (deps/maskrcnn-benchmark-master/demo/predictor.py:132-160, 198-202: Pillow's bilinear
     // Resize to min_size / max_size, ToTensor, x255 and / or channel flip, Normalize, zero padding to a multiple of size_divisible), bit for bit, as planar

@@ -263,6 +263,46 @@ class OwnerShardedElasticFusion:
         if knn:
             self.knn_vote_colour()
 
+    # ---- the device forms: one detector, on rank `root`'s GPU (include/ifx_c_api.h); root = -1: every rank holds the tensors
+    def _device_form(self, form, root, max_n, rgb, depth, tensors, frame, superpixels, knn):
+        ef = self.ef
+        flags = 2 if superpixels else 0
+        if self.transport == "library":
+            _, keep, kept = _device_form_call(ef, "ifx_owner_process_segmentation_", form, root, max_n, rgb, depth, tensors, frame, flags | (1 if knn else 0))
+        else:
+            r, keep, kept = _device_form_call(ef, "ifx_owner_segmentation_begin_", form, root, max_n, rgb, depth, tensors, frame, flags)
+            while r == 1:
+                self._exchange(200)
+                r = ef._chk(ef.L.ifx_owner_segmentation_resume(ef.handle), "ifx_owner_segmentation_resume")
+            if knn:
+                self.knn_vote_colour()
+        del keep   # (the call returned after its work finished: what was made for it may go)
+        return kept
+
+    def process_segmentation_device(self, rgb, depth, masks, class_ids, frame: int, superpixels: bool = True, knn: bool = False, threshold=0.5, stream=None, root: int = -1,
+                                    max_n: int = 256):
+        """process_segmentation on a detector's image-sized masks on rank `root`'s GPU (ifx_owner_process_segmentation_device): tensors, threshold and stream as
+        InstanceFusion.process_segmentation_device takes them, in any order.  root = -1: every rank passes the tensors.  Otherwise only rank root's are read
+        (the others pass masks = class_ids = None): the library packs them to one bit per pixel and one broadcast carries them.  max_n (1 .. 256, equal on all
+        ranks) is the record's capacity."""
+        self._device_form("device", root, max_n, rgb, depth, dict(masks=masks, class_ids=class_ids, threshold=threshold, stream=stream), frame, superpixels, knn)
+
+    def process_segmentation_rois(self, rgb, depth, roi_masks, boxes, class_ids, frame: int, superpixels: bool = True, knn: bool = False, threshold=0.5, stream=None,
+                                  root: int = -1, max_n: int = 256, roi_size=None):
+        """The same on a mask head's ROI masks [N,M,M] and boxes [N,4] (ifx_owner_process_segmentation_rois; tensors as InstanceFusion.process_segmentation_rois).
+        A rank that is not `root` passes roi_masks = boxes = class_ids = None and roi_size = M; threshold must be equal on all ranks."""
+        self._device_form("rois", root, max_n, rgb, depth, dict(roi_masks=roi_masks, boxes=boxes, class_ids=class_ids, threshold=threshold, stream=stream, roi_size=roi_size),
+                          frame, superpixels, knn)
+
+    def process_segmentation_detections(self, rgb, depth, mask_logits, boxes, scores, labels, in_size, frame: int, score_thresh=0.7, class_map=None, count=None,
+                                        superpixels: bool = True, knn: bool = False, threshold=0.5, stream=None, root: int = -1, max_n: int = 256, roi_size=None):
+        """The same on the mask head's logits and the box head's detections (ifx_owner_process_segmentation_detections; tensors as
+        InstanceFusion.process_segmentation_detections): the stage runs on rank `root` (root = -1: on every rank) and its kept rows travel.  A rank that is not
+        `root` passes None for the tensors and roi_size = M.  Returns kept where the stage ran (0 elsewhere); more than max_n raise IfxError (IFX_E_CAPACITY)."""
+        return self._device_form("detections", root, max_n, rgb, depth,
+                                 dict(mask_logits=mask_logits, boxes=boxes, scores=scores, labels=labels, in_size=in_size, score_thresh=score_thresh, class_map=class_map,
+                                      count=count, threshold=threshold, stream=stream, roi_size=roi_size), frame, superpixels, knn)
+
 
 def _knn_export(ef, torch, dev):
     pp, pl, n = C.c_void_p(), C.c_void_p(), C.c_int()
@@ -355,6 +395,106 @@ def emulate_owner_segmentation(efs, rgb, depth, masks, class_ids, frame: int, su
         _reduce_by_hand(efs, [_exchange_spec(e, 200) for e in efs])
         rs = [e._chk(e.L.ifx_owner_segmentation_resume(e.handle), "ifx_owner_segmentation_resume") for e in efs]
     assert all(r == 0 for r in rs)
+
+
+def _device_form_args(ef, form, root, t):
+    """The tensor arguments of a device form of the sharded segmentation call for this rank: checked as the InstanceFusion.process_segmentation_* methods check
+    them where the rank reads them (root = -1, or root = this rank), NULLs elsewhere.  -> (arguments, stream handle or None, kept, what must outlive the call)"""
+    from . import MASK_U8, InstanceFusion
+
+    def p(x):
+        return None if x is None else C.c_void_p(x.data_ptr() or None)
+
+    thr = float(t["threshold"])
+    kept = C.c_int32(0)
+    world = max(int(ef.cfgd["n_ranks"]), 1)
+    reader = root < 0 or (root == int(ef.cfgd["rank"]) and root < world)   # (a root outside the world is the library's to refuse: nothing is read)
+    if not reader:
+        M = 0 if form == "device" else int(t["roi_size"] or 0)
+        null = {"device": (None, MASK_U8, thr, None, 0), "rois": (None, M, None, thr, None, 0), "detections": (None,) * 6 + (0, 1, M, None, thr)}[form]
+        return null, None, kept, None
+    inst = InstanceFusion(ef)
+    if form == "device":
+        m, cls, fmt, n, stream = inst._device_masks(t["masks"], t["class_ids"], t["stream"])
+        return (p(m), fmt, thr, p(cls), n), stream.cuda_stream or None, kept, (m, cls)
+    if form == "rois":
+        m, M, bx, cls, n, stream = inst._device_rois(t["roi_masks"], t["boxes"], t["class_ids"], t["stream"])
+        return (p(m), M, p(bx), thr, p(cls), n), stream.cuda_stream or None, kept, (m, bx, cls)
+    R, Cn, M, par, stream = ef._mask_head_args(t["mask_logits"], t["boxes"], t["scores"], t["labels"], t["in_size"], (ef.w, ef.h), t["score_thresh"], True, t["count"],
+                                               t["class_map"], t["stream"])
+    return ((p(t["mask_logits"]), p(t["boxes"]), p(t["scores"]), p(t["labels"]), p(t["count"]), p(t["class_map"]), R, Cn, M, C.byref(par), thr), stream.cuda_stream or None,
+            kept, par)
+
+
+def _device_form_call(ef, prefix, form, root, max_n, rgb, depth, tensors, frame, flags):
+    """one C entry of a device form (prefix + form) on this rank -> (its return value, what must outlive the call it began, kept)"""
+    args, stream, kept, keep = _device_form_args(ef, form, root, tensors)
+    rgb = np.ascontiguousarray(rgb, np.uint8); depth = np.ascontiguousarray(depth, np.uint16)
+    name = prefix + form
+    tail = (C.c_void_p(stream),) + ((C.byref(kept),) if form == "detections" else ())
+    r = ef._chk(getattr(ef.L, name)(ef.handle, int(root), int(max_n), rgb.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), *args, int(frame), int(flags), *tail),
+                name)
+    return r, keep, int(kept.value)
+
+
+def _device_form_begin(ef, form, root, max_n, rgb, depth, tensors, frame, superpixels):
+    return _device_form_call(ef, "ifx_owner_segmentation_begin_", form, root, max_n, rgb, depth, tensors, frame, 2 if superpixels else 0)
+
+
+def _emulate_device_form(efs, form, root, max_n, rgb, depth, tensors, frame, superpixels):
+    """A device form on the handles of emulate_owner_ranks, in lock step, the exchanges done by hand.  With root >= 0 the tensors go to efs[root] only, and that rank
+    begins first: a refusal of its arguments then leaves no other rank waiting at the record's exchange point."""
+    first = root if 0 <= root < len(efs) else 0
+    order = [first] + [k for k in range(len(efs)) if k != first]
+    rs, keep, kept = [None] * len(efs), [], 0
+
+    def abort():   # a rank's call is over: the ranks still in flight end theirs
+        for e in efs:
+            e._chk(e.L.ifx_owner_segmentation_abort(e.handle), "ifx_owner_segmentation_abort")
+
+    try:
+        for k in order:
+            rs[k], kp, kk = _device_form_begin(efs[k], form, root, max_n[k] if isinstance(max_n, (list, tuple)) else max_n, rgb, depth, tensors, frame, superpixels)
+            keep.append(kp); kept = max(kept, kk)
+    except Exception:
+        abort()
+        raise
+    while rs[0] == 1:
+        assert all(r == 1 for r in rs), "the ranks disagree about the call's exchange points"
+        specs = [_exchange_spec(e, 200) for e in efs]
+        low = [min(sp[k][1] for sp in specs) for k in range(len(specs[0]))]   # (ranks that disagree about max_n list records of different sizes: stay inside every one)
+        _reduce_by_hand(efs, [[(ptr, low[k], op) for k, (ptr, _, op) in enumerate(sp)] for sp in specs])
+        rs, errs = [], []
+        for e in efs:   # (every rank resumes, also behind one that failed)
+            try:
+                rs.append(e._chk(e.L.ifx_owner_segmentation_resume(e.handle), "ifx_owner_segmentation_resume"))
+            except Exception as ex:   # noqa: BLE001 -- re-raised below
+                errs.append(ex)
+        if errs:
+            abort()
+            raise errs[0]
+    assert all(r == 0 for r in rs)
+    return kept
+
+
+def emulate_owner_segmentation_device(efs, root, rgb, depth, masks, class_ids, frame: int, superpixels: bool = True, threshold=0.5, max_n=256, stream=None):
+    """process_segmentation_device on the handles of emulate_owner_ranks (root >= 0: the tensors are handed to efs[root] only; max_n: one value, or one per rank)."""
+    _emulate_device_form(efs, "device", root, max_n, rgb, depth, dict(masks=masks, class_ids=class_ids, threshold=threshold, stream=stream), frame, superpixels)
+
+
+def emulate_owner_segmentation_rois(efs, root, rgb, depth, roi_masks, boxes, class_ids, frame: int, superpixels: bool = True, threshold=0.5, max_n=256, stream=None, roi_size=None):
+    """process_segmentation_rois on the handles of emulate_owner_ranks."""
+    M = int(roi_masks.shape[-1]) if roi_size is None else roi_size
+    _emulate_device_form(efs, "rois", root, max_n, rgb, depth, dict(roi_masks=roi_masks, boxes=boxes, class_ids=class_ids, threshold=threshold, stream=stream, roi_size=M), frame,
+                         superpixels)
+
+
+def emulate_owner_segmentation_detections(efs, root, rgb, depth, mask_logits, boxes, scores, labels, in_size, frame: int, score_thresh=0.7, class_map=None, count=None,
+                                          superpixels: bool = True, threshold=0.5, max_n=256, stream=None):
+    """process_segmentation_detections on the handles of emulate_owner_ranks; returns kept."""
+    return _emulate_device_form(efs, "detections", root, max_n, rgb, depth,
+                                dict(mask_logits=mask_logits, boxes=boxes, scores=scores, labels=labels, in_size=in_size, score_thresh=score_thresh, class_map=class_map,
+                                     count=count, threshold=threshold, stream=stream, roi_size=int(mask_logits.shape[-1])), frame, superpixels)
 
 
 def emulate_owner_ids(efs):
