@@ -264,6 +264,8 @@ int ifx_tracker_fallbacks(ifx_t* h);
  * may differ from run to run in the last bit.  >= 0; negative: error.  Replaces nothing of the reference (its reductions are f32 trees whose shape depends on the GPU,
  * EF/Utils/GPUConfig.h:53-137: no order-independence to guard).  Waits for the frames in flight. */
 int ifx_tracker_range_exceeded(ifx_t* h);
+/* photometric blocks of fused tracker iterations (option "rgb_fuse") that stopped waiting at their bounded meeting since ifx_create (0 in a healthy run; the poses do not depend on it) */
+int ifx_tracker_meet_giveups(ifx_t* h);
 
 /* ---- local loop-closure DETECTION (the closeLoops / countThresh / errThresh / covThresh constructor arguments, EF/ElasticFusion.h:48-51;
  * EF/ElasticFusion.cpp:453-566 with no fern match).  When enabled every tracked frame also runs predict() at the new pose, the INACTIVE
@@ -371,6 +373,10 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           blocks that does not happen is re-run by one workgroup inside the frame (ifx_tracker_fallbacks counts them): slower, never wrong.
  *   "rgb_cand" 0          -- the photometric term of the frame-to-model tracker over every pixel (the dense passes) instead of over the frame slot's candidate
  *                           list; same bits.  A run with a persistent level ("gn_persist") or row-sharded reductions is dense whatever the option says
+ *   "rgb_fuse" mask       -- a bit per pyramid level: in list runs ("rgb_cand") the photometric step of a prologue-chain iteration runs inside the iteration's
+ *                           residual launch (its photometric blocks meet, bounded, and step the records by claimed chunks); same bits.  0: two launches per
+ *                           iteration.  "rgb_fuse_poll" 0 (test switch) -- no block waits at that meeting: the last arriver steps every chunk alone
+ *                           (ifx_tracker_meet_giveups counts the blocks that left)
  *   "gn_prologue" 0       -- the 6x6 solve of an iteration by the last block of its second launch (round 3's form) instead of by every block of the next
  *                           iteration's first launch; "gn_prologue_blocks" n -- the prologue form only for launches of at most n blocks (default 2048)
  *   "fold_result" 0       -- the frame result by a launch of its own instead of the last block of the prediction's resolve

@@ -146,6 +146,7 @@ _SIGS = {
     "ifx_tracker_fallbacks": (C.c_int, [_P]),
     "ifx_build_pyramids": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(Pyramids)]),
     "ifx_tracker_range_exceeded": (C.c_int, [_P]),
+    "ifx_tracker_meet_giveups": (C.c_int, [_P]),
     "ifx_hot_records_stale": (C.c_int, [_P]),
     "ifx_set_loop_closure": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float]),
     "ifx_loop_closure_diag": (C.c_int, [_P, _P]),
@@ -1089,6 +1090,10 @@ class ElasticFusion:
     def tracker_range_exceeded(self):
         """reductions whose totals left the exact range of the tracker's sums so far (0: every pose is order-independent and equals the oracle's)"""
         return self._chk(self.L.ifx_tracker_range_exceeded(self.handle), "ifx_tracker_range_exceeded")
+
+    def tracker_meet_giveups(self):
+        """photometric blocks of fused tracker iterations (option rgb_fuse) that stopped waiting at their bounded meeting so far (0 in a healthy run)"""
+        return self._chk(self.L.ifx_tracker_meet_giveups(self.handle), "ifx_tracker_meet_giveups")
 
     # -- local loop-closure detection (closeLoops, countThresh, errThresh, covThresh of the reference constructor)
     def set_loop_closure(self, enable=True, count_thresh=35000, err_thresh=5e-5, cov_thresh=1e-5):

@@ -401,6 +401,14 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
     // the photometric term of the frame-to-model tracker over the frame slot's candidate list (1, default) or over every pixel (0: the dense bodies, bit for bit as they
     // were).  Where a dense form and the list form would share `corres` within one run -- a persistent level (gn_persist), own_track_rows -- the dense one wins for that run.
     else if (s == "rgb_cand") { ifx_drop_tracked(h); h->opt_rgb_cand = value ? 1 : 0; }
+    // list runs, prologue chain: the photometric step of an iteration inside its residual launch (k_icp_residual<.., FUSE>), a bit per pyramid level; 0: two launches per
+    // iteration.  rgb_fuse_poll (test switch): 0 = no photometric block waits at the meeting -- all but the last arriver leave at once and it steps every chunk alone
+    else if (s == "rgb_fuse") {
+        if (value < 0 || value > 7) { h->err = "rgb_fuse is a mask of pyramid levels (0..7)"; return IFX_E_INVALID; }
+        ifx_drop_tracked(h);
+        h->opt_rgb_fuse = value;
+    }
+    else if (s == "rgb_fuse_poll") { ifx_drop_tracked(h); h->opt_rgb_fuse_poll = value ? 1 : 0; }
     else if (s == "raster_lds") h->opt_raster_lds = value;
     else if (s == "raster_earlyz") h->opt_raster_earlyz = value;
     // ElasticFusion::setPyramid / setFastOdom / setSo3 / setIcpWeight (EF/ElasticFusion.h:153-176): tracker configuration from the next frame on;
@@ -1320,6 +1328,25 @@ extern "C" int ifx_hot_records_stale(ifx_t* h)
     int v = 0;
     HIPCHK(h, hipMemcpy(&v, &h->d_state->hot_stale, sizeof(int), hipMemcpyDeviceToHost));
     return v;
+}
+// Photometric blocks of fused iterations (option rgb_fuse) that stopped waiting at the meeting since ifx_create: the step was then done by the blocks that did meet (the
+// last arriver always does), so the poses are what they would have been -- the count says that the form did not run as designed (a photometric block was not resident
+// in time), or that the test switch rgb_fuse_poll = 0 is set.  Summed over the handle's tracker instances that can run a list run.  Waits for the frames in flight.
+extern "C" int ifx_tracker_meet_giveups(ifx_t* h)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = ifx_sync(h);
+    if (r) return r;
+    if (h->stream_c) HIPCHK(h, hipStreamSynchronize(h->stream_c));
+    if (h->stream_b) HIPCHK(h, hipStreamSynchronize(h->stream_b));
+    long long total = 0;
+    for (const DevState* d : {(const DevState*)h->d_state, (const DevState*)h->d_cam_trk}) {
+        if (!d) continue;
+        int v = 0;
+        HIPCHK(h, hipMemcpy(&v, (const char*)d + offsetof(DevState, rgb_meet_giveups), sizeof(int), hipMemcpyDeviceToHost));
+        total += v;
+    }
+    return (int)std::min<long long>(total, 0x7FFFFFFF);
 }
 extern "C" int ifx_tracker_range_exceeded(ifx_t* h)
 {

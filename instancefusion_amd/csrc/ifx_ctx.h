@@ -85,12 +85,16 @@ struct DevState {
     int gn_abort;                                             // this run's persistent kernel gave up at a barrier: its blocks leave, k_gn_level_solo re-runs the level on one workgroup (reset at the start of every run)
     int gn_done_seq;                                          // level + 1 of the last persistent launch whose result was published (k_gn_level's block 0 / k_gn_level_solo)
     int gn_spin_limit, gn_fault;                              // test hooks (options gn_spin_limit / gn_fault): polls before a barrier gives up (0: 2^21); != 0: block 1 never arrives at barrier number gn_fault
-    // "solve in the next launch's prologue" (option gn_prologue, ifx_track.hip): iteration j of a run's two-launch tail keeps its sums in parity j & 1 -- every block of
+    // "solve in the next launch's prologue" (option gn_prologue, ifx_track.hip): iteration j of a run's two-launch tail keeps its sums in set j % 3 -- every block of
     // the NEXT launch reads the 2 x 29 totals, rebuilds the 6x6 system and solves it itself (no last-block ticket, no pose store / pose load between the two launches);
-    // the running increment after iteration j lives in gnp_RRt[j & 1] (block 0 of the launch that solved it writes it; its readers are the launch after that)
-    alignas(64) double gnp_acc[2 * 2 * IFX_ACC_REPL * IFX_ACC_STRIDE];   // [parity][ICP | photometric]
-    alignas(64) int gnp_res[2 * 16];                                     // [parity] (count, sigma), a line each
+    // the running increment after iteration j lives in gnp_RRt[j & 1] (block 0 of the launch that solved it writes it; its readers are the launch after that).
+    // Three sets, because an iteration may be ONE launch (option rgb_fuse): iteration j sums into set j % 3, the prologues of iteration j + 1 read it, and iteration j
+    // clears set (j + 1) % 3, whose last readers (the prologues of iteration j - 1) are complete by stream order.  Every set is zero when a run starts.
+    alignas(64) double gnp_acc[3 * 2 * IFX_ACC_REPL * IFX_ACC_STRIDE];   // [set][ICP | photometric]
+    alignas(64) int gnp_res[3 * 16];                                     // [set] (count, sigma), a line each
+    alignas(64) unsigned int gnp_meet[3 * 32];                           // [set] fused iteration (rgb_fuse): arrivals of the photometric blocks at [0], next unclaimed chunk of the step at [16]: a line each
     alignas(64) double gnp_RRt[2][16];
+    int rgb_meet_giveups;                                                // photometric blocks of fused iterations that stopped waiting for the others (bounded meeting; ifx_tracker_meet_giveups): 0 in a healthy run unless rgb_fuse_poll = 0
 };
 
 // Ids in the id images are slot indices on an unsharded map and creation numbers on a spatially sharded one (ifx_map.hip, key_id / local_slot):
@@ -370,7 +374,8 @@ struct ifx {
                                      // +1.4 %); with the solve in the next launch's prologue the two-launch form is within 0.7 % of it (profiles/r04_b_ab_gn_prologue*.txt), and a spinning grid barrier does
                                      // not belong on the default frame path for that: off.  As an option it is safe: a meeting that does not happen costs time, never the pose (k_gn_level_solo)
     int gn_max_blocks[4] = {0, 0, 0, 0};   // co-resident blocks of k_gn_level<1 | 2 | 3 | 4>
-    int opt_rgb_blocks = 0;          // cap on the blocks of the photometric step (0: 192)
+    int opt_rgb_blocks = 0;          // cap on the blocks of the photometric step (0: 192; over the candidate list: rgb_cand_blocks()) AND, in fused iterations (rgb_fuse), the number of
+                                     // photometric blocks of the launch (0: RGB_FUSE_BLOCKS): one knob for both, so a sweep of it also moves the run's last, two-launch iteration
     int opt_gn_prologue = 1;         // two-launch Gauss-Newton iterations: the 6x6 solve of iteration j runs in the prologue of EVERY block of iteration j + 1's first launch (no last-block
                                      // hand-off inside the photometric step's launch); 0: round 3's form, the last block of the photometric step solves and stores the pose
     // spatially sharded map: ifx_owner_segmentation_begin / _resume carry one segmentation call across its exchange points
@@ -395,6 +400,10 @@ struct ifx {
     int opt_rgb_cand = 1;            // frame-to-model tracker, two-launch form: the residual pass and the photometric step run over the frame slot's candidate list (FrameSlot::cand) and
                                      // the level's `corres` holds one record per candidate.  0: the dense bodies, bit for bit what they were.  A run in which a dense form would
                                      // share `corres` with the list form (a persistent level: gn_persist; the row-sharded reductions: own_track_rows) is dense as a whole
+    int opt_rgb_fuse = 7;            // a bit per pyramid level (list runs, prologue chain): the photometric step of an iteration runs inside its residual launch -- the photometric
+                                     // blocks meet after their residual pass and step the records by claimed chunks (k_icp_residual<.., FUSE>).  0: two launches per iteration
+    int opt_rgb_fuse_poll = 1;       // test switch: 0 = no photometric block of a fused launch waits at the meeting (all but the last arriver leave at once; it steps every chunk alone)
+    int icp_resident_blocks_fuse = 1024;   // icp_resident_blocks of the fused variant
     int opt_icp_blocks = 0;          // cap on the blocks of a tracker reduction launch; 0 = by image size (ifx_track.hip red_blocks)
     int opt_raster_tiles = -1;       // tiled rasteriser (k_tile_*: key tiles resolved in LDS) instead of global atomics: 0 off, 1 on, -1 by image size (on from 1 Mpixel:
                                      // at 640x480 / 5M surfels the binning passes cost what the LDS tiles save, at 1280x960 / 20M the frame rate gains 12 %)

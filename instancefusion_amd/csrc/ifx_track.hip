@@ -9,6 +9,7 @@
 //  * reductions are wave64: 64-lane __shfl_down trees, one LDS slot per wave, fixed order.
 //  * the 13x13 bilateral stages its depth tile through LDS.
 #include "ifx_ctx.h"
+#include "ifx_rgb_chunks.h"
 #include <math.h>
 #include <string.h>
 
@@ -412,6 +413,7 @@ __global__ void k_model_down(const DevState* __restrict__ st, const float* __res
 
 #define RED_THREADS 256
 #define RED_WAVES (RED_THREADS / 64)
+static_assert(RGB_CHUNK_THREADS == RED_THREADS, "a chunk of the fused photometric step is RGB_CHUNK_IT records per thread of a reduction block");
 
 // Exact block sum of NV doubles per thread (grid-valued terms, see ifx_dev.h): quads by DPP, 64 quad sums per value through
 // LDS, eight partial sums per value, then ONE f64 atomic add per value and block into replica `rep` of the global accumulator
@@ -549,8 +551,14 @@ __shared__ long long s_dbg_blk[4];
 // A' were all on the critical path of every iteration.  Here B just sums; EVERY block of A' fetches the totals of the previous iteration itself (the same 58 agent-scope
 // loads the last block did), rebuilds the combined system and solves it on its lane 0 -- the same totals give the same bits in every block -- while the loads of its
 // first pixels, which do not depend on the pose, are already in flight.  No ticket, no last block, no pose round trip through memory; the run's LAST iteration keeps the
-// last-block form (it also ends the run: pose write-back, velocity weighting, view-list decision).  Sums, residual totals and the running increment are double-buffered
-// by iteration parity (DevState::gnp_*): iteration j writes parity j & 1, launch B of iteration j + 1 clears it after every block of launch A of j + 1 has read it.
+// last-block form (it also ends the run: pose write-back, velocity weighting, view-list decision).  The running increment is double-buffered by iteration parity
+// (DevState::gnp_RRt).  Sums, residual totals and the meeting words of the fused form rotate through THREE sets (DevState::gnp_acc / gnp_res / gnp_meet): iteration j sums
+// into set j % 3, the prologues of iteration j + 1 read it, and iteration j clears set (j + 1) % 3 = (j - 2) % 3, whose last readers -- the prologues of iteration j - 1
+// -- are complete by stream order.  Who clears: block 0 of launch B in a two-launch iteration, the last block of the one launch in a fused iteration (option rgb_fuse,
+// k_icp_residual<.., FUSE>: no launch B, so no block of the launch that reads a set may clear it -- hence three sets and not two); the clearing block also runs the
+// range guard on the totals it clears.  INVARIANT: all three sets are zero when a run starts.  Launch B of the run's last chain iteration (StepArgs::pro == 2, always
+// a two-launch iteration) guarantees it: its last block clears its own set behind the solve (gn_solve_block), its block 0 clears BOTH other sets.  A run that was
+// enqueued ahead and dropped still runs to that launch, so it leaves the sets zero too; DevState starts zeroed.
 struct KInv { double i0, i4, i2, i5; };
 struct GnPro {
     int k;                        // position of this launch's iteration in the run's two-launch tail; k >= 1: iteration k - 1 is solved in the prologue
@@ -566,7 +574,7 @@ __device__ __forceinline__ const float* gn_prologue(const DevState* __restrict__
 {
     __shared__ double s_psys[27];
     __shared__ float s_ppose[24];
-    const int prev = (g.k - 1) & 1;
+    const int prev = (g.k - 1) % 3;   // (the set of the iteration before; the running increment below keeps its parity)
     const double* const icp_acc = st->gnp_acc + (size_t)(prev * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE;
     const double* const rgb_acc = icp_acc + IFX_ACC_REPL * IFX_ACC_STRIDE;
     if (threadIdx.x < 27) {
@@ -818,8 +826,10 @@ __global__ __launch_bounds__(RED_THREADS) void k_rgb_residual(const DevState* __
 // goes to corres[t] -- one record per candidate, which the list form of the photometric step reads back by the same t.  The count lives on the device only: the grid is
 // fixed per level and strides over the list; a block past the count still runs the prologue (its barriers, block 0's hand-off of the increment) and adds nothing.
 // Three entries deep: the gathers of this round, the own-pixel loads of the next and the entry of the round after are in flight together; no load sits behind a branch.
-template <bool PRO>
-__device__ __forceinline__ void residual_cand_body(int bid, int nblk, const DevState* __restrict__ st, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n,
+// SC1 (the fused iteration, k_icp_residual<.., FUSE>): the records are read back by OTHER workgroups of the same launch, so each goes out as one 8-byte agent-scope
+// store (write-through).  Returns the count the block ran over.
+template <bool PRO, bool SC1 = false>
+__device__ __forceinline__ int residual_cand_body(int bid, int nblk, const DevState* __restrict__ st, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n,
                                                    const float* __restrict__ lastDepth, const float* __restrict__ nextDepth, const uint8_t* __restrict__ lastImage,
                                                    const uint8_t* __restrict__ nextImage, Corres8* __restrict__ corres, float maxDepthDelta, int w, int h,
                                                    int* __restrict__ res_total, const GnPro* pro, double* __restrict__ rrt_out)
@@ -828,7 +838,7 @@ __device__ __forceinline__ void residual_cand_body(int bid, int nblk, const DevS
     const int stride = nblk * RED_THREADS;
     int t = bid * RED_THREADS + threadIdx.x;
     // in flight before the warp matrices are known (PRO: under the prologue's solve): the count, the first two entries, then the first entry's own pixel
-    const int n = min((int)cand_n[0], N);
+    const int n = SC1 ? rgb_chunk_n(cand_n[0], N) : min((int)cand_n[0], N);   // (the fused form's clamp to the capacity is the one its chunk arithmetic is checked with)
     const CandEntry e0 = cand[t < N ? t : 0];
     CandEntry e1 = cand[t + stride < N ? t + stride : 0];
     int pix = t < n ? (int)min(e0.pixel, (uint32_t)(N - 1)) : 0;   // (an entry names a pixel of the level by construction; the clamp keeps a wrong one inside the images)
@@ -867,7 +877,11 @@ __device__ __forceinline__ void residual_cand_body(int bid, int nblk, const DevS
         c.diff = hit ? diff : 0.f;
         cnt += hit ? 1 : 0;
         sig += hit ? (int)(diff * diff) : 0;
-        corres[t] = c;
+        if (SC1) {
+            unsigned long long bits;
+            __builtin_memcpy(&bits, &c, 8);
+            __hip_atomic_store(reinterpret_cast<unsigned long long*>(corres + t), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else corres[t] = c;
         t = tn; pix = pixn; d1 = d1n; ni = nin; e1 = e2;
     }
     __shared__ int lds[RED_WAVES][2];
@@ -881,6 +895,150 @@ __device__ __forceinline__ void residual_cand_body(int bid, int nblk, const DevS
         for (int wv = 0; wv < RED_WAVES; wv++) s += lds[wv][threadIdx.x];
         if (s) atomicAdd(&res_total[threadIdx.x], s);   // grand totals by integer atomics (exact in any order)
     }
+    return n;
+}
+
+// ======================================================================= the photometric step inside the residual launch (option rgb_fuse)
+// Over the candidate list the whole photometric side of an iteration is the work of one or two dozen workgroups, and launch B of a prologue-chain iteration does
+// nothing but sum their ~6000 records: a launch boundary (8-10 us) where a meeting of a few workgroups (1.5 us, profiles/r06_h_xcd_meeting_micro.txt) does.  In the fused
+// form the G photometric blocks of launch A (a) run the residual pass over their strided share, storing each record with one 8-byte agent-scope (write-through) store,
+// (b) drain, meet the block's barrier and add 1 to the set's arrival word, (c) wait -- BOUNDED -- until all G have arrived, (d) form sigma from the now complete
+// totals and step the records by chunks claimed from the set's chunk counter (ifx_rgb_chunks.h), ending in one exact block sum into this iteration's photometric row.
+// The hand-off is the write-through form of cdna_hip_programming.md section 6 G16 (R1) with a counter as the flag: (1) every record store is an agent-scope atomic
+// store (sc1), the totals are agent-scope atomics; (2) every wave drains vmcnt, then the barrier, then ONE lane's arrival add; (3) the polled word is written by
+// atomics only; (4) the records and the totals are read back with agent-scope (sc1) loads to registers, never through the scalar path (no `const __restrict__` on
+// `corres` here) -- everything else the step loads (entries, point cloud) is written by no block of this launch.
+// The wait cannot hang: the block that draws the last arrival never waits, and any other block stops polling after RGB_MEET_TICKS and leaves (counted in
+// DevState::rgb_meet_giveups).  The last arriver always steps, and chunks are claimed, not assigned: every chunk is stepped whatever the others did, so a photometric
+// block that was not resident costs time, never the sums or a hang.  Which block steps which chunk varies from run to run and does not show: exact sums of
+// grid-valued terms, any partition gives the same bits (range_exceeded7's argument above).
+// The bound: four times the two-launch form's icp_residual@L0 launch, 13.43 us by HIP events (profiles/r18_rgb_candidates.txt section 3) = 53.7 us, in ticks of the
+// 100 MHz constant clock (wall_clock64).
+#define RGB_MEET_TICKS 5372u
+struct FuseArgs {
+    const float* cloud;
+    float sobelScale;
+    int g;                       // photometric blocks of the launch: they take the FIRST block ids (they are the launch's critical chain), the ICP blocks follow
+    unsigned int poll_ticks;     // RGB_MEET_TICKS; 0 (test switch rgb_fuse_poll = 0): nobody waits -- every block but the last arriver leaves at once
+    unsigned int* meet;          // this iteration's set of DevState::gnp_meet: [0] arrivals, [16] next unclaimed chunk
+    double* clear_acc;           // set (k + 1) % 3 of gnp_acc / gnp_res / gnp_meet, cleared by the launch's last block ...
+    int* clear_res;
+    unsigned int* clear_meet;
+    int* range_ctr;              // ... with the range guard on the totals it clears (DevState::range_exceeded)
+    int* giveups;                // DevState::rgb_meet_giveups
+};
+static_assert(sizeof(Corres8) == 8, "a record is handed over as one 8-byte store");
+// One set of the prologue chain's rotation back to zero, with the run-time guard of the exact sums (range_exceeded7) on the totals it held -- here, where they are
+// cleared, because the prologues that consumed them sit in a launch that has no register to spare.  A whole block; its last readers are complete by stream order.
+__device__ __forceinline__ void gnp_clear_set(double* acc, int* res, unsigned int* meet, int* range_ctr)
+{
+    if (threadIdx.x < 64) {
+        const int kind = threadIdx.x >> 5, k = threadIdx.x & 31;
+        if (k < 28 && range_exceeded7(kind, k, acc_total(acc + (size_t)kind * IFX_ACC_REPL * IFX_ACC_STRIDE, k))) atomicAdd(range_ctr, 1);
+    }
+    __syncthreads();
+    static_assert(2 * IFX_ACC_REPL * IFX_ACC_STRIDE == RED_THREADS, "one store per thread clears a set's rows");
+    __hip_atomic_store(&acc[threadIdx.x], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x < 2) __hip_atomic_store(&res[threadIdx.x], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x >= 64 && threadIdx.x < 66) __hip_atomic_store(&meet[(threadIdx.x - 64) * 16], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// (b) to (d) of a photometric block, behind its residual pass over `n_wave` records.  The count is read by every wave for itself, and under a dropped run whose slot is
+// being rewritten two waves of one block may have read different counts: everything block-wide below -- the early exit, the chunk loop with its barriers -- runs on
+// ONE count, thread 0's, handed round through LDS beside the first claim.
+__device__ __forceinline__ void rgb_fused_step(int bid, int n_wave, Corres8* corres, const CandEntry* __restrict__ cand, int w, int h, float fx, float fy, int* res_total,
+                                               double* __restrict__ rgb_acc, const FuseArgs& f)
+{
+    __shared__ int s_go, s_n;
+    __shared__ unsigned int s_chunk;
+    // (b) arrival: this block's records and its adds to the totals have been performed at the memory side before anybody can count it in
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int all = (unsigned int)f.g;
+        const unsigned int t = __hip_atomic_fetch_add(&f.meet[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int go = t + 1u >= all;   // the last arriver goes on at once
+        if (!go) {                // (c) everybody else polls one word, relaxed, until all have arrived or the bound has passed
+            if (f.poll_ticks) {
+                const unsigned long long t0 = wall_clock64();
+                for (;;) {
+                    if (__hip_atomic_load(&f.meet[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= all) { go = 1; break; }
+                    if (wall_clock64() - t0 > (unsigned long long)f.poll_ticks) break;
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            }
+            if (!go) atomicAdd(f.giveups, 1);
+        }
+        s_chunk = go ? __hip_atomic_fetch_add(&f.meet[16], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xFFFFFFFFu;
+        s_go = go;
+        s_n = n_wave;
+    }
+    __syncthreads();
+    if (!s_go) return;
+    const int n = __builtin_amdgcn_readfirstlane(s_n);   // the block's count: uniform over its waves
+    // (d) every block that is here has seen all G arrivals: the totals are complete and every record of [0, n) is in memory
+    unsigned int chunk = s_chunk;
+    if (chunk >= (unsigned int)rgb_chunk_count(n)) return;   // nothing left (uniform over the block)
+    float sigma;
+    {   // as rgb_step_cand_body forms it
+        const int cnt = __hip_atomic_load(&res_total[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sg = __hip_atomic_load(&res_total[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        float q = (float)sg / (float)cnt;
+        sigma = (float)sqrt((double)((q == 0) ? 1 : cnt));
+    }
+    double acc[29];
+#pragma unroll
+    for (int k = 0; k < 29; k++) acc[k] = 0.0;
+    for (;;) {
+        const RgbChunk r = rgb_chunk_range(chunk, n);
+        if (r.first >= r.end) break;   // (uniform)
+        Corres8 c[RGB_CHUNK_IT];
+        CandEntry e[RGB_CHUNK_IT];
+#pragma unroll
+        for (int u = 0; u < RGB_CHUNK_IT; u++) {   // (a thread past the chunk's end reads the chunk's first record and drops it: no branch around the loads)
+            const int k = r.first + (int)threadIdx.x + u * RED_THREADS;
+            const bool in = k < r.end;
+            const int kk = in ? k : r.first;
+            const unsigned long long bits = __hip_atomic_load(reinterpret_cast<unsigned long long*>(corres + kk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __builtin_memcpy(&c[u], &bits, 8);
+            e[u] = cand[kk];
+            if (!in) c[u].zx = -1;
+        }
+        __syncthreads();   // every thread holds `chunk`: the next claim goes out under this chunk's loads
+        if (threadIdx.x == 0) s_chunk = __hip_atomic_fetch_add(&f.meet[16], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        float X[RGB_CHUNK_IT], Y[RGB_CHUNK_IT], Z[RGB_CHUNK_IT];
+#pragma unroll
+        for (int u = 0; u < RGB_CHUNK_IT; u++) {
+            // a record counts only if its coordinates lie in the image (rgb_step_cand_body: a dropped run whose slot is rewritten under it may read records that no
+            // residual pass of this count wrote; changes no record that this iteration's residual pass wrote)
+            if (!((c[u].zx >= 0) & (c[u].zx < w) & (c[u].zy >= 0) & (c[u].zy < h))) c[u].zx = -1;
+            int g = (c[u].zx >= 0) ? ((int)c[u].zy * w + (int)c[u].zx) * 3 : 0;
+            X[u] = f.cloud[g]; Y[u] = f.cloud[g + 1]; Z[u] = f.cloud[g + 2];
+        }
+#pragma unroll
+        for (int u = 0; u < RGB_CHUNK_IT; u++) {
+            float row[7] = {0, 0, 0, 0, 0, 0, 0};
+            bool found = c[u].zx >= 0;
+            if (found) {
+                float wgt = sigma + fabsf(c[u].diff);
+                wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
+                if (sigma == -1) wgt = 1;
+                row[6] = -wgt * c[u].diff;
+                float invz = (float)(1.0 / Z[u]);
+                float dI_dx = wgt * f.sobelScale * e[u].gx;
+                float dI_dy = wgt * f.sobelScale * e[u].gy;
+                float v0 = dI_dx * fx * invz;
+                float v1 = dI_dy * fy * invz;
+                float v2 = -(v0 * X[u] + v1 * Y[u]) * invz;
+                row[0] = v0; row[1] = v1; row[2] = v2;
+                row[3] = -Z[u] * v1 + Y[u] * v2;
+                row[4] = Z[u] * v0 - X[u] * v2;
+                row[5] = -Y[u] * v0 + X[u] * v1;
+            }
+            products7<1>(row, found, acc);
+        }
+        __syncthreads();
+        chunk = s_chunk;
+    }
+    block_sum_exact<29>(acc, rgb_acc, bid % IFX_ACC_REPL);
 }
 
 // One launch for the two independent reductions of a Gauss-Newton iteration: blocks [0, nb_icp) run the
@@ -901,10 +1059,29 @@ struct PairArgs {
 // latency-bound launch.
 #define IFX_PIN_S(x) asm volatile("" ::"s"(x))
 // LIST (option rgb_cand): the residual half runs over the frame slot's candidate list `cand` / `cand_n` (residual_cand_body); the two arguments are unused otherwise
-template <bool CHECK_SKIP, bool PRO = false, bool LIST = false>
+// FUSE (option rgb_fuse, list runs only): the iteration's photometric step runs in this launch too (rgb_fused_step above; `f` is unused otherwise).  The a.nb_res
+// photometric blocks take the first block ids, the ICP blocks follow; block 0 stays the one publisher of `rrt_store`; the launch's last block first clears the next set.
+template <bool CHECK_SKIP, bool PRO = false, bool LIST = false, bool FUSE = false>
 __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState* __restrict__ st, int nb_icp, int w, int h, double* __restrict__ gacc, int* __restrict__ gres, PairArgs a, GnPro g,
-                                                              double* __restrict__ rrt_store, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n)
+                                                              double* __restrict__ rrt_store, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n, FuseArgs f)
 {
+    static_assert(!FUSE || LIST, "the fused iteration runs over the candidate list");
+    if (FUSE) {
+        __builtin_assume(st != nullptr);
+        if (CHECK_SKIP && st->skip) return;
+        const int nb_rgb = (int)gridDim.x - nb_icp;   // (= a.nb_res = f.g, without a load)
+        if (blockIdx.x == gridDim.x - 1) gnp_clear_set(f.clear_acc, f.clear_res, f.clear_meet, f.range_ctr);
+        if ((int)blockIdx.x < nb_rgb) {
+            const int n = residual_cand_body<PRO, true>(blockIdx.x, nb_rgb, st, cand, cand_n, a.lastDepth, a.nextDepth, a.lastImage, a.nextImage, a.corres, a.maxDepthDelta, w, h, gres, &g,
+                                                        blockIdx.x == 0 ? rrt_store : nullptr);
+            rgb_fused_step(blockIdx.x, n, a.corres, cand, w, h, a.fx, a.fy, gres, gacc + IFX_ACC_REPL * IFX_ACC_STRIDE, f);   // (the totals are read back with agent-scope loads)
+        } else {
+            IcpArgs ia;
+            icp_body<false, true, PRO>(blockIdx.x - nb_rgb, nb_icp, st, ia, a.vmap_curr, a.nmap_curr, a.vmap_prev, a.nmap_prev, a.fx, a.fy, a.cx, a.cy, a.distThres, a.angleThres, w, h, gacc, &g,
+                                       blockIdx.x == 0 ? rrt_store : nullptr);
+        }
+        return;
+    }
     // `st`, `nb_icp`, `w`, `h` and the two hand-off pointers (DevState::gn_acc / gn_res of `st`: separate arguments, so that the state itself stays
     // read-only here and its fields come through the scalar cache) arrive preloaded: the branch below is decided without a load, and each half then fetches its argument words and its
     // state fields in ONE scalar round trip (they used to be four to five dependent ones in front of the first vector load)
@@ -1918,7 +2095,7 @@ struct StepArgs {
     int end_run, commit;   // ... and ends the run in the same lane (track_end_dev)
     float weight_mult;
     unsigned int* lctr;
-    int pro, pro_k;        // option gn_prologue: 0 = round 3's form; 1 = sums only (the next launch's prologue solves); 2 = the run's last iteration (last-block form on the parity buffers).  pro_k: position in the two-launch tail
+    int pro, pro_k;        // option gn_prologue: 0 = round 3's form; 1 = sums only (the next launch's prologue solves); 2 = the run's last iteration (last-block form on the chain's buffers: sums and totals of set pro_k % 3, the increment by parity).  pro_k: position in the two-launch tail
 };
 // LIST (option rgb_cand): the sums run over the candidate list and its records (rgb_step_cand_body); `cand` / `cand_n` are unused otherwise
 template <bool CHECK_SKIP, bool LIST = false>
@@ -1926,22 +2103,18 @@ __global__ __launch_bounds__(RED_THREADS) void k_rgb_step_solve(DevState* st, in
 {
     __builtin_assume(st != nullptr);
     if (CHECK_SKIP && st->skip) return;   // (model-to-model instance only) uniform over the grid: the last-block ticket stays armed
-    // hand-off words and accumulator rows: behind the state pointer, which arrives preloaded.  gn_prologue: the buffers of this iteration's parity
-    const int par = a.pro_k & 1;
-    int* const res_total = a.pro ? st->gnp_res + par * 16 : st->gn_res;
+    // hand-off words and accumulator rows: behind the state pointer, which arrives preloaded.  gn_prologue: the buffers of this iteration's set (the increment: parity)
+    const int par = a.pro_k & 1, set = a.pro_k % 3;
+    int* const res_total = a.pro ? st->gnp_res + set * 16 : st->gn_res;
     unsigned int* const ticket = &st->gn_ticket;
-    double* const icp_acc = a.pro ? st->gnp_acc + (size_t)(par * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE : st->gn_acc;
+    double* const icp_acc = a.pro ? st->gnp_acc + (size_t)(set * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE : st->gn_acc;
     double* const rgb_acc = icp_acc + IFX_ACC_REPL * IFX_ACC_STRIDE;
     __shared__ int s_last;
-    if (a.pro && blockIdx.x == 0) {   // the other parity was last read by the prologues of this iteration's first launch: clean again for the next iteration's sums
-        double* const other = st->gnp_acc + (size_t)((1 - par) * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE;
-        if (threadIdx.x < 64) {   // run-time guard of the exact sums (range_exceeded7), on the totals of the iteration before, here where they are cleared: the prologues that
-            const int kind = threadIdx.x >> 5, k = threadIdx.x & 31;   // consumed them sit in a launch that has no register to spare (it spilled with the test in it)
-            if (k < 28 && range_exceeded7(kind, k, acc_total(other + (size_t)kind * IFX_ACC_REPL * IFX_ACC_STRIDE, k))) atomicAdd(&st->range_exceeded, 1);
+    if (a.pro && blockIdx.x == 0) {   // the rotation's rule (head of the prologue section): this iteration clears the next set, last read by the prologues of the iteration before;
+        for (int d = 1; d <= (a.pro == 2 ? 2 : 1); d++) {   // the chain's last iteration clears both other sets -- the next run starts from three zero sets
+            const int cs = (a.pro_k + d) % 3;
+            gnp_clear_set(st->gnp_acc + (size_t)(cs * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE, st->gnp_res + cs * 16, st->gnp_meet + cs * 32, &st->range_exceeded);
         }
-        __syncthreads();
-        __hip_atomic_store(&other[threadIdx.x], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // 2 x REPL x STRIDE = 256 doubles = RED_THREADS
-        if (threadIdx.x < 2) __hip_atomic_store(&st->gnp_res[(1 - par) * 16 + threadIdx.x], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #ifdef IFX_STAMPS
     long long t0 = clock64();
@@ -2526,6 +2699,8 @@ int ifx_alloc_tracker(ifx* h)
         for (int q = 0; q < 4; q++) h->gn_max_blocks[q] = std::max(0, occ[q]) * std::max(0, cus);
         int occ_ir = 0;   // one round of residency of the two-launch form's first launch (its residual half is capped to what the ICP half leaves of it: ifx_tracker_run)
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_ir, k_icp_residual<false, true>, RED_THREADS, 0) == hipSuccess && occ_ir > 0 && cus > 0) h->icp_resident_blocks = occ_ir * cus;
+        int occ_fu = 0;   // ... and of the fused variant (option rgb_fuse), whose photometric blocks meet inside the launch
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_fu, k_icp_residual<false, true, true, true>, RED_THREADS, 0) == hipSuccess && occ_fu > 0 && cus > 0) h->icp_resident_blocks_fuse = occ_fu * cus;
     }
     h->res_rows = std::max(maxb, cdiv(h->P, RED_THREADS) + 1);   // the residual pass runs one block per 256 pixels
     HIPCHK(h, hipMalloc(&h->res_partials, (size_t)h->res_rows * 2 * 4));
@@ -2591,6 +2766,15 @@ static inline int rgb_cand_blocks(const ifx* h, int n, int level, bool step)
     const int per_thread = 8 >> std::min(level, 2), opt = step ? h->opt_rgb_blocks : h->opt_res_blocks;
     const int b = opt > 0 ? std::min(opt, cdiv(n, RED_THREADS)) : cdiv(n, RED_THREADS * per_thread * (step ? RED_IT_RGB : 1));
     return std::max(1, b);
+}
+// Photometric blocks of a fused iteration (option rgb_fuse): they run the residual pass AND the step, and they are the launch's critical chain -- enough of them
+// that the bench stream's ~6000 candidates take one residual round and its dozen chunks a block each, few enough that the meeting stays a meeting of a few
+// workgroups.  640x480, frames/s of a --full run: 4: 1499, 8: 1703, 16: 1802, 32: 1803, 64: 1755; a long list (52 200 candidates at 320x240) wants 32 rather than 10
+// (profiles/r21_rgb_fused_step.txt section 4).  opt_rgb_blocks overrides -- the same option that sets the step's grid in the run's last, two-launch iteration.
+#define RGB_FUSE_BLOCKS 32
+static inline int rgb_fuse_blocks(const ifx* h, int n)
+{
+    return std::max(1, std::min(h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : RGB_FUSE_BLOCKS, cdiv(n, RED_THREADS)));
 }
 static inline int red_blocks(ifx* h, int n, int it = RED_IT)
 {
@@ -2823,8 +3007,9 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
     int persist_iters = 0;
     int tail_k = 0;   // position of the next two-launch iteration in the tail
     char* const stb = (char*)st;
-    auto gnp_acc_of = [&](int par) { return (double*)(stb + offsetof(DevState, gnp_acc)) + (size_t)(par * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE; };
-    auto gnp_res_of = [&](int par) { return (int*)(stb + offsetof(DevState, gnp_res)) + par * 16; };
+    auto gnp_acc_of = [&](int set) { return (double*)(stb + offsetof(DevState, gnp_acc)) + (size_t)(set * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE; };
+    auto gnp_res_of = [&](int set) { return (int*)(stb + offsetof(DevState, gnp_res)) + set * 16; };
+    auto gnp_meet_of = [&](int set) { return (unsigned int*)(stb + offsetof(DevState, gnp_meet)) + set * 32; };
     auto gnp_rrt_of = [&](int par) { return (double*)(stb + offsetof(DevState, gnp_RRt)) + par * 16; };
     // per-kernel timing (option kernel_timing) is kept per pyramid level: ifx_kernel_ms("icp_residual") sums the levels, "icp_residual@L0" is level 0 alone (bench.py's per-level roofline)
     static const char* const icp_name[3] = {"icp_residual@L0", "icp_residual@L1", "icp_residual@L2"};
@@ -2874,16 +3059,33 @@ static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3,
             continue;
         }
         for (int j = 0; j < iterations[i]; j++) {
-            // gn_prologue: iteration tail_k sums into parity tail_k & 1; from the tail's second iteration on, every block first solves the iteration before
+            // gn_prologue: iteration tail_k sums into set tail_k % 3 (its increment goes to parity tail_k & 1); from the tail's second iteration on, every block first solves the iteration before
             GnPro gp;
             gp.k = tail_k; gp.icp = icp; gp.rgb = rgb; gp.icp_weight = icp_weight; gp.nfx = fx; gp.nfy = fy; gp.ncx = cx; gp.ncy = cy; gp.ki = kinv_of(fx, fy, cx, cy);
             const bool it_pro = pro && tail_k < n_pro;
-            double* const ga = it_pro ? gnp_acc_of(tail_k & 1) : gacc;
-            int* const gr = it_pro ? gnp_res_of(tail_k & 1) : gres;
+            const bool fuse = cand_run && it_pro && tail_k < n_pro - 1 && (h->opt_rgb_fuse & (1 << i));   // option rgb_fuse: the step in this launch (every chain iteration but the last, StepArgs::pro == 1)
+            double* const ga = it_pro ? gnp_acc_of(tail_k % 3) : gacc;
+            int* const gr = it_pro ? gnp_res_of(tail_k % 3) : gres;
             double* const rrt_store = gnp_rrt_of((tail_k + 1) & 1);   // the increment after iteration tail_k - 1
             // <CHECK_SKIP, PRO>: the model-to-model tracker checks the skip flag; from the prologue chain's second iteration on every block first solves the iteration before
             // ... and over the candidate list when the run is a list run (LIST)
-            auto go_icp = [&](auto kernel) { LAUNCH(h, icp_name[i], dim3(pa.nb_icp + pa.nb_res), dim3(RED_THREADS), kernel, st, pa.nb_icp, pa.w, pa.h, ga, gr, pa, gp, rrt_store, cl, cln); };
+            FuseArgs fa;
+            memset(&fa, 0, sizeof(fa));
+            PairArgs paf = pa;
+            if (fuse) {   // G photometric blocks (rgb_fuse_blocks), within one round of residency beside the ICP blocks
+                paf.nb_res = std::max(1, std::min(rgb_fuse_blocks(h, n), h->icp_resident_blocks_fuse - pa.nb_icp));
+                const int cs = (tail_k + 1) % 3;
+                fa.cloud = p.cloud[i]; fa.sobelScale = (float)sobelScale; fa.g = paf.nb_res; fa.poll_ticks = h->opt_rgb_fuse_poll ? RGB_MEET_TICKS : 0u;
+                fa.meet = gnp_meet_of(tail_k % 3); fa.clear_acc = gnp_acc_of(cs); fa.clear_res = gnp_res_of(cs); fa.clear_meet = gnp_meet_of(cs);
+                fa.range_ctr = (int*)(stb + offsetof(DevState, range_exceeded)); fa.giveups = (int*)(stb + offsetof(DevState, rgb_meet_giveups));
+            }
+            auto go_icp = [&](auto kernel) { LAUNCH(h, icp_name[i], dim3(paf.nb_icp + paf.nb_res), dim3(RED_THREADS), kernel, st, paf.nb_icp, paf.w, paf.h, ga, gr, paf, gp, rrt_store, cl, cln, fa); };
+            if (fuse) {
+                if (tail_k > 0) { if (frame_tracker) go_icp(k_icp_residual<false, true, true, true>); else go_icp(k_icp_residual<true, true, true, true>); }
+                else { if (frame_tracker) go_icp(k_icp_residual<false, false, true, true>); else go_icp(k_icp_residual<true, false, true, true>); }
+                tail_k++;
+                continue;
+            }
             if (it_pro && tail_k > 0) {
                 if (frame_tracker) { if (cand_run) go_icp(k_icp_residual<false, true, true>); else go_icp(k_icp_residual<false, true>); }
                 else { if (cand_run) go_icp(k_icp_residual<true, true, true>); else go_icp(k_icp_residual<true, true>); }
