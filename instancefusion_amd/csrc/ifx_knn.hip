@@ -9,12 +9,14 @@
 // (bestIDInEachSurfel >= 0 only; first maximum; nothing changes when no neighbour is labelled).
 //
 // Here: exact k-NN on a uniform grid instead of a kd-tree.  Cells = bounding box of the live surfels cut into
-// <= 256 cells along its longest side; counting sort by cell (histogram, exclusive scan, scatter); a query walks
+// knn_grid_side(points) <= 256 cells along its longest side (at most 8 cells per point, ifx_knn_grid.h); counting
+// sort by cell (histogram, exclusive scan, scatter); a query walks
 // the cell shells around its own cell and stops as soon as its 10th candidate is closer than the inner border
 // of the next shell, so the result is the exact k-NN set.  Ties in distance go to the lower map index (FLANN
 // leaves that order unspecified); the oracle uses the same rule with a brute-force search.
 #include "ifx_ctx.h"
 #include "ifx_dev.h"
+#include "ifx_knn_grid.h"
 #include <algorithm>
 
 #define DEAD_TIME (-1.0e9f)   // tombstone marker in times.y (ifx_map.hip)
@@ -22,7 +24,7 @@
 namespace {
 
 constexpr int KNN = 10;
-constexpr int GRID_MAX = 256;
+constexpr int GRID_MAX = KNN_GRID_MAX;   // the buffers' size; the grid of a call has knn_grid_side(points) cells along its longest side
 
 struct KnnGrid {        // device-resident, filled by k_knn_grid
     int lo_bits[3], hi_bits[3];   // ordered-int encodings of the bounding box (atomicMin / atomicMax)
@@ -57,17 +59,19 @@ __global__ void k_knn_bounds(const DevState* __restrict__ st, const float4* __re
         if ((threadIdx.x & 63) == 0) { atomicMin(&g->lo_bits[k], lo[k]); atomicMax(&g->hi_bits[k], hi[k]); }
     }
 }
-__global__ void k_knn_grid(KnnGrid* g)
+// count: the points of the call -- st->count (tombstones included: an upper bound of the live ones) or, for an explicit set (st == nullptr), n
+__global__ void k_knn_grid(KnnGrid* g, const DevState* __restrict__ st, int n)
 {
     if (threadIdx.x != 0) return;
+    const int side = knn_grid_side(st ? st->count : n);
     float ext = 0.f;
     for (int k = 0; k < 3; k++) { g->lo[k] = unord(g->lo_bits[k]); ext = fmaxf(ext, unord(g->hi_bits[k]) - g->lo[k]); }
     if (!(ext > 0.f)) ext = 1.0f;
-    g->cell = ext / (float)(GRID_MAX - 1);
+    g->cell = ext / (float)(side - 1);
     g->inv_cell = 1.0f / g->cell;
     for (int k = 0; k < 3; k++) {
         int d = (int)((unord(g->hi_bits[k]) - g->lo[k]) * g->inv_cell) + 1;
-        g->dim[k] = min(max(d, 1), GRID_MAX);
+        g->dim[k] = min(max(d, 1), side);
     }
 }
 __device__ __forceinline__ void cell_of(const KnnGrid* g, float4 p, int* c)
@@ -126,9 +130,9 @@ __global__ void __launch_bounds__(128) k_knn_vote(const DevState* __restrict__ s
     for (int r = 0; r <= rmax; r++) {
         for (int z = max(c[2] - r, 0); z <= min(c[2] + r, dz - 1); z++)
             for (int y = max(c[1] - r, 0); y <= min(c[1] + r, dy - 1); y++) {
-                const bool face = abs(z - c[2]) == r || abs(y - c[1]) == r;   // on a z / y face the whole x run is new, else only its two ends
-                for (int x = max(c[0] - r, 0); x <= min(c[0] + r, dx - 1); x++) {
-                    if (!face && abs(x - c[0]) != r) continue;
+                const bool face = abs(z - c[2]) == r || abs(y - c[1]) == r;   // on a z / y face the whole x run is new, else only its two ends (ifx_knn_grid.h)
+                const int x1 = knn_row_last(c[0], r, dx), xs = knn_row_step(r, face);
+                for (int x = knn_row_first(c[0], r, face); x <= x1; x += xs) {
                     const int id = (z * dy + y) * dx + x, s0 = start[id], s1 = s0 + counts[id];
                     for (int s = s0; s < s1; s++) {
                         const float4 p = sorted[s];
@@ -250,8 +254,8 @@ __global__ void __launch_bounds__(128) k_knnx_vote(const KnnGrid* __restrict__ g
         for (int z = max(c[2] - r, 0); z <= min(c[2] + r, dz - 1); z++)
             for (int y = max(c[1] - r, 0); y <= min(c[1] + r, dy - 1); y++) {
                 const bool face = abs(z - c[2]) == r || abs(y - c[1]) == r;
-                for (int x = max(c[0] - r, 0); x <= min(c[0] + r, dx - 1); x++) {
-                    if (!face && abs(x - c[0]) != r) continue;
+                const int x1 = knn_row_last(c[0], r, dx), xs = knn_row_step(r, face);
+                for (int x = knn_row_first(c[0], r, face); x <= x1; x += xs) {
                     const int id = (z * dy + y) * dx + x, s0 = start[id], s1 = s0 + counts[id];
                     for (int s = s0; s < s1; s++) {
                         const float4 p = sorted[s];
@@ -327,7 +331,7 @@ int ifx_knn_vote(ifx* h, int32_t* d_nbr_out)
     HIPCHK(h, hipMemsetAsync(fill, 0, cells * 4, h->cur));
     LAUNCH(h, "knn_bounds_init", dim3(1), dim3(64), k_knn_bounds_init, g);
     LAUNCH(h, "knn_bounds", dim3(1024), dim3(256), k_knn_bounds, h->d_state, (const float4*)h->pc, (const float2*)h->tm, g);
-    LAUNCH(h, "knn_grid", dim3(1), dim3(64), k_knn_grid, g);
+    LAUNCH(h, "knn_grid", dim3(1), dim3(64), k_knn_grid, g, (const DevState*)h->d_state, 0);
     LAUNCH(h, "knn_count", dim3(2048), dim3(256), k_knn_count, h->d_state, (const float4*)h->pc, (const float2*)h->tm, g, cell_id, counts);
     int r = ifx_scan_exclusive(h, counts, (int)cells, starts, total);
     if (r) return r;
@@ -400,7 +404,7 @@ extern "C" int ifx_owner_knn_vote(ifx_t* h, const void* d_all_points, const void
     HIPCHK(h, hipMemsetAsync(fill, 0, cells * 4, h->cur));
     LAUNCH(h, "knn_bounds_init", dim3(1), dim3(64), k_knn_bounds_init, g);
     LAUNCH(h, "knnx_bounds", dim3(1024), dim3(256), k_knnx_bounds, pts, n_all, g);
-    LAUNCH(h, "knn_grid", dim3(1), dim3(64), k_knn_grid, g);
+    LAUNCH(h, "knn_grid", dim3(1), dim3(64), k_knn_grid, g, (const DevState*)nullptr, n_all);
     LAUNCH(h, "knnx_count", dim3(2048), dim3(256), k_knnx_count, pts, n_all, g, cell_id, counts);
     int r = ifx_scan_exclusive(h, counts, (int)cells, starts, total);
     if (r) return r;
