@@ -842,6 +842,72 @@ int ifx_process_segmentation_detections(ifx_t* h, const float* d_mask_logits, co
 int ifx_process_segmentation_deferred_detections(ifx_t* h, int ticket, const float* d_mask_logits, const float* d_boxes, const float* d_scores,
                                                  const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
                                                  const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept);
+/* ---- the reference's default detector (IF/main.cpp:33, maskRcnnType = 1 -> build/mask_ori.py: the Keras Mask R-CNN under deps/mask_rcnn).  Its model ends in
+ * detections [R,6] and mrcnn_mask [R,M,M,C]; MaskRCNN.unmold_detections (deps/mask_rcnn/model.py:2285-2344) turns them into image-sized masks on the CPU, one
+ * detection at a time, through utils.unmold_mask (deps/mask_rcnn/utils.py:490-507) and scipy.misc.imresize: a per-mask min/max stretch to bytes, Pillow's 8-bit
+ * bilinear resampling to the box's size, a threshold, a paste.  ifx_unmold_detections is that routine for ONE image on the device; ifx_process_segmentation_unmolded
+ * runs it in front of ifx_process_segmentation_device.  In numpy: tests/unmold_numpy.py, held against the reference's own Python through
+ * tests/golden/unmold_cases.npz (tests/test_unmold_cpu.py).
+ *   Inputs: d_detections [R][6] f32 (y1, x1, y2, x2, class_id, score) in molded-image pixels, zero rows behind the last detection; d_masks f32, [R][M][M][C]
+ *     (IFX_UNMOLD_NHWC, as Keras emits it) or [R][C][M][M] (IFX_UNMOLD_NCHW); window[4] int32 ON THE HOST (wy1, wx1, wy2, wx2), the image's place in the molded
+ *     input (ifx_molded_input_size's last four); d_class_map int32 [C] on the device or NULL, as ifx_mask_head_select takes it; width x height: the image the
+ *     masks are made for.  0 <= R <= 1024, 1 <= M <= 64, 2 <= C <= 1024.  Every f32 operation is rounded to f32, none is fused.
+ *   1 Count: N = the first row with class_id == 0.0f (-0 too), R when there is none (model.py:2304-2305).
+ *   2 Boxes (model.py:2314-2322): scale = min(height / (wy2 - wy1), width / (wx2 - wx1)) on the host in f64; per coordinate k with the shift (wy1, wx1, wy1, wx1):
+ *     b_k = (int32)trunc((f64(det[k]) - f64(shift_k)) * scale) -- numpy promotes f32 - int64 to f64.
+ *   3 Exclusion (model.py:2326-2333): a row survives iff (y2 - y1) * (x2 - x1) > 0, in int64.  Dropped rows vanish, later rows move up.
+ *   4 Bytes (scipy.misc.bytescale behind imresize): c = (int32)class_id, m = the M x M samples of channel c of the row; cmin, cmax over them; cs = f32(cmax - cmin),
+ *     1 if that is 0; s = f32(255.0 / f64(cs)); byte = (uint8)trunc(min(max(f32(f32(m - cmin) * s), 0), 255) + 0.5f).  This is bytescale as numpy evaluated it
+ *     when the reference was written: float / np.float32 gave a float64 scalar, and a float64 scalar did not widen a float32 array.
+ *   5 Resize: the M x M bytes to h = y2 - y1 rows and w = x2 - x1 columns by the 8-bit rule stated under ifx_detector_input: the taps of precompute_coeffs with
+ *     in = M in f64 (PRECISION_BITS 22), made on the device per detection and equal to ifx_detector_resize_taps' integer for integer; the horizontal pass first,
+ *     a uint8 intermediate [M][w], then the vertical pass; each pass clip8((2^21 + sum v * k) >> 22), an axis that keeps the size M being the identity.
+ *   6 Threshold: inside iff the byte >= 128 (f32(b) / 255.0f >= 0.5f holds exactly from 128 on).  7 Paste: pixel (y1 + j, x1 + i) (utils.py:505-506).
+ *   8 Where the reference raises or has no defined result the row's mask is empty and the call goes on (the ROI entry's convention); the row still counts:
+ *     a box not within 0 <= y1 < y2 <= height, 0 <= x1 < x2 <= width (both extents negative passes step 3); a coordinate that is not finite or beyond +-2^24,
+ *     before or after the scale -- such a row skips step 3 and its box is written as zeros; a class id that is NaN or outside 1 .. C - 1 -- its class id is
+ *     written as 0, not mapped; a NaN or +-inf among the M^2 samples, or cs or s not finite in f32.
+ *   Output, the surviving rows in input order: d_masks_out [R][height * width] u8, 0 / 1; d_class_ids [R] int32 (through d_class_map if given); d_boxes_out
+ *     [R][4] int32 (y1, x1, y2, x2); d_scores_out [R] f32 (may be NULL); d_rows [R] int32, the input row (may be NULL); d_kept one int32.  Behind kept: masks,
+ *     boxes and scores 0, class ids and rows -1.
+ *   How: one block of 1024 threads, one thread per row, does steps 1 to 3 and the detector operators' block scan, and scatters the records; one memset of the
+ *     masks; a launch over (column tiles of 64 pixels, R): a block finds its row by the same scan (the box is known only on the device, so nothing travels between
+ *     the launches), leaves when it is past kept or beside the box, reduces min / max, stretches the channel to bytes in LDS, makes the horizontal taps of its
+ *     columns (one lane per column, f64), resamples into an [M][64] byte tile, then walks the box's rows in chunks of 64 (one lane making one row's taps).
+ * ifx_unmold_detections: the stage on the caller's buffers and stream: enqueue only, no host synchronisation, no allocation, no frame or map state, any handle (a
+ *   sharded one too; the u8 masks fit ifx_owner_process_segmentation_device).  R == 0 writes kept = 0 and nothing else.
+ * ifx_process_segmentation_unmolded: the stage into scratch of the handle (the detector operators' buffer, grown on demand) on `stream`, the producer's, at the
+ *   handle's frame size; one 4-byte read of kept, the only wait the call adds; then exactly ifx_process_segmentation_device on the kept masks with IFX_MASK_U8 --
+ *   the bridge's maskOri == 1 -> 255 and its stable area sort (build/mask_ori.py:104-117) are that entry's ingestion.  *out_kept (host, may be NULL) receives
+ *   kept; kept == 0 is n == 0.  R > 256 is refused: the scratch is R x P bytes, and the reference's R is 100 (DETECTION_MAX_INSTANCES, deps/mask_rcnn/config.py).
+ * ifx_process_segmentation_deferred_unmolded: the same behind a snapshot ticket; ticket rules as ifx_process_segmentation_deferred_device.
+ * Refusals (nothing enqueued, the handle stays usable, ifx_last_error starts with the entry's name): IFX_E_INVALID for R, M or C outside their ranges, an
+ *   unknown layout, NULL inputs or outputs with R > 0, a NULL window or d_kept, a window with wy2 <= wy1 or wx2 <= wx1, width or height < 1 (the stage), R > 256
+ *   (the process entries); IFX_E_STATE on a sharded handle for the process entries. */
+enum { IFX_UNMOLD_NHWC = 0, IFX_UNMOLD_NCHW = 1 };
+int ifx_unmold_detections(ifx_t* h, const float* d_detections, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M, int C,
+                          int layout, int width, int height, uint8_t* d_masks_out, int32_t* d_class_ids, int32_t* d_boxes_out, float* d_scores_out,
+                          int32_t* d_rows, int32_t* d_kept, void* stream);
+int ifx_process_segmentation_unmolded(ifx_t* h, const float* d_detections, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M,
+                                      int C, int layout, int frame, int flags, void* stream, int32_t* out_kept);
+int ifx_process_segmentation_deferred_unmolded(ifx_t* h, int ticket, const float* d_detections, const float* d_masks, const int32_t* window,
+                                               const int32_t* d_class_map, int R, int M, int C, int layout, int frame, int flags, void* stream, int32_t* out_kept);
+/* ---- the same detector's input: MaskRCNN.mold_inputs (deps/mask_rcnn/model.py:2247-2283) = utils.resize_image (deps/mask_rcnn/utils.py:384-432) + mold_image
+ * (model.py:2524-2529): a resize by its own size rule, a centred zero padding to max_dim x max_dim, the mean subtracted without a division, channels last.
+ * ifx_molded_input_size (host only: no handle, no GPU), all in f64 with Python's semantics: s = max(1, min_dim / min(h, w)) when min_dim > 0, else 1; if
+ *   rint(max(h, w) * s) > max_dim then s = max_dim / max(h, w); nh = rint(h * s), nw = rint(w * s), half to even (Python 3's round; no resize when s == 1);
+ *   S = max_dim, top = (S - nh) / 2, left = (S - nw) / 2 by floor division.  out8 = nw, nh, S, S, top, left, top + nh, left + nw -- the last four are the window
+ *   ifx_unmold_detections needs.  IFX_E_INVALID: a NULL out8, width or height < 1, max_dim < 1, nh or nw outside 1 .. S, a resize scale above 8 on an axis.
+ * ifx_detector_input_molded / _image: the frame sources, the event protocol with the consumer's `stream`, the cached tap tables, the kernel's two resampling
+ *   phases and the refusals of ifx_detector_input / _image.  They write S x S x 3 floats: inside the window the Pillow-resized byte b of channel c (RGB order, no
+ *   flip) as f32(f64(b) - mean[c]) -- mold_image subtracts an f64 array from an f32 one and Keras casts to f32: one rounding --, in the padding f32(0.0 - mean[c])
+ *   (resize_image pads with 0 before the mean is subtracted; +0 for a mean of 0).  mean: double[3] (MEAN_PIXEL, deps/mask_rcnn/config.py).  layout: [S][S][3] (IFX_MOLD_NHWC, Keras)
+ *   or [3][S][S] (IFX_MOLD_NCHW).  IFX_E_INVALID also for a NULL mean, an unknown layout and out_floats < 3 * S * S. */
+enum { IFX_MOLD_NHWC = 0, IFX_MOLD_NCHW = 1 };
+int ifx_molded_input_size(int width, int height, int min_dim, int max_dim, int32_t* out8);
+int ifx_detector_input_molded(ifx_t* h, int ticket, int min_dim, int max_dim, const double* mean, int layout, float* d_out, int64_t out_floats, void* stream);
+int ifx_detector_input_molded_image(ifx_t* h, const uint8_t* d_rgb, int width, int height, int min_dim, int max_dim, const double* mean, int layout, float* d_out,
+                                    int64_t out_floats, void* stream);
 /* ---- the three device forms on a spatially sharded map: a deployment has ONE detector, on one rank's GPU (no counterpart in the reference: one GPU, host masks).
  * ifx_owner_segmentation_begin_device / _rois / _detections join the state machine of ifx_owner_segmentation_begin: 1 = an exchange point is pending (reduce what
  * ifx_owner_exchange(h, 200, ...) lists, then ifx_owner_segmentation_resume), 0 = complete.  ifx_owner_process_segmentation_device / _rois / _detections are the

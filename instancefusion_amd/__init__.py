@@ -209,6 +209,12 @@ _SIGS = {
     "ifx_process_segmentation_detections": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float, C.c_int, C.c_int, _P, _P]),
     "ifx_process_segmentation_deferred_detections": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(MaskHeadParams), C.c_float, C.c_int,
                                                                C.c_int, _P, _P]),
+    "ifx_unmold_detections": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "ifx_process_segmentation_unmolded": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ifx_process_segmentation_deferred_unmolded": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "ifx_molded_input_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_detector_input_molded": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, _P]),
+    "ifx_detector_input_molded_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, _P]),
     # the device forms on a sharded map: (h, root, max_n, rgb, depth) in front of the unsharded entry's arguments
     "ifx_owner_segmentation_begin_device": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_owner_segmentation_begin_rois": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -382,6 +388,80 @@ def detector_input_image(ef, rgb, min_size=800, max_size=None, size_divisible=0,
     ef._chk(ef.L.ifx_detector_input_image(ef.handle, C.c_void_p(rgb.data_ptr()), w, hh, C.byref(p), C.c_void_p(out.data_ptr()), int(out.numel()),
                                           C.c_void_p(stream.cuda_stream or None)), "ifx_detector_input_image")
     return out, (int(size[1]), int(size[0]))
+
+
+# layouts of ifx_unmold_detections' mrcnn_mask and of ifx_detector_input_molded's output (include/ifx_c_api.h)
+UNMOLD_NHWC = 0      # [R,M,M,C], as Keras emits it
+UNMOLD_NCHW = 1      # [R,C,M,M], a torch port
+MOLD_NHWC = 0        # [S,S,3], Keras
+MOLD_NCHW = 1        # [3,S,S]
+MOLD_MEAN_PIXEL = (123.7, 116.8, 103.9)   # Config.MEAN_PIXEL (deps/mask_rcnn/config.py)
+
+
+def molded_input_size(width, height, min_dim=800, max_dim=1024):
+    """ifx_molded_input_size (host only, no GPU): (nw, nh, S, S, top, left, top + nh, left + nw) of a width x height frame by utils.resize_image
+    (deps/mask_rcnn/utils.py:384-432) with padding; the last four are the window unmold_detections needs."""
+    out = np.zeros(8, np.int32)
+    if lib().ifx_molded_input_size(int(width), int(height), int(min_dim), int(max_dim), _ptr(out)) < 0:
+        raise IfxError(f"ifx_molded_input_size: refused ({width} x {height}, min_dim {min_dim}, max_dim {max_dim})")
+    return tuple(int(v) for v in out)
+
+
+def _molded_args(ef, w, hh, min_dim, max_dim, mean, channels_last, out, stream):
+    """what the two molded-input calls share: (size8, mean as double[3], layout, out tensor, stream)"""
+    import torch
+
+    mean = [float(v) for v in mean]
+    if len(mean) != 3:
+        raise ValueError("mean has three entries")
+    size = molded_input_size(w, hh, min_dim, max_dim)
+    S = size[2]
+    dev = torch.device("cuda", int(ef.cfgd["device"]))
+    if stream is None:
+        stream = torch.cuda.current_stream(dev)
+    shape = (1, S, S, 3) if channels_last else (1, 3, S, S)
+    if out is None:
+        with torch.cuda.stream(stream):
+            out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch tensor on the handle's device")
+        if out.dtype != torch.float32:
+            raise TypeError(f"out: dtype {out.dtype} is not supported (float32)")
+        if out.device != dev:
+            raise ValueError(f"out is on {out.device}, the handle on {dev}")
+        if tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError(f"out: shape {tuple(out.shape)}, expected a contiguous {list(shape)}")
+    return size, (C.c_double * 3)(*mean), MOLD_NHWC if channels_last else MOLD_NCHW, out, stream
+
+
+def _molded_result(size, out, w, hh, min_dim, max_dim):
+    """(tensor, window (y1, x1, y2, x2), scale): the image, and what utils.resize_image returns beside it (the scale by its own two statements, utils.py:409-416)"""
+    scale = max(1, min_dim / min(hh, w)) if min_dim else 1
+    if round(max(hh, w) * scale) > max_dim:
+        scale = max_dim / max(hh, w)
+    return out, tuple(size[4:8]), scale
+
+
+def detector_input_molded_image(ef, rgb, min_dim=800, max_dim=1024, mean=MOLD_MEAN_PIXEL, channels_last=True, out=None, stream=None):
+    """ifx_detector_input_molded_image: InstanceFusion.detector_input_molded's kernel on any uint8 [H,W,3] torch tensor on the handle's device (the stage call);
+    `rgb` must be complete on `stream` (default: the current stream), the consumer's.  Returns (tensor [1,S,S,3] or [1,3,S,S] float32, window (y1, x1, y2, x2), scale)."""
+    import torch
+
+    dev = torch.device("cuda", int(ef.cfgd["device"]))
+    if not isinstance(rgb, torch.Tensor):
+        raise TypeError("rgb must be a torch tensor on the handle's device")
+    if rgb.dtype != torch.uint8:
+        raise TypeError(f"rgb: dtype {rgb.dtype} is not supported (uint8)")
+    if rgb.device != dev:
+        raise ValueError(f"rgb is on {rgb.device}, the handle on {dev}")
+    if rgb.dim() != 3 or rgb.shape[2] != 3 or not rgb.is_contiguous():
+        raise ValueError(f"rgb: shape {tuple(rgb.shape)}, expected a contiguous [H,W,3]")
+    hh, w = int(rgb.shape[0]), int(rgb.shape[1])
+    size, mean3, layout, out, stream = _molded_args(ef, w, hh, min_dim, max_dim, mean, channels_last, out, stream)
+    ef._chk(ef.L.ifx_detector_input_molded_image(ef.handle, C.c_void_p(rgb.data_ptr()), w, hh, int(min_dim), int(max_dim), mean3, layout, C.c_void_p(out.data_ptr()),
+                                                 int(out.numel()), C.c_void_p(stream.cuda_stream or None)), "ifx_detector_input_molded_image")
+    return _molded_result(size, out, w, hh, int(min_dim), int(max_dim))
 
 
 def _ops_tensor(ef, t, name, dtype, what):
@@ -995,6 +1075,69 @@ class ElasticFusion:
             k = int(kept.item())
             return masks[:k], bout[:k], cls[:k], rows[:k]
 
+    # -- the reference's default detector: detections [R,6] and mrcnn_mask to image-sized masks (MaskRCNN.unmold_detections, deps/mask_rcnn/model.py:2285-2344)
+    def _unmold_args(self, detections, mrcnn_mask, window, layout, class_map, stream):
+        """validates the default detector's tensors: (R, M, C, layout flag, window as int32[4], stream)"""
+        import torch
+
+        _ops_tensor(self, detections, "detections", torch.float32, "float32")
+        _ops_tensor(self, mrcnn_mask, "mrcnn_mask", torch.float32, "float32")
+        if layout in ("nhwc", UNMOLD_NHWC):
+            flag = UNMOLD_NHWC
+        elif layout in ("nchw", UNMOLD_NCHW):
+            flag = UNMOLD_NCHW
+        else:
+            raise ValueError(f"layout {layout!r}: 'nhwc' ([R,M,M,C]) or 'nchw' ([R,C,M,M])")
+        sh = tuple(mrcnn_mask.shape)
+        if len(sh) != 4 or (sh[1] != sh[2] if flag == UNMOLD_NHWC else sh[2] != sh[3]):
+            raise ValueError(f"mrcnn_mask: shape {sh}, expected [R,M,M,C] ('nhwc') or [R,C,M,M] ('nchw')")
+        R, M, Cn = (sh[0], sh[1], sh[3]) if flag == UNMOLD_NHWC else (sh[0], sh[2], sh[1])
+        if not (1 <= M <= 64 and 2 <= Cn <= 1024 and R <= 1024):
+            raise ValueError(f"mrcnn_mask: shape {sh}, expected R <= 1024, C in 2 .. 1024, M in 1 .. 64")
+        if tuple(detections.shape) != (R, 6):
+            raise ValueError(f"detections: shape {tuple(detections.shape)}, expected [{R},6]")
+        if class_map is not None:
+            _ops_tensor(self, class_map, "class_map", torch.int32, "int32")
+            if tuple(class_map.shape) != (Cn,):
+                raise ValueError(f"class_map: shape {tuple(class_map.shape)}, expected [{Cn}]")
+        win = np.ascontiguousarray([int(v) for v in window], np.int32)
+        if win.shape != (4,) or win[2] <= win[0] or win[3] <= win[1]:
+            raise ValueError(f"window {tuple(window)}: four integers (y1, x1, y2, x2) with y2 > y1 and x2 > x1")
+        if stream is None:
+            stream = torch.cuda.current_stream(mrcnn_mask.device)
+        return R, M, Cn, flag, win, stream
+
+    def unmold_detections(self, detections, mrcnn_mask, window, out_size, layout="nhwc", class_map=None, padded=False, stream=None):
+        """ifx_unmold_detections, one image: detections [R,6] float32 (y1, x1, y2, x2, class_id, score) in molded-image pixels, mrcnn_mask [R,M,M,C] ('nhwc') or
+        [R,C,M,M] ('nchw') float32, window (y1, x1, y2, x2) of the image in the molded input, out_size = (width, height) ->
+        (masks [k,H,W] uint8 0/1, class_ids [k] int32, boxes [k,4] int32 (y1, x1, y2, x2), scores [k], rows [k] int32) by the rule of include/ifx_c_api.h:
+        MaskRCNN.unmold_detections with utils.unmold_mask.  class_map: an int32 device tensor [C], class id per class.  Everything runs on the device; the 4-byte
+        read of kept is this method's only synchronisation, and padded=True returns the uncut [R] tensors plus kept [1] int32 without it."""
+        import torch
+
+        R, M, Cn, flag, win, stream = self._unmold_args(detections, mrcnn_mask, window, layout, class_map, stream)
+        W, H = int(out_size[0]), int(out_size[1])
+        if W < 1 or H < 1:
+            raise ValueError(f"out_size {tuple(out_size)}: a size < 1")
+        with torch.cuda.stream(stream):
+            dev = mrcnn_mask.device
+            masks = torch.empty((R, H, W), dtype=torch.uint8, device=dev)
+            cls = torch.empty(R, dtype=torch.int32, device=dev)
+            boxes = torch.empty((R, 4), dtype=torch.int32, device=dev)
+            scores = torch.empty(R, dtype=torch.float32, device=dev)
+            rows = torch.empty(R, dtype=torch.int32, device=dev)
+            kept = torch.empty(1, dtype=torch.int32, device=dev)
+        self._chk(self.L.ifx_unmold_detections(self.handle, C.c_void_p(detections.data_ptr() or None), C.c_void_p(mrcnn_mask.data_ptr() or None), _ptr(win),
+                                               None if class_map is None else C.c_void_p(class_map.data_ptr()), R, M, Cn, flag, W, H,
+                                               C.c_void_p(masks.data_ptr() or None), C.c_void_p(cls.data_ptr() or None), C.c_void_p(boxes.data_ptr() or None),
+                                               C.c_void_p(scores.data_ptr() or None), C.c_void_p(rows.data_ptr() or None), C.c_void_p(kept.data_ptr()),
+                                               C.c_void_p(stream.cuda_stream or None)), "ifx_unmold_detections")
+        if padded:
+            return masks, cls, boxes, scores, rows, kept
+        with torch.cuda.stream(stream):
+            k = int(kept.item())
+            return masks[:k], cls[:k], boxes[:k], scores[:k], rows[:k]
+
     # -- frame entry (ElasticFusion::processFrame)
     def set_instance_gt(self, gt):
         """instanceGT of ElasticFusion::processFrame for the frames that follow (H x W uint8, None: off)."""
@@ -1535,6 +1678,42 @@ class InstanceFusion:
         """The deferred call on the mask head's logits: tensors and stream exactly as for process_segmentation_detections; releases the ticket."""
         return self._detections_call("ifx_process_segmentation_deferred_detections", (int(ticket),), mask_logits, boxes, scores, labels, in_size, frame, score_thresh,
                                      class_map, count, isflann, superpixels, threshold, stream)
+
+    # -- the reference's default detector (Keras Mask R-CNN): unmold_detections, the bridge and the votes in one call (include/ifx_c_api.h)
+    def _unmolded_call(self, name, lead, detections, mrcnn_mask, window, frame, layout, class_map, isflann, superpixels, stream):
+        R, M, Cn, flag, win, stream = self.ef._unmold_args(detections, mrcnn_mask, window, layout, class_map, stream)
+        kept = C.c_int32(0)
+        self._seg_call(name, lead, C.c_void_p(detections.data_ptr() or None), C.c_void_p(mrcnn_mask.data_ptr() or None), _ptr(win),
+                       None if class_map is None else C.c_void_p(class_map.data_ptr()), R, M, Cn, flag, int(frame), self._seg_flags(isflann, superpixels),
+                       C.c_void_p(stream.cuda_stream or None), C.byref(kept))
+        return int(kept.value)
+
+    def process_segmentation_unmolded(self, detections, mrcnn_mask, window, frame, class_map=None, isflann=False, superpixels=False, layout="nhwc", stream=None):
+        """ProcessSegmentation on the default detector's raw output on the handle's GPU (ifx_process_segmentation_unmolded): ElasticFusion.unmold_detections at the
+        frame's size, then process_segmentation_device on the masks it keeps -- the reference's MaskRCNN.unmold_detections and bridge (build/mask_ori.py).
+        Tensors and window as for unmold_detections (R <= 256), written on `stream` (default: the current one).  Returns kept."""
+        return self._unmolded_call("ifx_process_segmentation_unmolded", (), detections, mrcnn_mask, window, frame, layout, class_map, isflann, superpixels, stream)
+
+    def process_segmentation_deferred_unmolded(self, ticket, detections, mrcnn_mask, window, frame, class_map=None, isflann=False, superpixels=False, layout="nhwc",
+                                               stream=None):
+        """The deferred call on the default detector's raw output: tensors and stream exactly as for process_segmentation_unmolded; releases the ticket."""
+        return self._unmolded_call("ifx_process_segmentation_deferred_unmolded", (int(ticket),), detections, mrcnn_mask, window, frame, layout, class_map, isflann,
+                                   superpixels, stream)
+
+    def molded_input_size(self, min_dim=800, max_dim=1024):
+        """(nw, nh, S, S, top, left, top + nh, left + nw) of detector_input_molded for this handle's frame size (ifx_molded_input_size: host only)"""
+        return molded_input_size(self.ef.w, self.ef.h, min_dim, max_dim)
+
+    def detector_input_molded(self, ticket=None, min_dim=800, max_dim=1024, mean=MOLD_MEAN_PIXEL, channels_last=True, out=None, stream=None):
+        """ifx_detector_input_molded: what MaskRCNN.mold_inputs (deps/mask_rcnn/model.py:2247-2283) makes of a frame on the CPU -- utils.resize_image's size rule
+        and Pillow resize, the centred zero padding to max_dim x max_dim, the mean subtracted, channels last -- bit for bit, from the frame processed last
+        (ticket=None) or the frame of a snapshot(superpixels=True) ticket, which is NOT released.  stream, out and the enqueue-only protocol as for detector_input.
+        Returns (tensor [1,S,S,3] (channels_last) or [1,3,S,S] float32, window (y1, x1, y2, x2) for the unmold calls, scale)."""
+        ef = self.ef
+        size, mean3, layout, out, stream = _molded_args(ef, ef.w, ef.h, min_dim, max_dim, mean, channels_last, out, stream)
+        ef._chk(self.L.ifx_detector_input_molded(ef.handle, -1 if ticket is None else int(ticket), int(min_dim), int(max_dim), mean3, layout, C.c_void_p(out.data_ptr()),
+                                                 int(out.numel()), C.c_void_p(stream.cuda_stream or None)), "ifx_detector_input_molded")
+        return _molded_result(size, out, ef.w, ef.h, int(min_dim), int(max_dim))
 
     def paste_roi_masks(self, roi_masks, boxes, class_ids, threshold=0.5, stream=None):
         """The ingestion of process_segmentation_rois alone (ifx_paste_roi_masks): (the pasted 0/255 masks [N,H,W] in the bridge's order, the same after the

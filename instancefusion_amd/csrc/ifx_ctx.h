@@ -616,6 +616,11 @@ int ifx_mask_head_check(ifx* h, const char* who, const float* d_logits, const fl
 int ifx_mask_head_stage(ifx* h, const char* who, const float* d_logits, const float* d_boxes, const float* d_scores, const int64_t* d_labels, const int32_t* d_count,
                         const int32_t* d_class_map, int R, int C, int M, const ifx_mask_head_params* p, void* stream, const float** roi_masks, const float** boxes,
                         const int32_t** class_ids, int* kept);
+// ifx_detector.hip: the same pair for ifx_process_segmentation_[deferred_]unmolded -- ifx_unmold_detections' checks, and its stage into the scratch at the
+// handle's frame size followed by the 4-byte read of kept
+int ifx_unmold_check(ifx* h, const char* who, const float* d_det, const float* d_masks, const int32_t* window, int R, int M, int C, int layout, int max_r);
+int ifx_unmold_stage(ifx* h, const char* who, const float* d_det, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M, int C, int layout,
+                     void* stream, const uint8_t** masks_out, const int32_t** class_ids, int* kept);
 int ifx_preprocess(ifx* h);                                   // bilateral + metric
 int ifx_tracker_init_first(ifx* h);
 int ifx_tracker_run_frame(ifx* h, int commit = 1, int keep_last = 0);                            // model pyramid + GN loops (all on device); the frame side is in the slot

@@ -1,10 +1,13 @@
-// ifx_detector.hip -- the detector's side of the library, in five sections:
-//   1. the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input[_image]; described below)
+// ifx_detector.hip -- the detector's side of the library, in six sections:
+//   1. the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input[_image]; described below; the Keras model's
+//      form of it, ifx_detector_input_molded[_image], is the same kernel with another tail)
 //   2. ROIAlign forward and box NMS (ifx_roi_align_forward, ifx_nms)
 //   3. the RPN's proposal stage of one level and the box decoding it contains (ifx_rpn_proposals, ifx_box_decode)
 //   4. the box head's post-processing (ifx_box_detections)
 //   5. the mask head's logits to ROI masks, resized boxes and class ids (ifx_mask_head_select; as a stage of ifx_process_segmentation_detections, ifx_instance.hip)
-// Sections 2 to 5 run on the caller's stream and touch no frame or map state; the three calls with an NMS in them share one block scan (block_excl_scan), one
+//   6. the default (Keras) detector's detections and masks to image-sized masks, boxes and class ids (ifx_unmold_detections; as a stage of
+//      ifx_process_segmentation_unmolded, ifx_instance.hip)
+// Sections 2 to 6 run on the caller's stream and touch no frame or map state; the three calls with an NMS in them share one block scan (block_excl_scan), one
 // walk state (NmsWalk), one device-count mask kernel (k_nms_mask_dev) and the handle's one scratch buffer, carved by one Carver (ops_scratch).
 //
 //   ifx_detector_input[_image]  <-  COCODemo.build_transform       deps/maskrcnn-benchmark-master/demo/predictor.py:132-160
@@ -35,6 +38,8 @@ struct DetArgs {                                      // by value: every word ar
     const int32_t *fx, *cx, *kx, *fy, *cy, *ky;       // first / count / coeff[.][ksx|ksy] of the two axes (an axis that keeps its size: the identity, ks = 1)
     int w, h, ow, oh, Wp, Hp, ksx, ksy, flags;
     float mean[3], stdv[3];
+    int left, top, tx0, ty0, nhwc;                    // MOLD only: the window's corner in the S x S output (Wp = Hp = S), the tiles in front of it, the layout
+    double meand[3];                                  // MOLD only: MEAN_PIXEL
 };
 
 // Phase 1: the source rows under the tile, first[y0] .. first[y1] + count[y1], resampled horizontally for the tile's 64 columns into LDS as bytes (copied when the
@@ -46,15 +51,18 @@ struct DetArgs {                                      // by value: every word ar
 // 2^21 + sum v * k <= 2^21 + 255 * (2^22 + 9) < 2^31: 32-bit unsigned accumulators are exact (17 x 255 x 2^22 as a bound would not fit).
 // VEC: a lane owns four consecutive x of one row and stores 16 bytes per channel (W' a multiple of 4 and an aligned pointer: chosen by the host as for
 // k_mask_area's 16-B words); otherwise consecutive lanes sit on consecutive x and store 4 bytes each.
-template <bool VEC>
+// MOLD (ifx_detector_input_molded[_image]; mold_inputs, deps/mask_rcnn/model.py:2247-2283): the same two phases on tiles of the RESIZED image that start tx0, ty0
+// in front of it (multiples of the tile, so that no tile straddles the window's corner), another tail: the byte minus an f64 mean, rounded once, stored at
+// (top + y, left + x) of the S x S output, f32(-mean) everywhere else, channels last or planar; consecutive lanes on consecutive x, never VEC.
+template <bool VEC, bool MOLD = false>
 __global__ void __launch_bounds__(256) k_detector_input(const DetArgs a)
 {
     __shared__ int s_kx[DI_TX * DI_K], s_ky[DI_TY * DI_K];
     __shared__ int s_fx[DI_TX], s_cx[DI_TX], s_fy[DI_TY], s_cy[DI_TY];
     __shared__ uint8_t s_rows[DI_ROWS * 3 * DI_TX];
-    const int t = threadIdx.x, x0 = blockIdx.x * DI_TX, y0 = blockIdx.y * DI_TY;
+    const int t = threadIdx.x, x0 = blockIdx.x * DI_TX - (MOLD ? a.tx0 : 0), y0 = blockIdx.y * DI_TY - (MOLD ? a.ty0 : 0);
     const int nx = min(DI_TX, a.ow - x0), ny = min(DI_TY, a.oh - y0);   // the tile's share of the resized image (<= 0: wholly in the padding)
-    const bool image = nx > 0 && ny > 0;
+    const bool image = nx > 0 && ny > 0 && (!MOLD || (x0 >= 0 && y0 >= 0));
     int r0 = 0;
     if (image) {
         for (int i = t; i < nx * a.ksx; i += 256) { const int col = i / a.ksx, k = i - col * a.ksx; s_kx[col * DI_K + k] = a.kx[(size_t)(x0 + col) * a.ksx + k]; }
@@ -86,6 +94,33 @@ __global__ void __launch_bounds__(256) k_detector_input(const DetArgs a)
             }
         }
         __syncthreads();
+    }
+    if constexpr (MOLD) {
+        const int xl = t & 63, ox = x0 + xl + a.left;
+        if (ox < 0 || ox >= a.Wp) return;
+        const size_t plane = (size_t)a.Hp * a.Wp;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int yl = (t >> 6) + 4 * i, oy = y0 + yl + a.top;
+            if (oy < 0 || oy >= a.Hp) continue;
+            double b[3] = {0.0, 0.0, 0.0};            // the padding: byte 0 before the mean is subtracted
+            if (image && xl < nx && yl < ny) {
+                const int fy = s_fy[yl] - r0, n = s_cy[yl];
+                uint32_t q[3] = {DI_HALF, DI_HALF, DI_HALF};
+                for (int k = 0; k < n; k++) {
+                    const uint32_t kk = (uint32_t)s_ky[yl * DI_K + k];
+                    const int row = min(fy + k, DI_ROWS - 1);
+#pragma unroll
+                    for (int c = 0; c < 3; c++) q[c] += s_rows[(row * 3 + c) * DI_TX + xl] * kk;
+                }
+#pragma unroll
+                for (int c = 0; c < 3; c++) b[c] = (double)min(q[c] >> ifx_detprep::PRECISION_BITS, 255u);
+            }
+            const size_t px = (size_t)oy * a.Wp + ox;
+#pragma unroll
+            for (int c = 0; c < 3; c++) a.out[a.nhwc ? px * 3 + c : c * plane + px] = (float)(b[c] - a.meand[c]);
+        }
+        return;
     }
     const bool swap = a.flags & IFX_DET_SWAP_RB, s255 = a.flags & IFX_DET_SCALE_255;
     float v[3][4];
@@ -201,7 +236,9 @@ int det_check(ifx* h, const char* who, int w, int hh, const ifx_detector_prep* p
 }
 
 // everything behind the checks.  ev_src: what the source image waits for (a ticket's snapshot), slot: the frame slot whose next copy-in is held off behind the read
-int det_run(ifx* h, const uint8_t* d_rgb, int w, int hh, const ifx_detector_prep* p, const int32_t* sz, float* d_out, void* stream, hipEvent_t ev_src, FrameSlot* slot)
+struct MoldSpec { int left, top, nhwc; double mean[3]; };   // the molded form (p is NULL then): sz = nw, nh, S, S
+int det_run(ifx* h, const uint8_t* d_rgb, int w, int hh, const ifx_detector_prep* p, const int32_t* sz, float* d_out, void* stream, hipEvent_t ev_src, FrameSlot* slot,
+            const MoldSpec* mold = nullptr)
 {
     if (!h->det_prep) h->det_prep = new DetPrep();
     DetPrep* dp = (DetPrep*)h->det_prep;
@@ -221,11 +258,18 @@ int det_run(ifx* h, const uint8_t* d_rgb, int w, int hh, const ifx_detector_prep
     a.src = d_rgb; a.out = d_out;
     a.fx = t->dev; a.cx = a.fx + sz[0]; a.kx = a.cx + sz[0];
     a.fy = t->dev + t->off_y; a.cy = a.fy + sz[1]; a.ky = a.cy + sz[1];
-    a.w = w; a.h = hh; a.ow = sz[0]; a.oh = sz[1]; a.Wp = sz[2]; a.Hp = sz[3]; a.ksx = t->ksx; a.ksy = t->ksy; a.flags = p->flags;
-    for (int c = 0; c < 3; c++) { a.mean[c] = p->mean[c]; a.stdv[c] = p->std[c]; }
-    const dim3 grid((unsigned)cdiv(a.Wp, DI_TX), (unsigned)cdiv(a.Hp, DI_TY));
-    if (a.Wp % 4 == 0 && (uintptr_t)d_out % 16 == 0) LAUNCH(h, "detector_input", grid, dim3(256), k_detector_input<true>, a);
-    else LAUNCH(h, "detector_input", grid, dim3(256), k_detector_input<false>, a);
+    a.w = w; a.h = hh; a.ow = sz[0]; a.oh = sz[1]; a.Wp = sz[2]; a.Hp = sz[3]; a.ksx = t->ksx; a.ksy = t->ksy; a.flags = p ? p->flags : 0;
+    for (int c = 0; c < 3; c++) { a.mean[c] = p ? p->mean[c] : 0.f; a.stdv[c] = p ? p->std[c] : 1.f; a.meand[c] = mold ? mold->mean[c] : 0.0; }
+    a.left = mold ? mold->left : 0; a.top = mold ? mold->top : 0; a.nhwc = mold ? mold->nhwc : 0;
+    a.tx0 = cdiv(a.left, DI_TX) * DI_TX; a.ty0 = cdiv(a.top, DI_TY) * DI_TY;
+    if (mold) {   // tiles of the resized image's grid from (-tx0, -ty0) to the output's far edges at (S - left, S - top)
+        const dim3 grid((unsigned)cdiv(a.Wp - a.left + a.tx0, DI_TX), (unsigned)cdiv(a.Hp - a.top + a.ty0, DI_TY));
+        LAUNCH(h, "detector_input_molded", grid, dim3(256), (k_detector_input<false, true>), a);
+    } else {
+        const dim3 grid((unsigned)cdiv(a.Wp, DI_TX), (unsigned)cdiv(a.Hp, DI_TY));
+        if (a.Wp % 4 == 0 && (uintptr_t)d_out % 16 == 0) LAUNCH(h, "detector_input", grid, dim3(256), k_detector_input<true>, a);
+        else LAUNCH(h, "detector_input", grid, dim3(256), k_detector_input<false>, a);
+    }
     if (slot) {   // the side stream reuses the slot two frames on and waits only for the FRAME that used it: it is told about this reader as about a snapshot's copy
         if (!slot->snap_read) HIPCHK(h, hipEventCreateWithFlags(&slot->snap_read, hipEventDisableTiming));
         HIPCHK(h, hipEventRecord(slot->snap_read, h->cur));
@@ -1301,6 +1345,221 @@ __global__ void __launch_bounds__(256) k_mh_sigmoid(const MhArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The reference's default detector: detections [R,6] and mrcnn_mask to image-sized 0 / 1 masks, boxes and class ids: ifx_unmold_detections
+// (MaskRCNN.unmold_detections, deps/mask_rcnn/model.py:2285-2344; utils.unmold_mask, deps/mask_rcnn/utils.py:490-507, behind scipy.misc.imresize; the rule in full:
+// include/ifx_c_api.h, in numpy: tests/unmold_numpy.py).  Two launches around one memset; the number of kept rows stays on the device.
+constexpr int UM_TX = 64;                     // the columns of the frame a paste block owns
+constexpr int UM_KS = MH_MAX_M + 1;           // the stride of a tap row in LDS: first >= 0 and first + count <= M, so at most M <= 64 taps reach a sample
+constexpr double UM_LIMIT = 16777216.0;       // +-2^24: a coordinate beyond it has no defined box
+
+struct UmArgs {
+    const float *det, *masks;                         // [R][6]; [R][M][M][C] or (nchw) [R][C][M][M]
+    const int32_t* class_map;                         // [C] or NULL
+    int R, M, C, nchw, W, H, wy1, wx1;
+    double scale;
+    uint8_t* out;                                     // [R][H * W]
+    int32_t *class_ids, *boxes, *rows, *kept;         // [R], [R][4], [R] or NULL, one
+    float* scores;                                    // [R] or NULL
+};
+
+// Steps 2, 3 and the row's share of step 8, the ONE statement of them for the select block and for the paste blocks.
+struct UmRow { int y1, x1, y2, x2, c; bool survives, defined, valid; };
+__device__ __forceinline__ UmRow um_row(const UmArgs& a, int r)
+{
+    const float* d = a.det + 6 * (size_t)r;
+    double v[4];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float x = d[k];
+        v[k] = ((double)x - (double)((k & 1) ? a.wx1 : a.wy1)) * a.scale;
+        ok = ok && fabsf(x) <= (float)UM_LIMIT && fabs(v[k]) <= UM_LIMIT;     // (a NaN or an infinity compares false)
+    }
+    UmRow o;
+    o.y1 = o.x1 = o.y2 = o.x2 = 0; o.survives = true; o.defined = false;
+    if (ok) {
+        o.y1 = (int)v[0]; o.x1 = (int)v[1]; o.y2 = (int)v[2]; o.x2 = (int)v[3];                 // toward zero, as astype(int32)
+        o.survives = (long long)(o.y2 - o.y1) * (long long)(o.x2 - o.x1) > 0;
+        o.defined = 0 <= o.y1 && o.y1 < o.y2 && o.y2 <= a.H && 0 <= o.x1 && o.x1 < o.x2 && o.x2 <= a.W;
+    }
+    const float cid = d[4];
+    o.valid = cid >= 1.f && cid < (float)a.C;                                                   // (a NaN compares false)
+    o.c = o.valid ? (int)cid : 0;
+    o.defined = o.defined && o.valid;
+    return o;
+}
+
+// One block, thread t on input row t: step 1 through an LDS minimum, steps 2 and 3, the block scan -- its total is `kept`, its exclusive sum the row's place (a
+// stable compaction) -- and the scatter of the record; threads kept .. R - 1 write the padding.
+__global__ void __launch_bounds__(1024) k_unmold_select(const UmArgs a)
+{
+    __shared__ int s_w[16];
+    __shared__ int s_n;
+    const int t = threadIdx.x;
+    if (t == 0) s_n = a.R;
+    __syncthreads();
+    if (t < a.R && a.det[6 * (size_t)t + 4] == 0.f) atomicMin(&s_n, t);
+    __syncthreads();
+    UmRow row;
+    bool keep = false;
+    if (t < s_n) { row = um_row(a, t); keep = row.survives; }
+    int kept;
+    const int pos = block_excl_scan<16, int>(keep ? 1 : 0, s_w, &kept);
+    if (keep) {
+        int32_t* b = a.boxes + 4 * (size_t)pos;
+        b[0] = row.y1; b[1] = row.x1; b[2] = row.y2; b[3] = row.x2;
+        a.class_ids[pos] = row.valid ? (a.class_map ? a.class_map[row.c] : row.c) : 0;
+        if (a.scores) a.scores[pos] = a.det[6 * (size_t)t + 5];
+        if (a.rows) a.rows[pos] = t;
+    }
+    if (t >= kept && t < a.R) {
+        int32_t* b = a.boxes + 4 * (size_t)t;
+        b[0] = 0; b[1] = 0; b[2] = 0; b[3] = 0;
+        a.class_ids[t] = -1;
+        if (a.scores) a.scores[t] = 0.f;
+        if (a.rows) a.rows[t] = -1;
+    }
+    if (t == 0) a.kept[0] = kept;
+}
+
+// Pillow's taps of output sample xx of one axis (precompute_coeffs / normalize_coeffs_8bpc, the bilinear filter): ifx_detprep::resize_taps' arithmetic, statement
+// for statement, in f64 -- true divisions, no reciprocal instruction, nothing fused; the weights are summed in index order and made a second time for the division
+// instead of being kept.  k: count <= in <= 64 taps.
+__device__ void um_taps(int in, int out, int xx, int* k, int* first, int* count)
+{
+    const double scale = (double)in / (double)out;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = fs, ss = 1.0 / fs;
+    const double center = ((double)xx + 0.5) * scale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in) xmax = in;
+    const int n = min(max(xmax - xmin, 0), in);
+    double ww = 0.0;
+    for (int x = 0; x < n; x++) {
+        double w = ((double)(x + xmin) - center + 0.5) * ss;
+        if (w < 0.0) w = -w;
+        ww += w < 1.0 ? 1.0 - w : 0.0;
+    }
+    for (int x = 0; x < n; x++) {
+        double w = ((double)(x + xmin) - center + 0.5) * ss;
+        if (w < 0.0) w = -w;
+        w = w < 1.0 ? 1.0 - w : 0.0;
+        const double v = (ww != 0.0 ? w / ww : w) * (double)(1 << ifx_detprep::PRECISION_BITS);
+        k[x] = v < 0.0 ? (int)(-0.5 + v) : (int)(0.5 + v);
+    }
+    *first = min(xmin, in - n);
+    *count = n;
+}
+
+// Block (bx, k): the 64 columns of the frame from 64 bx on, output row k.  Thread t owns input rows 4t .. 4t + 3 in the scan that finds the k-th surviving row
+// (k_unmold_select's count, test and scan); the block leaves when k >= kept, when the paste is not defined (step 8) or when the box misses its columns -- every
+// one of these is the same for all its threads, and no barrier follows a return that is not.  Then: min / max of the row's channel (shuffles, four wave results
+// in LDS), the M^2 bytes of step 4, the horizontal taps (thread c < 64 those of column c), the horizontal pass into s_mid [M][64] bytes, and per chunk of 64
+// box rows the vertical taps (thread j < 64 those of row j) and the vertical pass: lane = column, a wave's rows four apart, consecutive lanes storing
+// consecutive x.  An axis that keeps the size M gets the tap (2^22), the same bytes.  Sums: every weight is >= 0 and a sample's taps add up to 2^22 give or take
+// half a unit per tap: 2^21 + 255 * (2^22 + 32) < 2^31, exact in 32-bit unsigned accumulators (k_detector_input's bound).
+// Bounds: a pixel is stored only for a defined paste, 0 <= y1 < y2 <= H and 0 <= x1 < x2 <= W, at y1 + j < y2 and x1 <= x < x2; LDS reads stay below first + count <= M.
+__global__ void __launch_bounds__(256) k_unmold_paste(const UmArgs a)
+{
+    __shared__ int s_w[4];
+    __shared__ int s_n, s_src, s_bad;
+    __shared__ float s_mn[4], s_mx[4];
+    __shared__ int s_kx[UM_TX * UM_KS], s_ky[UM_TX * UM_KS];
+    __shared__ int s_fx[UM_TX], s_cx[UM_TX], s_fy[UM_TX], s_cy[UM_TX];
+    __shared__ uint8_t s_byte[MH_MAX_M * MH_MAX_M], s_mid[MH_MAX_M * UM_TX];
+    const int t = threadIdx.x, k = blockIdx.y, x0 = blockIdx.x * UM_TX;
+    if (t == 0) { s_n = a.R; s_src = -1; s_bad = 0; }
+    __syncthreads();
+    for (int i = 0; i < 4; i++) {
+        const int r = 4 * t + i;
+        if (r < a.R && a.det[6 * (size_t)r + 4] == 0.f) { atomicMin(&s_n, r); break; }
+    }
+    __syncthreads();
+    const int N = s_n;
+    bool kp[4];
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int r = 4 * t + i;
+        kp[i] = r < N && um_row(a, r).survives;
+        cnt += kp[i] ? 1 : 0;
+    }
+    int kept;
+    int pos = block_excl_scan<4, int>(cnt, s_w, &kept);
+    if (k >= kept) return;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (kp[i]) { if (pos == k) s_src = 4 * t + i; pos++; }
+    __syncthreads();
+    const int src = s_src;
+    if (src < 0 || src >= a.R) return;
+    const UmRow row = um_row(a, src);
+    const int xa = max(row.x1, x0), xb = min(row.x2, x0 + UM_TX);
+    if (!row.defined || xa >= xb) return;
+
+    const int M = a.M, MM = M * M;
+    const float* ch = a.nchw ? a.masks + ((size_t)src * a.C + row.c) * MM : a.masks + (size_t)src * MM * a.C + row.c;
+    const size_t step = a.nchw ? 1 : (size_t)a.C;
+    float mn = INFINITY, mx = -INFINITY;
+    bool bad = false;
+    for (int i = t; i < MM; i += 256) {
+        const float v = ch[i * step];
+        bad = bad || !(fabsf(v) <= 3.402823466e+38f);
+        mn = fminf(mn, v); mx = fmaxf(mx, v);
+    }
+    for (int d = 32; d >= 1; d >>= 1) { mn = fminf(mn, __shfl_xor(mn, d)); mx = fmaxf(mx, __shfl_xor(mx, d)); }
+    if ((t & 63) == 0) { s_mn[t >> 6] = mn; s_mx[t >> 6] = mx; }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    const float cmin = fminf(fminf(s_mn[0], s_mn[1]), fminf(s_mn[2], s_mn[3])), cmax = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+    float cs = cmax - cmin;
+    if (cs == 0.f) cs = 1.f;
+    const float s = (float)(255.0 / (double)cs);
+    if (s_bad || !(fabsf(cs) <= 3.402823466e+38f) || !(fabsf(s) <= 3.402823466e+38f)) return;
+    for (int i = t; i < MM; i += 256) {
+        const float d = ch[i * step] - cmin;
+        const float q = fminf(fmaxf(d * s, 0.f), 255.f) + 0.5f;
+        s_byte[i] = (uint8_t)(int)q;
+    }
+    const int bw = row.x2 - row.x1, bh = row.y2 - row.y1;
+    if (t < UM_TX) {
+        const int x = x0 + t;
+        s_cx[t] = 0;
+        if (x >= xa && x < xb) {
+            if (bw == M) { s_fx[t] = x - row.x1; s_cx[t] = 1; s_kx[t * UM_KS] = 1 << ifx_detprep::PRECISION_BITS; }
+            else um_taps(M, bw, x - row.x1, s_kx + t * UM_KS, &s_fx[t], &s_cx[t]);
+        }
+    }
+    __syncthreads();
+    const int col = t & 63, nxc = s_cx[col], fxc = s_fx[col];
+    if (nxc > 0)
+        for (int y = t >> 6; y < M; y += 4) {
+            uint32_t q = DI_HALF;
+            for (int i = 0; i < nxc; i++) q += s_byte[y * M + fxc + i] * (uint32_t)s_kx[col * UM_KS + i];
+            s_mid[y * UM_TX + col] = (uint8_t)min(q >> ifx_detprep::PRECISION_BITS, 255u);
+        }
+    uint8_t* out = a.out + (size_t)k * a.H * a.W;
+    for (int j0 = 0; j0 < bh; j0 += UM_TX) {
+        __syncthreads();                                             // s_mid is complete; the previous chunk's readers are done with s_ky
+        if (t < UM_TX && j0 + t < bh) {
+            if (bh == M) { s_fy[t] = j0 + t; s_cy[t] = 1; s_ky[t * UM_KS] = 1 << ifx_detprep::PRECISION_BITS; }
+            else um_taps(M, bh, j0 + t, s_ky + t * UM_KS, &s_fy[t], &s_cy[t]);
+        }
+        __syncthreads();
+        const int nj = min(UM_TX, bh - j0);
+        if (nxc > 0)
+            for (int j = t >> 6; j < nj; j += 4) {
+                const int f = s_fy[j], n = s_cy[j];
+                uint32_t q = DI_HALF;
+                for (int i = 0; i < n; i++) q += s_mid[(f + i) * UM_TX + col] * (uint32_t)s_ky[j * UM_KS + i];
+                out[(size_t)(row.y1 + j0 + j) * a.W + x0 + col] = (q >> ifx_detprep::PRECISION_BITS) >= 128u ? 1 : 0;
+            }
+    }
+}
+
 // the stream the LAUNCH macro and the kernel timing use, for the length of a call on the caller's stream
 struct StreamScope {
     ifx* h; hipStream_t old;
@@ -1552,6 +1811,22 @@ int mh_launch(ifx* h, const float* d_logits, const float* d_boxes, const float* 
     StreamScope scope(h, stream);
     LAUNCH(h, "mh_select", dim3(1), dim3(1024), k_mh_select, a);
     LAUNCH(h, "mh_sigmoid", dim3((unsigned)R), dim3(256), k_mh_sigmoid, a);
+    return IFX_OK;
+}
+
+// ifx_unmold_detections' select, memset and paste on `stream` (R >= 1, the arguments checked; the outputs are the caller's or the handle's scratch).
+int um_launch(ifx* h, const float* d_det, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M, int C, int layout, int W, int H,
+              uint8_t* d_out, int32_t* d_class_ids, int32_t* d_boxes, float* d_scores, int32_t* d_rows, int32_t* d_kept, hipStream_t stream)
+{
+    UmArgs a;
+    a.det = d_det; a.masks = d_masks; a.class_map = d_class_map;
+    a.R = R; a.M = M; a.C = C; a.nchw = layout == IFX_UNMOLD_NCHW; a.W = W; a.H = H; a.wy1 = window[0]; a.wx1 = window[1];
+    a.scale = std::min((double)H / (double)((int64_t)window[2] - window[0]), (double)W / (double)((int64_t)window[3] - window[1]));   // model.py:2314-2316
+    a.out = d_out; a.class_ids = d_class_ids; a.boxes = d_boxes; a.rows = d_rows; a.kept = d_kept; a.scores = d_scores;
+    StreamScope scope(h, stream);
+    LAUNCH(h, "unmold_select", dim3(1), dim3(1024), k_unmold_select, a);
+    HIPCHK(h, hipMemsetAsync(d_out, 0, (size_t)R * H * W, stream));
+    LAUNCH(h, "unmold_paste", dim3((unsigned)cdiv(W, UM_TX), (unsigned)R), dim3(256), k_unmold_paste, a);
     return IFX_OK;
 }
 
@@ -1886,4 +2161,102 @@ int ifx_mask_head_stage(ifx* h, const char* who, const float* d_logits, const fl
     HIPCHK(h, hipStreamSynchronize(s));
     *roi_masks = masks; *boxes = bout; *class_ids = cls; *kept = n;
     return IFX_OK;
+}
+
+// the argument checks the three unmold entries share; they touch nothing (max_r: 1024 for the stage, 256 for the process entries, whose scratch is R x P bytes)
+int ifx_unmold_check(ifx* h, const char* who, const float* d_det, const float* d_masks, const int32_t* window, int R, int M, int C, int layout, int max_r)
+{
+    if (M < 1 || M > MH_MAX_M || C < 2 || C > MH_MAX_C || R < 0 || R > max_r) {
+        h->err = std::string(who) + ": M outside 1 .. 64, C outside 2 .. 1024 or R outside 0 .. " + std::to_string(max_r); return IFX_E_INVALID;
+    }
+    if (layout != IFX_UNMOLD_NHWC && layout != IFX_UNMOLD_NCHW) { h->err = std::string(who) + ": unknown layout"; return IFX_E_INVALID; }
+    if (!window) { h->err = std::string(who) + ": NULL window"; return IFX_E_INVALID; }
+    if (window[2] <= window[0] || window[3] <= window[1]) { h->err = std::string(who) + ": the window is empty (wy2 <= wy1 or wx2 <= wx1)"; return IFX_E_INVALID; }
+    if (R > 0 && (!d_det || !d_masks)) { h->err = std::string(who) + ": NULL pointer"; return IFX_E_INVALID; }
+    return IFX_OK;
+}
+
+extern "C" int ifx_unmold_detections(ifx_t* h, const float* d_detections, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M, int C,
+                                     int layout, int width, int height, uint8_t* d_masks_out, int32_t* d_class_ids, int32_t* d_boxes_out, float* d_scores_out,
+                                     int32_t* d_rows, int32_t* d_kept, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    int r = ifx_unmold_check(h, "ifx_unmold_detections", d_detections, d_masks, window, R, M, C, layout, MH_MAX_R);
+    if (r) return r;
+    if (width < 1 || height < 1) { h->err = "ifx_unmold_detections: width or height < 1"; return IFX_E_INVALID; }
+    if (!d_kept || (R > 0 && (!d_masks_out || !d_class_ids || !d_boxes_out))) { h->err = "ifx_unmold_detections: NULL pointer"; return IFX_E_INVALID; }
+    if (R == 0) { HIPCHK(h, hipMemsetAsync(d_kept, 0, 4, (hipStream_t)stream)); return IFX_OK; }
+    return um_launch(h, d_detections, d_masks, window, d_class_map, R, M, C, layout, width, height, d_masks_out, d_class_ids, d_boxes_out, d_scores_out, d_rows, d_kept,
+                     (hipStream_t)stream);
+}
+
+// The stage of ifx_process_segmentation_[deferred_]unmolded (ifx_instance.hip): into the detector operators' scratch on the producer's stream at the handle's frame
+// size, then the one 4-byte read of kept.  The pointers stay good until the next detector operator on this handle, as ifx_mask_head_stage's do.
+int ifx_unmold_stage(ifx* h, const char* who, const float* d_det, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M, int C, int layout,
+                     void* stream, const uint8_t** masks_out, const int32_t** class_ids, int* kept)
+{
+    *masks_out = nullptr; *class_ids = nullptr; *kept = 0;
+    if (R == 0) return IFX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* masks; int32_t *cls, *boxes, *dkept;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, who, [&](Carver& c) {
+        masks = c.take<uint8_t>((size_t)R * h->P);
+        cls = c.take<int32_t>(R);
+        boxes = c.take<int32_t>(4 * (size_t)R);
+        dkept = c.take<int32_t>(4);                    // kept (and padding)
+    }, s, &ops);
+    if (r) return r;
+    if ((r = um_launch(h, d_det, d_masks, window, d_class_map, R, M, C, layout, h->w, h->h, masks, cls, boxes, nullptr, nullptr, dkept, s))) return r;
+    if ((r = ops_done(h, ops, s))) return r;
+    int32_t n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, dkept, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    *masks_out = masks; *class_ids = cls; *kept = n;
+    return IFX_OK;
+}
+
+extern "C" int ifx_molded_input_size(int width, int height, int min_dim, int max_dim, int32_t* out8)
+{
+    return ifx_detprep::molded_input_size(width, height, min_dim, max_dim, out8) ? IFX_E_INVALID : IFX_OK;
+}
+
+// the argument checks the two molded entries share; sz8: ifx_molded_input_size's
+static int mold_check(ifx* h, const char* who, int w, int hh, int min_dim, int max_dim, const double* mean, int layout, const float* d_out, int64_t out_floats,
+                      int32_t* sz8, MoldSpec* m)
+{
+    if (!mean || !d_out) { h->err = std::string(who) + ": NULL pointer"; return IFX_E_INVALID; }
+    if (layout != IFX_MOLD_NHWC && layout != IFX_MOLD_NCHW) { h->err = std::string(who) + ": unknown layout"; return IFX_E_INVALID; }
+    const char* bad = ifx_detprep::molded_input_size(w, hh, min_dim, max_dim, sz8);
+    if (bad) { h->err = std::string(who) + ": " + bad; return IFX_E_INVALID; }
+    if (out_floats < (int64_t)3 * sz8[2] * sz8[3]) { h->err = std::string(who) + ": out_floats < 3 * S * S"; return IFX_E_INVALID; }
+    m->left = sz8[5]; m->top = sz8[4]; m->nhwc = layout == IFX_MOLD_NHWC;
+    for (int c = 0; c < 3; c++) m->mean[c] = mean[c];
+    return IFX_OK;
+}
+
+extern "C" int ifx_detector_input_molded_image(ifx_t* h, const uint8_t* d_rgb, int width, int height, int min_dim, int max_dim, const double* mean, int layout,
+                                               float* d_out, int64_t out_floats, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!d_rgb) { h->err = "ifx_detector_input_molded_image: NULL pointer"; return IFX_E_INVALID; }
+    int32_t sz[8];
+    MoldSpec m;
+    int r = mold_check(h, "ifx_detector_input_molded_image", width, height, min_dim, max_dim, mean, layout, d_out, out_floats, sz, &m);
+    if (r) return r;
+    return det_run(h, d_rgb, width, height, nullptr, sz, d_out, stream, nullptr, nullptr, &m);
+}
+
+extern "C" int ifx_detector_input_molded(ifx_t* h, int ticket, int min_dim, int max_dim, const double* mean, int layout, float* d_out, int64_t out_floats, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    int32_t sz[8];
+    MoldSpec m;
+    int r = mold_check(h, "ifx_detector_input_molded", h->w, h->h, min_dim, max_dim, mean, layout, d_out, out_floats, sz, &m);
+    if (r) return r;
+    const uint8_t* rgb = nullptr;
+    hipEvent_t ev = nullptr;
+    FrameSlot* slot = nullptr;
+    if ((r = ifx_frame_for_reader(h, "ifx_detector_input_molded", ticket, &rgb, &ev, &slot))) return r;
+    return det_run(h, rgb, h->w, h->h, nullptr, sz, d_out, stream, ev, slot, &m);
 }

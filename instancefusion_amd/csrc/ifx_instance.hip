@@ -1592,6 +1592,23 @@ static int seg_entry_detections(ifx* h, const char* who, const int* ticket, cons
     MaskSource s = src_rois(rois, M, boxes, threshold, cls, kept);
     return seg_run(h, who, s, snap, ticket, frame, flags, stream);   // (the event: the stage, and what the producer enqueued before this call)
 }
+// The default detector's output (ifx_unmold_detections' inputs): behind the checks, the stage runs into the handle's scratch on the producer's stream, kept comes
+// back, and the image form's path takes the scratch pointers as u8 masks -- seg_ingest_launch, k_mask_area, k_mask_order and the gather as they are.
+static int seg_entry_unmolded(ifx* h, const char* who, const int* ticket, const float* d_det, const float* d_masks, const int32_t* window, const int32_t* d_class_map,
+                              int R, int M, int C, int layout, int frame, int flags, void* stream, int32_t* out_kept)
+{
+    if (!h) return IFX_E_INVALID;
+    SegSnap* snap = nullptr;
+    int r = ifx_unmold_check(h, who, d_det, d_masks, window, R, M, C, layout, 256);
+    if (r || (r = seg_refuse_mode(h, who, true, ticket, flags, &snap))) return r;
+    const uint8_t* masks = nullptr;
+    const int32_t* cls = nullptr;
+    int kept = 0;
+    if ((r = ifx_unmold_stage(h, who, d_det, d_masks, window, d_class_map, R, M, C, layout, stream, &masks, &cls, &kept))) return r;
+    if (out_kept) *out_kept = kept;
+    MaskSource s = src_image(masks, IFX_MASK_U8, 0.5f, cls, kept);
+    return seg_run(h, who, s, snap, ticket, frame, flags, stream);   // (the event: the stage, and what the producer enqueued before this call)
+}
 
 extern "C" int ifx_process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
 {
@@ -1633,6 +1650,18 @@ extern "C" int ifx_process_segmentation_deferred_detections(ifx_t* h, int ticket
 {
     return seg_entry_detections(h, "ifx_process_segmentation_deferred_detections", &ticket, d_mask_logits, d_boxes, d_scores, d_labels, d_count, d_class_map, R, C, M, p, threshold, frame,
                                 flags, stream, out_kept);
+}
+extern "C" int ifx_process_segmentation_unmolded(ifx_t* h, const float* d_detections, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M,
+                                                 int C, int layout, int frame, int flags, void* stream, int32_t* out_kept)
+{
+    return seg_entry_unmolded(h, "ifx_process_segmentation_unmolded", nullptr, d_detections, d_masks, window, d_class_map, R, M, C, layout, frame, flags, stream, out_kept);
+}
+extern "C" int ifx_process_segmentation_deferred_unmolded(ifx_t* h, int ticket, const float* d_detections, const float* d_masks, const int32_t* window,
+                                                          const int32_t* d_class_map, int R, int M, int C, int layout, int frame, int flags, void* stream,
+                                                          int32_t* out_kept)
+{
+    return seg_entry_unmolded(h, "ifx_process_segmentation_deferred_unmolded", &ticket, d_detections, d_masks, window, d_class_map, R, M, C, layout, frame, flags, stream,
+                              out_kept);
 }
 extern "C" int ifx_paste_roi_masks(ifx_t* h, const float* d_roi_masks, int roi_size, const float* d_boxes, float threshold, const int32_t* d_class_ids, int n, void* stream, uint8_t* out_ori,
                                    uint8_t* out_clean, int32_t* out_order, int32_t* out_class_ids)

@@ -59,6 +59,27 @@ inline const char* input_size(int w, int h, const ifx_detector_prep* p, int32_t*
     return nullptr;
 }
 
+// ifx_molded_input_size: utils.resize_image (deps/mask_rcnn/utils.py:384-432) with padding, Python semantics in f64.  out8 = nw, nh, S, S, top, left, top + nh,
+// left + nw.  nullptr on success.
+inline const char* molded_input_size(int w, int h, int min_dim, int max_dim, int32_t* out8)
+{
+    if (!out8) return "NULL output";
+    if (w < 1 || h < 1) return "width or height < 1";
+    if (max_dim < 1) return "max_dim < 1";
+    const double mn = (double)(w < h ? w : h), mx = (double)(w < h ? h : w);
+    double s = 1.0;
+    if (min_dim > 0) { s = (double)min_dim / mn; if (s < 1.0) s = 1.0; }                      // scale up but not down
+    if (std::nearbyint(mx * s) > (double)max_dim) s = (double)max_dim / mx;                   // (default rounding mode: half to even, as Python 3's round)
+    double nh = (double)h, nw = (double)w;
+    if (s != 1.0) { nh = std::nearbyint((double)h * s); nw = std::nearbyint((double)w * s); }
+    const double S = (double)max_dim;
+    if (!(nh >= 1.0 && nh <= S && nw >= 1.0 && nw <= S)) return "the resized image is empty or larger than max_dim";
+    if ((double)h / nh > (double)MAX_SCALE || (double)w / nw > (double)MAX_SCALE) return "the output is smaller than an eighth of the frame (resize scale above 8)";
+    const int32_t ih = (int32_t)nh, iw = (int32_t)nw, top = (max_dim - ih) / 2, left = (max_dim - iw) / 2;   // (both differences >= 0: floor division)
+    out8[0] = iw; out8[1] = ih; out8[2] = max_dim; out8[3] = max_dim; out8[4] = top; out8[5] = left; out8[6] = top + ih; out8[7] = left + iw;
+    return nullptr;
+}
+
 inline int resize_ksize(int in_size, int out_size)
 {
     const double scale = (double)in_size / (double)out_size;

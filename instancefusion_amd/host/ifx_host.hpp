@@ -530,6 +530,19 @@ public:
             throw std::runtime_error(std::string("ifx_mask_head_select: ") + ifx_last_error(h_));
     }
 
+    // UnmoldDetections: the default detector's detections [R][6] and mrcnn_mask ([R][M][M][C], IFX_UNMOLD_NHWC, or [R][C][M][M], IFX_UNMOLD_NCHW) of one image to
+    // image-sized 0 / 1 masks, boxes and class ids (the rule: ifx_c_api.h; MaskRCNN.unmold_detections, deps/mask_rcnn/model.py:2285-2344, and utils.unmold_mask,
+    // deps/mask_rcnn/utils.py:490-507).  window: four int32 on the HOST (ifx_molded_input_size's last four).  -> d_masks_out [R][height * width] u8, d_class_ids
+    // [R], d_boxes_out [R][4] int32, d_scores_out [R] and d_rows [R] (each may be nullptr), kept in d_kept[0]; zeros and -1 behind kept.  Enqueue only.
+    void UnmoldDetections(const float* d_detections, const float* d_masks, const int32_t* window, const int32_t* d_class_map, int R, int M, int C, int layout, int width,
+                          int height, uint8_t* d_masks_out, int32_t* d_class_ids, int32_t* d_boxes_out, float* d_scores_out, int32_t* d_rows, int32_t* d_kept, void* stream)
+    {
+        require_handle(h_, "ElasticFusion::UnmoldDetections");
+        if (ifx_unmold_detections(h_, d_detections, d_masks, window, d_class_map, R, M, C, layout, width, height, d_masks_out, d_class_ids, d_boxes_out, d_scores_out, d_rows,
+                                  d_kept, stream) < 0)
+            throw std::runtime_error(std::string("ifx_unmold_detections: ") + ifx_last_error(h_));
+    }
+
     int getMapSurfelCount() { return ifx_map_count(h_); }
     ifx_t* handle() { return h_; }
     const ifx_config& config() const { return cfg_; }
@@ -1093,6 +1106,27 @@ public:
         });
         return kept;
     }
+    // ---- the reference's default detector (IF/main.cpp:33 -> build/mask_ori.py, the Keras Mask R-CNN): ElasticFusion::UnmoldDetections' inputs in device memory
+    // of the map's GPU, R <= 256.  The stage (MaskRCNN.unmold_detections, deps/mask_rcnn/model.py:2285-2344) runs on `stream`, the producer's, at the map's frame
+    // size; then everything as ProcessSegmentationDevice on the u8 masks it keeps.  Returns kept.
+    int ProcessSegmentationUnmolded(const std::unique_ptr<ElasticFusionInterface>& map, const float* d_detections, const float* d_masks, const int32_t* window,
+                                    const int32_t* d_class_map, int R, int M, int C, int layout, int frame_num, bool isflann, void* stream)
+    {
+        int32_t kept = 0;
+        seg_call("InstanceFusion::ProcessSegmentationUnmolded", "ifx_process_segmentation_unmolded", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_unmolded(h, d_detections, d_masks, window, d_class_map, R, M, C, layout, frame_num, flags, stream, &kept);
+        });
+        return kept;
+    }
+    int ProcessSegmentationDeferredUnmolded(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const float* d_detections, const float* d_masks,
+                                            const int32_t* window, const int32_t* d_class_map, int R, int M, int C, int layout, int frame_num, bool isflann, void* stream)
+    {
+        int32_t kept = 0;
+        seg_call("InstanceFusion::ProcessSegmentationDeferredUnmolded", "ifx_process_segmentation_deferred_unmolded", nullptr, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_process_segmentation_deferred_unmolded(h, ticket, d_detections, d_masks, window, d_class_map, R, M, C, layout, frame_num, flags, stream, &kept);
+        });
+        return kept;
+    }
     // ---- the device forms on a sharded map (ifx_owner_process_segmentation_device / _rois / _detections): the detector runs on rank `root`'s GPU, only that rank's
     // tensors, n and stream are read (the others pass null / 0), the library packs what the other ranks need into one record and broadcasts it on the handle's
     // communicator; root = -1: every rank holds the tensors.  max_n (1 .. 256, equal on all ranks) is the record's capacity.  rgb, depth: the host frame for the
@@ -1146,6 +1180,21 @@ public:
     {
         ifx_t* h = require_handle(map ? map->handle() : nullptr, "InstanceFusion::DetectorInput");
         if (ifx_detector_input(h, ticket, &prep, d_out, out_floats, stream) < 0) throw std::runtime_error(std::string("ifx_detector_input: ") + ifx_last_error(h));
+    }
+    // The default detector's input (ifx_detector_input_molded; MaskRCNN.mold_inputs, deps/mask_rcnn/model.py:2247-2283): utils.resize_image's size rule and Pillow
+    // resize, the centred padding to max_dim x max_dim, the f64 mean subtracted, as [S][S][3] (IFX_MOLD_NHWC) or [3][S][S] (IFX_MOLD_NCHW) f32 in d_out; ticket,
+    // stream and the protocol as DetectorInput.  MoldedInputSize (host only): out8 = nw, nh, S, S and the window (top, left, top + nh, left + nw).
+    static void MoldedInputSize(int w, int h, int min_dim, int max_dim, int32_t* out8)
+    {
+        if (ifx_molded_input_size(w, h, min_dim, max_dim, out8) < 0)
+            throw std::runtime_error("ifx_molded_input_size: refused (a size or max_dim < 1, an image that does not fit max_dim, or a resize scale above 8)");
+    }
+    void DetectorInputMolded(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, int min_dim, int max_dim, const double mean[3], int layout, float* d_out,
+                             int64_t out_floats, void* stream)
+    {
+        ifx_t* h = require_handle(map ? map->handle() : nullptr, "InstanceFusion::DetectorInputMolded");
+        if (ifx_detector_input_molded(h, ticket, min_dim, max_dim, mean, layout, d_out, out_floats, stream) < 0)
+            throw std::runtime_error(std::string("ifx_detector_input_molded: ") + ifx_last_error(h));
     }
     void ReleaseSnapshot(const std::unique_ptr<ElasticFusionInterface>& map, int ticket)
     {
