@@ -389,6 +389,16 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           the current id image at once.  Not the INACTIVE splat of the loop-closure detection, which is a splat render.
  *   "seg_device" 0, "seg_aside" 0, "ff_rounds" n -- the earlier forms of the segmentation call's schedule (host-driven / on the main stream) and the length
  *                           of the flood fill's fixed relaxation schedule (default 4); identical results
+ *   "compare_map" 1|2     -- how a segmentation call matches a mask to a map instance (the reference's compareMapType, IF/Core/InstanceFusion.h:227): 1 (default)
+ *                           box IoU, computeCompareMap (IF/Core/InstanceFusion.cpp:595-651); 2 mask IoU over 3 x 3-dilated pixel sets, the reference's "PLAN B"
+ *                           (maskCompareMapKernel, IF/Core/InstanceFusionCuda.cu:826-881; the decision, IF/Core/InstanceFusion.cpp:805-870) -- see
+ *                           ifx_mask_compare_map for the rule.  At 2 every entry that runs the call's body on an unsharded handle uses it, under both
+ *                           schedules ("seg_device") with identical results, and the recompute after an eviction uses it too (the reference falls back to the
+ *                           box rule there: DESIGN.md section 1).  Any other value: IFX_E_INVALID.  2 on a sharded handle, and ifx_set_shard(n > 1) while
+ *                           the option is 2: IFX_E_STATE (dilated presence is not additive over ranks).  Cost at 640x480 / 5 M surfels / the bench's 8 masks:
+ *                           +46 .. +51 us on a call of 0.40 ms (0.63 with superpixels) -- the presence pass 59-61 us in the place of the instance-box pass's 47-49,
+ *                           the count kernel 36-37 us (99-100 at 100 masks), the decision 7.7 for 6.4-7.2; the reference's remark for its own version is
+ *                           10 - 330 ms per call.  With the option at 1 the call is the parent's within the spread between runs (profiles/r23_compare_map_iou.txt)
  *   "clean_raster" 0, "hot_records" 0 -- round 5's map-pass forms off: the clean pass and the prediction's raster as ONE walk of the view list; the
  *                           gathered 64-byte copy of the hot fields.  Identical results
  *   "host_entry_async" 1  -- ifx_process_frame returns when the frame's POSE is known (see there)
@@ -978,6 +988,25 @@ int ifx_mask_clean_overlap(ifx_t* h, uint8_t* masks, int n);  /* IF/Core/Instanc
  * depth under the camera (u16 H x W, 1186 units per metre, what getProjectDepthMap :977-996 produces); masks n x H x W
  * in/out; ori = the masks before clean-overlap; unavailable n bytes in/out (set entries are skipped). */
 int ifx_mask_geometric_filter(ifx_t* h, const uint16_t* depth, uint8_t* masks, const uint8_t* ori, int n, uint8_t* unavailable);
+/* The mask rule of the compare map as a stage (the reference's compareMapType 2: getProjectInstanceListKernel, IF/Core/InstanceFusionCuda.cu:781-807,
+ * maskCompareMapKernel :826-881, the decision loop IF/Core/InstanceFusion.cpp:834-861), whatever option "compare_map" says.  masks: host, n x H x W, used as
+ * given (> 0 is inside); class_ids n; unavailable n bytes or NULL.  Reads the current id image (completed if lazy), the current votes and the instance table;
+ * changes no state.
+ *   presence(i, p): the id image names a surfel of this map under pixel p and counter i of that surfel decodes to > 0.  Md(m, p) / Id(i, p): some pixel of p's
+ *   3 x 3 neighbourhood inside the image has mask m > 0 / presence(i, .).  I[m][i] = #{p : Md and Id}, U[m][i] = #{p : Md or Id} = A_M[m] + A_I[i] - I[m][i]
+ *   over all pixels; pairs whose classes differ (every unused slot, class -1, included) stay 0.
+ *   decision per mask: none if it is unavailable or its box over the pixels that carry a surfel is degenerate (the box rule's test); otherwise over the instances
+ *   of its class in ascending order, iou = float(I) / float(U), a candidate iff iou > 0.5f, the best replaced iff iou > the best so far (equal maxima keep the
+ *   lowest index; 0 / 0 matches nothing); and a best of instance 0 is NO match, as under the box rule.
+ * out_I, out_U: n x 96 or NULL; out_best: n (the matched instance or -1) or NULL.  IFX_E_INVALID: n outside 0..256, NULL masks or class ids with n > 0;
+ * IFX_E_STATE: a sharded handle. */
+int ifx_mask_compare_map(ifx_t* h, const uint8_t* masks, const int32_t* class_ids, int n, const uint8_t* unavailable, int32_t* out_I, int32_t* out_U, int32_t* out_best);
+/* What the last segmentation call on this handle decided per mask (the reference prints it, IF/Core/InstanceFusion.cpp:955-1010), under either rule and either
+ * schedule: returns the call's mask count (0: none yet, or a call without masks or on an empty map) and fills the first min(count, max_n) entries of
+ * out_best -- the compare map's match, -1 if none (after an eviction: of the map recomputed for the mask that caused it and those behind it) -- and out_target
+ * -- the instance the mask voted for (its match, or the slot it registered), -1 if it was unusable.  Masks are in the call's order (device entries: sorted).
+ * The owners' calls of a sharded map are not recorded. */
+int ifx_segmentation_matches(ifx_t* h, int32_t* out_best, int32_t* out_target, int max_n);
 
 /* ---- superpixel refinement stages (the three calls of processInstance steps -1_1..-1_3,
  * IF/Core/InstanceFusion.cpp:722-738; ifx_process_segmentation runs them when flags bit1 is set).

@@ -234,6 +234,8 @@ _SIGS = {
     "ifx_loop_closure_instance_table": (C.c_int, [_P, _P]),
     "ifx_mask_clean_overlap": (C.c_int, [_P, _P, C.c_int]),
     "ifx_mask_geometric_filter": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
+    "ifx_mask_compare_map": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "ifx_segmentation_matches": (C.c_int, [_P, _P, _P, C.c_int]),
     "ifx_knn_vote_colour": (C.c_int, [_P, _P, C.c_int]),
     "ifx_slic_segment": (C.c_int, [_P, _P, _P]),
     "ifx_merge_superpixels": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -1337,6 +1339,18 @@ class ElasticFusion:
         self._chk(self.L.ifx_track_maps(self.handle, _ptr(a[0]), _ptr(a[1]), _ptr(im[0]), _ptr(a[2]), _ptr(a[3]), _ptr(im[1]), _ptr(p), _ptr(diag)), "ifx_track_maps")
         return p.reshape(4, 4), diag
 
+    def mask_compare_map(self, masks, class_ids, unavailable=None):
+        """ifx_mask_compare_map: the mask rule of the compare map (the reference's compareMapType 2) as a stage, whatever option compare_map says.
+        masks n x H x W uint8 (used as given), class_ids n -> (I, U, best): n x 96 int32 tables and the matched instance per mask (-1: none)."""
+        masks = np.ascontiguousarray(masks, np.uint8).reshape(-1, self.h, self.w)
+        n = int(masks.shape[0])
+        cls = np.ascontiguousarray(class_ids, np.int32)
+        un = None if unavailable is None else np.ascontiguousarray(unavailable, np.uint8)
+        I, U, best = np.zeros((n, 96), np.int32), np.zeros((n, 96), np.int32), np.full(n, -1, np.int32)
+        self._chk(self.L.ifx_mask_compare_map(self.handle, _ptr(masks) if n else None, _ptr(cls) if n else None, n, None if un is None else _ptr(un), _ptr(I), _ptr(U), _ptr(best)),
+                  "ifx_mask_compare_map")
+        return I, U, best
+
     # -- map access (getMapSurfelCount / getMapSurfelsGpu / id textures)
     def getMapSurfelCount(self):
         return self._chk(self.L.ifx_map_count(self.handle), "ifx_map_count")
@@ -1752,6 +1766,16 @@ class InstanceFusion:
         out = np.zeros(4, np.int32)
         self.ef._chk(self.L.ifx_segmentation_snapshot_stats(self.ef.handle, int(ticket), _ptr(out)), "ifx_segmentation_snapshot_stats")
         return dict(tick=int(out[0]), pixels=int(out[1]), lost=int(out[2]), in_use=int(out[3]))
+
+    def set_compare_map_type(self, t):
+        """the reference's compareMapType (IF/Core/InstanceFusion.h:227): 1 box IoU (default), 2 mask IoU over dilated pixel sets (option compare_map)"""
+        self.ef.set_option("compare_map", int(t))
+
+    def segmentation_matches(self):
+        """ifx_segmentation_matches: (best, target) of the last segmentation call -- per mask the compare map's match and the instance it voted for, -1 for none"""
+        best, target = np.full(256, -1, np.int32), np.full(256, -1, np.int32)
+        n = self.ef._chk(self.L.ifx_segmentation_matches(self.ef.handle, _ptr(best), _ptr(target), 256), "ifx_segmentation_matches")
+        return best[:n].copy(), target[:n].copy()
 
     def labels(self):
         n = self.ef.getMapSurfelCount()

@@ -383,6 +383,11 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
     else if (s == "pace") h->opt_pace = value;
     else if (s == "lazy_ids") { ifx_ids_ensure(h); h->opt_lazy_ids = value; }
     else if (s == "seg_device") h->opt_seg_device = value;
+    else if (s == "compare_map") {   // the compare map's rule: 1 box IoU (default), 2 mask IoU (the reference's compareMapType; ifx_instance.hip, k_cmp_count)
+        if (value != 1 && value != 2) { h->err = "compare_map must be 1 (box IoU) or 2 (mask IoU)"; return IFX_E_INVALID; }
+        if (value == 2 && (h->own || h->shard_n > 1)) { h->err = "compare_map 2: the mask rule is not offered on a sharded map (dilated presence is not additive over ranks)"; return IFX_E_STATE; }
+        h->opt_compare_map = value;
+    }
     else if (s == "seg_snapshots") { if (value < 1 || value > 8) { h->err = "seg_snapshots must be in [1, 8]"; return IFX_E_INVALID; } h->opt_seg_snapshots = value; }
     else if (s == "ff_rounds") h->opt_ff_rounds = value;
     else if (s == "gn_persist_blocks") { if (value < 1) return IFX_E_INVALID; ifx_drop_tracked(h); h->opt_gn_persist_blocks = value; }
@@ -879,6 +884,7 @@ extern "C" int ifx_owner_track_ahead(ifx_t* h, int cam, int tracking_rank, const
 extern "C" int ifx_set_shard(ifx_t* h, int rank, int nranks)
 {
     if (!h || nranks < 1 || rank < 0 || rank >= nranks) return IFX_E_INVALID;
+    if (nranks > 1 && h->opt_compare_map == 2) { h->err = "ifx_set_shard: option compare_map is 2, and the mask rule is not offered on a sharded map"; return IFX_E_STATE; }
     ifx_vlist_reap(h);
     hs_invalidate_view(h);
     h->shard_rank = rank; h->shard_n = nranks;

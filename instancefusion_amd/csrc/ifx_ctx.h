@@ -518,6 +518,11 @@ struct ifx {
     uint8_t* h_masks_stage = nullptr; size_t h_masks_cap = 0;    // pinned staging of the caller's masks
     int* d_mask_rank = nullptr;        // masks already on the device (ifx_process_segmentation_device): [256] inside-pixel counts (zero between calls), [256] order, [256] class ids in that order
     int opt_seg_device = 1;            // segmentation call without the host in the middle (0: the host-driven schedule of round 2)
+    int opt_compare_map = 1;           // the compare map's rule: 1 box IoU (computeCompareMap), 2 mask IoU over 3 x 3-dilated pixel sets (the reference's compareMapType 2)
+    int* d_cmp_tab = nullptr;          // mask rule: A_I[96], A_M[256], I[256][96] (+ a sink of 96 boxes); with d_pres allocated by the first call under the rule
+    void* d_pres = nullptr;            // mask rule: [P] uint4, the presence bits of the 96 instances under every pixel
+    int seg_last_nm = 0;               // ifx_segmentation_matches: the mask count of the last segmentation call and what it decided per mask
+    int32_t seg_last_best[256], seg_last_target[256];
     // deferred segmentation (ifx_segmentation_snapshot / ifx_process_segmentation_deferred, ifx_instance.hip)
     void* seg_snaps = nullptr;         // the ticket table and its device buffers, allocated by the first snapshot
     int opt_seg_snapshots = 4;         // outstanding tickets allowed (option seg_snapshots, 1..8)

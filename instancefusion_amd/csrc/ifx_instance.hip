@@ -476,10 +476,13 @@ __device__ __forceinline__ void bbox_extend_box(int* b, const int* sb)
 // MODE 0: instance boxes and mask boxes (the reference's two kernels as one).  The device-scheduled call splits them: MODE 1, the instance boxes -- the twelve vote
 // float4 of every pixel's surfel, the heavy half, and nothing of the masks -- is on the queue BEFORE the host copies the masks into pinned memory (and writes the model
 // depth under every pixel on the way: getProjectDepthMapKernel reads the same id); MODE 2, the mask boxes, follows the masks and needs one vote float4 per pixel.
+// MODE 3 (option compare_map 2): MODE 1 plus the presence image of the mask rule -- bit i of a pixel's 96 says "counter i of the surfel under it is > 0"
+// (instanceProjectMap[i][p] > 0 of getProjectInstanceListKernel, :781-807; no surfel: no bit) -- from the counters the pass decodes anyway.
 template <int MODE>
 __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const float4* __restrict__ votes, int cap, const uint8_t* __restrict__ masks,
                                int nm, int w, int h, int* __restrict__ bbox, IdMap im, const float4* __restrict__ pc = nullptr, uint16_t* __restrict__ pdm = nullptr,
-                               const float* __restrict__ cam = nullptr)   // cam: the row-major pose whose translation is the camera centre (SegView::cam; MODE 1 only)
+                               const float* __restrict__ cam = nullptr,   // cam: the row-major pose whose translation is the camera centre (SegView::cam; MODE 1 / 3 only)
+                               uint4* __restrict__ pres = nullptr)       // MODE 3: [P] presence words (x, y, z: instances 0-31, 32-63, 64-95)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
     const int lane = (threadIdx.y * blockDim.x + threadIdx.x) & 63;
@@ -496,7 +499,7 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
     const int id = idmap_slot(im, st->count, gid);   // (sharded map: the pixels whose surfel another rank owns extend that rank's partial boxes)
     bool has = inside && id >= 0;
     int maxNum = 0, maxID = -1, first = 0;
-    if (MODE == 1 && pdm && inside) {   // getProjectDepthMapKernel (k_project_depth) on the way
+    if ((MODE == 1 || MODE == 3) && pdm && inside) {   // getProjectDepthMapKernel (k_project_depth) on the way
         uint16_t o = 0;
         if (id >= 0) {
             const float4 p = pc[id];
@@ -505,6 +508,7 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
         }
         pdm[k] = o;
     }
+    unsigned int pw[3] = {0u, 0u, 0u};
     if (MODE == 2) {
         if (has) { int b_; vote_decode(VOTE4(votes, id, 0).x, first, b_); }
     } else if (has) {
@@ -521,9 +525,11 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
                 if (q == 0 && t == 0) first = a;
                 if (a > maxNum) { maxNum = a; maxID = (q * 4 + t) * 2; }
                 if (b > maxNum) { maxNum = b; maxID = (q * 4 + t) * 2 + 1; }
+                if (MODE == 3) pw[q / 4] |= (a > 0 ? 1u << ((q * 4 + t) * 2 & 31) : 0u) | (b > 0 ? 1u << (((q * 4 + t) * 2 + 1) & 31) : 0u);
             }
         }
     }
+    if (MODE == 3 && inside) pres[k] = make_uint4(pw[0], pw[1], pw[2], 0u);
     if (first == -1) has = false;   // instanceProjectMap[y*width+x] != -1 test (:915)
     // boxes of the projected instances: one reduction per distinct arg-max id in the wave (a wave rarely sees more than two or three)
     const int key = (MODE != 2 && has && maxID != -1) ? maxID : -1;
@@ -536,7 +542,7 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
         todo &= ~grp;
     }
     // boxes of the masks
-    for (int m0 = 0; MODE != 1 && m0 < nm; m0 += 8) {
+    for (int m0 = 0; (MODE == 0 || MODE == 2) && m0 < nm; m0 += 8) {
         uint8_t mb[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) mb[u] = (has && m0 + u < nm) ? masks[(size_t)(m0 + u) * P + k] : (uint8_t)0;
@@ -777,7 +783,7 @@ void ifx_free_snapshots(ifx* h);
 void ifx_free_instance(ifx* h)
 {
     hipFree(h->d_inst_color); hipFree(h->d_masks); hipFree(h->d_masks_ori); hipFree(h->d_unavail); hipFree(h->d_ff_label); hipFree(h->d_pdm); hipFree(h->d_bbox); hipFree(h->d_inst_stats); hipFree(h->d_clean_list);
-    hipFree(h->d_segctl); hipFree(h->d_mask_rank); hipFree(h->oseg_rec);
+    hipFree(h->d_segctl); hipFree(h->d_mask_rank); hipFree(h->oseg_rec); hipFree(h->d_cmp_tab); hipFree(h->d_pres);
     ifx_free_snapshots(h);
     ifx_detector_free(h);
     if (h->h_segctl) hipHostFree(h->h_segctl);
@@ -1234,6 +1240,156 @@ static int mask_geometric_filter_device(ifx* h, const uint16_t* d_depth, uint8_t
     LAUNCH(h, "ff_apply", per_px, dim3(256), k_ff_apply, a);
     if (!verdict_by_caller) LAUNCH(h, "ff_verdict", dim3(cdiv(nm, 64)), dim3(64), k_ff_verdict, a, d_unavail);
     return IFX_OK;
+}
+
+// ------------------------------------------------------------------ the mask rule of the compare map (option compare_map 2; the reference's "PLAN B",
+// compareMapType 2: maskCompareMapKernel, IF/Core/InstanceFusionCuda.cu:826-881, and the decision loop, IF/Core/InstanceFusion.cpp:805-870)
+// I[m][i] = #{p : Md(m, p) and Id(i, p)}, A_M[m] = #{p : Md(m, p)}, A_I[i] = #{p : Id(i, p)} over all pixels, Md / Id the 3 x 3 dilations (inside the image) of
+// mask m and of instance i's presence (k_project_bbox<3>); U = A_M + A_I - I is never counted.  The tables hold EVERY pair: the class test of the rule is made
+// where they are read (k_seg_compare_iou, compare_map_iou, ifx_mask_compare_map's outputs).
+// One workgroup per tile of 32 x 8 pixels.  Presence words and mask bits of the tile and its one-pixel halo go through LDS; a wave's ballot of "instance i is
+// here" is taken once per instance the wave sees at all and kept in LDS, so that a mask's row of I is popcount(mask ballot & instance ballot) with the lanes over
+// the instances; wave -> LDS accumulators of the workgroup -> one global integer add per cell it touched.  Integer adds only: exact in any order.
+#define CM_TW 32
+#define CM_TH 8
+#define CM_HW (CM_TW + 2)
+#define CM_HC (CM_HW * (CM_TH + 2))
+#define CM_AI 0                         // table layout (ints): A_I[NI], A_M[256], I[256][NI]; behind them the box sink of the presence pass outside the device body
+#define CM_AM NI
+#define CM_I (NI + 256)
+#define CM_INTS (NI + 256 + 256 * NI)
+__global__ void __launch_bounds__(CM_TW * CM_TH) k_cmp_count(const uint4* __restrict__ pres, const uint8_t* __restrict__ masks, int nm, int w, int h, int* __restrict__ tab)
+{
+    __shared__ unsigned int s_p[3][CM_HC];
+    __shared__ unsigned char s_mk[CM_HC];
+    __shared__ unsigned long long s_bal[CM_TW * CM_TH / 64][NI];
+    __shared__ int s_ai[NI], s_am[8], s_i[8 * NI];
+    const int tid = threadIdx.y * CM_TW + threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int x0 = blockIdx.x * CM_TW - 1, y0 = blockIdx.y * CM_TH - 1, P = w * h;
+    for (int c = tid; c < CM_HC; c += CM_TW * CM_TH) {
+        const int cx = x0 + c % CM_HW, cy = y0 + c / CM_HW;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (cx >= 0 && cx < w && cy >= 0 && cy < h) v = pres[cy * w + cx];   // (neighbours outside the image are skipped: no bits)
+        s_p[0][c] = v.x; s_p[1][c] = v.y; s_p[2][c] = v.z;
+    }
+    for (int t = tid; t < 8 * NI; t += CM_TW * CM_TH) s_i[t] = 0;
+    if (tid < NI) s_ai[tid] = 0;
+    if (tid < 8) s_am[tid] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * CM_TW + threadIdx.x, y = blockIdx.y * CM_TH + threadIdx.y;
+    const bool inside = x < w && y < h;
+    const int c0 = threadIdx.y * CM_HW + threadIdx.x;   // the halo cell above and left of this pixel
+    unsigned int idw[3] = {0u, 0u, 0u}, ow[3];
+    if (inside) {
+#pragma unroll
+        for (int d = 0; d < 9; d++) { const int c = c0 + (d / 3) * CM_HW + d % 3; idw[0] |= s_p[0][c]; idw[1] |= s_p[1][c]; idw[2] |= s_p[2][c]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {   // the instances this wave sees at all (uniform), a ballot of each
+        ow[k] = idw[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ow[k] |= __shfl_xor(ow[k], o, 64);
+        unsigned int bits = ow[k];
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1;
+            const unsigned long long bal = __ballot((idw[k] >> b) & 1u);
+            if (lane == 0) { s_bal[wv][k * 32 + b] = bal; atomicAdd(&s_ai[k * 32 + b], __popcll(bal)); }
+        }
+    }
+    for (int m0 = 0; m0 < nm; m0 += 8) {   // (uniform) the masks in chunks of eight, as k_project_bbox takes them: a bit each
+        for (int c = tid; c < CM_HC; c += CM_TW * CM_TH) {
+            const int cx = x0 + c % CM_HW, cy = y0 + c / CM_HW;
+            unsigned int bits = 0;
+            if (cx >= 0 && cx < w && cy >= 0 && cy < h) {
+                const int k = cy * w + cx;
+                uint8_t mb[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) mb[u] = m0 + u < nm ? masks[(size_t)(m0 + u) * P + k] : (uint8_t)0;
+#pragma unroll
+                for (int u = 0; u < 8; u++) bits |= (mb[u] > 0 ? 1u : 0u) << u;
+            }
+            s_mk[c] = (unsigned char)bits;
+        }
+        __syncthreads();   // (also: s_bal of this wave's lane 0 before its other lanes read it)
+        unsigned int md = 0;
+        if (inside) {
+#pragma unroll
+            for (int d = 0; d < 9; d++) md |= s_mk[c0 + (d / 3) * CM_HW + d % 3];
+        }
+        unsigned int om = md;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) om |= __shfl_xor(om, o, 64);
+        while (om) {   // (uniform) the masks this wave sees; cells no lane touches cost nothing
+            const int u = __ffs(om) - 1;
+            om &= om - 1;
+            const unsigned long long balm = __ballot((md >> u) & 1u);
+            if (lane == 0) atomicAdd(&s_am[u], __popcll(balm));
+            for (int i = lane; i < NI; i += 64) {
+                if (!((ow[i >> 5] >> (i & 31)) & 1u)) continue;
+                const int cnt = __popcll(balm & s_bal[wv][i]);
+                if (cnt) atomicAdd(&s_i[u * NI + i], cnt);
+            }
+        }
+        __syncthreads();
+        for (int t = tid; t < 8 * NI; t += CM_TW * CM_TH) {
+            const int v = s_i[t];
+            if (v) { atomicAdd(&tab[CM_I + m0 * NI + t], v); s_i[t] = 0; }   // (a chunk's partial row u >= nm - m0 never counts: its bits are 0)
+        }
+        if (tid < 8 && s_am[tid]) { atomicAdd(&tab[CM_AM + m0 + tid], s_am[tid]); s_am[tid] = 0; }
+        __syncthreads();
+    }
+    __syncthreads();
+    if (tid < NI && s_ai[tid]) atomicAdd(&tab[CM_AI + tid], s_ai[tid]);
+}
+
+// the tables and the presence image: allocated by the first call that runs under the mask rule (hipMalloc may synchronise the device: that one call of a handle
+// is not free of synchronisation in its middle, every later one is)
+static int cmp_ensure(ifx* h)
+{
+    if (!h->d_cmp_tab) HIPCHK(h, hipMalloc(&h->d_cmp_tab, (size_t)(CM_INTS + NI * 4) * 4));
+    if (!h->d_pres) HIPCHK(h, hipMalloc(&h->d_pres, (size_t)h->P * 16));
+    return IFX_OK;
+}
+static int cmp_launch_count(ifx* h, int nm)
+{
+    HIPCHK(h, hipMemsetAsync(h->d_cmp_tab, 0, (size_t)(CM_I + nm * NI) * 4, h->cur));
+    LAUNCH(h, "cmp_count", dim3(cdiv(h->w, CM_TW), cdiv(h->h, CM_TH)), dim3(CM_TW, CM_TH), k_cmp_count, (const uint4*)h->d_pres, (const uint8_t*)h->d_masks, nm, h->w, h->h, h->d_cmp_tab);
+    return IFX_OK;
+}
+// the tables of the masks in d_masks under the id image `ids`, read back (the host-driven schedule, the eviction tail, the stage entry): the presence pass sends
+// its instance boxes to a sink behind the tables, so that d_bbox stays what the box launches made it
+static int cmp_tables_host(ifx* h, const int32_t* ids, int nm, std::vector<int>& tab)
+{
+    int r = cmp_ensure(h);
+    if (r) return r;
+    int* sink = h->d_cmp_tab + CM_INTS;
+    LAUNCH(h, "init_bbox", dim3(cdiv(NI * 4, 256)), dim3(256), k_init_bbox, sink, NI, h->w, h->h);
+    LAUNCH(h, "project_bbox_pres", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<3>, h->d_state, ids, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr, nm,
+           h->w, h->h, sink, ifx_idmap(h), (const float4*)nullptr, (uint16_t*)nullptr, (const float*)nullptr, (uint4*)h->d_pres);
+    if ((r = cmp_launch_count(h, nm))) return r;
+    tab.resize((size_t)CM_I + (size_t)nm * NI);
+    HIPCHK(h, hipMemcpyAsync(tab.data(), h->d_cmp_tab, tab.size() * 4, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return IFX_OK;
+}
+// the decision over the tables (IF/Core/InstanceFusion.cpp:834-861) behind plan A's degenerate-box test: ascending instances of the mask's class, one f32 division,
+// a candidate iff iou > 0.5, the best replaced iff iou > the best so far (equal maxima keep the lowest index; 0 / 0 matches nothing), and "if (best > 0)" at the end
+static void compare_map_iou(ifx* h, const int* tab, const int* maskBBox, const int32_t* class_ids, int nm, std::vector<uint8_t>& unavailable, std::vector<int>& cmp)
+{
+    for (int m = 0; m < nm; m++) {
+        const int minX_m = maskBBox[m * 4], maxX_m = maskBBox[m * 4 + 1], minY_m = maskBBox[m * 4 + 2], maxY_m = maskBBox[m * 4 + 3];
+        if (maxX_m <= minX_m || maxY_m <= minY_m || unavailable[m]) { unavailable[m] = 1; continue; }
+        int best = -1;
+        float best_iou = 0;
+        for (int q = 0; q < NI; q++) {
+            if (h->inst_class[q] == -1 || class_ids[m] != h->inst_class[q]) continue;
+            const int I = tab[CM_I + m * NI + q], U = tab[CM_AM + m] + tab[CM_AI + q] - I;
+            const float iou = (float)I / (float)U;
+            if (iou > 0.5f && iou > best_iou) { best = q; best_iou = iou; }
+        }
+        if (best > 0) cmp[best + m * NI] = 1;
+    }
 }
 
 // computeCompareMap, IF/Core/InstanceFusion.cpp:595-651
@@ -1695,6 +1851,17 @@ static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* de
     return r;
 }
 
+// step 2 on the host, behind run_bboxes: the box rule, or (option compare_map 2) the mask rule -- the count kernels of the device schedule, the tables read back
+static int seg_compare_maps(ifx* h, const SegView& v, int nm, const int32_t* class_ids, const std::vector<int>& bbox, std::vector<uint8_t>& unavailable, std::vector<int>& cmp)
+{
+    if (h->opt_compare_map != 2) { compare_map(h, &bbox[NI * 4], &bbox[0], class_ids, nm, unavailable, cmp); return IFX_OK; }
+    std::vector<int> tab;
+    const int r = cmp_tables_host(h, v.ids, nm, tab);
+    if (r) return r;
+    compare_map_iou(h, tab.data(), &bbox[NI * 4], class_ids, nm, unavailable, cmp);
+    return IFX_OK;
+}
+
 // step 3 of processInstance (IF/Core/InstanceFusion.cpp:955-1040) from mask m_start on, driven by the host: registration, the eviction of a full table
 // (computeMaxCountInMap, getInstanceTableCleanList, cleanInstanceTableMap, boxes and compare map again), one vote launch per (mask, instance)
 static int seg_host_mask_loop(ifx* h, const SegView& v, int nm, const int32_t* class_ids, int m_start, std::vector<int>& cmp, std::vector<uint8_t>& unavailable, std::vector<int>& bbox)
@@ -1703,6 +1870,7 @@ static int seg_host_mask_loop(ifx* h, const SegView& v, int nm, const int32_t* c
     int r;
     for (int m = m_start; m < nm; m++) {
         bool exist = false;
+        int reg = -1;
         for (int q = 0; q < NI; q++) if (cmp[q + m * NI] == 1) { exist = true; break; }
         if (!exist && !unavailable[m]) {
             int empty = first_not_used(h);
@@ -1715,11 +1883,16 @@ static int seg_host_mask_loop(ifx* h, const SegView& v, int nm, const int32_t* c
                 r = run_bboxes(h, v, nm, bbox);
                 if (r) return r;
                 std::fill(cmp.begin(), cmp.end(), 0);
-                compare_map(h, &bbox[NI * 4], &bbox[0], class_ids, nm, unavailable, cmp);
+                if ((r = seg_compare_maps(h, v, nm, class_ids, bbox, unavailable, cmp))) return r;   // (the mask rule again under compare_map 2, on the votes as the eviction left them: DESIGN.md section 1)
                 empty = first_not_used(h);
             }
-            if (empty >= 0) { h->inst_class[empty] = class_ids[m]; cmp[empty + m * NI] = 1; }
+            if (empty >= 0) { h->inst_class[empty] = class_ids[m]; cmp[empty + m * NI] = 1; reg = empty; }
         }
+        // what the call decided for this mask (ifx_segmentation_matches): the match of the compare map the mask met (the one after an eviction it caused), and the
+        // instance it votes for -- the slot it registered, if it did (as in the reference, a mask that the recomputed map matches after all votes for both)
+        h->seg_last_best[m] = -1;
+        for (int q = NI - 1; q >= 0; q--) if (cmp[q + m * NI] == 1 && q != reg) h->seg_last_best[m] = q;
+        h->seg_last_target[m] = reg >= 0 ? reg : h->seg_last_best[m];
         for (int q = 0; q < NI; q++)
             if (cmp[q + m * NI] == 1)
                 LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update, h->d_state, v.ids, h->d_masks + (size_t)m * P, P, h->cap, q, m + 1, h->votes, ifx_idmap(h));
@@ -1998,6 +2171,7 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
     // (ifx_map.hip "View list") is unstable, so it was never in an id image, carries no votes and takes part in nothing else of this call.
     if (flags & 1) ifx_vlist_reap(h);
     h->seg_counts_valid = 0;
+    h->seg_last_nm = 0;
     PoolEvent ea(h);   // (given back on every return but the last, where stage_pending takes it)
     hipEventRecord(ea.ev, h->cur);
     HIPCHK(h, hipStreamSynchronize(h->cur));
@@ -2033,7 +2207,7 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
     r = run_bboxes(h, v, nm, bbox);
     if (r) return r;
     std::vector<int> cmp((size_t)nm * NI, 0);
-    compare_map(h, &bbox[NI * 4], &bbox[0], class_ids, nm, unavailable, cmp);
+    if ((r = seg_compare_maps(h, v, nm, class_ids, bbox, unavailable, cmp))) return r;
     // step 3_0: model depth under the camera, then the flood fill of every usable mask (device)
     LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, v.ids, (const float4*)h->pc, P, 1186, h->d_pdm, ifx_idmap(h), v.cam);
     HIPCHK(h, hipMemcpyAsync(h->d_unavail, unavailable.data(), nm, hipMemcpyHostToDevice, h->cur));
@@ -2050,6 +2224,7 @@ static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_
     if (flags & 1) { r = ifx_knn_vote(h, nullptr); if (r) return r; }
     ifx_stage_span_end(h, 2, ea);
     HIPCHK(h, hipStreamSynchronize(h->cur));
+    h->seg_last_nm = nm;
     return IFX_OK;
 }
 
@@ -2094,6 +2269,39 @@ __global__ void k_seg_compare(SegCtl* __restrict__ s, const int* __restrict__ bb
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+        if (lane == 0) { s->target[m] = -1; s->best[m] = best > 0 ? best : -1; }
+    }
+}
+// The mask rule's decision (compare_map_iou on the device; IF/Core/InstanceFusion.cpp:834-861) over the tables of k_cmp_count: a wave per mask, its lanes over the
+// instances, reduced on (iou descending, index ascending) -- the sequential loop's "replace iff iou > best so far".  Same side effects as k_seg_compare.
+__global__ void k_seg_compare_iou(SegCtl* __restrict__ s, const int* __restrict__ bbox, uint8_t* __restrict__ unavailable, const int* __restrict__ tab)
+{
+    __shared__ int s_cls[NI], s_ai[NI];
+    for (int t = threadIdx.x; t < NI; t += blockDim.x) { s_cls[t] = s->inst_class[t]; s_ai[t] = tab[CM_AI + t]; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, nm = s->nm;
+    for (int m = threadIdx.x >> 6; m < nm; m += blockDim.x >> 6) {
+        const int* mb = bbox + (NI + m) * 4;
+        const int minX_m = mb[0], maxX_m = mb[1], minY_m = mb[2], maxY_m = mb[3];
+        if (maxX_m <= minX_m || maxY_m <= minY_m || unavailable[m]) {   // (wave-uniform) plan A's degenerate-box test
+            if (lane == 0) { s->target[m] = -1; unavailable[m] = 1; s->best[m] = -1; }
+            continue;
+        }
+        const int cls = s->cls[m], am = tab[CM_AM + m];
+        int best = -1;
+        float best_iou = 0;
+        for (int q = lane; q < NI; q += 64) {
+            if (s_cls[q] == -1 || cls != s_cls[q]) continue;
+            const int I = tab[CM_I + m * NI + q], U = am + s_ai[q] - I;
+            const float iou = (float)I / (float)U;
+            if (iou > 0.5f && iou > best_iou) { best = q; best_iou = iou; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int ob = __shfl_xor(best, o, 64);
+            const float oi = __shfl_xor(best_iou, o, 64);
+            if (ob >= 0 && (best < 0 || oi > best_iou || (oi == best_iou && ob < best))) { best = ob; best_iou = oi; }
+        }
         if (lane == 0) { s->target[m] = -1; s->best[m] = best > 0 ? best : -1; }
     }
 }
@@ -2446,6 +2654,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     if (h->seg_counts_valid && h->ev_result) { HIPCHK(h, hipEventSynchronize(h->ev_result)); n = h->h_result->count; }
     else { HIPCHK(h, hipStreamSynchronize(h->cur)); HIPCHK(h, hipMemcpy(&n, &h->d_state->count, sizeof(int), hipMemcpyDeviceToHost)); }
     h->seg_counts_valid = 0;
+    h->seg_last_nm = 0;
     if (nm == 0 || n == 0) return IFX_OK;
     t_res = us();
     if (!snap) ifx_ids_ensure(h);   // the call reads the id image under every mask pixel: the whole image, if the frame rendered only the sampled lattice (a snapshot pinned the whole one)
@@ -2466,8 +2675,14 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     // what needs the map and the id image but not the masks -- the boxes of the projected instances (the twelve vote float4 under every pixel: the heavy half of
     // getProjectInstanceList / computeProjectBoundingBox) and the model depth under every pixel -- runs while the host copies the masks into pinned memory
     LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
-    LAUNCH(h, "project_bbox_inst", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<1>, h->d_state, v.ids, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr, nm,
-           h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)h->pc, h->d_pdm, v.cam);
+    const bool mask_rule = h->opt_compare_map == 2;   // (the mask rule: the same pass also stores the presence image, so the votes are gathered once)
+    if (mask_rule && (r = cmp_ensure(h))) return r;
+    if (mask_rule)
+        LAUNCH(h, "project_bbox_pres", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<3>, h->d_state, v.ids, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr,
+               nm, h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)h->pc, h->d_pdm, v.cam, (uint4*)h->d_pres);
+    else
+        LAUNCH(h, "project_bbox_inst", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<1>, h->d_state, v.ids, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr,
+               nm, h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)h->pc, h->d_pdm, v.cam);
     const bool default_early = !h->labels_stale_all;
     if (default_early) LAUNCH(h, "colour_default", dim3(2048), dim3(256), k_colour_default, h->d_state, (const float2*)h->tm, (float2*)h->col, h->labels, (const int*)nullptr);
     if (flags & 2) { if ((r = ifx_superpixel_filter_prepare(h, nm))) return r; }
@@ -2492,7 +2707,12 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     }
     LAUNCH(h, "project_bbox_mask", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<2>, h->d_state, v.ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
            h->d_bbox, ifx_idmap(h));
-    LAUNCH(h, "seg_compare", dim3(1), dim3(256), k_seg_compare, dc, (const int*)h->d_bbox, h->d_unavail);
+    if (mask_rule) {   // (the mask-box launch stays: the degenerate-box test reads it)
+        if ((r = cmp_launch_count(h, nm))) return r;
+        LAUNCH(h, "seg_compare_iou", dim3(1), dim3(256), k_seg_compare_iou, dc, (const int*)h->d_bbox, h->d_unavail, (const int*)h->d_cmp_tab);
+    } else {
+        LAUNCH(h, "seg_compare", dim3(1), dim3(256), k_seg_compare, dc, (const int*)h->d_bbox, h->d_unavail);
+    }
     const int rounds = h->opt_ff_rounds > 0 ? h->opt_ff_rounds : 4;   // (after the union-find start the first relaxation normally finds the fixpoint: the rest are spares for one-way edges)
     r = mask_geometric_filter_device(h, h->d_pdm, h->d_masks, h->d_masks_ori, nm, h->d_unavail, rounds, false, true);
     if (r) return r;
@@ -2512,6 +2732,7 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
         if (hc->evict_at >= 0 && full2) h->labels_stale_all = 1;
     }
     for (int i = 0; i < NI; i++) h->inst_class[i] = hc->inst_class[i];
+    for (int m = 0; m < nm; m++) { h->seg_last_best[m] = hc->best[m]; h->seg_last_target[m] = hc->target[m]; }   // (ifx_segmentation_matches; the host-driven tail overwrites its masks)
     if (hc->evict_at >= 0) {   // the table is full at this mask: the reference evicts its twenty weakest instances and goes on -- from here the host-driven loop
         std::vector<uint8_t> unavailable(h_un, h_un + nm);
         std::vector<int> cmp((size_t)nm * NI, 0), bbox;
@@ -2523,7 +2744,52 @@ static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint1
     if (flags & 1) { r = ifx_knn_vote(h, nullptr); if (r) return r; }
     ifx_stage_span_end(h, 2, ea);
     HIPCHK(h, hipStreamSynchronize(h->cur));
+    h->seg_last_nm = nm;
     return IFX_OK;
+}
+
+// The mask rule as a stage (host masks, used as given): the tables and the decision under the current id image, votes and instance table.  Map, votes, table
+// and what ifx_segmentation_matches reports stay as they are; the call's scratch -- d_masks, d_bbox, the presence image and the tables -- is overwritten, as by the
+// sibling stages, and the votes are gathered twice (the box pass for the degenerate-box test, then the presence pass with its boxes into the sink).
+extern "C" int ifx_mask_compare_map(ifx_t* h, const uint8_t* masks, const int32_t* class_ids, int n, const uint8_t* unavailable, int32_t* out_I, int32_t* out_U, int32_t* out_best)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || n > 256) { h->err = "ifx_mask_compare_map: n must be 0 .. 256"; return IFX_E_INVALID; }
+    if (n > 0 && (!masks || !class_ids)) { h->err = "ifx_mask_compare_map: null masks or class ids"; return IFX_E_INVALID; }
+    if (h->own || h->shard_n > 1) { h->err = "ifx_mask_compare_map: not on a sharded map"; return IFX_E_STATE; }
+    if (n == 0) return IFX_OK;
+    int r = ifx_ids_ensure(h);
+    if (r) return r;
+    const size_t bytes = (size_t)n * h->P;
+    if ((r = ifx_ensure_masks(h, bytes))) return r;
+    HIPCHK(h, hipMemcpyAsync(h->d_masks, masks, bytes, hipMemcpyHostToDevice, h->cur));
+    const SegView v = seg_view_current(h);
+    std::vector<int> bbox, tab, cmp((size_t)n * NI, 0);
+    if ((r = run_bboxes(h, v, n, bbox)) || (r = cmp_tables_host(h, v.ids, n, tab))) return r;
+    std::vector<uint8_t> un(n, 0);
+    if (unavailable) un.assign(unavailable, unavailable + n);
+    compare_map_iou(h, tab.data(), &bbox[NI * 4], class_ids, n, un, cmp);
+    for (int m = 0; m < n; m++) {
+        if (out_best) out_best[m] = -1;
+        for (int q = 0; q < NI; q++) {
+            const bool same = h->inst_class[q] != -1 && h->inst_class[q] == class_ids[m];   // pairs whose classes differ stay 0, as the reference leaves them
+            const int I = tab[CM_I + m * NI + q];
+            if (out_I) out_I[m * NI + q] = same ? I : 0;
+            if (out_U) out_U[m * NI + q] = same ? tab[CM_AM + m] + tab[CM_AI + q] - I : 0;
+            if (out_best && cmp[q + m * NI] == 1) out_best[m] = q;
+        }
+    }
+    return IFX_OK;
+}
+
+extern "C" int ifx_segmentation_matches(ifx_t* h, int32_t* out_best, int32_t* out_target, int max_n)
+{
+    if (!h || max_n < 0) return IFX_E_INVALID;
+    for (int m = 0; m < h->seg_last_nm && m < max_n; m++) {
+        if (out_best) out_best[m] = h->seg_last_best[m];
+        if (out_target) out_target[m] = h->seg_last_target[m];
+    }
+    return h->seg_last_nm;
 }
 
 __global__ void k_gather_labels(const DevState* __restrict__ st, const float2* __restrict__ tm, const int32_t* __restrict__ labels, const int* __restrict__ rank, int cap,

@@ -1280,6 +1280,33 @@ public:
     }
     int segmentationCalls() const { return segmentations_; }
 
+    // compareMapType (IF/Core/InstanceFusion.h:227): 1 the box rule (computeCompareMap, the default), 2 the mask rule over 3 x 3-dilated pixel sets (maskCompareMap,
+    // IF/Core/InstanceFusion.cpp:805-870) -- a constant in the reference, an option of the bound map here (ifx_c_api.h: "compare_map"); not on a sharded map
+    void setCompareMapType(int type)
+    {
+        ifx_t* h = require_handle(handle_, "setCompareMapType");
+        if (ifx_set_option(h, "compare_map", type) != IFX_OK) throw std::runtime_error(std::string("compare_map: ") + ifx_last_error(h));
+        compareMapType_ = type;
+    }
+    int getCompareMapType() const { return compareMapType_; }
+    // the mask rule as a stage (ifx_mask_compare_map): masks n x H x W, used as given; any output may be null (I, U: n x 96; best: n)
+    void maskCompareMap(const std::unique_ptr<ElasticFusionInterface>& map, const unsigned char* masks, const int* classIds, int n, const unsigned char* unavailable, int* I, int* U,
+                        int* best)
+    {
+        ifx_t* h = require_handle(map ? map->handle() : nullptr, "maskCompareMap");
+        if (ifx_mask_compare_map(h, masks, classIds, n, unavailable, I, U, best) != IFX_OK) throw std::runtime_error(std::string("ifx_mask_compare_map: ") + ifx_last_error(h));
+    }
+    // what the last segmentation call decided per mask (ifx_segmentation_matches): first = the compare map's match, second = the instance voted for; -1: none
+    std::pair<std::vector<int32_t>, std::vector<int32_t>> segmentationMatches()
+    {
+        ifx_t* h = require_handle(handle_, "segmentationMatches");
+        std::vector<int32_t> best(256, -1), target(256, -1);
+        const int n = ifx_segmentation_matches(h, best.data(), target.data(), 256);
+        if (n < 0) throw std::runtime_error(std::string("ifx_segmentation_matches: ") + ifx_last_error(h));
+        best.resize((size_t)n); target.resize((size_t)n);
+        return {best, target};
+    }
+
     // IF/Core/InstanceFusion.cpp:1261-1457: 3-D boxes of the instances (map3DBBox: 6 floats per instance, ground frame when bboxType) + the frames
     void computeMapBoundingBox(const std::unique_ptr<ElasticFusionInterface>& map, bool bboxType)
     {
@@ -1341,6 +1368,7 @@ private:
     ifx_t* handle_ = nullptr;
     bool superpixels_ = true;
     int segmentations_ = 0;
+    int compareMapType_ = 1;
     std::vector<float> projectColor_;
 };
 

@@ -21,7 +21,7 @@ struct Args {
     std::string log, masks, out = "./ResultModel", labels, gt_dir, eval_file;
     int width = 640, height = 480, max_frames = 0, max_surfels = 6 * 1000 * 1000, device = 0;
     float fx = 528.f, fy = 528.f, cx = 320.f, cy = 240.f;
-    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false;
+    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false, mask_iou = false;
     int decode_threads = 4;
     int mask_lag = -1;   // --mask-lag K: the masks recorded for frame t arrive K frames later (a detector slower than the frame loop) and are applied through a snapshot of frame t
     float confidence = 10.f;
@@ -32,7 +32,7 @@ int usage(const char* argv0)
 {
     std::fprintf(stderr,
                  "usage: %s LOG.klg|data.txt [--width W --height H --fx F --fy F --cx C --cy C] [--masks DIR] [--out PREFIX]\n"
-                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K]\n"
+                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K] [--mask-iou]\n"
                  "       [--gt-dir DIR (DIR/<frame, 6 digits>.png, 8-bit instance ground truth)] [--eval FILE (precision / recall rows, needs --gt-dir)]\n"
                  "       [--shard-ranks G --shard-rank r --shard-id FILE [--shard-nonce N] (one process per GPU over one spatially sharded map; every rank replays the same log; -1: a world of one)]\n",
                  argv0);
@@ -71,6 +71,7 @@ int main(int argc, char** argv)
         else if (s == "--confidence") a.confidence = (float)std::atof(val("--confidence"));
         else if (s == "--flip-colors") a.flip = true;
         else if (s == "--reference-ids") a.reference_ids = true;   // id images by the reference's screen-space quad rule (option "id_rule" = 1; not on a sharded map)
+        else if (s == "--mask-iou") a.mask_iou = true;   // masks are matched to instances by mask IoU over dilated pixel sets (the reference's compareMapType 2; option "compare_map" = 2; not on a sharded map)
         else if (s == "--mask-lag") a.mask_lag = std::atoi(val("--mask-lag"));   // snapshot at the frame the masks belong to, deferred call K frames later (one detection in flight, as with one detector)
         else if (s == "--no-lookahead") a.lookahead = false;   // frames are handed over one at a time, as the reference's loop does
         else if (s == "--shard-ranks") a.shard.ranks = std::atoi(val("--shard-ranks"));   // -1: a world of one on the sharded path
@@ -114,6 +115,7 @@ int main(int argc, char** argv)
         if (a.shard.on()) ifx_set_option(map->handle(), "own_lazy_ids", 1);
         if (!a.deform) map->elasticFusion().setDeformOnLoopClosure(false);
         if (a.reference_ids) map->elasticFusion().setReferenceIdRule(true);
+        if (a.mask_iou) instancefusion->setCompareMapType(2);
 
         if (a.mask_lag >= 0 && a.shard.on()) { std::fprintf(stderr, "--mask-lag is not available on a sharded map\n"); return 2; }
         struct { bool busy = false; int ticket = -1, frame = 0; bool flann = false, has = false; MaskResult res; } pending;   // the detection in flight (--mask-lag)
