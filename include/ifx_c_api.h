@@ -918,6 +918,77 @@ int ifx_molded_input_size(int width, int height, int min_dim, int max_dim, int32
 int ifx_detector_input_molded(ifx_t* h, int ticket, int min_dim, int max_dim, const double* mean, int layout, float* d_out, int64_t out_floats, void* stream);
 int ifx_detector_input_molded_image(ifx_t* h, const uint8_t* d_rgb, int width, int height, int min_dim, int max_dim, const double* mean, int layout, float* d_out,
                                     int64_t out_floats, void* stream);
+/* ---- the same detector's three layers that are no convolutions (deps/mask_rcnn/model.py): ProposalLayer.call (:227-311), PyramidROIAlign.call (:323-424) and
+ * DetectionLayer / refine_detections_graph (:670-807) with the box conversion behind it (:1961-1963).  In TensorFlow they are graphs of top_k, gather,
+ * non_max_suppression, crop_and_resize, where, unique, map_fn and set_intersection; here each is one enqueue-only call on the caller's buffers and `stream` (NULL =
+ * the handle's main stream): no wait for the device, no allocation in steady state (the detector operators' scratch, grown on demand), no frame or map state, the
+ * counts stay on the device.  In numpy: tests/keras_layers_numpy.py; TensorFlow's kernels are not in the reference tree, so only utils.apply_box_deltas,
+ * utils.non_max_suppression and the level expression are held against executed reference code (tests/golden/keras_layers_ref.npz, tests/test_keras_layers_cpu.py).
+ * Common: boxes are y1, x1, y2, x2 with the far corner OUTSIDE (no + 1 anywhere).  All arithmetic is f32, every operation rounded, none fused, divisions true,
+ *   sqrt correctly rounded.  EXP is the EXP of ifx_rpn_proposals.  The order of scores is ifx_nms's: descending, -0 == +0, equal scores by ascending index, a NaN
+ *   behind every number.
+ *   DECODE(box, d), apply_box_deltas_graph (model.py:185-206): h = y2 - y1; w = x2 - x1; cy = y1 + 0.5f h; cx = x1 + 0.5f w; cy += d0 h; cx += d1 w; h *= EXP(d2);
+ *     w *= EXP(d3); y1 = cy - 0.5f h; x1 = cx - 0.5f w; y2 = y1 + h; x2 = x1 + w.
+ *   CLIP(v, lo, hi), clip_boxes_graph (model.py:209-224): max(min(v, hi), lo) as (v > hi ? hi : v), then (v < lo ? lo : v); a NaN stays a NaN.
+ *   TFNMS(boxes in their order, threshold, limit), tf.image.non_max_suppression: per box ymin = min(y1, y2), ymax = max(y1, y2), likewise x (fminf / fmaxf),
+ *     area = (ymax - ymin) * (xmax - xmin).  IoU of a pair: 0 if either area <= 0; else inter = max(min(ymax) - max(ymin), 0) * max(min(xmax) - max(xmin), 0) and
+ *     iou = inter / (area_a + area_b - inter).  Walking the boxes in order, a box is kept unless a kept box in front of it has iou > threshold with it (strictly; a
+ *     NaN compares false); the walk ends when `limit` boxes are kept.
+ * ifx_keras_proposals, one image: d_rpn_probs [n][2] (background, foreground), d_rpn_bbox [n][4] deltas, d_anchors [n][4] in PIXELS (ProposalLayer's
+ *   self.anchors; utils.generate_pyramid_anchors stays the caller's, constant per configuration).
+ *   1 score[i] = probs[i][1], read in place with a stride of two.  2 K = min(pre_nms_limit, n); the K best anchors by the order above (tf.nn.top_k: equal scores
+ *   by ascending index).  3 d = bbox[i] * std_dev, per component; box = DECODE(anchor, d).  4 CLIP to 0 .. image_h (y) and 0 .. image_w (x).  5 Divide by
+ *   image_h (y) and image_w (x).  6 TFNMS(the K boxes in the selected order, nms_threshold, proposal_count).
+ *   Output: d_proposals [proposal_count][4], the kept boxes -- normalised, as decoded, NOT corner-ordered -- in kept order, zero rows behind them; d_index
+ *   [proposal_count] int64 (may be NULL), their anchor indices, -1 behind them; d_count one int32, the number kept.
+ *   How: n > 8192: one memset, the radix select's five launches with the score's stride as a template argument; then one block sorts and decodes, the pair mask
+ *   in its TF form, the walk: eight launches at any n, three when n <= 8192.  The reference's configuration: n = 65 472, K = 6000, 1000 out.
+ *   IFX_E_INVALID (nothing enqueued, the handle stays usable): pre_nms_limit or proposal_count outside 1 .. 8192, n outside 1 .. 2^24 - 1, a NULL pointer other
+ *   than d_index, image_h or image_w < 1.
+ * ifx_pyramid_level_thresholds (host only: no handle, no GPU): out3 = T0, T1, T2 with c = 224 / sqrt(image_h * image_w), T0 = c 2^-1.5, T1 = c 2^-0.5,
+ *   T2 = c 2^0.5, computed in f64 and rounded once to f32.  IFX_E_INVALID: a NULL out3 or a size < 1.
+ * ifx_pyramid_roi_align: d_features[4], the maps P2 .. P5 of heights[l] x widths[l], [batch][C][H_l][W_l] (layout 0) or [batch][H_l][W_l][C] (layout 1, as Keras
+ *   holds them); d_boxes [batch][n][4] normalised; the image of row r is r / n.
+ *   Level: s = sqrtf((y2 - y1) * (x2 - x1)); level = 2 + (s > T0) + (s >= T1) + (s > T2).  This is the reference's min(5, max(2, 4 + round(log2(s / c)))) with
+ *     tf.round's half-to-even written as compares (-1.5 -> -2, -0.5 -> 0, 0.5 -> 0), so that no device logarithm decides an integer; s zero or NaN: level 2, where
+ *     TensorFlow's clamp puts the zero-padded rows.
+ *   Sample, tf.image.crop_and_resize(method "bilinear", extrapolation_value 0) on the level's map H x W: for output row i, pool_h > 1: scale = ((y2 - y1) *
+ *     (H - 1)) / (pool_h - 1), in_y = y1 * (H - 1) + i * scale; pool_h == 1: in_y = (0.5f * (y1 + y2)) * (H - 1); x likewise with W and pool_w.  in_y < 0,
+ *     in_y > H - 1 or NaN (likewise x): 0 for every channel.  Else top = floorf(in_y), bot = ceilf(in_y), ly = in_y - top, likewise left, right, lx;
+ *     t = tl + (tr - tl) * lx; b = bl + (br - bl) * lx; out = t + (b - t) * ly.  A flipped box (y1 > y2) samples flipped.
+ *   Output: d_out [batch n][C][pool_h][pool_w] (layout 0) or [batch n][pool_h][pool_w][C] (layout 1), rows in the order of the boxes; d_levels [batch n] int32 (may
+ *     be NULL), 2 .. 5.
+ *   How: one launch, a block per box and 4096 outputs; the level, and per output row / column the two texels and the weight, are computed once into LDS, not per
+ *     channel.  Layout 1: the lanes run along C, with 16-byte loads and stores when C % 4 == 0 and the four maps and d_out are 16-byte aligned, scalar otherwise.
+ *     Layout 0: consecutive lanes take consecutive output columns of a channel plane.
+ *   IFX_E_INVALID: a NULL pointer other than d_levels, an unknown layout, batch, channels, n or an image or map size < 1, pool_h or pool_w outside 1 .. 128, a map
+ *     above 2^31 - 1 texels, more than 2^30 outputs per box or more than 2^31 - 1 blocks.
+ * ifx_keras_detections, one image: d_rois [R][4] normalised, d_probs [R][C], d_deltas [R][C][4]; window (y1, x1, y2, x2) in pixels, on the host.
+ *   1 class = the first maximum of the row: best = 0; for j = 1 .. C - 1: probs[j] > probs[best] -> best = j (a NaN never compares greater).  score =
+ *   probs[class].  2 d = deltas[class] * std_dev; box = DECODE(roi, d); times image_h (y) and image_w (x); CLIP to the window; rintf (half to even) to int32, kept
+ *   as floats.  3 A row is dropped if a clipped coordinate is a NaN, or if its class is 0; and, unless min_confidence == 0 (`if config.DETECTION_MIN_CONFIDENCE:`),
+ *   if not score >= min_confidence (a NaN score fails).  With min_confidence == 0 a NaN score stays and is ordered last.  4 Per class, TFNMS(the class's boxes by
+ *   descending score, then ascending row; nms_threshold; max_instances).  Integer boxes of zero area neither suppress nor are suppressed.  5 Of all kept rows the
+ *   max_instances best by descending score, then ascending row.
+ *   Output: d_detections [max_instances][6], rows y1, x1, y2, x2, class, score as floats, zero rows behind them; d_boxes_norm [max_instances][4] (may be NULL),
+ *   those boxes divided by image_h (y) and image_w (x) -- what the mask branch's ifx_pyramid_roi_align takes (model.py:1961-1963); d_index [max_instances] int64
+ *   (may be NULL), each detection's ROI row, -1 behind them; d_count one int32.  The rows are what ifx_unmold_detections takes.
+ *   How: a wave per row for steps 1 to 3; one block sorts all rows by (score, row); the pair mask in its TF form with the class as the group does step 4's
+ *   suppression in one pass; the walk stops at max_instances kept rows -- in descending score a row with max_instances kept rows of its own class in front of it
+ *   lies behind step 5's cut, so the first max_instances kept rows ARE steps 4 and 5.  Four launches.
+ *   IFX_E_INVALID: R outside 1 .. 8192, C outside 2 .. 1024, max_instances outside 1 .. 8192, image_h or image_w < 1, a window coordinate that is NaN or beyond
+ *   +-2^24, a NULL pointer other than d_boxes_norm and d_index. */
+typedef struct ifx_keras_proposal_params { int32_t pre_nms_limit, proposal_count; float nms_threshold; float std_dev[4]; int32_t image_h, image_w; } ifx_keras_proposal_params;
+typedef struct ifx_keras_detection_params {
+    float std_dev[4]; float min_confidence, nms_threshold; int32_t max_instances, image_h, image_w; float window[4];
+} ifx_keras_detection_params;
+int ifx_keras_proposals(ifx_t* h, const float* d_rpn_probs, const float* d_rpn_bbox, const float* d_anchors, int n, const ifx_keras_proposal_params* p,
+                        float* d_proposals, int64_t* d_index, int32_t* d_count, void* stream);
+int ifx_pyramid_level_thresholds(int image_h, int image_w, float* out3);
+int ifx_pyramid_roi_align(ifx_t* h, const float* const* d_features, const int32_t* heights, const int32_t* widths, int batch, int channels, int layout,
+                          const float* d_boxes, int n, int image_h, int image_w, int pool_h, int pool_w, float* d_out, int32_t* d_levels, void* stream);
+int ifx_keras_detections(ifx_t* h, const float* d_rois, const float* d_probs, const float* d_deltas, int R, int C, const ifx_keras_detection_params* p,
+                         float* d_detections, float* d_boxes_norm, int64_t* d_index, int32_t* d_count, void* stream);
 /* ---- the three device forms on a spatially sharded map: a deployment has ONE detector, on one rank's GPU (no counterpart in the reference: one GPU, host masks).
  * ifx_owner_segmentation_begin_device / _rois / _detections join the state machine of ifx_owner_segmentation_begin: 1 = an exchange point is pending (reduce what
  * ifx_owner_exchange(h, 200, ...) lists, then ifx_owner_segmentation_resume), 0 = complete.  ifx_owner_process_segmentation_device / _rois / _detections are the

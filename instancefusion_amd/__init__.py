@@ -70,6 +70,18 @@ class BoxDetParams(C.Structure):
                 ("xform_clip", C.c_float), ("image_w", C.c_int32), ("image_h", C.c_int32)]
 
 
+class KerasProposalParams(C.Structure):
+    """ifx_keras_proposal_params: the parameters of the Keras detector's proposal layer (include/ifx_c_api.h)"""
+    _fields_ = [("pre_nms_limit", C.c_int32), ("proposal_count", C.c_int32), ("nms_threshold", C.c_float), ("std_dev", C.c_float * 4), ("image_h", C.c_int32),
+                ("image_w", C.c_int32)]
+
+
+class KerasDetectionParams(C.Structure):
+    """ifx_keras_detection_params: the parameters of the Keras detector's detection layer (include/ifx_c_api.h)"""
+    _fields_ = [("std_dev", C.c_float * 4), ("min_confidence", C.c_float), ("nms_threshold", C.c_float), ("max_instances", C.c_int32), ("image_h", C.c_int32),
+                ("image_w", C.c_int32), ("window", C.c_float * 4)]
+
+
 class MaskHeadParams(C.Structure):
     """ifx_mask_head_params: the parameters of the mask head's select / sigmoid stage (include/ifx_c_api.h)"""
     _fields_ = [("score_thresh", C.c_float), ("in_w", C.c_int32), ("in_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("sort_by_score", C.c_int32)]
@@ -215,6 +227,10 @@ _SIGS = {
     "ifx_molded_input_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_detector_input_molded": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, _P]),
     "ifx_detector_input_molded_image": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int64, _P]),
+    "ifx_keras_proposals": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(KerasProposalParams), _P, _P, _P, _P]),
+    "ifx_pyramid_level_thresholds": (C.c_int, [C.c_int, C.c_int, _P]),
+    "ifx_pyramid_roi_align": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ifx_keras_detections": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.POINTER(KerasDetectionParams), _P, _P, _P, _P, _P]),
     # the device forms on a sharded map: (h, root, max_n, rgb, depth) in front of the unsharded entry's arguments
     "ifx_owner_segmentation_begin_device": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_owner_segmentation_begin_rois": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -669,6 +685,15 @@ def fpn_level_thresholds(scales, canonical_level=4):
     if r < 0:
         raise IfxError(f"ifx_fpn_level_thresholds: refused (scales {[float(v) for v in sc]})")
     return r, out
+
+
+def pyramid_level_thresholds(image_h, image_w):
+    """ifx_pyramid_level_thresholds (host only, no GPU): float32 [3], T0, T1, T2 of ifx_pyramid_roi_align's level rule, level = 2 + (s > T0) + (s >= T1) +
+    (s > T2) for s = sqrt(h * w) of a normalised box."""
+    out = np.zeros(3, np.float32)
+    if lib().ifx_pyramid_level_thresholds(int(image_h), int(image_w), _ptr(out)) < 0:
+        raise IfxError(f"ifx_pyramid_level_thresholds: refused (image {image_h} x {image_w})")
+    return out
 
 
 def detector_ops(ef):
@@ -1139,6 +1164,177 @@ class ElasticFusion:
         with torch.cuda.stream(stream):
             k = int(kept.item())
             return masks[:k], cls[:k], boxes[:k], scores[:k], rows[:k]
+
+    # -- the default detector's three layers that are no convolutions (deps/mask_rcnn/model.py: ProposalLayer, PyramidROIAlign, DetectionLayer)
+    def _keras_stream(self, t, stream):
+        import torch
+
+        return torch.cuda.current_stream(t.device) if stream is None else stream
+
+    def keras_proposals(self, rpn_probs, rpn_bbox, anchors, image_shape, pre_nms_limit=6000, proposal_count=1000, nms_threshold=0.7, std_dev=(0.1, 0.1, 0.2, 0.2),
+                        out=None, padded=False, stream=None):
+        """ifx_keras_proposals, ProposalLayer.call: rpn_probs [n,2] (background, foreground), rpn_bbox [n,4], anchors [n,4] in pixels (y1, x1, y2, x2), image_shape
+        (height, width) -> (proposals [c,4] normalised, index [c] int64 anchor indices) by the rule of include/ifx_c_api.h.  Everything runs on the device; the
+        4-byte read of the count is this method's only synchronisation, and padded=True returns (proposals [proposal_count,4] with zero rows behind the kept ones
+        -- the layer's own output --, index with -1 behind them, count [1] int32) without it.  With a batch dimension (rpn_probs [B,n,2], rpn_bbox [B,n,4]; the
+        anchors are shared) the images are enqueued one after the other and the result is always the padded form: [B,proposal_count,4], [B,proposal_count],
+        count [B].  out: the proposals tensor to write into.  Enqueue-only on `stream` (default: the current stream)."""
+        import torch
+
+        _ops_tensor(self, rpn_probs, "rpn_probs", torch.float32, "float32")
+        _ops_tensor(self, rpn_bbox, "rpn_bbox", torch.float32, "float32")
+        _ops_tensor(self, anchors, "anchors", torch.float32, "float32")
+        batched = rpn_probs.dim() == 3
+        if rpn_probs.dim() not in (2, 3) or rpn_probs.shape[-1] != 2:
+            raise ValueError(f"rpn_probs: shape {tuple(rpn_probs.shape)}, expected [n,2] or [B,n,2]")
+        n = int(rpn_probs.shape[-2])
+        lead = tuple(rpn_probs.shape[:-2])
+        if tuple(rpn_bbox.shape) != lead + (n, 4):
+            raise ValueError(f"rpn_bbox: shape {tuple(rpn_bbox.shape)}, expected {list(lead + (n, 4))}")
+        if tuple(anchors.shape) != (n, 4):
+            raise ValueError(f"anchors: shape {tuple(anchors.shape)}, expected [{n},4]")
+        p = KerasProposalParams()
+        p.pre_nms_limit, p.proposal_count, p.nms_threshold = int(pre_nms_limit), int(proposal_count), float(nms_threshold)
+        p.std_dev[:] = [float(v) for v in std_dev]
+        p.image_h, p.image_w = int(image_shape[0]), int(image_shape[1])
+        rows = max(p.proposal_count, 0)
+        B = int(lead[0]) if batched else 1
+        stream = self._keras_stream(rpn_probs, stream)
+        dev = rpn_probs.device
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(lead + (rows, 4), dtype=torch.float32, device=dev)
+        else:
+            _ops_tensor(self, out, "out", torch.float32, "float32")
+            if tuple(out.shape) != lead + (rows, 4):
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(lead + (rows, 4))}")
+        with torch.cuda.stream(stream):
+            index = torch.empty(lead + (rows,), dtype=torch.int64, device=dev)
+            count = torch.empty(B, dtype=torch.int32, device=dev)
+        e = 4                                       # bytes of a float32 / int32
+        for b in range(B):
+            self._chk(self.L.ifx_keras_proposals(self.handle, C.c_void_p(rpn_probs.data_ptr() + b * n * 2 * e), C.c_void_p(rpn_bbox.data_ptr() + b * n * 4 * e),
+                                                 C.c_void_p(anchors.data_ptr()), n, C.byref(p), C.c_void_p(out.data_ptr() + b * rows * 4 * e),
+                                                 C.c_void_p(index.data_ptr() + b * rows * 8), C.c_void_p(count.data_ptr() + b * e),
+                                                 C.c_void_p(stream.cuda_stream or None)), "ifx_keras_proposals")
+        if padded or batched:
+            return out, index, count
+        with torch.cuda.stream(stream):
+            c = int(count.item())
+            return out[:c], index[:c]
+
+    def pyramid_roi_align(self, features, boxes, image_shape, pool_shape, layout="nhwc", out=None, levels_out=None, stream=None):
+        """ifx_pyramid_roi_align, PyramidROIAlign.call in one launch: features, the four maps P2 .. P5, each [B,H_l,W_l,C] ('nhwc', as Keras holds them) or
+        [B,C,H_l,W_l] ('nchw'); boxes [B,n,4] (or [n,4] with B == 1) normalised y1, x1, y2, x2; image_shape (height, width); pool_shape (pool_h, pool_w) ->
+        [B,n,pool_h,pool_w,C] or [B,n,C,pool_h,pool_w] ([n,...] for boxes [n,4]) float32: every box sampled from the level the reference gives it, by the rule of
+        include/ifx_c_api.h.  levels_out: an int32 tensor shaped as the boxes' leading dimensions that receives each box's level 2 .. 5.  Enqueue-only on `stream`
+        (default: the current stream)."""
+        import torch
+
+        features = list(features)
+        if len(features) != 4:
+            raise ValueError(f"features: {len(features)} maps, expected the four P2 .. P5")
+        if layout not in ("nhwc", "nchw"):
+            raise ValueError(f"layout {layout!r}: 'nhwc' ([B,H,W,C]) or 'nchw' ([B,C,H,W])")
+        nhwc = layout == "nhwc"
+        for l, f in enumerate(features):
+            _ops_tensor(self, f, f"features[{l}]", torch.float32, "float32")
+            if f.dim() != 4:
+                raise ValueError(f"features[{l}]: shape {tuple(f.shape)}, expected four dimensions")
+        B = int(features[0].shape[0])
+        Cn = int(features[0].shape[3 if nhwc else 1])
+        for l, f in enumerate(features):
+            if int(f.shape[0]) != B or int(f.shape[3 if nhwc else 1]) != Cn:
+                raise ValueError(f"features[{l}]: shape {tuple(f.shape)}, expected the batch {B} and the {Cn} channels of features[0]")
+        _ops_tensor(self, boxes, "boxes", torch.float32, "float32")
+        if boxes.dim() not in (2, 3) or boxes.shape[-1] != 4 or (boxes.dim() == 2 and B != 1) or (boxes.dim() == 3 and int(boxes.shape[0]) != B):
+            raise ValueError(f"boxes: shape {tuple(boxes.shape)}, expected [{B},n,4]" + (" or [n,4]" if B == 1 else ""))
+        lead = tuple(int(v) for v in boxes.shape[:-1])
+        n = lead[-1]
+        ph, pw = int(pool_shape[0]), int(pool_shape[1])
+        shape = lead + ((max(ph, 0), max(pw, 0), Cn) if nhwc else (Cn, max(ph, 0), max(pw, 0)))
+        stream = self._keras_stream(boxes, stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(shape, dtype=torch.float32, device=boxes.device)
+        else:
+            _ops_tensor(self, out, "out", torch.float32, "float32")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(shape)}")
+        if levels_out is not None:
+            _ops_tensor(self, levels_out, "levels_out", torch.int32, "int32")
+            if tuple(levels_out.shape) != lead:
+                raise ValueError(f"levels_out: shape {tuple(levels_out.shape)}, expected {list(lead)}")
+        if n == 0:
+            return out
+        hw = (1, 2) if nhwc else (2, 3)
+        ptrs = (C.c_void_p * 4)(*[f.data_ptr() for f in features])
+        hs = (C.c_int32 * 4)(*[int(f.shape[hw[0]]) for f in features])
+        ws = (C.c_int32 * 4)(*[int(f.shape[hw[1]]) for f in features])
+        self._chk(self.L.ifx_pyramid_roi_align(self.handle, ptrs, hs, ws, B, Cn, 1 if nhwc else 0, C.c_void_p(boxes.data_ptr()), n, int(image_shape[0]),
+                                               int(image_shape[1]), ph, pw, C.c_void_p(out.data_ptr() or None),
+                                               None if levels_out is None else C.c_void_p(levels_out.data_ptr()), C.c_void_p(stream.cuda_stream or None)),
+                  "ifx_pyramid_roi_align")
+        return out
+
+    def keras_detections(self, rois, probs, deltas, window, image_shape, min_confidence=0.7, nms_threshold=0.3, max_instances=100, std_dev=(0.1, 0.1, 0.2, 0.2),
+                         out=None, padded=False, stream=None):
+        """ifx_keras_detections, refine_detections_graph: rois [R,4] normalised, probs [R,C], deltas [R,C,4], window (y1, x1, y2, x2) in pixels (numbers on the
+        host), image_shape (height, width) -> (detections [c,6]: y1, x1, y2, x2, class, score; boxes_norm [c,4]: the boxes normalised for the mask branch's
+        pyramid_roi_align; index [c] int64: each detection's ROI row) by the rule of include/ifx_c_api.h.  Everything runs on the device; the 4-byte read of the
+        count is this method's only synchronisation, and padded=True returns the [max_instances] tensors (zero rows behind the detections -- the layer's own output,
+        what unmold_detections and process_segmentation_unmolded take --, -1 in index) and count [1] int32 without it.  With a batch dimension (rois [B,R,4], probs
+        [B,R,C], deltas [B,R,C,4], window [B][4]) the images are enqueued one after the other and the result is always the padded form with a leading B.  out: the
+        detections tensor to write into.  Enqueue-only on `stream` (default: the current stream)."""
+        import torch
+
+        _ops_tensor(self, rois, "rois", torch.float32, "float32")
+        _ops_tensor(self, probs, "probs", torch.float32, "float32")
+        _ops_tensor(self, deltas, "deltas", torch.float32, "float32")
+        batched = probs.dim() == 3
+        if probs.dim() not in (2, 3):
+            raise ValueError(f"probs: shape {tuple(probs.shape)}, expected [R,C] or [B,R,C]")
+        lead = tuple(int(v) for v in probs.shape[:-2])
+        R, Cn = int(probs.shape[-2]), int(probs.shape[-1])
+        if tuple(rois.shape) != lead + (R, 4):
+            raise ValueError(f"rois: shape {tuple(rois.shape)}, expected {list(lead + (R, 4))}")
+        if tuple(deltas.shape) != lead + (R, Cn, 4):
+            raise ValueError(f"deltas: shape {tuple(deltas.shape)}, expected {list(lead + (R, Cn, 4))}")
+        B = lead[0] if batched else 1
+        win = np.ascontiguousarray(window, np.float32)
+        if win.shape != ((B, 4) if batched else (4,)):
+            raise ValueError(f"window: shape {win.shape}, expected {[B, 4] if batched else [4]}")
+        win = win.reshape(B, 4)
+        p = KerasDetectionParams()
+        p.std_dev[:] = [float(v) for v in std_dev]
+        p.min_confidence, p.nms_threshold, p.max_instances = float(min_confidence), float(nms_threshold), int(max_instances)
+        p.image_h, p.image_w = int(image_shape[0]), int(image_shape[1])
+        rows = max(p.max_instances, 0)
+        stream = self._keras_stream(probs, stream)
+        dev = probs.device
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(lead + (rows, 6), dtype=torch.float32, device=dev)
+        else:
+            _ops_tensor(self, out, "out", torch.float32, "float32")
+            if tuple(out.shape) != lead + (rows, 6):
+                raise ValueError(f"out: shape {tuple(out.shape)}, expected {list(lead + (rows, 6))}")
+        with torch.cuda.stream(stream):
+            norm = torch.empty(lead + (rows, 4), dtype=torch.float32, device=dev)
+            index = torch.empty(lead + (rows,), dtype=torch.int64, device=dev)
+            count = torch.empty(B, dtype=torch.int32, device=dev)
+        e = 4
+        for b in range(B):
+            p.window[:] = [float(v) for v in win[b]]
+            self._chk(self.L.ifx_keras_detections(self.handle, C.c_void_p(rois.data_ptr() + b * R * 4 * e), C.c_void_p(probs.data_ptr() + b * R * Cn * e),
+                                                  C.c_void_p(deltas.data_ptr() + b * R * Cn * 4 * e), R, Cn, C.byref(p), C.c_void_p(out.data_ptr() + b * rows * 6 * e),
+                                                  C.c_void_p(norm.data_ptr() + b * rows * 4 * e), C.c_void_p(index.data_ptr() + b * rows * 8),
+                                                  C.c_void_p(count.data_ptr() + b * e), C.c_void_p(stream.cuda_stream or None)), "ifx_keras_detections")
+        if padded or batched:
+            return out, norm, index, count
+        with torch.cuda.stream(stream):
+            c = int(count.item())
+            return out[:c], norm[:c], index[:c]
 
     # -- frame entry (ElasticFusion::processFrame)
     def set_instance_gt(self, gt):

@@ -478,6 +478,24 @@ __global__ void __launch_bounds__(1024) k_nms_sort(const float* boxes, const flo
 // The pair mask, nms.cu:26-68: one wave per 64 x 64 tile of the upper triangle, bit j of word (row, cb) = row suppresses box cb * 64 + j (IoU > threshold, strictly;
 // a NaN IoU compares false; same group; on the diagonal tile only j > row's lane).  max / min as fmaxf / fminf, every operation f32 and unfused, a true division.
 // (sgroups NULL: one group -- the proposal stage)
+// TF (the Keras layers: ifx_keras_proposals, ifx_keras_detections): the pair's IoU by tf.image.non_max_suppression's rule instead -- boxes y1, x1, y2, x2 with the
+// far corner outside (no + 1), the corners ordered first, a pair with an area <= 0 has IoU 0 -- nms_iou_tf below; everything else is the same tile.
+struct TfBox { float ymin, xmin, ymax, xmax, area; };
+__device__ __forceinline__ TfBox nms_tf_box(const float4 b)
+{
+    TfBox o;
+    o.ymin = fminf(b.x, b.z); o.ymax = fmaxf(b.x, b.z); o.xmin = fminf(b.y, b.w); o.xmax = fmaxf(b.y, b.w);
+    o.area = (o.ymax - o.ymin) * (o.xmax - o.xmin);
+    return o;
+}
+__device__ __forceinline__ float nms_iou_tf(const TfBox& a, const TfBox& b)
+{
+    if (a.area <= 0.f || b.area <= 0.f) return 0.f;
+    const float ih = fmaxf(fminf(a.ymax, b.ymax) - fmaxf(a.ymin, b.ymin), 0.f), iw = fmaxf(fminf(a.xmax, b.xmax) - fmaxf(a.xmin, b.xmin), 0.f);
+    const float inter = ih * iw;
+    return inter / (a.area + b.area - inter);
+}
+template <bool TF = false>
 __device__ __forceinline__ void nms_mask_tile(const float4* sboxes, const int32_t* sgroups, int n, int nb, float thr, unsigned long long* mask)
 {
     const int cb = blockIdx.x, rb = blockIdx.y, t = threadIdx.x;
@@ -494,6 +512,15 @@ __device__ __forceinline__ void nms_mask_tile(const float4* sboxes, const int32_
     const float sa = (a.z - a.x + 1.f) * (a.w - a.y + 1.f);
     const int first = rb == cb ? t + 1 : 0;
     unsigned long long word = 0;
+    if (TF) {
+        const TfBox ta = nms_tf_box(a);
+        for (int j = 0; j < cn; j++) {
+            const float iou = nms_iou_tf(ta, nms_tf_box(s_box[j]));
+            if (iou > thr && s_grp[j] == ga && j >= first) word |= 1ull << j;
+        }
+        mask[(size_t)row * nb + cb] = word;
+        return;
+    }
     for (int j = 0; j < cn; j++) {
         const float4 b = s_box[j];
         const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z), top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
@@ -518,6 +545,14 @@ __global__ void __launch_bounds__(64) k_nms_mask_dev(const float4* sboxes, const
     const int n = n_dev[0];
     if (n > NMS_MAX || (int)blockIdx.x * 64 >= n) return;      // (the column block; the row block is not behind it where the tile is computed)
     nms_mask_tile(sboxes, sgroups, n, nb, thr, mask);
+}
+
+// k_nms_mask_dev by TensorFlow's IoU: the Keras proposal layer (one group) and detection layer (the class as the group)
+__global__ void __launch_bounds__(64) k_nms_mask_dev_tf(const float4* sboxes, const int32_t* sgroups, const int32_t* n_dev, int nb, float thr, unsigned long long* mask)
+{
+    const int n = n_dev[0];
+    if (n > NMS_MAX || (int)blockIdx.x * 64 >= n) return;
+    nms_mask_tile<true>(sboxes, sgroups, n, nb, thr, mask);
 }
 
 // Exclusive scan of one value per thread over a block of W waves (64 W threads, every one of them calls): __shfl_up inside the wave, the wave sums through the W
@@ -702,7 +737,14 @@ constexpr int RPN_MAX_N = 1 << 24;
 __device__ __forceinline__ uint32_t rpn_key32(float s) { return (uint32_t)(nms_key(s, 0) >> 32); }
 
 // the logit of flat anchor index i = (y * W + x) * A + a out of [A][H][W]: permute_and_flatten's indexing (rpn/utils.py), nothing is permuted in memory
-__device__ __forceinline__ float rpn_logit(const float* obj, int i, int A, int HW) { const int cell = i / A; return obj[(size_t)(i - cell * A) * HW + cell]; }
+// (S > 0, the Keras proposal layer: the scores lie flat, S floats apart, and A, HW are not read; S == 0 is the [A][H][W] form, compiled as it always was)
+template <int S = 0>
+__device__ __forceinline__ float rpn_logit(const float* obj, int i, int A, int HW)
+{
+    if (S) return obj[(size_t)i * S];
+    const int cell = i / A;
+    return obj[(size_t)(i - cell * A) * HW + cell];
+}
 
 // 256 threads: the bin that holds rank `rank` (0-based) of a 2048-bin histogram, and the rank inside that bin.  The histogram's total is > rank.
 __device__ __forceinline__ void rpn_pick(const uint32_t* hist, uint32_t rank, uint32_t* s_w, uint32_t* s_out, uint32_t& digit, uint32_t& rest)
@@ -725,7 +767,7 @@ __device__ __forceinline__ void rpn_pick(const uint32_t* hist, uint32_t rank, ui
 
 // state[2p], state[2p + 1], p = 1 .. 3: the key's leading bits fixed by the first p passes and the rank among the keys that share them
 // (the bodies of the selection's kernels are device functions of one 256-thread block: the single-level kernels and the level-batched ones further down call them)
-template <int PASS>
+template <int PASS, int S = 0>
 __device__ __forceinline__ void rpn_hist_block(const float* obj, int n, uint32_t K, uint32_t* hist, uint32_t* state)
 {
     __shared__ uint32_t s_hist[RPN_BINS];
@@ -745,7 +787,7 @@ __device__ __forceinline__ void rpn_hist_block(const float* obj, int n, uint32_t
     for (int k = 0; k < 8; k++) {
         const int m = base + k * 256 + t;              // memory order: the histogram does not care, and the loads are contiguous
         if (m < n) {
-            const uint32_t key = rpn_key32(obj[m]);
+            const uint32_t key = rpn_key32(S ? obj[(size_t)m * S] : obj[m]);
             if (PASS == 0) atomicAdd(&s_hist[key >> 21], 1u);
             else if (PASS == 1) { if ((key >> 21) == prefix) atomicAdd(&s_hist[(key >> 10) & 2047u], 1u); }
             else if ((key >> 10) == prefix) atomicAdd(&s_hist[key & 1023u], 1u);
@@ -755,13 +797,14 @@ __device__ __forceinline__ void rpn_hist_block(const float* obj, int n, uint32_t
     for (int i = t; i < RPN_BINS; i += 256) { const uint32_t v = s_hist[i]; if (v) atomicAdd(&hist[PASS * RPN_BINS + i], v); }
 }
 
-template <int PASS>
+template <int PASS, int S = 0>
 __global__ void __launch_bounds__(256) k_rpn_hist(const float* obj, int n, uint32_t K, uint32_t* hist, uint32_t* state)
 {
-    rpn_hist_block<PASS>(obj, n, K, hist, state);
+    rpn_hist_block<PASS, S>(obj, n, K, hist, state);
 }
 
 // a thread's eight consecutive anchor indices against T: bit k of less / equal
+template <int S = 0>
 __device__ __forceinline__ uint2 rpn_classify(const float* obj, int n, int A, int HW, int first, uint32_t T)
 {
     uint32_t less = 0, equal = 0;
@@ -769,7 +812,7 @@ __device__ __forceinline__ uint2 rpn_classify(const float* obj, int n, int A, in
     for (int k = 0; k < 8; k++) {
         const int i = first + k;
         if (i < n) {
-            const uint32_t key = rpn_key32(rpn_logit(obj, i, A, HW));
+            const uint32_t key = rpn_key32(rpn_logit<S>(obj, i, A, HW));
             if (key < T) less |= 1u << k;
             else if (key == T) equal |= 1u << k;
         }
@@ -778,6 +821,7 @@ __device__ __forceinline__ uint2 rpn_classify(const float* obj, int n, int A, in
 }
 
 // blk[b], blk[nblk + b]: how many keys of block b's 2048 anchor indices lie in front of T and on T
+template <int S = 0>
 __device__ __forceinline__ void rpn_count_block(const float* obj, int n, int A, int HW, const uint32_t* hist, uint32_t* state, uint32_t* blk, int nblk)
 {
     __shared__ uint32_t s_w[4], s_out[2], s_sum[2];
@@ -787,7 +831,7 @@ __device__ __forceinline__ void rpn_count_block(const float* obj, int n, int A, 
     rpn_pick(hist + 2 * RPN_BINS, state[5], s_w, s_out, d, rest);
     const uint32_t T = (state[4] << 10) | d;
     if (blockIdx.x == 0 && t == 0) { state[6] = T; state[7] = rest; }
-    const uint2 le = rpn_classify(obj, n, A, HW, blockIdx.x * RPN_CHUNK + t * 8, T);
+    const uint2 le = rpn_classify<S>(obj, n, A, HW, blockIdx.x * RPN_CHUNK + t * 8, T);
     const uint32_t less = le.x, equal = le.y;
     if (less) atomicAdd(&s_sum[0], (uint32_t)__popc(less));
     if (equal) atomicAdd(&s_sum[1], (uint32_t)__popc(equal));
@@ -816,6 +860,7 @@ __device__ __forceinline__ void block_sum_before(const uint32_t* blk, int stride
 }
 
 // cand[0 .. K): the winners' 64-bit keys -- those in front of T in index order, then the first state[7] + 1 of those on T in index order
+template <int S = 0>
 __device__ __forceinline__ void rpn_compact_block(const float* obj, int n, int A, int HW, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk,
                                                   unsigned long long* cand)
 {
@@ -823,7 +868,7 @@ __device__ __forceinline__ void rpn_compact_block(const float* obj, int n, int A
     const int t = threadIdx.x, b = blockIdx.x;
     block_sum_before<2>(blk, nblk, b, s_before);
     const uint32_t T = state[6], take = state[7] + 1u;
-    const uint2 le = rpn_classify(obj, n, A, HW, b * RPN_CHUNK + t * 8, T);
+    const uint2 le = rpn_classify<S>(obj, n, A, HW, b * RPN_CHUNK + t * 8, T);
     const uint32_t less = le.x, equal = le.y;
     const uint32_t mine = (uint32_t)__popc(less) | ((uint32_t)__popc(equal) << 16);     // both counts of a block are <= 2048: one scan for the two
     const uint32_t excl = block_excl_scan<4, uint32_t>(mine, s_w, nullptr);
@@ -832,7 +877,7 @@ __device__ __forceinline__ void rpn_compact_block(const float* obj, int n, int A
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         const int i = b * RPN_CHUNK + t * 8 + k;
-        if (less & (1u << k)) { if (pl < base) cand[pl] = ((unsigned long long)rpn_key32(rpn_logit(obj, i, A, HW)) << 32) | (uint32_t)i; pl++; }
+        if (less & (1u << k)) { if (pl < base) cand[pl] = ((unsigned long long)rpn_key32(rpn_logit<S>(obj, i, A, HW)) << 32) | (uint32_t)i; pl++; }
         else if (equal & (1u << k)) { if (pe < take && base + pe < K) cand[base + pe] = ((unsigned long long)T << 32) | (uint32_t)i; pe++; }
     }
 }
@@ -1560,6 +1605,275 @@ __global__ void __launch_bounds__(256) k_unmold_paste(const UmArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------------
+// The Keras Mask R-CNN's three layers that are no convolutions (deps/mask_rcnn/model.py): ifx_keras_proposals (ProposalLayer.call, :227-311), ifx_pyramid_roi_align
+// (PyramidROIAlign.call, :323-424) and ifx_keras_detections (refine_detections_graph, :670-771).  The rules in full: include/ifx_c_api.h, in numpy:
+// tests/keras_layers_numpy.py.  Boxes are y1, x1, y2, x2 with the far corner outside; the selection, the sort, the pair mask (its TF form) and the walk are the
+// machinery above.
+constexpr int KP_STRIDE = 2;           // rpn_probs [n][2]: the foreground score is every second float, read in place
+
+__global__ void __launch_bounds__(256) k_kp_count(const float* score, int n, const uint32_t* hist, uint32_t* state, uint32_t* blk, int nblk)
+{
+    rpn_count_block<KP_STRIDE>(score, n, 1, 1, hist, state, blk, nblk);
+}
+
+__global__ void __launch_bounds__(256) k_kp_compact(const float* score, int n, uint32_t K, const uint32_t* state, const uint32_t* blk, int nblk, unsigned long long* cand)
+{
+    rpn_compact_block<KP_STRIDE>(score, n, 1, 1, K, state, blk, nblk, cand);
+}
+
+// apply_box_deltas_graph (model.py:185-206), operation for operation; b and the result are y1, x1, y2, x2 in .x .y .z .w
+__device__ __forceinline__ float4 keras_decode(const float4 b, float d0, float d1, float d2, float d3)
+{
+    float h = b.z - b.x, w = b.w - b.y;
+    float cy = b.x + 0.5f * h, cx = b.y + 0.5f * w;
+    cy = cy + d0 * h;
+    cx = cx + d1 * w;
+    h = h * rpn_exp(d2);
+    w = w * rpn_exp(d3);
+    const float y1 = cy - 0.5f * h, x1 = cx - 0.5f * w;
+    return make_float4(y1, x1, y1 + h, x1 + w);
+}
+
+// clip_boxes_graph's max(min(v, hi), lo) (model.py:209-224); a NaN stays a NaN
+__device__ __forceinline__ float keras_clip(float v, float lo, float hi)
+{
+    v = v > hi ? hi : v;
+    return v < lo ? lo : v;
+}
+
+struct KpArgs {
+    const float *score, *bbox, *anc;                   // probs + 1 (KP_STRIDE apart), [n][4], [n][4] pixels
+    const unsigned long long* cand;                    // the selection's winners, NULL: every anchor is a candidate (n <= 8192)
+    int n, m, P;                                       // m = min(pre_nms_limit, n), P = 2^k >= the keys sorted
+    float sd0, sd1, sd2, sd3, ih, iw;
+    float4* sboxes; int32_t* sindex; int32_t* ns;
+};
+
+// One block: the candidates into the order (k_nms_sort's network), then per sorted row the deltas times the std-dev vector, the decode, the clip to the image and
+// the division by its size.  Every candidate stays (the layer has no small-box filter): ns = m.
+__global__ void __launch_bounds__(1024) k_kp_sort_decode(const KpArgs a)
+{
+    __shared__ unsigned long long s_key[NMS_MAX];
+    const int t = threadIdx.x;
+    if (a.cand) for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.m ? a.cand[i] : ~0ull;
+    else for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.n ? nms_key(a.score[(size_t)i * KP_STRIDE], i) : ~0ull;
+    nms_bitonic(s_key, a.P, t);
+    for (int c = t; c < a.m; c += 1024) {
+        const uint32_t i = (uint32_t)s_key[c];
+        if (i >= (uint32_t)a.n) {                      // (cannot happen: every key holds an anchor index; the test keeps the gathers inside the inputs whatever the keys are)
+            a.sboxes[c] = make_float4(0.f, 0.f, 0.f, 0.f); a.sindex[c] = -1;
+            continue;
+        }
+        const float* an = a.anc + 4 * (size_t)i;
+        const float* d = a.bbox + 4 * (size_t)i;
+        float4 b = keras_decode(make_float4(an[0], an[1], an[2], an[3]), d[0] * a.sd0, d[1] * a.sd1, d[2] * a.sd2, d[3] * a.sd3);
+        b.x = keras_clip(b.x, 0.f, a.ih) / a.ih;
+        b.y = keras_clip(b.y, 0.f, a.iw) / a.iw;
+        b.z = keras_clip(b.z, 0.f, a.ih) / a.ih;
+        b.w = keras_clip(b.w, 0.f, a.iw) / a.iw;
+        a.sboxes[c] = b;
+        a.sindex[c] = (int32_t)i;
+    }
+    if (t == 0) a.ns[0] = a.m;
+}
+
+// ---- ifx_pyramid_roi_align: all levels and rows in one launch.  A block owns one box and PRA_UNITS of its outputs; it finds the box's level by three compares
+// against thresholds made on the host, fills the two axis tables (one entry per output row / column: the two texels and the weight of tf.image.crop_and_resize's
+// bilinear sample) in LDS and then only gathers and blends.
+constexpr int PRA_TAB = 128;           // pool_h, pool_w at the most
+constexpr int PRA_UNITS = 4096;        // outputs (16-byte groups of them in the vector form) of a block: sixteen per thread
+
+struct PraAxis { int lo, hi; float l; };               // lo < 0: outside the map, the output is 0
+
+__device__ __forceinline__ PraAxis pra_axis(float a1, float a2, int i, int pool, int size)
+{
+    const float sm1 = (float)(size - 1);
+    float in;
+    if (pool > 1) { const float scale = ((a2 - a1) * sm1) / (float)(pool - 1); in = a1 * sm1 + (float)i * scale; }
+    else in = (0.5f * (a1 + a2)) * sm1;
+    PraAxis s;
+    if (!(in >= 0.f && in <= sm1)) { s.lo = -1; s.hi = 0; s.l = 0.f; return s; }     // (a NaN too)
+    const float top = floorf(in);
+    s.lo = (int)top; s.hi = (int)ceilf(in); s.l = in - top;                           // both inside 0 .. size - 1
+    return s;
+}
+
+struct PraArgs {
+    const float* in[4];                // P2 .. P5: [batch][C][H_l][W_l] or [batch][H_l][W_l][C]
+    int height[4], width[4];
+    float thr[3];
+    const float* boxes;                // [batch n][4] normalised y1, x1, y2, x2
+    float* out;                        // [batch n][C][ph][pw] or [batch n][ph][pw][C]
+    int32_t* lev_out;                  // NULL or [batch n]
+    int n, channels, ph, pw, chunks;
+};
+
+__device__ __forceinline__ float pra_blend(float tl, float tr, float bl, float br, float lx, float ly)
+{
+    const float top = tl + (tr - tl) * lx, bot = bl + (br - bl) * lx;
+    return top + (bot - top) * ly;
+}
+
+// MODE 0: NCHW, consecutive lanes on consecutive output columns of a channel plane; 1: NHWC, the lanes along C; 2: NHWC, four channels per lane in 16-byte words
+template <int MODE>
+__global__ void __launch_bounds__(256) k_pyramid_roi_align(const PraArgs a)
+{
+    __shared__ PraAxis s_y[PRA_TAB], s_x[PRA_TAB];
+    const int t = threadIdx.x;
+    const int row = blockIdx.x / a.chunks, chunk = blockIdx.x - row * a.chunks;
+    const float* bx = a.boxes + 4 * (size_t)row;
+    const float y1 = bx[0], x1 = bx[1], y2 = bx[2], x2 = bx[3];
+    const float s = sqrtf((y2 - y1) * (x2 - x1));
+    const int lv = (s > a.thr[0] ? 1 : 0) + (s >= a.thr[1] ? 1 : 0) + (s > a.thr[2] ? 1 : 0);        // s zero or NaN: 0, the reference's clamp
+    if (chunk == 0 && t == 0 && a.lev_out) a.lev_out[row] = 2 + lv;
+    const int H = lv == 0 ? a.height[0] : lv == 1 ? a.height[1] : lv == 2 ? a.height[2] : a.height[3];
+    const int W = lv == 0 ? a.width[0] : lv == 1 ? a.width[1] : lv == 2 ? a.width[2] : a.width[3];
+    const float* map = lv == 0 ? a.in[0] : lv == 1 ? a.in[1] : lv == 2 ? a.in[2] : a.in[3];
+    for (int i = t; i < a.ph; i += 256) s_y[i] = pra_axis(y1, y2, i, a.ph, H);
+    for (int i = t; i < a.pw; i += 256) s_x[i] = pra_axis(x1, x2, i, a.pw, W);
+    __syncthreads();
+    const int C = a.channels, bins = a.ph * a.pw;
+    const float* img = map + (size_t)(row / a.n) * C * ((size_t)H * W);
+    float* out = a.out + (size_t)row * C * bins;
+    const int units = MODE == 2 ? bins * (C >> 2) : bins * C;
+    const int end = min(units, (chunk + 1) * PRA_UNITS);
+    for (int o = chunk * PRA_UNITS + t; o < end; o += 256) {
+        if (MODE == 0) {
+            const int c = o / bins, bin = o - c * bins, py = bin / a.pw, px = bin - py * a.pw;
+            const PraAxis y = s_y[py], x = s_x[px];
+            float v = 0.f;
+            if (y.lo >= 0 && x.lo >= 0) {
+                const float *r0 = img + ((size_t)c * H + y.lo) * W, *r1 = img + ((size_t)c * H + y.hi) * W;
+                v = pra_blend(r0[x.lo], r0[x.hi], r1[x.lo], r1[x.hi], x.l, y.l);
+            }
+            out[o] = v;
+        } else {
+            const int cg = MODE == 2 ? C >> 2 : C;
+            const int bin = o / cg, c = o - bin * cg, py = bin / a.pw, px = bin - py * a.pw;
+            const PraAxis y = s_y[py], x = s_x[px];
+            const bool inside = y.lo >= 0 && x.lo >= 0;
+            const size_t tl = ((size_t)y.lo * W + x.lo) * C, tr = ((size_t)y.lo * W + x.hi) * C, bl = ((size_t)y.hi * W + x.lo) * C, br = ((size_t)y.hi * W + x.hi) * C;
+            if (MODE == 2) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (inside) {
+                    const float4 q0 = *(const float4*)(img + tl + 4 * c), q1 = *(const float4*)(img + tr + 4 * c);
+                    const float4 q2 = *(const float4*)(img + bl + 4 * c), q3 = *(const float4*)(img + br + 4 * c);
+                    v.x = pra_blend(q0.x, q1.x, q2.x, q3.x, x.l, y.l);
+                    v.y = pra_blend(q0.y, q1.y, q2.y, q3.y, x.l, y.l);
+                    v.z = pra_blend(q0.z, q1.z, q2.z, q3.z, x.l, y.l);
+                    v.w = pra_blend(q0.w, q1.w, q2.w, q3.w, x.l, y.l);
+                }
+                *(float4*)(out + 4 * (size_t)o) = v;
+            } else {
+                float v = 0.f;
+                if (inside) v = pra_blend(img[tl + c], img[tr + c], img[bl + c], img[br + c], x.l, y.l);
+                out[o] = v;
+            }
+        }
+    }
+}
+
+// ---- ifx_keras_detections.  k_kd_rows, one wave per ROI row: the first maximum of the row's probabilities, the class's deltas, decode, image scale, window clip,
+// rint; the row's record and its sort key (~0: the row is dropped).
+struct KdArgs {
+    const float *rois, *probs, *deltas;                // [R][4], [R][C], [R][C][4]
+    int R, C, P;
+    float sd0, sd1, sd2, sd3, minconf, ih, iw, wy1, wx1, wy2, wx2;
+    unsigned long long* keys;                          // [R]
+    float4* rbox; int32_t* rcls; float* rscore;        // per ROI row
+    float4* sboxes; int32_t* sgroups; float* sscore; int32_t* srow; int32_t* ns;     // per sorted row
+};
+
+__global__ void __launch_bounds__(256) k_kd_rows(const KdArgs a)
+{
+    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    const float* p = a.probs + (size_t)r * a.C;
+    // the sequential rule (best = 0; p[j] > p[best]: best = j) is: class 0 when p[0] is a NaN, else the lowest index of the largest number (a NaN never compares greater)
+    float bv = -INFINITY;
+    int bi = 0x7FFFFFFF;
+    for (int j = lane; j < a.C; j += 64) { const float v = p[j]; if (v > bv || (v == bv && j < bi)) { bv = v; bi = j; } }
+    for (int d = 32; d > 0; d >>= 1) {
+        const float ov = __shfl_xor(bv, d);
+        const int oi = __shfl_xor(bi, d);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    const float p0 = p[0];
+    const int cls = (p0 != p0 || bi >= a.C) ? 0 : bi;   // (no number in the row: p[0] is a NaN)
+    if (lane) return;
+    const float score = p[cls];
+    const float* d = a.deltas + ((size_t)r * a.C + cls) * 4;
+    const float* ro = a.rois + 4 * (size_t)r;
+    float4 b = keras_decode(make_float4(ro[0], ro[1], ro[2], ro[3]), d[0] * a.sd0, d[1] * a.sd1, d[2] * a.sd2, d[3] * a.sd3);
+    b.x = keras_clip(b.x * a.ih, a.wy1, a.wy2);
+    b.y = keras_clip(b.y * a.iw, a.wx1, a.wx2);
+    b.z = keras_clip(b.z * a.ih, a.wy1, a.wy2);
+    b.w = keras_clip(b.w * a.iw, a.wx1, a.wx2);
+    bool keep = b.x == b.x && b.y == b.y && b.z == b.z && b.w == b.w && cls > 0;
+    if (a.minconf != 0.f) keep = keep && score >= a.minconf;        // (`if config.DETECTION_MIN_CONFIDENCE:` -- 0 skips the test, and a NaN score then stays, ordered last)
+    if (keep) {                                         // tf.to_int32(tf.rint(.)) and back to float: the window bounds the values to +-2^24, -0 becomes +0
+        b.x = (float)(int)rintf(b.x); b.y = (float)(int)rintf(b.y); b.z = (float)(int)rintf(b.z); b.w = (float)(int)rintf(b.w);
+    } else b = make_float4(0.f, 0.f, 0.f, 0.f);
+    a.rbox[r] = b; a.rcls[r] = cls; a.rscore[r] = score;
+    a.keys[r] = keep ? nms_key(score, r) : ~0ull;
+}
+
+// One block: the rows into the order (score descending, then ascending row; the dropped rows' keys ~0 behind all of them), the records gathered, the number of
+// rows that stay
+__global__ void __launch_bounds__(1024) k_kd_sort(const KdArgs a)
+{
+    __shared__ unsigned long long s_key[NMS_MAX];
+    const int t = threadIdx.x;
+    for (int i = t; i < a.P; i += 1024) s_key[i] = i < a.R ? a.keys[i] : ~0ull;
+    nms_bitonic(s_key, a.P, t);
+    if (t == 0 && s_key[0] == ~0ull) a.ns[0] = 0;
+    for (int c = t; c < a.R; c += 1024) {
+        const unsigned long long key = s_key[c];
+        if (key == ~0ull) continue;
+        if (c + 1 == a.P || s_key[c + 1] == ~0ull) a.ns[0] = c + 1;      // the last row that stays: one thread
+        const uint32_t r = (uint32_t)key;
+        if (r >= (uint32_t)a.R) { a.sboxes[c] = make_float4(0.f, 0.f, 0.f, 0.f); a.sgroups[c] = -1 - c; a.sscore[c] = 0.f; a.srow[c] = 0; continue; }   // (cannot happen)
+        a.sboxes[c] = a.rbox[r]; a.sgroups[c] = a.rcls[r]; a.sscore[c] = a.rscore[r]; a.srow[c] = (int32_t)r;
+    }
+}
+
+struct KdOut { float* det; float* boxes_norm; long long* index; int32_t* count; int max_inst; float ih, iw; };
+
+// One block: the walk (the class is the pair mask's group: the per-class suppression in one pass), stopped once max_inst rows are kept, and the output.  The
+// per-class cap needs no pass of its own: the rows are in descending score, so a row with max_inst kept rows of its own class in front of it has max_inst kept
+// rows in front of it -- the cut across the classes drops it, and every row the cap drops lies behind that cut.  The first max_inst kept rows are the layer's output.
+__global__ void __launch_bounds__(1024) k_kd_reduce(const unsigned long long* mask, const float4* sboxes, const int32_t* sgroups, const float* sscore, const int32_t* srow,
+                                                    const int32_t* ns, int nb, const KdOut o)
+{
+    __shared__ NmsWalk s;
+    const int t = threadIdx.x, n = min(ns[0], NMS_MAX);
+    nms_walk(mask, nullptr, n, nb, o.max_inst, s);
+    uint32_t bits;
+    int pos, total;
+    nms_flag_scan(s, s.flag, n, bits, pos, total);           // by sorted row
+    for (int k = 0; k < 8; k++)
+        if (bits & (1u << k)) {
+            if (pos < o.max_inst) {
+                const int row = t * 8 + k;
+                const float4 b = sboxes[row];
+                float* d = o.det + 6 * (size_t)pos;
+                d[0] = b.x; d[1] = b.y; d[2] = b.z; d[3] = b.w; d[4] = (float)sgroups[row]; d[5] = sscore[row];
+                if (o.boxes_norm) { float* q = o.boxes_norm + 4 * (size_t)pos; q[0] = b.x / o.ih; q[1] = b.y / o.iw; q[2] = b.z / o.ih; q[3] = b.w / o.iw; }
+                if (o.index) o.index[pos] = srow[row];
+            }
+            pos++;
+        }
+    total = min(total, o.max_inst);
+    for (int i = total + t; i < o.max_inst; i += 1024) {
+        float* d = o.det + 6 * (size_t)i;
+        d[0] = 0.f; d[1] = 0.f; d[2] = 0.f; d[3] = 0.f; d[4] = 0.f; d[5] = 0.f;
+        if (o.boxes_norm) { float* q = o.boxes_norm + 4 * (size_t)i; q[0] = 0.f; q[1] = 0.f; q[2] = 0.f; q[3] = 0.f; }
+        if (o.index) o.index[i] = -1;
+    }
+    if (t == 0) o.count[0] = total;
+}
+
 // the stream the LAUNCH macro and the kernel timing use, for the length of a call on the caller's stream
 struct StreamScope {
     ifx* h; hipStream_t old;
@@ -1852,6 +2166,90 @@ const char* box_code(const float weights[4], float xform_clip, int clip_w, int c
     q->clip = clip_w > 0;
     q->xmax = (float)(clip_w - 1); q->ymax = (float)(clip_h - 1);
     return nullptr;
+}
+
+// ifx_keras_proposals' launches: one memset and eight launches when the layer selects (n > 8192), three launches otherwise.  Scratch as rpn_run's, less the logits.
+int kp_run(ifx* h, const float* d_probs, const float* d_bbox, const float* d_anc, int n, const ifx_keras_proposal_params* p, float* d_proposals, int64_t* d_index,
+           int32_t* d_count, hipStream_t stream)
+{
+    const int m = std::min(p->pre_nms_limit, n), mc = cdiv(m, 64) * 64, nb = mc / 64, nblk = cdiv(n, RPN_CHUNK);
+    const bool select = n > NMS_MAX;
+    const size_t zero_words = 3 * RPN_BINS + 8 + 8;    // histograms, state, the count (and padding)
+    float4* sboxes; unsigned long long *mask, *cand; int32_t* sindex; uint32_t *blk, *hist;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, "ifx_keras_proposals", [&](Carver& c) {
+        sboxes = c.take<float4>(mc);
+        mask = c.take<unsigned long long>((size_t)mc * nb);
+        cand = c.take<unsigned long long>(mc);
+        sindex = c.take<int32_t>(mc);
+        blk = c.take<uint32_t>(2 * (size_t)nblk);
+        hist = c.take<uint32_t>(zero_words);           // one take: one memset zeroes the histograms and the state
+    }, stream, &ops);
+    if (r) return r;
+    uint32_t* state = hist + 3 * RPN_BINS;
+    int32_t* ns = (int32_t*)(state + 8);
+    const float* score = d_probs + 1;                  // probs[i][1]
+    StreamScope scope(h, stream);
+    const uint32_t K = (uint32_t)m;
+    if (select) {
+        HIPCHK(h, hipMemsetAsync(hist, 0, zero_words * 4, stream));
+        LAUNCH(h, "kp_hist", dim3((unsigned)nblk), dim3(256), (k_rpn_hist<0, KP_STRIDE>), score, n, K, hist, state);
+        LAUNCH(h, "kp_hist", dim3((unsigned)nblk), dim3(256), (k_rpn_hist<1, KP_STRIDE>), score, n, K, hist, state);
+        LAUNCH(h, "kp_hist", dim3((unsigned)nblk), dim3(256), (k_rpn_hist<2, KP_STRIDE>), score, n, K, hist, state);
+        LAUNCH(h, "kp_count", dim3((unsigned)nblk), dim3(256), k_kp_count, score, n, (const uint32_t*)hist, state, blk, nblk);
+        LAUNCH(h, "kp_compact", dim3((unsigned)nblk), dim3(256), k_kp_compact, score, n, K, (const uint32_t*)state, (const uint32_t*)blk, nblk, cand);
+    }
+    KpArgs a;
+    a.score = score; a.bbox = d_bbox; a.anc = d_anc; a.cand = select ? cand : nullptr;
+    a.n = n; a.m = m;
+    a.P = 2;
+    while (a.P < (select ? m : n)) a.P <<= 1;
+    a.sd0 = p->std_dev[0]; a.sd1 = p->std_dev[1]; a.sd2 = p->std_dev[2]; a.sd3 = p->std_dev[3];
+    a.ih = (float)p->image_h; a.iw = (float)p->image_w;
+    a.sboxes = sboxes; a.sindex = sindex; a.ns = ns;
+    LAUNCH(h, "kp_sort_decode", dim3(1), dim3(1024), k_kp_sort_decode, a);
+    LAUNCH(h, "kp_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_nms_mask_dev_tf, (const float4*)sboxes, (const int32_t*)nullptr, (const int32_t*)ns, nb, p->nms_threshold,
+           mask);
+    LAUNCH(h, "kp_reduce", dim3(1), dim3(1024), k_rpn_reduce, (const unsigned long long*)mask, (const float4*)sboxes, (const float*)nullptr, (const int32_t*)sindex,
+           (const int32_t*)ns, nb, p->proposal_count, d_proposals, (float*)nullptr, (long long*)d_index, d_count);
+    return ops_done(h, ops, stream);
+}
+
+// ifx_keras_detections' four launches.  Every word a kernel reads is written by a kernel in front of it in the same call: nothing is zeroed.
+int kd_run(ifx* h, const float* d_rois, const float* d_probs, const float* d_deltas, int R, int C, const ifx_keras_detection_params* p, const KdOut& out, hipStream_t stream)
+{
+    const int mc = cdiv(R, 64) * 64, nb = mc / 64;
+    KdArgs a;
+    unsigned long long* mask;
+    DetOps* ops = nullptr;
+    int r = ops_scratch(h, "ifx_keras_detections", [&](Carver& c) {
+        a.sboxes = c.take<float4>(mc);
+        mask = c.take<unsigned long long>((size_t)mc * nb);
+        a.keys = c.take<unsigned long long>(mc);
+        a.rbox = c.take<float4>(mc);
+        a.rcls = c.take<int32_t>(mc);
+        a.rscore = c.take<float>(mc);
+        a.sgroups = c.take<int32_t>(mc);
+        a.sscore = c.take<float>(mc);
+        a.srow = c.take<int32_t>(mc);
+        a.ns = c.take<int32_t>(4);                     // the rows that stay (and padding)
+    }, stream, &ops);
+    if (r) return r;
+    a.rois = d_rois; a.probs = d_probs; a.deltas = d_deltas;
+    a.R = R; a.C = C;
+    a.P = 2;
+    while (a.P < R) a.P <<= 1;
+    a.sd0 = p->std_dev[0]; a.sd1 = p->std_dev[1]; a.sd2 = p->std_dev[2]; a.sd3 = p->std_dev[3];
+    a.minconf = p->min_confidence; a.ih = (float)p->image_h; a.iw = (float)p->image_w;
+    a.wy1 = p->window[0]; a.wx1 = p->window[1]; a.wy2 = p->window[2]; a.wx2 = p->window[3];
+    StreamScope scope(h, stream);
+    LAUNCH(h, "kd_rows", dim3((unsigned)cdiv(R, 4)), dim3(256), k_kd_rows, a);
+    LAUNCH(h, "kd_sort", dim3(1), dim3(1024), k_kd_sort, a);
+    LAUNCH(h, "kd_mask", dim3((unsigned)nb, (unsigned)nb), dim3(64), k_nms_mask_dev_tf, (const float4*)a.sboxes, (const int32_t*)a.sgroups, (const int32_t*)a.ns, nb,
+           p->nms_threshold, mask);
+    LAUNCH(h, "kd_reduce", dim3(1), dim3(1024), k_kd_reduce, (const unsigned long long*)mask, (const float4*)a.sboxes, (const int32_t*)a.sgroups, (const float*)a.sscore,
+           (const int32_t*)a.srow, (const int32_t*)a.ns, nb, out);
+    return ops_done(h, ops, stream);
 }
 
 }   // namespace
@@ -2259,4 +2657,73 @@ extern "C" int ifx_detector_input_molded(ifx_t* h, int ticket, int min_dim, int 
     FrameSlot* slot = nullptr;
     if ((r = ifx_frame_for_reader(h, "ifx_detector_input_molded", ticket, &rgb, &ev, &slot))) return r;
     return det_run(h, rgb, h->w, h->h, nullptr, sz, d_out, stream, ev, slot, &m);
+}
+
+// ---- the Keras Mask R-CNN's proposal, pyramid ROI and detection layers (the rules: include/ifx_c_api.h).  stream NULL: the handle's main stream.
+extern "C" int ifx_keras_proposals(ifx_t* h, const float* d_rpn_probs, const float* d_rpn_bbox, const float* d_anchors, int n, const ifx_keras_proposal_params* p,
+                                   float* d_proposals, int64_t* d_index, int32_t* d_count, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!p || !d_rpn_probs || !d_rpn_bbox || !d_anchors || !d_proposals || !d_count) { h->err = "ifx_keras_proposals: NULL pointer"; return IFX_E_INVALID; }
+    if (n < 1 || n >= RPN_MAX_N) { h->err = "ifx_keras_proposals: n outside 1 .. 2^24 - 1"; return IFX_E_INVALID; }
+    if (p->pre_nms_limit < 1 || p->pre_nms_limit > NMS_MAX || p->proposal_count < 1 || p->proposal_count > NMS_MAX) {
+        h->err = "ifx_keras_proposals: pre_nms_limit or proposal_count outside 1 .. 8192"; return IFX_E_INVALID;
+    }
+    if (p->image_h < 1 || p->image_w < 1) { h->err = "ifx_keras_proposals: image_h or image_w < 1"; return IFX_E_INVALID; }
+    return kp_run(h, d_rpn_probs, d_rpn_bbox, d_anchors, n, p, d_proposals, d_index, d_count, stream ? (hipStream_t)stream : h->stream);
+}
+
+extern "C" int ifx_pyramid_level_thresholds(int image_h, int image_w, float* out3)
+{
+    return ifx_detprep::pyramid_level_thresholds(image_h, image_w, out3) ? IFX_E_INVALID : IFX_OK;
+}
+
+extern "C" int ifx_pyramid_roi_align(ifx_t* h, const float* const* d_features, const int32_t* heights, const int32_t* widths, int batch, int channels, int layout,
+                                     const float* d_boxes, int n, int image_h, int image_w, int pool_h, int pool_w, float* d_out, int32_t* d_levels, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!d_features || !heights || !widths || !d_boxes || !d_out) { h->err = "ifx_pyramid_roi_align: NULL pointer"; return IFX_E_INVALID; }
+    if (layout != 0 && layout != 1) { h->err = "ifx_pyramid_roi_align: layout is neither 0 (NCHW) nor 1 (NHWC)"; return IFX_E_INVALID; }
+    if (batch < 1 || channels < 1 || n < 1 || image_h < 1 || image_w < 1) { h->err = "ifx_pyramid_roi_align: batch, channels, n, image_h or image_w < 1"; return IFX_E_INVALID; }
+    if (pool_h < 1 || pool_h > PRA_TAB || pool_w < 1 || pool_w > PRA_TAB) { h->err = "ifx_pyramid_roi_align: pool_h or pool_w outside 1 .. 128"; return IFX_E_INVALID; }
+    PraArgs a;
+    bool vec = layout == 1 && channels % 4 == 0 && ((uintptr_t)d_out & 15) == 0;
+    for (int l = 0; l < 4; l++) {
+        if (!d_features[l]) { h->err = "ifx_pyramid_roi_align: NULL pointer"; return IFX_E_INVALID; }
+        if (heights[l] < 1 || widths[l] < 1 || (int64_t)heights[l] * widths[l] > 0x7FFFFFFF) {
+            h->err = "ifx_pyramid_roi_align: a map with a size < 1 or more than 2^31 - 1 texels"; return IFX_E_INVALID;
+        }
+        a.in[l] = d_features[l]; a.height[l] = heights[l]; a.width[l] = widths[l];
+        vec = vec && ((uintptr_t)d_features[l] & 15) == 0;
+    }
+    const int64_t rows = (int64_t)batch * n, per_row = (int64_t)channels * pool_h * pool_w;
+    const int64_t units = vec ? per_row / 4 : per_row, chunks = (units + PRA_UNITS - 1) / PRA_UNITS;
+    if (per_row > (1 << 30) || rows * chunks > 0x7FFFFFFF) {
+        h->err = "ifx_pyramid_roi_align: more than 2^30 outputs per box or more than 2^31 - 1 blocks (batch x n x ceil(outputs / 4096))"; return IFX_E_INVALID;
+    }
+    if (ifx_detprep::pyramid_level_thresholds(image_h, image_w, a.thr)) { h->err = "ifx_pyramid_roi_align: image_h or image_w < 1"; return IFX_E_INVALID; }
+    a.boxes = d_boxes; a.out = d_out; a.lev_out = d_levels;
+    a.n = n; a.channels = channels; a.ph = pool_h; a.pw = pool_w; a.chunks = (int)chunks;
+    StreamScope scope(h, stream ? (hipStream_t)stream : h->stream);
+    const dim3 grid((unsigned)(rows * chunks));
+    if (layout == 0) LAUNCH(h, "pyramid_roi_align", grid, dim3(256), k_pyramid_roi_align<0>, a);
+    else if (!vec) LAUNCH(h, "pyramid_roi_align", grid, dim3(256), k_pyramid_roi_align<1>, a);
+    else LAUNCH(h, "pyramid_roi_align", grid, dim3(256), k_pyramid_roi_align<2>, a);
+    return IFX_OK;
+}
+
+extern "C" int ifx_keras_detections(ifx_t* h, const float* d_rois, const float* d_probs, const float* d_deltas, int R, int C, const ifx_keras_detection_params* p,
+                                    float* d_detections, float* d_boxes_norm, int64_t* d_index, int32_t* d_count, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!p || !d_rois || !d_probs || !d_deltas || !d_detections || !d_count) { h->err = "ifx_keras_detections: NULL pointer"; return IFX_E_INVALID; }
+    if (R < 1 || R > NMS_MAX || C < 2 || C > BD_MAX_C) { h->err = "ifx_keras_detections: R outside 1 .. 8192 or C outside 2 .. 1024"; return IFX_E_INVALID; }
+    if (p->max_instances < 1 || p->max_instances > NMS_MAX) { h->err = "ifx_keras_detections: max_instances outside 1 .. 8192"; return IFX_E_INVALID; }
+    if (p->image_h < 1 || p->image_w < 1) { h->err = "ifx_keras_detections: image_h or image_w < 1"; return IFX_E_INVALID; }
+    for (int i = 0; i < 4; i++)
+        if (!(std::fabs(p->window[i]) <= 16777216.f)) { h->err = "ifx_keras_detections: a window coordinate is NaN or beyond +-2^24"; return IFX_E_INVALID; }
+    KdOut o;
+    o.det = d_detections; o.boxes_norm = d_boxes_norm; o.index = (long long*)d_index; o.count = d_count;
+    o.max_inst = p->max_instances; o.ih = (float)p->image_h; o.iw = (float)p->image_w;
+    return kd_run(h, d_rois, d_probs, d_deltas, R, C, p, o, stream ? (hipStream_t)stream : h->stream);
 }

@@ -80,6 +80,22 @@ inline const char* molded_input_size(int w, int h, int min_dim, int max_dim, int
     return nullptr;
 }
 
+// ifx_pyramid_level_thresholds: PyramidROIAlign's level rule (deps/mask_rcnn/model.py:351-357) as three thresholds on s = sqrt(h * w) of a normalised box.
+// The reference takes k = round(log2(s / c)), c = 224 / sqrt(image_h * image_w), half to even, and level = min(5, max(2, 4 + k)); so level >= 3 iff log2(s / c) >
+// -1.5 (-1.5 rounds to -2), level >= 4 iff log2(s / c) >= -0.5 (-0.5 rounds to -0) and level == 5 iff log2(s / c) > 0.5 (0.5 rounds to 0):
+// level = 2 + (s > T0) + (s >= T1) + (s > T2) with T0 = c 2^-1.5, T1 = c 2^-0.5, T2 = c 2^0.5, in f64 (sqrt is correctly rounded, the powers of two below are
+// sqrt(2) / 4, sqrt(2) / 2 and sqrt(2)) and rounded ONCE to f32.  nullptr on success.
+inline const char* pyramid_level_thresholds(int image_h, int image_w, float* out3)
+{
+    if (!out3) return "NULL output";
+    if (image_h < 1 || image_w < 1) return "image_h or image_w < 1";
+    const double c = 224.0 / std::sqrt((double)image_h * (double)image_w), r2 = std::sqrt(2.0);
+    out3[0] = (float)(c * (r2 / 4.0));
+    out3[1] = (float)(c * (r2 / 2.0));
+    out3[2] = (float)(c * r2);
+    return nullptr;
+}
+
 inline int resize_ksize(int in_size, int out_size)
 {
     const double scale = (double)in_size / (double)out_size;

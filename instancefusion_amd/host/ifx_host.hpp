@@ -543,6 +543,36 @@ public:
             throw std::runtime_error(std::string("ifx_unmold_detections: ") + ifx_last_error(h_));
     }
 
+    // The same detector's three layers that are no convolutions (the rules: ifx_c_api.h; deps/mask_rcnn/model.py: ProposalLayer.call :227-311, PyramidROIAlign.call
+    // :323-424, refine_detections_graph :670-771).  Enqueue only; stream nullptr: the map's main stream.
+    // KerasProposals: d_rpn_probs [n][2], d_rpn_bbox [n][4], d_anchors [n][4] pixels -> d_proposals [proposal_count][4] normalised, d_index [proposal_count] (may be
+    // nullptr), the count in d_count[0]; zeros and -1 behind the count.
+    void KerasProposals(const float* d_rpn_probs, const float* d_rpn_bbox, const float* d_anchors, int n, const ifx_keras_proposal_params& p, float* d_proposals,
+                        int64_t* d_index, int32_t* d_count, void* stream)
+    {
+        require_handle(h_, "ElasticFusion::KerasProposals");
+        if (ifx_keras_proposals(h_, d_rpn_probs, d_rpn_bbox, d_anchors, n, &p, d_proposals, d_index, d_count, stream) < 0)
+            throw std::runtime_error(std::string("ifx_keras_proposals: ") + ifx_last_error(h_));
+    }
+    // PyramidRoiAlign: d_features[4], P2 .. P5, [batch][C][H_l][W_l] (layout 0) or [batch][H_l][W_l][C] (layout 1); d_boxes [batch][n][4] normalised -> d_out
+    // [batch n][C][pool_h][pool_w] or [batch n][pool_h][pool_w][C], d_levels [batch n] (may be nullptr).
+    void PyramidRoiAlign(const float* const* d_features, const int32_t* heights, const int32_t* widths, int batch, int channels, int layout, const float* d_boxes, int n,
+                         int image_h, int image_w, int pool_h, int pool_w, float* d_out, int32_t* d_levels, void* stream)
+    {
+        require_handle(h_, "ElasticFusion::PyramidRoiAlign");
+        if (ifx_pyramid_roi_align(h_, d_features, heights, widths, batch, channels, layout, d_boxes, n, image_h, image_w, pool_h, pool_w, d_out, d_levels, stream) < 0)
+            throw std::runtime_error(std::string("ifx_pyramid_roi_align: ") + ifx_last_error(h_));
+    }
+    // KerasDetections: d_rois [R][4] normalised, d_probs [R][C], d_deltas [R][C][4] -> d_detections [max_instances][6] (y1, x1, y2, x2, class, score: what
+    // UnmoldDetections takes), d_boxes_norm [max_instances][4] and d_index [max_instances] (each may be nullptr), the count in d_count[0]; zeros and -1 behind it.
+    void KerasDetections(const float* d_rois, const float* d_probs, const float* d_deltas, int R, int C, const ifx_keras_detection_params& p, float* d_detections,
+                         float* d_boxes_norm, int64_t* d_index, int32_t* d_count, void* stream)
+    {
+        require_handle(h_, "ElasticFusion::KerasDetections");
+        if (ifx_keras_detections(h_, d_rois, d_probs, d_deltas, R, C, &p, d_detections, d_boxes_norm, d_index, d_count, stream) < 0)
+            throw std::runtime_error(std::string("ifx_keras_detections: ") + ifx_last_error(h_));
+    }
+
     int getMapSurfelCount() { return ifx_map_count(h_); }
     ifx_t* handle() { return h_; }
     const ifx_config& config() const { return cfg_; }
