@@ -11,6 +11,8 @@
    -DCOMPILE_WITHOUT_CUDA; driver loops in oracle/ref_slic.cpp) on both colour images of the pair and
    on one synthetic 640x480 frame, plus the oracle's merged-region ids for them (regression pins of
    mergeSuperPixel, for which the reference holds no expected values).
+5. slic_cases_ref.npz -- labels of the same reference build on the adversarial images of tests/slic_cases.py (uniform, checkers, stripes, noise, discs): all twelve
+   at 64x48 and 72x56, five of them at 320x240 and 328x248.  Labels only, int16.  `make_golden.py slic_cases` writes this file alone.
 """
 import os
 import sys
@@ -87,7 +89,30 @@ def knn_fixture():
     assert ref.ref_knn(pos.ctypes.data, n, 10, 64, idx.ctypes.data, dist.ctypes.data) == 0
     np.savez_compressed(os.path.join(OUT, "knn_ref.npz"), pos=pos, idx=idx.astype(np.int16), dist=dist)
     print("knn_ref", pos.shape, idx.shape)
+    slic_cases_fixture()
+
+
+def slic_cases_fixture():
+    import ctypes as C
+
+    import slic_cases as sc
+
+    ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_slic.so"))
+    ref.ref_slic_segment.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]
+    out = {}
+    for name, w, h in sc.golden_cases():
+        rgb = np.ascontiguousarray(sc.image(name, w, h), np.uint8)
+        seg = np.zeros((h, w), np.int32)
+        n = ref.ref_slic_segment(rgb.ctypes.data, w, h, 16, 0.6, 5, seg.ctypes.data)
+        assert n == (w // 16) * (h // 16) and seg.min() >= 0 and seg.max() < n
+        out[sc.key(name, w, h)] = seg.astype(np.int16)
+    path = os.path.join(OUT, "slic_cases_ref.npz")
+    np.savez_compressed(path, **out)
+    print("slic_cases_ref", len(out), "arrays,", os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["slic_cases"]:
+        slic_cases_fixture()
+    else:
+        main()
