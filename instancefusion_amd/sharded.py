@@ -400,10 +400,7 @@ def emulate_owner_segmentation(efs, rgb, depth, masks, class_ids, frame: int, su
 def _device_form_args(ef, form, root, t):
     """The tensor arguments of a device form of the sharded segmentation call for this rank: checked as the InstanceFusion.process_segmentation_* methods check
     them where the rank reads them (root = -1, or root = this rank), NULLs elsewhere.  -> (arguments, stream handle or None, kept, what must outlive the call)"""
-    from . import MASK_U8, InstanceFusion
-
-    def p(x):
-        return None if x is None else C.c_void_p(x.data_ptr() or None)
+    from . import MASK_U8, InstanceFusion, _dp
 
     thr = float(t["threshold"])
     kept = C.c_int32(0)
@@ -416,14 +413,14 @@ def _device_form_args(ef, form, root, t):
     inst = InstanceFusion(ef)
     if form == "device":
         m, cls, fmt, n, stream = inst._device_masks(t["masks"], t["class_ids"], t["stream"])
-        return (p(m), fmt, thr, p(cls), n), stream.cuda_stream or None, kept, (m, cls)
+        return (_dp(m), fmt, thr, _dp(cls), n), stream.cuda_stream or None, kept, (m, cls)
     if form == "rois":
         m, M, bx, cls, n, stream = inst._device_rois(t["roi_masks"], t["boxes"], t["class_ids"], t["stream"])
-        return (p(m), M, p(bx), thr, p(cls), n), stream.cuda_stream or None, kept, (m, bx, cls)
+        return (_dp(m), M, _dp(bx), thr, _dp(cls), n), stream.cuda_stream or None, kept, (m, bx, cls)
     R, Cn, M, par, stream = ef._mask_head_args(t["mask_logits"], t["boxes"], t["scores"], t["labels"], t["in_size"], (ef.w, ef.h), t["score_thresh"], True, t["count"],
                                                t["class_map"], t["stream"])
-    return ((p(t["mask_logits"]), p(t["boxes"]), p(t["scores"]), p(t["labels"]), p(t["count"]), p(t["class_map"]), R, Cn, M, C.byref(par), thr), stream.cuda_stream or None,
-            kept, par)
+    return ((_dp(t["mask_logits"]), _dp(t["boxes"]), _dp(t["scores"]), _dp(t["labels"]), _dp(t["count"]), _dp(t["class_map"]), R, Cn, M, C.byref(par), thr),
+            stream.cuda_stream or None, kept, par)
 
 
 def _device_form_call(ef, prefix, form, root, max_n, rgb, depth, tensors, frame, flags):
