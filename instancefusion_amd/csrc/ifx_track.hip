@@ -221,6 +221,30 @@ __global__ void k_frame_down(const uint16_t* __restrict__ dsrc, const uint8_t* _
         idst[y * dw + x] = count ? (uint8_t)f2i_rz(sum / (float)count) : (uint8_t)0;
     }
 }
+// The photometric residual's own-pixel tests that need no pose -- one copy for the frame side's candidate list (k_frame_maps) and for every per-iteration form of the
+// tracker (residual_body, k_gn_level).  RGBResidual (EF/Cuda/reduce.cu:739-790): the 16-px border and "all 16 pixels of the 4x4 block [i-2,i+2) x [j0-2,j0+2) non-zero"
+// (inside the border the block is always in the image) -- four unaligned 4-byte loads issued together and a has-zero-byte test per row (the byte-by-byte form compiled
+// to 16 dependent loads, each behind the previous one's branch: ~2 us of every residual launch).  CLAMP: a pixel outside the border reads the block of pixel (16, 16)
+// and drops it, so that no load hides behind a branch (the per-iteration forms); without it the loads sit behind the border test (k_frame_maps, once per frame).
+template <bool CLAMP>
+__device__ __forceinline__ bool own_pixel_ok(const uint8_t* __restrict__ img, int w, int h, bool in, int i, int j0)
+{
+    const int border = 16;
+    const bool ok = in && i >= border && i < h - border && j0 >= border && j0 < w - border && j0 < w - 5 && i < h - 1;
+    const int ci = (CLAMP && !ok) ? 16 : i, cj = (CLAMP && !ok) ? 16 : j0;
+    bool valid = true;
+    if (CLAMP || ok) {
+#pragma unroll
+        for (int a = -2; a < 2; a++) {
+            uint32_t r4;
+            __builtin_memcpy(&r4, img + (ci + a) * w + cj - 2, 4);
+            valid = valid & (((r4 - 0x01010101u) & ~r4 & 0x80808080u) == 0u);
+        }
+    }
+    return ok & valid;
+}
+// ... and its gradient gate (minScale: rgb_min_scale of the level)
+__device__ __forceinline__ bool rgb_grad_gate(short gx, short gy, float minScale) { return (float)((gx * gx) + (gy * gy)) >= minScale; }
 struct FrameLevel {
     const uint16_t* depth; const uint8_t* img; float *vmap, *nmap; int16_t *dx, *dy; int w, h, tiles_x, first_block; float fx_inv, fy_inv, cx, cy;
     CandEntry* cand; unsigned int* cand_n; float minScale;   // the level's candidate list of the photometric term (nullptr: none is built), its count, rgb_min_scale(level)
@@ -272,18 +296,8 @@ __global__ void __launch_bounds__(256) k_frame_maps(FrameLevels a)
         // decided here once per frame instead of in every Gauss-Newton iteration: the pixels that pass go into the level's list, compacted by a ballot and ONE atomic per
         // wave.  No order is kept -- the sums the list feeds are exact, any order gives the same bits.  At most w * h entries, the list's capacity.
         const int i = v, j0 = u;
-        const bool ok = i >= 16 && i < h - 16 && j0 >= 16 && j0 < w - 16 && j0 < w - 5 && i < h - 1;
-        bool valid = ok;
-        if (ok) {   // inside the 16-px border the 4x4 block [i-2,i+2) x [j0-2,j0+2) is always in the image
-#pragma unroll
-            for (int a4 = -2; a4 < 2; a4++) {
-                uint32_t r4;
-                __builtin_memcpy(&r4, L.img + (i + a4) * w + j0 - 2, 4);
-                valid = valid & (((r4 - 0x01010101u) & ~r4 & 0x80808080u) == 0u);
-            }
-        }
-        const float mTwo = (float)((sx * sx) + (sy * sy));
-        const bool pass = valid & (mTwo >= L.minScale);
+        const bool valid = own_pixel_ok<false>(L.img, w, h, true, i, j0);
+        const bool pass = valid & rgb_grad_gate(sx, sy, L.minScale);
         const unsigned long long m = __ballot(pass);
         if (m) {   // (uniform over the wave)
             const int lane = threadIdx.x & 63, lead = __ffsll((long long)m) - 1;
@@ -525,6 +539,122 @@ __device__ __forceinline__ void products7(const float* row, bool found, double* 
     acc[28] += found ? 1.0 : 0.0;
 }
 
+// ---- the reference's per-pixel arithmetic, one copy each: every form of the run (two-launch, prologue chain, fused list iteration, persistent level and its
+// one-workgroup fallback, row-sharded) calls these.  Values and references to fixed-size arrays only, so that a caller's rows stay in registers; no load, no LDS, no barrier.
+
+// ICPReduction's correspondence test and row (EF/Cuda/reduce.cu:302-387) for a pixel whose projection lies in the image: true if the pair counts, `row` filled then
+__device__ __forceinline__ bool icp_pair(float (&row)[7], const float (&Rcurr)[9], const float (&Rprev_inv)[9], const v3& tp, const v3& vcurr_g, const v3& ncurr, const v3& vprev, const v3& nprev, float distThres,
+                                         float angleThres)
+{
+    const v3 ncurr_g = mulp(Rcurr, ncurr);
+    const float dist = norm(vprev - vcurr_g);
+    const float sine = norm(cross(ncurr_g, nprev));
+    const bool found = (sine < angleThres && dist <= distThres && !(ncurr.x != ncurr.x) && !(nprev.x != nprev.x));
+    if (found) {
+        const v3 s_cp = mulp(Rprev_inv, vcurr_g - tp);
+        const v3 d_cp = mulp(Rprev_inv, vprev - tp);
+        const v3 n_cp = mulp(Rprev_inv, nprev);
+        const v3 c = cross(s_cp, n_cp);
+        row[0] = n_cp.x; row[1] = n_cp.y; row[2] = n_cp.z;
+        row[3] = c.x; row[4] = c.y; row[5] = c.z;
+        row[6] = dot(n_cp, s_cp - d_cp);
+    }
+    return found;
+}
+// (own_pixel_ok / rgb_grad_gate, its own-pixel tests that need no pose: beside k_frame_maps, which decides them once per frame for the candidate list)
+// RGBResidual's warp of pixel (x, y) with depth d1 into the last image (EF/Cuda/reduce.cu:791-810): its depth there and its pixel; true if the pixel lies in the image
+__device__ __forceinline__ bool rgb_warp(const float (&krk)[9], float kt0, float kt1, float kt2, float d1, int x, int y, int w, int h, float& td1, int& u0, int& v0)
+{
+    td1 = (float)(d1 * (krk[6] * x + krk[7] * y + krk[8]) + kt2);
+    u0 = f2i_rn((d1 * (krk[0] * x + krk[1] * y + krk[2]) + kt0) / td1);
+    v0 = f2i_rn((d1 * (krk[3] * x + krk[4] * y + krk[5]) + kt1) / td1);
+    return (u0 >= 0) & (v0 >= 0) & (u0 < w) & (v0 < h);
+}
+// ... and the hit test on what the gathers brought back (:811-842): `cand` the pixel's own tests and the warp's, d0 / last_nonzero the last image's depth and intensity
+__device__ __forceinline__ bool rgb_warp_hit(bool cand, float d0, float td1, float maxDepthDelta, bool last_nonzero)
+{
+    return cand & (d0 > 0) & (fabsf(td1 - d0) <= maxDepthDelta) & last_nonzero;
+}
+// sigma of the photometric weights from the residual pass's totals, with the reference's precedence quirk (EF/Utils/RGBDOdometry.cpp:461)
+__device__ __forceinline__ float rgb_sigma(int cnt, int sg)
+{
+    float q = (float)sg / (float)cnt;
+    return (float)sqrt((double)((q == 0) ? 1 : cnt));
+}
+// RGBReduction's weight and Jacobian row of a correspondence (EF/Cuda/reduce.cu:494-619): residual `diff`, gradients of the own pixel, point-cloud entry of the hit
+__device__ __forceinline__ void rgb_row(float (&row)[7], float sigma, float diff, short gx, short gy, float X, float Y, float Z, float fx, float fy, float sobelScale)
+{
+    float wgt = sigma + fabsf(diff);
+    wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
+    if (sigma == -1) wgt = 1;
+    row[6] = -wgt * diff;
+    float invz = (float)(1.0 / Z);
+    float dI_dx = wgt * sobelScale * gx;
+    float dI_dy = wgt * sobelScale * gy;
+    float v0 = dI_dx * fx * invz;
+    float v1 = dI_dy * fy * invz;
+    float v2 = -(v0 * X + v1 * Y) * invz;
+    row[0] = v0; row[1] = v1; row[2] = v2;
+    row[3] = -Z * v1 + Y * v2;
+    row[4] = Z * v0 - X * v2;
+    row[5] = -Y * v0 + X * v1;
+}
+
+// ---- ... and of its per-iteration host logic (EF/Utils/RGBDOdometry.cpp:461-583)
+
+// element k (k < 27) of the combined system in the layout of the reference's 29-vector, from the element's two totals rounded to f32 as the reference's reductions
+// deliver them: lastA = A_rgb + w*w*A_icp, lastb = b_rgb + w*b_icp (:547-565); column 6 of a row is its b entry
+// (icp / rgb / icp_weight by reference: a caller's kernel-argument words are then fetched where they are used, as in the copies this replaces -- by value their scalar
+// loads moved ahead of the prologue's and the fused launch grew by 110 instructions)
+__device__ __forceinline__ double gn_system_entry(int k, float oi, float orr, const int& icp, const int& rgb, const float& icp_weight)
+{
+    const double wgt = icp_weight;
+    const double wa = wgt * wgt, wb = wgt;
+    const bool is_b = (k == 6) | (k == 12) | (k == 17) | (k == 21) | (k == 24) | (k == 26);
+    const double vi = (double)oi, vr = (double)orr;
+    return (icp && rgb) ? vr + (is_b ? wb : wa) * vi : (icp ? vi : vr);
+}
+// The diagnostics of an iteration, by lane t of a wave that is off the serial lane, from LDS: `counts` -- error norms and counts; `matrices` -- lastA / lastb / the
+// 2 x 29 sums, which describe the run's LAST iteration (getCovariance): 130 stores.  The last-block form writes the counts on every iteration, the level kernels both
+// parts on the last iteration of the final level only.
+__device__ __forceinline__ void gn_diagnostics(DevState* st, int t, const int (&s_res)[2], const float (&s_oi)[29], const float (&s_or)[29], const double (&s_sys)[27], int icp, int rgb,
+                                               bool counts, bool matrices)
+{
+    if (counts && t == 0) {
+        const int rgbSize = rgb ? s_res[0] : 0, sigma = rgb ? s_res[1] : 0;
+        st->rgb_count = rgbSize; st->rgb_sigma = sigma;
+        st->lastRGBError = (float)(sqrt((double)sigma) / (rgbSize == 0 ? 1 : rgbSize));
+        st->lastRGBCount = (float)rgbSize;
+        if (icp) { st->lastICPError = sqrtf(s_oi[27]) / s_oi[28]; st->lastICPCount = s_oi[28]; }
+    }
+    if (matrices) {
+        if (t < 29) { st->icp29[t] = s_oi[t]; st->rgb29[t] = s_or[t]; }
+        if (t < 36) {
+            const int i = t / 6, j = t - 6 * i, lo = i < j ? i : j, hi = i < j ? j : i;
+            st->lastA[t] = s_sys[lo * 7 - (lo * (lo - 1)) / 2 + (hi - lo)];
+        }
+        if (t < 6) st->lastb[t] = s_sys[t * 7 - (t * (t - 1)) / 2 + (6 - t)];
+    }
+}
+// a solved pose (gn_serial_lane's outputs) for whatever runs next from the state: the next launch, the end of the run, diagnostics ...
+__device__ __forceinline__ void gn_publish_pose(DevState* st, const double (&RRt)[16], const float (&Rc)[9], const float (&tc)[3], const float (&krk)[9], const float (&kt)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 16; k++) st->resultRt[k] = RRt[k];
+#pragma unroll
+    for (int k = 0; k < 9; k++) { st->Rcurr[k] = Rc[k]; st->krkinv[k] = krk[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { st->tcurr[k] = tc[k]; st->kt[k] = kt[k]; }
+}
+// ... and for the iteration about to run in this block, as the 24-float LDS block every form reads it from: Rcurr 9, tcurr 3, krkinv 9, kt 3
+__device__ __forceinline__ void pose_to_lds(float (&s_pose)[24], const float (&Rc)[9], const float (&tc)[3], const float (&krk)[9], const float (&kt)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 9; k++) { s_pose[k] = Rc[k]; s_pose[12 + k] = krk[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { s_pose[9 + k] = tc[k]; s_pose[21 + k] = kt[k]; }
+}
+
 // Every reduction body handles IT pixels per thread in four straight-line stages -- coalesced
 // loads of all IT pixels, projection, dependent gathers of all IT pixels, arithmetic -- so that a
 // thread has all of its memory requests in flight together.  (The first version used a rolled
@@ -580,13 +710,8 @@ __device__ __forceinline__ const float* gn_prologue(const DevState* __restrict__
     if (threadIdx.x < 27) {
         const int k = threadIdx.x;
         const double ti = acc_total(icp_acc, k), tr = acc_total(rgb_acc, k);
-        const float oi = g.icp ? (float)ti : 0.f, orr = g.rgb ? (float)tr : 0.f;   // rounded to f32 as the reference's reductions deliver them
-        // lastA = A_rgb + w*w*A_icp, lastb = b_rgb + w*b_icp (EF/Utils/RGBDOdometry.cpp:547-565); column 6 of a row is its b entry
-        const double wgt = g.icp_weight;
-        const double wa = wgt * wgt, wb = wgt;
-        const bool is_b = (k == 6) | (k == 12) | (k == 17) | (k == 21) | (k == 24) | (k == 26);
-        const double vi = (double)oi, vr = (double)orr;
-        s_psys[k] = (g.icp && g.rgb) ? vr + (is_b ? wb : wa) * vi : (g.icp ? vi : vr);
+        const float oi = g.icp ? (float)ti : 0.f, orr = g.rgb ? (float)tr : 0.f;
+        s_psys[k] = gn_system_entry(k, oi, orr, g.icp, g.rgb, g.icp_weight);
     }
     // the increment after iteration k - 2 (the run's start value for k == 1) and the run's constants: uniform addresses, fetched beside the totals
     const double* const rsrc = g.k == 1 ? st->resultRt : st->gnp_RRt[g.k & 1];
@@ -614,10 +739,7 @@ __device__ __forceinline__ const float* gn_prologue(const DevState* __restrict__
         }
 #endif
         gn_serial_lane(s_psys, g.icp, RRt, Rp, tp, g.nfx, g.nfy, g.ncx, g.ncy, g.ki, Rc, tc, krk, kt);
-#pragma unroll
-        for (int k = 0; k < 9; k++) { s_ppose[k] = Rc[k]; s_ppose[12 + k] = krk[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; k++) { s_ppose[9 + k] = tc[k]; s_ppose[21 + k] = kt[k]; }
+        pose_to_lds(s_ppose, Rc, tc, krk, kt);
         if (rrt_out) {
 #pragma unroll
             for (int k = 0; k < 12; k++) rrt_out[k] = RRt[k];
@@ -680,21 +802,7 @@ __device__ __forceinline__ void icp_body(int bid, int nblk, const DevState* __re
         // stage 4: row of the normal equations
         float row[7] = {0, 0, 0, 0, 0, 0, 0};
         bool found = false;
-        if (inb) {
-            v3 ncurr_g = mulp(Rcurr, ncurr);
-            float dist = norm(vprev - vcurr_g);
-            float sine = norm(cross(ncurr_g, nprev));
-            found = (sine < angleThres && dist <= distThres && !(ncurr.x != ncurr.x) && !(nprev.x != nprev.x));
-            if (found) {
-                v3 s_cp = mulp(Rprev_inv, vcurr_g - tp);
-                v3 d_cp = mulp(Rprev_inv, vprev - tp);
-                v3 n_cp = mulp(Rprev_inv, nprev);
-                v3 c = cross(s_cp, n_cp);
-                row[0] = n_cp.x; row[1] = n_cp.y; row[2] = n_cp.z;
-                row[3] = c.x; row[4] = c.y; row[5] = c.z;
-                row[6] = dot(n_cp, s_cp - d_cp);
-            }
-        }
+        if (inb) found = icp_pair(row, Rcurr, Rprev_inv, tp, vcurr_g, ncurr, vprev, nprev, distThres, angleThres);
         products7<0>(row, found, acc);
         vcurr = vnext; ncurr = nnext; i = inext;
     }
@@ -722,7 +830,6 @@ __device__ __forceinline__ void residual_body(int bid, int nblk, const DevState*
                                               float maxDepthDelta, int w, int h, int* __restrict__ partials, int* __restrict__ res_total = nullptr,
                                               const GnPro* pro = nullptr, double* __restrict__ rrt_out = nullptr)
 {
-    const int border = 16;
     const int N = w * h;
     // stage 1 of a round: own-pixel tests (4x4 non-zero block, gradient gate) and depth -- nothing of it depends on the pose
     struct Own { bool cand[RED_IT]; int kidx[RED_IT]; float d1[RED_IT]; uint8_t ni[RED_IT]; };
@@ -734,23 +841,11 @@ __device__ __forceinline__ void residual_body(int bid, int nblk, const DevState*
             bool in = k < N;
             int kk2 = in ? k : 0;
             int i = kk2 / w, j0 = kk2 - i * w;
-            bool ok = in && i >= border && i < h - border && j0 >= border && j0 < w - border && j0 < w - 5 && i < h - 1;
-            // inside the 16-px border the 4x4 block [i-2,i+2) x [j0-2,j0+2) is always in the image
-            int ci = ok ? i : 16, cj = ok ? j0 : 16;
-            // "all 16 pixels non-zero": four unaligned 4-byte loads issued together and a has-zero-byte test per row (the byte-by-byte
-            // form compiled to 16 dependent loads, each behind the previous one's branch: ~2 us of every residual launch)
-            bool valid = true;
-#pragma unroll
-            for (int a = -2; a < 2; a++) {
-                uint32_t r4;
-                __builtin_memcpy(&r4, nextImage + (ci + a) * w + cj - 2, 4);
-                valid = valid & (((r4 - 0x01010101u) & ~r4 & 0x80808080u) == 0u);
-            }
+            const bool ok = own_pixel_ok<true>(nextImage, w, h, in, i, j0);
             short valx = dIdx[kk2], valy = dIdy[kk2];
-            float mTwo = (float)((valx * valx) + (valy * valy));
             o.d1[u] = nextDepth[kk2];
             o.ni[u] = nextImage[kk2];
-            o.cand[u] = ok & valid & (mTwo >= minScale) & !(o.d1[u] != o.d1[u]);   // (bitwise: no load of this stage may hide behind a branch)
+            o.cand[u] = ok & rgb_grad_gate(valx, valy, minScale) & !(o.d1[u] != o.d1[u]);   // (bitwise: no load of this stage may hide behind a branch)
         }
     };
     const int base0 = bid * (RED_THREADS * RED_IT) + threadIdx.x, stride = nblk * RED_THREADS * RED_IT;
@@ -772,11 +867,8 @@ __device__ __forceinline__ void residual_body(int bid, int nblk, const DevState*
 #pragma unroll
         for (int u = 0; u < RED_IT; u++) {   // stage 2: warp into the last image
             int i = own.kidx[u] / w, j0 = own.kidx[u] - i * w;
-            int y = i, x = j0;
-            td1[u] = (float)(own.d1[u] * (krk[6] * x + krk[7] * y + krk[8]) + kt2);
-            int u0 = f2i_rn((own.d1[u] * (krk[0] * x + krk[1] * y + krk[2]) + kt0) / td1[u]);
-            int v0 = f2i_rn((own.d1[u] * (krk[3] * x + krk[4] * y + krk[5]) + kt1) / td1[u]);
-            own.cand[u] = own.cand[u] & ((u0 >= 0) & (v0 >= 0) & (u0 < w) & (v0 < h));
+            int u0, v0;
+            own.cand[u] = own.cand[u] & rgb_warp(krk, kt0, kt1, kt2, own.d1[u], j0, i, w, h, td1[u], u0, v0);
             gj[u] = own.cand[u] ? v0 * w + u0 : 0;
         }
         float d0[RED_IT];
@@ -786,7 +878,7 @@ __device__ __forceinline__ void residual_body(int bid, int nblk, const DevState*
 #pragma unroll
         for (int u = 0; u < RED_IT; u++) {   // stage 4
             Corres8 c;
-            const bool hit = own.cand[u] & (d0[u] > 0) & (fabsf(td1[u] - d0[u]) <= maxDepthDelta) & (li[u] != 0);
+            const bool hit = rgb_warp_hit(own.cand[u], d0[u], td1[u], maxDepthDelta, li[u] != 0);
             const int v0 = gj[u] / w, u0 = gj[u] - v0 * w;
             const float diff = (float)own.ni[u] - (float)li[u];
             c.zx = hit ? (short)u0 : (short)-1; c.zy = hit ? (short)v0 : (short)-1;
@@ -855,11 +947,9 @@ __device__ __forceinline__ int residual_cand_body(int bid, int nblk, const DevSt
     while (t < n) {
         // stage 2: warp into the last image
         const int i = pix / w, j0 = pix - i * w;
-        const int y = i, x = j0;
-        const float td1 = (float)(d1 * (krk[6] * x + krk[7] * y + krk[8]) + kt2);
-        const int u0 = f2i_rn((d1 * (krk[0] * x + krk[1] * y + krk[2]) + kt0) / td1);
-        const int v0 = f2i_rn((d1 * (krk[3] * x + krk[4] * y + krk[5]) + kt1) / td1);
-        const bool c0 = !(d1 != d1) & ((u0 >= 0) & (v0 >= 0) & (u0 < w) & (v0 < h));
+        float td1;
+        int u0, v0;
+        const bool c0 = !(d1 != d1) & rgb_warp(krk, kt0, kt1, kt2, d1, j0, i, w, h, td1, u0, v0);
         const int gj = c0 ? v0 * w + u0 : 0;
         // stage 3: gathers; behind them the next round's own pixel and the entry of the round after (past the count: pixel 0 / entry 0, dropped)
         const float d0 = lastDepth[gj];
@@ -871,7 +961,7 @@ __device__ __forceinline__ int residual_cand_body(int bid, int nblk, const DevSt
         const CandEntry e2 = cand[tnn < N ? tnn : 0];
         // stage 4
         Corres8 c;
-        const bool hit = c0 & (d0 > 0) & (fabsf(td1 - d0) <= maxDepthDelta) & (li != 0);
+        const bool hit = rgb_warp_hit(c0, d0, td1, maxDepthDelta, li != 0);
         const float diff = (float)ni - (float)li;
         c.zx = hit ? (short)u0 : (short)-1; c.zy = hit ? (short)v0 : (short)-1;
         c.diff = hit ? diff : 0.f;
@@ -978,12 +1068,7 @@ __device__ __forceinline__ void rgb_fused_step(int bid, int n_wave, Corres8* cor
     // (d) every block that is here has seen all G arrivals: the totals are complete and every record of [0, n) is in memory
     unsigned int chunk = s_chunk;
     if (chunk >= (unsigned int)rgb_chunk_count(n)) return;   // nothing left (uniform over the block)
-    float sigma;
-    {   // as rgb_step_cand_body forms it
-        const int cnt = __hip_atomic_load(&res_total[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), sg = __hip_atomic_load(&res_total[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        float q = (float)sg / (float)cnt;
-        sigma = (float)sqrt((double)((q == 0) ? 1 : cnt));
-    }
+    const float sigma = rgb_sigma(__hip_atomic_load(&res_total[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(&res_total[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     double acc[29];
 #pragma unroll
     for (int k = 0; k < 29; k++) acc[k] = 0.0;
@@ -1017,22 +1102,7 @@ __device__ __forceinline__ void rgb_fused_step(int bid, int n_wave, Corres8* cor
         for (int u = 0; u < RGB_CHUNK_IT; u++) {
             float row[7] = {0, 0, 0, 0, 0, 0, 0};
             bool found = c[u].zx >= 0;
-            if (found) {
-                float wgt = sigma + fabsf(c[u].diff);
-                wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
-                if (sigma == -1) wgt = 1;
-                row[6] = -wgt * c[u].diff;
-                float invz = (float)(1.0 / Z[u]);
-                float dI_dx = wgt * f.sobelScale * e[u].gx;
-                float dI_dy = wgt * f.sobelScale * e[u].gy;
-                float v0 = dI_dx * fx * invz;
-                float v1 = dI_dy * fy * invz;
-                float v2 = -(v0 * X[u] + v1 * Y[u]) * invz;
-                row[0] = v0; row[1] = v1; row[2] = v2;
-                row[3] = -Z[u] * v1 + Y[u] * v2;
-                row[4] = Z[u] * v0 - X[u] * v2;
-                row[5] = -Y[u] * v0 + X[u] * v1;
-            }
+            if (found) rgb_row(row, sigma, c[u].diff, e[u].gx, e[u].gy, X[u], Y[u], Z[u], fx, fy, f.sobelScale);
             products7<1>(row, found, acc);
         }
         __syncthreads();
@@ -1127,11 +1197,8 @@ __device__ __forceinline__ void rgb_step_body(int bid, int nblk, const Corres8* 
         if (!in) c[u].zx = -1;
     }
     float sigma = sigma_explicit;
-    if (res_total) {
-        int cnt = res_total[0], sg = res_total[1];
-        float q = (float)sg / (float)cnt;
-        sigma = (float)sqrt((double)((q == 0) ? 1 : cnt));
-    } else if (res_partials) {
+    if (res_total) sigma = rgb_sigma(res_total[0], res_total[1]);
+    else if (res_partials) {
         __shared__ int s_cs[2];
         if (threadIdx.x < 64) {
             int cnt = 0, sg = 0;
@@ -1147,9 +1214,7 @@ __device__ __forceinline__ void rgb_step_body(int bid, int nblk, const Corres8* 
             if (threadIdx.x == 0) { s_cs[0] = cnt; s_cs[1] = sg; }
         }
         __syncthreads();
-        int cnt = s_cs[0], sg = s_cs[1];
-        float q = (float)sg / (float)cnt;
-        sigma = (float)sqrt((double)((q == 0) ? 1 : cnt));
+        sigma = rgb_sigma(s_cs[0], s_cs[1]);
     }
 #ifdef IFX_STAMPS
     g_ts[0] = clock64();
@@ -1181,22 +1246,7 @@ __device__ __forceinline__ void rgb_step_body(int bid, int nblk, const Corres8* 
         for (int u = 0; u < RED_IT_RGB; u++) {
             float row[7] = {0, 0, 0, 0, 0, 0, 0};
             bool found = c[u].zx >= 0;
-            if (found) {
-                float wgt = sigma + fabsf(c[u].diff);
-                wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
-                if (sigma == -1) wgt = 1;
-                row[6] = -wgt * c[u].diff;
-                float invz = (float)(1.0 / Z[u]);
-                float dI_dx = wgt * sobelScale * gx[u];
-                float dI_dy = wgt * sobelScale * gy[u];
-                float v0 = dI_dx * fx * invz;
-                float v1 = dI_dy * fy * invz;
-                float v2 = -(v0 * X[u] + v1 * Y[u]) * invz;
-                row[0] = v0; row[1] = v1; row[2] = v2;
-                row[3] = -Z[u] * v1 + Y[u] * v2;
-                row[4] = Z[u] * v0 - X[u] * v2;
-                row[5] = -Y[u] * v0 + X[u] * v1;
-            }
+            if (found) rgb_row(row, sigma, c[u].diff, gx[u], gy[u], X[u], Y[u], Z[u], fx, fy, sobelScale);
             products7<1>(row, found, acc);
         }
 #pragma unroll
@@ -1237,12 +1287,7 @@ __device__ __forceinline__ void rgb_step_cand_body(int bid, int nblk, const Corr
     if (bid * (RED_THREADS * RED_IT_RGB) >= n) return;   // (uniform over the block)
 #pragma unroll
     for (int u = 0; u < RED_IT_RGB; u++) if (base0 + u * RED_THREADS >= n) c[u].zx = -1;   // (past the count: a record of another frame or none at all)
-    float sigma;
-    {
-        int cnt = res_total[0], sg = res_total[1];
-        float q = (float)sg / (float)cnt;
-        sigma = (float)sqrt((double)((q == 0) ? 1 : cnt));
-    }
+    const float sigma = rgb_sigma(res_total[0], res_total[1]);
     double acc[29];
 #pragma unroll
     for (int k = 0; k < 29; k++) acc[k] = 0.0;
@@ -1270,22 +1315,7 @@ __device__ __forceinline__ void rgb_step_cand_body(int bid, int nblk, const Corr
         for (int u = 0; u < RED_IT_RGB; u++) {
             float row[7] = {0, 0, 0, 0, 0, 0, 0};
             bool found = c[u].zx >= 0;
-            if (found) {
-                float wgt = sigma + fabsf(c[u].diff);
-                wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
-                if (sigma == -1) wgt = 1;
-                row[6] = -wgt * c[u].diff;
-                float invz = (float)(1.0 / Z[u]);
-                float dI_dx = wgt * sobelScale * e[u].gx;
-                float dI_dy = wgt * sobelScale * e[u].gy;
-                float v0 = dI_dx * fx * invz;
-                float v1 = dI_dy * fy * invz;
-                float v2 = -(v0 * X[u] + v1 * Y[u]) * invz;
-                row[0] = v0; row[1] = v1; row[2] = v2;
-                row[3] = -Z[u] * v1 + Y[u] * v2;
-                row[4] = Z[u] * v0 - X[u] * v2;
-                row[5] = -Y[u] * v0 + X[u] * v1;
-            }
+            if (found) rgb_row(row, sigma, c[u].diff, e[u].gx, e[u].gy, X[u], Y[u], Z[u], fx, fy, sobelScale);
             products7<1>(row, found, acc);
         }
 #pragma unroll
@@ -2003,14 +2033,7 @@ __device__ __forceinline__ void gn_solve_block(DevState* st, double* __restrict_
         range_note(st, icp && range_exceeded7(0, k, ti), rgb && range_exceeded7(1, k, tr));
         const float oi = icp ? (float)ti : 0.f, orr = rgb ? (float)tr : 0.f;
         s_oi[k] = oi; s_or[k] = orr;
-        if (k < 27) {
-            // lastA = A_rgb + w*w*A_icp, lastb = b_rgb + w*b_icp (EF/Utils/RGBDOdometry.cpp:547-565); column 6 of a row is its b entry
-            const double wgt = icp_weight;
-            const double wa = wgt * wgt, wb = wgt;
-            const bool is_b = (k == 6) | (k == 12) | (k == 17) | (k == 21) | (k == 24) | (k == 26);
-            const double vi = (double)oi, vr = (double)orr;
-            s_sys[k] = (icp && rgb) ? vr + (is_b ? wb : wa) * vi : (icp ? vi : vr);
-        }
+        if (k < 27) s_sys[k] = gn_system_entry(k, oi, orr, icp, rgb, icp_weight);
     }
     if (res_total) {   // totals accumulated by the residual pass; re-armed (zeroed) for the next iteration
         if (threadIdx.x == 64) {
@@ -2039,35 +2062,14 @@ __device__ __forceinline__ void gn_solve_block(DevState* st, double* __restrict_
     long long ts_c = clock64();
 #endif
     if (threadIdx.x >= 64 && threadIdx.x < 128) {   // ---- wave 1: diagnostics, off the serial lane
-        const int t = threadIdx.x - 64;
-        if (t == 0) {
-            const int rgbSize = rgb ? s_res[0] : 0, sigma = rgb ? s_res[1] : 0;
-            st->rgb_count = rgbSize; st->rgb_sigma = sigma;
-            st->lastRGBError = (float)(sqrt((double)sigma) / (rgbSize == 0 ? 1 : rgbSize));
-            st->lastRGBCount = (float)rgbSize;
-            if (icp) { st->lastICPError = sqrtf(s_oi[27]) / s_oi[28]; st->lastICPCount = s_oi[28]; }
-        }
-        if (final_iter) {   // lastA / lastb / the 2 x 29 sums describe the run's LAST iteration (getCovariance, diagnostics)
-            if (t < 29) { st->icp29[t] = s_oi[t]; st->rgb29[t] = s_or[t]; }
-            if (t < 36) {
-                const int i = t / 6, j = t - 6 * i, lo = i < j ? i : j, hi = i < j ? j : i;
-                st->lastA[t] = s_sys[lo * 7 - (lo * (lo - 1)) / 2 + (hi - lo)];
-            }
-            if (t < 6) st->lastb[t] = s_sys[t * 7 - (t * (t - 1)) / 2 + (6 - t)];
-        }
+        gn_diagnostics(st, threadIdx.x - 64, s_res, s_oi, s_or, s_sys, icp, rgb, true, final_iter != 0);
         return;
     }
     if (threadIdx.x != 0) return;
     // ---- serial part on one lane.  Every input is in registers or LDS and every output is stored once at the end.
     float Rc[9], tc[3], krk[9], kt[3];
     gn_serial_lane(s_sys, icp, RRt, Rp, tp, nfx, nfy, ncx, ncy, ki, Rc, tc, krk, kt);
-    // ---- stores
-#pragma unroll
-    for (int k = 0; k < 16; k++) st->resultRt[k] = RRt[k];
-#pragma unroll
-    for (int k = 0; k < 9; k++) { st->Rcurr[k] = Rc[k]; st->krkinv[k] = krk[k]; }
-#pragma unroll
-    for (int k = 0; k < 3; k++) { st->tcurr[k] = tc[k]; st->kt[k] = kt[k]; }
+    gn_publish_pose(st, RRt, Rc, tc, krk, kt);
     // the run's last iteration also ends the run (:587-603, pose write-back, velocity weighting, view-list decision): the same lane, one launch less per frame
     if (end_run) track_end_vals(st, rgb, 1, Rc, tc, Rp, tp, weight_mult, commit, lctr);
 #ifdef IFX_STAMPS
@@ -2220,23 +2222,75 @@ struct LevelArgs {
 // The level on ONE workgroup (enqueued behind every k_gn_level launch; returns at its first instruction unless a meeting of that launch failed): the bodies of the two-launch form with a grid of one, the sums through the single-buffer
 // accumulator rows (DevState::gn_acc / gn_res, which nothing else uses while this kernel runs), agent-scope fences between the phases (the block reads back what it
 // wrote: correspondence records, residual totals).  Same rows, same exact sums, same solve: the level's result is the one the meetings would have produced.
+// What a level kernel keeps in LDS across the iterations of its level and hands to the tail they share
+struct GnLevelLds {
+    double RRt[16];          // the running increment
+    double sys[27];          // combined system: index = position in the reference's 29-vector
+    float pose[24];          // Rcurr 9, tcurr 3, krkinv 9, kt 3 of the iteration about to run
+    float oi[29], orr[29];   // the 2 x 29 totals as f32
+    int res[2];              // the residual totals
+};
+// the pose the level starts from
+__device__ __forceinline__ void gn_level_lds_begin(GnLevelLds& s, const DevState* st)
+{
+    const int tid = threadIdx.x;
+    if (tid < 9) { s.pose[tid] = st->Rcurr[tid]; s.pose[12 + tid] = st->krkinv[tid]; }
+    if (tid < 3) { s.pose[9 + tid] = st->tcurr[tid]; s.pose[21 + tid] = st->kt[tid]; }
+    if (tid < 16) s.RRt[tid] = st->resultRt[tid];
+}
+// The end of an iteration of a level kernel, behind its second meeting: totals -> combined system -> diagnostics -> serial lane -> the next iteration's pose in LDS ->
+// the level's result in the state.  Every block solves -- the same totals give the same bits: no broadcast of the pose, no third meeting -- and block 0 alone
+// publishes: the diagnostics of the run's last iteration (wave 1, off the serial lane) and, behind the level's last solve, the pose with the mark that the level is
+// done.  `bid`: the block; the one-workgroup fallback is block 0 of a grid of one, where every meeting is trivially met.  SINGLE: the accumulator rows are the
+// single-buffered ones of the fallback, cleared behind the read (the persistent kernel's are double-buffered by parity; its block 0 clears a buffer one meeting after its
+// last reader).  rcnt / rsig: the residual totals, on thread 64 at least.
+// (ICP + photometric term, the reference's default: any other weighting takes the two-launch form, which also carries the pivoted solve)
+template <bool SINGLE>
+__device__ __forceinline__ void gn_level_tail(DevState* st, const LevelArgs& a, GnLevelLds& s, int bid, bool last_it, double* icp_acc, double* rgb_acc, int rcnt, int rsig,
+                                              const float (&Rp)[9], const float (&tpv)[3])
+{
+    const int tid = threadIdx.x;
+    if (tid < 29) {
+        const double ti = acc_total(icp_acc, tid), tr = acc_total(rgb_acc, tid);
+        if (SINGLE) { acc_clear(icp_acc, tid); acc_clear(rgb_acc, tid); }
+        if (bid == 0) range_note(st, range_exceeded7(0, tid, ti), range_exceeded7(1, tid, tr));
+        const float oi = (float)ti, orr = (float)tr;
+        s.oi[tid] = oi; s.orr[tid] = orr;
+        if (tid < 27) s.sys[tid] = gn_system_entry(tid, oi, orr, 1, 1, a.icp_weight);
+    }
+    if (tid == 64) { s.res[0] = rcnt; s.res[1] = rsig; }
+    __syncthreads();
+    if (bid == 0 && last_it && a.final_level && tid >= 64 && tid < 128) gn_diagnostics(st, tid - 64, s.res, s.oi, s.orr, s.sys, 1, 1, true, true);
+    if (tid == 0 && !(last_it && bid != 0)) {   // (the level's last solve is only block 0's to publish)
+        double RRt[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) RRt[k] = s.RRt[k];
+        float Rc[9], tcn[3], krkn[9], ktn[3];
+        if (last_it) gn_serial_lane(s.sys, 1, RRt, Rp, tpv, a.nfx, a.nfy, a.ncx, a.ncy, a.ki_next, Rc, tcn, krkn, ktn);
+        else gn_serial_lane(s.sys, 1, RRt, Rp, tpv, a.fx, a.fy, a.cx, a.cy, a.ki_same, Rc, tcn, krkn, ktn);
+#pragma unroll
+        for (int k = 0; k < 12; k++) s.RRt[k] = RRt[k];
+        pose_to_lds(s.pose, Rc, tcn, krkn, ktn);
+        if (bid == 0 && last_it) {   // the level's result for whatever runs next (the next level's launch, the end of the run, diagnostics)
+            gn_publish_pose(st, RRt, Rc, tcn, krkn, ktn);
+            if (a.final_level) track_end_vals(st, 1, 1, Rc, tcn, Rp, tpv, a.weight_mult, a.commit, a.lctr);
+            st->gn_done_seq = a.level + 1;
+        }
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(RED_THREADS) void k_gn_level_solo(DevState* st, LevelArgs a)
 {
     if (st->gn_done_seq == a.level + 1) return;   // the meetings happened (every healthy launch): nothing to do
-    __shared__ float s_pose[24];
-    __shared__ double s_RRt[16];
-    __shared__ double s_sys[27];
-    __shared__ float s_oi[29], s_or[29];
-    __shared__ int s_res[2];
+    __shared__ GnLevelLds s;
     const int tid = threadIdx.x;
     float Rp[9], tpv[3];
 #pragma unroll
     for (int k = 0; k < 9; k++) Rp[k] = st->Rprev[k];
 #pragma unroll
     for (int k = 0; k < 3; k++) tpv[k] = st->tprev[k];
-    if (tid < 9) { s_pose[tid] = st->Rcurr[tid]; s_pose[12 + tid] = st->krkinv[tid]; }
-    if (tid < 3) { s_pose[9 + tid] = st->tcurr[tid]; s_pose[21 + tid] = st->kt[tid]; }
-    if (tid < 16) s_RRt[tid] = st->resultRt[tid];
+    gn_level_lds_begin(s, st);
     if (tid == 0) atomicAdd(&st->gn_timeout, 1);
     __syncthreads();
     double* const icp_acc = st->gn_acc, * const rgb_acc = st->gn_acc + IFX_ACC_REPL * IFX_ACC_STRIDE;
@@ -2246,9 +2300,9 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level_solo(DevState* st, Lev
         IcpArgs ia;
         ResArgs ra;
 #pragma unroll
-        for (int k = 0; k < 9; k++) { ia.Rcurr[k] = s_pose[k]; ia.Rprev_inv[k] = st->Rprev_inv[k]; ra.krkinv[k] = s_pose[12 + k]; }
+        for (int k = 0; k < 9; k++) { ia.Rcurr[k] = s.pose[k]; ia.Rprev_inv[k] = st->Rprev_inv[k]; ra.krkinv[k] = s.pose[12 + k]; }
 #pragma unroll
-        for (int k = 0; k < 3; k++) { ia.tcurr[k] = s_pose[9 + k]; ia.tprev[k] = tpv[k]; ra.kt[k] = s_pose[21 + k]; }
+        for (int k = 0; k < 3; k++) { ia.tcurr[k] = s.pose[9 + k]; ia.tprev[k] = tpv[k]; ra.kt[k] = s.pose[21 + k]; }
         icp_body<false, false>(0, 1, nullptr, ia, a.vmap_curr, a.nmap_curr, a.vmap_prev, a.nmap_prev, a.fx, a.fy, a.cx, a.cy, a.distThres, a.angleThres, a.w, a.h, icp_acc);
         residual_body<false>(0, 1, nullptr, ra, a.minScale, a.dIdx, a.dIdy, a.lastDepth, a.nextDepth, a.lastImage, a.nextImage, corres, a.maxDepthDelta, a.w, a.h, st->gn_pad, gres);
         __threadfence();
@@ -2256,69 +2310,14 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level_solo(DevState* st, Lev
         rgb_step_body(0, 1, corres, 0.f, nullptr, 0, a.cloud, a.fx, a.fy, a.dIdx, a.dIdy, a.sobelScale, a.w, a.h, rgb_acc, gres);
         __threadfence();
         __syncthreads();
-        const bool last_it = it == a.iters - 1;
-        if (tid < 29) {
-            const double ti = acc_total(icp_acc, tid), tr = acc_total(rgb_acc, tid);
-            acc_clear(icp_acc, tid);
-            acc_clear(rgb_acc, tid);
-            range_note(st, range_exceeded7(0, tid, ti), range_exceeded7(1, tid, tr));
-            const float oi = (float)ti, orr = (float)tr;
-            s_oi[tid] = oi; s_or[tid] = orr;
-            if (tid < 27) {
-                const double wgt = a.icp_weight;
-                const double wa = wgt * wgt, wb = wgt;
-                const bool is_b = (tid == 6) | (tid == 12) | (tid == 17) | (tid == 21) | (tid == 24) | (tid == 26);
-                s_sys[tid] = (double)orr + (is_b ? wb : wa) * (double)oi;
-            }
-        }
-        if (tid == 64) {
-            s_res[0] = __hip_atomic_load(&gres[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_res[1] = __hip_atomic_load(&gres[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int rcnt = 0, rsig = 0;
+        if (tid == 64) {   // the residual totals, re-armed (zeroed) for the next iteration
+            rcnt = __hip_atomic_load(&gres[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            rsig = __hip_atomic_load(&gres[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&gres[0], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&gres[1], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        __syncthreads();
-        if (last_it && a.final_level && tid >= 64 && tid < 128) {   // diagnostics of the run's last iteration
-            const int t = tid - 64;
-            if (t == 0) {
-                const int rgbSize = s_res[0], sigma = s_res[1];
-                st->rgb_count = rgbSize; st->rgb_sigma = sigma;
-                st->lastRGBError = (float)(sqrt((double)sigma) / (rgbSize == 0 ? 1 : rgbSize));
-                st->lastRGBCount = (float)rgbSize;
-                st->lastICPError = sqrtf(s_oi[27]) / s_oi[28]; st->lastICPCount = s_oi[28];
-            }
-            if (t < 29) { st->icp29[t] = s_oi[t]; st->rgb29[t] = s_or[t]; }
-            if (t < 36) {
-                const int i = t / 6, j = t - 6 * i, lo = i < j ? i : j, hi = i < j ? j : i;
-                st->lastA[t] = s_sys[lo * 7 - (lo * (lo - 1)) / 2 + (hi - lo)];
-            }
-            if (t < 6) st->lastb[t] = s_sys[t * 7 - (t * (t - 1)) / 2 + (6 - t)];
-        }
-        if (tid == 0) {
-            double RRt[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) RRt[k] = s_RRt[k];
-            float Rc[9], tcn[3], krkn[9], ktn[3];
-            if (last_it) gn_serial_lane(s_sys, 1, RRt, Rp, tpv, a.nfx, a.nfy, a.ncx, a.ncy, a.ki_next, Rc, tcn, krkn, ktn);
-            else gn_serial_lane(s_sys, 1, RRt, Rp, tpv, a.fx, a.fy, a.cx, a.cy, a.ki_same, Rc, tcn, krkn, ktn);
-#pragma unroll
-            for (int k = 0; k < 12; k++) s_RRt[k] = RRt[k];
-#pragma unroll
-            for (int k = 0; k < 9; k++) { s_pose[k] = Rc[k]; s_pose[12 + k] = krkn[k]; }
-#pragma unroll
-            for (int k = 0; k < 3; k++) { s_pose[9 + k] = tcn[k]; s_pose[21 + k] = ktn[k]; }
-            if (last_it) {
-#pragma unroll
-                for (int k = 0; k < 16; k++) st->resultRt[k] = RRt[k];
-#pragma unroll
-                for (int k = 0; k < 9; k++) { st->Rcurr[k] = Rc[k]; st->krkinv[k] = krkn[k]; }
-#pragma unroll
-                for (int k = 0; k < 3; k++) { st->tcurr[k] = tcn[k]; st->kt[k] = ktn[k]; }
-                if (a.final_level) track_end_vals(st, 1, 1, Rc, tcn, Rp, tpv, a.weight_mult, a.commit, a.lctr);
-                st->gn_done_seq = a.level + 1;
-            }
-        }
-        __syncthreads();
+        gn_level_tail<true>(st, a, s, 0, it == a.iters - 1, icp_acc, rgb_acc, rcnt, rsig, Rp, tpv);
     }
 }
 
@@ -2366,14 +2365,9 @@ __device__ __forceinline__ bool gn_grid_barrier(unsigned int* bar, int k, int nb
 template <int PX>
 __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArgs a)
 {
-    // (ICP + photometric term, the reference's default: any other weighting takes the two-launch form, which also carries the pivoted solve)
-    constexpr int ICP = 1, RGB = 1;
+    constexpr int ICP = 1, RGB = 1;   // (see gn_level_tail)
     const int N = a.w * a.h, nb = gridDim.x, bid = blockIdx.x, tid = threadIdx.x;
-    __shared__ float s_pose[24];      // Rcurr 9, tcurr 3, krkinv 9, kt 3 of the iteration about to run
-    __shared__ double s_RRt[16];
-    __shared__ double s_sys[27];
-    __shared__ float s_oi[29], s_or[29];
-    __shared__ int s_res[2];
+    __shared__ GnLevelLds s;
     __shared__ int s_cs[RED_WAVES][2];
     // ---- state of the run (constant over the level) and the pose the level starts from
     float Rprev_inv[9], Rp[9], tpv[3];
@@ -2382,16 +2376,13 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArg
 #pragma unroll
     for (int k = 0; k < 3; k++) tpv[k] = st->tprev[k];
     const v3 tp = v3m(tpv[0], tpv[1], tpv[2]);
-    if (tid < 9) { s_pose[tid] = st->Rcurr[tid]; s_pose[12 + tid] = st->krkinv[tid]; }
-    if (tid < 3) { s_pose[9 + tid] = st->tcurr[tid]; s_pose[21 + tid] = st->kt[tid]; }
-    if (tid < 16) s_RRt[tid] = st->resultRt[tid];
+    gn_level_lds_begin(s, st);
     // ---- per-pixel constants: pixel u of a thread is (u * nb + bid) * 256 + tid (coalesced across lanes)
     v3 vcurr[PX], ncurr[PX];
     float d1[PX], nif[PX];
     short gx[PX], gy[PX];
     bool cand0[PX];
     int xy[PX];
-    const int border = 16;
 #pragma unroll
     for (int u = 0; u < PX; u++) {
         const int p = (u * nb + bid) * RED_THREADS + tid;
@@ -2402,21 +2393,12 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArg
         vcurr[u] = v3m(a.vmap_curr[pp], a.vmap_curr[pp + N], a.vmap_curr[pp + 2 * N]);
         ncurr[u] = v3m(a.nmap_curr[pp], a.nmap_curr[pp + N], a.nmap_curr[pp + 2 * N]);
         if (!in) vcurr[u].x = qnan_f();
-        // RGBResidual's own-pixel tests (EF/Cuda/reduce.cu:739-790): 16-px border, 4x4 non-zero block, gradient gate, valid depth
-        const bool ok = in && i >= border && i < a.h - border && j0 >= border && j0 < a.w - border && j0 < a.w - 5 && i < a.h - 1;
-        const int ci = ok ? i : 16, cj = ok ? j0 : 16;
-        bool valid = true;
-#pragma unroll
-        for (int q = -2; q < 2; q++) {
-            uint32_t r4;
-            __builtin_memcpy(&r4, a.nextImage + (ci + q) * a.w + cj - 2, 4);
-            valid = valid & (((r4 - 0x01010101u) & ~r4 & 0x80808080u) == 0u);
-        }
+        // RGBResidual's own-pixel tests: border and 4x4 non-zero block, gradient gate, valid depth
+        const bool ok = own_pixel_ok<true>(a.nextImage, a.w, a.h, in, i, j0);
         gx[u] = a.dIdx[pp]; gy[u] = a.dIdy[pp];
-        const float mTwo = (float)((gx[u] * gx[u]) + (gy[u] * gy[u]));
         d1[u] = a.nextDepth[pp];
         nif[u] = (float)a.nextImage[pp];
-        cand0[u] = ok & valid & (mTwo >= a.minScale) & !(d1[u] != d1[u]);
+        cand0[u] = ok & rgb_grad_gate(gx[u], gy[u], a.minScale) & !(d1[u] != d1[u]);
     }
     __syncthreads();
     unsigned int* bar = &st->gn_bar[a.level * GN_BAR_SUB * 16];
@@ -2428,9 +2410,9 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArg
         int* const gres = st->gn_res2 + par * 16;
         float Rcurr[9], krk[9];
 #pragma unroll
-        for (int k = 0; k < 9; k++) { Rcurr[k] = s_pose[k]; krk[k] = s_pose[12 + k]; }
-        const v3 tc = v3m(s_pose[9], s_pose[10], s_pose[11]);
-        const float kt0 = s_pose[21], kt1 = s_pose[22], kt2 = s_pose[23];
+        for (int k = 0; k < 9; k++) { Rcurr[k] = s.pose[k]; krk[k] = s.pose[12 + k]; }
+        const v3 tc = v3m(s.pose[9], s.pose[10], s.pose[11]);
+        const float kt0 = s.pose[21], kt1 = s.pose[22], kt2 = s.pose[23];
         // ---- phase A: projections, then every gather of the iteration in one batch
         v3 vcurr_g[PX], vprev[PX], nprev[PX];
         bool inb[PX], cand[PX];
@@ -2446,11 +2428,8 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArg
             inb[u] = !(vcurr[u].x != vcurr[u].x) && !(ux < 0 || uy < 0 || ux >= a.w || uy >= a.h || vcurr_cp.z < 0);
             const int j = inb[u] ? uy * a.w + ux : 0;
             // RGBResidual warp, EF/Cuda/reduce.cu:791-810
-            const int y = xy[u] >> 16, x = xy[u] & 0xFFFF;
-            td1[u] = (float)(d1[u] * (krk[6] * x + krk[7] * y + krk[8]) + kt2);
-            const int u0 = f2i_rn((d1[u] * (krk[0] * x + krk[1] * y + krk[2]) + kt0) / td1[u]);
-            const int v0 = f2i_rn((d1[u] * (krk[3] * x + krk[4] * y + krk[5]) + kt1) / td1[u]);
-            cand[u] = cand0[u] & ((u0 >= 0) & (v0 >= 0) & (u0 < a.w) & (v0 < a.h));
+            int u0, v0;
+            cand[u] = cand0[u] & rgb_warp(krk, kt0, kt1, kt2, d1[u], xy[u] & 0xFFFF, xy[u] >> 16, a.w, a.h, td1[u], u0, v0);
             gj[u] = cand[u] ? v0 * a.w + u0 : 0;
             vprev[u] = v3m(a.vmap_prev[j], a.vmap_prev[j + N], a.vmap_prev[j + 2 * N]);
             nprev[u] = v3m(a.nmap_prev[j], a.nmap_prev[j + N], a.nmap_prev[j + 2 * N]);
@@ -2469,24 +2448,9 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArg
         for (int u = 0; u < PX; u++) {
             float row[7] = {0, 0, 0, 0, 0, 0, 0};
             bool found = false;
-            if (ICP && inb[u]) {   // EF/Cuda/reduce.cu:302-387
-                const v3 ncurr_g = mulp(Rcurr, ncurr[u]);
-                const float dist = norm(vprev[u] - vcurr_g[u]);
-                const float sine = norm(cross(ncurr_g, nprev[u]));
-                found = (sine < a.angleThres && dist <= a.distThres && !(ncurr[u].x != ncurr[u].x) && !(nprev[u].x != nprev[u].x));
-                if (found) {
-                    const v3 s_cp = mulp(Rprev_inv, vcurr_g[u] - tp);
-                    const v3 d_cp = mulp(Rprev_inv, vprev[u] - tp);
-                    const v3 n_cp = mulp(Rprev_inv, nprev[u]);
-                    const v3 c = cross(s_cp, n_cp);
-                    row[0] = n_cp.x; row[1] = n_cp.y; row[2] = n_cp.z;
-                    row[3] = c.x; row[4] = c.y; row[5] = c.z;
-                    row[6] = dot(n_cp, s_cp - d_cp);
-                }
-            }
+            if (ICP && inb[u]) found = icp_pair(row, Rcurr, Rprev_inv, tp, vcurr_g[u], ncurr[u], vprev[u], nprev[u], a.distThres, a.angleThres);
             if (ICP) products7<0>(row, found, acc);
-            // EF/Cuda/reduce.cu:811-842
-            hit[u] = RGB && (cand[u] & (d0[u] > 0) & (fabsf(td1[u] - d0[u]) <= a.maxDepthDelta) & (lif[u] != 0.f));
+            hit[u] = RGB && rgb_warp_hit(cand[u], d0[u], td1[u], a.maxDepthDelta, lif[u] != 0.f);
             diff[u] = nif[u] - lif[u];
             cnt += hit[u] ? 1 : 0;
             sig += hit[u] ? (int)(diff[u] * diff[u]) : 0;
@@ -2513,93 +2477,20 @@ __global__ __launch_bounds__(RED_THREADS) void k_gn_level(DevState* st, LevelArg
         // ---- phase B: the photometric rows (RGBReduction, EF/Cuda/reduce.cu:494-619) from registers
         const int rcnt = __hip_atomic_load(&gres[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), rsig = __hip_atomic_load(&gres[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (RGB) {
-            const float q = (float)rsig / (float)rcnt;
-            const float sigma = (float)sqrt((double)((q == 0) ? 1 : rcnt));   // the reference's precedence quirk (EF/Utils/RGBDOdometry.cpp:461)
+            const float sigma = rgb_sigma(rcnt, rsig);
 #pragma unroll
             for (int k = 0; k < 29; k++) acc[k] = 0.0;
 #pragma unroll
             for (int u = 0; u < PX; u++) {
                 float row[7] = {0, 0, 0, 0, 0, 0, 0};
                 const bool found = hit[u];
-                if (found) {
-                    float wgt = sigma + fabsf(diff[u]);
-                    wgt = wgt > 1.19209290E-07F ? 1.0f / wgt : 1.0f;
-                    if (sigma == -1) wgt = 1;
-                    row[6] = -wgt * diff[u];
-                    const float invz = (float)(1.0 / Z[u]);
-                    const float dI_dx = wgt * a.sobelScale * gx[u];
-                    const float dI_dy = wgt * a.sobelScale * gy[u];
-                    const float v0 = dI_dx * a.fx * invz;
-                    const float v1 = dI_dy * a.fy * invz;
-                    const float v2 = -(v0 * X[u] + v1 * Y[u]) * invz;
-                    row[0] = v0; row[1] = v1; row[2] = v2;
-                    row[3] = -Z[u] * v1 + Y[u] * v2;
-                    row[4] = Z[u] * v0 - X[u] * v2;
-                    row[5] = -Y[u] * v0 + X[u] * v1;
-                }
+                if (found) rgb_row(row, sigma, diff[u], gx[u], gy[u], X[u], Y[u], Z[u], a.fx, a.fy, a.sobelScale);
                 products7<1>(row, found, acc);
             }
             block_sum_exact<29>(acc, rgb_acc, bid % IFX_ACC_REPL);
         }
         if (!gn_grid_barrier(bar, 2 * it + 2, nb, st, a.acc_base * 2 + 2 * it + 2)) { failed = true; break; }
-        // ---- every block: totals -> combined system -> solve -> the next iteration's pose in LDS
-        const bool last_it = it == a.iters - 1;
-        if (tid < 29) {
-            const double ti = acc_total(icp_acc, tid), tr = acc_total(rgb_acc, tid);
-            if (bid == 0) range_note(st, ICP && range_exceeded7(0, tid, ti), RGB && range_exceeded7(1, tid, tr));
-            const float oi = ICP ? (float)ti : 0.f, orr = RGB ? (float)tr : 0.f;
-            s_oi[tid] = oi; s_or[tid] = orr;
-            if (tid < 27) {
-                const double wgt = a.icp_weight;
-                const double wa = wgt * wgt, wb = wgt;
-                const bool is_b = (tid == 6) | (tid == 12) | (tid == 17) | (tid == 21) | (tid == 24) | (tid == 26);
-                const double vi = (double)oi, vr = (double)orr;
-                s_sys[tid] = (ICP != 0 && RGB != 0) ? vr + (is_b ? wb : wa) * vi : (ICP ? vi : vr);
-            }
-        }
-        if (tid == 64) { s_res[0] = rcnt; s_res[1] = rsig; }
-        __syncthreads();
-        if (bid == 0 && last_it && a.final_level && tid >= 64 && tid < 128) {   // diagnostics of the run's last iteration (block 0, off the serial lane)
-            const int t = tid - 64;
-            if (t == 0) {
-                const int rgbSize = RGB ? s_res[0] : 0, sigma = RGB ? s_res[1] : 0;
-                st->rgb_count = rgbSize; st->rgb_sigma = sigma;
-                st->lastRGBError = (float)(sqrt((double)sigma) / (rgbSize == 0 ? 1 : rgbSize));
-                st->lastRGBCount = (float)rgbSize;
-                if (ICP) { st->lastICPError = sqrtf(s_oi[27]) / s_oi[28]; st->lastICPCount = s_oi[28]; }
-            }
-            if (t < 29) { st->icp29[t] = s_oi[t]; st->rgb29[t] = s_or[t]; }
-            if (t < 36) {
-                const int i = t / 6, j = t - 6 * i, lo = i < j ? i : j, hi = i < j ? j : i;
-                st->lastA[t] = s_sys[lo * 7 - (lo * (lo - 1)) / 2 + (hi - lo)];
-            }
-            if (t < 6) st->lastb[t] = s_sys[t * 7 - (t * (t - 1)) / 2 + (6 - t)];
-        }
-        if (tid == 0 && !(last_it && bid != 0)) {   // (the level's last solve is only block 0's to publish)
-            double RRt[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) RRt[k] = s_RRt[k];
-            float Rc[9], tcn[3], krkn[9], ktn[3];
-            if (last_it) gn_serial_lane(s_sys, ICP, RRt, Rp, tpv, a.nfx, a.nfy, a.ncx, a.ncy, a.ki_next, Rc, tcn, krkn, ktn);
-            else gn_serial_lane(s_sys, ICP, RRt, Rp, tpv, a.fx, a.fy, a.cx, a.cy, a.ki_same, Rc, tcn, krkn, ktn);
-#pragma unroll
-            for (int k = 0; k < 12; k++) s_RRt[k] = RRt[k];
-#pragma unroll
-            for (int k = 0; k < 9; k++) { s_pose[k] = Rc[k]; s_pose[12 + k] = krkn[k]; }
-#pragma unroll
-            for (int k = 0; k < 3; k++) { s_pose[9 + k] = tcn[k]; s_pose[21 + k] = ktn[k]; }
-            if (bid == 0 && last_it) {   // the level's result for whatever runs next (the next level's launch, the end of the run, diagnostics)
-#pragma unroll
-                for (int k = 0; k < 16; k++) st->resultRt[k] = RRt[k];
-#pragma unroll
-                for (int k = 0; k < 9; k++) { st->Rcurr[k] = Rc[k]; st->krkinv[k] = krkn[k]; }
-#pragma unroll
-                for (int k = 0; k < 3; k++) { st->tcurr[k] = tcn[k]; st->kt[k] = ktn[k]; }
-                if (a.final_level) track_end_vals(st, RGB, 1, Rc, tcn, Rp, tpv, a.weight_mult, a.commit, a.lctr);
-                st->gn_done_seq = a.level + 1;
-            }
-        }
-        __syncthreads();
+        gn_level_tail<false>(st, a, s, bid, it == a.iters - 1, icp_acc, rgb_acc, rcnt, rsig, Rp, tpv);
     }
     // A meeting failed: nothing of this level was published (only block 0 publishes, and only behind the level's last meeting, when it also marks the level done).
     // Every block leaves; the one-workgroup kernel enqueued behind this launch (k_gn_level_solo) finds the level not done and runs it again from the state the level
@@ -2884,227 +2775,305 @@ static void tracker_init_frame(ifx* h, const uint16_t* depth_filt, const uint8_t
 
 int ifx_comm_ready(ifx* h);
 int ifx_comm_allreduce_f64(ifx* h, double* d_ptr, int n);   // SUM over the ranks, in place, on the handle's CURRENT stream (ifx_comm.hip)
+// per-kernel timing (option kernel_timing) is kept per pyramid level: ifx_kernel_ms("icp_residual") sums the levels, "icp_residual@L0" is level 0 alone (bench.py's per-level roofline)
+static_assert(IFX_NUM_PYRS == 3, "level names");
 static inline const char* icp_name_rows(int level) { static const char* const n[3] = {"icp_residual_rows@L0", "icp_residual_rows@L1", "icp_residual_rows@L2"}; return n[level]; }
-// getIncrementalTransformation, EF/Utils/RGBDOdometry.cpp:267-603, enqueued without any readback
-// `st` / `p`: the state and pyramids of the tracker instance (frame-to-model: h->d_state / h->pyr; model-to-model: h->d_m2m / h->m2m)
-static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3, float weight_mult, int commit, bool frame_tracker, int keep_last = 0)
+static inline const char* icp_name(int level) { static const char* const n[3] = {"icp_residual@L0", "icp_residual@L1", "icp_residual@L2"}; return n[level]; }
+static inline const char* rgb_name(int level) { static const char* const n[3] = {"rgb_step_solve@L0", "rgb_step_solve@L1", "rgb_step_solve@L2"}; return n[level]; }
+
+// The instantiation of an iteration's first launch for a run's booleans.  CHECK_SKIP: the model-to-model tracker checks the skip flag; PRO: from the prologue chain's
+// second iteration on every block first solves the iteration before; LIST: the residual half runs over the candidate list; FUSE (list runs only): the step too.
+using IcpResidualKernel = decltype(&k_icp_residual<false>);
+static IcpResidualKernel icp_residual_kernel(bool check_skip, bool pro, bool list, bool fuse)
+{
+    static const IcpResidualKernel k[2][2][3] = {
+        {{k_icp_residual<false, false>, k_icp_residual<false, false, true>, k_icp_residual<false, false, true, true>},
+         {k_icp_residual<false, true>, k_icp_residual<false, true, true>, k_icp_residual<false, true, true, true>}},
+        {{k_icp_residual<true, false>, k_icp_residual<true, false, true>, k_icp_residual<true, false, true, true>},
+         {k_icp_residual<true, true>, k_icp_residual<true, true, true>, k_icp_residual<true, true, true, true>}}};
+    return k[check_skip][pro][fuse ? 2 : list ? 1 : 0];
+}
+// ... and of its second launch
+using RgbStepSolveKernel = decltype(&k_rgb_step_solve<false>);
+static RgbStepSolveKernel rgb_step_solve_kernel(bool check_skip, bool list)
+{
+    static const RgbStepSolveKernel k[2][2] = {{k_rgb_step_solve<false>, k_rgb_step_solve<false, true>}, {k_rgb_step_solve<true>, k_rgb_step_solve<true, true>}};
+    return k[check_skip][list];
+}
+
+// What a tracker run does, decided once per run from the options and the pyramid: which levels iterate, and in which form.
+struct RunPlan {
+    int icp, rgb;                                            // the terms the weighting keeps
+    int iterations[IFX_NUM_PYRS], first;                     // Gauss-Newton iterations per level; the coarsest level that iterates (-1: none does)
+    bool finer[IFX_NUM_PYRS];                                // does a finer level still iterate (if none does, the level's last iteration ends the run)
+    float next_div[IFX_NUM_PYRS];                            // scale of the level the iteration after the level's last one runs at (for the warp matrices the solve emits)
+    int persist_q[IFX_NUM_PYRS], persist_nb[IFX_NUM_PYRS];   // the level runs in the persistent kernel k_gn_level<q + 1> (-1: two-launch iterations) with this grid
+    bool cand_run;                                           // the two-launch iterations run over the frame slot's candidate list (option rgb_cand)
+    bool pro;                                                // the two-launch iterations form the run's tail: their solves move into the next launch's prologue (gn_prologue) ...
+    int n_pro;                                               // ... for this many leading iterations of the tail
+};
+static RunPlan plan_run(ifx* h, const Pyr& p, float icp_weight, bool frame_tracker)
 {
     const ifx_config& c = h->cfg;
+    RunPlan pl;
     const int icp = icp_weight > 0, rgb = icp_weight < 100;
-    int iterations[3] = {c.fast_odom ? 3 : 10, c.pyramid ? 5 : 0, c.pyramid ? 4 : 0};
-    int first = -1;
-    for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) if (iterations[i] > 0) { first = i; break; }
-    if (frame_tracker && h->gn_begin_folded) h->gn_begin_folded = 0;   // the model side's last launch already did it (ifx_tracker_model_side)
-    else {
-        const float div = (float)(1 << (first < 0 ? 0 : first));
-        LAUNCH(h, "track_gn_begin", dim3(1), dim3(64), k_track_gn_begin, st, h->slot[h->cur_slot].so3, so3, c.fx / div, c.fy / div, c.cx / div, c.cy / div, keep_last, h->opt_gn_persist ? 1 : 0);
-    }
-    const double sobelScale = 1.0 / 8.0;
-    bool ended = false;
-    // which levels run in the persistent kernel, and whether the two-launch iterations form the run's tail (then their solves move into the next launch's prologue: gn_prologue)
-    int persist_q[IFX_NUM_PYRS], persist_nb[IFX_NUM_PYRS];
+    pl.icp = icp; pl.rgb = rgb;
+    const int iterations[3] = {c.fast_odom ? 3 : 10, c.pyramid ? 5 : 0, c.pyramid ? 4 : 0};
+    pl.first = -1;
+    for (int i = 0; i < IFX_NUM_PYRS; i++) pl.iterations[i] = iterations[i];
+    for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) if (iterations[i] > 0) { pl.first = i; break; }
+    // which levels run in the persistent kernel
     for (int i = 0; i < IFX_NUM_PYRS; i++) {
-        persist_q[i] = -1; persist_nb[i] = 0;
+        pl.persist_q[i] = -1; pl.persist_nb[i] = 0;
         if (frame_tracker && (h->opt_gn_persist & (1 << i)) && iterations[i] > 0 && icp && rgb) {
             static const int pxs[4] = {1, 2, 3, 4};
             const int n = p.w[i] * p.h[i];
-            for (int t = 0; t < 4 && persist_q[i] < 0; t++) {   // (fewer, fatter blocks at the finer levels -- 4 pixels per thread -- were tried for cheaper meetings: slower)
+            for (int t = 0; t < 4 && pl.persist_q[i] < 0; t++) {   // (fewer, fatter blocks at the finer levels -- 4 pixels per thread -- were tried for cheaper meetings: slower)
                 const int need = cdiv(n, RED_THREADS * pxs[t]);
-                if (need <= h->gn_max_blocks[t] * 7 / 8 && need <= h->opt_gn_persist_blocks) { persist_q[i] = t; persist_nb[i] = need; }   // (co-residency is what the barriers need; an eighth of the slots stays free for whatever shares the GPU)
+                if (need <= h->gn_max_blocks[t] * 7 / 8 && need <= h->opt_gn_persist_blocks) { pl.persist_q[i] = t; pl.persist_nb[i] = need; }   // (co-residency is what the barriers need; an eighth of the slots stays free for whatever shares the GPU)
             }
         }
     }
-    // per level: does a finer level still iterate (if none does, the level's last iteration ends the run), and the scale of the level the iteration after its last one runs at
-    // (for the warp matrices the solve emits)
-    bool finer[IFX_NUM_PYRS];
-    float next_div[IFX_NUM_PYRS];
     for (int i = 0, nl = -1; i < IFX_NUM_PYRS; i++) {   // nl: the nearest level below i that iterates
-        finer[i] = nl >= 0; next_div[i] = (float)(1 << (nl < 0 ? 0 : nl));
+        pl.finer[i] = nl >= 0; pl.next_div[i] = (float)(1 << (nl < 0 ? 0 : nl));
         if (iterations[i] > 0) nl = i;
-    }
-    double* const gacc = (double*)((char*)st + offsetof(DevState, gn_acc));   // (accumulator rows, residual totals, ticket: DevState::gn_acc / gn_res / gn_ticket of `st`)
-    int* const gres = (int*)((char*)st + offsetof(DevState, gn_res));
-    // The arguments of level i's correspondence / residual launch and of the step of its iteration j.  What differs between the forms of the run is set by the caller:
-    // the block counts (nb*), check_skip, lctr, pro / pro_k.
-    auto pair_args = [&](int i) {
-        const float div = (float)(1 << i);
-        PairArgs pa;
-        pa.vmap_curr = p.vmap_curr[i]; pa.nmap_curr = p.nmap_curr[i]; pa.vmap_prev = p.vmap_prev[i]; pa.nmap_prev = p.nmap_prev[i];
-        pa.fx = c.fx / div; pa.fy = c.fy / div; pa.cx = c.cx / div; pa.cy = c.cy / div; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
-        pa.minScale = rgb_min_scale(i); pa.maxDepthDelta = 0.07f;
-        pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
-        pa.corres = (Corres8*)p.corres[i]; pa.w = p.w[i]; pa.h = p.h[i];
-        return pa;
-    };
-    auto step_args = [&](int i, int j) {
-        const float div = (float)(1 << i);
-        const bool last = j == iterations[i] - 1;
-        const float nd = last ? next_div[i] : div;
-        StepArgs sa;
-        sa.corres = (const Corres8*)p.corres[i]; sa.cloud = p.cloud[i]; sa.fx = c.fx / div; sa.fy = c.fy / div; sa.sobelScale = (float)sobelScale;
-        sa.dIdx = p.didx[i]; sa.dIdy = p.didy[i]; sa.w = p.w[i]; sa.h = p.h[i];
-        sa.icp = icp; sa.rgb = rgb; sa.icp_weight = icp_weight; sa.nfx = c.fx / nd; sa.nfy = c.fy / nd; sa.ncx = c.cx / nd; sa.ncy = c.cy / nd; sa.ki = kinv_of(sa.nfx, sa.nfy, sa.ncx, sa.ncy);
-        sa.final_iter = (last && !finer[i]) ? 1 : 0;   // the run's last iteration
-        sa.end_run = sa.final_iter; sa.commit = commit; sa.weight_mult = weight_mult;
-        return sa;
-    };
-    if (frame_tracker && h->own && h->opt_own_track_rows && ifx_comm_ready(h) && h->own_track_rank < 0) {
-        // the reductions over this rank's blocks + all-reduce + one-workgroup solve (k_icp_residual_rows above).  opt_own_track_rows_emulate = G > 1 (test switch): this ONE rank
-        // plays G in turn into the same accumulator rows -- the partition's cover, without a second GPU
-        const int Ge = h->opt_own_track_rows_emulate > 1 ? h->opt_own_track_rows_emulate : 0;
-        const int sn = Ge ? Ge : h->own_g, r_lo = Ge ? 0 : h->cfg.rank, r_hi = Ge ? Ge : h->cfg.rank + 1;
-        const int row = IFX_ACC_REPL * IFX_ACC_STRIDE;
-        for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) {
-            if (i == 0) ifx_enqueue_hinted_frame_side(h);
-            const int lw = p.w[i], lh = p.h[i], n = lw * lh;
-            const int nbv = cdiv(red_blocks(h, n), sn), nbr = std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows);
-            const int nb_rgb_v = cdiv(std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192), sn);
-            PairArgs pa = pair_args(i);
-            pa.nb_icp = icp ? nbv : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = 0;
-            for (int j = 0; j < iterations[i]; j++) {
-                for (int r = r_lo; r < r_hi; r++)   // (the residual pass once: with the first of the launches)
-                    LAUNCH(h, icp_name_rows(i), dim3(pa.nb_icp + (r == r_lo ? pa.nb_res : 0)), dim3(RED_THREADS), k_icp_residual_rows, (const DevState*)st, pa.nb_icp, lw, lh, gacc, gres, pa, r, sn);
-                if (icp && h->track_rc == IFX_OK) h->track_rc = ifx_comm_allreduce_f64(h, gacc, row);
-                StepArgs sa2 = step_args(i, j);
-                sa2.nb = nb_rgb_v; sa2.nb_icp = pa.nb_icp; sa2.nb_res = pa.nb_res; sa2.check_skip = 0; sa2.lctr = h->d_list_ctr; sa2.pro = 0; sa2.pro_k = 0;
-                ended = ended || sa2.end_run;
-                if (rgb) {
-                    for (int r = r_lo; r < r_hi; r++) LAUNCH(h, "rgb_step_rows", dim3(nb_rgb_v), dim3(RED_THREADS), k_rgb_step_rows, st, nb_rgb_v, lw, lh, sa2, r, sn);
-                    if (h->track_rc == IFX_OK) h->track_rc = ifx_comm_allreduce_f64(h, gacc + row, row);   // (a failed collective: the run is enqueued to its end, the frame call reports it)
-                }
-                LAUNCH(h, "gn_solve_rows", dim3(1), dim3(RED_THREADS), k_gn_solve_rows, st, sa2);
-            }
-        }
-        if (!ended) LAUNCH(h, "track_end", dim3(1), dim3(64), k_track_end, st, rgb, 1, weight_mult, commit, h->d_list_ctr);
-        return;
     }
     // Option rgb_cand: the residual half and the photometric step of the two-launch iterations run over the bound frame slot's candidate list, and `corres` holds one record
     // per candidate.  Frame-to-model runs only (the live tracker, looked-ahead or not, and a camera's run ahead: `cand` is set and the next depth is the model's); a run
     // with a persistent level stays dense as a whole -- the dense forms index `corres` by pixel, and where both would meet in one run the dense one wins.
-    bool cand_run = h->opt_rgb_cand != 0 && rgb;
-    for (int i = 0; i < IFX_NUM_PYRS; i++) cand_run = cand_run && p.cand[i] && p.cand_n[i] && !p.next_depth[i] && persist_q[i] < 0;
-    bool pro = h->opt_gn_prologue != 0;
+    pl.cand_run = h->opt_rgb_cand != 0 && rgb;
+    for (int i = 0; i < IFX_NUM_PYRS; i++) pl.cand_run = pl.cand_run && p.cand[i] && p.cand_n[i] && !p.next_depth[i] && pl.persist_q[i] < 0;
+    pl.pro = h->opt_gn_prologue != 0;
     // The prologue solve is repeated by every block of a launch: free while the grid is one wave of blocks, 4-6 us per launch at 4800 + 304 blocks (level 0 of a
     // 1280x960 frame: 516 against 540 frames/s, profiles/r04_z2_*).  n_pro: the leading iterations of the tail (coarse levels first) whose launches stay under
     // opt_gn_prologue_blocks; the last of them is solved in the last-block form (StepArgs::pro = 2) and leaves the pose in the state, where round 3's form of the
     // finer levels reads it.
-    int n_pro = 0;
-    {
-        bool seen_two_launch = false, small = true;
-        for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) {
-            if (iterations[i] <= 0) continue;
-            if (persist_q[i] >= 0) { if (seen_two_launch) pro = false; }   // a persistent level BEHIND two-launch iterations reads the pose from the state: round 3's form keeps it there
-            else {
-                seen_two_launch = true;
-                const int n = p.w[i] * p.h[i];
-                const int blocks = (icp ? red_blocks(h, n) : 0) + (cand_run ? rgb_cand_blocks(h, n, i, false) : rgb ? std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : (1 << 30)) : 0);
-                small = small && blocks <= h->opt_gn_prologue_blocks;
-                if (small) n_pro += iterations[i];
-            }
-        }
-        if (n_pro < 2) pro = false;   // (a chain of one has nothing to hand over)
-    }
-    int persist_iters = 0;
-    int tail_k = 0;   // position of the next two-launch iteration in the tail
-    char* const stb = (char*)st;
-    auto gnp_acc_of = [&](int set) { return (double*)(stb + offsetof(DevState, gnp_acc)) + (size_t)(set * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE; };
-    auto gnp_res_of = [&](int set) { return (int*)(stb + offsetof(DevState, gnp_res)) + set * 16; };
-    auto gnp_meet_of = [&](int set) { return (unsigned int*)(stb + offsetof(DevState, gnp_meet)) + set * 32; };
-    auto gnp_rrt_of = [&](int par) { return (double*)(stb + offsetof(DevState, gnp_RRt)) + par * 16; };
-    // per-kernel timing (option kernel_timing) is kept per pyramid level: ifx_kernel_ms("icp_residual") sums the levels, "icp_residual@L0" is level 0 alone (bench.py's per-level roofline)
-    static const char* const icp_name[3] = {"icp_residual@L0", "icp_residual@L1", "icp_residual@L2"};
-    static const char* const rgb_name[3] = {"rgb_step_solve@L0", "rgb_step_solve@L1", "rgb_step_solve@L2"};
-    static_assert(IFX_NUM_PYRS == 3, "level names");
+    pl.n_pro = 0;
+    bool seen_two_launch = false, small = true;
     for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) {
-        // The coarse levels are on the queue: the host is now ahead of the GPU by ~20 latency-bound launches, and the
-        // finest level keeps the GPU mostly idle for another ~0.3 ms -- the place to slip in the next frame's image-only work.
-        if (i == 0 && frame_tracker) ifx_enqueue_hinted_frame_side(h);
-        float div = (float)(1 << i);
-        float fx = c.fx / div, fy = c.fy / div, cx = c.cx / div, cy = c.cy / div;
-        int lw = p.w[i], lh = p.h[i], n = lw * lh, nb = red_blocks(h, n), nb_rgb = cand_run ? rgb_cand_blocks(h, n, i, true) : std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192);   // the photometric step's launch is dominated by the last block's hand-off and solve: fewer blocks, fewer partial rows (64: 16.9, 192: 15.3, 304: 16.1, 608: 18.5 us per launch)
-        const float ld = next_div[i];   // the level the iteration after this level's last one runs at
-        PairArgs pa = pair_args(i);
-        // The residual half of the launch is the slower one and scales with its blocks (its totals go through integer atomics, it has no partial rows for the
-        // last block to sum): one pixel per thread, no loop -- 152 blocks 17.5 us, 304 blocks 13.3 us, 1200 blocks 11.3 us per launch at 640x480 (1053 -> 1102 frames/s).
-        // One round of residency: the launch's blocks (ICP half + residual half) must all be on the GPU at once.  At 640x480 level 0 they were 456 + 1024 = 1480 against the 1024 the GPU holds
-        // (118 VGPRs: 4 blocks per CU), so a third of them started when the first ones left -- and paid the launch's start-up chain (kernel arguments, the previous iteration's totals and
-        // 6x6 solve in every block's prologue, the first loads) a second time: 17.2 -> 14.5 us per level-0 launch with the residual half capped to what is left of one round
-        // (profiles/r05_ai_ab_tracker_blocks.txt: 1514 -> 1561 frames/s).  The halves loop over their pixels anyway (grid-stride); opt_res_blocks > 0 overrides.
-        const int res_round = std::max(128, h->icp_resident_blocks - (icp ? nb : 0));
-        const int nbr = cand_run ? rgb_cand_blocks(h, n, i, false) : std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : res_round);
-        const CandEntry* const cl = cand_run ? p.cand[i] : nullptr;
-        const unsigned int* const cln = cand_run ? p.cand_n[i] : nullptr;
-        pa.nb_icp = icp ? nb : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = frame_tracker ? 0 : 1;
-        if (persist_q[i] >= 0) {   // all iterations of the level in one persistent launch
-            const int q = persist_q[i], nbp = persist_nb[i];
-            LevelArgs la;
-            la.vmap_curr = pa.vmap_curr; la.nmap_curr = pa.nmap_curr; la.vmap_prev = pa.vmap_prev; la.nmap_prev = pa.nmap_prev;
-            la.dIdx = pa.dIdx; la.dIdy = pa.dIdy; la.lastDepth = pa.lastDepth; la.nextDepth = pa.nextDepth; la.lastImage = pa.lastImage; la.nextImage = pa.nextImage;
-            la.cloud = p.cloud[i]; la.corres = (Corres8*)p.corres[i];
-            la.fx = fx; la.fy = fy; la.cx = cx; la.cy = cy; la.distThres = pa.distThres; la.angleThres = pa.angleThres; la.minScale = pa.minScale; la.maxDepthDelta = pa.maxDepthDelta;
-            la.sobelScale = (float)sobelScale;
-            la.w = lw; la.h = lh; la.iters = iterations[i]; la.icp = icp; la.rgb = rgb; la.icp_weight = icp_weight;
-            la.nfx = c.fx / ld; la.nfy = c.fy / ld; la.ncx = c.cx / ld; la.ncy = c.cy / ld;
-            la.ki_same = kinv_of(fx, fy, cx, cy); la.ki_next = kinv_of(la.nfx, la.nfy, la.ncx, la.ncy);
-            la.acc_base = persist_iters; la.level = i;   // (parity of the persistent kernel's double buffers: continuous over ITS launches, whatever two-launch levels lie between them)
-            persist_iters += iterations[i];
-            la.final_level = finer[i] ? 0 : 1; la.commit = commit; la.weight_mult = weight_mult; la.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
-            auto go = [&](auto kernel) { LAUNCH(h, "gn_level", dim3(nbp), dim3(RED_THREADS), kernel, st, la); };
-            if (q == 0) go(k_gn_level<1>);   // (pixels per thread)
-            else if (q == 1) go(k_gn_level<2>);
-            else if (q == 2) go(k_gn_level<3>);
-            else go(k_gn_level<4>);
-            LAUNCH(h, "gn_level_solo", dim3(1), dim3(RED_THREADS), k_gn_level_solo, st, la);   // the safety net: a no-op unless a meeting of the launch above did not happen
-            ended = ended || la.final_level;
-            continue;
-        }
-        for (int j = 0; j < iterations[i]; j++) {
-            // gn_prologue: iteration tail_k sums into set tail_k % 3 (its increment goes to parity tail_k & 1); from the tail's second iteration on, every block first solves the iteration before
-            GnPro gp;
-            gp.k = tail_k; gp.icp = icp; gp.rgb = rgb; gp.icp_weight = icp_weight; gp.nfx = fx; gp.nfy = fy; gp.ncx = cx; gp.ncy = cy; gp.ki = kinv_of(fx, fy, cx, cy);
-            const bool it_pro = pro && tail_k < n_pro;
-            const bool fuse = cand_run && it_pro && tail_k < n_pro - 1 && (h->opt_rgb_fuse & (1 << i));   // option rgb_fuse: the step in this launch (every chain iteration but the last, StepArgs::pro == 1)
-            double* const ga = it_pro ? gnp_acc_of(tail_k % 3) : gacc;
-            int* const gr = it_pro ? gnp_res_of(tail_k % 3) : gres;
-            double* const rrt_store = gnp_rrt_of((tail_k + 1) & 1);   // the increment after iteration tail_k - 1
-            // <CHECK_SKIP, PRO>: the model-to-model tracker checks the skip flag; from the prologue chain's second iteration on every block first solves the iteration before
-            // ... and over the candidate list when the run is a list run (LIST)
-            FuseArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            PairArgs paf = pa;
-            if (fuse) {   // G photometric blocks (rgb_fuse_blocks), within one round of residency beside the ICP blocks
-                paf.nb_res = std::max(1, std::min(rgb_fuse_blocks(h, n), h->icp_resident_blocks_fuse - pa.nb_icp));
-                const int cs = (tail_k + 1) % 3;
-                fa.cloud = p.cloud[i]; fa.sobelScale = (float)sobelScale; fa.g = paf.nb_res; fa.poll_ticks = h->opt_rgb_fuse_poll ? RGB_MEET_TICKS : 0u;
-                fa.meet = gnp_meet_of(tail_k % 3); fa.clear_acc = gnp_acc_of(cs); fa.clear_res = gnp_res_of(cs); fa.clear_meet = gnp_meet_of(cs);
-                fa.range_ctr = (int*)(stb + offsetof(DevState, range_exceeded)); fa.giveups = (int*)(stb + offsetof(DevState, rgb_meet_giveups));
-            }
-            auto go_icp = [&](auto kernel) { LAUNCH(h, icp_name[i], dim3(paf.nb_icp + paf.nb_res), dim3(RED_THREADS), kernel, st, paf.nb_icp, paf.w, paf.h, ga, gr, paf, gp, rrt_store, cl, cln, fa); };
-            if (fuse) {
-                if (tail_k > 0) { if (frame_tracker) go_icp(k_icp_residual<false, true, true, true>); else go_icp(k_icp_residual<true, true, true, true>); }
-                else { if (frame_tracker) go_icp(k_icp_residual<false, false, true, true>); else go_icp(k_icp_residual<true, false, true, true>); }
-                tail_k++;
-                continue;
-            }
-            if (it_pro && tail_k > 0) {
-                if (frame_tracker) { if (cand_run) go_icp(k_icp_residual<false, true, true>); else go_icp(k_icp_residual<false, true>); }
-                else { if (cand_run) go_icp(k_icp_residual<true, true, true>); else go_icp(k_icp_residual<true, true>); }
-            } else {
-                if (frame_tracker) { if (cand_run) go_icp(k_icp_residual<false, false, true>); else go_icp(k_icp_residual<false, false>); }
-                else { if (cand_run) go_icp(k_icp_residual<true, false, true>); else go_icp(k_icp_residual<true, false>); }
-            }
-            StepArgs sa2 = step_args(i, j);
-            sa2.nb = nb_rgb; sa2.nb_icp = nb; sa2.nb_res = nbr; sa2.check_skip = frame_tracker ? 0 : 1; sa2.lctr = frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
-            sa2.pro = (pro && tail_k < n_pro) ? (tail_k == n_pro - 1 ? 2 : 1) : 0; sa2.pro_k = tail_k;   // (the chain's last iteration: last-block form; it is the run's last too unless finer levels were too large for the prologue)
-            tail_k++;
-            ended = ended || sa2.end_run;
-            auto go_rgb = [&](auto kernel) { LAUNCH(h, rgb_name[i], dim3(nb_rgb), dim3(RED_THREADS), kernel, st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2, cl, cln); };
-            if (frame_tracker) { if (cand_run) go_rgb(k_rgb_step_solve<false, true>); else go_rgb(k_rgb_step_solve<false>); }
-            else { if (cand_run) go_rgb(k_rgb_step_solve<true, true>); else go_rgb(k_rgb_step_solve<true>); }
+        if (iterations[i] <= 0) continue;
+        if (pl.persist_q[i] >= 0) { if (seen_two_launch) pl.pro = false; }   // a persistent level BEHIND two-launch iterations reads the pose from the state: round 3's form keeps it there
+        else {
+            seen_two_launch = true;
+            const int n = p.w[i] * p.h[i];
+            const int blocks = (icp ? red_blocks(h, n) : 0) + (pl.cand_run ? rgb_cand_blocks(h, n, i, false) : rgb ? std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : (1 << 30)) : 0);
+            small = small && blocks <= h->opt_gn_prologue_blocks;
+            if (small) pl.n_pro += iterations[i];
         }
     }
-    if (!ended)   // (no iteration ran at all: every level has zero iterations)
-        LAUNCH(h, "track_end", dim3(1), dim3(64), k_track_end, st, rgb, 1, weight_mult, commit, frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr);
+    if (pl.n_pro < 2) pl.pro = false;   // (a chain of one has nothing to hand over)
+    return pl;
+}
+
+// One tracker_run call: its arguments, its plan, and what its emitters carry from one launch to the next.
+// `st` / `p`: the state and pyramids of the tracker instance (frame-to-model: h->d_state / h->pyr; model-to-model: h->d_m2m / h->m2m)
+struct TrackRun {
+    ifx* h; DevState* st; Pyr& p;
+    float icp_weight, weight_mult; int commit; bool frame_tracker;
+    RunPlan plan;
+    int persist_iters;   // iterations the persistent kernel has run so far
+    int tail_k;          // position of the next two-launch iteration in the tail
+    bool ended;          // an emitted launch ends the run (pose write-back, velocity weighting, view-list decision)
+};
+static const double GN_SOBEL_SCALE = 1.0 / 8.0;
+// accumulator rows, residual totals and ticket of the last-block form: DevState::gn_acc / gn_res / gn_ticket of `st`
+static inline double* gn_acc_of(DevState* st) { return (double*)((char*)st + offsetof(DevState, gn_acc)); }
+static inline int* gn_res_of(DevState* st) { return (int*)((char*)st + offsetof(DevState, gn_res)); }
+// ... and the three sets of the prologue chain's rotation, its increment by parity
+static inline double* gnp_acc_of(DevState* st, int set) { return (double*)((char*)st + offsetof(DevState, gnp_acc)) + (size_t)(set * 2) * IFX_ACC_REPL * IFX_ACC_STRIDE; }
+static inline int* gnp_res_of(DevState* st, int set) { return (int*)((char*)st + offsetof(DevState, gnp_res)) + set * 16; }
+static inline unsigned int* gnp_meet_of(DevState* st, int set) { return (unsigned int*)((char*)st + offsetof(DevState, gnp_meet)) + set * 32; }
+static inline double* gnp_rrt_of(DevState* st, int par) { return (double*)((char*)st + offsetof(DevState, gnp_RRt)) + par * 16; }
+
+// The arguments of level i's correspondence / residual launch and of the step of its iteration j.  What differs between the forms of the run is set by the caller:
+// the block counts (nb*), check_skip, lctr, pro / pro_k.
+static PairArgs pair_args(const TrackRun& r, int i)
+{
+    const ifx_config& c = r.h->cfg;
+    const Pyr& p = r.p;
+    const float div = (float)(1 << i);
+    PairArgs pa;
+    pa.vmap_curr = p.vmap_curr[i]; pa.nmap_curr = p.nmap_curr[i]; pa.vmap_prev = p.vmap_prev[i]; pa.nmap_prev = p.nmap_prev[i];
+    pa.fx = c.fx / div; pa.fy = c.fy / div; pa.cx = c.cx / div; pa.cy = c.cy / div; pa.distThres = 0.10f; pa.angleThres = sinf(20.f * 3.14159254f / 180.f);
+    pa.minScale = rgb_min_scale(i); pa.maxDepthDelta = 0.07f;
+    pa.dIdx = p.didx[i]; pa.dIdy = p.didy[i]; pa.lastDepth = p.last_depth[i]; pa.nextDepth = p.next_depth[i] ? p.next_depth[i] : p.last_depth[i]; pa.lastImage = p.last_img[i]; pa.nextImage = p.next_img[i];
+    pa.corres = (Corres8*)p.corres[i]; pa.w = p.w[i]; pa.h = p.h[i];
+    return pa;
+}
+static StepArgs step_args(const TrackRun& r, int i, int j)
+{
+    const ifx_config& c = r.h->cfg;
+    const Pyr& p = r.p;
+    const float div = (float)(1 << i);
+    const bool last = j == r.plan.iterations[i] - 1;
+    const float nd = last ? r.plan.next_div[i] : div;
+    StepArgs sa;
+    sa.corres = (const Corres8*)p.corres[i]; sa.cloud = p.cloud[i]; sa.fx = c.fx / div; sa.fy = c.fy / div; sa.sobelScale = (float)GN_SOBEL_SCALE;
+    sa.dIdx = p.didx[i]; sa.dIdy = p.didy[i]; sa.w = p.w[i]; sa.h = p.h[i];
+    sa.icp = r.plan.icp; sa.rgb = r.plan.rgb; sa.icp_weight = r.icp_weight; sa.nfx = c.fx / nd; sa.nfy = c.fy / nd; sa.ncx = c.cx / nd; sa.ncy = c.cy / nd; sa.ki = kinv_of(sa.nfx, sa.nfy, sa.ncx, sa.ncy);
+    sa.final_iter = (last && !r.plan.finer[i]) ? 1 : 0;   // the run's last iteration
+    sa.end_run = sa.final_iter; sa.commit = r.commit; sa.weight_mult = r.weight_mult;
+    return sa;
+}
+// ... and of the persistent kernel's launch for the level, from the level's PairArgs
+static LevelArgs level_args(const PairArgs& pa, const TrackRun& r, int i)
+{
+    const ifx_config& c = r.h->cfg;
+    const float ld = r.plan.next_div[i];   // the level the iteration after this level's last one runs at
+    LevelArgs la;
+    la.vmap_curr = pa.vmap_curr; la.nmap_curr = pa.nmap_curr; la.vmap_prev = pa.vmap_prev; la.nmap_prev = pa.nmap_prev;
+    la.dIdx = pa.dIdx; la.dIdy = pa.dIdy; la.lastDepth = pa.lastDepth; la.nextDepth = pa.nextDepth; la.lastImage = pa.lastImage; la.nextImage = pa.nextImage;
+    la.cloud = r.p.cloud[i]; la.corres = pa.corres;
+    la.fx = pa.fx; la.fy = pa.fy; la.cx = pa.cx; la.cy = pa.cy; la.distThres = pa.distThres; la.angleThres = pa.angleThres; la.minScale = pa.minScale; la.maxDepthDelta = pa.maxDepthDelta;
+    la.sobelScale = (float)GN_SOBEL_SCALE;
+    la.w = pa.w; la.h = pa.h; la.iters = r.plan.iterations[i]; la.icp = r.plan.icp; la.rgb = r.plan.rgb; la.icp_weight = r.icp_weight;
+    la.nfx = c.fx / ld; la.nfy = c.fy / ld; la.ncx = c.cx / ld; la.ncy = c.cy / ld;
+    la.ki_same = kinv_of(pa.fx, pa.fy, pa.cx, pa.cy); la.ki_next = kinv_of(la.nfx, la.nfy, la.ncx, la.ncy);
+    la.acc_base = r.persist_iters; la.level = i;   // (parity of the persistent kernel's double buffers: continuous over ITS launches, whatever two-launch levels lie between them)
+    la.final_level = r.plan.finer[i] ? 0 : 1; la.commit = r.commit; la.weight_mult = r.weight_mult; la.lctr = r.frame_tracker ? r.h->d_list_ctr : (unsigned int*)nullptr;
+    return la;
+}
+
+// The row-sharded run (option own_track_rows): the reductions over this rank's blocks + all-reduce + one-workgroup solve (k_icp_residual_rows above).
+// opt_own_track_rows_emulate = G > 1 (test switch): this ONE rank plays G in turn into the same accumulator rows -- the partition's cover, without a second GPU
+static void emit_rows_run(TrackRun& r)
+{
+    ifx* const h = r.h;
+    DevState* const st = r.st;
+    const Pyr& p = r.p;
+    const int icp = r.plan.icp, rgb = r.plan.rgb;
+    double* const gacc = gn_acc_of(st);
+    int* const gres = gn_res_of(st);
+    const int Ge = h->opt_own_track_rows_emulate > 1 ? h->opt_own_track_rows_emulate : 0;
+    const int sn = Ge ? Ge : h->own_g, r_lo = Ge ? 0 : h->cfg.rank, r_hi = Ge ? Ge : h->cfg.rank + 1;
+    const int row = IFX_ACC_REPL * IFX_ACC_STRIDE;
+    for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) {
+        if (i == 0) ifx_enqueue_hinted_frame_side(h);
+        const int lw = p.w[i], lh = p.h[i], n = lw * lh;
+        const int nbv = cdiv(red_blocks(h, n), sn), nbr = std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows);
+        const int nb_rgb_v = cdiv(std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192), sn);
+        PairArgs pa = pair_args(r, i);
+        pa.nb_icp = icp ? nbv : 0; pa.nb_res = rgb ? nbr : 0; pa.check_skip = 0;
+        for (int j = 0; j < r.plan.iterations[i]; j++) {
+            for (int q = r_lo; q < r_hi; q++) {   // (the residual pass once: with the first of the launches)
+                const int grid = pa.nb_icp + (q == r_lo ? pa.nb_res : 0);
+                if (grid > 0)   // (ICP off: only the first of the launches has blocks)
+                    LAUNCH(h, icp_name_rows(i), dim3(grid), dim3(RED_THREADS), k_icp_residual_rows, (const DevState*)st, pa.nb_icp, lw, lh, gacc, gres, pa, q, sn);
+            }
+            if (icp && h->track_rc == IFX_OK) h->track_rc = ifx_comm_allreduce_f64(h, gacc, row);
+            StepArgs sa2 = step_args(r, i, j);
+            sa2.nb = nb_rgb_v; sa2.nb_icp = pa.nb_icp; sa2.nb_res = pa.nb_res; sa2.check_skip = 0; sa2.lctr = h->d_list_ctr; sa2.pro = 0; sa2.pro_k = 0;
+            r.ended = r.ended || sa2.end_run;
+            if (rgb) {
+                for (int q = r_lo; q < r_hi; q++) LAUNCH(h, "rgb_step_rows", dim3(nb_rgb_v), dim3(RED_THREADS), k_rgb_step_rows, st, nb_rgb_v, lw, lh, sa2, q, sn);
+                if (h->track_rc == IFX_OK) h->track_rc = ifx_comm_allreduce_f64(h, gacc + row, row);   // (a failed collective: the run is enqueued to its end, the frame call reports it)
+            }
+            LAUNCH(h, "gn_solve_rows", dim3(1), dim3(RED_THREADS), k_gn_solve_rows, st, sa2);
+        }
+    }
+}
+
+// Level i of a run in the other forms: the arguments its launches share and their grids
+struct LevelLaunch {
+    PairArgs pa;
+    int nb, nb_rgb, nbr;            // blocks of the ICP half, of the photometric step, of the residual half
+    const CandEntry* cl;            // the level's candidate list and its count (a list run), nullptr otherwise
+    const unsigned int* cln;
+};
+static LevelLaunch level_launch(const TrackRun& r, int i)
+{
+    ifx* const h = r.h;
+    const Pyr& p = r.p;
+    const bool cand_run = r.plan.cand_run;
+    LevelLaunch L;
+    const int n = p.w[i] * p.h[i];
+    L.nb = red_blocks(h, n);
+    L.nb_rgb = cand_run ? rgb_cand_blocks(h, n, i, true) : std::min(red_blocks(h, n, RED_IT_RGB), h->opt_rgb_blocks > 0 ? h->opt_rgb_blocks : 192);   // the photometric step's launch is dominated by the last block's hand-off and solve: fewer blocks, fewer partial rows (64: 16.9, 192: 15.3, 304: 16.1, 608: 18.5 us per launch)
+    // The residual half of the launch is the slower one and scales with its blocks (its totals go through integer atomics, it has no partial rows for the
+    // last block to sum): one pixel per thread, no loop -- 152 blocks 17.5 us, 304 blocks 13.3 us, 1200 blocks 11.3 us per launch at 640x480 (1053 -> 1102 frames/s).
+    // One round of residency: the launch's blocks (ICP half + residual half) must all be on the GPU at once.  At 640x480 level 0 they were 456 + 1024 = 1480 against the 1024 the GPU holds
+    // (118 VGPRs: 4 blocks per CU), so a third of them started when the first ones left -- and paid the launch's start-up chain (kernel arguments, the previous iteration's totals and
+    // 6x6 solve in every block's prologue, the first loads) a second time: 17.2 -> 14.5 us per level-0 launch with the residual half capped to what is left of one round
+    // (profiles/r05_ai_ab_tracker_blocks.txt: 1514 -> 1561 frames/s).  The halves loop over their pixels anyway (grid-stride); opt_res_blocks > 0 overrides.
+    const int res_round = std::max(128, h->icp_resident_blocks - (r.plan.icp ? L.nb : 0));
+    L.nbr = cand_run ? rgb_cand_blocks(h, n, i, false) : std::min(std::min(cdiv(n, RED_THREADS * RED_IT), h->res_rows), h->opt_res_blocks > 0 ? h->opt_res_blocks : res_round);
+    L.cl = cand_run ? p.cand[i] : nullptr;
+    L.cln = cand_run ? p.cand_n[i] : nullptr;
+    L.pa = pair_args(r, i);
+    L.pa.nb_icp = r.plan.icp ? L.nb : 0; L.pa.nb_res = r.plan.rgb ? L.nbr : 0; L.pa.check_skip = r.frame_tracker ? 0 : 1;
+    return L;
+}
+// all iterations of level i in one persistent launch
+static void emit_persistent_level(TrackRun& r, int i, const PairArgs& pa)
+{
+    ifx* const h = r.h;
+    static const decltype(&k_gn_level<1>) kernel[4] = {k_gn_level<1>, k_gn_level<2>, k_gn_level<3>, k_gn_level<4>};   // (pixels per thread)
+    const LevelArgs la = level_args(pa, r, i);
+    r.persist_iters += r.plan.iterations[i];
+    LAUNCH(h, "gn_level", dim3(r.plan.persist_nb[i]), dim3(RED_THREADS), kernel[r.plan.persist_q[i]], r.st, la);
+    LAUNCH(h, "gn_level_solo", dim3(1), dim3(RED_THREADS), k_gn_level_solo, r.st, la);   // the safety net: a no-op unless a meeting of the launch above did not happen
+    r.ended = r.ended || la.final_level;
+}
+// iteration j of level i as two launches, or as one (a fused iteration of a list run)
+static void emit_iteration(TrackRun& r, int i, int j, const LevelLaunch& L)
+{
+    ifx* const h = r.h;
+    DevState* const st = r.st;
+    const RunPlan& pl = r.plan;
+    const PairArgs& pa = L.pa;
+    const int tail_k = r.tail_k++;
+    // gn_prologue: iteration tail_k sums into set tail_k % 3 (its increment goes to parity tail_k & 1); from the tail's second iteration on, every block first solves the iteration before
+    GnPro gp;
+    gp.k = tail_k; gp.icp = pl.icp; gp.rgb = pl.rgb; gp.icp_weight = r.icp_weight; gp.nfx = pa.fx; gp.nfy = pa.fy; gp.ncx = pa.cx; gp.ncy = pa.cy; gp.ki = kinv_of(pa.fx, pa.fy, pa.cx, pa.cy);
+    const bool it_pro = pl.pro && tail_k < pl.n_pro;
+    const bool fuse = pl.cand_run && it_pro && tail_k < pl.n_pro - 1 && (h->opt_rgb_fuse & (1 << i));   // option rgb_fuse: the step in this launch (every chain iteration but the last, StepArgs::pro == 1)
+    double* const ga = it_pro ? gnp_acc_of(st, tail_k % 3) : gn_acc_of(st);
+    int* const gr = it_pro ? gnp_res_of(st, tail_k % 3) : gn_res_of(st);
+    double* const rrt_store = gnp_rrt_of(st, (tail_k + 1) & 1);   // the increment after iteration tail_k - 1
+    FuseArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    PairArgs paf = pa;
+    if (fuse) {   // G photometric blocks (rgb_fuse_blocks), within one round of residency beside the ICP blocks
+        paf.nb_res = std::max(1, std::min(rgb_fuse_blocks(h, pa.w * pa.h), h->icp_resident_blocks_fuse - pa.nb_icp));
+        const int cs = (tail_k + 1) % 3;
+        fa.cloud = r.p.cloud[i]; fa.sobelScale = (float)GN_SOBEL_SCALE; fa.g = paf.nb_res; fa.poll_ticks = h->opt_rgb_fuse_poll ? RGB_MEET_TICKS : 0u;
+        fa.meet = gnp_meet_of(st, tail_k % 3); fa.clear_acc = gnp_acc_of(st, cs); fa.clear_res = gnp_res_of(st, cs); fa.clear_meet = gnp_meet_of(st, cs);
+        fa.range_ctr = (int*)((char*)st + offsetof(DevState, range_exceeded)); fa.giveups = (int*)((char*)st + offsetof(DevState, rgb_meet_giveups));
+    }
+    LAUNCH(h, icp_name(i), dim3(paf.nb_icp + paf.nb_res), dim3(RED_THREADS), icp_residual_kernel(!r.frame_tracker, it_pro && tail_k > 0, pl.cand_run, fuse), st, paf.nb_icp, paf.w, paf.h, ga, gr, paf,
+           gp, rrt_store, L.cl, L.cln, fa);
+    if (fuse) return;
+    StepArgs sa2 = step_args(r, i, j);
+    sa2.nb = L.nb_rgb; sa2.nb_icp = L.nb; sa2.nb_res = L.nbr; sa2.check_skip = r.frame_tracker ? 0 : 1; sa2.lctr = r.frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr;
+    sa2.pro = it_pro ? (tail_k == pl.n_pro - 1 ? 2 : 1) : 0; sa2.pro_k = tail_k;   // (the chain's last iteration: last-block form; it is the run's last too unless finer levels were too large for the prologue)
+    r.ended = r.ended || sa2.end_run;
+    LAUNCH(h, rgb_name(i), dim3(L.nb_rgb), dim3(RED_THREADS), rgb_step_solve_kernel(!r.frame_tracker, pl.cand_run), st, sa2.nb, sa2.rgb, sa2.w, sa2.h, sa2, L.cl, L.cln);
+}
+
+// getIncrementalTransformation, EF/Utils/RGBDOdometry.cpp:267-603, enqueued without any readback
+static void tracker_run(ifx* h, DevState* st, Pyr& p, float icp_weight, int so3, float weight_mult, int commit, bool frame_tracker, int keep_last = 0)
+{
+    const ifx_config& c = h->cfg;
+    TrackRun r = {h, st, p, icp_weight, weight_mult, commit, frame_tracker, plan_run(h, p, icp_weight, frame_tracker), 0, 0, false};
+    const RunPlan& pl = r.plan;
+    if (frame_tracker && h->gn_begin_folded) h->gn_begin_folded = 0;   // the model side's last launch already did it (ifx_tracker_model_side)
+    else {
+        const float div = (float)(1 << (pl.first < 0 ? 0 : pl.first));
+        LAUNCH(h, "track_gn_begin", dim3(1), dim3(64), k_track_gn_begin, st, h->slot[h->cur_slot].so3, so3, c.fx / div, c.fy / div, c.cx / div, c.cy / div, keep_last, h->opt_gn_persist ? 1 : 0);
+    }
+    if (frame_tracker && h->own && h->opt_own_track_rows && ifx_comm_ready(h) && h->own_track_rank < 0) emit_rows_run(r);
+    else
+        for (int i = IFX_NUM_PYRS - 1; i >= 0; i--) {
+            // The coarse levels are on the queue: the host is now ahead of the GPU by ~20 latency-bound launches, and the
+            // finest level keeps the GPU mostly idle for another ~0.3 ms -- the place to slip in the next frame's image-only work.
+            if (i == 0 && frame_tracker) ifx_enqueue_hinted_frame_side(h);
+            const LevelLaunch L = level_launch(r, i);
+            if (pl.persist_q[i] >= 0) emit_persistent_level(r, i, L.pa);
+            else
+                for (int j = 0; j < pl.iterations[i]; j++) emit_iteration(r, i, j, L);
+        }
+    if (!r.ended)   // (no iteration ran at all: every level has zero iterations)
+        LAUNCH(h, "track_end", dim3(1), dim3(64), k_track_end, st, pl.rgb, 1, weight_mult, commit, frame_tracker ? h->d_list_ctr : (unsigned int*)nullptr);
 }
 
 // frame side of the tracker for the bound slot: frame pyramids, then (unless this is the first frame, which only

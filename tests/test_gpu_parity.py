@@ -746,11 +746,16 @@ def _tracker_variants_equal(ifx, variants):
         g = ifx.ElasticFusion(w=W, h=H, max_surfels=1_000_000, **K)
         for k, v in opts.items():
             g.set_option(k, v)
-        out.append((np.stack([g.processFrame(st["rgb"][i], st["depth"][i]) for i in range(8)]), g.download()))
+        poses, diags = [], []
+        for i in range(8):
+            poses.append(g.processFrame(st["rgb"][i], st["depth"][i]))
+            diags.append(g.tracker_diag())   # after every frame: the run's diagnostics are written by whichever form ran its last iteration
+        out.append((np.stack(poses), g.download(), np.stack(diags).view(np.uint32)))
         g.close()
     for v, other in zip(variants[1:], out[1:]):
         assert np.array_equal(out[0][0], other[0]), (variants[0], v)
         assert all(np.array_equal(out[0][1][k], other[1][k]) for k in MAP_KEYS), (variants[0], v)
+        assert np.array_equal(out[0][2], other[2]), (variants[0], v, np.argwhere(out[0][2] != other[2]).tolist())   # every bit of every frame's diagnostics
 
 
 def test_persistent_level_kernel_is_bit_identical(ifx):
