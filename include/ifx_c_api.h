@@ -266,6 +266,9 @@ int ifx_tracker_fallbacks(ifx_t* h);
 int ifx_tracker_range_exceeded(ifx_t* h);
 /* photometric blocks of fused tracker iterations (option "rgb_fuse") that stopped waiting at their bounded meeting since ifx_create (0 in a healthy run; the poses do not depend on it) */
 int ifx_tracker_meet_giveups(ifx_t* h);
+/* shares of such blocks that the last arriver of the meeting stepped in their place (option "rgb_own": a block steps the records it wrote, and one that leaves hands them
+ * over); equal to ifx_tracker_meet_giveups while every fused launch runs that form, 0 in a healthy run */
+int ifx_tracker_meet_adopted(ifx_t* h);
 
 /* ---- local loop-closure DETECTION (the closeLoops / countThresh / errThresh / covThresh constructor arguments, EF/ElasticFusion.h:48-51;
  * EF/ElasticFusion.cpp:453-566 with no fern match).  When enabled every tracked frame also runs predict() at the new pose, the INACTIVE
@@ -377,6 +380,10 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           residual launch (its photometric blocks meet, bounded, and step the records by claimed chunks); same bits.  0: two launches per
  *                           iteration.  "rgb_fuse_poll" 0 (test switch) -- no block waits at that meeting: the last arriver steps every chunk alone
  *                           (ifx_tracker_meet_giveups counts the blocks that left)
+ *   "rgb_own" mask        -- a bit per pyramid level: in a fused iteration ("rgb_fuse") every photometric block steps the records it wrote itself, the first of
+ *                           each thread from registers, instead of claiming chunks; a block that stops waiting at the meeting hands its share to the last
+ *                           arriver (ifx_tracker_meet_adopted); same bits.  0: chunk claims.  Launches with more than 64 photometric blocks ("rgb_blocks")
+ *                           run the chunk form
  *   "gn_prologue" 0       -- the 6x6 solve of an iteration by the last block of its second launch (round 3's form) instead of by every block of the next
  *                           iteration's first launch; "gn_prologue_blocks" n -- the prologue form only for launches of at most n blocks (default 2048)
  *   "fold_result" 0       -- the frame result by a launch of its own instead of the last block of the prediction's resolve

@@ -158,6 +158,7 @@ _SIGS = {
     "ifx_build_pyramids": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(Pyramids)]),
     "ifx_tracker_range_exceeded": (C.c_int, [_P]),
     "ifx_tracker_meet_giveups": (C.c_int, [_P]),
+    "ifx_tracker_meet_adopted": (C.c_int, [_P]),
     "ifx_hot_records_stale": (C.c_int, [_P]),
     "ifx_set_loop_closure": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float]),
     "ifx_loop_closure_diag": (C.c_int, [_P, _P]),
@@ -460,6 +461,10 @@ class ElasticFusion(_DetectorOperators):
     def tracker_meet_giveups(self):
         """photometric blocks of fused tracker iterations (option rgb_fuse) that stopped waiting at their bounded meeting so far (0 in a healthy run)"""
         return self._chk(self.L.ifx_tracker_meet_giveups(self.handle), "ifx_tracker_meet_giveups")
+
+    def tracker_meet_adopted(self):
+        """shares of such blocks that the last arriver stepped in their place (option rgb_own; equal to tracker_meet_giveups() in that form, 0 in a healthy run)"""
+        return self._chk(self.L.ifx_tracker_meet_adopted(self.handle), "ifx_tracker_meet_adopted")
 
     # -- local loop-closure detection (closeLoops, countThresh, errThresh, covThresh of the reference constructor)
     def set_loop_closure(self, enable=True, count_thresh=35000, err_thresh=5e-5, cov_thresh=1e-5):

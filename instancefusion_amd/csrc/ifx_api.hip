@@ -414,6 +414,12 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
         h->opt_rgb_fuse = value;
     }
     else if (s == "rgb_fuse_poll") { ifx_drop_tracked(h); h->opt_rgb_fuse_poll = value ? 1 : 0; }
+    // fused iterations: the photometric blocks step the records they wrote themselves (k_icp_residual<.., FUSE, OWN>), a bit per pyramid level; 0: they claim chunks
+    else if (s == "rgb_own") {
+        if (value < 0 || value > 7) { h->err = "rgb_own is a mask of pyramid levels (0..7)"; return IFX_E_INVALID; }
+        ifx_drop_tracked(h);
+        h->opt_rgb_own = value;
+    }
     else if (s == "raster_lds") h->opt_raster_lds = value;
     else if (s == "raster_earlyz") h->opt_raster_earlyz = value;
     // ElasticFusion::setPyramid / setFastOdom / setSo3 / setIcpWeight (EF/ElasticFusion.h:153-176): tracker configuration from the next frame on;
@@ -1338,7 +1344,7 @@ extern "C" int ifx_hot_records_stale(ifx_t* h)
 // Photometric blocks of fused iterations (option rgb_fuse) that stopped waiting at the meeting since ifx_create: the step was then done by the blocks that did meet (the
 // last arriver always does), so the poses are what they would have been -- the count says that the form did not run as designed (a photometric block was not resident
 // in time), or that the test switch rgb_fuse_poll = 0 is set.  Summed over the handle's tracker instances that can run a list run.  Waits for the frames in flight.
-extern "C" int ifx_tracker_meet_giveups(ifx_t* h)
+static int ifx_tracker_meet_counter(ifx_t* h, size_t offset)
 {
     if (!h) return IFX_E_INVALID;
     int r = ifx_sync(h);
@@ -1349,11 +1355,15 @@ extern "C" int ifx_tracker_meet_giveups(ifx_t* h)
     for (const DevState* d : {(const DevState*)h->d_state, (const DevState*)h->d_cam_trk}) {
         if (!d) continue;
         int v = 0;
-        HIPCHK(h, hipMemcpy(&v, (const char*)d + offsetof(DevState, rgb_meet_giveups), sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&v, (const char*)d + offset, sizeof(int), hipMemcpyDeviceToHost));
         total += v;
     }
     return (int)std::min<long long>(total, 0x7FFFFFFF);
 }
+extern "C" int ifx_tracker_meet_giveups(ifx_t* h) { return ifx_tracker_meet_counter(h, offsetof(DevState, rgb_meet_giveups)); }
+// Own-records form (option rgb_own): shares of blocks that had stopped waiting which the last arriver stepped in their place.  Every block that leaves such a launch
+// has its share adopted, so the two counters are equal while every fused launch runs that form.
+extern "C" int ifx_tracker_meet_adopted(ifx_t* h) { return ifx_tracker_meet_counter(h, offsetof(DevState, rgb_meet_adopted)); }
 extern "C" int ifx_tracker_range_exceeded(ifx_t* h)
 {
     if (!h) return IFX_E_INVALID;

@@ -92,9 +92,10 @@ struct DevState {
     // clears set (j + 1) % 3, whose last readers (the prologues of iteration j - 1) are complete by stream order.  Every set is zero when a run starts.
     alignas(64) double gnp_acc[3 * 2 * IFX_ACC_REPL * IFX_ACC_STRIDE];   // [set][ICP | photometric]
     alignas(64) int gnp_res[3 * 16];                                     // [set] (count, sigma), a line each
-    alignas(64) unsigned int gnp_meet[3 * 32];                           // [set] fused iteration (rgb_fuse): arrivals of the photometric blocks at [0], next unclaimed chunk of the step at [16]: a line each
+    alignas(64) unsigned int gnp_meet[3 * 32];                           // [set] fused iteration (rgb_fuse): arrivals of the photometric blocks at [0], next unclaimed chunk of the step at [16]: a line each; own-records form (rgb_own): 64-bit orphan mask at [18], taken mask at [20]
     alignas(64) double gnp_RRt[2][16];
     int rgb_meet_giveups;                                                // photometric blocks of fused iterations that stopped waiting for the others (bounded meeting; ifx_tracker_meet_giveups): 0 in a healthy run unless rgb_fuse_poll = 0
+    int rgb_meet_adopted;                                                // own-records form (rgb_own): shares of such blocks that the last arriver stepped in their place (ifx_tracker_meet_adopted): equal to the give-ups of that form
 };
 
 // Ids in the id images are slot indices on an unsharded map and creation numbers on a spatially sharded one (ifx_map.hip, key_id / local_slot):
@@ -402,6 +403,9 @@ struct ifx {
                                      // share `corres` with the list form (a persistent level: gn_persist; the row-sharded reductions: own_track_rows) is dense as a whole
     int opt_rgb_fuse = 7;            // a bit per pyramid level (list runs, prologue chain): the photometric step of an iteration runs inside its residual launch -- the photometric
                                      // blocks meet after their residual pass and step the records by claimed chunks (k_icp_residual<.., FUSE>).  0: two launches per iteration
+    int opt_rgb_own = 7;             // a bit per pyramid level (fused iterations): the photometric blocks step the records they wrote themselves -- the first from registers, no claim,
+                                     // a block that stops waiting hands its share to the last arriver (k_icp_residual<.., FUSE, OWN>, ifx_rgb_own.h).  0: chunk claims.  A launch
+                                     // with more than RGB_OWN_MAX_G photometric blocks runs the chunk form
     int opt_rgb_fuse_poll = 1;       // test switch: 0 = no photometric block of a fused launch waits at the meeting (all but the last arriver leave at once; it steps every chunk alone)
     int icp_resident_blocks_fuse = 1024;   // icp_resident_blocks of the fused variant
     int opt_icp_blocks = 0;          // cap on the blocks of a tracker reduction launch; 0 = by image size (ifx_track.hip red_blocks)

@@ -10,6 +10,7 @@
 //  * the 13x13 bilateral stages its depth tile through LDS.
 #include "ifx_ctx.h"
 #include "ifx_rgb_chunks.h"
+#include "ifx_rgb_own.h"
 #include <math.h>
 #include <string.h>
 
@@ -920,12 +921,17 @@ __global__ __launch_bounds__(RED_THREADS) void k_rgb_residual(const DevState* __
 // Three entries deep: the gathers of this round, the own-pixel loads of the next and the entry of the round after are in flight together; no load sits behind a branch.
 // SC1 (the fused iteration, k_icp_residual<.., FUSE>): the records are read back by OTHER workgroups of the same launch, so each goes out as one 8-byte agent-scope
 // store (write-through).  Returns the count the block ran over.
-template <bool PRO, bool SC1 = false>
+// OWN (the own-records form of the fused iteration, option rgb_own): the thread keeps what the step needs of its first-round candidate -- the record, the entry's
+// gradients and, requested behind the record's store, the cloud point of the hit (it depends on (zx, zy) alone, and no block of the launch writes the cloud).
+struct RgbOwn { Corres8 c; int16_t gx, gy; float X, Y, Z; };   // c.zx < 0: no first-round record, or not a hit
+template <bool PRO, bool SC1 = false, bool OWN = false>
 __device__ __forceinline__ int residual_cand_body(int bid, int nblk, const DevState* __restrict__ st, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n,
                                                    const float* __restrict__ lastDepth, const float* __restrict__ nextDepth, const uint8_t* __restrict__ lastImage,
                                                    const uint8_t* __restrict__ nextImage, Corres8* __restrict__ corres, float maxDepthDelta, int w, int h,
-                                                   int* __restrict__ res_total, const GnPro* pro, double* __restrict__ rrt_out)
+                                                   int* __restrict__ res_total, const GnPro* pro, double* __restrict__ rrt_out, const float* __restrict__ cloud = nullptr,
+                                                   RgbOwn* own = nullptr)
 {
+    static_assert(!OWN || SC1, "the own-records form is a form of the fused iteration");
     const int N = w * h;   // the list's capacity
     const int stride = nblk * RED_THREADS;
     int t = bid * RED_THREADS + threadIdx.x;
@@ -944,6 +950,8 @@ __device__ __forceinline__ int residual_cand_body(int bid, int nblk, const DevSt
     for (int k = 0; k < 9; k++) krk[k] = kk[k];
     const float kt0 = ktp[0], kt1 = ktp[1], kt2 = ktp[2];
     int cnt = 0, sig = 0;
+    bool first = OWN;
+    if (OWN) { own->c.zx = -1; own->c.zy = -1; own->c.diff = 0.f; own->gx = e0.gx; own->gy = e0.gy; own->X = own->Y = own->Z = 0.f; }
     while (t < n) {
         // stage 2: warp into the last image
         const int i = pix / w, j0 = pix - i * w;
@@ -972,6 +980,12 @@ __device__ __forceinline__ int residual_cand_body(int bid, int nblk, const DevSt
             __builtin_memcpy(&bits, &c, 8);
             __hip_atomic_store(reinterpret_cast<unsigned long long*>(corres + t), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else corres[t] = c;
+        if (OWN && first) {   // round 0, t = bid * RED_THREADS + threadIdx.x: kept for the step, its cloud point on the way behind the store
+            first = false;
+            own->c = c;
+            const int g = hit ? gj * 3 : 0;
+            own->X = cloud[g]; own->Y = cloud[g + 1]; own->Z = cloud[g + 2];
+        }
         t = tn; pix = pixn; d1 = d1n; ni = nin; e1 = e2;
     }
     __shared__ int lds[RED_WAVES][2];
@@ -1010,13 +1024,17 @@ struct FuseArgs {
     float sobelScale;
     int g;                       // photometric blocks of the launch: they take the FIRST block ids (they are the launch's critical chain), the ICP blocks follow
     unsigned int poll_ticks;     // RGB_MEET_TICKS; 0 (test switch rgb_fuse_poll = 0): nobody waits -- every block but the last arriver leaves at once
-    unsigned int* meet;          // this iteration's set of DevState::gnp_meet: [0] arrivals, [16] next unclaimed chunk
+    unsigned int* meet;          // this iteration's set of DevState::gnp_meet: [0] arrivals, [16] next unclaimed chunk; own-records form: 64-bit orphan mask at [18], taken mask at [20]
     double* clear_acc;           // set (k + 1) % 3 of gnp_acc / gnp_res / gnp_meet, cleared by the launch's last block ...
     int* clear_res;
     unsigned int* clear_meet;
     int* range_ctr;              // ... with the range guard on the totals it clears (DevState::range_exceeded)
     int* giveups;                // DevState::rgb_meet_giveups
+    int* adopted;                // DevState::rgb_meet_adopted (own-records form: shares the last arriver stepped for blocks that had left)
 };
+#define RGB_MEET_ORPHAN 18   // words of a set of gnp_meet (own-records form): the 64-bit orphan mask, a bit per photometric block that stopped waiting, ...
+#define RGB_MEET_TAKEN 20    // ... and the 64-bit taken mask: whose bit is set here has had its share claimed, by the last arriver or by the block itself
+static_assert(RGB_MEET_ORPHAN % 2 == 0 && RGB_MEET_TAKEN == RGB_MEET_ORPHAN + 2 && RGB_MEET_ORPHAN > 16 && RGB_MEET_TAKEN + 2 <= 32, "two aligned 64-bit words in the set's second line");
 static_assert(sizeof(Corres8) == 8, "a record is handed over as one 8-byte store");
 // One set of the prologue chain's rotation back to zero, with the run-time guard of the exact sums (range_exceeded7) on the totals it held -- here, where they are
 // cleared, because the prologues that consumed them sit in a launch that has no register to spare.  A whole block; its last readers are complete by stream order.
@@ -1031,6 +1049,8 @@ __device__ __forceinline__ void gnp_clear_set(double* acc, int* res, unsigned in
     __hip_atomic_store(&acc[threadIdx.x], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x < 2) __hip_atomic_store(&res[threadIdx.x], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x >= 64 && threadIdx.x < 66) __hip_atomic_store(&meet[(threadIdx.x - 64) * 16], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x >= 128 && threadIdx.x < 130)   // the own-records form's orphan and taken masks
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(meet + RGB_MEET_ORPHAN) + (threadIdx.x - 128), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // (b) to (d) of a photometric block, behind its residual pass over `n_wave` records.  The count is read by every wave for itself, and under a dropped run whose slot is
 // being rewritten two waves of one block may have read different counts: everything block-wide below -- the early exit, the chunk loop with its barriers -- runs on
@@ -1111,6 +1131,135 @@ __device__ __forceinline__ void rgb_fused_step(int bid, int n_wave, Corres8* cor
     block_sum_exact<29>(acc, rgb_acc, bid % IFX_ACC_REPL);
 }
 
+// The own-records form of (b) to (d) (option rgb_own, k_icp_residual<.., FUSE, OWN>; f.g <= RGB_OWN_MAX_G).  The chunk form above re-fetches, behind the meeting, what
+// the same threads held a few microseconds earlier: a claim, the records, the entries, then the cloud points -- three memory-side round trips in a row on the
+// launch's critical chain.  Here block b steps the records it wrote (ifx_rgb_own.h: thread t has b * 256 + t + k * G * 256 < n): round 0 from the registers of its
+// residual pass, cloud point included (residual_cand_body<.., OWN>), so behind the meeting only the totals for sigma are loaded; rounds k >= 1 are read back as the
+// chunk form reads its chunks, RGB_OWN_IT records in flight per thread.  There is no claim and meet[16] is unused.  A static assignment gives the same bits as the
+// claims do, for the same reason: exact sums of grid-valued terms.
+// The arrival, the drain in front of it and the bounded wait are the chunk form's, and so are the four rules of the hand-off.  What the claims gave for free -- every
+// record is stepped whoever left -- takes two words here, the set's orphan mask and taken mask (a bit per block, cleared with the set):
+//   a block b whose wait runs out ORs its bit into the orphan mask with a returning atomic, waits for the result and loads the arrival word once more.  Still
+//   incomplete: it counts a give-up and leaves.  Complete: it ORs its bit into the taken mask; if the bit was set already the last arriver has its share and it
+//   leaves (a give-up too), if not it goes on as a block that met.
+//   The block that draws the last arrival never waits.  It loads the orphan mask beside the totals, steps its own share, ORs the bits it saw into the taken mask and
+//   steps, from memory, the shares whose bits it was the first to set (counted in DevState::rgb_meet_adopted: give-ups and adopted shares are equal).
+// No share is lost: a block leaves only after it saw the meeting incomplete BEHIND its own performed OR, so the last arrival and the last arriver's load of the mask,
+// issued after that arrival's result returned, come later and see the bit.  None is stepped twice: an OR performed after that load is followed by a re-load that sees
+// the meeting complete, the block takes its share back itself, and where both reach for a share ONE atomic on the taken mask decides.  The host model of the
+// protocol runs every interleaving (tests/cpp/rgb_own_check.cpp).  A dropped run may see any count: shares are clamped by rgb_chunk_n, everything block-wide runs
+// on thread 0's count, the per-thread loops hold no barrier, and nothing waits unbounded.
+__device__ __forceinline__ void rgb_own_step(int bid, int n_wave, const RgbOwn& own, Corres8* corres, const CandEntry* __restrict__ cand, int w, int h, float fx, float fy, int* res_total,
+                                             double* __restrict__ rgb_acc, const FuseArgs& f)
+{
+    __shared__ int s_go, s_n;
+    __shared__ unsigned int s_adopt[2];
+    unsigned long long* const orphan = reinterpret_cast<unsigned long long*>(f.meet + RGB_MEET_ORPHAN);
+    unsigned long long* const taken = reinterpret_cast<unsigned long long*>(f.meet + RGB_MEET_TAKEN);
+    // (b) arrival: this block's records and its adds to the totals have been performed at the memory side before anybody can count it in
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int all = (unsigned int)f.g;
+        const unsigned long long bit = 1ull << (bid & 63);
+        const unsigned int t = __hip_atomic_fetch_add(&f.meet[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int go = t + 1u >= all ? 2 : 0;   // 2: the last arriver goes on at once
+        if (!go) {                        // (c) everybody else polls one word, relaxed, until all have arrived or the bound has passed
+            if (f.poll_ticks) {
+                const unsigned long long t0 = wall_clock64();
+                for (;;) {
+                    if (__hip_atomic_load(&f.meet[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= all) { go = 1; break; }
+                    if (wall_clock64() - t0 > (unsigned long long)f.poll_ticks) break;
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            }
+            if (!go) {   // the wait ran out: the share is handed over -- or taken back
+                const unsigned long long before = __hip_atomic_fetch_or(orphan, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::"v"(before) : "memory");   // the OR's result is here: it has been performed before the arrival word is looked at again
+                if (__hip_atomic_load(&f.meet[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= all)
+                    go = (__hip_atomic_fetch_or(taken, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) ? 0 : 1;
+                if (!go) atomicAdd(f.giveups, 1);
+            }
+        }
+        s_go = go;
+        s_n = n_wave;
+    }
+    __syncthreads();
+    const int go = __builtin_amdgcn_readfirstlane(s_go);
+    if (!go) return;
+    const bool last = go == 2;
+    const int n = __builtin_amdgcn_readfirstlane(s_n);   // the block's count: uniform over its waves
+    const int g = f.g;
+    // (d) every block that is here has seen all G arrivals: the totals are complete and every record of [0, n) is in memory
+    if (!last && rgb_own_block_rounds(n, g, bid) == 0) return;   // no record of its own, nobody's to adopt (uniform over the block)
+    const int r_cnt = __hip_atomic_load(&res_total[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), r_sig = __hip_atomic_load(&res_total[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long orph = 0;   // the last arriver: who has left, in the same round trip (its arrival's result came back before s_go was written)
+    if (last && threadIdx.x == 0) orph = __hip_atomic_load(orphan, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float sigma = rgb_sigma(r_cnt, r_sig);
+    double acc[29];
+#pragma unroll
+    for (int k = 0; k < 29; k++) acc[k] = 0.0;
+    // a record counts only if its coordinates lie in the image (rgb_fused_step: changes no record that this iteration's residual pass wrote)
+    auto in_image = [&](const Corres8& c) { return (c.zx >= 0) & (c.zx < w) & (c.zy >= 0) & (c.zy < h); };
+    {   // round 0: the thread's own record, entry and cloud point, from registers
+        float row[7] = {0, 0, 0, 0, 0, 0, 0};
+        const bool found = in_image(own.c);
+        if (found) rgb_row(row, sigma, own.c.diff, own.gx, own.gy, own.X, own.Y, own.Z, fx, fy, f.sobelScale);
+        products7<1>(row, found, acc);
+    }
+    // rounds k0 .. of block b's share, read back with agent-scope loads (a round past the thread's last reads the round before and drops it: no branch around the loads)
+    auto step_share = [&](int b, int k0) {
+        const int first = rgb_own_first(b, (int)threadIdx.x);
+        const int rounds = rgb_own_rounds(n, g, first);
+        for (int k = k0; k < rounds; k += RGB_OWN_IT) {
+            Corres8 c[RGB_OWN_IT];
+            CandEntry e[RGB_OWN_IT];
+#pragma unroll
+            for (int u = 0; u < RGB_OWN_IT; u++) {
+                const bool in = k + u < rounds;
+                const int kk = rgb_own_record(g, first, in ? k + u : k);
+                const unsigned long long bits = __hip_atomic_load(reinterpret_cast<unsigned long long*>(corres + kk), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __builtin_memcpy(&c[u], &bits, 8);
+                e[u] = cand[kk];
+                if (!in) c[u].zx = -1;
+            }
+            float X[RGB_OWN_IT], Y[RGB_OWN_IT], Z[RGB_OWN_IT];
+#pragma unroll
+            for (int u = 0; u < RGB_OWN_IT; u++) {
+                if (!in_image(c[u])) c[u].zx = -1;
+                const int gi = (c[u].zx >= 0) ? ((int)c[u].zy * w + (int)c[u].zx) * 3 : 0;
+                X[u] = f.cloud[gi]; Y[u] = f.cloud[gi + 1]; Z[u] = f.cloud[gi + 2];
+            }
+#pragma unroll
+            for (int u = 0; u < RGB_OWN_IT; u++) {
+                float row[7] = {0, 0, 0, 0, 0, 0, 0};
+                const bool found = c[u].zx >= 0;
+                if (found) rgb_row(row, sigma, c[u].diff, e[u].gx, e[u].gy, X[u], Y[u], Z[u], fx, fy, f.sobelScale);
+                products7<1>(row, found, acc);
+            }
+        }
+    };
+    step_share(bid, 1);
+    if (last) {   // the shares of the blocks that left: one OR for all the bits it saw, the ones it was first to set are its own now
+        if (threadIdx.x == 0) {
+            unsigned long long mine = 0;
+            if (orph) {
+                mine = orph & ~__hip_atomic_fetch_or(taken, orph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (mine) atomicAdd(f.adopted, __popcll(mine));
+            }
+            s_adopt[0] = (unsigned int)mine; s_adopt[1] = (unsigned int)(mine >> 32);
+        }
+        __syncthreads();
+        unsigned long long mine = (unsigned long long)__builtin_amdgcn_readfirstlane(s_adopt[0]) | ((unsigned long long)__builtin_amdgcn_readfirstlane(s_adopt[1]) << 32);
+        while (mine) {
+            const int o = __ffsll((long long)mine) - 1;
+            mine &= mine - 1;
+            if (o < g) step_share(o, 0);
+        }
+    }
+    block_sum_exact<29>(acc, rgb_acc, bid % IFX_ACC_REPL);
+}
+
 // One launch for the two independent reductions of a Gauss-Newton iteration: blocks [0, nb_icp) run the
 // ICP reduction, blocks [nb_icp, nb_icp + nb_res) the photometric residual pass.
 struct PairArgs {
@@ -1131,17 +1280,24 @@ struct PairArgs {
 // LIST (option rgb_cand): the residual half runs over the frame slot's candidate list `cand` / `cand_n` (residual_cand_body); the two arguments are unused otherwise
 // FUSE (option rgb_fuse, list runs only): the iteration's photometric step runs in this launch too (rgb_fused_step above; `f` is unused otherwise).  The a.nb_res
 // photometric blocks take the first block ids, the ICP blocks follow; block 0 stays the one publisher of `rrt_store`; the launch's last block first clears the next set.
-template <bool CHECK_SKIP, bool PRO = false, bool LIST = false, bool FUSE = false>
+// OWN (option rgb_own, fused iterations only): the photometric blocks step the records they wrote themselves (rgb_own_step) instead of claiming chunks.
+template <bool CHECK_SKIP, bool PRO = false, bool LIST = false, bool FUSE = false, bool OWN = false>
 __global__ __launch_bounds__(RED_THREADS, 4) void k_icp_residual(const DevState* __restrict__ st, int nb_icp, int w, int h, double* __restrict__ gacc, int* __restrict__ gres, PairArgs a, GnPro g,
                                                               double* __restrict__ rrt_store, const CandEntry* __restrict__ cand, const unsigned int* __restrict__ cand_n, FuseArgs f)
 {
     static_assert(!FUSE || LIST, "the fused iteration runs over the candidate list");
+    static_assert(!OWN || FUSE, "the own-records form is a form of the fused iteration");
     if (FUSE) {
         __builtin_assume(st != nullptr);
         if (CHECK_SKIP && st->skip) return;
         const int nb_rgb = (int)gridDim.x - nb_icp;   // (= a.nb_res = f.g, without a load)
         if (blockIdx.x == gridDim.x - 1) gnp_clear_set(f.clear_acc, f.clear_res, f.clear_meet, f.range_ctr);
-        if ((int)blockIdx.x < nb_rgb) {
+        if (OWN && (int)blockIdx.x < nb_rgb) {
+            RgbOwn own;
+            const int n = residual_cand_body<PRO, true, true>(blockIdx.x, nb_rgb, st, cand, cand_n, a.lastDepth, a.nextDepth, a.lastImage, a.nextImage, a.corres, a.maxDepthDelta, w, h, gres, &g,
+                                                              blockIdx.x == 0 ? rrt_store : nullptr, f.cloud, &own);
+            rgb_own_step(blockIdx.x, n, own, a.corres, cand, w, h, a.fx, a.fy, gres, gacc + IFX_ACC_REPL * IFX_ACC_STRIDE, f);
+        } else if ((int)blockIdx.x < nb_rgb) {
             const int n = residual_cand_body<PRO, true>(blockIdx.x, nb_rgb, st, cand, cand_n, a.lastDepth, a.nextDepth, a.lastImage, a.nextImage, a.corres, a.maxDepthDelta, w, h, gres, &g,
                                                         blockIdx.x == 0 ? rrt_store : nullptr);
             rgb_fused_step(blockIdx.x, n, a.corres, cand, w, h, a.fx, a.fy, gres, gacc + IFX_ACC_REPL * IFX_ACC_STRIDE, f);   // (the totals are read back with agent-scope loads)
@@ -2592,6 +2748,9 @@ int ifx_alloc_tracker(ifx* h)
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_ir, k_icp_residual<false, true>, RED_THREADS, 0) == hipSuccess && occ_ir > 0 && cus > 0) h->icp_resident_blocks = occ_ir * cus;
         int occ_fu = 0;   // ... and of the fused variant (option rgb_fuse), whose photometric blocks meet inside the launch
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_fu, k_icp_residual<false, true, true, true>, RED_THREADS, 0) == hipSuccess && occ_fu > 0 && cus > 0) h->icp_resident_blocks_fuse = occ_fu * cus;
+        int occ_own = 0;   // ... in either form of its step (option rgb_own)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_own, k_icp_residual<false, true, true, true, true>, RED_THREADS, 0) == hipSuccess && occ_own > 0 && cus > 0)
+            h->icp_resident_blocks_fuse = std::min(h->icp_resident_blocks_fuse, occ_own * cus);
     }
     h->res_rows = std::max(maxb, cdiv(h->P, RED_THREADS) + 1);   // the residual pass runs one block per 256 pixels
     HIPCHK(h, hipMalloc(&h->res_partials, (size_t)h->res_rows * 2 * 4));
@@ -2782,16 +2941,16 @@ static inline const char* icp_name(int level) { static const char* const n[3] = 
 static inline const char* rgb_name(int level) { static const char* const n[3] = {"rgb_step_solve@L0", "rgb_step_solve@L1", "rgb_step_solve@L2"}; return n[level]; }
 
 // The instantiation of an iteration's first launch for a run's booleans.  CHECK_SKIP: the model-to-model tracker checks the skip flag; PRO: from the prologue chain's
-// second iteration on every block first solves the iteration before; LIST: the residual half runs over the candidate list; FUSE (list runs only): the step too.
+// second iteration on every block first solves the iteration before; LIST: the residual half runs over the candidate list; FUSE (list runs only): the step too; OWN (fused only): in the own-records form.
 using IcpResidualKernel = decltype(&k_icp_residual<false>);
-static IcpResidualKernel icp_residual_kernel(bool check_skip, bool pro, bool list, bool fuse)
+static IcpResidualKernel icp_residual_kernel(bool check_skip, bool pro, bool list, bool fuse, bool own)
 {
-    static const IcpResidualKernel k[2][2][3] = {
-        {{k_icp_residual<false, false>, k_icp_residual<false, false, true>, k_icp_residual<false, false, true, true>},
-         {k_icp_residual<false, true>, k_icp_residual<false, true, true>, k_icp_residual<false, true, true, true>}},
-        {{k_icp_residual<true, false>, k_icp_residual<true, false, true>, k_icp_residual<true, false, true, true>},
-         {k_icp_residual<true, true>, k_icp_residual<true, true, true>, k_icp_residual<true, true, true, true>}}};
-    return k[check_skip][pro][fuse ? 2 : list ? 1 : 0];
+    static const IcpResidualKernel k[2][2][4] = {
+        {{k_icp_residual<false, false>, k_icp_residual<false, false, true>, k_icp_residual<false, false, true, true>, k_icp_residual<false, false, true, true, true>},
+         {k_icp_residual<false, true>, k_icp_residual<false, true, true>, k_icp_residual<false, true, true, true>, k_icp_residual<false, true, true, true, true>}},
+        {{k_icp_residual<true, false>, k_icp_residual<true, false, true>, k_icp_residual<true, false, true, true>, k_icp_residual<true, false, true, true, true>},
+         {k_icp_residual<true, true>, k_icp_residual<true, true, true>, k_icp_residual<true, true, true, true>, k_icp_residual<true, true, true, true, true>}}};
+    return k[check_skip][pro][fuse ? (own ? 3 : 2) : list ? 1 : 0];
 }
 // ... and of its second launch
 using RgbStepSolveKernel = decltype(&k_rgb_step_solve<false>);
@@ -3039,8 +3198,11 @@ static void emit_iteration(TrackRun& r, int i, int j, const LevelLaunch& L)
         fa.cloud = r.p.cloud[i]; fa.sobelScale = (float)GN_SOBEL_SCALE; fa.g = paf.nb_res; fa.poll_ticks = h->opt_rgb_fuse_poll ? RGB_MEET_TICKS : 0u;
         fa.meet = gnp_meet_of(st, tail_k % 3); fa.clear_acc = gnp_acc_of(st, cs); fa.clear_res = gnp_res_of(st, cs); fa.clear_meet = gnp_meet_of(st, cs);
         fa.range_ctr = (int*)((char*)st + offsetof(DevState, range_exceeded)); fa.giveups = (int*)((char*)st + offsetof(DevState, rgb_meet_giveups));
+        fa.adopted = (int*)((char*)st + offsetof(DevState, rgb_meet_adopted));
     }
-    LAUNCH(h, icp_name(i), dim3(paf.nb_icp + paf.nb_res), dim3(RED_THREADS), icp_residual_kernel(!r.frame_tracker, it_pro && tail_k > 0, pl.cand_run, fuse), st, paf.nb_icp, paf.w, paf.h, ga, gr, paf,
+    // option rgb_own: the photometric blocks step the records they wrote (a bit per block in the set's two mask words: a launch with more blocks runs the chunk form)
+    const bool own = fuse && (h->opt_rgb_own & (1 << i)) && paf.nb_res <= RGB_OWN_MAX_G;
+    LAUNCH(h, icp_name(i), dim3(paf.nb_icp + paf.nb_res), dim3(RED_THREADS), icp_residual_kernel(!r.frame_tracker, it_pro && tail_k > 0, pl.cand_run, fuse, own), st, paf.nb_icp, paf.w, paf.h, ga, gr, paf,
            gp, rrt_store, L.cl, L.cln, fa);
     if (fuse) return;
     StepArgs sa2 = step_args(r, i, j);

@@ -6,7 +6,8 @@
 #   NAME=value      an environment variable (upper case)     e.g. IFX_OPTS=..., HIP_FORCE_DEV_KERNARG=0
 #   lib:PATH        another build of libifx.so               (IFX_LIB=PATH; "lib:variant" = the library -b built)
 #   tree:NAME       bench.py and library of another commit, exported and built under tools/ab/NAME
-#                   (git archive <commit> bench.py instancefusion_amd include | tar -x -C tools/ab/NAME; make -C tools/ab/NAME/instancefusion_amd/csrc)
+#                   (git archive <commit> bench.py instancefusion_amd include tests oracle | tar -x -C tools/ab/NAME; make -C tools/ab/NAME/instancefusion_amd/csrc;
+#                   make -C tools/ab/NAME/oracle all -- bench.py imports the oracle's binding from tests/ whatever its arguments)
 # -w: driver = the driver-shaped window (20 steps after 5, one segmentation call inside), long = 200 steps after 30 (default), full = the default run with every extra leg.
 # -b: compile SRC.hip (e.g. ifx_track, or "ifx_track ifx_map") with the extra flags into scratch objects and link /tmp/libifx_variant.so; the in-tree library is not touched.
 cd ${GRAFT_REPO_ROOT:-$(dirname "$0")/..}

@@ -1,6 +1,7 @@
 """What option "rgb_fuse" costs or saves on a frame whose candidate list is long: the 320x240 test stream with a colour image of uniform noise (about 52 200
-candidates at level 0: a hundred chunks for the fused form's 32 photometric blocks) and, for comparison, with its own colour images.  Per form (rgb_fuse = 7 / 0,
-alternating): HIP-event time (option kernel_timing) of the tracker's iteration launches per frame, per level, and the meeting give-ups.
+candidates at level 0: a hundred chunks, or six to seven rounds per thread, for the fused form's 32 photometric blocks) and, for comparison, with its own colour
+images.  Per form (rgb_fuse = 7 with rgb_own = 7, rgb_fuse = 7 with rgb_own = 0 -- the chunk claims --, rgb_fuse = 0; alternating, two runs each): HIP-event time
+(option kernel_timing) of the tracker's iteration launches per frame, per level, the meeting give-ups and the adopted shares.
 
     python tools/rgb_fuse_cost.py [frames] [rgb_blocks: photometric blocks of the fused launches, 0 = the default]"""
 import os
@@ -24,9 +25,9 @@ NOISE = np.random.RandomState(1234).randint(0, 256, (H, W, 3)).astype(np.uint8)
 NAMES = [f"{fam}@L{l}" for fam in ("icp_residual", "rgb_step_solve") for l in range(3)]
 
 
-def run(fuse, noise):
+def run(fuse, own, noise):
     ef = ifx.ElasticFusion(w=W, h=H, max_surfels=400000, confidence=3.0, **K)
-    ef.set_option("gn_persist", 0); ef.set_option("rgb_fuse", fuse)
+    ef.set_option("gn_persist", 0); ef.set_option("rgb_fuse", fuse); ef.set_option("rgb_own", own)
     if blocks and fuse:
         ef.set_option("rgb_blocks", blocks)
     order = list(range(12)) + list(range(10, 0, -1))
@@ -41,14 +42,14 @@ def run(fuse, noise):
     ef.sync()
     t = {nm: ef.kernel_ms(nm) for nm in NAMES}
     cand = [int(ef.tracker_buffer("cand_n", lvl)[0]) for lvl in range(3)]
-    gu = ef.tracker_meet_giveups()
+    gu, ad = ef.tracker_meet_giveups(), ef.tracker_meet_adopted()
     ef.close()
     per_frame = sum(avg * cnt for avg, cnt in t.values()) / frames * 1e3
-    return per_frame, t, cand, gu
+    return per_frame, t, cand, gu, ad
 
 
 for noise in (True, False):
-    for fuse in (7, 0, 7, 0):
-        per_frame, t, cand, gu = run(fuse, noise)
+    for fuse, own in ((7, 7), (7, 0), (0, 0)) * 2:
+        per_frame, t, cand, gu, ad = run(fuse, own, noise)
         cols = "  ".join(f"{nm.replace('icp_residual', 'A').replace('rgb_step_solve', 'B')} {avg * 1e3:6.2f} x{cnt / frames:4.1f}" for nm, (avg, cnt) in t.items() if cnt)
-        print(f"{'noise' if noise else 'plain'} rgb_fuse={fuse}: iteration launches {per_frame:7.1f} us per frame; candidates {cand}; give-ups {gu}\n    {cols}")
+        print(f"{'noise' if noise else 'plain'} rgb_fuse={fuse} rgb_own={own}: iteration launches {per_frame:7.1f} us per frame; candidates {cand}; give-ups {gu}, adopted {ad}\n    {cols}")
