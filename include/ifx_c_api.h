@@ -1061,6 +1061,25 @@ int ifx_precision_recall(ifx_t* h, int32_t* inst_num96, int32_t* gt_num256, int3
 int ifx_instance_table(ifx_t* h, int32_t* out96);
 /* getLoopClosureInstanceTable, IF/Core/InstanceTable.cpp:98-121: int[96*5] = r,g,b,class,index */
 int ifx_loop_closure_instance_table(ifx_t* h, int32_t* out480);
+/* ---- duplicate instances after a loop closure (what the reference wrote and switched off: InstanceFusion::checkLoopClosure, IF/Core/InstanceTable.cpp:122-169, its
+ * call commented out at IF/main.cpp:143; loopClosureCopyMatchInstanceKernel, IF/Core/InstanceFusionCuda.cu:1370-1427; cleanInstanceTable / cleanInstanceTableMap).
+ * ifx_merge_instances: pairs = n entries (from, to), 0 <= n <= 95.  For every surfel slot below the count (tombstones included) and every pair, in ascending `from`:
+ *   f = the from-counter as decoded; if f > 0 the target's word is decoded, f added to the target's half, clamped (>= 65535 -> 65535), encoded and stored; if f <= 0
+ *   the target's word stays bit for bit (the -1 of a first-frame surfel is "not projected", not a count: the reference would make it -2).  Then every from-half is
+ *   cleared as a table eviction clears it, inst_class[from] = -1, the full label scan runs, and a live surfel that carries the table colour of a cleared slot takes
+ *   the colour of its new label (the default colour 7434609 for label -1).  Returns with the stream drained.  One pass over the vote store; a record of which no
+ *   word changed is not written.
+ *   IFX_E_INVALID, nothing enqueued and nothing changed: an id outside 0 .. 95, from == to, a from or to whose slot is unused, a from named twice, or a chain (an
+ *   id that is the target of one pair and the source of another: the reference's loop would lose the far end's votes -- resolve chains to their roots first, as
+ *   the wrappers do).  n == 0: IFX_OK, nothing done.  A deferred-segmentation ticket taken before the call stays valid.
+ *   Sharded handles (n_ranks > 1, ifx_set_shard): every rank makes the same call with THE SAME pairs on its shard; the table is replicated, nothing is exchanged.
+ * ifx_instance_duplicates: over the current id image (completed if lazy) the projected box of every instance, as the segmentation call computes them.  Registered
+ *   instances l < h of one class are duplicates when both boxes are non-empty and I / U > iou_thresh in the float arithmetic of computeCompareMap
+ *   (IF/Core/InstanceFusion.cpp:595-651) with the second box in the mask's place; instance 0 may be a target.  Every h takes its best l (largest I / U, ties to the
+ *   lower index), chains are resolved to their roots, and out_pairs receives (from = h, to = root) ascending in from: ready for ifx_merge_instances.  Returns the
+ *   number of pairs found (at most max_pairs are written; 95 always suffice).  Changes no state.  IFX_E_STATE on a sharded handle. */
+int ifx_merge_instances(ifx_t* h, const int32_t* pairs, int n);
+int ifx_instance_duplicates(ifx_t* h, float iou_thresh, int32_t* out_pairs, int max_pairs);
 int ifx_mask_clean_overlap(ifx_t* h, uint8_t* masks, int n);  /* IF/Core/InstanceFusionCuda.cu:118-141 (host in/out) */
 /* maskGeometricFilter + filterAreaCompute (IF/Core/InstanceFusion.cpp:470-593) as a stage, host buffers: depth = model
  * depth under the camera (u16 H x W, 1186 units per metre, what getProjectDepthMap :977-996 produces); masks n x H x W

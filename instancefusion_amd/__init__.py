@@ -248,6 +248,8 @@ _SIGS = {
     "ifx_precision_recall": (C.c_int, [_P, _P, _P, _P]),
     "ifx_instance_table": (C.c_int, [_P, _P]),
     "ifx_loop_closure_instance_table": (C.c_int, [_P, _P]),
+    "ifx_merge_instances": (C.c_int, [_P, _P, C.c_int]),
+    "ifx_instance_duplicates": (C.c_int, [_P, C.c_float, _P, C.c_int]),
     "ifx_mask_clean_overlap": (C.c_int, [_P, _P, C.c_int]),
     "ifx_mask_geometric_filter": (C.c_int, [_P, _P, _P, _P, C.c_int, _P]),
     "ifx_mask_compare_map": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, _P]),
@@ -732,6 +734,34 @@ class ElasticFusion(_DetectorOperators):
         return float(avg.value), int(n.value)
 
 
+def resolve_merge_pairs(pairs):
+    """(from, to) pairs with their chains resolved to the roots (5 -> 3, 3 -> 1 becomes 5 -> 1, 3 -> 1), ascending in from, as [n, 2] int32.  ValueError for a from
+    named twice with two targets, or a cycle; from == to and ids outside the table are left for ifx_merge_instances to refuse."""
+    pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
+    to = {}
+    for f, t in pairs.tolist():
+        if to.setdefault(f, t) != t:
+            raise ValueError(f"instance {f} is merged into two targets")
+    out = []
+    for f in sorted(to):
+        t, steps = to[f], 0
+        while t in to and t != f:
+            t, steps = to[t], steps + 1
+            if steps > len(to):
+                break
+        if f in to and (t == f and to[f] != f or steps > len(to)):
+            raise ValueError(f"the merge pairs form a cycle through instance {f}")
+        out.append((f, t))
+    return np.asarray(out, np.int32).reshape(-1, 2)
+
+
+def merge_instances(ef, pairs, resolve=True):
+    """ifx_merge_instances on the handle of `ef` (every rank of a sharded map makes the same call); returns the pairs as passed to it"""
+    pairs = resolve_merge_pairs(pairs) if resolve else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    ef._chk(ef.L.ifx_merge_instances(ef.handle, _ptr(pairs) if len(pairs) else None, int(len(pairs))), "ifx_merge_instances")
+    return pairs
+
+
 class InstanceFusion:
     """Mirror of the ``InstanceFusion`` class for the hot path; masks come from the caller (replay)."""
 
@@ -1021,6 +1051,30 @@ class InstanceFusion:
         out = np.zeros(96 * 5, np.int32)
         self.ef._chk(self.L.ifx_loop_closure_instance_table(self.ef.handle, _ptr(out)), "ifx_loop_closure_instance_table")
         return out.reshape(96, 5)
+
+    # -- duplicate instances after a loop closure (include/ifx_c_api.h: the reference's checkLoopClosure, IF/Core/InstanceTable.cpp:122-169)
+    def merge_instances(self, pairs, resolve=True):
+        """ifx_merge_instances: pairs of (from, to) -- the votes of `from` are added to `to` in every surfel, `from` leaves the table, labels and colours follow.
+        resolve: chains (5 -> 3, 3 -> 1) are first resolved to their roots (5 -> 1, 3 -> 1), which the C entry refuses to guess; a cycle raises ValueError.
+        Returns the pairs as merged, [n, 2] int32 ascending in from."""
+        return merge_instances(self.ef, pairs, resolve)
+
+    def duplicate_instances(self, iou=0.5):
+        """ifx_instance_duplicates: (from, to) for the registered instances of one class whose projected boxes in the current view overlap with I / U > iou,
+        resolved to their roots, ascending in from: what merge_instances takes."""
+        out = np.zeros((95, 2), np.int32)
+        n = self.ef._chk(self.L.ifx_instance_duplicates(self.ef.handle, float(iou), _ptr(out), 95), "ifx_instance_duplicates")
+        return out[:n].copy()
+
+    def check_loop_closure(self, table):
+        """InstanceFusion::checkLoopClosure: `table` as getLoopClosureInstanceTable gives it ([96, 5] int32), its column 4 the instance every row matches.  Rows whose
+        match is another instance are merged into it (chains resolved); the column is reset to the row index in place.  Returns the pairs merged."""
+        table = np.asarray(table)
+        t = table.reshape(96, 5)
+        pairs = [(i, int(t[i, 4])) for i in range(96) if int(t[i, 4]) != i]
+        done = self.merge_instances(pairs)
+        t[:, 4] = np.arange(96)
+        return done
 
     # superpixel refinement stages (IF/Core/InstanceFusion_superpixel.cpp)
     def gSLICrInterface(self, rgb):

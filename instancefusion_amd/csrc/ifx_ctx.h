@@ -518,6 +518,7 @@ struct ifx {
     int* d_bbox = nullptr;             // [96*4 + maxmasks*4]
     int* d_inst_stats = nullptr;       // [96*2]
     int* d_clean_list = nullptr;
+    void* d_merge_plan = nullptr;      // MergePlan of ifx_merge_instances (allocated by the first merge)
     void* d_segctl = nullptr; void* h_segctl = nullptr;          // SegCtl of the device-side segmentation call + its pinned mirror (+ 256 verdict bytes)
     uint8_t* h_masks_stage = nullptr; size_t h_masks_cap = 0;    // pinned staging of the caller's masks
     int* d_mask_rank = nullptr;        // masks already on the device (ifx_process_segmentation_device): [256] inside-pixel counts (zero between calls), [256] order, [256] class ids in that order

@@ -783,7 +783,7 @@ void ifx_free_snapshots(ifx* h);
 void ifx_free_instance(ifx* h)
 {
     hipFree(h->d_inst_color); hipFree(h->d_masks); hipFree(h->d_masks_ori); hipFree(h->d_unavail); hipFree(h->d_ff_label); hipFree(h->d_pdm); hipFree(h->d_bbox); hipFree(h->d_inst_stats); hipFree(h->d_clean_list);
-    hipFree(h->d_segctl); hipFree(h->d_mask_rank); hipFree(h->oseg_rec); hipFree(h->d_cmp_tab); hipFree(h->d_pres);
+    hipFree(h->d_segctl); hipFree(h->d_mask_rank); hipFree(h->oseg_rec); hipFree(h->d_cmp_tab); hipFree(h->d_pres); hipFree(h->d_merge_plan);
     ifx_free_snapshots(h);
     ifx_detector_free(h);
     if (h->h_segctl) hipHostFree(h->h_segctl);
@@ -2919,6 +2919,213 @@ extern "C" int ifx_loop_closure_instance_table(ifx_t* h, int32_t* out)
         out[5 * i + 4] = i;
     }
     return IFX_OK;
+}
+
+// =========================================================================== f-3: duplicate instances after a loop closure
+// InstanceFusion::checkLoopClosure (IF/Core/InstanceTable.cpp:122-169): loopClosureCopyMatchInstanceKernel (IF/Core/InstanceFusionCuda.cu:1370-1427) per pair, then
+// cleanInstanceTable / cleanInstanceTableMap -- written by the reference and switched off (IF/main.cpp:143).  Here the copy and the clean are ONE pass over the
+// 192-byte records: a block stages MG_RECS (128) records in LDS with 16-byte loads (only the quarters the plan names), one thread per record walks
+// the pairs in ascending `from` on the staged words -- the reference's order, pair by pair on the words as the pairs before left them, because the packing is lossy
+// and a decode / encode per pair is not a decode / encode per word -- then the clears with k_clean_table's arithmetic, and the block writes back the quarters of
+// which a word changed, 16 bytes each.  Staged stride 13 float4 (52 words): a 16-byte aligned stride is a multiple of 4 words, so the record-per-lane word reads
+// of the middle phase meet on 32 / gcd(stride, 32) banks: 8 banks (4-way) at 52, 2 banks (16-way) at the natural 48.
+#define MG_RECS 128            // records per block and pass (27 KB staged: five blocks of two waves per CU, each with its own loads in flight)
+#define MG_BLOCKS 1280          // 256 CUs x 5 resident blocks: one round of blocks, so that no CU idles behind a second one
+#define MG_STRIDE 13
+struct MergePlan {
+    int n_pairs, n_clear;
+    uint32_t qneed, pad;         // bit q: quarter q of a record holds a source or a target word
+    uint32_t pair[NI];           // ascending `from`: source word | source half << 6 | target word << 8 | target half << 14   (half 0: the high one, instance 2 * word)
+    uint32_t clear[IFX_VF];      // word | mask << 6   (bit 0: the high half, bit 1: the low half)
+    float from_color[NI];        // the table colours of the cleared slots (k_merge_recolour)
+};
+__global__ __launch_bounds__(MG_RECS) void k_merge_votes(const DevState* __restrict__ st, float4* __restrict__ votes, int cap, const MergePlan* __restrict__ plan)
+{
+    __shared__ float4 s_rec[MG_RECS * MG_STRIDE];
+    __shared__ uint32_t s_pair[NI], s_clear[IFX_VF], s_chg[MG_RECS];
+    const int tid = threadIdx.x;
+    const int np = min(plan->n_pairs, NI), nc = min(plan->n_clear, IFX_VF);
+    const uint32_t qneed = plan->qneed;
+    if (tid < np) s_pair[tid] = plan->pair[tid];
+    if (tid < nc) s_clear[tid] = plan->clear[tid];
+    const int n = min(st->count, cap);
+    float* const w = (float*)s_rec + tid * (MG_STRIDE * 4);
+    for (int r0 = blockIdx.x * MG_RECS; r0 < n; r0 += gridDim.x * MG_RECS) {   // (uniform per block: the barriers below see whole blocks)
+        const int nrec = min(MG_RECS, n - r0);
+        float4* const g = votes + (size_t)r0 * 12;
+        // consecutive lanes, consecutive 16 bytes; the twelve loads of a lane are issued together and waited for once (a lane that has nothing to fetch re-reads a
+        // quarter of the block's first record, which exists: a load per branch was one memory latency after the other, twelve per pass)
+        float4 v[12];
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            const int slot = tid + j * MG_RECS, rec = slot / 12, q = slot - rec * 12;
+            const bool want = rec < nrec && ((qneed >> q) & 1u);
+            v[j] = g[want ? slot : q];
+        }
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            const int slot = tid + j * MG_RECS, rec = slot / 12, q = slot - rec * 12;
+            if (rec < nrec && ((qneed >> q) & 1u)) s_rec[rec * MG_STRIDE + q] = v[j];
+        }
+        __syncthreads();
+        uint32_t chg = 0;
+        if (tid < nrec) {
+            for (int p = 0; p < np; p++) {
+                const uint32_t e = s_pair[p];
+                int a, b;
+                vote_decode(w[e & 63u], a, b);
+                const int f = ((e >> 6) & 1u) ? b : a;
+                if (f <= 0) continue;   // nothing to give -- and the -1 of a first-frame surfel is no count
+                const int tw = (e >> 8) & 63u;
+                const float old = w[tw];
+                vote_decode(old, a, b);
+                if ((e >> 14) & 1u) { b += f; if (b >= 65535) b = 65535; }
+                else { a += f; if (a >= 65535) a = 65535; }
+                const float nw = vote_encode(a, b);
+                if (__float_as_uint(nw) != __float_as_uint(old)) { w[tw] = nw; chg |= 1u << (tw >> 2); }
+            }
+            for (int c = 0; c < nc; c++) {   // cleanInstanceTableMapKernel on the from-halves
+                const uint32_t e = s_clear[c];
+                const int cw = e & 63u;
+                const float old = w[cw];
+                int a, b;
+                vote_decode(old, a, b);
+                if ((e >> 6) & 1u) a = 0;
+                if ((e >> 7) & 1u) b = 0;
+                const float nw = vote_encode(a, b);
+                if (__float_as_uint(nw) != __float_as_uint(old)) { w[cw] = nw; chg |= 1u << (cw >> 2); }
+            }
+        }
+        s_chg[tid] = chg;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            const int slot = tid + j * MG_RECS, rec = slot / 12, q = slot - rec * 12;
+            if (rec < nrec && ((s_chg[rec] >> q) & 1u)) g[slot] = s_rec[rec * MG_STRIDE + q];
+        }
+        __syncthreads();   // (the next pass stages over these records)
+    }
+}
+// Colours are assigned once (k_count_colour): a live surfel that carries the table colour of a cleared slot takes the colour of the label the scan just gave it
+__global__ __launch_bounds__(256) void k_merge_recolour(const DevState* __restrict__ st, int cap, const float2* __restrict__ tm, float2* __restrict__ col, const float* __restrict__ inst_color,
+                                                        const int32_t* __restrict__ labels, const MergePlan* __restrict__ plan)
+{
+    __shared__ float s_from[NI], s_col[NI];
+    const int np = min(plan->n_pairs, NI);
+    for (int t = threadIdx.x; t < NI; t += blockDim.x) { s_col[t] = inst_color[t]; if (t < np) s_from[t] = plan->from_color[t]; }
+    __syncthreads();
+    const float defaultColor = 7434609;
+    const int n = min(st->count, cap);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += blockDim.x * gridDim.x) {
+        if (!(tm[i].y > DEAD_TIME)) continue;
+        float2 c = col[i];
+        bool hit = false;
+        for (int k = 0; k < np; k++) hit = hit || c.y == s_from[k];
+        if (!hit) continue;
+        const int l = labels[i];
+        c.y = (l >= 0 && l < NI) ? s_col[l] : defaultColor;
+        col[i] = c;
+    }
+}
+// the checks of ifx_merge_instances and the plan of its pass, on the host; 0 or the refusal's text
+static const char* merge_plan_build(const int32_t* inst_class, const float* inst_color, const int32_t* pairs, int n, MergePlan* mp)
+{
+    int to_of[NI];
+    bool is_to[NI];
+    for (int i = 0; i < NI; i++) { to_of[i] = -1; is_to[i] = false; }
+    for (int k = 0; k < n; k++) {
+        const int f = pairs[2 * k], t = pairs[2 * k + 1];
+        if (f < 0 || f >= NI || t < 0 || t >= NI) return "an instance id outside 0 .. 95";
+        if (f == t) return "a pair merges an instance into itself";
+        if (inst_class[f] == -1 || inst_class[t] == -1) return "a pair names an unused slot of the instance table";
+        if (to_of[f] != -1) return "an instance is the source of two pairs";
+        to_of[f] = t; is_to[t] = true;
+    }
+    for (int i = 0; i < NI; i++) if (to_of[i] != -1 && is_to[i]) return "a chain: an instance is the target of one pair and the source of another (resolve it to its root first)";
+    memset(mp, 0, sizeof(*mp));
+    uint32_t cmask[IFX_VF] = {};
+    for (int f = 0; f < NI; f++) {   // ascending `from`
+        if (to_of[f] == -1) continue;
+        const int t = to_of[f];
+        mp->pair[mp->n_pairs] = (uint32_t)(f >> 1) | (uint32_t)(f & 1) << 6 | (uint32_t)(t >> 1) << 8 | (uint32_t)(t & 1) << 14;
+        mp->from_color[mp->n_pairs++] = inst_color[f];
+        cmask[f >> 1] |= 1u << (f & 1);
+        mp->qneed |= 1u << (f >> 3) | 1u << (t >> 3);   // (word / 4: the 16-byte quarter)
+    }
+    for (int w = 0; w < IFX_VF; w++) if (cmask[w]) mp->clear[mp->n_clear++] = (uint32_t)w | cmask[w] << 6;
+    return nullptr;
+}
+extern "C" int ifx_merge_instances(ifx_t* h, const int32_t* pairs, int n)
+{
+    if (!h) return IFX_E_INVALID;
+    if (n < 0 || n > NI - 1) { h->err = "ifx_merge_instances: n must be 0 .. 95"; return IFX_E_INVALID; }
+    if (n == 0) return IFX_OK;
+    if (!pairs) { h->err = "ifx_merge_instances: null pairs"; return IFX_E_INVALID; }
+    if (h->oseg_pending) { h->err = "ifx_merge_instances: a sharded segmentation call is waiting for an exchange"; return IFX_E_STATE; }
+    MergePlan mp;
+    if (const char* why = merge_plan_build(h->inst_class, h->inst_color, pairs, n, &mp)) { h->err = std::string("ifx_merge_instances: ") + why; return IFX_E_INVALID; }
+    if (!h->d_merge_plan) HIPCHK(h, hipMalloc(&h->d_merge_plan, sizeof(MergePlan)));
+    const MergePlan* dp = (const MergePlan*)h->d_merge_plan;
+    HIPCHK(h, hipMemcpyAsync(h->d_merge_plan, &mp, sizeof(mp), hipMemcpyHostToDevice, h->cur));
+    HIPCHK(h, hipMemcpyAsync(h->d_inst_color, h->inst_color, sizeof(h->inst_color), hipMemcpyHostToDevice, h->cur));
+    LAUNCH(h, "merge_votes", dim3(std::max(1, std::min(cdiv(h->cap, MG_RECS), MG_BLOCKS))), dim3(MG_RECS), k_merge_votes, (const DevState*)h->d_state, (float4*)h->votes, h->cap, dp);
+    for (int k = 0; k < n; k++) h->inst_class[pairs[2 * k]] = -1;
+    h->labels_stale_all = 1;   // votes rewritten across the map, as after an eviction: the full scan, here and now
+    h->seg_counts_valid = 0;
+    seg_label_scan(h, seg_view_current(h));
+    LAUNCH(h, "merge_recolour", dim3(1024), dim3(256), k_merge_recolour, (const DevState*)h->d_state, h->cap, (const float2*)h->tm, (float2*)h->col, (const float*)h->d_inst_color,
+           (const int32_t*)h->labels, dp);
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return IFX_OK;
+}
+
+// The duplicates of the current view: the box rule of computeCompareMap (IF/Core/InstanceFusion.cpp:595-651, k_seg_compare's float arithmetic) between the projected
+// boxes of two registered instances of one class instead of a mask and an instance.  boxes: [96][4] {minX, maxX, minY, maxY}.  parent: per instance the lower
+// instance it duplicates best (largest I / U over the threshold, ties to the lower index) or -1.
+static void duplicates_decide(const int32_t* inst_class, const int* boxes, float thresh, int* parent)
+{
+    for (int hi = 0; hi < NI; hi++) {
+        parent[hi] = -1;
+        const int minX_m = boxes[hi * 4], maxX_m = boxes[hi * 4 + 1], minY_m = boxes[hi * 4 + 2], maxY_m = boxes[hi * 4 + 3];
+        if (inst_class[hi] == -1 || maxX_m <= minX_m || maxY_m <= minY_m) continue;
+        float best = 0;
+        for (int q = 0; q < hi; q++) {
+            if (inst_class[q] == -1 || inst_class[q] != inst_class[hi]) continue;
+            const int minX_i = boxes[q * 4], maxX_i = boxes[q * 4 + 1], minY_i = boxes[q * 4 + 2], maxY_i = boxes[q * 4 + 3];
+            if (maxX_i <= minX_i || maxY_i <= minY_i) continue;
+            const float IW = (float)(std::min(maxX_i, maxX_m) - std::max(minX_i, minX_m));
+            const float IH = (float)(std::min(maxY_i, maxY_m) - std::max(minY_i, minY_m));
+            if (IW <= 0 || IH <= 0) continue;
+            const float I = IW * IH;
+            const float U = (float)(((maxX_i - minX_i) * (maxY_i - minY_i)) + ((maxX_m - minX_m) * (maxY_m - minY_m))) - I;
+            const float iou = I / U;
+            if (iou > thresh && (parent[hi] == -1 || iou > best)) { parent[hi] = q; best = iou; }
+        }
+    }
+}
+extern "C" int ifx_instance_duplicates(ifx_t* h, float iou_thresh, int32_t* out_pairs, int max_pairs)
+{
+    if (!h) return IFX_E_INVALID;
+    if (max_pairs < 0 || (max_pairs > 0 && !out_pairs) || !(iou_thresh >= 0.0f)) { h->err = "ifx_instance_duplicates: a negative or NaN threshold, or no room for the pairs"; return IFX_E_INVALID; }
+    if (h->own || h->shard_n > 1) { h->err = "ifx_instance_duplicates: not on a sharded map"; return IFX_E_STATE; }
+    int r = ifx_ids_ensure(h);
+    if (r) return r;
+    const SegView v = seg_view_current(h);
+    LAUNCH(h, "init_bbox", dim3(cdiv(NI * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI, h->w, h->h);
+    LAUNCH(h, "project_bbox_inst", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<1>, h->d_state, v.ids, (const float4*)h->votes, h->cap, (const uint8_t*)nullptr,
+           0, h->w, h->h, h->d_bbox, ifx_idmap(h), (const float4*)nullptr, (uint16_t*)nullptr, (const float*)nullptr);
+    int boxes[NI * 4], parent[NI], root[NI];
+    HIPCHK(h, hipMemcpyAsync(boxes, h->d_bbox, sizeof(boxes), hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    duplicates_decide(h->inst_class, boxes, iou_thresh, parent);
+    int n = 0;
+    for (int i = 0; i < NI; i++) {   // (a parent is a lower index: its root is known)
+        root[i] = parent[i] == -1 ? i : root[parent[i]];
+        if (parent[i] == -1) continue;
+        if (n < max_pairs) { out_pairs[2 * n] = i; out_pairs[2 * n + 1] = root[i]; }
+        n++;
+    }
+    return n;
 }
 
 // =========================================================================== f-4: 3-D boxes and per-instance point clouds

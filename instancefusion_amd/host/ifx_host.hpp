@@ -30,6 +30,7 @@
 #include <fstream>
 #include <functional>
 #include <iomanip>
+#include <map>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -1297,6 +1298,56 @@ public:
             return;
         }
         if (ifx_loop_closure_instance_table(handle_, out_table) != IFX_OK) throw std::runtime_error(ifx_last_error(handle_));
+    }
+    // ---- duplicate instances after a loop closure (ifx_c_api.h: ifx_merge_instances, ifx_instance_duplicates)
+    // (from, to) pairs with their chains resolved to the roots -- 5 -> 3, 3 -> 1 becomes 5 -> 1, 3 -> 1 -- ascending in from; throws on a cycle or a from with two targets
+    static std::vector<std::pair<int, int>> resolveMergePairs(const std::vector<std::pair<int, int>>& pairs)
+    {
+        std::map<int, int> to;
+        for (const auto& p : pairs) {
+            const auto it = to.emplace(p.first, p.second);
+            if (!it.second && it.first->second != p.second) throw std::runtime_error("resolveMergePairs: instance " + std::to_string(p.first) + " is merged into two targets");
+        }
+        std::vector<std::pair<int, int>> out;
+        for (const auto& p : to) {
+            int t = p.second;
+            size_t steps = 0;
+            while (t != p.first && to.count(t) && steps <= to.size()) { t = to[t]; steps++; }
+            if ((t == p.first && p.second != p.first) || steps > to.size()) throw std::runtime_error("resolveMergePairs: a cycle through instance " + std::to_string(p.first));
+            out.emplace_back(p.first, t);
+        }
+        return out;
+    }
+    // the votes of every `from` added to its `to` in every surfel, `from` cleared and taken off the table, labels and colours following; returns the pairs as merged
+    std::vector<std::pair<int, int>> mergeInstances(const std::vector<std::pair<int, int>>& pairs)
+    {
+        ifx_t* h = require_handle(handle_, "mergeInstances");
+        const std::vector<std::pair<int, int>> r = resolveMergePairs(pairs);
+        std::vector<int32_t> flat;
+        for (const auto& p : r) { flat.push_back(p.first); flat.push_back(p.second); }
+        if (ifx_merge_instances(h, flat.data(), (int)r.size()) != IFX_OK) throw std::runtime_error(std::string("ifx_merge_instances: ") + ifx_last_error(h));
+        return r;
+    }
+    // the instances of one class whose projected boxes in the current view overlap with I / U > iou: (from, to = root), ascending in from
+    std::vector<std::pair<int, int>> findDuplicateInstances(const std::unique_ptr<ElasticFusionInterface>& map, float iou = 0.5f)
+    {
+        int32_t flat[2 * IFX_NUM_INSTANCES];
+        const int n = ifx_instance_duplicates(map->handle(), iou, flat, IFX_NUM_INSTANCES - 1);
+        if (n < 0) throw std::runtime_error(std::string("ifx_instance_duplicates: ") + ifx_last_error(map->handle()));
+        std::vector<std::pair<int, int>> out;
+        for (int k = 0; k < n; k++) out.emplace_back(flat[2 * k], flat[2 * k + 1]);
+        return out;
+    }
+    // IF/Core/InstanceTable.cpp:122-169 (its call is commented out at IF/main.cpp:143): rows whose column 4 names another instance are merged into it -- chains
+    // resolved, where the reference's loop would lose the far end's votes -- and the column is reset to the row index
+    void checkLoopClosure(int* loopClosureInstanceTable, const std::unique_ptr<ElasticFusionInterface>& map)
+    {
+        if (!handle_) bindMap(map);
+        std::vector<std::pair<int, int>> pairs;
+        for (int i = 0; i < instanceNum; i++)
+            if (loopClosureInstanceTable[5 * i + 4] != i) pairs.emplace_back(i, loopClosureInstanceTable[5 * i + 4]);
+        mergeInstances(pairs);
+        for (int i = 0; i < instanceNum; i++) loopClosureInstanceTable[5 * i + 4] = i;
     }
     void bindMap(const std::unique_ptr<ElasticFusionInterface>& map) { handle_ = map->handle(); }
     // bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) of the live surfels, map order

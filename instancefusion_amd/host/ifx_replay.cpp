@@ -5,7 +5,7 @@
 // (map->SavePly(), IF/main.cpp:300-305), and optionally the per-surfel instance labels.
 //
 //   ifx_replay LOG.klg|data.txt [--width 640 --height 480 --fx 528 --fy 528 --cx 320 --cy 240] [--masks DIR] [--out PREFIX]
-//              [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--device K] [--gt-dir DIR --eval FILE] [--mask-lag K]
+//              [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--device K] [--gt-dir DIR --eval FILE] [--mask-lag K] [--merge-duplicates]
 #include <chrono>
 #include <cstdlib>
 #include <iostream>
@@ -21,7 +21,7 @@ struct Args {
     std::string log, masks, out = "./ResultModel", labels, gt_dir, eval_file;
     int width = 640, height = 480, max_frames = 0, max_surfels = 6 * 1000 * 1000, device = 0;
     float fx = 528.f, fy = 528.f, cx = 320.f, cy = 240.f;
-    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false, mask_iou = false;
+    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false, mask_iou = false, merge_duplicates = false;
     int decode_threads = 4;
     int mask_lag = -1;   // --mask-lag K: the masks recorded for frame t arrive K frames later (a detector slower than the frame loop) and are applied through a snapshot of frame t
     float confidence = 10.f;
@@ -32,7 +32,7 @@ int usage(const char* argv0)
 {
     std::fprintf(stderr,
                  "usage: %s LOG.klg|data.txt [--width W --height H --fx F --fy F --cx C --cy C] [--masks DIR] [--out PREFIX]\n"
-                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K] [--mask-iou]\n"
+                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K] [--mask-iou] [--merge-duplicates]\n"
                  "       [--gt-dir DIR (DIR/<frame, 6 digits>.png, 8-bit instance ground truth)] [--eval FILE (precision / recall rows, needs --gt-dir)]\n"
                  "       [--shard-ranks G --shard-rank r --shard-id FILE [--shard-nonce N] (one process per GPU over one spatially sharded map; every rank replays the same log; -1: a world of one)]\n",
                  argv0);
@@ -72,6 +72,7 @@ int main(int argc, char** argv)
         else if (s == "--flip-colors") a.flip = true;
         else if (s == "--reference-ids") a.reference_ids = true;   // id images by the reference's screen-space quad rule (option "id_rule" = 1; not on a sharded map)
         else if (s == "--mask-iou") a.mask_iou = true;   // masks are matched to instances by mask IoU over dilated pixel sets (the reference's compareMapType 2; option "compare_map" = 2; not on a sharded map)
+        else if (s == "--merge-duplicates") a.merge_duplicates = true;   // on the first frame after a deformation: instances of one class whose projected boxes coincide are merged (the reference's checkLoopClosure, switched off there; not on a sharded map)
         else if (s == "--mask-lag") a.mask_lag = std::atoi(val("--mask-lag"));   // snapshot at the frame the masks belong to, deferred call K frames later (one detection in flight, as with one detector)
         else if (s == "--no-lookahead") a.lookahead = false;   // frames are handed over one at a time, as the reference's loop does
         else if (s == "--shard-ranks") a.shard.ranks = std::atoi(val("--shard-ranks"));   // -1: a world of one on the sharded path
@@ -83,6 +84,7 @@ int main(int argc, char** argv)
         else a.log = s;
     }
     if (a.log.empty()) return usage(argv[0]);
+    if (a.merge_duplicates && a.shard.on()) { std::fprintf(stderr, "--merge-duplicates is not available on a sharded map\n"); return 2; }
 
     try {
         Resolution::getInstance(a.width, a.height);            // IF/main.cpp:46-47
@@ -118,6 +120,7 @@ int main(int argc, char** argv)
         if (a.mask_iou) instancefusion->setCompareMapType(2);
 
         if (a.mask_lag >= 0 && a.shard.on()) { std::fprintf(stderr, "--mask-lag is not available on a sharded map\n"); return 2; }
+        int deformsSeen = 0, mergedPairs = 0;   // (--merge-duplicates)
         struct { bool busy = false; int ticket = -1, frame = 0; bool flann = false, has = false; MaskResult res; } pending;   // the detection in flight (--mask-lag)
         auto apply_pending = [&]() {
             if (pending.has) instancefusion->ProcessSegmentationDeferred(map, pending.ticket, pending.res, pending.frame, pending.flann);
@@ -152,6 +155,15 @@ int main(int argc, char** argv)
                 std::cout << "Elastic fusion lost!" << a.log << std::endl;
                 return 1;
             }
+            if (a.merge_duplicates) {   // a loop just closed: what drift registered twice now lies on top of itself
+                const int deforms = map->elasticFusion().getDeforms() + map->elasticFusion().getFernDeforms();
+                if (deforms > deformsSeen) {
+                    deformsSeen = deforms;
+                    const std::vector<std::pair<int, int>> dup = instancefusion->findDuplicateInstances(map);
+                    for (const auto& p : instancefusion->mergeInstances(dup)) std::fprintf(stderr, "frame %d: instance %d merged into %d\n", frame_Fusion, p.first, p.second);
+                    mergedPairs += (int)dup.size();
+                }
+            }
             if (pending.busy && frame_Fusion - pending.frame >= a.mask_lag) apply_pending();   // the masks of frame t arrive at frame t + K
             if (frame_Fusion >= cnn_start_frames && !a.masks.empty() && !pending.busy && instancefusion->whetherDoSegmentation(map, frame_Fusion)) {   // (a busy detector is not asked)
                 bool flannFlag = false;
@@ -184,6 +196,7 @@ int main(int argc, char** argv)
         const Matrix4f P = map->getCurrPose();
         int32_t la[3] = {0, 0, 0};
         ifx_lookahead_stats(map->handle(), la, 0);
+        if (a.merge_duplicates) std::fprintf(stderr, "%d duplicate instances merged\n", mergedPairs);
         std::printf("%d frames announced ahead (%d with their tracker run ahead), ", la[2], la[1]);
         std::printf("%d frames in %.2f s (%.1f frames/s incl. log decoding), %d segmentation calls, %d surfels, %d stable -> %s.ply / _Instance.ply (%d), "
                     "last position %.6f %.6f %.6f, %d local loop-closure candidates, %d fern keyframes, %d fern matches, %d local / %d global deformations\n",

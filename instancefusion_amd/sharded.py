@@ -236,6 +236,13 @@ class OwnerShardedElasticFusion:
         torch.cuda.synchronize()
         self.ef._chk(self.ef.L.ifx_owner_knn_vote(self.ef.handle, C.c_void_p(allp.data_ptr()), C.c_void_p(alll.data_ptr()), int(allp.shape[0]), int(off)), "ifx_owner_knn_vote")
 
+    def merge_instances(self, pairs, resolve=True):
+        """InstanceFusion.merge_instances on this rank's shard (ifx_merge_instances): every rank makes the call with the same pairs -- the instance table is
+        replicated, the votes of a surfel live on its owner, nothing is exchanged."""
+        from . import merge_instances
+
+        return merge_instances(self.ef, pairs, resolve)
+
     def ensure_ids(self):
         """Option own_lazy_ids: the whole id image (a frame exchanges the sampled lattice only).  With the library's communicator whoever reads the image completes it in
         place; a caller-driven transport does it here -- every rank together, before ef.image("ids_after") / camera_select."""
