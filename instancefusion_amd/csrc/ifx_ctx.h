@@ -536,7 +536,7 @@ struct ifx {
     int32_t* d_snap_ids = nullptr;     // [P] a snapshot's id image in today's slots (k_seg_translate): what a deferred call reads instead of ids_after
     void* det_prep = nullptr;          // the detector-input stage (ifx_detector.hip): its two events and the cached tap tables, allocated by the first call
     void* det_ops = nullptr;           // ifx_nms, ifx_rpn_proposals, ifx_box_detections (ifx_detector.hip): their one scratch and the event that orders it across streams, allocated by the first call
-    int opt_ff_rounds = 0;             // relaxation launches of the flood fill's fixed schedule (0: 24)
+    int opt_ff_rounds = 0;             // relaxation launches of the flood fill's fixed schedule (0: 4; at most FF_SLOTS = 64)
     int last_seg_frame = -1;
     int seg_counts_valid = 0;          // h_result->seg_counts describe the current ids_after / votes
     int clean_times = 0;

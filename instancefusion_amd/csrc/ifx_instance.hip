@@ -1153,14 +1153,36 @@ __global__ void k_ff_select(FFArgs a)
         if (slot < 20) a.meta[m * 32 + 4 + slot] = k;
     }
 }
+// The reference's list holds the FIRST twenty qualifying regions in scan order (`if(p<20) list[p++]`, :557); k_ff_select's slots are handed out in whatever
+// order its atomics land.  With twenty or fewer (every mask that lies inside its `ori`: at most three regions exceed a quarter of it) the two lists hold the
+// same set.  With more -- `ori` much smaller than the mask, or empty, where every ratio is inf -- the block rebuilds the list itself: the twenty smallest
+// qualifying roots, found by one wave scanning the labels in order.  Never taken in a run; a few hundred redundant scans of the image when it is.
 __global__ void k_ff_apply(FFArgs a)
 {
     if (a.gate && *a.gate) return;
     const int P = a.w * a.h, k = blockIdx.x * blockDim.x + threadIdx.x, m = blockIdx.y;
+    __shared__ int s_first[20];
+    const int found = a.skip[m] ? 0 : a.meta[m * 32 + 1];   // (the same for the whole block: the branch below is uniform)
+    if (found > 20) {
+        if (threadIdx.x < 64) {
+            const float oriPoints = (float)a.meta[m * 32];
+            int n = 0;
+            for (int base = 0; base < P && n < 20; base += 64) {
+                const int q = base + (int)threadIdx.x;
+                const bool root = q < P && a.label[(size_t)m * P + q] == q && (float)a.cnt[(size_t)m * P + q] / oriPoints > 0.25f;   // k_ff_select's test
+                const unsigned long long b = __ballot(root);
+                const int pos = n + __popcll(b & ((1ull << threadIdx.x) - 1ull));
+                if (root && pos < 20) s_first[pos] = q;
+                n += __popcll(b);
+            }
+        }
+        __syncthreads();
+    }
     bool keep = false;
     if (k < P && !a.skip[m]) {
-        const int l = a.label[(size_t)m * P + k], n = min(a.meta[m * 32 + 1], 20);
-        for (int j = 0; j < n; j++) keep = keep || (l >= 0 && l == a.meta[m * 32 + 4 + j]);
+        const int l = a.label[(size_t)m * P + k];
+        if (found > 20) { for (int j = 0; j < 20; j++) keep = keep || (l >= 0 && l == s_first[j]); }
+        else for (int j = 0; j < found; j++) keep = keep || (l >= 0 && l == a.meta[m * 32 + 4 + j]);
         a.masks[(size_t)m * P + k] = keep ? 255 : 0;
     }
     unsigned long long b = __ballot(keep);

@@ -417,8 +417,11 @@ def test_segmentation_device_schedule_equals_host_schedule(ifx, small_stream, ff
     """The segmentation call without the host in the middle of it (default since round 3: compare map, registration and the flood fill's termination on the
     device, one synchronisation at the end) against round 2's host-driven schedule (`seg_device` 0): instance tables, votes, labels and colours bit for bit
     over calls with superpixels, calls that match registered instances, and the eviction of a full table (the device stops at the mask that finds no free
-    slot, the host evicts and goes on from there).  ff_rounds = 2 makes the fixed relaxation schedule too short on purpose: the fill is then finished the
-    host-driven way and the tail re-issued -- same results."""
+    slot, the host evicts and goes on from there).  ff_rounds = 2 halves the fixed relaxation schedule (default 4).  That is NOT too short here: the room's objects
+    stand nearer than 3.37 m (4000 depth units), every edge of the fill is two-way, the union-find start is already the fixpoint and the first relaxation changes
+    nothing.  Launch counts of the first call, printed below: 2 ff_relax and 1 ff_count with ff_rounds = 2, 4 and 1 by default -- the tail is issued once, the
+    host-driven resume does not run.  What this parameter exercises is a schedule whose LAST launch is the second one (the gate word moves with it); the resume
+    itself is driven by tests/test_gpu_flood_fill_cases.py::test_serpentine_inside_a_call."""
     from instancefusion_amd import synth
 
     st = small_stream
@@ -436,7 +439,12 @@ def test_segmentation_device_schedule_equals_host_schedule(ifx, small_stream, ff
                 e.upload(m); e.set_pose(pa, a.tick)
         if i >= 4:
             masks, cls = synth.canned_masks(st["obj"][i], st["scene"])
+            if i == 4:      # the launch counts of one call, read once (see the docstring)
+                a.set_option("kernel_timing", 1); a.kernel_ms("__reset__")
             ia.ProcessSegmentation(st["rgb"][i], st["depth"][i], masks, cls, 100 + 3 * i, superpixels=True)
+            if i == 4:
+                print("ff_rounds", ff_rounds, ": ff_relax launches", a.kernel_ms("ff_relax")[1], "ff_count launches", a.kernel_ms("ff_count")[1])
+                a.set_option("kernel_timing", 0)
             ib.ProcessSegmentation(st["rgb"][i], st["depth"][i], masks, cls, 100 + 3 * i, superpixels=True)
             assert np.array_equal(ia.getInstanceTable(), ib.getInstanceTable()), i
             assert np.array_equal(ia.labels(), ib.labels()), i

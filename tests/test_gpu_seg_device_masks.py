@@ -67,7 +67,10 @@ def _twins(ifx, st, n_frames=8, **opts):
 @pytest.mark.parametrize("seg_device", [1, 0])
 def test_device_masks_equal_host_entry(ifx, small_stream, seg_device, ff_rounds):
     """test_segmentation_device_schedule_equals_host_schedule's sequence on twins: device uint8 tensors on one, the host entry with the same numpy masks on the
-    other (both on the resident frame) -- calls with superpixels, one with the kNN smoothing, then new classes until the table evicts."""
+    other (both on the resident frame) -- calls with superpixels, one with the kNN smoothing, then new classes until the table evicts.  ff_rounds = 2 only moves
+    the gate of the flood fill's fixed schedule to its second launch: on this scene (every edge two-way) the first relaxation changes nothing, and the launch
+    counts of the first call, printed below, are 2 ff_relax and 1 ff_count with seg_device 1 (4 and 1 by default; 7 and 1 on the host-driven schedule, which
+    ignores the option) -- the host-driven resume of an incomplete fill does not run here (tests/test_gpu_flood_fill_cases.py::test_serpentine_inside_a_call)."""
     import torch
 
     from instancefusion_amd import synth
@@ -88,7 +91,12 @@ def test_device_masks_equal_host_entry(ifx, small_stream, seg_device, ff_rounds)
         if i >= 4:
             masks, cls = synth.canned_masks(st["obj"][i], st["scene"])
             flann = i == 6
+            if i == 4:      # the launch counts of one call, read once (see the docstring)
+                a.set_option("kernel_timing", 1); a.kernel_ms("__reset__")
             ia.process_segmentation_device(torch.from_numpy(masks).cuda(), cls, 100 + 3 * i, isflann=flann, superpixels=True)
+            if i == 4:
+                print("seg_device", seg_device, "ff_rounds", ff_rounds, ": ff_relax launches", a.kernel_ms("ff_relax")[1], "ff_count launches", a.kernel_ms("ff_count")[1])
+                a.set_option("kernel_timing", 0)
             ib.ProcessSegmentation(None, None, masks, cls, 100 + 3 * i, isflann=flann, superpixels=True)
             _same(ia, ib, i)
     assert (ia.labels() >= 0).sum() > 100
