@@ -66,7 +66,7 @@ const char* ifx_global_error(void);
  * (IF/map_interface/ElasticFusionInterface.h:129-130).
  * rgb: H*W*3 u8 row-major, depth: H*W u16 millimetres (0 invalid).  in_pose16: NULL to track, or a
  * row-major 4x4 camera-to-world pose to use instead of tracking.  out_pose16 (may be NULL) receives
- * currPose.  Returns 0 ok, 1 lost (never in this configuration: reloc=false), <0 error.
+ * currPose.  Returns 0 ok, 1 lost (option "reloc", ifx_set_option; never without it), <0 error.
  * The caller's buffers are copied during the call, which returns when the whole frame is done.
  * Option "host_entry_async" 1 (for a host whose loop is ifx_process_frame after ifx_process_frame -- a log replay without masks): the call returns when the frame's
  * POSE is known (it is read back right behind the tracker); the frame's map passes finish under the caller's next steps -- its copy of the next frame, typically
@@ -85,7 +85,10 @@ int ifx_process_frame(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, int64
 int ifx_process_frame_ex(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, int64_t timestamp, const int32_t* inst_table,
                          const float* in_pose16, float weight_mult, int bootstrap, float* out_pose16);
 /* Same, with the frame already resident in HBM and no host synchronisation: the call only
- * enqueues work on the handle's stream.  Poses are appended to the device-side trajectory log. */
+ * enqueues work on the handle's stream.  Poses are appended to the device-side trajectory log.
+ * With option "reloc" the call synchronises ONCE, behind the tracking gate (what it enqueues next depends on the verdict;
+ * a handle with loop-closure callbacks synchronises behind its renders in the same way), announcements of the next frame
+ * (ifx_hint_next_frame, ifx_hint_next_frame_device) are ignored, and it returns 1 while the map is lost. */
 int ifx_enqueue_frame_device(ifx_t* h, const uint8_t* d_rgb, const uint16_t* d_depth,
                              int64_t timestamp, const float* in_pose16, float weight_mult);
 /* Optional one-frame look-ahead for replayed streams (the reference's log readers know the next frame,
@@ -414,6 +417,20 @@ int ifx_compact(ifx_t* h);        /* order-preserving removal of tombstones */
  *                           reference's in the cases test_owner_sharded_map_emulated holds)
  * An unknown name is refused (IFX_E_INVALID); ifx_create reports each entry of IFX_OPTS that is refused on stderr and goes on. */
 int ifx_set_option(ifx_t* h, const char* name, int value);
+/* Options "reloc" and "frame_to_frame_rgb" (0 | 1): the `reloc` and `frameToFrameRGB` arguments of the ElasticFusion constructor
+ * (EF/ElasticFusion.h:47-62), which replace "kept for the getter only" and the constructor's throw of host/ifx_host.hpp.
+ * IFX_E_STATE on a sharded handle, with camera contexts, and while a frame is in flight or announced.
+ *   reloc: every tracked or bootstrapped frame is judged behind its tracker (ifx_reloc_gate's rule; a frame with an external pose
+ *   is not, EF/ElasticFusion.cpp:334, :428-431).  The pose is adopted whatever the verdict (:425-426).  A frame that is not ok, or
+ *   any frame while lost, runs no index map, fusion, clean or id render (:620): the id image stays the last fused frame's.  While
+ *   lost the local loop-closure detection is skipped (:516), the fern callback sees the raw frame (ifx_fern_frame: passthrough 3),
+ *   ifx_adopt_pose from it also sets lastFrameRecovery (:480-484), the tick stands still (:713-717) and the frame entries return 1;
+ *   with lastFrameRecovery both predict() calls take the time window (0, tick) (:733-754).  The trajectory takes a pose every frame.
+ *   frame_to_frame_rgb: the photometric term's model image is the fill-in image whatever the dense test says (:346), and that image is
+ *   the previous raw frame (passthrough 2, :759).
+ * ifx_reloc_state: out12 = {ok, lost, lastFrameRecovery, trackingCount, lastICPError, the six covariance diagonals (as float),
+ * 1 if the last frame ran its map passes}; waits for the last frame. */
+int ifx_reloc_state(ifx_t* h, float* out12);
 
 /* R32I surfel-id image after fusion (getSurfelIdsAfterFusionGpu, ElasticFusionInterface.h:90-102):
  * linear H*W int32 device buffer, 0 = empty. */
@@ -429,6 +446,22 @@ int ifx_image_download(ifx_t* h, const char* name, void* out, int64_t max_bytes)
 /* ---- map stage API (unit-parity surface; each replaces one GL pass of the reference) */
 int ifx_predict_indices(ifx_t* h, const float* pose16, int time);                /* EF/IndexMap.cpp:221-279 */
 int ifx_combined_predict(ifx_t* h, const float* pose16, int time, int max_time); /* EF/IndexMap.cpp:468-574 */
+/* The same pass with the fill-in stage's `passthrough` uniform (fill_vertex / fill_normal / fill_rgb.frag,
+ * EF/Shaders/FillIn.cpp:65-195, called with it at EF/ElasticFusion.cpp:757-759).  passthrough_mask bit 0: fill_vertex and
+ * fill_normal take the frame (vertex from the filtered depth, normal from its +x / +y neighbours) at every pixel; bit 1:
+ * fill_image takes the frame's colour, alpha 255, at every pixel.  An output whose bit is clear keeps the passthrough = 0
+ * rule; pred_* are never touched.  The reference passes 3 while lost and 2 with frameToFrameRGB.  Mask 0 is
+ * ifx_combined_predict; a mask outside 0..3 is IFX_E_INVALID. */
+int ifx_combined_predict_ex(ifx_t* h, const float* pose16, int time, int max_time, int passthrough_mask);
+/* The tracking gate of the relocalisation mode (reloc = true), EF/ElasticFusion.cpp:371-423 with RGBDOdometry::getCovariance
+ * (EF/Utils/RGBDOdometry.cpp:605-608), as a stage on the device.  lastA36: the tracker's last normal matrix, row-major f64;
+ * icp_error: its lastICPError; state3_inout: {lost, lastFrameRecovery, trackingCount}, updated in place.
+ *   ok = icp_error < 1e-4f (a NaN is not ok);
+ *   not lost: a diagonal of lastA^-1 > 1e-04 (f64) clears ok; not ok counts up and the count passing 10 sets lost, ok clears the count;
+ *   lost with lastFrameRecovery: the same covariance test; ok clears lost and the count; lastFrameRecovery is cleared either way;
+ *   lost without it: the state is untouched.
+ * ok_out (may be null): the verdict; cov_diag6 (may be null): the six diagonals of lastA^-1, reported in every branch. */
+int ifx_reloc_gate(ifx_t* h, const double* lastA36, float icp_error, int32_t* state3_inout, int32_t* ok_out, double* cov_diag6);
 int ifx_fuse(ifx_t* h, const float* pose16, int time, float weighting);          /* EF/GlobalModel.cpp:459-698 */
 int ifx_clean(ifx_t* h, const float* pose16, int time);                          /* EF/GlobalModel.cpp:700-925 */
 int ifx_render_ids(ifx_t* h, const float* pose16, int mode);                     /* EF/IndexMap.cpp:315-465; result in "ids_tmp" */

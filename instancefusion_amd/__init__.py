@@ -185,6 +185,9 @@ _SIGS = {
     "ifx_image_download": (C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
     "ifx_predict_indices": (C.c_int, [_P, _P, C.c_int]),
     "ifx_combined_predict": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "ifx_combined_predict_ex": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
+    "ifx_reloc_gate": (C.c_int, [_P, _P, C.c_float, _P, _P, _P]),
+    "ifx_reloc_state": (C.c_int, [_P, _P]),
     "ifx_fuse": (C.c_int, [_P, _P, C.c_int, C.c_float]),
     "ifx_clean": (C.c_int, [_P, _P, C.c_int]),
     "ifx_render_ids": (C.c_int, [_P, _P, C.c_int]),
@@ -329,9 +332,10 @@ from .detector import (DET_SCALE_255, DET_SWAP_RB, MOLD_MEAN_PIXEL, MOLD_NCHW, M
 
 class ElasticFusion(_DetectorOperators):
     """Mirror of ``ElasticFusion`` / ``ElasticFusionInterface`` for the hot path.  ``id_rule``: ID_RULE_REFERENCE draws the id images with the reference's
-    screen-space quad rule (option "id_rule"); None leaves the library's default."""
+    screen-space quad rule (option "id_rule"); None leaves the library's default.  ``reloc`` / ``frame_to_frame_rgb``: the constructor arguments of the same
+    names (EF/ElasticFusion.h:47-62; options "reloc" / "frame_to_frame_rgb")."""
 
-    def __init__(self, id_rule=None, **cfg):
+    def __init__(self, id_rule=None, reloc=False, frame_to_frame_rgb=False, **cfg):
         self.cfgd = default_config(**cfg)
         self.cfg = IfxConfig(**self.cfgd)
         self.L = lib()
@@ -341,8 +345,13 @@ class ElasticFusion(_DetectorOperators):
         if r != 0:
             raise IfxError(f"ifx_create failed ({r}): {self.L.ifx_global_error().decode()}")
         self.handle = hp
+        self.last_frame_status = 0   # what the last processFrame returned: 0 ok, 1 lost (reloc)
         if id_rule is not None:
             self.set_option("id_rule", id_rule)
+        if reloc:
+            self.set_option("reloc", 1)
+        if frame_to_frame_rgb:
+            self.set_option("frame_to_frame_rgb", 1)
 
     # -- life cycle
     def close(self):
@@ -379,9 +388,15 @@ class ElasticFusion(_DetectorOperators):
         out = np.zeros(16, np.float32)
         ip = None if inPose is None else np.ascontiguousarray(inPose, np.float32).reshape(16)
         tab = None if smallInstanceTable is None else np.ascontiguousarray(smallInstanceTable, np.int32)
-        self._chk(self.L.ifx_process_frame_ex(self.handle, _ptr(rgb), _ptr(depth), int(timestamp), _ptr(tab), _ptr(ip), float(weightMultiplier), int(bool(bootstrap)), _ptr(out)),
-                  "ifx_process_frame_ex")
+        self.last_frame_status = self._chk(self.L.ifx_process_frame_ex(self.handle, _ptr(rgb), _ptr(depth), int(timestamp), _ptr(tab), _ptr(ip), float(weightMultiplier),
+                                                                       int(bool(bootstrap)), _ptr(out)), "ifx_process_frame_ex")
         return out.reshape(4, 4)
+
+    def reloc_state(self):
+        """ifx_reloc_state: the last tracking verdict of the relocalisation mode and whether the last frame ran its map passes"""
+        o = np.zeros(12, np.float32)
+        self._chk(self.L.ifx_reloc_state(self.handle, _ptr(o)), "ifx_reloc_state")
+        return dict(ok=bool(o[0]), lost=bool(o[1]), last_frame_recovery=bool(o[2]), tracking_count=int(o[3]), icp_error=float(o[4]), cov_diag=o[5:11].copy(), fused=bool(o[11]))
 
     process_frame = processFrame
 
@@ -650,8 +665,19 @@ class ElasticFusion(_DetectorOperators):
     def predict_indices(self, pose, time):
         self._chk(self.L.ifx_predict_indices(self.handle, _ptr(self._pose(pose)), int(time)), "ifx_predict_indices")
 
-    def combined_predict(self, pose, time, max_time):
-        self._chk(self.L.ifx_combined_predict(self.handle, _ptr(self._pose(pose)), int(time), int(max_time)), "ifx_combined_predict")
+    def combined_predict(self, pose, time, max_time, passthrough=0):
+        """passthrough: the fill-in stage's mask (bit 0 fill_vertex + fill_normal, bit 1 fill_image take the frame at every pixel; EF/ElasticFusion.cpp:757-759)"""
+        self._chk(self.L.ifx_combined_predict_ex(self.handle, _ptr(self._pose(pose)), int(time), int(max_time), int(passthrough)), "ifx_combined_predict_ex")
+
+    def reloc_gate(self, lastA, icp_error, state):
+        """The tracking gate of EF/ElasticFusion.cpp:371-423 on the device.  lastA: 6x6 f64; state: (lost, lastFrameRecovery, trackingCount).
+        Returns (ok, (lost, lastFrameRecovery, trackingCount), the six diagonals of lastA^-1)."""
+        a = np.ascontiguousarray(lastA, np.float64).reshape(36)
+        st = np.array([int(bool(state[0])), int(bool(state[1])), int(state[2])], np.int32)
+        ok = np.zeros(1, np.int32)
+        cov = np.zeros(6, np.float64)
+        self._chk(self.L.ifx_reloc_gate(self.handle, _ptr(a), float(icp_error), _ptr(st), _ptr(ok), _ptr(cov)), "ifx_reloc_gate")
+        return bool(ok[0]), (bool(st[0]), bool(st[1]), int(st[2])), cov
 
     def fuse(self, pose, time, weighting):
         self._chk(self.L.ifx_fuse(self.handle, _ptr(self._pose(pose)), int(time), float(weighting)), "ifx_fuse")

@@ -432,7 +432,37 @@ extern "C" int ifx_set_option(ifx_t* h, const char* name, int value)
         else if (s == "so3") h->cfg.so3 = value ? 1 : 0;
         else { if (value < 0 || value > 100000) { h->err = "icp_weight_x1000 must be in [0, 100000]"; return IFX_E_INVALID; } h->cfg.icp_weight = value / 1000.f; }
     }
+    // ElasticFusion's `reloc` and `frameToFrameRGB` (EF/ElasticFusion.h:47-62).  reloc: the tracking gate behind every tracked frame, no fusion of a frame that fails it, lost
+    // after eleven in a row (enqueue_frame); frame_to_frame_rgb: the photometric term tracks against the previous raw frame (ifx_tracker_model_side, ifx_map_predict)
+    else if (s == "reloc" || s == "frame_to_frame_rgb") {
+        if (h->own || h->shard_n > 1) { h->err = s + ": not offered on a sharded map"; return IFX_E_STATE; }
+        if (!h->cams.empty()) { h->err = s + ": not offered with camera contexts"; return IFX_E_STATE; }
+        if (h->hint_rgb || h->slot[h->tick & 1].for_tick == h->tick || h->ids_pending || h->clean_raster_pending) { h->err = s + " cannot change while a frame is in flight or announced ahead"; return IFX_E_STATE; }
+        ifx_drop_tracked(h);
+        if (s == "reloc") {
+            h->opt_reloc = value ? 1 : 0;
+            if (!value && (h->reloc_lost || h->reloc_recovery)) {   // `lost` has no meaning without the gate: back to a tracking map
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                HIPCHK(h, hipMemset(h->d_state->reloc, 0, sizeof(h->d_state->reloc)));
+                h->reloc_lost = 0; h->reloc_recovery = 0;
+            }
+        } else h->opt_f2f_rgb = value ? 1 : 0;
+    }
     else { h->err = "unknown option " + s; return IFX_E_INVALID; }
+    return IFX_OK;
+}
+extern "C" int ifx_reloc_state(ifx_t* h, float* out12)
+{
+    if (!h || !out12) return IFX_E_INVALID;
+    memset(out12, 0, 12 * 4);
+    if (h->ev_result) HIPCHK(h, hipEventSynchronize(h->ev_result));
+    if (h->h_reloc) {
+        const RelocVerdict v = *h->h_reloc;
+        out12[0] = (float)v.ok; out12[3] = (float)v.tracking_count; out12[4] = v.icp_error;
+        for (int i = 0; i < 6; i++) out12[5 + i] = (float)v.cov_diag[i];
+    } else out12[0] = 1.f;
+    out12[1] = (float)h->reloc_lost; out12[2] = (float)h->reloc_recovery;   // (the host's: ifx_adopt_pose sets lastFrameRecovery behind the gate)
+    out12[11] = (float)h->reloc_fused;
     return IFX_OK;
 }
 
@@ -551,6 +581,28 @@ static int enqueue_loop_closure_renders(ifx* h)
     }
     return IFX_OK;
 }
+// The same block on a LOST frame (option reloc): predict() at the adopted pose (:453), the fern lookup on the raw frame -- the fill-in passes everything through while lost
+// (:757-759; ifx_fern_frame evaluates it at its samples) -- and nothing else: the local detection is skipped (:516), the host's global deformation is not entered (:478-484;
+// ifx_adopt_pose from the callback sets lastFrameRecovery).
+static int enqueue_lost_predict(ifx* h)
+{
+    h->lc_deferred = 0;
+    if (h->lc_pending) { HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_lc_done, 0)); h->lc_pending = 0; }   // (the previous frame's model-to-model run owns the act* images until it is done)
+    {
+        StageTimer t(h, 1);
+        ifx_map_predict_lost(h);
+    }
+    if (h->reloc_recovery) ifx_tracker_reloc_recovery(h, 0);   // :455 (a frame with an external pose right behind a recovery: the gate did not clear it)
+    if (h->fern_cb) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->in_fern_cb = 1;
+        int r = h->fern_cb(h, h->fern_user);
+        h->in_fern_cb = 0;
+        if (r < 0) { h->err = "fern callback failed"; return r; }
+    }
+    LAUNCH(h, "lc_idle", dim3(1), dim3(64), k_lc_idle, h->d_state, h->h_lc);
+    return IFX_OK;
+}
 // Part 2, after the map passes of the frame are on the main stream: the model-to-model tracker reads only the two renders (images of their
 // own) and its own state, and nothing of the frame consumes its verdict, so it goes to a stream of its own and runs under the map passes, the
 // end-of-frame predict() and the next frame's tracker (both trackers are chains of small latency-bound launches).  Enqueued AFTER the map
@@ -648,16 +700,30 @@ static int enqueue_frame(ifx* h, const uint8_t* rgb, const uint16_t* depth, int 
                 hold_last_image(h, s, h->opt_two_streams ? h->stream_b : h->stream);
             }
         }
+        // Option reloc (EF/ElasticFusion.cpp:371-423): the gate behind the tracker of a tracked or bootstrapped frame -- a frame with an external pose is not judged (:334,
+        // :428-431) -- and the frame's one synchronisation: what the host enqueues next depends on the verdict.  The pose stays adopted whatever it says (:425-426).
+        bool fuse = true;
+        if (h->opt_reloc) {
+            if (!in_pose16 || bootstrap) {
+                int r = ifx_tracker_reloc_gate(h);
+                if (r) return r;
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                const RelocVerdict v = *h->h_reloc;
+                h->reloc_lost = v.lost; h->reloc_recovery = v.last_frame_recovery;
+                fuse = v.ok && !v.lost;
+            } else fuse = !h->reloc_lost;   // trackingOk = true
+        }
+        h->reloc_fused = fuse ? 1 : 0;
         if (h->want_early_pose && !h->lc_enable) {   // ifx_process_frame: the pose the call returns, behind the tracker and in front of the map passes
             HIPCHK(h, hipMemcpyAsync(h->h_pose_early, (const void*)h->d_state, 64, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipEventRecord(h->ev_pose_early, h->stream));
             h->early_pose_valid = 1;
         }
         if (h->lc_enable) {
-            int r = enqueue_loop_closure_renders(h);
+            int r = h->reloc_lost ? enqueue_lost_predict(h) : enqueue_loop_closure_renders(h);
             if (r) return r;
         }
-        {
+        if (fuse) {   // (:620 -- a frame that failed the gate, or a lost map: no index map, fusion, clean or id render; ids_after stays the last fused frame's)
             StageTimer t(h, 1);
             h->frame_weight_mult = weight_mult;
             h->result_fold_traj = h->d_traj + (size_t)(h->n_traj % h->max_traj) * 16;   // (ifx_map_frame asks whether the prediction's resolve will take the frame result along)
@@ -678,6 +744,15 @@ static int enqueue_frame(ifx* h, const uint8_t* rgb, const uint16_t* depth, int 
         h->result_fold_traj = nullptr;
     }
     if (!h->result_folded) LAUNCH(h, "frame_result", dim3(1), dim3(64), k_frame_result, h->d_state, h->h_result, h->d_traj + (size_t)slot * 16);
+    const bool lost = h->opt_reloc && h->reloc_lost;
+    if (h->opt_reloc && !h->reloc_fused && h->view_scan_tick != h->tick && h->opt_vlist) hs_invalidate_view(h);   // the pose's commit may have asked for a scan no pass of this frame ran: the lists are rebuilt by the next frame that fuses
+    if (lost) {
+        // `tick` stands still while lost (:713-717) and the next frame takes this frame's slot again: its "previous image" -- what its SO(3) pre-alignment compares itself
+        // with (RGBDOdometry::initRGB ran for this frame) -- is read from the OTHER slot, which therefore takes this frame's intensity pyramid (cf. hold_last_image)
+        const FrameSlot& other = h->slot[s ^ 1];
+        for (int l = 0; l < IFX_NUM_PYRS; l++)
+            HIPCHK(h, hipMemcpyAsync(other.next_img[l], f.next_img[l], (size_t)h->pyr.w[l] * h->pyr.h[l], hipMemcpyDeviceToDevice, h->stream));
+    }
     hipEventRecord(f.released, h->stream);   // one marker: the side stream waits for it before it reuses the slot,
     h->ev_result = f.released;               // the host before it reads the frame result
     {
@@ -685,13 +760,13 @@ static int enqueue_frame(ifx* h, const uint8_t* rgb, const uint16_t* depth, int 
         if (r) return r;
     }
     h->seg_counts_valid = 1;
-    h->n_traj++;
-    h->tick++;
+    h->n_traj++;          // (the trajectory takes a pose every frame, as poseGraph does: :700)
+    if (!lost) h->tick++;   // (:713-717; the caller announces no fern frame while lost: the entry returned 1)
     // Tracking of the announced next frame reads only its frame slot, the prediction just rendered and the pose: nothing
     // a segmentation call in between touches.  Enqueue it now, parked (DevState::spec_*), so that the GPU has ~0.6 ms of
     // work while the host waits for this frame's result to decide about segmentation.
     FrameSlot& nf = h->slot[h->tick & 1];
-    if (h->opt_track_ahead && h->opt_two_streams && nf.for_tick == h->tick && h->tick > 1) {
+    if (h->opt_track_ahead && h->opt_two_streams && nf.for_tick == h->tick && h->tick > 1 && !h->opt_reloc) {   // (option reloc: a tracker run is judged before anything is built on it)
         ifx_bind_slot(h, h->tick & 1);
         HIPCHK(h, hipStreamWaitEvent(h->stream, nf.ready, 0));
         {
@@ -1244,7 +1319,10 @@ extern "C" int ifx_enqueue_frame_device(ifx_t* h, const uint8_t* d_rgb, const ui
     (void)timestamp;
     if (!h || !d_rgb || !d_depth) return IFX_E_INVALID;
     ifx_housekeeping(h);   // before this frame's map passes; a tracker run that is already queued does not care about slot numbers
-    return enqueue_frame(h, d_rgb, d_depth, 0, in_pose16, weight_mult);
+    // Option reloc: the frame synchronises once, behind the tracking gate (as a handle with loop-closure callbacks does behind its renders), so whether the map is lost
+    // is known when the frame is on the queue: 1 while lost, as ifx_process_frame returns it
+    const int r = enqueue_frame(h, d_rgb, d_depth, 0, in_pose16, weight_mult);
+    return r ? r : (h->reloc_lost ? 1 : 0);
 }
 
 // One-frame look-ahead for streams whose next frame is already resident (log replay, the benchmark): the frame
@@ -1263,6 +1341,7 @@ extern "C" int ifx_prefetch_frame_device(ifx_t* h, const uint8_t* d_rgb_next, co
 extern "C" int ifx_hint_next_frame_device(ifx_t* h, const uint8_t* d_rgb_next, const uint16_t* d_depth_next)
 {
     if (!h || !d_rgb_next || !d_depth_next) return IFX_E_INVALID;
+    if (h->opt_reloc) return IFX_OK;   // (a lost frame does not advance the tick: the announced frame's slot would not be the one it takes; ifx_prefetch_frame_device, behind the verdict, still overlaps)
     h->hint_rgb = d_rgb_next; h->hint_depth = d_depth_next; h->hint_kind = 0;
     return IFX_OK;
 }
@@ -1276,7 +1355,7 @@ extern "C" int ifx_hint_next_frame(ifx_t* h, const uint8_t* rgb_next, const uint
 {
     if (!h || !rgb_next || !depth_next) return IFX_E_INVALID;
     if (h->own || !h->cams.empty()) { h->err = "ifx_hint_next_frame: single-stream, unsharded handles (use ifx_hint_next_frame_device)"; return IFX_E_STATE; }
-    if (!h->opt_two_streams || !h->stream_b) return IFX_OK;   // nothing to overlap with
+    if (!h->opt_two_streams || !h->stream_b || h->opt_reloc) return IFX_OK;   // nothing to overlap with (option reloc: see ifx_hint_next_frame_device)
     const int p = (h->tick + 1) & 1;   // (this pair's last transfer belongs to frame tick - 1, whose pose a call has returned: complete)
     if (!h->hint_stage_rgb[p] || !h->hint_stage_depth[p]) {   // the pair is allocated together or not at all (a half-allocated pair would be written through a null pointer by the next call)
         if (h->hint_stage_rgb[p]) { (void)hipHostFree(h->hint_stage_rgb[p]); h->hint_stage_rgb[p] = nullptr; }
@@ -1438,9 +1517,9 @@ extern "C" int ifx_process_frame_ex(ifx_t* h, const uint8_t* rgb, const uint16_t
         if (r) return r;
         ifx_housekeeping(h);
         h->housekeeping_due = 0;
-        return 0;
+        return h->reloc_lost ? 1 : 0;
     }
-    const bool can_early = h->opt_host_entry_async && !h->lc_enable && !h->in_fern_cb && h->tick > 1 && h->cams.empty() && !in_pose16;   // (plain tracked frames of a single stream)
+    const bool can_early = h->opt_host_entry_async && !h->lc_enable && !h->in_fern_cb && h->tick > 1 && h->cams.empty() && !in_pose16 && !h->opt_reloc;   // (plain tracked frames of a single stream)
     // (the staging buffers are free: their last copy to the device ran in front of a tracker whose pose a previous call has waited for -- or behind a full synchronisation)
     if (!can_early) HIPCHK(h, hipStreamSynchronize(h->stream));
     memcpy(h->depth_stage, depth, (size_t)h->P * 2);
@@ -1478,7 +1557,7 @@ extern "C" int ifx_process_frame_ex(ifx_t* h, const uint8_t* rgb, const uint16_t
     if (r) return r;
     ifx_housekeeping(h);
     h->housekeeping_due = 0;
-    return 0;
+    return h->reloc_lost ? 1 : 0;
 }
 
 // Tombstones pile up: when the last frame result the host has seen says that more than 1/8 of the

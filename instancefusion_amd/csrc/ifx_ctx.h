@@ -96,6 +96,15 @@ struct DevState {
     alignas(64) double gnp_RRt[2][16];
     int rgb_meet_giveups;                                                // photometric blocks of fused iterations that stopped waiting for the others (bounded meeting; ifx_tracker_meet_giveups): 0 in a healthy run unless rgb_fuse_poll = 0
     int rgb_meet_adopted;                                                // own-records form (rgb_own): shares of such blocks that the last arriver stepped in their place (ifx_tracker_meet_adopted): equal to the give-ups of that form
+    int reloc[4];                                                        // option reloc: {lost, lastFrameRecovery, trackingCount, -} of EF/ElasticFusion.cpp:371-423 (k_reloc_gate; at the end: no other field moves)
+};
+
+// verdict of the tracking gate (k_reloc_gate, EF/ElasticFusion.cpp:371-423), written to pinned host memory
+struct RelocVerdict {
+    int ok, lost, last_frame_recovery, tracking_count;
+    float icp_error;
+    int pad;
+    double cov_diag[6];
 };
 
 // Ids in the id images are slot indices on an unsharded map and creation numbers on a spatially sharded one (ifx_map.hip, key_id / local_slot):
@@ -427,7 +436,13 @@ struct ifx {
     int own_tracked_tick = 0;                                  // sharded map with the detection on: the frame side + tracker of this tick ran in phase 300 already
     float* h_lc = nullptr;                                     // pinned: verdict of the last detection (ifx_loop_closure_diag)
     int lc_event_valid = 0;
-    float* d_graph = nullptr;           // deformation graph handed in for the next clean (ifx_set_deformation): nodes x 16 floats
+    // relocalisation and frame-to-frame RGB (options reloc / frame_to_frame_rgb; EF/ElasticFusion.cpp:371-423, 455-484, 620, 713-717, 729-763)
+    int opt_reloc = 0, opt_f2f_rgb = 0;
+    int reloc_lost = 0, reloc_recovery = 0;   // host mirror of DevState::reloc[0..1] (the frame synchronises once behind the gate)
+    int reloc_fused = 1;                // the last frame ran its map passes (trackingOk && !lost, :620)
+    RelocVerdict* h_reloc = nullptr;    // pinned: verdict of the last tracking gate (frame path and ifx_reloc_gate)
+    void* d_reloc_stage = nullptr;      // ifx_reloc_gate scratch: [lastA 36 x f64 | icp error f32, pad | state 3 x i32]
+    float* d_graph = nullptr;          // deformation graph handed in for the next clean (ifx_set_deformation): nodes x 16 floats
     int graph_nodes = 0, graph_is_fern = 0;
     uint8_t* d_inst_gt = nullptr;       // instanceGT of processFrame (H x W bytes) for the frames to come
     int inst_gt_on = 0;
@@ -654,6 +669,9 @@ int ifx_tracker_alloc_m2m(ifx* h);
 int ifx_tracker_loop_closure(ifx* h);                         // model-to-model tracking + gates, after ifx_map_predict_loop_closure
 int ifx_tracker_m2m_begin(ifx* h);
 int ifx_map_predict(ifx* h);                                  // splat + fill-in + dense flag
+int ifx_map_predict_lost(ifx* h);                             // option reloc, lost: predict() of EF/ElasticFusion.cpp:453 alone, into the act* images
+int ifx_tracker_reloc_gate(ifx* h);                           // option reloc: k_reloc_gate on the live state, the verdict into h_reloc
+void ifx_tracker_reloc_recovery(ifx* h, int v);               // lastFrameRecovery on the host and in the state
 int ifx_scan_exclusive(ifx* h, const int* d_flags, int n, int* d_out, int* d_total /*device ptr or null*/);
 int ifx_alloc_tracker(ifx* h);
 void ifx_free_tracker(ifx* h);

@@ -3046,6 +3046,8 @@ static void view_clean_append(ifx* h, const Cam& c, int time)
     launch_append_scan(h, c, time, h->list_v);
 }
 
+static inline int ifx_passthrough_mask(const ifx* h);
+static void ifx_map_fill_passthrough(ifx* h, int mask);
 // EF/ElasticFusion.cpp:620-694 without the loop-closure branches
 int ifx_map_frame(ifx* h)
 {
@@ -3131,7 +3133,8 @@ int ifx_map_predict(ifx* h)
         const Cam c = whole_cam(h);
         // The id image has one consumer per frame -- whetherDoSegmentation's sums over every 10th pixel -- and a full-image consumer only when a segmentation call, a
         // download or the display asks for it: the frame renders the sampled lattice only (the id half of this pass: 71 -> 40 us), ifx_ids_ensure the rest on demand.
-        const int ids_step = (h->opt_lazy_ids && !h->ids_full_hint && (want & LIST_IDS)) ? 10 : 1;
+        // (option reloc: the whole image -- ids_after must stay the last FUSED frame's through skipped frames, and a completion on demand would draw it at a later pose)
+        const int ids_step = (h->opt_lazy_ids && !h->ids_full_hint && !h->opt_reloc && (want & LIST_IDS)) ? 10 : 1;
         h->ids_full_hint = 0;
         h->ids_full_valid = ids_step == 1;
         h->ids_sparse_frame = ids_step > 1;
@@ -3151,12 +3154,21 @@ int ifx_map_predict(ifx* h)
             h->clean_raster_pending = 0;
             view_clean_append(h, whole_cam(h), h->tick);
         }
-        raster_pass(h, nullptr, h->tick, h->tick, want, h->ids_after, true);
+        // (lastFrameRecovery implies lost, a lost frame runs no map passes: the window (0, tick) of :733-742 is only ever this branch's)
+        raster_pass(h, nullptr, h->reloc_recovery ? 0 : h->tick, h->tick, want, h->ids_after, true);
         if (want & LIST_IDS) { h->ids_full_valid = 1; h->ids_sparse_frame = 0; }
         h->ids_view_ok = 0;
     }
+    ifx_map_fill_passthrough(h, ifx_passthrough_mask(h));   // (:757-759; nothing with both options off)
     h->view_frame = 0;
     h->ids_pending = 0;
+    return IFX_OK;
+}
+// predict() of EF/ElasticFusion.cpp:453 on a lost frame (option reloc): the ACTIVE render alone, into the act* images the fern callback samples -- the local
+// detection is skipped while lost (:516), so no INACTIVE render; the time window is predict()'s (:733-754)
+int ifx_map_predict_lost(ifx* h)
+{
+    raster_pass(h, nullptr, h->reloc_recovery ? 0 : h->tick, h->tick, LIST_SPLAT, nullptr, false, 0, 2);
     return IFX_OK;
 }
 
@@ -3242,6 +3254,39 @@ __global__ void k_fill_in(Cam c, const uint8_t* __restrict__ rgb, const uint16_t
         v3 nn = normalized(cross(vx - vp, vy - vp));
         fn[k] = make_float4(nn.x, nn.y, nn.z, 1.f);
     } else fn[k] = no;
+}
+
+// fill_vertex / fill_normal / fill_rgb.frag with passthrough = 1 (EF/Shaders/FillIn.cpp:65-195: `sample.z == 0 || passthrough == 1`): every pixel takes the branch
+// k_splat_resolve / k_fill_in take for an empty sample -- the vertex from the filtered depth, the normal from its +x / +y neighbours (clamped at the edge), the image from
+// the frame's colour with alpha 255.  mask bit 0: fill_vertex and fill_normal, bit 1: fill_image; an output whose bit is clear keeps what the resolve wrote (passthrough = 0).
+// A streaming kernel behind the resolve: one pixel per lane, a wave covers 64 pixels of a row (16-byte stores of fv / fn: 1 KiB per wave and image, whole lines).
+__global__ __launch_bounds__(256) void k_fill_passthrough(Cam c, const uint8_t* __restrict__ rgb, const uint16_t* __restrict__ depth_filt, float4* __restrict__ fv, float4* __restrict__ fn,
+                                                          uchar4* __restrict__ fimg, int mask)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= c.w || y >= c.h) return;
+    const int k = y * c.w + x;
+    if (mask & 2) fimg[k] = make_uchar4(rgb[k * 3], rgb[k * 3 + 1], rgb[k * 3 + 2], 255);
+    if (!(mask & 1)) return;
+    const int xr = clampi(x + 1, 0, c.w - 1), yd = clampi(y + 1, 0, c.h - 1);
+    const uint16_t d = depth_filt[k], dx = depth_filt[y * c.w + xr], dy = depth_filt[yd * c.w + x];
+    const float ifx_ = 1.0f / c.fx, ify_ = 1.0f / c.fy;
+    const float zc = (float)d / 1000.0f, zx = (float)dx / 1000.0f, zy = (float)dy / 1000.0f;
+    const v3 vp = v3m(((float)x - c.cx) * zc * ifx_, ((float)y - c.cy) * zc * ify_, zc);
+    const v3 vx = v3m(((float)(x + 1) - c.cx) * zx * ifx_, ((float)y - c.cy) * zx * ify_, zx);
+    const v3 vy = v3m(((float)x - c.cx) * zy * ifx_, ((float)(y + 1) - c.cy) * zy * ify_, zy);
+    const v3 nn = normalized(cross(vx - vp, vy - vp));
+    fv[k] = make_float4(vp.x, vp.y, vp.z, 1.f);
+    fn[k] = make_float4(nn.x, nn.y, nn.z, 1.f);
+}
+// ElasticFusion::predict's passthrough arguments (EF/ElasticFusion.cpp:757-759), behind the pass that resolved the prediction; mask 0 launches nothing
+static inline int ifx_passthrough_mask(const ifx* h) { return h->reloc_lost ? 3 : (h->opt_f2f_rgb ? 2 : 0); }   // fillIn.vertex / .normal(.., lost), fillIn.image(.., lost || frameToFrameRGB)
+static void ifx_map_fill_passthrough(ifx* h, int mask)
+{
+    if (!(mask & 3)) return;
+    const Cam c = whole_cam(h);
+    LAUNCH(h, "fill_passthrough", dim3(cdiv(h->w, 64), cdiv(h->h, 4)), dim3(64, 4), k_fill_passthrough, c, (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, (float4*)h->fill_vertex,
+           (float4*)h->fill_normal, (uchar4*)h->fill_image, mask & 3);
 }
 
 // sharded map, behind the exchange of the prediction: fill-in and dense flag, replicated; mass_in: the summed vote mass of whetherDoSegmentation (null: none travelled)
@@ -3472,17 +3517,20 @@ extern "C" int ifx_predict_indices(ifx_t* h, const float* pose16, int time)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return IFX_OK;
 }
-extern "C" int ifx_combined_predict(ifx_t* h, const float* pose16, int time, int max_time)
+extern "C" int ifx_combined_predict_ex(ifx_t* h, const float* pose16, int time, int max_time, int passthrough_mask)
 {
     if (!h || !pose16) return IFX_E_INVALID;
+    if (passthrough_mask & ~3) { h->err = "passthrough_mask: bit 0 = fill_vertex and fill_normal, bit 1 = fill_image"; return IFX_E_INVALID; }
     ifx_drop_tracked(h);
     float *dp, *di;
     int r = upload_pose(h, pose16, &dp, &di);
     if (r) return r;
     raster_pass(h, di, time, max_time, LIST_SPLAT, nullptr);
+    ifx_map_fill_passthrough(h, passthrough_mask);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return IFX_OK;
 }
+extern "C" int ifx_combined_predict(ifx_t* h, const float* pose16, int time, int max_time) { return ifx_combined_predict_ex(h, pose16, time, max_time, 0); }
 extern "C" int ifx_fuse(ifx_t* h, const float* pose16, int time, float weighting)
 {
     if (!h || !pose16) return IFX_E_INVALID;
@@ -3571,7 +3619,7 @@ extern "C" int ifx_loop_closure_constraints(ifx_t* h, float* src3, float* dst3, 
 // k_splat_resolve) is evaluated at the samples only
 __global__ void k_fern_resize(const uchar4* __restrict__ img, const float4* __restrict__ vert, const float4* __restrict__ norm, const uchar4* __restrict__ inst, int w, int h,
                               uint8_t* __restrict__ o_img, float4* __restrict__ o_vert, float4* __restrict__ o_norm, uint8_t* __restrict__ o_inst, int fill, Cam c,
-                              const uint8_t* __restrict__ rgb, const uint16_t* __restrict__ depth_filt)
+                              const uint8_t* __restrict__ rgb, const uint16_t* __restrict__ depth_filt, int pt = 0)   // pt: the fill-in's passthrough mask (k_fill_passthrough), with fill
 {
     const int rw = w / 8, rh = h / 8, t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= rw * rh) return;
@@ -3583,9 +3631,9 @@ __global__ void k_fern_resize(const uchar4* __restrict__ img, const float4* __re
     float4 vo = vert[k], no = norm[k];
     if (fill) {
         const float ifx_ = 1.0f / c.fx, ify_ = 1.0f / c.fy;
-        if ((int)cl.x + (int)cl.y + (int)cl.z == 0) cl = make_uchar4(rgb[k * 3], rgb[k * 3 + 1], rgb[k * 3 + 2], 255);
+        if ((int)cl.x + (int)cl.y + (int)cl.z == 0 || (pt & 2)) cl = make_uchar4(rgb[k * 3], rgb[k * 3 + 1], rgb[k * 3 + 2], 255);
         const float zc = (float)depth_filt[k] / 1000.0f;
-        if (no.z == 0) {
+        if (no.z == 0 || (pt & 1)) {
             v3 vp = v3m(((float)x - c.cx) * zc * ifx_, ((float)y - c.cy) * zc * ify_, zc);
             int xr = clampi(x + 1, 0, w - 1), yd = clampi(y + 1, 0, h - 1);
             float zx = (float)depth_filt[y * w + xr] / 1000.0f, zy = (float)depth_filt[yd * w + x] / 1000.0f;
@@ -3594,7 +3642,7 @@ __global__ void k_fern_resize(const uchar4* __restrict__ img, const float4* __re
             v3 nn = normalized(cross(vx - vp, vy - vp));
             no = make_float4(nn.x, nn.y, nn.z, 1.f);
         }
-        if (vo.z == 0) vo = make_float4(((float)x - c.cx) * zc * ifx_, ((float)y - c.cy) * zc * ify_, zc, 1.f);
+        if (vo.z == 0 || (pt & 1)) vo = make_float4(((float)x - c.cx) * zc * ifx_, ((float)y - c.cy) * zc * ify_, zc, 1.f);
     }
     o_img[t * 3] = cl.x; o_img[t * 3 + 1] = cl.y; o_img[t * 3 + 2] = cl.z;
     o_inst[t * 3] = q.x; o_inst[t * 3 + 1] = q.y; o_inst[t * 3 + 2] = q.z;
@@ -3609,7 +3657,7 @@ static void launch_fern_resize(ifx* h, int n, bool tracked)
     uint8_t *di = (uint8_t*)(dn + n), *ds = di + (size_t)n * 3;
     LAUNCH(h, "fern_resize", dim3(cdiv(n, 64)), dim3(64), k_fern_resize, (const uchar4*)(tracked ? h->act_image : h->fill_image), (const float4*)(tracked ? h->act_vertex : h->fill_vertex),
            (const float4*)(tracked ? h->act_normal : h->fill_normal), (const uchar4*)(tracked ? h->act_inst : h->pred_inst), h->w, h->h, di, dv, dn, ds, tracked ? 1 : 0, make_cam(h),
-           (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt);
+           (const uint8_t*)h->rgb, (const uint16_t*)h->depth_filt, tracked ? ifx_passthrough_mask(h) : 0);   // (the end-of-frame fill-in images carry the passthrough already)
 }
 extern "C" int ifx_fern_frame(ifx_t* h, uint8_t* img_rgb, float* verts4, float* norms4, uint8_t* inst_rgb)
 {
@@ -3698,6 +3746,7 @@ extern "C" int ifx_adopt_pose(ifx_t* h, const float* pose16)
     ifx_drop_tracked(h);
     h->view_block = 1;
     LAUNCH(h, "adopt_pose", dim3(1), dim3(64), k_adopt_pose, h->d_state, p);
+    if (h->reloc_lost) ifx_tracker_reloc_recovery(h, 1);   // currPose = recoveryPose; lastFrameRecovery = true (:480-484)
     return IFX_OK;
 }
 

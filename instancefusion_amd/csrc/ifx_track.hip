@@ -2802,6 +2802,8 @@ void ifx_free_tracker(ifx* h)
     }
     free_m2m(h);
     hipFree(h->d_graph); hipFree(h->d_sample); hipFree(h->d_cons); hipFree(h->d_project); hipFree(h->d_fern); hipFree(h->d_inst_gt);
+    hipFree(h->d_reloc_stage);
+    if (h->h_reloc) hipHostFree(h->h_reloc);
     if (h->h_fern) hipHostFree(h->h_fern);
     if (h->ev_fern) hipEventDestroy(h->ev_fern);
     hipFree(h->pyr.acc); hipFree(h->res_partials); hipFree(h->d_out29); hipFree(h->d_ticket);
@@ -3277,7 +3279,9 @@ int ifx_tracker_model_side(ifx* h, int fold_begin)
         gb.st = h->d_state; gb.ss = h->slot[h->cur_slot].so3; gb.so3 = c.so3; gb.fx = c.fx / div; gb.fy = c.fy / div; gb.cx = c.cx / div; gb.cy = c.cy / div;
         gb.keep_last = 0; gb.enabled = 1; gb.persist = h->opt_gn_persist ? 1 : 0;
     }
-    tracker_init_model(h, h->d_state, h->pyr, h->cfg.icp_weight, h->pred_vertex, h->pred_normal, h->pred_image, h->fill_vertex, h->fill_normal, h->fill_image, fold ? &gb : nullptr);
+    // option frame_to_frame_rgb: initRGBModel takes the fill-in image whatever the dense flag says (EF/ElasticFusion.cpp:346) -- the previous raw frame (:759)
+    tracker_init_model(h, h->d_state, h->pyr, h->cfg.icp_weight, h->pred_vertex, h->pred_normal, h->opt_f2f_rgb ? h->fill_image : h->pred_image, h->fill_vertex, h->fill_normal, h->fill_image,
+                       fold ? &gb : nullptr);
     h->gn_begin_folded = fold ? 1 : 0;
     return IFX_OK;
 }
@@ -3422,7 +3426,44 @@ __global__ void k_m2m_arm(DevState* __restrict__ m)
 {
     if (threadIdx.x == 0) m->skip = (m->count == 0);
 }
-// getCovariance (EF/Utils/RGBDOdometry.cpp:605-608: lastA.lu().inverse(), here Gauss-Jordan with partial pivoting in f64) and the gates of
+// getCovariance (EF/Utils/RGBDOdometry.cpp:605-608: lastA.lu().inverse()): the diagonal of the inverse of the run's last normal matrix, Gauss-Jordan with partial
+// pivoting in f64.  One copy, for the loop-closure verdict (k_m2m_decide) and for the tracking gate (k_reloc_gate); the caller is one lane.
+__device__ __forceinline__ void covariance_diag6(const double* __restrict__ lastA, double* __restrict__ diag)
+{
+    // every index below is a compile-time constant after unrolling (the pivot row is swapped in by predicated exchanges), so the
+    // 6 x 12 tableau lives in registers: 50 us -> a few us for a one-thread kernel on the critical path of the frame result
+    double a[6][12];
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+        for (int c = 0; c < 6; c++) { a[r][c] = lastA[r * 6 + c]; a[r][6 + c] = (r == c) ? 1.0 : 0.0; }
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        int piv = k;
+        double best = fabs(a[k][k]);
+#pragma unroll
+        for (int r = k + 1; r < 6; r++) { const double v = fabs(a[r][k]); if (v > best) { best = v; piv = r; } }
+#pragma unroll
+        for (int r = k + 1; r < 6; r++)
+            if (piv == r) {
+#pragma unroll
+                for (int c = 0; c < 12; c++) { const double tmp = a[k][c]; a[k][c] = a[r][c]; a[r][c] = tmp; }
+            }
+        const double d = 1.0 / a[k][k];
+#pragma unroll
+        for (int c = 0; c < 12; c++) a[k][c] *= d;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            if (r == k) continue;
+            const double f = a[r][k];
+#pragma unroll
+            for (int c = 0; c < 12; c++) a[r][c] -= f * a[k][c];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) diag[i] = a[i][6 + i];
+}
+// getCovariance (covariance_diag6) and the gates of
 // EF/ElasticFusion.cpp:547-566.  The verdict goes to the main state; the deformation an accepted candidate triggers in the reference is
 // not part of this path: candidates are counted and reported.
 __global__ void k_m2m_decide(DevState* __restrict__ st, const DevState* __restrict__ m, int count_thresh, float err_thresh, float cov_thresh, float* __restrict__ host_lc)
@@ -3433,42 +3474,14 @@ __global__ void k_m2m_decide(DevState* __restrict__ st, const DevState* __restri
     lc[1] = (float)m->count;
     for (int k = 0; k < 16; k++) lc[6 + k] = st->pose[k];
     if (!m->skip) {
-        // every index below is a compile-time constant after unrolling (the pivot row is swapped in by predicated exchanges), so the
-        // 6 x 12 tableau lives in registers: 50 us -> a few us for this one-thread kernel on the critical path of the frame result
-        double a[6][12];
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = 0; c < 6; c++) { a[r][c] = m->lastA[r * 6 + c]; a[r][6 + c] = (r == c) ? 1.0 : 0.0; }
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            int piv = k;
-            double best = fabs(a[k][k]);
-#pragma unroll
-            for (int r = k + 1; r < 6; r++) { const double v = fabs(a[r][k]); if (v > best) { best = v; piv = r; } }
-#pragma unroll
-            for (int r = k + 1; r < 6; r++)
-                if (piv == r) {
-#pragma unroll
-                    for (int c = 0; c < 12; c++) { const double tmp = a[k][c]; a[k][c] = a[r][c]; a[r][c] = tmp; }
-                }
-            const double d = 1.0 / a[k][k];
-#pragma unroll
-            for (int c = 0; c < 12; c++) a[k][c] *= d;
-#pragma unroll
-            for (int r = 0; r < 6; r++) {
-                if (r == k) continue;
-                const double f = a[r][k];
-#pragma unroll
-                for (int c = 0; c < 12; c++) a[r][c] -= f * a[k][c];
-            }
-        }
+        double cov[6];
+        covariance_diag6(m->lastA, cov);
         int cov_ok = 1;
         double cmax = 0;
 #pragma unroll
         for (int i = 0; i < 6; i++) {
-            if (a[i][6 + i] > (double)cov_thresh) cov_ok = 0;
-            if (!(a[i][6 + i] <= cmax)) cmax = a[i][6 + i];
+            if (cov[i] > (double)cov_thresh) cov_ok = 0;
+            if (!(cov[i] <= cmax)) cmax = cov[i];
         }
         const int accept = cov_ok && m->lastICPCount > (float)count_thresh && m->lastICPError < err_thresh;
         lc[0] = 1.f; lc[2] = m->lastICPError; lc[3] = m->lastICPCount; lc[4] = (float)cov_ok; lc[5] = (float)accept;
@@ -3478,6 +3491,85 @@ __global__ void k_m2m_decide(DevState* __restrict__ st, const DevState* __restri
     }
     lc[23] = (float)st->lc_candidates;
     for (int k = 0; k < 24; k++) host_lc[k] = lc[k];
+}
+
+// ---- tracking gate of the relocalisation mode (EF/ElasticFusion.cpp:371-423), behind the frame-to-model tracker of a tracked or bootstrapped frame.
+// One wave, lane 0 decides: icp_error / lastA are the run's lastICPError and the last iteration's normal matrix (what getCovariance inverts), state =
+// {lost, lastFrameRecovery, trackingCount}.  The error is compared in f32 against 1e-4f; a covariance diagonal in f64 against the double literal 1e-04
+// (not against (double)1e-4f, as k_m2m_decide compares with its float argument).  A NaN fails either comparison's "passes" side: error NaN -> not ok.
+// The diagonals are reported whatever the branch; they decide only where the reference computes them (not lost, or lost with lastFrameRecovery).
+__global__ __launch_bounds__(64) void k_reloc_gate(const double* __restrict__ lastA, const float* __restrict__ icp_error, int* __restrict__ state, RelocVerdict* __restrict__ out)
+{
+    if (threadIdx.x != 0) return;
+    const float err = *icp_error;
+    int lost = state[0], recovery = state[1], count = state[2];
+    double cov[6];
+    covariance_diag6(lastA, cov);
+    int cov_ok = 1;
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+        if (cov[i] > 1e-04) cov_ok = 0;
+    int ok = err < 1e-4f;
+    if (!lost) {
+        ok = ok && cov_ok;
+        if (!ok) { count++; if (count > 10) lost = 1; }
+        else count = 0;
+    } else if (recovery) {
+        ok = ok && cov_ok;
+        if (ok) { lost = 0; count = 0; }
+        recovery = 0;
+    }
+    state[0] = lost; state[1] = recovery; state[2] = count;
+    out->ok = ok; out->lost = lost; out->last_frame_recovery = recovery; out->tracking_count = count;
+    out->icp_error = err; out->pad = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) out->cov_diag[i] = cov[i];
+}
+static int reloc_verdict_alloc(ifx* h)
+{
+    if (h->h_reloc) return IFX_OK;
+    HIPCHK(h, hipHostMalloc((void**)&h->h_reloc, sizeof(RelocVerdict), hipHostMallocDefault));
+    memset(h->h_reloc, 0, sizeof(RelocVerdict));
+    return IFX_OK;
+}
+// frame path (option reloc): the gate behind the frame-to-model tracker of the frame just tracked, on the live state; the caller waits for the stream and reads h_reloc
+int ifx_tracker_reloc_gate(ifx* h)
+{
+    const int r = reloc_verdict_alloc(h);
+    if (r) return r;
+    DevState* st = h->d_state;
+    LAUNCH(h, "reloc_gate", dim3(1), dim3(64), k_reloc_gate, (const double*)st->lastA, (const float*)&st->lastICPError, st->reloc, h->h_reloc);
+    return IFX_OK;
+}
+// lastFrameRecovery outside the gate: set by ifx_adopt_pose while lost (EF/ElasticFusion.cpp:480-484), cleared in front of the fern lookup (:455)
+__global__ void k_reloc_recovery(DevState* st, int v) { if (threadIdx.x == 0) st->reloc[1] = v; }
+void ifx_tracker_reloc_recovery(ifx* h, int v)
+{
+    h->reloc_recovery = v;
+    LAUNCH(h, "reloc_recovery", dim3(1), dim3(64), k_reloc_recovery, h->d_state, v);
+}
+// the gate as a stage: the caller's matrix, error and state through a scratch block of the handle, the verdict back through pinned memory
+extern "C" int ifx_reloc_gate(ifx_t* h, const double* lastA36, float icp_error, int32_t* state3_inout, int32_t* ok_out, double* cov_diag6)
+{
+    if (!h || !lastA36 || !state3_inout) return IFX_E_INVALID;
+    struct Stage { double lastA[36]; float err; int pad; int state[4]; } s;
+    if (!h->d_reloc_stage) HIPCHK(h, hipMalloc(&h->d_reloc_stage, sizeof(Stage)));
+    { const int r = reloc_verdict_alloc(h); if (r) return r; }
+    const RelocVerdict keep = *h->h_reloc;   // (the frame path's last verdict stays what ifx_reloc_state reports)
+    memcpy(s.lastA, lastA36, sizeof(s.lastA));
+    s.err = icp_error; s.pad = 0;
+    s.state[0] = state3_inout[0] != 0; s.state[1] = state3_inout[1] != 0; s.state[2] = state3_inout[2]; s.state[3] = 0;
+    Stage* d = (Stage*)h->d_reloc_stage;
+    HIPCHK(h, hipMemcpyAsync(d, &s, sizeof(Stage), hipMemcpyHostToDevice, h->stream));
+    LAUNCH(h, "reloc_gate", dim3(1), dim3(64), k_reloc_gate, (const double*)d->lastA, (const float*)&d->err, d->state, h->h_reloc);
+    HIPCHK(h, hipMemcpyAsync(s.state, d->state, sizeof(s.state), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const RelocVerdict v = *h->h_reloc;
+    *h->h_reloc = keep;
+    state3_inout[0] = s.state[0]; state3_inout[1] = s.state[1]; state3_inout[2] = s.state[2];
+    if (ok_out) *ok_out = v.ok;
+    if (cov_diag6) memcpy(cov_diag6, v.cov_diag, sizeof(v.cov_diag));
+    return IFX_OK;
 }
 
 int ifx_tracker_alloc_m2m(ifx* h)

@@ -217,7 +217,8 @@ public:
     // countThresh / errThresh / covThresh: INACTIVE prediction + model-to-model tracking + gates; candidates are counted, the deformation
     // they trigger in the reference is outside the path) and the fern data base (ferns(500, depthCut * 1000, photoThresh),
     // EF/ElasticFusion.cpp:49): findFrame every frame inside the handle's fern callback, addFrame with fernThresh after every frame.  A fern match
-    // needs the reference's global graph optimiser to become a deformation: that is the caller's (setFernHandler).  reloc is kept for the getter only.
+    // needs the reference's global graph optimiser to become a deformation: that is the caller's (setFernHandler).  reloc and frameToFrameRGB set the library's
+    // options of those names (ifx_set_option: the tracking gate, lost / recovery, the passthrough fill-in); neither is offered on a sharded map.
     ElasticFusion(const int timeDelta = 200, const int countThresh = 35000, const float errThresh = 5e-05, const float covThresh = 1e-05,
                   const bool closeLoops = true, const bool iclnuim = false, const bool reloc = false, const float photoThresh = 115,
                   const float confidence = 10, const float depthCut = 3, const float icpThresh = 10, const bool fastOdom = false,
@@ -226,7 +227,7 @@ public:
         : saveFilename(fileName), closeLoops_(closeLoops), iclnuim_(iclnuim), reloc_(reloc), frameToFrameRGB_(frameToFrameRGB),
           countThresh_(countThresh), errThresh_(errThresh), covThresh_(covThresh), photoThresh_(photoThresh), fernThresh_(fernThresh), sharding_(sharding)
     {
-        if (frameToFrameRGB) throw std::runtime_error("ElasticFusion: frameToFrameRGB is not part of the MI355X path");
+        if (sharding.on() && (reloc || frameToFrameRGB)) throw std::runtime_error("ElasticFusion: reloc / frameToFrameRGB are not available on a spatially sharded map");
         if (sharding.on() && closeLoops) throw std::runtime_error("ElasticFusion: loop closure is not available on a spatially sharded map (pass closeLoops = false)");
         std::memset(&cfg_, 0, sizeof(cfg_));
         cfg_.width = Resolution::getInstance().width();
@@ -273,6 +274,11 @@ public:
                 ifx_destroy(h_);
                 throw std::runtime_error("ifx_set_fern_callback: " + e);
             }
+        }
+        if ((reloc && ifx_set_option(h_, "reloc", 1) != IFX_OK) || (frameToFrameRGB && ifx_set_option(h_, "frame_to_frame_rgb", 1) != IFX_OK)) {
+            const std::string e = ifx_last_error(h_);
+            ifx_destroy(h_);
+            throw std::runtime_error("ifx_set_option: " + e);
         }
         currPose_ = Matrix4f::Identity();
     }
@@ -322,7 +328,7 @@ public:
             if (ifx_fern_frame_async(h_) < 0) throw std::runtime_error(std::string("ifx_fern_frame_async: ") + ifx_last_error(h_));
             fernPending_ = true; fernPendingPose_ = currPose_; fernPendingTick_ = tick_;
         }
-        tick_++;
+        if (!lost_) tick_++;   // EF/ElasticFusion.cpp:713-717
         poseGraph_.push_back(currPose_);
         poseLogTimes_.push_back(timestamp);
     }
@@ -360,6 +366,7 @@ public:
     void setPyramid(const bool& val) { option("pyramid", val ? 1 : 0); cfg_.pyramid = val; }
     void setFastOdom(const bool& val) { option("fast_odom", val ? 1 : 0); cfg_.fast_odom = val; }
     void setSo3(const bool& val) { option("so3", val ? 1 : 0); cfg_.so3 = val; }
+    void setFrameToFrameRGB(const bool& val) { option("frame_to_frame_rgb", val ? 1 : 0); frameToFrameRGB_ = val; }   // EF/ElasticFusion.cpp:1303
     // option "id_rule" (ifx_c_api.h): true = the id images by the reference's surfel_ids.geom / .frag rule (screen-space quads, 24-bit depth); unsharded maps only
     void setReferenceIdRule(const bool& val) { option("id_rule", val ? 1 : 0); }
 
@@ -696,9 +703,16 @@ private:
             Matrix4f tracked;
             if (ifx_get_pose(h, tracked.data()) < 0) return IFX_E_STATE;
             std::vector<Ferns::SurfaceConstraint> constraints;
-            const Matrix4f recoveryPose = self->ferns_->findFrame(constraints, tracked, h, self->smallInstanceTable_, self->tick_, self->lost_);
+            float rs[12];   // `lost` as THIS frame's gate left it (the library judged the tracker before it got here)
+            if (ifx_reloc_state(h, rs) < 0) return IFX_E_STATE;
+            const bool lost = rs[1] != 0.f;
+            const Matrix4f recoveryPose = self->ferns_->findFrame(constraints, tracked, h, self->smallInstanceTable_, self->tick_, lost);
             if (self->ferns_->lastClosest == -1) return 0;
             self->fernMatches_++;
+            if (lost) {   // EF/ElasticFusion.cpp:478-484: currPose = recoveryPose, lastFrameRecovery = true (ifx_adopt_pose sets it while lost); no global deformation
+                self->adoptPose(recoveryPose);
+                return 0;
+            }
             const int fernSrcTime = self->ferns_->frames[self->ferns_->lastClosest]->srcTime;
             if (!self->fernHandler_ && !self->deformOnLoopClosure_) return 0;
             const std::vector<float> rawGraph = self->fernHandler_ ? self->fernHandler_(*self, constraints, recoveryPose, fernSrcTime)
@@ -801,11 +815,12 @@ public:
     // IF/map_interface/ElasticFusionInterface.cpp:27-58 (the GL context and colour look-up go away; the constants stay)
     // closeLoops / confidence: the reference passes true / 10; exposed for replays that want the plain pipeline or a quicker map
     virtual bool Init(std::vector<ClassColour> class_colour_lookup, int maxSurfels = 6 * 1000 * 1000, int device = 0,
-                      const std::string& fileName = "./ResultModel", bool closeLoops = true, float confidence = 10.f, const Sharding& sharding = Sharding())
+                      const std::string& fileName = "./ResultModel", bool closeLoops = true, float confidence = 10.f, const Sharding& sharding = Sharding(),
+                      bool reloc = false, bool frameToFrameRGB = false)
     {
         class_colour_lookup_ = std::move(class_colour_lookup);
         try {
-            elastic_fusion_.reset(new ElasticFusion(200, 35000, 5e-05, 1e-05, closeLoops, false, false, 115, confidence, 12, 10, false, 0.3095, true, false, fileName,
+            elastic_fusion_.reset(new ElasticFusion(200, 35000, 5e-05, 1e-05, closeLoops, false, reloc, 115, confidence, 12, 10, false, 0.3095, true, frameToFrameRGB, fileName,
                                                     maxSurfels, device, sharding));
         } catch (const std::exception& e) {
             std::fprintf(stderr, "ElasticFusionInterface::Init: %s\n", e.what());

@@ -21,7 +21,7 @@ struct Args {
     std::string log, masks, out = "./ResultModel", labels, gt_dir, eval_file;
     int width = 640, height = 480, max_frames = 0, max_surfels = 6 * 1000 * 1000, device = 0;
     float fx = 528.f, fy = 528.f, cx = 320.f, cy = 240.f;
-    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false, mask_iou = false, merge_duplicates = false;
+    bool superpixels = true, flip = false, close_loops = true, deform = true, lookahead = true, reference_ids = false, mask_iou = false, merge_duplicates = false, reloc = false, f2f_rgb = false;
     int decode_threads = 4;
     int mask_lag = -1;   // --mask-lag K: the masks recorded for frame t arrive K frames later (a detector slower than the frame loop) and are applied through a snapshot of frame t
     float confidence = 10.f;
@@ -32,7 +32,7 @@ int usage(const char* argv0)
 {
     std::fprintf(stderr,
                  "usage: %s LOG.klg|data.txt [--width W --height H --fx F --fy F --cx C --cy C] [--masks DIR] [--out PREFIX]\n"
-                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K] [--mask-iou] [--merge-duplicates]\n"
+                 "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K] [--mask-iou] [--merge-duplicates] [--reloc] [--frame-to-frame-rgb]\n"
                  "       [--gt-dir DIR (DIR/<frame, 6 digits>.png, 8-bit instance ground truth)] [--eval FILE (precision / recall rows, needs --gt-dir)]\n"
                  "       [--shard-ranks G --shard-rank r --shard-id FILE [--shard-nonce N] (one process per GPU over one spatially sharded map; every rank replays the same log; -1: a world of one)]\n",
                  argv0);
@@ -73,6 +73,8 @@ int main(int argc, char** argv)
         else if (s == "--reference-ids") a.reference_ids = true;   // id images by the reference's screen-space quad rule (option "id_rule" = 1; not on a sharded map)
         else if (s == "--mask-iou") a.mask_iou = true;   // masks are matched to instances by mask IoU over dilated pixel sets (the reference's compareMapType 2; option "compare_map" = 2; not on a sharded map)
         else if (s == "--merge-duplicates") a.merge_duplicates = true;   // on the first frame after a deformation: instances of one class whose projected boxes coincide are merged (the reference's checkLoopClosure, switched off there; not on a sharded map)
+        else if (s == "--reloc") a.reloc = true;   // ElasticFusion's relocalisation mode: frames that fail the tracking gate are not fused; a lost frame ends the replay (IF/main.cpp:137-142)
+        else if (s == "--frame-to-frame-rgb") a.f2f_rgb = true;   // the photometric term tracks against the previous raw frame (frameToFrameRGB)
         else if (s == "--mask-lag") a.mask_lag = std::atoi(val("--mask-lag"));   // snapshot at the frame the masks belong to, deferred call K frames later (one detection in flight, as with one detector)
         else if (s == "--no-lookahead") a.lookahead = false;   // frames are handed over one at a time, as the reference's loop does
         else if (s == "--shard-ranks") a.shard.ranks = std::atoi(val("--shard-ranks"));   // -1: a world of one on the sharded path
@@ -85,6 +87,7 @@ int main(int argc, char** argv)
     }
     if (a.log.empty()) return usage(argv[0]);
     if (a.merge_duplicates && a.shard.on()) { std::fprintf(stderr, "--merge-duplicates is not available on a sharded map\n"); return 2; }
+    if ((a.reloc || a.f2f_rgb) && a.shard.on()) { std::fprintf(stderr, "--reloc / --frame-to-frame-rgb are not available on a sharded map\n"); return 2; }
 
     try {
         Resolution::getInstance(a.width, a.height);            // IF/main.cpp:46-47
@@ -105,7 +108,7 @@ int main(int argc, char** argv)
         std::unique_ptr<ElasticFusionInterface> map(new ElasticFusionInterface());
         if (a.shard.on()) a.close_loops = false;   // (not available on a sharded map)
         if (a.shard.ranks > 1 && a.shard.nonce == 0) a.shard.nonce = Sharding::nonceFromLauncher();   // (the launcher's job id tells this run's id file from a leftover; 0 when it exports none)
-        if (!map->Init(instancefusion->getInstanceTable(), a.max_surfels, a.device, a.out, a.close_loops, a.confidence, a.shard)) {
+        if (!map->Init(instancefusion->getInstanceTable(), a.max_surfels, a.device, a.out, a.close_loops, a.confidence, a.shard, a.reloc, a.f2f_rgb)) {
             std::cout << "ElasticFusionInterface init failure" << std::endl;
             return 1;
         }
