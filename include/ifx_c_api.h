@@ -1083,6 +1083,30 @@ int ifx_labels(ifx_t* h, int32_t* out, int max_n);
  * floats (r, g, b in [0,1], alpha 1; black where no stable surfel is visible).  out_rgba: host buffer or NULL; d_out_rgba: device buffer or NULL
  * (enqueue only, no synchronisation).  The 2-D boxes the reference draws on top on the host are not drawn. */
 int ifx_render_project_map(ifx_t* h, float* out_rgba, float* d_out_rgba);
+/* Free-viewpoint render of the map: the surfel pass of the reference's main window -- GlobalModel::renderPointCloud (draw_global_surface.vert / .geom / .frag,
+ * EF/GlobalModel.cpp:328-391) and GlobalModel::renderGlobalID (draw_global_ID.*) -- from any camera on a viewport of any size.
+ *   mvp          4 x 4, row-major: clip = mvp . (x, y, z, 1) of a world point.  The reference's camera is Pangolin's ProjectionMatrix(w, h, fu, fv, u0, v0, zNear, zFar) times
+ *                the inverse pose (viewer_mvp in the Python package, ifx::viewerMvp in ifx_host.hpp): clip.x = (2 fx / w) X + (1 - 2 cx / w) Z,
+ *                clip.y = -(2 fy / h) Y - (1 - 2 cy / h) Z, clip.z = (far + near) / (far - near) Z - 2 far near / (far - near), clip.w = Z in the camera frame (y down,
+ *                z forward).  With the frame's intrinsics at the tracked pose the output has the orientation of pred_image.
+ *   w, h         the viewport, 1..4096 each, unrelated to the frame's size.
+ *   threshold    a surfel is drawn if its confidence is above it, or if `unstable`; NaN: the handle's confidence threshold.  A surfel at or below it is pushed back
+ *                by its radius in depth (draw_global_surface.frag:35-42).  A surfel whose instance-colour word is -1 is never drawn (.vert:44).
+ *   color_type   0 shaded grey, 1 normal, 2 the colour word, 3 a ramp of the creation time against `time`, 4 the instance-colour word; then dimmed by 0.25 when
+ *                draw_window and time - lastUpdate > time_delta, then blended 0.6 / 0.4 with the shaded grey (.geom:50-88).
+ *   time         < 0: the handle's tick.  time_delta < 0: the handle's.  clear_rgb: the colour where nothing is drawn (the GUI clears to white).
+ * Outputs, top row first (output row r is GL window row h - 1 - r), host (out_*), device (d_out_*), both or neither of each:
+ *   rgba  h x w x 4 floats: the base colour of the nearest surfel (per surfel, not interpolated), alpha 1; clear_rgb with alpha 0 where nothing was drawn
+ *   ids   h x w int32: the slot of that surfel in the numbering of ids_after; -1 where nothing was drawn (there is no "surfel 0" rule here)
+ * Rasterised as GL does it (quads of four separately projected corners, 1/256 px snap, top-left rule, perspective-correct texcoord, 24-bit depth cleared to 1 with
+ * GL_LESS, ties to the lower slot), with ONE deviation: a quad with a corner at clip.w <= 0 or more than 65536 px outside the window is not drawn, where GL clips
+ * it and draws the visible part.  Read-only on the map; enqueued on the main stream behind the last frame; the host is synchronised only
+ * when a host output is given.  IFX_E_INVALID: w or h outside 1..4096, color_type outside 0..4, a non-finite mvp (nothing is written).  IFX_E_STATE: a sharded
+ * handle, or between the stage calls of a frame.
+ * ifx_render_view_big_quads: how many quads of the last call covered more than 256 pixels and were drawn by a workgroup each (synchronises the main stream). */
+typedef struct { float mvp[16]; int32_t w, h; float threshold; int32_t color_type, unstable, draw_window, time, time_delta; float clear_rgb[3]; } ifx_view_params;
+int ifx_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids);
+int ifx_render_view_big_quads(ifx_t* h);
 /* ---- instance ground truth (the reference's ScanNet evaluation).
  * ifx_set_instance_gt: the instanceGT argument of ElasticFusion::processFrame (EF/ElasticFusion.h:79, EF/ElasticFusion.cpp:285-291): H x W bytes; surfels created by the
  *   frames that follow remember the id under the pixel that created them (vImgCorr.w, data.vert:215-228; -2 without ground truth).  NULL switches it off.

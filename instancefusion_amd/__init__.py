@@ -86,6 +86,12 @@ class MaskHeadParams(C.Structure):
     _fields_ = [("score_thresh", C.c_float), ("in_w", C.c_int32), ("in_h", C.c_int32), ("out_w", C.c_int32), ("out_h", C.c_int32), ("sort_by_score", C.c_int32)]
 
 
+class ViewParams(C.Structure):
+    """ifx_view_params: the camera and the flags of ifx_render_view (include/ifx_c_api.h)"""
+    _fields_ = [("mvp", C.c_float * 16), ("w", C.c_int32), ("h", C.c_int32), ("threshold", C.c_float), ("color_type", C.c_int32), ("unstable", C.c_int32),
+                ("draw_window", C.c_int32), ("time", C.c_int32), ("time_delta", C.c_int32), ("clear_rgb", C.c_float * 3)]
+
+
 class SoaView(C.Structure):
     _fields_ = [("count", C.c_int32), ("capacity", C.c_int32), ("d_pos_conf", C.c_void_p), ("d_norm_rad", C.c_void_p),
                 ("d_color", C.c_void_p), ("d_times", C.c_void_p), ("d_img_corr", C.c_void_p), ("d_votes", C.c_void_p)]
@@ -247,6 +253,8 @@ _SIGS = {
     "ifx_segmentation_snapshot_stats": (C.c_int, [_P, C.c_int, _P]),
     "ifx_labels": (C.c_int, [_P, _P, C.c_int]),
     "ifx_render_project_map": (C.c_int, [_P, _P, _P]),
+    "ifx_render_view": (C.c_int, [_P, C.POINTER(ViewParams), _P, _P, _P, _P]),
+    "ifx_render_view_big_quads": (C.c_int, [_P]),
     "ifx_set_instance_gt": (C.c_int, [_P, _P]),
     "ifx_precision_recall": (C.c_int, [_P, _P, _P, _P]),
     "ifx_instance_table": (C.c_int, [_P, _P]),
@@ -321,6 +329,41 @@ MASK_F32 = 1    # inside iff the value is > threshold (mask probabilities; NaN i
 # option "id_rule" (include/ifx_c_api.h): which rule draws the surfel-id images
 ID_RULE_RAY_DISC = 0     # default: a ray through each pixel centre against the disc, f32 depth keys
 ID_RULE_REFERENCE = 1    # the reference's surfel_ids.geom / .frag: screen-space quads, 24-bit depth
+
+
+
+def viewer_mvp(fx, fy, cx, cy, w, h, near, far, pose):
+    """The reference viewer's camera as the 4x4 MVP of ifx_render_view: Pangolin's ProjectionMatrix(w, h, fu, fv, u0, v0, zNear, zFar) times the inverse of
+    the (rigid) camera pose -- camera frame y down, z forward.  Computed in f64 and rounded to f32 once.  With the frame's intrinsics at the tracked pose
+    the output of render_view has the orientation of pred_image."""
+    T = [[float(v) for v in row] for row in np.asarray(pose, np.float64).reshape(4, 4)]
+    Ti = [[0.0] * 4 for _ in range(4)]      # R^T, -(R^T t); every sum left to right, as ifx_host.hpp viewerMvp (the two agree bit for bit)
+    for i in range(3):
+        t = 0.0
+        for j in range(3):
+            Ti[i][j] = T[j][i]
+            t += T[j][i] * T[j][3]
+        Ti[i][3] = -t
+    Ti[3][3] = 1.0
+    fx, fy, cx, cy, w, h, near, far = (float(v) for v in (fx, fy, cx, cy, w, h, near, far))
+    P = [[2.0 * fx / w, 0.0, 1.0 - 2.0 * cx / w, 0.0],
+         [0.0, -(2.0 * fy / h), -(1.0 - 2.0 * cy / h), 0.0],
+         [0.0, 0.0, (far + near) / (far - near), -(2.0 * far * near) / (far - near)],
+         [0.0, 0.0, 1.0, 0.0]]
+    out = np.zeros((4, 4), np.float64)
+    for i in range(4):
+        for j in range(4):
+            s = 0.0
+            for k in range(4):
+                s += P[i][k] * Ti[k][j]
+            out[i, j] = s
+    return out.astype(np.float32)
+
+
+def view_color_type(draw_instances=False, draw_times=False, draw_colors=False, draw_normals=False):
+    """The GUI's flags as colorType, in the order GlobalModel::renderPointCloud resolves them (EF/GlobalModel.cpp:355): instances 4, normals 1, colours 2, times 3, else 0"""
+    return 4 if draw_instances else 1 if draw_normals else 2 if draw_colors else 3 if draw_times else 0
+
 
 # -- the detector side of the binding (detector.py): it needs the names above, and its names are this package's too
 from .detector import (DET_SCALE_255, DET_SWAP_RB, MOLD_MEAN_PIXEL, MOLD_NCHW, MOLD_NHWC, UNMOLD_NCHW, UNMOLD_NHWC, _box_post_processor_class,  # noqa: E402,F401
@@ -629,6 +672,35 @@ class ElasticFusion(_DetectorOperators):
         a = {k: np.ascontiguousarray(m[k], np.float32) for k in ("pc", "nr", "col", "tm", "ic", "votes")}
         self._chk(self.L.ifx_map_upload(self.handle, n, _ptr(a["pc"]), _ptr(a["nr"]), _ptr(a["col"]), _ptr(a["tm"]), _ptr(a["ic"]), _ptr(a["votes"])),
                   "ifx_map_upload")
+
+    def render_view(self, mvp, size, color_type=None, threshold=None, unstable=False, draw_window=False, time=-1, time_delta=-1, clear_rgb=(1.0, 1.0, 1.0),
+                    draw_instances=False, draw_times=False, draw_colors=False, draw_normals=False, device=False):
+        """ifx_render_view: the map drawn from any camera, the reference viewer's surfel pass (GlobalModel::renderPointCloud + renderGlobalID).
+        mvp: 4x4 (viewer_mvp builds the reference's); size: (w, h) of the viewport, unrelated to the frame's.  color_type 0..4, or the GUI's flags by
+        name (view_color_type).  threshold None / time < 0 / time_delta < 0: the handle's own.  Returns (rgba [h, w, 4] f32, ids [h, w] int32: the slot
+        under each pixel in the numbering of ids_after, -1 where nothing was drawn), top row first; device=True: two torch tensors on the GPU."""
+        w, h = int(size[0]), int(size[1])
+        p = ViewParams()
+        m = np.ascontiguousarray(mvp, np.float32).reshape(16)
+        p.mvp[:] = [float(v) for v in m]
+        p.w, p.h = w, h
+        p.threshold = float("nan") if threshold is None else float(threshold)
+        p.color_type = int(view_color_type(draw_instances, draw_times, draw_colors, draw_normals) if color_type is None else color_type)
+        p.unstable, p.draw_window, p.time, p.time_delta = int(bool(unstable)), int(bool(draw_window)), int(time), int(time_delta)
+        p.clear_rgb[:] = [float(v) for v in clear_rgb]
+        ok = 1 <= w <= 4096 and 1 <= h <= 4096      # (the call refuses other sizes; the buffers below only need to exist)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.cfgd["device"])
+            rgba = torch.empty((h if ok else 1, w if ok else 1, 4), dtype=torch.float32, device=dev)
+            ids = torch.empty((h if ok else 1, w if ok else 1), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()      # the tensors' memory is ours before the handle's stream writes it
+            self._chk(self.L.ifx_render_view(self.handle, C.byref(p), None, None, C.c_void_p(rgba.data_ptr()), C.c_void_p(ids.data_ptr())), "ifx_render_view")
+            self.sync()
+            return rgba, ids
+        rgba, ids = np.zeros((h if ok else 1, w if ok else 1, 4), np.float32), np.zeros((h if ok else 1, w if ok else 1), np.int32)
+        self._chk(self.L.ifx_render_view(self.handle, C.byref(p), _ptr(rgba), _ptr(ids), None, None), "ifx_render_view")
+        return rgba, ids
 
     def set_pose(self, pose, tick):
         p = np.ascontiguousarray(pose, np.float32).reshape(16)

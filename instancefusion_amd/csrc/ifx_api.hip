@@ -271,6 +271,7 @@ extern "C" void ifx_destroy(ifx_t* h)
     for (int q_ = 0; q_ < 2; q_++) { if (h->hint_stage_rgb[q_]) hipHostFree(h->hint_stage_rgb[q_]); if (h->hint_stage_depth[q_]) hipHostFree(h->hint_stage_depth[q_]); }
     if (h->rgb_stage) hipHostFree(h->rgb_stage);
     if (h->depth_stage) hipHostFree(h->depth_stage);
+    ifx_view_free(h);
     ifx_free_tracker(h);
     ifx_free_instance(h);
     ifx_slic_free(h);

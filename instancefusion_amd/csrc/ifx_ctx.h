@@ -448,6 +448,11 @@ struct ifx {
     int inst_gt_on = 0;
     void* d_fern = nullptr;             // ifx_fern_frame scratch
     float* d_project = nullptr;         // ifx_render_project_map scratch (H x W float4)
+    // ifx_render_view (ifx_map.hip): the viewer's own key image ([view_keys_px], all-empty between calls), its big-quad list ([0] length, [1 + cap] slots) and the
+    // staging of host outputs ([view_out_px] float4 | [view_out_px] int32); allocated by the first call, the two images regrown for a larger viewport
+    unsigned long long* view_keys = nullptr; size_t view_keys_px = 0;
+    unsigned int* view_big = nullptr;
+    void* view_out = nullptr; size_t view_out_px = 0;
     float *d_sample = nullptr, *d_cons = nullptr;   // scratch of ifx_sample_graph_model / ifx_loop_closure_constraints
     ifx_loop_closure_cb lc_cb = nullptr;
     void* lc_user = nullptr;
@@ -662,6 +667,7 @@ int ifx_ids_ensure(ifx* h);                                   // the whole id im
 int ifx_owner_ids_begin_impl(ifx* h);                         // sharded map: 1 = the shard's id render is enqueued and waits for its key exchange, 0 = the image is whole already
 int ifx_owner_ids_resume_impl(ifx* h);
 int ifx_own_lattice(const ifx* h);                            // entries of the id lattice (one per 10 x 10 pixels)
+void ifx_view_free(ifx* h);                                   // ifx_render_view's buffers
 int ifx_vlist_reap(ifx* h);                                   // forced view-list scan: applies the age rule to the slots outside the list (before any whole-map consumer)
 int ifx_map_sharded_phase(ifx* h, int phase, bool first_frame);
 int ifx_map_predict_loop_closure(ifx* h);                     // predict() at the tracked pose + INACTIVE prediction (old* images)

@@ -665,6 +665,190 @@ __global__ __launch_bounds__(MAP_THREADS) void k_raster_quad(const DevState* __r
     }
 }
 
+// ------------------------------------------------------------------ free-viewpoint render: the viewer's surfel pass (ifx_render_view)
+// draw_global_surface.vert / .geom / .frag and draw_global_ID.* (GlobalModel::renderPointCloud / renderGlobalID, EF/GlobalModel.cpp:328-457) as GL rasterises
+// them: the quads of the id rule above under an arbitrary 4x4 MVP with w != 1 -- texcoord perspective-correct through the corners' 1 / w, depth affine in window
+// space, GL's depth clip for near and far, the fragment shader's depth push of an unstable surfel, a 24-bit depth buffer cleared to 1 with GL_LESS -- on a viewport
+// of its own.  A quad with a corner at w <= 0 or outside the guard band is NOT drawn (GL clips it and draws the visible part: the stated deviation, DESIGN.md
+// section 1).  Every f32 operation is the one tests/viewer_numpy.py performs (-ffp-contract=off): the GPU tests ask for equal images.
+#define VIEW_SMALL 256   // a quad whose pixel box holds at most this many pixels is drawn by the thread that set it up; a larger one by a workgroup (k_view_big)
+struct ViewCam { float m[16]; int w, h; float thr; int unstable; };
+struct ViewCol { int color_type, draw_window, time, time_delta; float clear[3]; };
+struct ViewQuad { long long x[4], y[4]; float z[4], iw[4]; float push; int x0, x1, y0, y1; };
+
+// clip = MVP . (corner, 1) summed left to right, window coordinates, the 1/256 px snap; false: w not > 0 and finite, or outside the guard band
+__device__ __forceinline__ bool view_corner(const ViewCam& c, float qx, float qy, float qz, long long& X, long long& Y, float& zw, float& iw)
+{
+    const float cx = ((c.m[0] * qx + c.m[1] * qy) + c.m[2] * qz) + c.m[3], cy = ((c.m[4] * qx + c.m[5] * qy) + c.m[6] * qz) + c.m[7];
+    const float cz = ((c.m[8] * qx + c.m[9] * qy) + c.m[10] * qz) + c.m[11], cw = ((c.m[12] * qx + c.m[13] * qy) + c.m[14] * qz) + c.m[15];
+    if (!(cw > 0.0f && cw < INFINITY)) return false;
+    const float xw = ((cx / cw) * 0.5f + 0.5f) * (float)c.w, yw = ((cy / cw) * 0.5f + 0.5f) * (float)c.h;
+    zw = (cz / cw) * 0.5f + 0.5f;
+    if (!(fabsf(xw) <= QUAD_GUARD) || !(fabsf(yw) <= QUAD_GUARD) || !(fabsf(zw) < INFINITY)) return false;
+    X = (long long)rintf(xw * (float)QUAD_SUB);
+    Y = (long long)rintf(yw * (float)QUAD_SUB);
+    iw = 1.0f / cw;
+    return true;
+}
+
+// the per-surfel part: the culls of draw_global_surface.vert:44-66 (w = the instance-colour word; a negative confidence is a tombstone of the store), the corners
+// of .geom:94-118 and the pixel box of the snapped quad clipped to the viewport; false = nothing to draw
+__device__ __forceinline__ bool view_setup(const ViewCam& c, float4 p4, float4 n4, float inst_word, ViewQuad& Q)
+{
+    if (inst_word == -1.0f || !(p4.w >= 0.0f) || !(p4.w > c.thr || c.unstable)) return false;
+    Q.push = p4.w <= c.thr ? n4.w : 0.0f;   // draw_global_surface.frag:35-42
+    float ax = n4.y - n4.z, ay = -n4.x, az = n4.x;
+    const float rn = 1.0f / sqrtf((ax * ax + ay * ay) + az * az);
+    ax = ((ax * rn) * n4.w) * 1.41421356f; ay = ((ay * rn) * n4.w) * 1.41421356f; az = ((az * rn) * n4.w) * 1.41421356f;
+    const float bx = n4.y * az - n4.z * ay, by = n4.z * ax - n4.x * az, bz = n4.x * ay - n4.y * ax;
+    bool ok = view_corner(c, p4.x + ax, p4.y + ay, p4.z + az, Q.x[0], Q.y[0], Q.z[0], Q.iw[0]);
+    ok = view_corner(c, p4.x + bx, p4.y + by, p4.z + bz, Q.x[1], Q.y[1], Q.z[1], Q.iw[1]) && ok;
+    ok = view_corner(c, p4.x - bx, p4.y - by, p4.z - bz, Q.x[2], Q.y[2], Q.z[2], Q.iw[2]) && ok;
+    ok = view_corner(c, p4.x - ax, p4.y - ay, p4.z - az, Q.x[3], Q.y[3], Q.z[3], Q.iw[3]) && ok;
+    if (!ok) return false;
+    long long mnx = Q.x[0], mxx = Q.x[0], mny = Q.y[0], mxy = Q.y[0];
+#pragma unroll
+    for (int k = 1; k < 4; k++) { mnx = min(mnx, Q.x[k]); mxx = max(mxx, Q.x[k]); mny = min(mny, Q.y[k]); mxy = max(mxy, Q.y[k]); }
+    Q.x0 = (int)max(-((-(mnx - QUAD_SUB / 2)) >> 8), 0LL); Q.x1 = (int)min((mxx - QUAD_SUB / 2) >> 8, (long long)(c.w - 1));
+    Q.y0 = (int)max(-((-(mny - QUAD_SUB / 2)) >> 8), 0LL); Q.y1 = (int)min((mxy - QUAD_SUB / 2) >> 8, (long long)(c.h - 1));
+    return Q.x0 <= Q.x1 && Q.y0 <= Q.y1;
+}
+
+// one triangle of the strip at the pixel centre (sx, sy): depth24 << 32, or IFX_KEY_EMPTY
+__device__ __forceinline__ unsigned long long view_tri(const ViewQuad& Q, int ia, int ib, int ic, float ua, float va, float ub, float vb, float uc, float vc, long long sx, long long sy)
+{
+    const long long ax = Q.x[ia], ay = Q.y[ia];
+    long long bx = Q.x[ib], by = Q.y[ib], cx = Q.x[ic], cy = Q.y[ic];
+    float zb = Q.z[ib], zc = Q.z[ic], qb = Q.iw[ib], qc = Q.iw[ic];
+    long long A = quad_edge(ax, ay, bx, by, cx, cy);
+    if (A == 0) return IFX_KEY_EMPTY;
+    if (A < 0) {   // clockwise: b <-> c
+        long long t = bx; bx = cx; cx = t; t = by; by = cy; cy = t;
+        float f = zb; zb = zc; zc = f; f = qb; qb = qc; qc = f; f = ub; ub = uc; uc = f; f = vb; vb = vc; vc = f;
+        A = -A;
+    }
+    const long long w0 = quad_edge(bx, by, cx, cy, sx, sy), w1 = quad_edge(cx, cy, ax, ay, sx, sy), w2 = quad_edge(ax, ay, bx, by, sx, sy);
+    if (!quad_in(w0, bx, by, cx, cy) || !quad_in(w1, cx, cy, ax, ay) || !quad_in(w2, ax, ay, bx, by)) return IFX_KEY_EMPTY;
+    const float fA = (float)A, la = (float)w0 / fA, lb = (float)w1 / fA, lc = (float)w2 / fA;
+    const float pa = la * Q.iw[ia], pb = lb * qb, pc = lc * qc, den = (pa + pb) + pc;
+    const float u = ((pa * ua + pb * ub) + pc * uc) / den, v = ((pa * va + pb * vb) + pc * vc) / den;
+    const float z = (la * Q.z[ia] + lb * zb) + lc * zc;
+    if (u * u + v * v > 1.0f || !(z >= 0.0f && z <= 1.0f)) return IFX_KEY_EMPTY;
+    const float d24 = rintf(fminf(fmaxf(z + Q.push, 0.0f), 1.0f) * 16777215.0f);
+    if (!(d24 < 16777215.0f)) return IFX_KEY_EMPTY;   // GL_LESS against the cleared buffer
+    return (unsigned long long)(unsigned int)d24 << 32;
+}
+__device__ __forceinline__ unsigned long long view_key(const ViewQuad& Q, int px, int py)
+{
+    const long long sx = (long long)px * QUAD_SUB + QUAD_SUB / 2, sy = (long long)py * QUAD_SUB + QUAD_SUB / 2;
+    const unsigned long long k1 = view_tri(Q, 0, 1, 2, -1.f, -1.f, 1.f, -1.f, -1.f, 1.f, sx, sy), k2 = view_tri(Q, 2, 1, 3, -1.f, 1.f, 1.f, -1.f, 1.f, 1.f, sx, sy);
+    return k1 < k2 ? k1 : k2;
+}
+
+// All slots, one thread per slot: culls and set-up; a quad of at most VIEW_SMALL pixels is drawn here, a larger one goes to big[1 + ...] (big[0] = the list's
+// length; capacity = the slot count, a slot is listed at most once), appended with one atomic per wave.  The trip count of the loop is the same for a whole block.
+__global__ __launch_bounds__(MAP_THREADS) void k_view_quad(const DevState* __restrict__ st, const float4* __restrict__ pc, const float4* __restrict__ nr, const float2* __restrict__ col,
+                                                           ViewCam c, unsigned long long* __restrict__ keys, unsigned int* __restrict__ big)
+{
+    const int n = st->count;
+    const unsigned int lane = threadIdx.x & 63u;
+    for (int b = blockIdx.x * blockDim.x; b < n; b += blockDim.x * gridDim.x) {
+        const int i = b + (int)threadIdx.x;
+        bool is_big = false;
+        if (i < n) {
+            ViewQuad Q;
+            if (view_setup(c, pc[i], nr[i], col[i].y, Q)) {
+                const int bw = Q.x1 - Q.x0 + 1;
+                if (bw * (Q.y1 - Q.y0 + 1) > VIEW_SMALL) is_big = true;
+                else
+                    for (int py = Q.y0; py <= Q.y1; py++)
+                        for (int px = Q.x0; px <= Q.x1; px++) {
+                            const unsigned long long k = view_key(Q, px, py);
+                            if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | (unsigned long long)(unsigned int)i);
+                        }
+            }
+        }
+        const unsigned long long m = __ballot(is_big);
+        if (m) {
+            const int leader = __ffsll((long long)m) - 1;
+            unsigned int at = 0;
+            if ((int)lane == leader) at = atomicAdd(&big[0], (unsigned int)__popcll(m));
+            at = __shfl(at, leader);
+            if (is_big) big[1u + at + (unsigned int)__popcll(m & ((1ull << lane) - 1ull))] = (unsigned int)i;
+        }
+    }
+}
+
+// The listed quads, one workgroup each (a fixed grid strides over the list, whose length is read from device memory): one thread redoes the set-up, the
+// workgroup's threads stride over the pixel box.
+__global__ __launch_bounds__(256) void k_view_big(const float4* __restrict__ pc, const float4* __restrict__ nr, const float2* __restrict__ col, ViewCam c,
+                                                  unsigned long long* __restrict__ keys, const unsigned int* __restrict__ big)
+{
+    __shared__ ViewQuad Qs;
+    __shared__ int drawn;
+    const unsigned int n_big = big[0];
+    for (unsigned int q = blockIdx.x; q < n_big; q += gridDim.x) {
+        const unsigned int i = big[1u + q];
+        if (threadIdx.x == 0) {
+            ViewQuad Q;
+            drawn = view_setup(c, pc[i], nr[i], col[i].y, Q) ? 1 : 0;
+            Qs = Q;
+        }
+        __syncthreads();
+        if (drawn) {
+            const ViewQuad Q = Qs;
+            const int bw = Q.x1 - Q.x0 + 1, np = bw * (Q.y1 - Q.y0 + 1);
+            for (int t = threadIdx.x; t < np; t += blockDim.x) {
+                const int px = Q.x0 + t % bw, py = Q.y0 + t / bw;
+                const unsigned long long k = view_key(Q, px, py);
+                if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | (unsigned long long)i);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// decodeColor of color.glsl
+__device__ __forceinline__ void view_decode(float w, float& r, float& g, float& b)
+{
+    const int v = (int)w;
+    r = (float)((v >> 16) & 0xFF) / 255.0f; g = (float)((v >> 8) & 0xFF) / 255.0f; b = (float)(v & 0xFF) / 255.0f;
+}
+// One thread per output pixel: the key of GL window row h - 1 - r (a screenshot's order, top row first), re-armed; the winner's slot (-1: nothing drawn) and its
+// base colour -- draw_global_surface.geom:50-88, per surfel, not interpolated -- with alpha 1; the clear colour with alpha 0 elsewhere.
+__global__ void k_view_resolve(unsigned long long* __restrict__ keys, const float4* __restrict__ nr, const float2* __restrict__ col, const float2* __restrict__ tm, int w, int h,
+                               ViewCol v, int32_t* __restrict__ ids, float4* __restrict__ rgba)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= w * h) return;
+    const int r = k / w, x = k - r * w, src = (h - 1 - r) * w + x;
+    const unsigned long long key = keys[src];
+    keys[src] = IFX_KEY_EMPTY;
+    if (key == IFX_KEY_EMPTY) {
+        if (ids) ids[k] = -1;
+        if (rgba) rgba[k] = make_float4(v.clear[0], v.clear[1], v.clear[2], 0.0f);
+        return;
+    }
+    const unsigned int i = (unsigned int)(key & 0xFFFFFFFFull);
+    if (ids) ids[k] = (int32_t)i;
+    if (!rgba) return;
+    const float4 n4 = nr[i];
+    const float2 c2 = col[i], t2 = tm[i];
+    const float d = fabsf((n4.x + n4.y) + n4.z), grey = 0.5f * d + 0.1f;
+    float cr = grey, cg = grey, cb = grey;
+    if (v.color_type == 1) { cr = n4.x; cg = n4.y; cb = n4.z; }
+    else if (v.color_type == 2) view_decode(c2.x, cr, cg, cb);
+    else if (v.color_type == 3) {
+        const float ratio = (2.0f * (t2.x - 1.0f)) / ((float)v.time - 1.0f);
+        const float a = 1.0f - ratio, b = ratio - 1.0f, s = d + 0.1f;
+        cr = a > 0.0f ? a : 0.0f; cg = b > 0.0f ? b : 0.0f; cb = (1.0f - cr) - cg;
+        cr = cr * s; cg = cg * s; cb = cb * s;
+    }
+    else if (v.color_type == 4) view_decode(c2.y, cr, cg, cb);
+    if (v.draw_window && (float)v.time - t2.y > (float)v.time_delta) { cr = cr * 0.25f; cg = cg * 0.25f; cb = cb * 0.25f; }
+    rgba[k] = make_float4(cr * 0.6f + grey * 0.4f, cg * 0.6f + grey * 0.4f, cb * 0.6f + grey * 0.4f, 1.0f);
+}
+
 __device__ inline float key_depth(unsigned long long key)
 {
     unsigned int b = (unsigned int)(key >> 32);
@@ -3758,4 +3942,77 @@ extern "C" int ifx_adopt_estimated_pose(ifx_t* h)
     h->view_block = 1;
     LAUNCH(h, "adopt_est_pose", dim3(1), dim3(64), k_adopt_est_pose, h->d_state);
     return IFX_OK;
+}
+
+// ------------------------------------------------------------------ ifx_render_view: the map from any camera (kernels: "free-viewpoint render" above)
+// Read-only on the map, enqueued on the main stream behind the last frame: k_view_quad ; k_view_big ; k_view_resolve with no host round trip in between.  The key
+// image ([w * h], all-empty between calls: the resolve re-arms what it reads) and the big-quad list ([1 + capacity]) are the viewer's own, allocated by the first
+// call, the key image regrown for a larger viewport; key_ids and the frame's work lists belong to the frame.
+void ifx_view_free(ifx* h)
+{
+    void* ptrs[] = {h->view_keys, h->view_big, h->view_out};
+    for (void* p : ptrs) if (p) hipFree(p);
+    h->view_keys = nullptr; h->view_big = nullptr; h->view_out = nullptr; h->view_keys_px = 0; h->view_out_px = 0;
+}
+extern "C" int ifx_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids)
+{
+    if (!h || !p) return IFX_E_INVALID;
+    if (p->w < 1 || p->w > 4096 || p->h < 1 || p->h > 4096) { h->err = "ifx_render_view: the viewport is 1..4096 pixels on each axis"; return IFX_E_INVALID; }
+    if (p->color_type < 0 || p->color_type > 4) { h->err = "ifx_render_view: color_type is 0..4"; return IFX_E_INVALID; }
+    for (int k = 0; k < 16; k++)
+        if (!(fabsf(p->mvp[k]) < INFINITY)) { h->err = "ifx_render_view: mvp is not finite"; return IFX_E_INVALID; }
+    if (h->own || h->shard_n > 1) { h->err = "ifx_render_view: not on a sharded handle"; return IFX_E_STATE; }
+    if (h->clean_raster_pending) { h->err = "ifx_render_view: a frame's map passes are in flight"; return IFX_E_STATE; }
+    if (!out_rgba && !out_ids && !d_out_rgba && !d_out_ids) return IFX_OK;
+    ifx_vlist_reap(h);   // whole-map consumer: nothing outside the cached view list may outlive the age rule ("View list")
+    const size_t px = (size_t)p->w * p->h;
+    if (px > h->view_keys_px) {
+        if (h->view_keys) { HIPCHK(h, hipStreamSynchronize(h->cur)); hipFree(h->view_keys); h->view_keys = nullptr; h->view_keys_px = 0; }
+        HIPCHK(h, hipMalloc(&h->view_keys, px * 8));
+        h->view_keys_px = px;
+        HIPCHK(h, hipMemsetAsync(h->view_keys, 0xFF, px * 8, h->cur));
+    }
+    if (!h->view_big) HIPCHK(h, hipMalloc(&h->view_big, ((size_t)h->cap + 1) * 4));
+    float* rgba = d_out_rgba;
+    int32_t* ids = d_out_ids;
+    if ((out_rgba && !d_out_rgba) || (out_ids && !d_out_ids)) {   // host outputs alone: staged in the viewer's own buffer ([px] float4 | [px] int32)
+        if (px > h->view_out_px) {
+            if (h->view_out) { HIPCHK(h, hipStreamSynchronize(h->cur)); hipFree(h->view_out); h->view_out = nullptr; h->view_out_px = 0; }
+            HIPCHK(h, hipMalloc(&h->view_out, px * 20));
+            h->view_out_px = px;
+        }
+        if (out_rgba && !rgba) rgba = (float*)h->view_out;
+        if (out_ids && !ids) ids = (int32_t*)((char*)h->view_out + h->view_out_px * 16);
+    }
+    ViewCam c;
+    memcpy(c.m, p->mvp, sizeof(c.m));
+    c.w = p->w; c.h = p->h;
+    c.thr = p->threshold == p->threshold ? p->threshold : h->cfg.confidence;
+    c.unstable = p->unstable ? 1 : 0;
+    ViewCol v;
+    v.color_type = p->color_type; v.draw_window = p->draw_window ? 1 : 0;
+    v.time = p->time < 0 ? h->tick : p->time;
+    v.time_delta = p->time_delta < 0 ? h->cfg.time_delta : p->time_delta;
+    memcpy(v.clear, p->clear_rgb, sizeof(v.clear));
+    HIPCHK(h, hipMemsetAsync(h->view_big, 0, 4, h->cur));
+    LAUNCH(h, "view_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_view_quad, (const DevState*)h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, h->view_big);
+    LAUNCH(h, "view_big", dim3(LIST_BLOCKS), dim3(256), k_view_big, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, (const unsigned int*)h->view_big);
+    LAUNCH(h, "view_resolve", dim3((unsigned int)((px + 255) / 256)), dim3(256), k_view_resolve, h->view_keys, (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, p->w, p->h, v, ids,
+           (float4*)rgba);
+    if (out_rgba || out_ids) {
+        if (out_rgba) HIPCHK(h, hipMemcpyAsync(out_rgba, rgba, px * 16, hipMemcpyDeviceToHost, h->cur));
+        if (out_ids) HIPCHK(h, hipMemcpyAsync(out_ids, ids, px * 4, hipMemcpyDeviceToHost, h->cur));
+        HIPCHK(h, hipStreamSynchronize(h->cur));
+    }
+    return IFX_OK;
+}
+// the length of the big-quad list of the last ifx_render_view (quads drawn by k_view_big); synchronises the main stream
+extern "C" int ifx_render_view_big_quads(ifx_t* h)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!h->view_big) return 0;
+    unsigned int n = 0;
+    HIPCHK(h, hipMemcpyAsync(&n, h->view_big, 4, hipMemcpyDeviceToHost, h->cur));
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    return (int)n;
 }

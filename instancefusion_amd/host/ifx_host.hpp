@@ -61,6 +61,32 @@ struct Matrix4f {   // row-major camera-to-world pose; stands in for Eigen::Matr
     float* data() { return m; }
 };
 
+// The reference viewer's camera as the MVP of ifx_render_view: Pangolin's ProjectionMatrix(w, h, fu, fv, u0, v0, zNear, zFar) times the inverse of the (rigid)
+// camera pose; camera frame y down, z forward.  Computed in double and rounded to float once (the Python package's viewer_mvp is the same arithmetic).
+inline Matrix4f viewerMvp(double fx, double fy, double cx, double cy, double w, double h, double zNear, double zFar, const Matrix4f& pose)
+{
+    double Ti[16] = {0};
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Ti[i * 4 + j] = (double)pose(j, i);
+        double t = 0.0;
+        for (int j = 0; j < 3; j++) t += (double)pose(j, i) * (double)pose(j, 3);
+        Ti[i * 4 + 3] = -t;
+    }
+    Ti[15] = 1.0;
+    const double P[16] = {2.0 * fx / w, 0.0, 1.0 - 2.0 * cx / w, 0.0,
+                          0.0, -(2.0 * fy / h), -(1.0 - 2.0 * cy / h), 0.0,
+                          0.0, 0.0, (zFar + zNear) / (zFar - zNear), -(2.0 * zFar * zNear) / (zFar - zNear),
+                          0.0, 0.0, 1.0, 0.0};
+    Matrix4f r;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double s = 0.0;
+            for (int k = 0; k < 4; k++) s += P[i * 4 + k] * Ti[k * 4 + j];
+            r(i, j) = (float)s;
+        }
+    return r;
+}
+
 #include "ifx_deformation.hpp"
 #include "ifx_ferns.hpp"
 typedef FernsT<Matrix4f> Ferns;   // EF/Ferns.h
@@ -856,6 +882,23 @@ public:
         if (elastic_fusion_) ifx_map_view(handle(), &v);
         return v;
     }
+    // The headless forms of RenderMapToBoundGlBuffer (IF/map_interface/ElasticFusionInterface.cpp: GlobalModel::renderPointCloud with the handle's threshold,
+    // tick and time window, stable surfels only, no window dimming) and of RenderMapIDToGUIBuffer (renderGlobalID): the map from the camera `mvp` (viewerMvp)
+    // into host buffers, top row first -- rgba: h x w x 4 floats (the GUI's white where nothing is drawn, alpha 0 there), ids: h x w slots, -1 where nothing is
+    // drawn.  Either buffer may be null.
+    void RenderMapToBuffer(const Matrix4f& mvp, int w, int h, bool drawInstances, bool drawTimes, bool drawColors, float* rgba, int32_t* ids, bool drawNormals = false)
+    {
+        ifx_view_params p;
+        std::memset(&p, 0, sizeof(p));
+        std::memcpy(p.mvp, mvp.data(), sizeof(p.mvp));
+        p.w = w; p.h = h;
+        p.threshold = std::nanf("");
+        p.color_type = drawInstances ? 4 : drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0;   // EF/GlobalModel.cpp:348
+        p.time = -1; p.time_delta = -1;
+        p.clear_rgb[0] = p.clear_rgb[1] = p.clear_rgb[2] = 1.0f;   // Gui::preCall
+        if (ifx_render_view(handle(), &p, rgba, ids, nullptr, nullptr) != IFX_OK) throw std::runtime_error(std::string("ifx_render_view: ") + ifx_last_error(handle()));
+    }
+    void RenderMapIDToBuffer(const Matrix4f& mvp, int w, int h, int32_t* ids) { RenderMapToBuffer(mvp, w, h, false, false, false, nullptr, ids); }
     int getMapSurfelCount() { return elastic_fusion_ ? elastic_fusion_->getMapSurfelCount() : 0; }
     Matrix4f getCurrPose() { return elastic_fusion_->getCurrPose(); }
     void setTrackingOnly(const bool) {}   // GUI switch of the reference (IF/main.cpp:131); no counterpart

@@ -6,6 +6,7 @@
 //
 //   ifx_replay LOG.klg|data.txt [--width 640 --height 480 --fx 528 --fy 528 --cx 320 --cy 240] [--masks DIR] [--out PREFIX]
 //              [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--device K] [--gt-dir DIR --eval FILE] [--mask-lag K] [--merge-duplicates]
+//              [--view-ppm PATH [--view-pose "16 floats"] [--view-size WxH] [--view-instances]]
 #include <chrono>
 #include <cstdlib>
 #include <iostream>
@@ -25,6 +26,13 @@ struct Args {
     int decode_threads = 4;
     int mask_lag = -1;   // --mask-lag K: the masks recorded for frame t arrive K frames later (a detector slower than the frame loop) and are applied through a snapshot of frame t
     float confidence = 10.f;
+    // --view-ppm PATH: the final map drawn from a free camera (ifx_render_view) as a binary PPM.  Default camera: the GUI's initial one (IF/gui/Gui.cpp:105-106),
+    // 640x480, focal 420, at (0, 0, -1) looking down +z; --view-pose: another camera-to-world pose (row-major); --view-size: another viewport (the focal length scales
+    // with its width); --view-instances: instance colours (the GUI's drawInstances) instead of the surfels' colours
+    std::string view_ppm;
+    float view_pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, -1, 0, 0, 0, 1};
+    int view_w = 640, view_h = 480;
+    bool view_instances = false;
     Sharding shard;   // --shard-ranks G --shard-rank r --shard-id FILE: this process is rank r of G over one spatially sharded map (one process per GPU)
 };
 
@@ -33,6 +41,7 @@ int usage(const char* argv0)
     std::fprintf(stderr,
                  "usage: %s LOG.klg|data.txt [--width W --height H --fx F --fy F --cx C --cy C] [--masks DIR] [--out PREFIX]\n"
                  "       [--max-frames N] [--max-surfels N] [--no-superpixels] [--labels FILE] [--flip-colors] [--flann-every N] [--device K] [--no-close-loops] [--detect-only] [--decode-threads N] [--no-lookahead] [--confidence C] [--reference-ids] [--mask-lag K] [--mask-iou] [--merge-duplicates] [--reloc] [--frame-to-frame-rgb]\n"
+                 "       [--view-ppm PATH [--view-pose \"16 floats, camera-to-world, row-major\"] [--view-size WxH] [--view-instances]] (the final map from a free camera, binary PPM)\n"
                  "       [--gt-dir DIR (DIR/<frame, 6 digits>.png, 8-bit instance ground truth)] [--eval FILE (precision / recall rows, needs --gt-dir)]\n"
                  "       [--shard-ranks G --shard-rank r --shard-id FILE [--shard-nonce N] (one process per GPU over one spatially sharded map; every rank replays the same log; -1: a world of one)]\n",
                  argv0);
@@ -76,6 +85,17 @@ int main(int argc, char** argv)
         else if (s == "--reloc") a.reloc = true;   // ElasticFusion's relocalisation mode: frames that fail the tracking gate are not fused; a lost frame ends the replay (IF/main.cpp:137-142)
         else if (s == "--frame-to-frame-rgb") a.f2f_rgb = true;   // the photometric term tracks against the previous raw frame (frameToFrameRGB)
         else if (s == "--mask-lag") a.mask_lag = std::atoi(val("--mask-lag"));   // snapshot at the frame the masks belong to, deferred call K frames later (one detection in flight, as with one detector)
+        else if (s == "--view-ppm") a.view_ppm = val("--view-ppm");
+        else if (s == "--view-pose") {
+            const char* v = val("--view-pose");
+            if (std::sscanf(v, "%f %f %f %f %f %f %f %f %f %f %f %f %f %f %f %f", a.view_pose, a.view_pose + 1, a.view_pose + 2, a.view_pose + 3, a.view_pose + 4, a.view_pose + 5, a.view_pose + 6,
+                            a.view_pose + 7, a.view_pose + 8, a.view_pose + 9, a.view_pose + 10, a.view_pose + 11, a.view_pose + 12, a.view_pose + 13, a.view_pose + 14, a.view_pose + 15) != 16) {
+                std::fprintf(stderr, "--view-pose needs 16 floats\n");
+                return 2;
+            }
+        }
+        else if (s == "--view-size") { if (std::sscanf(val("--view-size"), "%dx%d", &a.view_w, &a.view_h) != 2) { std::fprintf(stderr, "--view-size needs WxH\n"); return 2; } }
+        else if (s == "--view-instances") a.view_instances = true;
         else if (s == "--no-lookahead") a.lookahead = false;   // frames are handed over one at a time, as the reference's loop does
         else if (s == "--shard-ranks") a.shard.ranks = std::atoi(val("--shard-ranks"));   // -1: a world of one on the sharded path
         else if (s == "--shard-rank") a.shard.rank = std::atoi(val("--shard-rank"));
@@ -87,6 +107,7 @@ int main(int argc, char** argv)
     }
     if (a.log.empty()) return usage(argv[0]);
     if (a.merge_duplicates && a.shard.on()) { std::fprintf(stderr, "--merge-duplicates is not available on a sharded map\n"); return 2; }
+    if (!a.view_ppm.empty() && a.shard.on()) { std::fprintf(stderr, "--view-ppm is not available on a sharded map\n"); return 2; }
     if ((a.reloc || a.f2f_rgb) && a.shard.on()) { std::fprintf(stderr, "--reloc / --frame-to-frame-rgb are not available on a sharded map\n"); return 2; }
 
     try {
@@ -188,6 +209,24 @@ int main(int argc, char** argv)
         ifx_sync(map->handle());
         const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
+        if (!a.view_ppm.empty()) {   // the labelled map as the GUI's main window shows it: 8 bit, rint(c * 255) clamped
+            Matrix4f vp;
+            std::memcpy(vp.data(), a.view_pose, sizeof(a.view_pose));
+            const double focal = 420.0 * a.view_w / 640.0;
+            const Matrix4f mvp = viewerMvp(focal, focal, a.view_w / 2.0, a.view_h / 2.0, a.view_w, a.view_h, 0.1, 1000.0, vp);
+            std::vector<float> rgba((size_t)a.view_w * a.view_h * 4);
+            map->RenderMapToBuffer(mvp, a.view_w, a.view_h, a.view_instances, false, !a.view_instances, rgba.data(), nullptr);
+            std::vector<unsigned char> ppm((size_t)a.view_w * a.view_h * 3);
+            for (size_t k = 0; k < (size_t)a.view_w * a.view_h; k++)
+                for (int ch = 0; ch < 3; ch++) {
+                    const float v = std::rint(rgba[k * 4 + ch] * 255.0f);
+                    ppm[k * 3 + ch] = (unsigned char)(v >= 255.0f ? 255.0f : v >= 0.0f ? v : 0.0f);   // (a NaN becomes 0)
+                }
+            std::ofstream f(a.view_ppm, std::ios::binary);
+            f << "P6\n" << a.view_w << " " << a.view_h << "\n255\n";
+            f.write((const char*)ppm.data(), (std::streamsize)ppm.size());
+            if (!f) throw std::runtime_error("cannot write " + a.view_ppm);
+        }
         const int n_geo = map->elasticFusion().savePly();
         const int n_ins = map->elasticFusion().savePlyInstance();
         if (!a.labels.empty()) {   // bestIDInEachSurfel of the live surfels, one int32 each (what evaluateAndSave consumes, IF/Core/InstanceFusion.h:79)

@@ -44,6 +44,10 @@ def main(argv=None):
     ap.add_argument("--confidence", type=float, default=10.0, help="surfel stability threshold (the reference's constructor argument)")
     ap.add_argument("--no-close-loops", action="store_true", help="switch the local loop-closure detection off (the reference runs with closeLoops = true)")
     ap.add_argument("--labels", default=None, help="write bestIDInEachSurfel of the live surfels (int32, map order) to this file")
+    ap.add_argument("--view-ppm", default=None, help="write the final map drawn from a free camera (ElasticFusion.render_view) as a binary PPM")
+    ap.add_argument("--view-pose", default="1 0 0 0 0 1 0 0 0 0 1 -1 0 0 0 1", help="camera-to-world pose of that camera, 16 floats row-major (default: the GUI's initial camera)")
+    ap.add_argument("--view-size", default="640x480", help="its viewport, WxH (the focal length, 420 at 640, scales with the width)")
+    ap.add_argument("--view-instances", action="store_true", help="instance colours instead of the surfels' colours")
     args = ap.parse_args(argv)
 
     import torch  # noqa: F401  (binds the HIP runtime first)
@@ -78,6 +82,17 @@ def main(argv=None):
         frame += 1
     ef.sync()
     dt = time.perf_counter() - t0
+    if args.view_ppm:
+        vw, vh = (int(v) for v in args.view_size.split("x"))
+        vpose = np.array([float(v) for v in args.view_pose.split()], np.float32).reshape(4, 4)
+        focal = 420.0 * vw / 640.0
+        rgba, _ = ef.render_view(ifx.viewer_mvp(focal, focal, vw / 2.0, vh / 2.0, vw, vh, 0.1, 1000.0, vpose), (vw, vh), draw_instances=args.view_instances,
+                                 draw_colors=not args.view_instances)
+        with np.errstate(invalid="ignore"):
+            q = np.rint(rgba[..., :3] * np.float32(255.0))
+        q = np.where(q >= 255.0, 255.0, np.where(q >= 0.0, q, 0.0)).astype(np.uint8)
+        with open(args.view_ppm, "wb") as f:
+            f.write(f"P6\n{vw} {vh}\n255\n".encode() + q.tobytes())
     logio.save_freiburg(args.out + ".freiburg", stamps, poses)
     m = ef.download()
     n_geo = logio.save_ply(args.out + ".ply", m, confidence=args.confidence)
