@@ -13,6 +13,7 @@
 //    whole map through a second buffer every frame.
 #include <climits>
 #include "ifx_ctx.h"
+#include "ifx_walk_owner.h"
 #include <string.h>
 
 #define DEAD_TIME (-1.0e9f)
@@ -2041,7 +2042,10 @@ __global__ __launch_bounds__(MAP_THREADS) void k_clean_view(DevState* st, Cam c,
 // earlyz: a plain (agent-scope) read of the key before the atomic; a key that is not below what the image already held
 // at ANY earlier time cannot win (keys only decrease during the pass), so the atomic is dropped -- with ~17 discs over
 // every pixel of the benchmark map most of them lose.
-struct alignas(16) RvRec { float qx, qy, qz, nx, ny, nz, r2; unsigned int id; int x0, y0, bw, excl; int s01, s23, i01, i23; };
+// A prepared surfel as its lane holds it, and a wave's 64 of them in LDS: field group by field group (a: qx..nx, b: ny..id, r: s01..i23, x: xy, bw -- 56 B a record) in
+// front of the 64 words of the owner lookup's table: 60 B a lane, where the records alone took 64 B with the box's first candidate in them (the mark brings it now).
+struct RvRec { float qx, qy, qz, nx, ny, nz, r2; unsigned int id; int s01, s23, i01, i23; int xy, bw; };   // xy: x0 | y0 << 16 (the box is clipped to the image: both in [0, 65535])
+struct alignas(16) RvWave { float4 a[64], b[64]; int4 r[64]; int2 x[64]; int tab[64]; };
 // LDSMIN: the depth test of a wave's 64 surfels is first played out in LDS.  The entries of a wave are neighbours in creation order, i.e. (mostly)
 // neighbouring pixels of the frame that created them, so their discs overlap each other: ~3 candidates per touched pixel inside one wave.  A
 // wave-private direct-mapped table (16 x 16 pixel window x 2 targets, tag = pixel and target image) takes the minimum per pixel with LDS atomics;
@@ -2065,6 +2069,18 @@ __device__ __forceinline__ void new_flags_body(DevState* st, const float* __rest
 #ifndef WALK_MIN_WAVES
 #define WALK_MIN_WAVES 1
 #endif
+// Inclusive maximum over lanes 0..l of a wave, the scan of ifx_walk_owner.h: step k joins the value of lane wo_scan_src(k, l), the identity 0 where there is none
+// (bound_ctrl and the row masks deliver 0 there).
+__device__ __forceinline__ int wave_scan_owner(int v)
+{
+    v = wo_join(v, __builtin_amdgcn_update_dpp(IFX_WO_IDENTITY, v, 0x111, 0xF, 0xF, true));   // row_shr:1
+    v = wo_join(v, __builtin_amdgcn_update_dpp(IFX_WO_IDENTITY, v, 0x112, 0xF, 0xF, true));   // row_shr:2
+    v = wo_join(v, __builtin_amdgcn_update_dpp(IFX_WO_IDENTITY, v, 0x114, 0xF, 0xF, true));   // row_shr:4
+    v = wo_join(v, __builtin_amdgcn_update_dpp(IFX_WO_IDENTITY, v, 0x118, 0xF, 0xF, true));   // row_shr:8: every lane holds the maximum of its row up to itself
+    v = wo_join(v, __builtin_amdgcn_update_dpp(IFX_WO_IDENTITY, v, 0x142, 0xA, 0xF, true));   // row_bcast15 into rows 1 and 3
+    v = wo_join(v, __builtin_amdgcn_update_dpp(IFX_WO_IDENTITY, v, 0x143, 0xC, 0xF, true));   // row_bcast31 into rows 2 and 3
+    return v;
+}
 template <bool LDSMIN, bool CLEAN>
 __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_raster_view(DevState* st, const float4* __restrict__ pc, const float4* __restrict__ nr, const float2* __restrict__ tm, Cam c,
                                                              int time, int maxTime, unsigned int want, const unsigned int* __restrict__ list_a, const unsigned int* __restrict__ list_i,
@@ -2077,7 +2093,7 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
     const int fl = FIRST_LIVE(c);
     if (CLEAN && (int)blockIdx.x < ca.nf_blocks) { new_flags_body(st, stc->pose_inv, c, time, ca.assoc, ca.mpc, ca.mnr, ca.tap, ca.flags, ca.block_counts, (int)blockIdx.x); return; }
     const unsigned int rblk = CLEAN ? blockIdx.x - (unsigned int)ca.nf_blocks : blockIdx.x, rgrid = CLEAN ? gridDim.x - (unsigned int)ca.nf_blocks : gridDim.x;
-    __shared__ RvRec recs[MAP_THREADS / 64][64];
+    __shared__ RvWave rv_all[MAP_THREADS / 64];
     __shared__ unsigned int s_tag[LDSMIN ? MAP_THREADS / 64 : 1][LDSMIN ? RV_SLOTS : 1];
     __shared__ unsigned long long s_key[LDSMIN ? MAP_THREADS / 64 : 1][LDSMIN ? RV_SLOTS : 1];
     float T[12];
@@ -2088,6 +2104,9 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
 #pragma unroll
         for (int q = 0; q < RV_SLOTS / 64; q++) { s_tag[wid][q * 64 + lane] = 0u; s_key[wid][q * 64 + lane] = ~0ull; }
     }
+    RvWave& rv = rv_all[__builtin_amdgcn_readfirstlane(wid)];   // (the wave's number in a scalar register: one LDS base for every field group, offsets in the instructions)
+    rv.tab[lane] = IFX_WO_IDENTITY;
+    const unsigned int lat_m = wo_lattice_magic(ids_step);   // x % ids_step == 0 as one multiply and one compare (ifx_walk_owner.h has the exactness argument)
     // the two view lists, one after the other: [0, na) the time-window list, [na, na + ni) the stable slots outside the window (id render only)
     // want & LIST_DUAL (the loop-closure detection's two splat renders, as k_cull_raster / k_raster_list's dual mode): the ACTIVE prediction goes to key_splat, the INACTIVE
     // one -- last seen at or before time - timeDelta -- to key_ids with the SPLAT geometry and depth rule; every entry of both lists is classified by its own time stamp
@@ -2217,7 +2236,7 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
                         const int nx_ = lattice ? (x1 - x0) / ids_step + 1 : x1 - x0 + 1, ny_ = lattice ? (y1 - y0) / ids_step + 1 : y1 - y0 + 1;
                         area = nx_ * ny_;
                         R.qx = G.q.x; R.qy = G.q.y; R.qz = G.q.z; R.nx = G.nn.x; R.ny = G.nn.y; R.nz = G.nn.z; R.r2 = G.r * G.r; R.id = CLEAN ? i : key_id(c, i, fl);   // (CLEAN: slot numbers -- first_live is not settled while this walk removes surfels; k_splat_resolve names "surfel 0")
-                        R.x0 = x0; R.y0 = y0; R.bw = nx_ | (lattice << 16);
+                        R.xy = (int)((unsigned int)x0 | ((unsigned int)y0 << 16)); R.bw = nx_ | (lattice << 16);
                         R.s01 = (sx0 & 0xFFFF) | (sx1 << 16); R.s23 = (sy0 & 0xFFFF) | (sy1 << 16);
                         R.i01 = (ix0 & 0xFFFF) | (ix1 << 16); R.i23 = (iy0 & 0xFFFF) | (iy1 << 16);
                     }
@@ -2227,29 +2246,50 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
         int incl = area;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-        const int excl = incl - area, total = __shfl(incl, 63, 64);
+        const int excl = incl - area, total = __builtin_amdgcn_readlane(incl, 63);   // (in a scalar register: the step loop's control is the wave's, not a lane's)
         if (total == 0) continue;
-        R.excl = excl;
-        if (area) recs[wid][lane] = R;
+        if (area) {
+            rv.a[lane] = make_float4(R.qx, R.qy, R.qz, R.nx); rv.b[lane] = make_float4(R.ny, R.nz, R.r2, __uint_as_float(R.id));
+            rv.r[lane] = make_int4(R.s01, R.s23, R.i01, R.i23); rv.x[lane] = make_int2(R.xy, R.bw);
+        }
         // (single wave: LDS writes are ordered before the reads below by the wave's own program order + s_waitcnt)
-        int jlo = 0;
+        // Which of the wave's 64 records a lane's candidate belongs to (ifx_walk_owner.h): the boxes that start inside the step leave their mark -- first candidate and
+        // lane number in one word -- at their first candidate's slot of the wave's table, a max-scan spreads it over the candidates behind it, the carry covers the box that
+        // reaches in from the step before.  A fixed sequence -- one LDS write, read and clear, six DPP steps, one readlane -- however many boxes a step spans;
+        // the table is this wave's alone, as the records are, and its accesses are ordered as theirs.
+        // The table's round trip of step s + 1 is on its way while step s tests its pixels: scatter, gather and clear are issued one step ahead, the scan takes the
+        // gathered word at the top of the next turn, where every lane is back (a `continue` below ends a lane's turn, not its part in the scan).
+        const int mark = wo_mark(excl, area, lane);
+        int carry = IFX_WO_IDENTITY;
+        auto gather = [&](int g0_) -> int {
+            // (lanes talk to each other through the table: wavefront-scope atomics and fences, so that the compiler neither forwards a lane's own store to its load nor
+            // reorders them -- plain ds_write / ds_read in the code, which the LDS runs in the wave's issue order)
+            const int sl = wo_slot(mark, g0_);
+            if (sl >= 0) __hip_atomic_store(&rv.tab[sl], mark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const int v = __hip_atomic_load(&rv.tab[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __hip_atomic_store(&rv.tab[lane], IFX_WO_IDENTITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            return v;
+        };
+        int slot_word = gather(0);
         for (int g0 = 0; g0 < total; g0 += 64) {
-            while (jlo < 63 && __builtin_amdgcn_readlane(incl, __builtin_amdgcn_readfirstlane(jlo)) <= g0) jlo++;
+            const int own = wo_owner(wave_scan_owner(slot_word), carry);
+            carry = __builtin_amdgcn_readlane(own, 63);
+            if (g0 + 64 < total) slot_word = gather(g0 + 64);
             const int g = g0 + lane;
-            int mine = jlo;
-            for (int j = jlo + 1; j < 64; j++) {
-                const int ej = __builtin_amdgcn_readlane(excl, __builtin_amdgcn_readfirstlane(j));
-                if (ej >= g0 + 64) break;
-                if (g >= ej) mine = j;
-            }
             if (g >= total) continue;
-            const RvRec* rp = &recs[wid][mine];
-            const float4 a = *reinterpret_cast<const float4*>(&rp->qx), b = *reinterpret_cast<const float4*>(&rp->ny);
-            const int4 bx = *reinterpret_cast<const int4*>(&rp->x0), rg = *reinterpret_cast<const int4*>(&rp->s01);
-            const int k = g - bx.w;
-            const int bwv = bx.z & 0xFFFF, stp = (bx.z >> 16) ? ids_step : 1;
-            const int row = (int)(((float)k + 0.5f) * __builtin_amdgcn_rcpf((float)bwv)), col = k - row * bwv;   // exact for boxes up to 512 x 512 (IFX_MAX_SPRITE)
-            const int px = bx.x + col * stp, py = bx.y + row * stp;
+            const int mine = wo_lane(own);
+            const float4 a = rv.a[mine], b = rv.b[mine];
+            const int4 rg = rv.r[mine];
+            const int2 bx = rv.x[mine];
+            const int k = g - wo_first(own);
+            const int lat = bx.y >> 16, bwv = bx.y & 0xFFFF, stp = lat ? ids_step : 1;
+            const int row = (int)(((float)k + 0.5f) * __builtin_amdgcn_rcpf((float)bwv)), col = k - __mul24(row, bwv);   // exact for boxes up to 512 x 512 (IFX_MAX_SPRITE)
+            const int px = (bx.x & 0xFFFF) + __mul24(col, stp), py = (int)((unsigned int)bx.x >> 16) + __mul24(row, stp);   // (24-bit multiplies, exact: row, col and bwv are below 2^16, stp below 2^14)
             Disc d;
             d.q = v3m(a.x, a.y, a.z); d.n = v3m(a.w, b.x, b.y); d.r2 = b.z;
             const unsigned int id = __float_as_uint(b.w);
@@ -2259,7 +2299,7 @@ __global__ __launch_bounds__(MAP_THREADS, CLEAN ? WALK_MIN_WAVES : 1) void k_ras
             const int ix0 = (short)(rg.z & 0xFFFF), ix1 = rg.z >> 16, iy0 = (short)(rg.w & 0xFFFF), iy1 = rg.w >> 16;
             const bool in_s = px >= sx0 && px <= sx1 && py >= sy0 && py <= sy1 && (z >= -c.maxDepth && z <= c.maxDepth);
             const bool in_i = px >= ix0 && px <= ix1 && py >= iy0 && py <= iy1 && (dual ? (z >= -c.maxDepth && z <= c.maxDepth) : (z > 0 && z <= c.maxDepth)) &&
-                              (ids_step <= 1 || (px % ids_step == 0 && py % ids_step == 0));
+                              (lat || (wo_on_lattice(px, lat_m) && wo_on_lattice(py, lat_m)));   // (a lattice record's candidates are lattice points by construction; px, py >= 0 here: in_i's range test comes first, and the id box is clipped to the image)
             if (!in_s && !in_i) continue;
             if (dual && in_s && in_i) {   // (last seen exactly timeDelta frames ago: in both renders; their resolves do not read key_both)
                 key_min(key_splat + (py * c.w + px), make_key(z, id));
