@@ -349,7 +349,9 @@ typedef struct ifx_soa_view {
  * ifx_map_view, so writes made between this call and the next frame are seen; writes through a pointer kept PAST a frame call are not (the list passes would read the
  * stale copy while the scans read the arrays) -- call ifx_map_view again before such writes.  ifx_set_option(h, "hot_verify", 1) makes every frame compare the copy with
  * the arrays first (one streaming pass, debug only); ifx_hot_records_stale returns how many slots it found differing (and repaired) since ifx_create: 0 for a caller
- * that keeps the rule. */
+ * that keeps the rule.
+ * The arrays are AS OF THE REFERENCE'S CLEAN PASS of the last frame: the call first applies the age rule to every slot the cached view list leaves out (the forced scan
+ * every whole-store reader makes, ifx_map.hip "View list"), so a slot whose times.y is above the tombstone marker is a surfel the reference's map holds, and no other. */
 int ifx_map_view(ifx_t* h, ifx_soa_view* out);
 int ifx_hot_records_stale(ifx_t* h);
 int ifx_map_count(ifx_t* h);      /* live surfels (synchronises) */

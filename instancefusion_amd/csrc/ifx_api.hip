@@ -1685,6 +1685,7 @@ extern "C" int ifx_map_view(ifx_t* h, ifx_soa_view* out)
 {
     if (h) h->hot_valid = 0;   // (the caller holds the arrays' addresses from here on: whatever it writes, the next frame rebuilds the gathered copy)
     if (!h || !out) return IFX_E_INVALID;
+    ifx_vlist_reap(h);   // whole-map consumer (the caller's kernels): nothing outside the cached view list may outlive the age rule (ifx_map.hip "View list")
     int r = ifx_sync(h);
     DevState hs;
     HIPCHK(h, hipMemcpy(&hs, h->d_state, sizeof(hs), hipMemcpyDeviceToHost));

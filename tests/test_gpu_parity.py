@@ -408,7 +408,7 @@ def test_bounding_boxes_and_instance_point_clouds(ifx, orc, small_stream):
     assert np.array_equal(rg[:, 0], ro[:, 0]) and np.array_equal(rg[:, 7:], ro[:, 7:])      # slots in map order, colours
     assert np.allclose(rg[:, 1:7], ro[:, 1:7], atol=2e-5)
     lab = inst.labels()
-    assert set(rg[:, 0].astype(int).tolist()) <= set(np.nonzero(lab >= 0)[0].tolist()) or True
+    assert set(rg[:, 0].astype(int).tolist()) <= set(np.nonzero(lab >= 0)[0].tolist())       # every record's slot is a labelled live surfel (compacted store: slot = rank)
     g.close(); o.close()
 
 
