@@ -1109,6 +1109,30 @@ int ifx_render_project_map(ifx_t* h, float* out_rgba, float* d_out_rgba);
 typedef struct { float mvp[16]; int32_t w, h; float threshold; int32_t color_type, unstable, draw_window, time, time_delta; float clear_rgb[3]; } ifx_view_params;
 int ifx_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids);
 int ifx_render_view_big_quads(ifx_t* h);
+/* The same render of a spatially sharded map (ifx_config::n_ranks), where no rank holds the whole map.  RULE: the rule of ifx_render_view with one change -- the low
+ * word of a pixel's key is the surfel's CREATION NUMBER, not its slot.  Creation numbers are the same on every rank and ascend with the slots of the unsharded,
+ * compacted map, so a depth tie goes to the lower creation number on every rank, which is ifx_render_view's "lower slot": rgba equals the unsharded render of the
+ * merged map bit for bit, and ids holds creation numbers (the slots of that map through ifx_map_seq's numbering), -1 where nothing is drawn (creation numbers stop at
+ * 0xFFF00000).  Every rank makes the calls with the same parameters and gets the whole image.
+ *   ifx_owner_render_view_begin(h, p, want_rgba, want_ids)   draws this rank's shard into the viewer's key image.  Returns 1: an exchange is pending, 0: nothing was
+ *       asked for (neither output wanted), < 0: refused.
+ *   ifx_owner_render_view_resume(h, out_rgba, out_ids, d_out_rgba, d_out_ids)   continues behind the exchange; 1: another exchange is pending (the outputs are not
+ *       yet read or written), 0: the outputs are written (host, device, both or neither of each wanted image, as ifx_render_view).  An output begin was not
+ *       asked for is IFX_E_INVALID.
+ *   The pending exchange is listed by ifx_owner_exchange under 400 -- the key image, op 0 (u64 MIN), 8 B / pixel -- and then, only when rgba is wanted, under 401 --
+ *       the colour block, in which the owner of each pixel's winner has written the colour and every other rank zeros, op 1 (i32 SUM), 16 B / pixel.  An ids-only
+ *       call has one exchange.
+ *   ifx_owner_render_view   the same as ONE call when the library holds the communicator (ifx_owner_init_comm / ifx_owner_set_comm): its collectives are counted by
+ *       ifx_owner_exchange_stats (1 and 8 B / pixel, or 2 and 24 B / pixel with rgba); enqueue only unless a host output is given.
+ *   ifx_owner_render_view_big_quads   the big-quad count of THIS rank's shard in the last call.
+ * IFX_E_INVALID exactly where ifx_render_view returns it.  IFX_E_STATE: an unsharded handle; between the phases of a frame (ifx_owner_frame_phase) or of a predict;
+ * while a segmentation call or an id render waits for its exchange; _begin while a render is pending, _resume without _begin; ifx_owner_render_view without a
+ * communicator.  Nothing is written by a refused call.  Read-only on the map: only the viewer's own buffers are written or exchanged, and the key image is all-empty
+ * again when the call ends.  ifx_render_view itself keeps refusing sharded handles. */
+int ifx_owner_render_view_begin(ifx_t* h, const ifx_view_params* p, int want_rgba, int want_ids);
+int ifx_owner_render_view_resume(ifx_t* h, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids);
+int ifx_owner_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids);
+int ifx_owner_render_view_big_quads(ifx_t* h);
 /* ---- instance ground truth (the reference's ScanNet evaluation).
  * ifx_set_instance_gt: the instanceGT argument of ElasticFusion::processFrame (EF/ElasticFusion.h:79, EF/ElasticFusion.cpp:285-291): H x W bytes; surfels created by the
  *   frames that follow remember the id under the pixel that created them (vImgCorr.w, data.vert:215-228; -2 without ground truth).  NULL switches it off.

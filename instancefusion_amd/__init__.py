@@ -255,6 +255,10 @@ _SIGS = {
     "ifx_render_project_map": (C.c_int, [_P, _P, _P]),
     "ifx_render_view": (C.c_int, [_P, C.POINTER(ViewParams), _P, _P, _P, _P]),
     "ifx_render_view_big_quads": (C.c_int, [_P]),
+    "ifx_owner_render_view_begin": (C.c_int, [_P, C.POINTER(ViewParams), C.c_int, C.c_int]),
+    "ifx_owner_render_view_resume": (C.c_int, [_P, _P, _P, _P, _P]),
+    "ifx_owner_render_view": (C.c_int, [_P, C.POINTER(ViewParams), _P, _P, _P, _P]),
+    "ifx_owner_render_view_big_quads": (C.c_int, [_P]),
     "ifx_set_instance_gt": (C.c_int, [_P, _P]),
     "ifx_precision_recall": (C.c_int, [_P, _P, _P, _P]),
     "ifx_instance_table": (C.c_int, [_P, _P]),
@@ -330,6 +334,19 @@ MASK_F32 = 1    # inside iff the value is > threshold (mask probabilities; NaN i
 ID_RULE_RAY_DISC = 0     # default: a ray through each pixel centre against the disc, f32 depth keys
 ID_RULE_REFERENCE = 1    # the reference's surfel_ids.geom / .frag: screen-space quads, 24-bit depth
 
+
+
+def view_params(mvp, size, color_type=None, threshold=None, unstable=False, draw_window=False, time=-1, time_delta=-1, clear_rgb=(1.0, 1.0, 1.0), draw_instances=False,
+                draw_times=False, draw_colors=False, draw_normals=False):
+    """the ifx_view_params of a render_view call (ElasticFusion.render_view documents the arguments)"""
+    p = ViewParams()
+    p.mvp[:] = [float(v) for v in np.ascontiguousarray(mvp, np.float32).reshape(16)]
+    p.w, p.h = int(size[0]), int(size[1])
+    p.threshold = float("nan") if threshold is None else float(threshold)
+    p.color_type = int(view_color_type(draw_instances, draw_times, draw_colors, draw_normals) if color_type is None else color_type)
+    p.unstable, p.draw_window, p.time, p.time_delta = int(bool(unstable)), int(bool(draw_window)), int(time), int(time_delta)
+    p.clear_rgb[:] = [float(v) for v in clear_rgb]
+    return p
 
 
 def viewer_mvp(fx, fy, cx, cy, w, h, near, far, pose):
@@ -679,28 +696,28 @@ class ElasticFusion(_DetectorOperators):
         mvp: 4x4 (viewer_mvp builds the reference's); size: (w, h) of the viewport, unrelated to the frame's.  color_type 0..4, or the GUI's flags by
         name (view_color_type).  threshold None / time < 0 / time_delta < 0: the handle's own.  Returns (rgba [h, w, 4] f32, ids [h, w] int32: the slot
         under each pixel in the numbering of ids_after, -1 where nothing was drawn), top row first; device=True: two torch tensors on the GPU."""
-        w, h = int(size[0]), int(size[1])
-        p = ViewParams()
-        m = np.ascontiguousarray(mvp, np.float32).reshape(16)
-        p.mvp[:] = [float(v) for v in m]
-        p.w, p.h = w, h
-        p.threshold = float("nan") if threshold is None else float(threshold)
-        p.color_type = int(view_color_type(draw_instances, draw_times, draw_colors, draw_normals) if color_type is None else color_type)
-        p.unstable, p.draw_window, p.time, p.time_delta = int(bool(unstable)), int(bool(draw_window)), int(time), int(time_delta)
-        p.clear_rgb[:] = [float(v) for v in clear_rgb]
-        ok = 1 <= w <= 4096 and 1 <= h <= 4096      # (the call refuses other sizes; the buffers below only need to exist)
+        p = view_params(mvp, size, color_type, threshold, unstable, draw_window, time, draw_instances=draw_instances, draw_times=draw_times, draw_colors=draw_colors,
+                        draw_normals=draw_normals, time_delta=time_delta, clear_rgb=clear_rgb)
+        rgba, ids = self._view_outputs(size, device)
         if device:
-            import torch
-            dev = torch.device("cuda", self.cfgd["device"])
-            rgba = torch.empty((h if ok else 1, w if ok else 1, 4), dtype=torch.float32, device=dev)
-            ids = torch.empty((h if ok else 1, w if ok else 1), dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()      # the tensors' memory is ours before the handle's stream writes it
             self._chk(self.L.ifx_render_view(self.handle, C.byref(p), None, None, C.c_void_p(rgba.data_ptr()), C.c_void_p(ids.data_ptr())), "ifx_render_view")
             self.sync()
             return rgba, ids
-        rgba, ids = np.zeros((h if ok else 1, w if ok else 1, 4), np.float32), np.zeros((h if ok else 1, w if ok else 1), np.int32)
         self._chk(self.L.ifx_render_view(self.handle, C.byref(p), _ptr(rgba), _ptr(ids), None, None), "ifx_render_view")
         return rgba, ids
+
+    def _view_outputs(self, size, device):
+        """the two images of a render_view call: numpy arrays, or torch tensors on the handle's GPU whose memory is ours before the handle's stream writes it"""
+        w, h = int(size[0]), int(size[1])
+        if not (1 <= w <= 4096 and 1 <= h <= 4096):      # (the call refuses other sizes; the buffers only need to exist)
+            w = h = 1
+        if device:
+            import torch
+            dev = torch.device("cuda", self.cfgd["device"])
+            rgba, ids = torch.empty((h, w, 4), dtype=torch.float32, device=dev), torch.empty((h, w), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            return rgba, ids
+        return np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32)
 
     def set_pose(self, pose, tick):
         p = np.ascontiguousarray(pose, np.float32).reshape(16)

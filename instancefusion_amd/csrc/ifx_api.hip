@@ -1104,6 +1104,7 @@ static int owner_frame_phase(ifx* h, int phase, const uint8_t* d_rgb, const uint
     if (!h->own) { h->err = "ifx_owner_frame_phase: the handle was not created with n_ranks > 1"; return IFX_E_STATE; }
     if (h->lc_enable && (h->lc_cb || h->fern_cb)) { h->err = "on a sharded map the loop-closure DETECTION is available; the deformation callbacks are not"; return IFX_E_STATE; }
     if (h->own_ids_pending || h->oseg_state) { h->err = "ifx_owner_frame_phase: an id render / a segmentation call of this sharded map is waiting for its exchange (ifx_owner_ids_resume / ifx_owner_segmentation_resume)"; return IFX_E_STATE; }
+    if (h->view_pending) { h->err = "ifx_owner_frame_phase: a render of this sharded map is waiting for its exchange (ifx_owner_render_view_resume)"; return IFX_E_STATE; }
     const bool first = h->tick == 1 && h->n_traj == 0;
     const int s = h->tick & 1;
     FrameSlot& f = h->slot[s];
@@ -1179,6 +1180,7 @@ static int owner_frame_phase(ifx* h, int phase, const uint8_t* d_rgb, const uint
         { int r = ifx_enqueue_hinted_frame_side(h); if (r) return r; }   // (a tracker enqueue consumed the hint already: no-op)
         h->own_frame_pose_set = 0;
         h->own_tracked_tick = h->tick;
+        h->own_open = 1;   // until phase 7 (what ifx_owner_render_view refuses on)
         if (phase == 310) return IFX_OK;   // the pose block travels from the tracking rank next (exchange 310)
     }
     if (phase == 300 && h->own_tracked_tick == h->tick) {
@@ -1206,6 +1208,7 @@ static int owner_frame_phase(ifx* h, int phase, const uint8_t* d_rgb, const uint
         h->seg_counts_valid = first ? 0 : 1;
         h->n_traj++;
         h->tick++;
+        h->own_open = 0;
         // the announced next frame: its tracker reads only its slot, the prediction just exchanged and the pose -- enqueued now, parked (DevState::spec_*), so that the
         // GPU has work while the host decides about segmentation (enqueue_frame does the same on the unsharded path).  Replicated tracking only: with camera contexts /
         // a tracking rank the frames of a set interleave cameras (ifx_owner_track_camera_ahead is that case's look-ahead)
@@ -1232,6 +1235,7 @@ extern "C" int ifx_owner_predict_phase(ifx_t* h, int step)
     if (!h || step < 0 || step > 2) return IFX_E_INVALID;
     if (!h->own) { h->err = "ifx_owner_predict_phase: the handle was not created with n_ranks > 1"; return IFX_E_STATE; }
     ifx_drop_tracked(h);
+    h->own_open = step < 2;
     const int r = ifx_map_owner_phase(h, 104 + step, false);
     if (!r && step == 1) h->pred_root = owner_pred_root(h);   // (the exchange behind this step is exchange 5)
     return r;
@@ -1277,6 +1281,8 @@ extern "C" int ifx_owner_exchange(ifx_t* h, int phase, void** ptrs, int64_t* byt
         default: break;
         }
         break;
+    case 400: if (h->view_pending == 1) add(h->view_keys, (size_t)h->view_p.w * h->view_p.h * 8, 0); break;    // ifx_owner_render_view_begin: the viewer's key image (depth | creation number): MIN
+    case 401: if (h->view_pending == 2) add(h->view_col, (size_t)h->view_p.w * h->view_p.h * 16, 1); break;    // the owners' colours of the winners, zeros elsewhere: disjoint supports
     default: break;
     }
     return n;

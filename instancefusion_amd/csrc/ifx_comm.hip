@@ -22,6 +22,9 @@
 // Options (round 6): own_lazy_ids -- exchange 4 carries [key_splat | the id keys of the sampled 10 x 10 lattice]: 72 B / pixel, the whole id image's keys travel with a
 // segmentation call; own_key_rs -- the index keys of exchanges 0 and 2 as reduce-scatter + all-gather of the creation numbers (op 6): 68 B / pixel in all-reduce-equivalent
 // bytes, eight collectives.
+// Outside a frame: the free-viewpoint render of the sharded map (ifx_owner_render_view, below) has two exchange points over the viewer's own buffers, per viewport pixel:
+//   400  view_keys (depth24 | creation number)             u64 MIN     8 B / pixel
+//   401  view_col (the winners' colours, by their owners)  i32 SUM    16 B / pixel    (only when rgba is asked for)
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 #include <string.h>
@@ -308,6 +311,23 @@ extern "C" int ifx_owner_knn_vote_colour(ifx_t* h)
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return ifx_owner_knn_vote(h, allp, alll, (int)total, (int)my_off);
+}
+
+// ifx_render_view on the sharded map in one call (ifx_map.hip: ifx_owner_render_view_begin / _resume with the exchanges done here): the key image's MIN (400), then --
+// when rgba is wanted -- the colour block's SUM (401); enqueue-only unless a host output is given.  Every rank makes the call with the same parameters.
+extern "C" int ifx_owner_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids)
+{
+    if (!h || !p) return IFX_E_INVALID;
+    int r = ifx_owner_view_check(h, p, "ifx_owner_render_view");
+    if (r) return r;
+    if (!ifx_comm_ready(h)) { h->err = "ifx_owner_render_view: no communicator: ifx_owner_init_comm / ifx_owner_set_comm first (or ifx_owner_render_view_begin / _resume around the caller's own exchanges)"; return IFX_E_STATE; }
+    r = ifx_owner_render_view_begin(h, p, out_rgba || d_out_rgba, out_ids || d_out_ids);
+    while (r == 1) {
+        r = ifx_comm_exchange(h, 399 + h->view_pending);
+        if (r) { ifx_owner_view_abort(h); return r; }
+        r = ifx_owner_render_view_resume(h, out_rgba, out_ids, d_out_rgba, d_out_ids);
+    }
+    return r;
 }
 
 // r: what a begin form returned -- the exchange points of the call until it is complete, then the kNN smoothing (flags bit 0)

@@ -453,6 +453,12 @@ struct ifx {
     unsigned long long* view_keys = nullptr; size_t view_keys_px = 0;
     unsigned int* view_big = nullptr;
     void* view_out = nullptr; size_t view_out_px = 0;
+    // ifx_owner_render_view (sharded map): the colour block the owners fill ([view_col_px] float4, summed over the ranks: exchange 401; allocated by the first call that
+    // wants rgba) and the call in flight -- view_pending 1: the key image waits for its MIN (exchange 400), 2: the colour block for its SUM; view_want bit 0 rgba, bit 1 ids
+    void* view_col = nullptr; size_t view_col_px = 0;
+    int view_pending = 0, view_want = 0;
+    ifx_view_params view_p;             // the pending call's parameters, time and time_delta resolved
+    int own_open = 0;                   // sharded map: between the phases of a frame (ifx_owner_frame_phase) or of a predict (ifx_owner_predict_phase)
     float *d_sample = nullptr, *d_cons = nullptr;   // scratch of ifx_sample_graph_model / ifx_loop_closure_constraints
     ifx_loop_closure_cb lc_cb = nullptr;
     void* lc_user = nullptr;
@@ -668,6 +674,8 @@ int ifx_owner_ids_begin_impl(ifx* h);                         // sharded map: 1 
 int ifx_owner_ids_resume_impl(ifx* h);
 int ifx_own_lattice(const ifx* h);                            // entries of the id lattice (one per 10 x 10 pixels)
 void ifx_view_free(ifx* h);                                   // ifx_render_view's buffers
+int ifx_owner_view_check(ifx* h, const ifx_view_params* p, const char* who);   // the refusals of the sharded render, nothing touched
+void ifx_owner_view_abort(ifx* h);                            // a sharded render that failed at an exchange is over: the key image all-empty again
 int ifx_vlist_reap(ifx* h);                                   // forced view-list scan: applies the age rule to the slots outside the list (before any whole-map consumer)
 int ifx_map_sharded_phase(ifx* h, int phase, bool first_frame);
 int ifx_map_predict_loop_closure(ifx* h);                     // predict() at the tracked pose + INACTIVE prediction (old* images)

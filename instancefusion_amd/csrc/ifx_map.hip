@@ -748,8 +748,12 @@ __device__ __forceinline__ unsigned long long view_key(const ViewQuad& Q, int px
 
 // All slots, one thread per slot: culls and set-up; a quad of at most VIEW_SMALL pixels is drawn here, a larger one goes to big[1 + ...] (big[0] = the list's
 // length; capacity = the slot count, a slot is listed at most once), appended with one atomic per wave.  The trip count of the loop is the same for a whole block.
+// SEQ (the sharded render, ifx_owner_render_view): the low word of a key is the slot's creation number seq[slot] -- the same number on every rank, ascending with the
+// slot, so a depth tie goes to the surfel the unsharded map holds in the lower slot.  The list still names slots.  A template parameter, no run-time branch: the
+// unsharded instantiation never reads seq (nullptr) and keeps its registers.
+template <bool SEQ>
 __global__ __launch_bounds__(MAP_THREADS) void k_view_quad(const DevState* __restrict__ st, const float4* __restrict__ pc, const float4* __restrict__ nr, const float2* __restrict__ col,
-                                                           ViewCam c, unsigned long long* __restrict__ keys, unsigned int* __restrict__ big)
+                                                           ViewCam c, unsigned long long* __restrict__ keys, unsigned int* __restrict__ big, const uint32_t* __restrict__ seq)
 {
     const int n = st->count;
     const unsigned int lane = threadIdx.x & 63u;
@@ -758,6 +762,7 @@ __global__ __launch_bounds__(MAP_THREADS) void k_view_quad(const DevState* __res
         bool is_big = false;
         if (i < n) {
             ViewQuad Q;
+            const unsigned int low = SEQ ? seq[i] : (unsigned int)i;   // (with the slot's record, not behind the first drawn pixel)
             if (view_setup(c, pc[i], nr[i], col[i].y, Q)) {
                 const int bw = Q.x1 - Q.x0 + 1;
                 if (bw * (Q.y1 - Q.y0 + 1) > VIEW_SMALL) is_big = true;
@@ -765,7 +770,7 @@ __global__ __launch_bounds__(MAP_THREADS) void k_view_quad(const DevState* __res
                     for (int py = Q.y0; py <= Q.y1; py++)
                         for (int px = Q.x0; px <= Q.x1; px++) {
                             const unsigned long long k = view_key(Q, px, py);
-                            if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | (unsigned long long)(unsigned int)i);
+                            if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | (unsigned long long)low);
                         }
             }
         }
@@ -782,8 +787,9 @@ __global__ __launch_bounds__(MAP_THREADS) void k_view_quad(const DevState* __res
 
 // The listed quads, one workgroup each (a fixed grid strides over the list, whose length is read from device memory): one thread redoes the set-up, the
 // workgroup's threads stride over the pixel box.
+template <bool SEQ>
 __global__ __launch_bounds__(256) void k_view_big(const float4* __restrict__ pc, const float4* __restrict__ nr, const float2* __restrict__ col, ViewCam c,
-                                                  unsigned long long* __restrict__ keys, const unsigned int* __restrict__ big)
+                                                  unsigned long long* __restrict__ keys, const unsigned int* __restrict__ big, const uint32_t* __restrict__ seq)
 {
     __shared__ ViewQuad Qs;
     __shared__ int drawn;
@@ -799,10 +805,11 @@ __global__ __launch_bounds__(256) void k_view_big(const float4* __restrict__ pc,
         if (drawn) {
             const ViewQuad Q = Qs;
             const int bw = Q.x1 - Q.x0 + 1, np = bw * (Q.y1 - Q.y0 + 1);
+            const unsigned long long low = SEQ ? (unsigned long long)seq[i] : (unsigned long long)i;
             for (int t = threadIdx.x; t < np; t += blockDim.x) {
                 const int px = Q.x0 + t % bw, py = Q.y0 + t / bw;
                 const unsigned long long k = view_key(Q, px, py);
-                if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | (unsigned long long)i);
+                if (k != IFX_KEY_EMPTY) atomicMin(&keys[py * c.w + px], k | low);
             }
         }
         __syncthreads();
@@ -815,8 +822,25 @@ __device__ __forceinline__ void view_decode(float w, float& r, float& g, float& 
     const int v = (int)w;
     r = (float)((v >> 16) & 0xFF) / 255.0f; g = (float)((v >> 8) & 0xFF) / 255.0f; b = (float)(v & 0xFF) / 255.0f;
 }
+// the base colour of a drawn surfel -- draw_global_surface.geom:50-88, per surfel, not interpolated -- with alpha 1 (k_view_resolve; the owner's resolve of the sharded render)
+__device__ __forceinline__ float4 view_colour(const ViewCol& v, float4 n4, float2 c2, float2 t2)
+{
+    const float d = fabsf((n4.x + n4.y) + n4.z), grey = 0.5f * d + 0.1f;
+    float cr = grey, cg = grey, cb = grey;
+    if (v.color_type == 1) { cr = n4.x; cg = n4.y; cb = n4.z; }
+    else if (v.color_type == 2) view_decode(c2.x, cr, cg, cb);
+    else if (v.color_type == 3) {
+        const float ratio = (2.0f * (t2.x - 1.0f)) / ((float)v.time - 1.0f);
+        const float a = 1.0f - ratio, b = ratio - 1.0f, s = d + 0.1f;
+        cr = a > 0.0f ? a : 0.0f; cg = b > 0.0f ? b : 0.0f; cb = (1.0f - cr) - cg;
+        cr = cr * s; cg = cg * s; cb = cb * s;
+    }
+    else if (v.color_type == 4) view_decode(c2.y, cr, cg, cb);
+    if (v.draw_window && (float)v.time - t2.y > (float)v.time_delta) { cr = cr * 0.25f; cg = cg * 0.25f; cb = cb * 0.25f; }
+    return make_float4(cr * 0.6f + grey * 0.4f, cg * 0.6f + grey * 0.4f, cb * 0.6f + grey * 0.4f, 1.0f);
+}
 // One thread per output pixel: the key of GL window row h - 1 - r (a screenshot's order, top row first), re-armed; the winner's slot (-1: nothing drawn) and its
-// base colour -- draw_global_surface.geom:50-88, per surfel, not interpolated -- with alpha 1; the clear colour with alpha 0 elsewhere.
+// base colour with alpha 1; the clear colour with alpha 0 elsewhere.
 __global__ void k_view_resolve(unsigned long long* __restrict__ keys, const float4* __restrict__ nr, const float2* __restrict__ col, const float2* __restrict__ tm, int w, int h,
                                ViewCol v, int32_t* __restrict__ ids, float4* __restrict__ rgba)
 {
@@ -833,21 +857,44 @@ __global__ void k_view_resolve(unsigned long long* __restrict__ keys, const floa
     const unsigned int i = (unsigned int)(key & 0xFFFFFFFFull);
     if (ids) ids[k] = (int32_t)i;
     if (!rgba) return;
-    const float4 n4 = nr[i];
-    const float2 c2 = col[i], t2 = tm[i];
-    const float d = fabsf((n4.x + n4.y) + n4.z), grey = 0.5f * d + 0.1f;
-    float cr = grey, cg = grey, cb = grey;
-    if (v.color_type == 1) { cr = n4.x; cg = n4.y; cb = n4.z; }
-    else if (v.color_type == 2) view_decode(c2.x, cr, cg, cb);
-    else if (v.color_type == 3) {
-        const float ratio = (2.0f * (t2.x - 1.0f)) / ((float)v.time - 1.0f);
-        const float a = 1.0f - ratio, b = ratio - 1.0f, s = d + 0.1f;
-        cr = a > 0.0f ? a : 0.0f; cg = b > 0.0f ? b : 0.0f; cb = (1.0f - cr) - cg;
-        cr = cr * s; cg = cg * s; cb = cb * s;
+    rgba[k] = view_colour(v, nr[i], col[i], tm[i]);
+}
+
+// ---- the sharded render (ifx_owner_render_view): the key image holds depth24 << 32 | creation number and has been MIN-reduced over the ranks
+// One thread per pixel of the key image (GL row order): the winner's creation number is looked up in this rank's ascending seq[0 .. count) by a lower-bound search
+// (ceil(log2 count) dependent loads: 23 at 5 M slots); a hit means this rank owns the pixel and knows the slot, and it writes the pixel's colour -- view_colour, as
+// k_view_resolve -- into the colour block; every other rank (and an empty pixel) writes zeros, so the int32 SUM over the ranks is a bitwise merge.  The keys stay:
+// the final pass reads them once more and re-arms them.
+__global__ void k_view_own_resolve(const DevState* __restrict__ st, const unsigned long long* __restrict__ keys, const uint32_t* __restrict__ seq, const float4* __restrict__ nr,
+                                   const float2* __restrict__ col, const float2* __restrict__ tm, int px, ViewCol v, float4* __restrict__ colour)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= px) return;
+    const unsigned long long key = keys[k];
+    float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (key != IFX_KEY_EMPTY) {
+        const unsigned int id = (unsigned int)(key & 0xFFFFFFFFull);
+        int lo = 0, hi = st->count;   // first slot whose creation number is >= id
+        while (lo < hi) {
+            const int mid = (int)(((unsigned int)lo + (unsigned int)hi) >> 1);
+            if (seq[mid] < id) lo = mid + 1; else hi = mid;
+        }
+        if (lo < st->count && seq[lo] == id) out = view_colour(v, nr[lo], col[lo], tm[lo]);
     }
-    else if (v.color_type == 4) view_decode(c2.y, cr, cg, cb);
-    if (v.draw_window && (float)v.time - t2.y > (float)v.time_delta) { cr = cr * 0.25f; cg = cg * 0.25f; cb = cb * 0.25f; }
-    rgba[k] = make_float4(cr * 0.6f + grey * 0.4f, cg * 0.6f + grey * 0.4f, cb * 0.6f + grey * 0.4f, 1.0f);
+    colour[k] = out;
+}
+// One thread per output pixel, behind the last exchange: the key of GL window row h - 1 - r, re-armed; the creation number of the winner (-1: nothing drawn) and the
+// summed colour block's pixel (colour == nullptr: the caller wanted no rgba, there is no block), the clear colour with alpha 0 where the key was empty.
+__global__ void k_view_own_final(unsigned long long* __restrict__ keys, const float4* __restrict__ colour, int w, int h, ViewCol v, int32_t* __restrict__ ids, float4* __restrict__ rgba)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= w * h) return;
+    const int r = k / w, x = k - r * w, src = (h - 1 - r) * w + x;
+    const unsigned long long key = keys[src];
+    keys[src] = IFX_KEY_EMPTY;
+    const bool empty = key == IFX_KEY_EMPTY;
+    if (ids) ids[k] = empty ? -1 : (int32_t)(unsigned int)(key & 0xFFFFFFFFull);
+    if (rgba) rgba[k] = empty ? make_float4(v.clear[0], v.clear[1], v.clear[2], 0.0f) : colour[src];
 }
 
 __device__ inline float key_depth(unsigned long long key)
@@ -3990,61 +4037,103 @@ extern "C" int ifx_adopt_estimated_pose(ifx_t* h)
 // call, the key image regrown for a larger viewport; key_ids and the frame's work lists belong to the frame.
 void ifx_view_free(ifx* h)
 {
-    void* ptrs[] = {h->view_keys, h->view_big, h->view_out};
+    void* ptrs[] = {h->view_keys, h->view_big, h->view_out, h->view_col};
     for (void* p : ptrs) if (p) hipFree(p);
-    h->view_keys = nullptr; h->view_big = nullptr; h->view_out = nullptr; h->view_keys_px = 0; h->view_out_px = 0;
+    h->view_keys = nullptr; h->view_big = nullptr; h->view_out = nullptr; h->view_col = nullptr; h->view_keys_px = 0; h->view_out_px = 0; h->view_col_px = 0;
+    h->view_pending = 0;
 }
-extern "C" int ifx_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids)
+// IFX_E_INVALID of both renders; who: the entry's name for the message
+static int view_params_check(ifx* h, const ifx_view_params* p, const char* who)
 {
-    if (!h || !p) return IFX_E_INVALID;
-    if (p->w < 1 || p->w > 4096 || p->h < 1 || p->h > 4096) { h->err = "ifx_render_view: the viewport is 1..4096 pixels on each axis"; return IFX_E_INVALID; }
-    if (p->color_type < 0 || p->color_type > 4) { h->err = "ifx_render_view: color_type is 0..4"; return IFX_E_INVALID; }
+    if (p->w < 1 || p->w > 4096 || p->h < 1 || p->h > 4096) { h->err = std::string(who) + ": the viewport is 1..4096 pixels on each axis"; return IFX_E_INVALID; }
+    if (p->color_type < 0 || p->color_type > 4) { h->err = std::string(who) + ": color_type is 0..4"; return IFX_E_INVALID; }
     for (int k = 0; k < 16; k++)
-        if (!(fabsf(p->mvp[k]) < INFINITY)) { h->err = "ifx_render_view: mvp is not finite"; return IFX_E_INVALID; }
-    if (h->own || h->shard_n > 1) { h->err = "ifx_render_view: not on a sharded handle"; return IFX_E_STATE; }
-    if (h->clean_raster_pending) { h->err = "ifx_render_view: a frame's map passes are in flight"; return IFX_E_STATE; }
-    if (!out_rgba && !out_ids && !d_out_rgba && !d_out_ids) return IFX_OK;
-    ifx_vlist_reap(h);   // whole-map consumer: nothing outside the cached view list may outlive the age rule ("View list")
-    const size_t px = (size_t)p->w * p->h;
+        if (!(fabsf(p->mvp[k]) < INFINITY)) { h->err = std::string(who) + ": mvp is not finite"; return IFX_E_INVALID; }
+    return IFX_OK;
+}
+// one of the viewer's per-pixel buffers, regrown for a larger viewport (the stream is drained before the old one goes)
+static int view_grow(ifx* h, void** buf, size_t* have_px, size_t px, size_t bytes_per_px)
+{
+    if (px <= *have_px) return IFX_OK;
+    if (*buf) { HIPCHK(h, hipStreamSynchronize(h->cur)); hipFree(*buf); *buf = nullptr; *have_px = 0; }
+    HIPCHK(h, hipMalloc(buf, px * bytes_per_px));
+    *have_px = px;
+    return IFX_OK;
+}
+// the key image (all-empty when new) and the big-quad list
+static int view_key_buffers(ifx* h, size_t px)
+{
     if (px > h->view_keys_px) {
-        if (h->view_keys) { HIPCHK(h, hipStreamSynchronize(h->cur)); hipFree(h->view_keys); h->view_keys = nullptr; h->view_keys_px = 0; }
-        HIPCHK(h, hipMalloc(&h->view_keys, px * 8));
-        h->view_keys_px = px;
+        const int r = view_grow(h, (void**)&h->view_keys, &h->view_keys_px, px, 8);
+        if (r) return r;
         HIPCHK(h, hipMemsetAsync(h->view_keys, 0xFF, px * 8, h->cur));
     }
     if (!h->view_big) HIPCHK(h, hipMalloc(&h->view_big, ((size_t)h->cap + 1) * 4));
-    float* rgba = d_out_rgba;
-    int32_t* ids = d_out_ids;
-    if ((out_rgba && !d_out_rgba) || (out_ids && !d_out_ids)) {   // host outputs alone: staged in the viewer's own buffer ([px] float4 | [px] int32)
-        if (px > h->view_out_px) {
-            if (h->view_out) { HIPCHK(h, hipStreamSynchronize(h->cur)); hipFree(h->view_out); h->view_out = nullptr; h->view_out_px = 0; }
-            HIPCHK(h, hipMalloc(&h->view_out, px * 20));
-            h->view_out_px = px;
-        }
-        if (out_rgba && !rgba) rgba = (float*)h->view_out;
-        if (out_ids && !ids) ids = (int32_t*)((char*)h->view_out + h->view_out_px * 16);
+    return IFX_OK;
+}
+// where the last kernel writes: the device outputs, or -- host outputs alone -- the viewer's own staging buffer ([px] float4 | [px] int32)
+static int view_targets(ifx* h, size_t px, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids, float** rgba, int32_t** ids)
+{
+    *rgba = d_out_rgba; *ids = d_out_ids;
+    if ((out_rgba && !d_out_rgba) || (out_ids && !d_out_ids)) {
+        const int r = view_grow(h, &h->view_out, &h->view_out_px, px, 20);
+        if (r) return r;
+        if (out_rgba && !*rgba) *rgba = (float*)h->view_out;
+        if (out_ids && !*ids) *ids = (int32_t*)((char*)h->view_out + h->view_out_px * 16);
     }
-    ViewCam c;
-    memcpy(c.m, p->mvp, sizeof(c.m));
-    c.w = p->w; c.h = p->h;
-    c.thr = p->threshold == p->threshold ? p->threshold : h->cfg.confidence;
-    c.unstable = p->unstable ? 1 : 0;
-    ViewCol v;
-    v.color_type = p->color_type; v.draw_window = p->draw_window ? 1 : 0;
-    v.time = p->time < 0 ? h->tick : p->time;
-    v.time_delta = p->time_delta < 0 ? h->cfg.time_delta : p->time_delta;
-    memcpy(v.clear, p->clear_rgb, sizeof(v.clear));
-    HIPCHK(h, hipMemsetAsync(h->view_big, 0, 4, h->cur));
-    LAUNCH(h, "view_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_view_quad, (const DevState*)h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, h->view_big);
-    LAUNCH(h, "view_big", dim3(LIST_BLOCKS), dim3(256), k_view_big, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, (const unsigned int*)h->view_big);
-    LAUNCH(h, "view_resolve", dim3((unsigned int)((px + 255) / 256)), dim3(256), k_view_resolve, h->view_keys, (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, p->w, p->h, v, ids,
-           (float4*)rgba);
+    return IFX_OK;
+}
+static int view_copy_out(ifx* h, size_t px, float* out_rgba, int32_t* out_ids, const float* rgba, const int32_t* ids)
+{
     if (out_rgba || out_ids) {
         if (out_rgba) HIPCHK(h, hipMemcpyAsync(out_rgba, rgba, px * 16, hipMemcpyDeviceToHost, h->cur));
         if (out_ids) HIPCHK(h, hipMemcpyAsync(out_ids, ids, px * 4, hipMemcpyDeviceToHost, h->cur));
         HIPCHK(h, hipStreamSynchronize(h->cur));
     }
     return IFX_OK;
+}
+static ViewCam view_cam_of(const ifx* h, const ifx_view_params* p)
+{
+    ViewCam c;
+    memcpy(c.m, p->mvp, sizeof(c.m));
+    c.w = p->w; c.h = p->h;
+    c.thr = p->threshold == p->threshold ? p->threshold : h->cfg.confidence;
+    c.unstable = p->unstable ? 1 : 0;
+    return c;
+}
+static ViewCol view_col_of(const ifx* h, const ifx_view_params* p)
+{
+    ViewCol v;
+    v.color_type = p->color_type; v.draw_window = p->draw_window ? 1 : 0;
+    v.time = p->time < 0 ? h->tick : p->time;
+    v.time_delta = p->time_delta < 0 ? h->cfg.time_delta : p->time_delta;
+    memcpy(v.clear, p->clear_rgb, sizeof(v.clear));
+    return v;
+}
+extern "C" int ifx_render_view(ifx_t* h, const ifx_view_params* p, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids)
+{
+    if (!h || !p) return IFX_E_INVALID;
+    int r = view_params_check(h, p, "ifx_render_view");
+    if (r) return r;
+    if (h->own || h->shard_n > 1) { h->err = "ifx_render_view: not on a sharded handle"; return IFX_E_STATE; }
+    if (h->clean_raster_pending) { h->err = "ifx_render_view: a frame's map passes are in flight"; return IFX_E_STATE; }
+    if (!out_rgba && !out_ids && !d_out_rgba && !d_out_ids) return IFX_OK;
+    ifx_vlist_reap(h);   // whole-map consumer: nothing outside the cached view list may outlive the age rule ("View list")
+    const size_t px = (size_t)p->w * p->h;
+    if ((r = view_key_buffers(h, px))) return r;
+    float* rgba;
+    int32_t* ids;
+    if ((r = view_targets(h, px, out_rgba, out_ids, d_out_rgba, d_out_ids, &rgba, &ids))) return r;
+    const ViewCam c = view_cam_of(h, p);
+    const ViewCol v = view_col_of(h, p);
+    HIPCHK(h, hipMemsetAsync(h->view_big, 0, 4, h->cur));
+    LAUNCH(h, "view_quad", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_view_quad<false>, (const DevState*)h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, h->view_big,
+           (const uint32_t*)nullptr);
+    LAUNCH(h, "view_big", dim3(LIST_BLOCKS), dim3(256), k_view_big<false>, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, (const unsigned int*)h->view_big,
+           (const uint32_t*)nullptr);
+    LAUNCH(h, "view_resolve", dim3((unsigned int)((px + 255) / 256)), dim3(256), k_view_resolve, h->view_keys, (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, p->w, p->h, v, ids,
+           (float4*)rgba);
+    return view_copy_out(h, px, out_rgba, out_ids, rgba, ids);
 }
 // the length of the big-quad list of the last ifx_render_view (quads drawn by k_view_big); synchronises the main stream
 extern "C" int ifx_render_view_big_quads(ifx_t* h)
@@ -4055,4 +4144,83 @@ extern "C" int ifx_render_view_big_quads(ifx_t* h)
     HIPCHK(h, hipMemcpyAsync(&n, h->view_big, 4, hipMemcpyDeviceToHost, h->cur));
     HIPCHK(h, hipStreamSynchronize(h->cur));
     return (int)n;
+}
+
+// ------------------------------------------------------------------ ifx_owner_render_view: the same image from a spatially sharded map
+// No rank holds the map, so the image is put together at two exchange points (ifx_owner_exchange; the library's communicator or the caller reduces):
+//   _begin    k_view_quad<true> ; k_view_big<true> over the shard: depth24 << 32 | creation number          | 400: the key image, u64 MIN, 8 B / pixel
+//   _resume   k_view_own_resolve: the winner's owner writes the pixel's colour, the others zeros        | 401: the colour block, i32 SUM, 16 B / pixel  (rgba wanted only)
+//   _resume   k_view_own_final: rows flipped, clear colour, ids = creation numbers, the keys re-armed
+// A creation number is the surfel's slot in the unsharded, compacted map, so the MIN breaks depth ties as ifx_render_view does and the result equals it bit for
+// bit (ids through that numbering).  Everything the call writes is the viewer's: the key image (all-empty again when the call ends), the big-quad list (zeroed where
+// a call starts, as in ifx_render_view; its length stays readable for ifx_owner_render_view_big_quads), the colour block, the staging of host outputs.
+int ifx_owner_view_check(ifx* h, const ifx_view_params* p, const char* who)
+{
+    const int r = view_params_check(h, p, who);
+    if (r) return r;
+    if (!h->own) { h->err = std::string(who) + ": the handle was not created for a sharded map (ifx_render_view draws an unsharded one)"; return IFX_E_STATE; }
+    if (h->own_open || h->clean_raster_pending) { h->err = std::string(who) + ": between the phases of a frame"; return IFX_E_STATE; }
+    if (h->own_ids_pending || h->oseg_state) { h->err = std::string(who) + ": an id render / a segmentation call of this sharded map is waiting for its exchange"; return IFX_E_STATE; }
+    return IFX_OK;
+}
+void ifx_owner_view_abort(ifx* h)
+{
+    if (h->view_pending && h->view_keys) hipMemsetAsync(h->view_keys, 0xFF, h->view_keys_px * 8, h->cur);
+    h->view_pending = 0;
+}
+extern "C" int ifx_owner_render_view_begin(ifx_t* h, const ifx_view_params* p, int want_rgba, int want_ids)
+{
+    if (!h || !p) return IFX_E_INVALID;
+    int r = ifx_owner_view_check(h, p, "ifx_owner_render_view_begin");
+    if (r) return r;
+    if (h->view_pending) { h->err = "ifx_owner_render_view_begin: a render is already waiting for its exchange (ifx_owner_render_view_resume)"; return IFX_E_STATE; }
+    if (!want_rgba && !want_ids) return 0;
+    ifx_vlist_reap(h);   // whole-map consumer, as ifx_render_view
+    const size_t px = (size_t)p->w * p->h;
+    if ((r = view_key_buffers(h, px))) return r;
+    if (want_rgba && (r = view_grow(h, &h->view_col, &h->view_col_px, px, 16))) return r;
+    const ViewCam c = view_cam_of(h, p);
+    h->view_p = *p;
+    h->view_p.time = p->time < 0 ? h->tick : p->time;
+    h->view_p.time_delta = p->time_delta < 0 ? h->cfg.time_delta : p->time_delta;
+    h->view_want = (want_rgba ? 1 : 0) | (want_ids ? 2 : 0);
+    HIPCHK(h, hipMemsetAsync(h->view_big, 0, 4, h->cur));
+    LAUNCH(h, "view_quad_seq", dim3(MAP_BLOCKS), dim3(MAP_THREADS), k_view_quad<true>, (const DevState*)h->d_state, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys,
+           h->view_big, (const uint32_t*)h->seq);
+    LAUNCH(h, "view_big_seq", dim3(LIST_BLOCKS), dim3(256), k_view_big<true>, (const float4*)h->pc, (const float4*)h->nr, (const float2*)h->col, c, h->view_keys, (const unsigned int*)h->view_big,
+           (const uint32_t*)h->seq);
+    h->view_pending = 1;
+    return 1;
+}
+extern "C" int ifx_owner_render_view_resume(ifx_t* h, float* out_rgba, int32_t* out_ids, float* d_out_rgba, int32_t* d_out_ids)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!h->view_pending) { h->err = "ifx_owner_render_view_resume: no render is waiting (ifx_owner_render_view_begin)"; return IFX_E_STATE; }
+    if (((out_rgba || d_out_rgba) && !(h->view_want & 1)) || ((out_ids || d_out_ids) && !(h->view_want & 2))) {
+        h->err = "ifx_owner_render_view_resume: an output that ifx_owner_render_view_begin was not asked for";
+        return IFX_E_INVALID;
+    }
+    const ifx_view_params* p = &h->view_p;
+    const size_t px = (size_t)p->w * p->h;
+    const ViewCol v = view_col_of(h, p);
+    if (h->view_pending == 1 && (h->view_want & 1)) {   // the keys are merged: the owners' colours, then the second exchange
+        LAUNCH(h, "view_own_resolve", dim3((unsigned int)((px + 255) / 256)), dim3(256), k_view_own_resolve, (const DevState*)h->d_state, (const unsigned long long*)h->view_keys,
+               (const uint32_t*)h->seq, (const float4*)h->nr, (const float2*)h->col, (const float2*)h->tm, (int)px, v, (float4*)h->view_col);
+        h->view_pending = 2;
+        return 1;
+    }
+    float* rgba;
+    int32_t* ids;
+    int r = view_targets(h, px, out_rgba, out_ids, d_out_rgba, d_out_ids, &rgba, &ids);
+    if (r) { ifx_owner_view_abort(h); return r; }
+    LAUNCH(h, "view_own_final", dim3((unsigned int)((px + 255) / 256)), dim3(256), k_view_own_final, h->view_keys, (const float4*)h->view_col, p->w, p->h, v, ids, (float4*)rgba);
+    h->view_pending = 0;
+    return view_copy_out(h, px, out_rgba, out_ids, rgba, ids);
+}
+// the length of this rank's big-quad list in the last sharded render (quads of its shard drawn by k_view_big<true>); synchronises the main stream
+extern "C" int ifx_owner_render_view_big_quads(ifx_t* h)
+{
+    if (!h) return IFX_E_INVALID;
+    if (!h->own) { h->err = "ifx_owner_render_view_big_quads: the handle was not created for a sharded map"; return IFX_E_STATE; }
+    return ifx_render_view_big_quads(h);
 }

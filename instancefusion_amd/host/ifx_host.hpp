@@ -885,7 +885,8 @@ public:
     // The headless forms of RenderMapToBoundGlBuffer (IF/map_interface/ElasticFusionInterface.cpp: GlobalModel::renderPointCloud with the handle's threshold,
     // tick and time window, stable surfels only, no window dimming) and of RenderMapIDToGUIBuffer (renderGlobalID): the map from the camera `mvp` (viewerMvp)
     // into host buffers, top row first -- rgba: h x w x 4 floats (the GUI's white where nothing is drawn, alpha 0 there), ids: h x w slots, -1 where nothing is
-    // drawn.  Either buffer may be null.
+    // drawn.  Either buffer may be null.  On a spatially sharded map every rank makes the call and gets the whole image (ifx_owner_render_view: two collectives on
+    // the library's communicator); ids are then creation numbers -- the slots of the merged, unsharded map.
     void RenderMapToBuffer(const Matrix4f& mvp, int w, int h, bool drawInstances, bool drawTimes, bool drawColors, float* rgba, int32_t* ids, bool drawNormals = false)
     {
         ifx_view_params p;
@@ -896,7 +897,9 @@ public:
         p.color_type = drawInstances ? 4 : drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0;   // EF/GlobalModel.cpp:348
         p.time = -1; p.time_delta = -1;
         p.clear_rgb[0] = p.clear_rgb[1] = p.clear_rgb[2] = 1.0f;   // Gui::preCall
-        if (ifx_render_view(handle(), &p, rgba, ids, nullptr, nullptr) != IFX_OK) throw std::runtime_error(std::string("ifx_render_view: ") + ifx_last_error(handle()));
+        const bool sharded = elastic_fusion_ && elastic_fusion_->sharding().on();
+        const int r = sharded ? ifx_owner_render_view(handle(), &p, rgba, ids, nullptr, nullptr) : ifx_render_view(handle(), &p, rgba, ids, nullptr, nullptr);
+        if (r != IFX_OK) throw std::runtime_error(std::string(sharded ? "ifx_owner_render_view: " : "ifx_render_view: ") + ifx_last_error(handle()));
     }
     void RenderMapIDToBuffer(const Matrix4f& mvp, int w, int h, int32_t* ids) { RenderMapToBuffer(mvp, w, h, false, false, false, nullptr, ids); }
     int getMapSurfelCount() { return elastic_fusion_ ? elastic_fusion_->getMapSurfelCount() : 0; }

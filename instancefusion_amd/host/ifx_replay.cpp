@@ -107,7 +107,6 @@ int main(int argc, char** argv)
     }
     if (a.log.empty()) return usage(argv[0]);
     if (a.merge_duplicates && a.shard.on()) { std::fprintf(stderr, "--merge-duplicates is not available on a sharded map\n"); return 2; }
-    if (!a.view_ppm.empty() && a.shard.on()) { std::fprintf(stderr, "--view-ppm is not available on a sharded map\n"); return 2; }
     if ((a.reloc || a.f2f_rgb) && a.shard.on()) { std::fprintf(stderr, "--reloc / --frame-to-frame-rgb are not available on a sharded map\n"); return 2; }
 
     try {
@@ -215,17 +214,19 @@ int main(int argc, char** argv)
             const double focal = 420.0 * a.view_w / 640.0;
             const Matrix4f mvp = viewerMvp(focal, focal, a.view_w / 2.0, a.view_h / 2.0, a.view_w, a.view_h, 0.1, 1000.0, vp);
             std::vector<float> rgba((size_t)a.view_w * a.view_h * 4);
-            map->RenderMapToBuffer(mvp, a.view_w, a.view_h, a.view_instances, false, !a.view_instances, rgba.data(), nullptr);
+            map->RenderMapToBuffer(mvp, a.view_w, a.view_h, a.view_instances, false, !a.view_instances, rgba.data(), nullptr);   // (a sharded map: every rank takes part, rank 0 writes)
             std::vector<unsigned char> ppm((size_t)a.view_w * a.view_h * 3);
             for (size_t k = 0; k < (size_t)a.view_w * a.view_h; k++)
                 for (int ch = 0; ch < 3; ch++) {
                     const float v = std::rint(rgba[k * 4 + ch] * 255.0f);
                     ppm[k * 3 + ch] = (unsigned char)(v >= 255.0f ? 255.0f : v >= 0.0f ? v : 0.0f);   // (a NaN becomes 0)
                 }
-            std::ofstream f(a.view_ppm, std::ios::binary);
-            f << "P6\n" << a.view_w << " " << a.view_h << "\n255\n";
-            f.write((const char*)ppm.data(), (std::streamsize)ppm.size());
-            if (!f) throw std::runtime_error("cannot write " + a.view_ppm);
+            if (!a.shard.on() || a.shard.rank == 0) {
+                std::ofstream f(a.view_ppm, std::ios::binary);
+                f << "P6\n" << a.view_w << " " << a.view_h << "\n255\n";
+                f.write((const char*)ppm.data(), (std::streamsize)ppm.size());
+                if (!f) throw std::runtime_error("cannot write " + a.view_ppm);
+            }
         }
         const int n_geo = map->elasticFusion().savePly();
         const int n_ins = map->elasticFusion().savePlyInstance();

@@ -252,6 +252,31 @@ class OwnerShardedElasticFusion:
             self._exchange(200)
             self.ef._chk(self.ef.L.ifx_owner_ids_resume(self.ef.handle), "ifx_owner_ids_resume")
 
+    def render_view(self, mvp, size, color_type=None, threshold=None, unstable=False, draw_window=False, time=-1, time_delta=-1, clear_rgb=(1.0, 1.0, 1.0),
+                    draw_instances=False, draw_times=False, draw_colors=False, draw_normals=False, device=False):
+        """ElasticFusion.render_view on the sharded map (ifx_owner_render_view): same arguments, same return, on every rank -- every rank makes the call with the same
+        arguments and gets the whole image.  rgba equals the unsharded render of the merged map bit for bit; ids holds creation numbers (ef.seq()), -1 where nothing
+        is drawn.  Two exchanges: the key image (8 B / pixel, MIN) and the owners' colours (16 B / pixel, SUM)."""
+        from . import view_params
+
+        ef = self.ef
+        p = view_params(mvp, size, color_type, threshold, unstable, draw_window, time, draw_instances=draw_instances, draw_times=draw_times, draw_colors=draw_colors,
+                        draw_normals=draw_normals, time_delta=time_delta, clear_rgb=clear_rgb)
+        rgba, ids = ef._view_outputs(size, device)
+        outs = _view_out_args(rgba, ids, device)
+        if self.transport == "library":
+            ef._chk(ef.L.ifx_owner_render_view(ef.handle, C.byref(p), *outs), "ifx_owner_render_view")
+        else:
+            r = ef._chk(ef.L.ifx_owner_render_view_begin(ef.handle, C.byref(p), 1, 1), "ifx_owner_render_view_begin")
+            phase = 400
+            while r == 1:
+                self._exchange(phase)
+                r = ef._chk(ef.L.ifx_owner_render_view_resume(ef.handle, *outs), "ifx_owner_render_view_resume")
+                phase += 1
+        if device:
+            ef.sync()
+        return rgba, ids
+
     def process_segmentation(self, rgb, depth, masks, class_ids, frame: int, superpixels: bool = True, knn: bool = False):
         """InstanceFusion::processInstance on the sharded map (same masks on every rank): the owners' partial boxes, model depth and -- when the
         instance table overflows -- eviction statistics are merged at the call's exchange points; labels of the owned surfels: ef.labels()."""
@@ -509,6 +534,42 @@ def emulate_owner_ids(efs):
         _reduce_by_hand(efs, [_exchange_spec(e, 200) for e in efs])
         for e in efs:
             e._chk(e.L.ifx_owner_ids_resume(e.handle), "ifx_owner_ids_resume")
+
+
+def _view_out_args(rgba, ids, device):
+    """(out_rgba, out_ids, d_out_rgba, d_out_ids) of the render_view entries for two numpy arrays or two torch tensors; None: that image is not wanted"""
+    if device:
+        return (None, None, C.c_void_p(rgba.data_ptr()) if rgba is not None else None, C.c_void_p(ids.data_ptr()) if ids is not None else None)
+    return (rgba.ctypes.data_as(C.c_void_p) if rgba is not None else None, ids.ctypes.data_as(C.c_void_p) if ids is not None else None, None, None)
+
+
+def emulate_owner_render_view(efs, mvp, size, device=False, want_rgba=True, want_ids=True, exchanges=None, **kw):
+    """OwnerShardedElasticFusion.render_view on the handles of emulate_owner_ranks, in lock step, the exchanges done by hand (`kw`: the arguments of
+    ElasticFusion.render_view).  Returns one (rgba, ids) per rank, None for an image that is not wanted; `exchanges` (a list) receives the number of the exchange
+    points the call went through."""
+    from . import view_params
+
+    p = view_params(mvp, size, **kw)
+    outs = []
+    for e in efs:
+        rgba, ids = e._view_outputs(size, device)
+        outs.append((rgba if want_rgba else None, ids if want_ids else None))
+    rs = [e._chk(e.L.ifx_owner_render_view_begin(e.handle, C.byref(p), int(want_rgba), int(want_ids)), "ifx_owner_render_view_begin") for e in efs]
+    phase = 400
+    while rs[0] == 1:
+        assert all(r == 1 for r in rs), "the ranks disagree about the render's exchange points"
+        specs = [_exchange_spec(e, phase) for e in efs]
+        assert all(len(sp) == 1 for sp in specs) and not any(_exchange_spec(e, 801 - phase) for e in efs), "one buffer, under the pending exchange's number only"
+        _reduce_by_hand(efs, specs)
+        if exchanges is not None:
+            exchanges.append(phase)
+        rs = [e._chk(e.L.ifx_owner_render_view_resume(e.handle, *_view_out_args(*o, device)), "ifx_owner_render_view_resume") for e, o in zip(efs, outs)]
+        phase += 1
+    assert all(r == 0 for r in rs)
+    if device:
+        for e in efs:
+            e.sync()
+    return outs
 
 
 def emulate_owner_knn(efs):
