@@ -1078,6 +1078,40 @@ int ifx_owner_process_segmentation_rois(ifx_t* h, int root, int max_n, const uin
 int ifx_owner_process_segmentation_detections(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_mask_logits, const float* d_boxes,
                                               const float* d_scores, const int64_t* d_labels, const int32_t* d_count, const int32_t* d_class_map, int R, int C, int M,
                                               const ifx_mask_head_params* p, float threshold, int frame, int flags, void* stream, int32_t* out_kept);
+/* Deferred segmentation on a spatially sharded map: a slow detector's masks of frame t, applied at frame t + k to the map as it is then (the unsharded pair is
+ * ifx_segmentation_snapshot / ifx_process_segmentation_deferred*, which keep refusing a sharded handle).  Every rank makes the same calls behind the same frames.
+ *
+ * ifx_owner_segmentation_snapshot(h, flags): enqueue-only on the handle's stream.  Pins the whole replicated id image as creation numbers, the pose block, with
+ * flags bit 1 the raw rgb / depth of the frame just processed, and per pixel THIS rank's slot of the surfel as a hint (one bisection, here and in no later launch) or
+ * "another rank's".  Returns the ticket: tickets come from the handle's one counter, so ranks that make the same calls hold the same numbers.  The ticket table,
+ * option seg_snapshots, the generation that ifx_map_upload bumps, ifx_segmentation_snapshot_release and _stats are the unsharded tickets' own; on a sharded ticket
+ * _stats reports `pixels` of the whole image (equal on every rank) and `lost` = the pixels whose surfel THIS rank owned and lost (the ranks' sum is the unsharded
+ * figure).  Under option own_lazy_ids the image is completed first: in place and collectively with the library's communicator; with a caller-driven transport the
+ * call returns IFX_E_STATE and names ifx_owner_ids_begin.
+ *
+ * ifx_owner_segmentation_begin_deferred (host masks, sorted as for ifx_owner_segmentation_begin) and ifx_owner_segmentation_begin_deferred_device (image masks on
+ * rank root's GPU, or on every rank's with root = -1; arguments as ifx_owner_segmentation_begin_device without rgb / depth: the superpixels are cut from the
+ * ticket's frame, read in place on the device) return 1 / 0 like the ordinary begin forms and go on through ifx_owner_segmentation_resume and
+ * ifx_owner_exchange(h, 200, ...): the record (root >= 0), the boxes, the model depth, the eviction statistics, the boxes again -- never the id image's keys.
+ * ifx_owner_process_segmentation_deferred[_device] are the one-call forms on the library's communicator (flags bit 0 there: the kNN smoothing after the call).
+ * Per rank the semantics are the unsharded deferred call's: a pixel keeps its surfel on the owning rank if the surfel is still stored, alive, and not today's
+ * "surfel 0" -- the lowest live creation number of any rank, the word the last frame's id resolve used (creation number 0 under own_first_live = 0); every other
+ * pixel reads "no surfel of this rank".  The camera centre of the model depth is the ticket's pose.  A call that completes releases its ticket on every rank; so
+ * do n == 0 and a call on an empty shard.  With no frame between snapshot and call the result is the ordinary sharded call's bit for bit; at any lag it is the
+ * unsharded deferred call's (maps merged by creation number).
+ *
+ * Refusals (nothing enqueued, the handle stays usable, ifx_last_error starts with the entry's name): IFX_E_STATE for an unsharded handle, more than one camera
+ * context, a segmentation call in flight, no frame processed yet, a ticket older than an ifx_map_upload, flags bit 1 on a ticket taken without its frame;
+ * IFX_E_INVALID for an unknown or released ticket, flags bit 0 on a begin form, and whatever the ordinary form refuses in its arguments; IFX_E_CAPACITY for one
+ * ticket more than seg_snapshots allows.  A refused or failed call keeps its ticket.
+ * Not offered (yet): the ROI, detections and unmolded forms of the deferred call, and camera contexts. */
+int ifx_owner_segmentation_snapshot(ifx_t* h, int flags);
+int ifx_owner_segmentation_begin_deferred(ifx_t* h, int ticket, const uint8_t* masks, const int32_t* class_ids, int nm, int frame, int flags);
+int ifx_owner_segmentation_begin_deferred_device(ifx_t* h, int ticket, int root, int max_n, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids,
+                                                 int n, int frame, int flags, void* stream);
+int ifx_owner_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks, const int32_t* class_ids, int nm, int frame, int flags);
+int ifx_owner_process_segmentation_deferred_device(ifx_t* h, int ticket, int root, int max_n, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids,
+                                                   int n, int frame, int flags, void* stream);
 /* bestIDInEachSurfel (IF/Core/InstanceFusionCuda.cu:1158-1200) for the live surfels, map order. */
 int ifx_labels(ifx_t* h, int32_t* out, int max_n);
 /* InstanceFusion::renderProjectMap (IF/Core/InstanceFusion.cpp:1232-1252, renderProjectFrameKernel IF/Core/InstanceFusionCuda.cu:1432-1498): the

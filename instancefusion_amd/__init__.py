@@ -144,6 +144,11 @@ _SIGS = {
     "ifx_owner_process_frame": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "ifx_owner_predict": (C.c_int, [_P]),
     "ifx_owner_process_segmentation": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "ifx_owner_segmentation_snapshot": (C.c_int, [_P, C.c_int]),
+    "ifx_owner_segmentation_begin_deferred": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "ifx_owner_segmentation_begin_deferred_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "ifx_owner_process_segmentation_deferred": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "ifx_owner_process_segmentation_deferred_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_float, _P, C.c_int, C.c_int, C.c_int, _P]),
     "ifx_owner_knn_vote_colour": (C.c_int, [_P]),
     "ifx_owner_exchange_stats": (C.c_int, [_P, _P, C.c_int]),
     "ifx_owner_comm_ranks": (C.c_int, [_P]),
@@ -307,7 +312,7 @@ def _ptr(a):
 
 
 _IMG_SPECS = {
-    "ids_after": (np.int32, 1), "ids_tmp": (np.int32, 1), "index": (np.uint32, 1), "index_vc": (np.float32, 4),
+    "ids_after": (np.int32, 1), "ids_tmp": (np.int32, 1), "snap_ids": (np.int32, 1), "index": (np.uint32, 1), "index_vc": (np.float32, 4),
     "index_ct": (np.float32, 4), "index_nr": (np.float32, 4), "pred_vertex": (np.float32, 4),
     "pred_normal": (np.float32, 4), "pred_image": (np.uint8, 4), "pred_inst": (np.uint8, 4), "pred_time": (np.uint16, 1),
     "fill_vertex": (np.float32, 4), "fill_normal": (np.float32, 4), "fill_image": (np.uint8, 4),

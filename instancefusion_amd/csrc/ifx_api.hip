@@ -1850,6 +1850,7 @@ extern "C" int ifx_image_download(ifx_t* h, const char* name, void* out, int64_t
     if (h->stream_c) HIPCHK(h, hipStreamSynchronize(h->stream_c));
     if (s == "ids_after") { const int r_ = ifx_ids_ensure(h); if (r_) return r_; src = h->ids_after; bytes = P * 4; }
     else if (s == "ids_tmp") { src = h->ids_tmp; bytes = P * 4; }
+    else if (s == "snap_ids" && h->d_snap_ids) { src = h->d_snap_ids; bytes = P * 4; }   // the image the last deferred call read (slots; on a sharded map this rank's slot + 1)
     else if (s == "index") { src = h->index_id; bytes = P * 4; }
     else if (s == "index_vc") { src = h->index_vc; bytes = P * 16; }
     else if (s == "index_ct") { src = h->index_ct; bytes = P * 16; }

@@ -335,7 +335,7 @@ static int comm_seg_run(ifx* h, int r, int flags)
 {
     while (r == 1) {
         r = ifx_comm_exchange(h, 200);
-        if (r) { h->oseg_state = 0; h->oseg_pending = 0; return r; }   // a failed call is over: the next one starts from scratch
+        if (r) { h->oseg_state = 0; h->oseg_pending = 0; h->oseg_ticket = -1; return r; }   // a failed call is over: the next one starts from scratch
         r = ifx_owner_segmentation_resume(h);
     }
     if (r) return r;
@@ -368,6 +368,22 @@ extern "C" int ifx_owner_process_segmentation_device(ifx_t* h, int root, int max
     const int r = comm_seg_ready(h, "ifx_owner_process_segmentation_device");
     if (r) return r;
     return comm_seg_run(h, ifx_owner_segmentation_begin_device(h, root, max_n, rgb, depth, d_masks, mask_format, threshold, d_class_ids, n, frame, flags & ~1, stream), flags);
+}
+// The deferred forms (ifx_owner_segmentation_begin_deferred[_device]) in one call each; a call that completes releases its ticket on every rank.
+extern "C" int ifx_owner_process_segmentation_deferred(ifx_t* h, int ticket, const uint8_t* masks, const int32_t* class_ids, int nm, int frame, int flags)
+{
+    if (!h) return IFX_E_INVALID;
+    const int r = comm_seg_ready(h, "ifx_owner_process_segmentation_deferred");
+    if (r) return r;
+    return comm_seg_run(h, ifx_owner_segmentation_begin_deferred(h, ticket, masks, class_ids, nm, frame, flags & ~1), flags);
+}
+extern "C" int ifx_owner_process_segmentation_deferred_device(ifx_t* h, int ticket, int root, int max_n, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids,
+                                                              int n, int frame, int flags, void* stream)
+{
+    if (!h) return IFX_E_INVALID;
+    const int r = comm_seg_ready(h, "ifx_owner_process_segmentation_deferred_device");
+    if (r) return r;
+    return comm_seg_run(h, ifx_owner_segmentation_begin_deferred_device(h, ticket, root, max_n, d_masks, mask_format, threshold, d_class_ids, n, frame, flags & ~1, stream), flags);
 }
 extern "C" int ifx_owner_process_segmentation_rois(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const float* d_roi_masks, int roi_size, const float* d_boxes,
                                                    float threshold, const int32_t* d_class_ids, int n, int frame, int flags, void* stream)

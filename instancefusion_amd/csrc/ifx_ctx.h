@@ -125,6 +125,19 @@ __device__ __forceinline__ int idmap_slot(const IdMap& m, int count, int id)
     }
     return -1;
 }
+// A third coding, which only a deferred call on a sharded map selects (ifx_instance.hip, k_seg_translate<1>): the image holds THIS rank's slot + 1, found once per
+// call instead of once per pixel and launch.  Slot 0 of a shard is an ordinary surfel (the identity coding's "id 0 = none" would lose it), so 0 stays "no surfel of
+// this rank" and slot s travels as s + 1.  The kernels of the sharded call body read ids through segmap_slot; everything else keeps idmap_slot.
+#define IDMAP_SLOTS (-1)
+__device__ __forceinline__ int segmap_slot(const IdMap& m, int count, int id)
+{
+    if (m.own_n == IDMAP_SLOTS) return (id > 0 && id <= count) ? id - 1 : -1;
+    return idmap_slot(m, count, id);
+}
+// What a segmentation call reads of "the frame it belongs to": the id image and its coding, the pose whose translation is the camera centre of the model-depth
+// kernels, and the frame the superpixels are cut from.  The ordinary entries fill it with the handle's current id image, the state's pose and no frame pointers (the
+// caller's host images, or the resident frame slot); the deferred entries with the snapshot's translated id image, pinned pose and pinned frame (seg_view_snapshot).
+struct SegView { const int32_t* ids; const float* cam; const uint8_t* d_rgb; const uint16_t* d_depth; IdMap im; };
 
 struct FrameResult {   // copied to pinned host memory at the end of every frame
     float pose[16];
@@ -393,6 +406,8 @@ struct ifx {
     std::vector<uint8_t> oseg_unavail;
     std::vector<int> oseg_cmp, oseg_bbox, oseg_class;
     hipEvent_t oseg_ev = nullptr;
+    SegView oseg_view = {};            // what the call in flight reads: the current id image (creation numbers), or a ticket's image in this rank's slots (ifx_owner_segmentation_begin_deferred*)
+    int oseg_ticket = -1;              // the ticket the call in flight releases when it completes; -1: an ordinary call
     // its device forms (ifx_owner_segmentation_begin_device / _rois / _detections): the record the root's rank packs and one broadcast carries (layout: include/ifx_c_api.h),
     // one allocation grown on demand, and what the first resume checks the record's header against
     int32_t* oseg_rec = nullptr;

@@ -496,7 +496,7 @@ __global__ void __launch_bounds__(32 * PB_ROWS) k_project_bbox(const DevState* _
     const bool inside = x < w && y < h;
     const int P = w * h, k = inside ? y * w + x : 0;
     const int gid = inside ? ids[k] : 0;
-    const int id = idmap_slot(im, st->count, gid);   // (sharded map: the pixels whose surfel another rank owns extend that rank's partial boxes)
+    const int id = MODE == 0 ? segmap_slot(im, st->count, gid) : idmap_slot(im, st->count, gid);   // (MODE 0 is the sharded call's: its deferred form hands it slots; sharded map: the pixels whose surfel another rank owns extend that rank's partial boxes)
     bool has = inside && id >= 0;
     int maxNum = 0, maxID = -1, first = 0;
     if ((MODE == 1 || MODE == 3) && pdm && inside) {   // getProjectDepthMapKernel (k_project_depth) on the way
@@ -569,7 +569,7 @@ __global__ void k_project_depth(const DevState* __restrict__ st, const int32_t* 
 {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
-    const int id = idmap_slot(im, st->count, ids[k]);
+    const int id = segmap_slot(im, st->count, ids[k]);
     uint16_t o = 0;
     if (id >= 0) {
         float4 p = pc[id];
@@ -589,7 +589,7 @@ __global__ void k_vote_update(const DevState* __restrict__ st, const int32_t* __
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= P) return;
     if (!(mask[k] > 0)) return;
-    const int id = idmap_slot(im, st->count, ids[k]);
+    const int id = segmap_slot(im, st->count, ids[k]);
     if (id < 0) return;
     int fi = instanceID / 2, p = instanceID % 2;
     // planar float4 store: float fi of surfel id lives in plane fi/4, component fi%4
@@ -1442,22 +1442,19 @@ static int first_not_used(ifx* h)
     return -1;
 }
 
-// What a segmentation call reads of "the frame it belongs to": the id image, the pose whose translation is the camera centre of the model-depth kernels, and the
-// frame the superpixels are cut from.  The ordinary entries fill it with the handle's current id image, the state's pose and no frame pointers (the caller's host
-// images, or the resident frame slot); the deferred entry with the snapshot's translated id image, pinned pose and pinned frame (seg_view_snapshot).
-struct SegView { const int32_t* ids; const float* cam; const uint8_t* d_rgb; const uint16_t* d_depth; };
-static SegView seg_view_current(const ifx* h) { return SegView{h->ids_after, h->d_state->pose, nullptr, nullptr}; }
+// (SegView: ifx_ctx.h)
+static SegView seg_view_current(const ifx* h) { return SegView{h->ids_after, h->d_state->pose, nullptr, nullptr, ifx_idmap(h)}; }
 
-// the boxes of the projected instances and of the nm masks under the id image `ids` (the host-driven loop and the owners' call read them back differently)
-static void launch_bboxes(ifx* h, const int32_t* ids, int nm)
+// the boxes of the projected instances and of the nm masks under the view's id image (the host-driven loop and the owners' call read them back differently)
+static void launch_bboxes(ifx* h, const SegView& v, int nm)
 {
     LAUNCH(h, "init_bbox", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_init_bbox, h->d_bbox, NI + nm, h->w, h->h);
-    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
-           h->d_bbox, ifx_idmap(h));
+    LAUNCH(h, "project_bbox", dim3(cdiv(h->w, 32), cdiv(h->h, PB_ROWS)), dim3(32, PB_ROWS), k_project_bbox<0>, h->d_state, v.ids, (const float4*)h->votes, h->cap, h->d_masks, nm, h->w, h->h,
+           h->d_bbox, v.im);
 }
 static int run_bboxes(ifx* h, const SegView& v, int nm, std::vector<int>& bbox)
 {
-    launch_bboxes(h, v.ids, nm);
+    launch_bboxes(h, v, nm);
     bbox.resize((size_t)(NI + nm) * 4);
     HIPCHK(h, hipMemcpyAsync(bbox.data(), h->d_bbox, bbox.size() * 4, hipMemcpyDeviceToHost, h->cur));
     HIPCHK(h, hipStreamSynchronize(h->cur));
@@ -1503,10 +1500,26 @@ __global__ void k_bbox_flip(int* __restrict__ bbox, int nboxes)
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k < nboxes * 4 && (k & 1)) bbox[k] = -bbox[k];   // {minX, maxX, minY, maxY}: entries 1 and 3 are maxima
 }
+struct SegSnap;   // a pinned frame of ifx_segmentation_snapshot / ifx_owner_segmentation_snapshot (below): null for the ordinary entries
+static int seg_view_snapshot(ifx* h, SegSnap* q, SegView* v);
+extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
+// what the call in flight reads, settled once at its begin: the current id image, or (deferred call) the ticket's image in this rank's slots, pinned pose and frame
+static int oseg_set_view(ifx* h, SegSnap* snap, int ticket)
+{
+    h->oseg_view = seg_view_current(h);
+    h->oseg_ticket = snap ? ticket : -1;
+    return snap ? seg_view_snapshot(h, snap, &h->oseg_view) : IFX_OK;
+}
+// a call that completed releases its ticket, on every rank alike (so do n == 0 and an empty shard; a call that failed keeps it)
+static void oseg_release_ticket(ifx* h)
+{
+    if (h->oseg_ticket >= 0) ifx_segmentation_snapshot_release(h, h->oseg_ticket);
+    h->oseg_ticket = -1;
+}
 static int oseg_launch_bboxes(ifx* h)
 {
     const int nm = h->oseg_nm;
-    launch_bboxes(h, h->ids_after, nm);
+    launch_bboxes(h, h->oseg_view, nm);
     LAUNCH(h, "bbox_flip", dim3(cdiv((NI + nm) * 4, 256)), dim3(256), k_bbox_flip, h->d_bbox, NI + nm);
     h->oseg_pending = 1;
     return 1;
@@ -1548,7 +1561,7 @@ static int oseg_mask_loop(ifx* h, bool after_eviction)
         }
         for (int q = 0; q < NI; q++)
             if (cmp[q + m * NI] == 1)
-                LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update, h->d_state, h->ids_after, h->d_masks + (size_t)m * P, P, h->cap, q, m + 1, h->votes, ifx_idmap(h));
+                LAUNCH(h, "vote_update", dim3(cdiv(P, 256)), dim3(256), k_vote_update, h->d_state, h->oseg_view.ids, h->d_masks + (size_t)m * P, P, h->cap, q, m + 1, h->votes, h->oseg_view.im);
     }
     // step 4: labels of the owned surfels
     LAUNCH(h, "count_colour", dim3(2048), dim3(256), k_count_colour, h->d_state, (const float4*)h->votes, h->cap, (const float2*)h->tm, (float2*)h->col, h->d_inst_color, h->labels, (const int*)nullptr);
@@ -1558,18 +1571,53 @@ static int oseg_mask_loop(ifx* h, bool after_eviction)
     h->oseg_ev = nullptr;
     HIPCHK(h, hipStreamSynchronize(h->cur));
     h->oseg_state = 0; h->oseg_pending = 0;
+    oseg_release_ticket(h);
     return 0;
 }
 // behind the masks and their refinement, the exchange points every form of the call shares
 static int oseg_first_exchange(ifx* h)
 {
-    int r = ifx_owner_ids_begin_impl(h);   // option own_lazy_ids: the frame exchanged the sampled lattice only -- the exchange point in front of the boxes is the whole id image's keys
+    // option own_lazy_ids: the frame exchanged the sampled lattice only -- the exchange point in front of the boxes is the whole id image's keys (a deferred call never
+    // comes by it: its ticket pinned a whole image)
+    int r = h->oseg_ticket >= 0 ? 0 : ifx_owner_ids_begin_impl(h);
     if (r == 1) { h->oseg_state = 6; h->oseg_pending = 0; return 1; }
     if (r < 0) { h->oseg_state = 0; h->oseg_pending = 0; return r; }
     h->oseg_state = 1;
     r = oseg_launch_bboxes(h);
     if (r < 0) { h->oseg_state = 0; h->oseg_pending = 0; }
     return r;
+}
+// the host-mask form behind its checks; snap: the deferred entry's ticket (ifx_owner_segmentation_begin_deferred), null for the ordinary one
+static int oseg_begin_host(ifx* h, SegSnap* snap, int ticket, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
+{
+    ifx_vlist_reap(h);
+    h->seg_counts_valid = 0;
+    h->oseg_ev = ifx_event_get(h);
+    hipEventRecord(h->oseg_ev, h->cur);
+    HIPCHK(h, hipStreamSynchronize(h->cur));
+    if (nm == 0) {   // (an empty shard still takes part: the other ranks wait for its boxes)
+        h->event_pool.push_back(h->oseg_ev); h->oseg_ev = nullptr;
+        if (snap) ifx_segmentation_snapshot_release(h, ticket);
+        return 0;
+    }
+    const int P = h->P;
+    const size_t mbytes = (size_t)nm * P;
+    int r = ifx_ensure_masks(h, mbytes);
+    if (r) return r;
+    if ((r = oseg_set_view(h, snap, ticket))) return r;
+    h->oseg_nm = nm; h->oseg_m = 0; h->oseg_flags = flags;
+    h->oseg_unavail.assign(nm, 0);
+    h->oseg_cmp.assign((size_t)nm * NI, 0);
+    h->oseg_class.assign(class_ids, class_ids + nm);
+    HIPCHK(h, hipMemcpyAsync(h->d_masks_ori, masks_in, mbytes, hipMemcpyHostToDevice, h->cur));
+    HIPCHK(h, hipMemcpyAsync(h->d_masks, h->d_masks_ori, mbytes, hipMemcpyDeviceToDevice, h->cur));
+    LAUNCH(h, "mask_clean_overlap", dim3(cdiv(P, 256)), dim3(256), k_mask_clean_overlap, h->d_masks, nm, P);
+    if (flags & 2) {   // (a deferred call cuts the superpixels from the ticket's frame, read in place)
+        r = snap ? ifx_superpixel_begin_device(h, h->oseg_view.d_rgb, h->oseg_view.d_depth) : ifx_superpixel_refine(h, rgb, depth, nm, frame);
+        if (!r && snap) r = ifx_superpixel_filter(h, nm);
+        if (r) return r;
+    }
+    return oseg_first_exchange(h);
 }
 extern "C" int ifx_owner_segmentation_begin(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
 {
@@ -1578,28 +1626,7 @@ extern "C" int ifx_owner_segmentation_begin(ifx_t* h, const uint8_t* rgb, const 
     if (flags & 1) { h->err = "kNN smoothing is not offered on a sharded map (it needs every rank's positions)"; return IFX_E_INVALID; }
     if (h->oseg_state) { h->err = "a segmentation call is already in flight"; return IFX_E_STATE; }
     if (nm > 256) { h->err = "too many masks"; return IFX_E_INVALID; }
-    ifx_vlist_reap(h);
-    h->seg_counts_valid = 0;
-    h->oseg_ev = ifx_event_get(h);
-    hipEventRecord(h->oseg_ev, h->cur);
-    HIPCHK(h, hipStreamSynchronize(h->cur));
-    if (nm == 0) { h->event_pool.push_back(h->oseg_ev); h->oseg_ev = nullptr; return 0; }   // (an empty shard still takes part: the other ranks wait for its boxes)
-    const int P = h->P;
-    const size_t mbytes = (size_t)nm * P;
-    int r = ifx_ensure_masks(h, mbytes);
-    if (r) return r;
-    h->oseg_nm = nm; h->oseg_m = 0; h->oseg_flags = flags;
-    h->oseg_unavail.assign(nm, 0);
-    h->oseg_cmp.assign((size_t)nm * NI, 0);
-    h->oseg_class.assign(class_ids, class_ids + nm);
-    HIPCHK(h, hipMemcpyAsync(h->d_masks_ori, masks_in, mbytes, hipMemcpyHostToDevice, h->cur));
-    HIPCHK(h, hipMemcpyAsync(h->d_masks, h->d_masks_ori, mbytes, hipMemcpyDeviceToDevice, h->cur));
-    LAUNCH(h, "mask_clean_overlap", dim3(cdiv(P, 256)), dim3(256), k_mask_clean_overlap, h->d_masks, nm, P);
-    if (flags & 2) {
-        r = ifx_superpixel_refine(h, rgb, depth, nm, frame);
-        if (r) return r;
-    }
-    return oseg_first_exchange(h);
+    return oseg_begin_host(h, nullptr, -1, rgb, depth, masks_in, class_ids, nm, frame, flags);
 }
 static int oseg_resume(ifx* h);
 static int oseg_resume_record(ifx* h);
@@ -1608,8 +1635,8 @@ extern "C" int ifx_owner_segmentation_resume(ifx_t* h)
     if (!h) return IFX_E_INVALID;
     if (!h->oseg_state) { h->err = "no segmentation call in flight"; return IFX_E_STATE; }
     const int r = oseg_resume(h);
-    if (r < 0) {   // a failed call is over: the next _begin starts from scratch
-        h->oseg_state = 0; h->oseg_pending = 0;
+    if (r < 0) {   // a failed call is over: the next _begin starts from scratch (a deferred call's ticket stays in use)
+        h->oseg_state = 0; h->oseg_pending = 0; h->oseg_ticket = -1;
         if (h->oseg_ev) { h->event_pool.push_back(h->oseg_ev); h->oseg_ev = nullptr; }
     }
     return r;
@@ -1627,7 +1654,7 @@ static int oseg_resume(ifx* h)
         return oseg_launch_bboxes(h);
     case 1:   // boxes merged -> compare map; model depth of the owned surfels
         if ((r = oseg_read_bboxes(h))) return r;
-        LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, h->ids_after, (const float4*)h->pc, P, 1186, h->d_pdm, ifx_idmap(h), (const float*)h->d_state->pose);
+        LAUNCH(h, "project_depth", dim3(cdiv(P, 256)), dim3(256), k_project_depth, h->d_state, h->oseg_view.ids, (const float4*)h->pc, P, 1186, h->d_pdm, h->oseg_view.im, h->oseg_view.cam);
         h->oseg_state = 2; h->oseg_pending = 2;
         return 1;
     case 2:   // model depth merged -> flood fill (replicated), then the masks
@@ -1669,7 +1696,6 @@ static MaskSource src_rois(const float* d_rois, int M, const float* d_boxes, flo
 {
     return MaskSource{n, MaskSource::ROIS, DevMasks{d_rois, IFX_MASK_F32, thr, d_cls, nullptr, d_boxes, M}, nullptr, nullptr, nullptr, nullptr};
 }
-struct SegSnap;   // a pinned frame of ifx_segmentation_snapshot (below): null for the ordinary entries
 static int process_segmentation_host(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags);
 static int process_segmentation_device(ifx_t* h, const uint8_t* rgb, const uint16_t* depth, const uint8_t* masks_in, const int32_t* class_ids, const DevMasks* dm, int nm, int frame, int flags,
                                        SegSnap* snap);
@@ -1677,7 +1703,6 @@ static int process_segmentation(ifx_t* h, const uint8_t* rgb, const uint16_t* de
                                 SegSnap* snap = nullptr);
 static int seg_ingest_device(ifx* h, const DevMasks* dm, int nm, int* cls_out, uint8_t* unavail);
 static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
-extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket);
 
 // ---- the one body behind the segmentation entries.  Its steps keep this order (the order decides which error a doubly-bad call reports): the arguments of the
 // source's form, the refusal by mode, the producer's event, the call, the ticket's release.
@@ -1998,6 +2023,8 @@ static int oseg_end(ifx* h, int r)
 {
     if (h->oseg_ev) { h->event_pool.push_back(h->oseg_ev); h->oseg_ev = nullptr; }
     h->oseg_state = 0; h->oseg_pending = 0;
+    if (r == 0) oseg_release_ticket(h);   // (no masks: the call is complete)
+    h->oseg_ticket = -1;
     return r;
 }
 // n masks are coming: the buffers and the host state of a call, as ifx_owner_segmentation_begin sets them
@@ -2022,8 +2049,9 @@ static int oseg_read_classes(ifx* h)
     return IFX_OK;
 }
 // s: the tensors of the reading rank (root = -1: every rank; otherwise rank root) -- ignored on the others; form 1 image masks, 2 ROI masks (M = roi_size)
+// snap: the deferred entry's ticket (the superpixels are then cut from its frame, read in place: rgb / depth are null), null for the ordinary ones
 static int oseg_begin_dev(ifx* h, const char* who, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, MaskSource s, int n_hdr, int form, int M, float thr, int frame,
-                          int flags, void* stream)
+                          int flags, void* stream, SegSnap* snap = nullptr, int ticket = -1)
 {
     const int P = h->P, n = s.n;
     const bool reader = root < 0 || root == h->cfg.rank;
@@ -2034,6 +2062,8 @@ static int oseg_begin_dev(ifx* h, const char* who, int root, int max_n, const ui
     HIPCHK(h, hipStreamSynchronize(h->cur));
     h->oseg_flags = flags; h->oseg_root = root; h->oseg_form = form; h->oseg_M = form == 2 ? M : 0; h->oseg_maxn = max_n; h->oseg_thr = thr; h->oseg_who = who;
     int r;
+    if ((r = oseg_set_view(h, snap, ticket))) { h->oseg_ticket = -1; return oseg_end(h, r); }
+    const SegView& v = h->oseg_view;
     if (root < 0) {
         if (n == 0) return oseg_end(h, 0);
         if ((r = oseg_prepare(h, n))) return oseg_end(h, r);
@@ -2042,7 +2072,8 @@ static int oseg_begin_dev(ifx* h, const char* who, int root, int max_n, const ui
             if ((r = seg_record_ready(h, who, &s.dm, ready, stream)) || (r = seg_ingest_device(h, &s.dm, n, nullptr, nullptr))) return oseg_end(h, r);
         }
         if ((r = oseg_read_classes(h))) return oseg_end(h, r);
-        if ((flags & 2) && (r = ifx_superpixel_refine(h, rgb, depth, n, frame))) return oseg_end(h, r);
+        if ((flags & 2) && (r = snap ? ifx_superpixel_begin_device(h, v.d_rgb, v.d_depth) : ifx_superpixel_refine(h, rgb, depth, n, frame))) return oseg_end(h, r);
+        if ((flags & 2) && snap && (r = ifx_superpixel_filter(h, n))) return oseg_end(h, r);
         r = oseg_first_exchange(h);
         return r < 0 ? oseg_end(h, r) : r;
     }
@@ -2077,7 +2108,7 @@ static int oseg_begin_dev(ifx* h, const char* who, int root, int max_n, const ui
             }
         }
     }
-    if ((flags & 2) && (r = ifx_superpixel_begin(h, rgb, depth))) return oseg_end(h, r);   // (the frame's superpixels need no mask: the host pointers are done with when this returns)
+    if ((flags & 2) && (r = snap ? ifx_superpixel_begin_device(h, v.d_rgb, v.d_depth) : ifx_superpixel_begin(h, rgb, depth))) return oseg_end(h, r);   // (the frame's superpixels need no mask: the host pointers are done with when this returns)
     h->oseg_state = 7; h->oseg_pending = 4;
     return 1;
 }
@@ -2130,18 +2161,22 @@ static int oseg_refuse(ifx* h, const char* who, int root, int max_n, int flags)
     if (bad) { h->err = std::string(who) + bad; return code; }
     return IFX_OK;
 }
-static int oseg_entry(ifx* h, const char* who, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, MaskSource s, float thr, int frame, int flags, void* stream)
+static int oseg_snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out);
+// ticket: the deferred entry's (null for the ordinary ones)
+static int oseg_entry(ifx* h, const char* who, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, MaskSource s, float thr, int frame, int flags, void* stream,
+                      const int* ticket = nullptr)
 {
     if (!h) return IFX_E_INVALID;
+    SegSnap* snap = nullptr;
     int r = oseg_refuse(h, who, root, max_n, flags);
-    if (r) return r;
+    if (r || (ticket && (r = oseg_snap_for_call(h, who, *ticket, flags, &snap)))) return r;
     const bool rois = s.kind == MaskSource::ROIS;
     if (rois && (s.dm.roi < 1 || s.dm.roi > ROI_M_MAX)) { h->err = std::string(who) + ": roi_size must be 1 .. 64"; return IFX_E_INVALID; }   // (every rank: the record's size depends on it)
     if (root < 0 || root == h->cfg.rank) {
         if ((r = seg_check_args(h, who, s))) return r;
         if (s.n > max_n) { h->err = std::string(who) + ": n is larger than max_n"; return IFX_E_INVALID; }
     } else s.n = 0;
-    return oseg_begin_dev(h, who, root, max_n, rgb, depth, s, s.n, rois ? 2 : 1, s.dm.roi, thr, frame, flags, stream);
+    return oseg_begin_dev(h, who, root, max_n, rgb, depth, s, s.n, rois ? 2 : 1, s.dm.roi, thr, frame, flags, stream, snap, ticket ? *ticket : -1);
 }
 // A call in flight ends here on this rank: what a rank does whose peers' call is over (their begin refused, their resume failed) while it waits at an exchange point
 extern "C" int ifx_owner_segmentation_abort(ifx_t* h)
@@ -2151,6 +2186,7 @@ extern "C" int ifx_owner_segmentation_abort(ifx_t* h)
     if (!h->oseg_state) return IFX_OK;
     HIPCHK(h, hipStreamSynchronize(h->cur));
     h->labels_stale_all = 1;   // (votes may have been updated without the label scan that follows them)
+    h->oseg_ticket = -1;       // (a deferred call that did not complete keeps its ticket)
     return oseg_end(h, IFX_OK);
 }
 extern "C" int ifx_owner_segmentation_begin_device(ifx_t* h, int root, int max_n, const uint8_t* rgb, const uint16_t* depth, const void* d_masks, int mask_format, float threshold,
@@ -2426,14 +2462,22 @@ static int seg_ensure_ctl(ifx* h, size_t mask_bytes)
 struct SnapHdr { float pose[16]; int tick, pad[15]; };   // what one lane copies out of the state: the host reads nothing at snapshot time
 #define SNAP_NONE 0xFFFFFFFFu
 // id -> {creation number, slot as a hint}: 8 bytes per pixel.  have[block]: pixels of the block that name a surfel (ifx_segmentation_snapshot_stats).
+// OWN (a shard of a spatially sharded map): the replicated id image holds creation numbers already, and every rank pins the WHOLE image; the hint is this rank's own
+// slot -- the one bisection a pixel ever costs, here and not in every later launch -- or SNAP_NONE where another rank owns the surfel.  have counts the whole image,
+// the same on every rank.
+template <int OWN>
 __global__ void __launch_bounds__(256) k_seg_snapshot(const DevState* __restrict__ st, const int32_t* __restrict__ ids, const uint32_t* __restrict__ seq, int P, int tick,
                                                       uint2* __restrict__ px, SnapHdr* __restrict__ hdr, int* __restrict__ have)
 {
     const int count = st->count;   // launch-uniform: read once, before the first store
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     const int id = k < P ? ids[k] : 0;
-    const bool has = id > 0 && id < count;
-    if (k < P) px[k] = has ? make_uint2(seq[id], (unsigned int)id) : make_uint2(0u, SNAP_NONE);
+    const bool has = OWN ? id != 0 : (id > 0 && id < count);
+    if (OWN) {
+        IdMap im; im.seq = seq; im.own_n = 1;
+        const int mine = has ? idmap_slot(im, count, id) : -1;
+        if (k < P) px[k] = make_uint2((unsigned int)id, mine >= 0 ? (unsigned int)mine : SNAP_NONE);
+    } else if (k < P) px[k] = has ? make_uint2(seq[id], (unsigned int)id) : make_uint2(0u, SNAP_NONE);
     __shared__ int s_n[4];
     const unsigned long long bal = __ballot(has);
     if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(bal);
@@ -2449,10 +2493,16 @@ __global__ void __launch_bounds__(256) k_seg_snapshot(const DevState* __restrict
 // otherwise a gallop downwards with doubling steps brackets the number and a bisection of the bracket finds it (a full bisection of 5 M slots is 23 dependent loads
 // per pixel: DESIGN.md section 7 has what that costs).  A pixel keeps its surfel if it is still in the store, alive, and not today's "surfel 0" (first_live: never
 // voted for); everything else reads 0 = no surfel.  lost[block]: pixels of the block that named a surfel and lost it.
+// OWN (a shard): only the pixels with a hint -- the surfels this rank owned at the snapshot; ownership never changes -- are probed, the same way.  "Surfel 0" is a
+// creation number there, the lowest live one of any rank (flw: the word the last frame's id resolve used, ifx_map.hip FIRST_LIVE; null under own_first_live = 0:
+// creation number 0, which no id image names), and the image is written as slot + 1 (IDMAP_SLOTS: slot 0 of a shard is an ordinary surfel), 0 = no surfel of this
+// rank.  lost counts the pixels whose surfel THIS rank owned and lost.
+template <int OWN>
 __global__ void __launch_bounds__(256) k_seg_translate(const DevState* __restrict__ st, const uint2* __restrict__ px, const uint32_t* __restrict__ seq, const float2* __restrict__ tm, int P,
-                                                       int32_t* __restrict__ out, int* __restrict__ lost)
+                                                       int32_t* __restrict__ out, int* __restrict__ lost, const unsigned int* __restrict__ flw = nullptr)
 {
-    const int count = st->count, fl = st->first_live;   // launch-uniform words: read once, before the first store ("Uniform loads")
+    const int count = st->count;   // launch-uniform words: read once, before the first store ("Uniform loads")
+    const unsigned int fl = OWN ? (flw ? *flw : 0u) : (unsigned int)st->first_live;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     int slot = 0;
     bool had = false;
@@ -2479,7 +2529,8 @@ __global__ void __launch_bounds__(256) k_seg_translate(const DevState* __restric
                     }
                 }
             }   // (v < want: every slot up to j carries a smaller number and the surfel cannot sit above its old slot -- compacted away)
-            if (found > 0 && found != fl && tm[found].y > DEAD_TIME) slot = found;
+            if (OWN) { if (found >= 0 && want != fl && tm[found].y > DEAD_TIME) slot = found + 1; }
+            else if (found > 0 && found != (int)fl && tm[found].y > DEAD_TIME) slot = found;
         }
         out[k] = slot;
     }
@@ -2534,19 +2585,26 @@ static int snap_refuse_mode(ifx* h, const char* who)
     if (h->cams.size() > 1) { h->err = std::string(who) + ": not offered with more than one camera context"; return IFX_E_STATE; }
     return IFX_OK;
 }
-extern "C" int ifx_segmentation_snapshot(ifx_t* h, int flags)
+// what the sharded map's snapshot and deferred entries refuse by mode (nothing enqueued, the handle stays usable)
+static int osnap_refuse_mode(ifx* h, const char* who)
 {
-    if (!h) return IFX_E_INVALID;
-    if (flags & ~2) { h->err = "ifx_segmentation_snapshot: unknown flags (bit 1: keep the frame for the superpixels)"; return IFX_E_INVALID; }
-    int r = snap_refuse_mode(h, "ifx_segmentation_snapshot");
-    if (r) return r;
-    if (h->tick < 2) { h->err = "ifx_segmentation_snapshot: no frame has been processed yet"; return IFX_E_STATE; }
-    if (snap_in_use(h) >= h->opt_seg_snapshots) { h->err = "ifx_segmentation_snapshot: every ticket is in use (option seg_snapshots)"; return IFX_E_CAPACITY; }
+    if (!h->own) { h->err = std::string(who) + ": the handle was not created for a sharded map"; return IFX_E_STATE; }
+    if (h->cams.size() > 1) { h->err = std::string(who) + ": not offered with more than one camera context"; return IFX_E_STATE; }
+    if (h->oseg_state) { h->err = std::string(who) + ": a segmentation call is already in flight"; return IFX_E_STATE; }
+    if (h->tick < 2) { h->err = std::string(who) + ": no frame has been processed yet"; return IFX_E_STATE; }
+    return IFX_OK;
+}
+// the one body of ifx_segmentation_snapshot and ifx_owner_segmentation_snapshot (own), behind the refusal by mode
+static int snap_take(ifx* h, const char* who, bool own, int flags)
+{
+    int r;
+    if (h->tick < 2) { h->err = std::string(who) + ": no frame has been processed yet"; return IFX_E_STATE; }
+    if (snap_in_use(h) >= h->opt_seg_snapshots) { h->err = std::string(who) + ": every ticket is in use (option seg_snapshots)"; return IFX_E_CAPACITY; }
     if (!h->seg_snaps) h->seg_snaps = new SegSnapSet();
     SegSnapSet* set = (SegSnapSet*)h->seg_snaps;
     SegSnap* q = nullptr;   // the free slot released longest ago: a released ticket's figures stay readable (ifx_segmentation_snapshot_stats) until its buffers are taken again
     for (SegSnap& c_ : set->s) if (!c_.in_use && (!q || c_.ticket < q->ticket)) q = &c_;
-    if (!q) { h->err = "ifx_segmentation_snapshot: every ticket is in use"; return IFX_E_CAPACITY; }
+    if (!q) { h->err = std::string(who) + ": every ticket is in use"; return IFX_E_CAPACITY; }
     const int P = h->P, nb = cdiv(P, 256);
     // (each buffer on its own: an allocation that fails leaves the slot free and the ones before it in place for the next attempt)
     if (!q->px) HIPCHK(h, hipMalloc((void**)&q->px, (size_t)P * sizeof(uint2)));
@@ -2555,8 +2613,11 @@ extern "C" int ifx_segmentation_snapshot(ifx_t* h, int flags)
     if (!q->ev) HIPCHK(h, hipEventCreateWithFlags(&q->ev, hipEventDisableTiming));
     if ((flags & 2) && !q->rgb) HIPCHK(h, hipMalloc((void**)&q->rgb, (size_t)P * 3));
     if ((flags & 2) && !q->depth) HIPCHK(h, hipMalloc((void**)&q->depth, (size_t)P * 2));
-    if ((r = ifx_ids_ensure(h))) return r;   // the whole id image, whatever id_rule / lazy_ids drew
-    LAUNCH(h, "seg_snapshot", dim3(nb), dim3(256), k_seg_snapshot, (const DevState*)h->d_state, (const int32_t*)h->ids_after, (const uint32_t*)h->seq, P, h->tick, q->px, q->hdr, q->counts);
+    // the whole id image, whatever id_rule / lazy_ids drew (a sharded map under own_lazy_ids: completed in place by the library's communicator, collectively; a
+    // caller-driven transport is told to complete it first)
+    if ((r = ifx_ids_ensure(h))) { if (own) h->err = std::string(who) + ": " + h->err; return r; }
+    if (own) LAUNCH(h, "seg_snapshot_own", dim3(nb), dim3(256), k_seg_snapshot<1>, (const DevState*)h->d_state, (const int32_t*)h->ids_after, (const uint32_t*)h->seq, P, h->tick, q->px, q->hdr, q->counts);
+    else LAUNCH(h, "seg_snapshot", dim3(nb), dim3(256), k_seg_snapshot<0>, (const DevState*)h->d_state, (const int32_t*)h->ids_after, (const uint32_t*)h->seq, P, h->tick, q->px, q->hdr, q->counts);
     if (flags & 2) {
         // the raw frame, device to device, out of its frame slot; the side stream reuses the slot two frames on and waits for the FRAME that used it only
         // (FrameSlot::released), so it is told about this reader too (enqueue_frame_side)
@@ -2570,6 +2631,20 @@ extern "C" int ifx_segmentation_snapshot(ifx_t* h, int flags)
     HIPCHK(h, hipEventRecord(q->ev, h->cur));
     q->ticket = h->snap_next_ticket++; q->in_use = 1; q->flags = flags; q->translated = 0; q->generation = h->seq_generation;
     return q->ticket;
+}
+extern "C" int ifx_segmentation_snapshot(ifx_t* h, int flags)
+{
+    if (!h) return IFX_E_INVALID;
+    if (flags & ~2) { h->err = "ifx_segmentation_snapshot: unknown flags (bit 1: keep the frame for the superpixels)"; return IFX_E_INVALID; }
+    const int r = snap_refuse_mode(h, "ifx_segmentation_snapshot");
+    return r ? r : snap_take(h, "ifx_segmentation_snapshot", false, flags);
+}
+extern "C" int ifx_owner_segmentation_snapshot(ifx_t* h, int flags)
+{
+    if (!h) return IFX_E_INVALID;
+    const int r = osnap_refuse_mode(h, "ifx_owner_segmentation_snapshot");
+    if (!r && (flags & ~2)) { h->err = "ifx_owner_segmentation_snapshot: unknown flags (bit 1: keep the frame for the superpixels)"; return IFX_E_INVALID; }
+    return r ? r : snap_take(h, "ifx_owner_segmentation_snapshot", true, flags);
 }
 extern "C" int ifx_segmentation_snapshot_release(ifx_t* h, int ticket)
 {
@@ -2601,7 +2676,13 @@ static int seg_view_snapshot(ifx* h, SegSnap* q, SegView* v)
     const int P = h->P, nb = cdiv(P, 256);
     if (!h->d_snap_ids) HIPCHK(h, hipMalloc((void**)&h->d_snap_ids, (size_t)P * 4));
     HIPCHK(h, hipStreamWaitEvent(h->cur, q->ev, 0));   // (the call may run on the third stream)
-    LAUNCH(h, "seg_translate", dim3(nb), dim3(256), k_seg_translate, (const DevState*)h->d_state, (const uint2*)q->px, (const uint32_t*)h->seq, (const float2*)h->tm, P, h->d_snap_ids, q->counts + nb);
+    if (h->own) {   // this rank's slots, coded slot + 1; "surfel 0": the word behind the last frame's [key_splat | key_ids], which that frame's id resolve used
+        LAUNCH(h, "seg_translate_own", dim3(nb), dim3(256), k_seg_translate<1>, (const DevState*)h->d_state, (const uint2*)q->px, (const uint32_t*)h->seq, (const float2*)h->tm, P, h->d_snap_ids,
+               q->counts + nb, (h->opt_own_first_live && h->gfl_splat) ? (const unsigned int*)h->gfl_splat : (const unsigned int*)nullptr);
+        v->im.seq = nullptr; v->im.own_n = IDMAP_SLOTS;
+    } else
+        LAUNCH(h, "seg_translate", dim3(nb), dim3(256), k_seg_translate<0>, (const DevState*)h->d_state, (const uint2*)q->px, (const uint32_t*)h->seq, (const float2*)h->tm, P, h->d_snap_ids,
+               q->counts + nb, (const unsigned int*)nullptr);
     q->translated = 1;
     v->ids = h->d_snap_ids; v->cam = q->hdr->pose; v->d_rgb = q->rgb; v->d_depth = q->depth;
     if (!(q->flags & 2)) { v->d_rgb = nullptr; v->d_depth = nullptr; }
@@ -2619,6 +2700,39 @@ static int snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap
     *out = q;
     return IFX_OK;
 }
+// the ticket of a deferred call on a sharded map: the refusal by mode, then what snap_for_call checks of the ticket
+static int oseg_snap_for_call(ifx* h, const char* who, int ticket, int flags, SegSnap** out)
+{
+    int r = osnap_refuse_mode(h, who);
+    if (r) return r;
+    SegSnap* q = snap_find(h, ticket);
+    if (!q) { h->err = std::string(who) + ": unknown or released ticket"; return IFX_E_INVALID; }
+    if ((flags & 2) && !(q->flags & 2)) { h->err = std::string(who) + ": superpixels need a ticket taken with the frame (ifx_owner_segmentation_snapshot flags bit 1)"; return IFX_E_STATE; }
+    if (q->generation != h->seq_generation) { h->err = std::string(who) + ": the map was uploaded since the ticket was taken (creation numbers renumbered)"; return IFX_E_STATE; }
+    *out = q;
+    return IFX_OK;
+}
+// Deferred segmentation on a spatially sharded map: ifx_owner_segmentation_begin[_device] on a ticket of ifx_owner_segmentation_snapshot.  Every rank re-addresses
+// the pinned image in its own slots (k_seg_translate<1>: no exchange -- the image is replicated, ownership never changes), the call body reads slots, and the call
+// goes on through ifx_owner_segmentation_resume and the same exchange points (never the id image's: the ticket pinned a whole one).  Out of scope here: the ROI,
+// detections and unmolded forms (same record, same body), camera contexts, and moving the ordinary sharded call onto a translated image.
+extern "C" int ifx_owner_segmentation_begin_deferred(ifx_t* h, int ticket, const uint8_t* masks_in, const int32_t* class_ids, int nm, int frame, int flags)
+{
+    const char* who = "ifx_owner_segmentation_begin_deferred";
+    if (!h) return IFX_E_INVALID;
+    if (h->own && (flags & 1)) { h->err = std::string(who) + ": kNN smoothing is not offered on a sharded map's begin / resume (it needs every rank's positions)"; return IFX_E_INVALID; }
+    if (nm < 0 || nm > 256 || (nm > 0 && (!masks_in || !class_ids))) { h->err = std::string(who) + ": n must be 0 .. 256, with masks and class ids"; return IFX_E_INVALID; }
+    SegSnap* snap = nullptr;
+    const int r = oseg_snap_for_call(h, who, ticket, flags, &snap);
+    return r ? r : oseg_begin_host(h, snap, ticket, nullptr, nullptr, masks_in, class_ids, nm, frame, flags);
+}
+extern "C" int ifx_owner_segmentation_begin_deferred_device(ifx_t* h, int ticket, int root, int max_n, const void* d_masks, int mask_format, float threshold, const int32_t* d_class_ids,
+                                                            int n, int frame, int flags, void* stream)
+{
+    return oseg_entry(h, "ifx_owner_segmentation_begin_deferred_device", root, max_n, nullptr, nullptr, src_image(d_masks, mask_format, threshold, d_class_ids, n), threshold, frame, flags,
+                      stream, &ticket);
+}
+
 // what ifx_detector_input (ifx_detector.hip) reads: the frame a ticket kept (ticket >= 0: *ev is the event behind the snapshot, the ticket stays in use) or the
 // resident frame slot (*slot, whose next copy-in the caller holds off as the snapshot above does).  Refuses as the snapshot entries do.
 int ifx_frame_for_reader(ifx* h, const char* who, int ticket, const uint8_t** rgb, hipEvent_t* ev, FrameSlot** slot)

@@ -1130,12 +1130,14 @@ public:
     // SnapshotSegmentation pins, without stalling the frame loop, what a call reads of the frame just processed -- id image, pose and (with the superpixel refinement on)
     // the raw frame -- and returns a ticket; frames go on; ProcessSegmentationDeferred[Device] applies the masks the detector made of THAT frame to the map as it is
     // then (surfels gone since get no votes, surfels created since are in no pixel) and releases the ticket.  detect(): the mask source's answer for a frame, for the
-    // caller to hold until then.  Not on a sharded map.
+    // caller to hold until then.  On a sharded map every rank makes the same calls (ifx_owner_segmentation_snapshot / ifx_owner_process_segmentation_deferred: the
+    // ticket numbers are equal on all ranks, and a call that completes releases its ticket on every rank); its device form is OwnerProcessSegmentationDeferredDevice.
     int SnapshotSegmentation(const std::unique_ptr<ElasticFusionInterface>& map)
     {
         ifx_t* h = require_handle(map ? map->handle() : nullptr, "InstanceFusion::SnapshotSegmentation");
-        const int t = ifx_segmentation_snapshot(h, superpixels_ ? 2 : 0);
-        if (t < 0) throw std::runtime_error(std::string("ifx_segmentation_snapshot: ") + ifx_last_error(h));
+        const bool sharded = map->elasticFusion().sharding().on();
+        const int t = sharded ? ifx_owner_segmentation_snapshot(h, superpixels_ ? 2 : 0) : ifx_segmentation_snapshot(h, superpixels_ ? 2 : 0);
+        if (t < 0) throw std::runtime_error(std::string(sharded ? "ifx_owner_segmentation_snapshot: " : "ifx_segmentation_snapshot: ") + ifx_last_error(h));
         return t;
     }
     bool detect(int frame_num, const ImagePtr rgb, MaskResult* out)
@@ -1145,8 +1147,9 @@ public:
     }
     void ProcessSegmentationDeferred(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const MaskResult& res, int frame_num, bool isflann)
     {
-        seg_call("InstanceFusion::ProcessSegmentationDeferred", "ifx_process_segmentation_deferred", nullptr, map, isflann, [&](ifx_t* h, int flags) {
-            return ifx_process_segmentation_deferred(h, ticket, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
+        seg_call("InstanceFusion::ProcessSegmentationDeferred", "ifx_process_segmentation_deferred", "ifx_owner_process_segmentation_deferred", map, isflann, [&](ifx_t* h, int flags) {
+            return map->elasticFusion().sharding().on() ? ifx_owner_process_segmentation_deferred(h, ticket, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags)
+                                                        : ifx_process_segmentation_deferred(h, ticket, res.masks.data(), res.class_ids.data(), res.n, frame_num, flags);
         });
     }
     void ProcessSegmentationDeferredDevice(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, const void* d_masks, int format, float threshold, const int32_t* d_class_ids,
@@ -1251,6 +1254,16 @@ public:
                                                              frame_num, flags, stream, &kept);
         });
         return kept;
+    }
+    // The deferred call's image-mask device form on a sharded map (ifx_owner_process_segmentation_deferred_device): root, max_n and the tensors as
+    // OwnerProcessSegmentationDevice; no frame -- the superpixels are cut from the ticket's.
+    void OwnerProcessSegmentationDeferredDevice(const std::unique_ptr<ElasticFusionInterface>& map, int ticket, int root, int max_n, const void* d_masks, int format, float threshold,
+                                                const int32_t* d_class_ids, int n, int frame_num, bool isflann, void* stream)
+    {
+        const char* c = "ifx_owner_process_segmentation_deferred_device";
+        seg_call("InstanceFusion::OwnerProcessSegmentationDeferredDevice", c, c, map, isflann, [&](ifx_t* h, int flags) {
+            return ifx_owner_process_segmentation_deferred_device(h, ticket, root, max_n, d_masks, format, threshold, d_class_ids, n, frame_num, flags, stream);
+        });
     }
     // ---- the opposite direction: the detector's input tensor, made on the device from the frame that is already there (ifx_detector_input).  What
     // COCODemo.build_transform and to_image_list make of a frame on the CPU (deps/maskrcnn-benchmark-master/demo/predictor.py:132-160, 198-202: Pillow's bilinear

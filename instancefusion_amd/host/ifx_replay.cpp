@@ -142,7 +142,6 @@ int main(int argc, char** argv)
         if (a.reference_ids) map->elasticFusion().setReferenceIdRule(true);
         if (a.mask_iou) instancefusion->setCompareMapType(2);
 
-        if (a.mask_lag >= 0 && a.shard.on()) { std::fprintf(stderr, "--mask-lag is not available on a sharded map\n"); return 2; }
         int deformsSeen = 0, mergedPairs = 0;   // (--merge-duplicates)
         struct { bool busy = false; int ticket = -1, frame = 0; bool flann = false, has = false; MaskResult res; } pending;   // the detection in flight (--mask-lag)
         auto apply_pending = [&]() {

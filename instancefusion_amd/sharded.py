@@ -335,6 +335,56 @@ class OwnerShardedElasticFusion:
                                  dict(mask_logits=mask_logits, boxes=boxes, scores=scores, labels=labels, in_size=in_size, score_thresh=score_thresh, class_map=class_map,
                                       count=count, threshold=threshold, stream=stream, roi_size=roi_size), frame, superpixels, knn)
 
+    # ---- a detector slower than the frame loop (include/ifx_c_api.h, "Deferred segmentation on a spatially sharded map"): every rank makes the same calls
+    def snapshot(self, superpixels: bool = False):
+        """ifx_owner_segmentation_snapshot: pins the replicated id image, the pose, this rank's slot hints and -- superpixels=True -- the raw frame of the frame just
+        processed, without synchronising; returns the ticket (the same number on every rank).  Option own_lazy_ids: the image is completed first, collectively."""
+        if self.transport != "library":
+            self.ensure_ids()
+        return self.ef._chk(self.ef.L.ifx_owner_segmentation_snapshot(self.ef.handle, 2 if superpixels else 0), "ifx_owner_segmentation_snapshot")
+
+    def _resume_by_hand(self, r):
+        while r == 1:
+            self._exchange(200)
+            r = self.ef._chk(self.ef.L.ifx_owner_segmentation_resume(self.ef.handle), "ifx_owner_segmentation_resume")
+
+    def process_segmentation_deferred(self, ticket, masks, class_ids, frame: int, superpixels: bool = False, knn: bool = False):
+        """process_segmentation of the masks a detector made of the ticket's frame, on the map as it is now; releases the ticket on every rank."""
+        ef = self.ef
+        if self.transport == "library":
+            masks = np.ascontiguousarray(masks, np.uint8); cls = np.ascontiguousarray(class_ids, np.int32)
+            ef._chk(ef.L.ifx_owner_process_segmentation_deferred(ef.handle, int(ticket), masks.ctypes.data_as(C.c_void_p), cls.ctypes.data_as(C.c_void_p), int(masks.shape[0]),
+                                                                 int(frame), (2 if superpixels else 0) | (1 if knn else 0)), "ifx_owner_process_segmentation_deferred")
+            return
+        self._resume_by_hand(_seg_begin_deferred(ef, ticket, masks, class_ids, frame, superpixels))
+        if knn:
+            self.knn_vote_colour()
+
+    def process_segmentation_deferred_device(self, ticket, masks, class_ids, frame: int, superpixels: bool = False, knn: bool = False, threshold=0.5, stream=None,
+                                             root: int = -1, max_n: int = 256):
+        """The deferred call on a detector's image-sized masks on rank `root`'s GPU: tensors, root and max_n as for process_segmentation_device."""
+        ef = self.ef
+        t = dict(masks=masks, class_ids=class_ids, threshold=threshold, stream=stream)
+        flags = 2 if superpixels else 0
+        if self.transport == "library":
+            _, keep, _ = _device_form_call(ef, "ifx_owner_process_segmentation_deferred_", "device", root, max_n, None, None, t, frame, flags | (1 if knn else 0), ticket)
+        else:
+            r, keep, _ = _device_form_call(ef, "ifx_owner_segmentation_begin_deferred_", "device", root, max_n, None, None, t, frame, flags, ticket)
+            self._resume_by_hand(r)
+            if knn:
+                self.knn_vote_colour()
+        del keep
+
+    def release_snapshot(self, ticket):
+        self.ef._chk(self.ef.L.ifx_segmentation_snapshot_release(self.ef.handle, int(ticket)), "ifx_segmentation_snapshot_release")
+
+    def snapshot_stats(self, ticket):
+        """ifx_segmentation_snapshot_stats on a sharded ticket: the tick pinned, the pixels of the WHOLE image with a surfel (equal on every rank), the pixels whose
+        surfel THIS rank owned and lost at the deferred call (-1: none yet), tickets in use"""
+        out = np.zeros(4, np.int32)
+        self.ef._chk(self.ef.L.ifx_segmentation_snapshot_stats(self.ef.handle, int(ticket), out.ctypes.data_as(C.c_void_p)), "ifx_segmentation_snapshot_stats")
+        return dict(tick=int(out[0]), pixels=int(out[1]), lost=int(out[2]), in_use=int(out[3]))
+
 
 def _knn_export(ef, torch, dev):
     pp, pl, n = C.c_void_p(), C.c_void_p(), C.c_int()
@@ -353,6 +403,13 @@ def _seg_begin(ef, rgb, depth, masks, class_ids, frame, superpixels):
     depth = np.ascontiguousarray(depth, np.uint16)
     return ef._chk(ef.L.ifx_owner_segmentation_begin(ef.handle, rgb.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), masks.ctypes.data_as(C.c_void_p),
                                                      cls.ctypes.data_as(C.c_void_p), int(masks.shape[0]), int(frame), 2 if superpixels else 0), "ifx_owner_segmentation_begin")
+
+
+def _seg_begin_deferred(ef, ticket, masks, class_ids, frame, superpixels):
+    masks = np.ascontiguousarray(masks, np.uint8)
+    cls = np.ascontiguousarray(class_ids, np.int32)
+    return ef._chk(ef.L.ifx_owner_segmentation_begin_deferred(ef.handle, int(ticket), masks.ctypes.data_as(C.c_void_p), cls.ctypes.data_as(C.c_void_p), int(masks.shape[0]), int(frame),
+                                                              2 if superpixels else 0), "ifx_owner_segmentation_begin_deferred")
 
 
 def _strip_depth(t):
@@ -419,9 +476,30 @@ def emulate_owner_ranks(efs, d_rgb_ptr: int, d_depth_ptr: int):
             _reduce_by_hand(efs, specs)
 
 
+def emulate_owner_snapshot(efs, superpixels: bool = False):
+    """ifx_owner_segmentation_snapshot on the handles of emulate_owner_ranks (option own_lazy_ids: the whole id image first, its keys reduced by hand); returns one
+    ticket per rank -- equal numbers when the ranks made the same calls."""
+    emulate_owner_ids(efs)
+    return [e._chk(e.L.ifx_owner_segmentation_snapshot(e.handle, 2 if superpixels else 0), "ifx_owner_segmentation_snapshot") for e in efs]
+
+
+def emulate_owner_segmentation_deferred(efs, tickets, masks, class_ids, frame: int, superpixels: bool = False):
+    """The deferred call (host masks) on the handles of emulate_owner_ranks, in lock step, the exchanges done by hand; tickets: emulate_owner_snapshot's."""
+    _lock_step(efs, [_seg_begin_deferred(e, t, masks, class_ids, frame, superpixels) for e, t in zip(efs, tickets)])
+
+
+def emulate_owner_segmentation_deferred_device(efs, tickets, root, masks, class_ids, frame: int, superpixels: bool = False, threshold=0.5, max_n=256, stream=None):
+    """The deferred call on a detector's image-sized masks (root >= 0: the tensors are handed to efs[root] only), on the handles of emulate_owner_ranks."""
+    _emulate_device_form(efs, "device", root, max_n, None, None, dict(masks=masks, class_ids=class_ids, threshold=threshold, stream=stream), frame, superpixels, tickets)
+
+
 def emulate_owner_segmentation(efs, rgb, depth, masks, class_ids, frame: int, superpixels: bool = True):
     """A segmentation call on the handles of emulate_owner_ranks, in lock step, the exchanges done by hand."""
-    rs = [_seg_begin(e, rgb, depth, masks, class_ids, frame, superpixels) for e in efs]
+    _lock_step(efs, [_seg_begin(e, rgb, depth, masks, class_ids, frame, superpixels) for e in efs])
+
+
+def _lock_step(efs, rs):
+    """rs: what the ranks' begin forms returned -- the exchange points of the call, reduced by hand, until it is complete"""
     while rs[0] == 1:
         assert all(r == 1 for r in rs), "the ranks disagree about the call's exchange points"
         _reduce_by_hand(efs, [_exchange_spec(e, 200) for e in efs])
@@ -455,22 +533,27 @@ def _device_form_args(ef, form, root, t):
             stream.cuda_stream or None, kept, par)
 
 
-def _device_form_call(ef, prefix, form, root, max_n, rgb, depth, tensors, frame, flags):
-    """one C entry of a device form (prefix + form) on this rank -> (its return value, what must outlive the call it began, kept)"""
+def _device_form_call(ef, prefix, form, root, max_n, rgb, depth, tensors, frame, flags, ticket=None):
+    """one C entry of a device form (prefix + form) on this rank -> (its return value, what must outlive the call it began, kept).  ticket: a deferred entry's, which
+    leads the arguments and takes no frame (it is the ticket's)"""
     args, stream, kept, keep = _device_form_args(ef, form, root, tensors)
-    rgb = np.ascontiguousarray(rgb, np.uint8); depth = np.ascontiguousarray(depth, np.uint16)
     name = prefix + form
     tail = (C.c_void_p(stream),) + ((C.byref(kept),) if form == "detections" else ())
-    r = ef._chk(getattr(ef.L, name)(ef.handle, int(root), int(max_n), rgb.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p), *args, int(frame), int(flags), *tail),
-                name)
+    if ticket is None:
+        rgb = np.ascontiguousarray(rgb, np.uint8); depth = np.ascontiguousarray(depth, np.uint16)
+        lead = (int(root), int(max_n), rgb.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p))
+    else:
+        lead = (int(ticket), int(root), int(max_n))
+    r = ef._chk(getattr(ef.L, name)(ef.handle, *lead, *args, int(frame), int(flags), *tail), name)
     return r, keep, int(kept.value)
 
 
-def _device_form_begin(ef, form, root, max_n, rgb, depth, tensors, frame, superpixels):
-    return _device_form_call(ef, "ifx_owner_segmentation_begin_", form, root, max_n, rgb, depth, tensors, frame, 2 if superpixels else 0)
+def _device_form_begin(ef, form, root, max_n, rgb, depth, tensors, frame, superpixels, ticket=None):
+    prefix = "ifx_owner_segmentation_begin_" if ticket is None else "ifx_owner_segmentation_begin_deferred_"
+    return _device_form_call(ef, prefix, form, root, max_n, rgb, depth, tensors, frame, 2 if superpixels else 0, ticket)
 
 
-def _emulate_device_form(efs, form, root, max_n, rgb, depth, tensors, frame, superpixels):
+def _emulate_device_form(efs, form, root, max_n, rgb, depth, tensors, frame, superpixels, tickets=None):
     """A device form on the handles of emulate_owner_ranks, in lock step, the exchanges done by hand.  With root >= 0 the tensors go to efs[root] only, and that rank
     begins first: a refusal of its arguments then leaves no other rank waiting at the record's exchange point."""
     first = root if 0 <= root < len(efs) else 0
@@ -483,7 +566,8 @@ def _emulate_device_form(efs, form, root, max_n, rgb, depth, tensors, frame, sup
 
     try:
         for k in order:
-            rs[k], kp, kk = _device_form_begin(efs[k], form, root, max_n[k] if isinstance(max_n, (list, tuple)) else max_n, rgb, depth, tensors, frame, superpixels)
+            rs[k], kp, kk = _device_form_begin(efs[k], form, root, max_n[k] if isinstance(max_n, (list, tuple)) else max_n, rgb, depth, tensors, frame, superpixels,
+                                               None if tickets is None else tickets[k])
             keep.append(kp); kept = max(kept, kk)
     except Exception:
         abort()
